@@ -24,7 +24,7 @@ once (n=88 789) on 8, dt halved per refinement (and once more on the level-3
 meshes: the explicit convection needs it).  `value` is the time steps/s of
 that one simulation (no normalisation); `config.weak_scaling` carries n, the
 rows per rank and dof-steps/s, `config.collectives` the RCCL call counts of
-the timed window from `dns_comm_stats2`.  Secondary figures on the same ranks:
+the timed window from `dns_comm_stats2`.  Secondary figures (`--full`):
 `config.strong_scaling` (the N=1 workload itself partitioned over the N ranks,
 reported as it is -- at n ~ 1e4 a step is ~45 us of work on one GPU and every
 collective costs 10-20 us, so this is SLOWER than one GPU) and
@@ -38,7 +38,13 @@ rendezvous) under a time limit, so that a collective that never completes
 leaves an error in the JSON line instead of a hung benchmark; if the headline
 run fails the line says so and falls back to the ensemble figure.
 
-The JSON line also carries
+A plain run sets up, warms up, times the `--steps` steps and prints the line
+(`ms_per_step` is the wall time of one timed step); `--dump-outputs DIR`
+writes the state the last timed step leaves (`v.npy`, `p.npy`, float64), so
+that two builds can be compared output for output.  The inputs are the same
+from run to run: the mesh is stored, the start state is the Stokes solution.
+
+With `--full` the JSON line also carries (and a run takes minutes)
   roofline     : CSR SpMV `y = K x` (the kernel family that dominates the
                  step), HIP-event timed inside this script, at the benchmark
                  size AND on a uniformly refined mesh that leaves the caches
@@ -1399,9 +1405,11 @@ def multi_gpu_main(args, world, rank, local_rank):
     # GPU -- a single-GPU run of this script per rank (own timed window of
     # exactly --steps steps each; the slowest rank counts)
     ensemble = None
-    if not args.no_ensemble and headline_ok and remaining() < 75.:
+    # (without --full the ensemble only stands in for a failed headline)
+    with_ensemble = not args.no_ensemble and (args.full or not headline_ok)
+    if with_ensemble and headline_ok and remaining() < 75.:
         ensemble = dict(error='skipped: --time-budget spent', steps_per_s=None)
-    elif not args.no_ensemble:
+    elif with_ensemble:
         env = {k: v for k, v in child_env().items()
                if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR',
                             'MASTER_PORT', 'GROUP_RANK', 'LOCAL_WORLD_SIZE',
@@ -1614,8 +1622,27 @@ def main():
                     help='N > 1: wall-clock budget [s] of the whole line; the '
                     'self-test and the headline leg always run, a secondary '
                     'leg only while its expected cost still fits')
+    ap.add_argument('--full', action='store_true',
+                    help='the secondary figures as well (the --no-* options '
+                    'above pick among them): N = 1 the HBM roofline SpMV and '
+                    'streaming probes, the early-transient and 400-step '
+                    'windows, the run through the partitioned code path, the '
+                    'Newton/Picard sweeps, the refined meshes, the CPU '
+                    'baseline and its parity; N > 1 the bandwidth, strong-'
+                    'scaling and ensemble legs.  Without it the line carries '
+                    'the headline window alone')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='(N = 1) write the state the last timed step leaves, '
+                    'v and p (float64), to DIR/v.npy and DIR/p.npy')
     ap.set_defaults(force_dist=True, window_400=True)
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error('--dump-outputs writes the state of the N = 1 line only')
+    if not args.full:
+        args.no_cpu = args.no_refined = args.no_picard = True
+        args.no_bandwidth = args.no_strong = True
+        args.force_dist = args.window_400 = False
+        args.roofline_refine = 0
 
     internal = args.partitioned_only or args.selftest_only
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1 and not internal:
@@ -1743,9 +1770,15 @@ def main():
 
     # headline: the complete time step, convection evaluated on the device
     wall, dev_s, iters, last, v_gpu, p_gpu = timed_run(True)
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in (('v', v_gpu), ('p', p_gpu)):
+            np.save(os.path.join(args.dump_outputs, name + '.npy'),
+                    np.asarray(arr, dtype=np.float64))
+    wall_et = None
     if args.profile_step:
         wall_et, iters_et = wall, iters
-    else:
+    elif args.full:
         # secondary: the same window right behind the impulsive start (Stokes
         # state, no spin-up): the solves need about two Krylov steps there
         wall_et, _, iters_et, _, _, _ = timed_run(True, spinup=0)
@@ -1780,12 +1813,13 @@ def main():
             system.precond_info(), int(R1.nnz), int(th.mesh.ncells),
             iters/float(args.steps), 1e3*wall/args.steps,
             peak_GBs=HBM_PEAK_GBS)
-        roof = None if args.profile_step else roofline_spmv(
-            saddle, saddle_csr(F, J), 200,
-            'K at the benchmark size (cache resident)', variants=('vector',))
+        roof = None if (args.profile_step or not args.full) else \
+            roofline_spmv(saddle, saddle_csr(F, J), 200,
+                          'K at the benchmark size (cache resident)',
+                          variants=('vector',))
         roof_hbm, traffic, attain = hbm_roof
         main_roof = roof_hbm if roof_hbm is not None else roof
-        if main_roof is None:          # --profile-step: the step's own figure
+        if main_roof is None:     # --profile-step, no --full: the step's figure
             main_roof = dict(achieved=step_roof['achieved'],
                              kernel='(whole CNAB step, see roofline.step)')
         roofline = dict(bound='hbm', achieved=main_roof['achieved'],
@@ -1871,7 +1905,7 @@ def main():
                                     args.spinup, args.scheme.upper())),
                         window_400=window_400,
                         spinup_steps=args.spinup,
-                        early_transient=dict(
+                        early_transient=None if wall_et is None else dict(
                             steps_per_s=world*args.steps/wall_et,
                             krylov_iters_per_step=iters_et/float(args.steps),
                             what='the same window with no spin-up (steps '

@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd $R
 export DNS_BENCH_REHEARSE_ONE_GPU=1 GLOO_SOCKET_IFNAME=lo
 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 \
-  bench.py --gpus 2 --steps 20 --warmup 5 --partitioned-timeout 400 \
+  bench.py --full --gpus 2 --steps 20 --warmup 5 --partitioned-timeout 400 \
   > $OUT/rehearsal_two_ranks_one_gpu_gloo.json 2> $OUT/rehearsal.err || echo "rehearsal failed"
 export DNS_TEST_CORRUPT_HALO=1
 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29631 \

@@ -115,7 +115,7 @@ def test_multi_rank_launch_plumbing_on_cpu(tmp_path):
            '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'bench.py'),
            '--gpus', '2', '--steps', '3', '--warmup', '1', '--dry-run',
-           '--partitioned-timeout', '120']
+           '--partitioned-timeout', '120', '--full']
     env = dict(os.environ, GLOO_SOCKET_IFNAME='lo')
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, timeout=300)
@@ -172,6 +172,10 @@ def test_gpus_n_without_a_launcher_starts_its_own_ranks():
         name + suffix for name, _ in bench.SELFTEST_LEGS[::2]
         for suffix in ('_eager', '_graph'))
     assert 'FALLBACK' not in rec['config']['parallelism']
+    # without --full the line carries the headline leg alone
+    cfg = rec['config']
+    assert cfg['strong_scaling'] is None and cfg['ensemble'] is None
+    assert cfg['weak_scaling_bandwidth'] is None
 
 
 def test_a_launch_for_another_n_is_refused():
@@ -185,6 +189,20 @@ def test_a_launch_for_another_n_is_refused():
     assert out.returncode != 0
     assert not _json_lines(out.stdout)
     assert 'refusing' in out.stderr.decode()
+
+
+def test_dump_outputs_is_refused_on_more_than_one_gpu():
+    """the dumped state is the N = 1 line's: an N > 1 run prints no line"""
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'),
+                          '--gpus', '2', '--dry-run', '--dump-outputs',
+                          os.path.join(ROOT, 'never_written')],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                         timeout=120)
+    assert out.returncode != 0
+    assert not _json_lines(out.stdout)
+    assert '--dump-outputs' in out.stderr.decode()
+    assert not os.path.exists(os.path.join(ROOT, 'never_written'))
 
 
 def test_self_launch_refuses_more_ranks_than_gpus(monkeypatch):
