@@ -65,7 +65,8 @@ inline int guarded(Body body) noexcept {
 // its host range [ptr, ptr + bytes) on stderr before it is enqueued, so that
 // the address of a "Memory access fault by GPU ... on address" report can be
 // tied to a buffer and an offset (round 4: a fault at a host heap address
-// whose record held no ranges)
+// whose record held no ranges).  Copies of the library's own page-locked
+// buffers carry the tags "pinned_h2d" / "pinned_d2h".
 inline bool debug_uploads() {
     static const bool on = [] {
         const char *e = getenv("DNS_DEBUG_UPLOADS");
@@ -81,50 +82,75 @@ inline void log_host_copy(const char *what, const void *host, const void *dev,
     fflush(stderr);
 }
 
-// ---------------------------------------------------------------------------
-// Host <-> device copies never hand PAGEABLE memory to the DMA engine.
-// Twice now (rounds 4 and 5) a run of the GPU suite died with "Memory access
-// fault by GPU ... on address <page-aligned HOST heap address>" inside a call
-// whose only touch of host memory was a hipMemcpyAsync out of pageable memory
-// (a caller's NumPy block, a std::vector of the set-up) -- intermittently, at
-// different places, every kernel argument accounted for.  For pageable
-// memory the runtime pins the pages in place and lets a blit kernel read
-// them; what exactly goes wrong there is not ours to find (DNS_DEBUG_UPLOADS
-// prints the ranges for whoever looks).  So every copy goes through a
-// page-locked bounce buffer of this thread: the CPU copies between the
-// caller's memory and the bounce buffer, the DMA engine only ever sees
-// hipHostMalloc memory.  4 MiB chunks, each synchronised (a copy IS complete
-// when the call returns, as DevBuf::upload promises anyway): PCIe rate minus
-// a few per cent.
-// ---------------------------------------------------------------------------
-struct BounceBuffer {
-    void *p = nullptr;
-    size_t bytes = 0;
-    ~BounceBuffer() {
-        if (p) (void)hipHostFree(p);
-    }
-    int reserve(size_t want) {
-        if (want <= bytes) return DNS_OK;
+// page-locked host memory (hipHostMalloc) owned by the library
+template <typename T>
+struct PinnedBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { release(); }
+    void release() {
         if (p) (void)hipHostFree(p);
         p = nullptr;
-        bytes = 0;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return fail(DNS_ERR_HIP, "hipHostMalloc(%zu) failed: %s", want,
-                        hipGetErrorString(e));
-        }
-        bytes = want;
+        n = 0;
+    }
+    int reserve(size_t count) {
+        if (count <= n) return DNS_OK;
+        release();
+        DNS_HIP(hipHostMalloc(reinterpret_cast<void **>(&p),
+                              count * sizeof(T), hipHostMallocDefault));
+        n = count;
         return DNS_OK;
     }
 };
-inline thread_local BounceBuffer g_bounce;
+
+// ---------------------------------------------------------------------------
+// THE copy layer: no other code moves bytes between host memory and the
+// device (tests/test_capi_cpu.py::test_every_host_copy_goes_through_common_hpp).
+//
+// Staged copies, for ANY host memory (a caller's array, a std::vector, a
+// stack scalar): DevBuf::upload / download, upload_to, download_from and the
+// raw staged_h2d / staged_d2h under them.  The DMA engine never sees pageable
+// memory.  Twice now (rounds 4 and 5) a run of the GPU suite died with
+// "Memory access fault by GPU ... on address <page-aligned HOST heap
+// address>" inside a call whose only touch of host memory was a
+// hipMemcpyAsync out of pageable memory -- intermittently, at different
+// places, every kernel argument accounted for.  For pageable memory the
+// runtime pins the pages in place and lets a blit kernel read them; what
+// exactly goes wrong there is not established (DNS_DEBUG_UPLOADS prints the
+// ranges for whoever looks).  So the CPU copies between the caller's memory
+// and a page-locked bounce buffer of this thread, and the DMA engine only
+// sees the bounce buffer: 4 MiB chunks, each synchronised, PCIe rate minus a
+// few per cent.  A staged copy is COMPLETE when it returns, so the lifetime
+// of the host memory after the call is nobody's concern.  It synchronises
+// the stream, which an open stream capture cannot take: inside one it fails
+// with its name instead of invalidating the capture.
+//
+// Pinned copies, for the library's PinnedBuf memory (and the trajectory
+// export stages) only: h2d_pinned / d2h_pinned only ENQUEUE.  The caller
+// synchronises before it reads or refills the host side.
+// ---------------------------------------------------------------------------
+inline thread_local PinnedBuf<char> g_bounce;
 constexpr size_t kBounceChunk = (size_t)4 << 20;
 
-inline int staged_h2d(void *dev, const void *host, size_t bytes,
-                      hipStream_t s) {
+inline int staged_prologue(const char *what, const void *host, const void *dev,
+                           size_t bytes, hipStream_t s) {
+    log_host_copy(what, host, dev, bytes);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess ||
+        cs != hipStreamCaptureStatusNone)
+        return fail(DNS_ERR_HIP,
+                    "%s: a staged host copy of %zu bytes inside an open "
+                    "stream capture", what, bytes);
+    return g_bounce.reserve(std::min(bytes, kBounceChunk));
+}
+
+inline int staged_h2d(const char *what, void *dev, const void *host,
+                      size_t bytes, hipStream_t s) {
     if (bytes == 0) return DNS_OK;
-    DNS_TRY(g_bounce.reserve(std::min(bytes, kBounceChunk)));
+    DNS_TRY(staged_prologue(what, host, dev, bytes, s));
     const char *src = static_cast<const char *>(host);
     char *dst = static_cast<char *>(dev);
     for (size_t off = 0; off < bytes; off += kBounceChunk) {
@@ -137,10 +163,10 @@ inline int staged_h2d(void *dev, const void *host, size_t bytes,
     return DNS_OK;
 }
 
-inline int staged_d2h(void *host, const void *dev, size_t bytes,
-                      hipStream_t s) {
+inline int staged_d2h(const char *what, void *host, const void *dev,
+                      size_t bytes, hipStream_t s) {
     if (bytes == 0) return DNS_OK;
-    DNS_TRY(g_bounce.reserve(std::min(bytes, kBounceChunk)));
+    DNS_TRY(staged_prologue(what, host, dev, bytes, s));
     char *dst = static_cast<char *>(host);
     const char *src = static_cast<const char *>(dev);
     for (size_t off = 0; off < bytes; off += kBounceChunk) {
@@ -150,6 +176,32 @@ inline int staged_d2h(void *host, const void *dev, size_t bytes,
         DNS_HIP(hipStreamSynchronize(s));
         memcpy(dst + off, g_bounce.p, len);
     }
+    return DNS_OK;
+}
+
+// staged, into / out of the middle of a device buffer
+template <typename T>
+inline int upload_to(T *dev, const T *host, size_t count, hipStream_t s) {
+    return staged_h2d("upload_to", dev, host, count * sizeof(T), s);
+}
+template <typename T>
+inline int download_from(T *host, const T *dev, size_t count, hipStream_t s) {
+    return staged_d2h("download_from", host, dev, count * sizeof(T), s);
+}
+
+// pinned: only enqueued on `s`
+template <typename T>
+inline int h2d_pinned(T *dev, const T *pinned, size_t count, hipStream_t s) {
+    log_host_copy("pinned_h2d", pinned, dev, count * sizeof(T));
+    DNS_HIP(hipMemcpyAsync(dev, pinned, count * sizeof(T),
+                           hipMemcpyHostToDevice, s));
+    return DNS_OK;
+}
+template <typename T>
+inline int d2h_pinned(T *pinned, const T *dev, size_t count, hipStream_t s) {
+    log_host_copy("pinned_d2h", pinned, dev, count * sizeof(T));
+    DNS_HIP(hipMemcpyAsync(pinned, dev, count * sizeof(T),
+                           hipMemcpyDeviceToHost, s));
     return DNS_OK;
 }
 
@@ -174,80 +226,19 @@ struct DevBuf {
         n = count;
         return DNS_OK;
     }
-    // Host -> device, SAFE BY CONSTRUCTION: when the call returns the copy
-    // has left `host`, whose lifetime is therefore nobody's concern (a local
-    // std::vector, a caller's borrowed array).  An asynchronous copy out of
-    // pageable memory that is freed -- and possibly unmapped -- before the
-    // DMA engine gets to it is a GPU memory fault (round 3: intermittent
-    // aborts of the test session).  Ordered on `s` like any other work.
+    // staged: complete on return, ordered on `s` like any other work
     int upload(const T *host, size_t count, hipStream_t s) {
-        return upload_async(host, count, s);
-    }
-    // ... and the variant that only enqueues: the CALLER guarantees that
-    // `host` stays valid and unmodified until it has synchronised `s` on
-    // EVERY path out of its scope (error returns included -- `SyncOnExit`)
-    int upload_async(const T *host, size_t count, hipStream_t s) {
         if (count > n) return fail(DNS_ERR_BAD_ARGUMENT, "upload overflow");
-        if (count == 0) return DNS_OK;
-        log_host_copy("upload", host, p, count * sizeof(T));
-        // (through the page-locked bounce buffer: complete on return)
-        return staged_h2d(p, host, count * sizeof(T), s);
+        return staged_h2d("upload", p, host, count * sizeof(T), s);
     }
     int download(T *host, size_t count, hipStream_t s) const {
         if (count > n) return fail(DNS_ERR_BAD_ARGUMENT, "download overflow");
-        if (count == 0) return DNS_OK;
-        log_host_copy("download", host, p, count * sizeof(T));
-        // (through the page-locked bounce buffer: complete on return)
-        return staged_d2h(host, p, count * sizeof(T), s);
+        return staged_d2h("download", host, p, count * sizeof(T), s);
     }
     int zero(hipStream_t s) {
         DNS_HIP(hipMemsetAsync(p, 0, n * sizeof(T), s));
         return DNS_OK;
     }
-};
-
-// host -> device into the middle of a buffer, with the guarantee of
-// DevBuf::upload: the copy has left `host` when the call returns
-template <typename T>
-inline int upload_to(T *dev, const T *host, size_t count, hipStream_t s) {
-    if (count == 0) return DNS_OK;
-    log_host_copy("upload_to", host, dev, count * sizeof(T));
-    return staged_h2d(dev, host, count * sizeof(T), s);
-}
-
-// page-locked host staging (hipHostMalloc): copies between it and the device
-// never pin or unpin caller memory
-template <typename T>
-struct PinnedBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf &) = delete;
-    PinnedBuf &operator=(const PinnedBuf &) = delete;
-    ~PinnedBuf() { release(); }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    int reserve(size_t count) {
-        if (count <= n) return DNS_OK;
-        release();
-        DNS_HIP(hipHostMalloc(reinterpret_cast<void **>(&p),
-                              count * sizeof(T), hipHostMallocDefault));
-        n = count;
-        return DNS_OK;
-    }
-};
-
-// synchronises the stream when the scope is left, whichever way: what makes a
-// group of `upload_async` calls from buffers of that scope safe
-struct SyncOnExit {
-    hipStream_t s;
-    explicit SyncOnExit(hipStream_t s_) : s(s_) {}
-    SyncOnExit(const SyncOnExit &) = delete;
-    SyncOnExit &operator=(const SyncOnExit &) = delete;
-    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
 };
 
 // CSR matrix resident in HBM

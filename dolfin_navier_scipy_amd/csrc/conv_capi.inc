@@ -28,7 +28,9 @@ static int upload_conv_tables() {
             t.dphi[q][3 + k][j] = 4 * qp[q][i];
         }
     }
-    DNS_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_conv), &t, sizeof(t)));
+    void *dst = nullptr;
+    DNS_HIP(hipGetSymbolAddress(&dst, HIP_SYMBOL(c_conv)));
+    DNS_TRY(upload_to(static_cast<ConvTables *>(dst), &t, 1, nullptr));
     done = true;
     return DNS_OK;
 }
@@ -160,8 +162,8 @@ static int dns_conv_set_dbcvals_impl(dns_conv *cv, const double *dbcvals) {
     if (!cv || !dbcvals) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(cv->device));
     if (cv->ndbc > 0)
-        DNS_TRY(dns::staged_h2d(cv->dbcvals.p, dbcvals,
-                                (size_t)cv->ndbc * sizeof(double), nullptr));
+        DNS_TRY(dns::upload_to(cv->dbcvals.p, dbcvals, (size_t)cv->ndbc,
+                               nullptr));
     cv->dbc_rows = 0;                  // one constant value set from here on
     cv->dbc_gen++;
     cv->dbc_ctr = nullptr;
@@ -180,9 +182,8 @@ static int dns_conv_set_dbc_table_impl(dns_conv *cv, int32_t nrows, const double
     const size_t nd = (size_t)std::max(1, cv->ndbc);
     if (cv->dbc_tab.n < nd * nrows) DNS_TRY(cv->dbc_tab.alloc(nd * nrows));
     if (cv->ndbc > 0)
-        DNS_TRY(dns::staged_h2d(cv->dbc_tab.p, vals,
-                                (size_t)cv->ndbc * nrows * sizeof(double),
-                                nullptr));
+        DNS_TRY(dns::upload_to(cv->dbc_tab.p, vals,
+                               (size_t)cv->ndbc * nrows, nullptr));
     cv->dbc_rows = nrows;
     cv->dbc_row = 0;
     cv->dbc_gen++;

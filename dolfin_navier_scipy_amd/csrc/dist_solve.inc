@@ -701,27 +701,23 @@ int dns_saddle::all_ranks_any(bool mine, bool *any) {
     *any = mine;
     if (!dist()) return DNS_OK;
     double v = mine ? 1.0 : 0.0;
-    DNS_HIP(hipMemcpyAsync(scal.p, &v, sizeof(double), hipMemcpyHostToDevice,
-                           stream));
-    DNS_HIP(hipStreamSynchronize(stream));       // `v` is a local
-    DNS_TRY(comm->allreduce(scal.p, 1, stream));
-    DNS_HIP(hipMemcpyAsync(&v, scal.p, sizeof(double), hipMemcpyDeviceToHost,
-                           stream));
-    DNS_HIP(hipStreamSynchronize(stream));
+    DNS_TRY(allreduce_host(&v, 1));
     *any = v > 0.5;
     return DNS_OK;
+}
+
+int dns_saddle::allreduce_host(double *v, int count) {
+    if (scal.n < 1) DNS_TRY(scal.alloc(16));
+    DNS_TRY(scal.upload(v, (size_t)count, stream));   // (fails past scal.n)
+    DNS_TRY(comm->allreduce(scal.p, count, stream));
+    return scal.download(v, (size_t)count, stream);
 }
 
 int dns_saddle::agree(int rc_local, const char *where) {
     if (!comm || comm->nranks < 2) return rc_local;
     const std::string kept = dns::g_last_error;     // (the local message)
     double v = rc_local != DNS_OK ? 1.0 : 0.0;
-    if (scal.n < 1) DNS_TRY(scal.alloc(16));
-    DNS_TRY(dns::upload_to(scal.p, &v, 1, stream));
-    DNS_TRY(comm->allreduce(scal.p, 1, stream));
-    DNS_HIP(hipMemcpyAsync(&v, scal.p, sizeof(double), hipMemcpyDeviceToHost,
-                           stream));
-    DNS_HIP(hipStreamSynchronize(stream));
+    DNS_TRY(allreduce_host(&v, 1));
     if (rc_local != DNS_OK) {
         dns::g_last_error = kept;
         return rc_local;

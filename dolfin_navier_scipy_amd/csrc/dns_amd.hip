@@ -53,8 +53,6 @@ static void free_dist_data(dns_dist_data *d);
 dns_saddle::~dns_saddle() {
     drop_graphs();
     free_dist_data(dd);
-    if (hdr_host) (void)hipHostFree(hdr_host);
-    if (scal_host) (void)hipHostFree(scal_host);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (stream) (void)hipStreamDestroy(stream);
@@ -124,10 +122,8 @@ int dns_saddle::init_device(int dev) {
         mg_cheb_alpha = std::max(1.5, atof(sn));
     DNS_HIP(hipEventCreate(&ev0));
     DNS_HIP(hipEventCreate(&ev1));
-    DNS_HIP(hipHostMalloc(reinterpret_cast<void **>(&hdr_host),
-                          sizeof(CtlHeaderAcc)));
-    DNS_HIP(hipHostMalloc(reinterpret_cast<void **>(&scal_host),
-                          16 * sizeof(double)));
+    DNS_TRY(hdr_host.reserve(1));
+    DNS_TRY(scal_host.reserve(16));
     return DNS_OK;
 }
 
@@ -353,10 +349,9 @@ int dns_saddle::dot_host(int64_t len, const double *x, const double *y,
     hipLaunchKernelGGL(k_sum_partials, 1, kBlock, 0, stream, partC.p, nred,
                        scal.p);
     DNS_HIP(hipGetLastError());
-    DNS_HIP(hipMemcpyAsync(scal_host, scal.p, sizeof(double),
-                           hipMemcpyDeviceToHost, stream));
+    DNS_TRY(d2h_pinned(scal_host.p, scal.p, 1, stream));
     DNS_HIP(hipStreamSynchronize(stream));
-    *out = scal_host[0];
+    *out = scal_host.p[0];
     return DNS_OK;
 }
 
@@ -684,9 +679,7 @@ int dns_saddle::invert_dense(double *a, int nn) {
     }
     DNS_HIP(hipGetLastError());
     int hflag = 0;
-    DNS_HIP(hipMemcpyAsync(&hflag, flag.p, sizeof(int), hipMemcpyDeviceToHost,
-                           stream));
-    DNS_HIP(hipStreamSynchronize(stream));
+    DNS_TRY(flag.download(&hflag, 1, stream));
     if (hflag)
         return fail(DNS_BREAKDOWN, "zero pivot in the dense Schur inverse");
     return DNS_OK;
@@ -1442,8 +1435,9 @@ int dns_saddle::ensure_workspace(int m) {
 }
 
 int dns_saddle::read_header() {
-    DNS_HIP(hipMemcpyAsync(hdr_host, ctl.p, sizeof(CtlHeaderAcc),
-                           hipMemcpyDeviceToHost, stream));
+    DNS_TRY(d2h_pinned(hdr_host.p,
+                       reinterpret_cast<const CtlHeaderAcc *>(ctl.p), 1,
+                       stream));
     DNS_HIP(hipStreamSynchronize(stream));
     return DNS_OK;
 }
@@ -1460,10 +1454,9 @@ int dns_saddle::true_residual(const double *b, const double *x, double *out) {
                        scal.p);
     DNS_HIP(hipGetLastError());
     if (dist_sliced && comm) DNS_TRY(comm->allreduce(scal.p, 1, stream));
-    DNS_HIP(hipMemcpyAsync(scal_host, scal.p, sizeof(double),
-                           hipMemcpyDeviceToHost, stream));
+    DNS_TRY(d2h_pinned(scal_host.p, scal.p, 1, stream));
     DNS_HIP(hipStreamSynchronize(stream));
-    *out = std::sqrt(scal_host[0]);
+    *out = std::sqrt(scal_host.p[0]);
     spmv_count++;
     return DNS_OK;
 }
@@ -1910,6 +1903,7 @@ int dns_saddle::gmres(const double *b, double *x, const dns_solve_opts *o,
         tek ^= (uint64_t)(uintptr_t)tail_extrap.out + 0x9e3779b97f4a7c15ULL +
                (tek << 6) + (tek >> 2);
     }
+    const CtlHeader &hdr = hdr_host.p->h;        // (filled by read_header)
     while (true) {
         std::vector<uint64_t> key = {
             1u, tek, (uint64_t)(uintptr_t)b, (uint64_t)(uintptr_t)x, (uint64_t)c,
@@ -1938,7 +1932,7 @@ int dns_saddle::gmres(const double *b, double *x, const dns_solve_opts *o,
             return DNS_OK;
         }
         DNS_TRY(read_header());
-        if (hdr_host->status == kGsFallback) {
+        if (hdr.status == kGsFallback) {
             // the fused Gram-Schmidt gave up on its norm: go on from the
             // current iterate with the explicit kernel (row-partitioned: with
             // a new fused cycle -- it restarts from a fresh, orthonormal basis)
@@ -1949,28 +1943,27 @@ int dns_saddle::gmres(const double *b, double *x, const dns_solve_opts *o,
             restarts++;
             continue;
         }
-        if (hdr_host->status != DNS_OK || hdr_host->conv ||
-            hdr_host->total_it >= oo.maxiter || std::isnan(hdr_host->resnorm))
+        if (hdr.status != DNS_OK || hdr.conv ||
+            hdr.total_it >= oo.maxiter || std::isnan(hdr.resnorm))
             break;
         restarts++;
         c = std::min(m, std::max(2 * c, 8));
     }
     if (o->reorth == 2 && oo.reorth == 2) gs_fallbacks = 0;   // clean fused solve
-    const int total = hdr_host->total_it;
+    const int total = hdr.total_it;
     last_iters = total;
-    history.assign((size_t)std::max(1, hdr_host->hist_len), hdr_host->resnorm);
-    if (hdr_host->hist_len > 0 && want_history) {
-        DNS_TRY(dns::staged_d2h(history.data(), histdev.p,
-                                history.size() * sizeof(double), stream));
+    history.assign((size_t)std::max(1, hdr.hist_len), hdr.resnorm);
+    if (hdr.hist_len > 0 && want_history) {
+        DNS_TRY(download_from(history.data(), histdev.p, history.size(),
+                              stream));
     }
     st->iters = total;
     st->restarts = restarts;
-    st->bnorm = hdr_host->bnorm;
-    st->est_relres = hdr_host->bnorm > 0 ? hdr_host->resnorm / hdr_host->bnorm
-                                         : hdr_host->resnorm;
-    if (hdr_host->status != DNS_OK)
-        st->status = hdr_host->status;
-    else if (hdr_host->conv)
+    st->bnorm = hdr.bnorm;
+    st->est_relres = hdr.bnorm > 0 ? hdr.resnorm / hdr.bnorm : hdr.resnorm;
+    if (hdr.status != DNS_OK)
+        st->status = hdr.status;
+    else if (hdr.conv)
         st->status = DNS_OK;
     else
         st->status = DNS_NOT_CONVERGED;
@@ -1985,6 +1978,7 @@ int dns_saddle::bicgstab(const double *b, double *x, const dns_solve_opts *o,
                          dns_solve_stats *st) {
     const int check = std::max(1, o->check_every);
     const size_t hcap = (size_t)o->maxiter + 2;
+    const CtlHeader &hdr = hdr_host.p->h;        // (filled by read_header)
     if (bi_rhat.n < ld) {
         DNS_TRY(bi_rhat.alloc(ld));
         DNS_TRY(bi_p.alloc(ld));
@@ -2045,21 +2039,18 @@ int dns_saddle::bicgstab(const double *b, double *x, const dns_solve_opts *o,
         }
         DNS_HIP(hipGetLastError());
         DNS_TRY(read_header());
-        done = hdr_host->done != 0 || it > o->maxiter;
+        done = hdr.done != 0 || it > o->maxiter;
     }
-    const int total = hdr_host->total_it;
+    const int total = hdr.total_it;
     history.assign((size_t)total + 1, 0.0);
-    DNS_TRY(dns::staged_d2h(history.data(), histdev.p,
-                            history.size() * sizeof(double), stream));
+    DNS_TRY(download_from(history.data(), histdev.p, history.size(), stream));
     st->iters = total;
     st->restarts = 0;
-    st->bnorm = hdr_host->bnorm;
-    st->est_relres = hdr_host->bnorm > 0 ? hdr_host->resnorm / hdr_host->bnorm
-                                         : hdr_host->resnorm;
-    const bool conv = !(hdr_host->resnorm > hdr_host->tol);
+    st->bnorm = hdr.bnorm;
+    st->est_relres = hdr.bnorm > 0 ? hdr.resnorm / hdr.bnorm : hdr.resnorm;
+    const bool conv = !(hdr.resnorm > hdr.tol);
     st->status = conv ? DNS_OK
-                      : (hdr_host->status != DNS_OK ? hdr_host->status
-                                                    : DNS_NOT_CONVERGED);
+                      : (hdr.status != DNS_OK ? hdr.status : DNS_NOT_CONVERGED);
     return DNS_OK;
 }
 
@@ -2389,11 +2380,9 @@ static int dns_saddle_solve_multi_impl(dns_saddle *h, int32_t ncols,
                 memcpy(sx + c * ld, x0 + (x0_cols > 1 ? c * n : 0),
                        n * sizeof(double));
         }
-        SyncOnExit arrived(h->stream);
-        DNS_HIP(hipMemcpyAsync(h->mrhs.p, sr, k * ld * sizeof(double),
-                               hipMemcpyHostToDevice, h->stream));
-        DNS_HIP(hipMemcpyAsync(h->msol.p, sx, k * ld * sizeof(double),
-                               hipMemcpyHostToDevice, h->stream));
+        DNS_TRY(h2d_pinned(h->mrhs.p, sr, k * ld, h->stream));
+        DNS_TRY(h2d_pinned(h->msol.p, sx, k * ld, h->stream));
+        DNS_HIP(hipStreamSynchronize(h->stream));
     }
     h->col_history.assign(k, std::vector<double>());
     int worst = DNS_OK;
@@ -2405,8 +2394,7 @@ static int dns_saddle_solve_multi_impl(dns_saddle *h, int32_t ncols,
         h->col_history[c] = h->history;
         if (st->status != DNS_OK && worst == DNS_OK) worst = st->status;
     }
-    DNS_HIP(hipMemcpyAsync(h->mstage.p, h->msol.p, k * ld * sizeof(double),
-                           hipMemcpyDeviceToHost, h->stream));
+    DNS_TRY(d2h_pinned(h->mstage.p, h->msol.p, k * ld, h->stream));
     DNS_HIP(hipStreamSynchronize(h->stream));
     for (size_t c = 0; c < k; ++c)
         memcpy(out_vp + c * n, h->mstage.p + c * ld, n * sizeof(double));
@@ -2768,8 +2756,7 @@ static int dns_device_read_impl(int device, const void *dev, void *host, size_t 
     if (!dev || !host) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(device));
     DNS_HIP(hipDeviceSynchronize());
-    dns::log_host_copy("device_read", host, dev, bytes);
-    DNS_TRY(dns::staged_d2h(host, dev, bytes, nullptr));
+    DNS_TRY(dns::staged_d2h("device_read", host, dev, bytes, nullptr));
     return DNS_OK;
 }
 
@@ -2781,8 +2768,7 @@ static int dns_device_write_impl(int device, void *dev, const void *host, size_t
     if (!dev || !host) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(device));
     DNS_HIP(hipDeviceSynchronize());
-    dns::log_host_copy("device_write", host, dev, bytes);
-    DNS_TRY(dns::staged_h2d(dev, host, bytes, nullptr));
+    DNS_TRY(dns::staged_h2d("device_write", dev, host, bytes, nullptr));
     return DNS_OK;
 }
 
@@ -2907,9 +2893,7 @@ static int dns_saddle_probe_impl(dns_saddle *h, int32_t which, int32_t chain,
         CtlHeader hd;
         memset(&hd, 0, sizeof(hd));
         hd.tol = -1.0;
-        DNS_HIP(hipMemcpyAsync(h->ctl.p, &hd, sizeof(hd), hipMemcpyHostToDevice,
-                               s));
-        DNS_HIP(hipStreamSynchronize(s));
+        DNS_TRY(upload_to(reinterpret_cast<CtlHeader *>(h->ctl.p), &hd, 1, s));
     }
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;

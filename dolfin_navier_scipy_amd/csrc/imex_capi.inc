@@ -672,10 +672,7 @@ int dns_imex::gather_state() {
 }
 
 int dns_imex::sync_counter() {
-    DNS_HIP(hipMemcpyAsync(stepctr.p, &tab_pos, sizeof(int),
-                           hipMemcpyHostToDevice, sys->stream));
-    DNS_HIP(hipStreamSynchronize(sys->stream));   // `tab_pos` is borrowed
-    return DNS_OK;
+    return stepctr.upload(&tab_pos, 1, sys->stream);
 }
 
 // everything a captured group of `group` steps depends on
@@ -1284,8 +1281,7 @@ static int dns_imex_run_impl(dns_imex *st, int32_t nsteps, const dns_imex_coeffs
         c_batch = std::min(c_batch, std::max(1, std::min(o.restart,
                                                          dns::kMaxRestart)));
         bool batch_ok = false;
-        const dns::CtlHeaderAcc *ha =
-            reinterpret_cast<const dns::CtlHeaderAcc *>(h->hdr_host);
+        const dns::CtlHeaderAcc *ha = h->hdr_host.p;
         for (int attempt = 0; attempt < 2 && !batch_ok; ++attempt) {
             if (attempt == 1) {
                 // restore the ring and try once more with a longer cycle
@@ -1336,8 +1332,8 @@ static int dns_imex_run_impl(dns_imex *st, int32_t nsteps, const dns_imex_coeffs
                                        dns::RowMap{0, h->n, 0, 0}));
                 hipLaunchKernelGGL(dns::k_sum_partials, 1, dns::kBlock, 0,
                                    h->stream, h->partR.p, h->gridS, h->scal.p);
-                DNS_HIP(hipMemcpyAsync(h->scal_host, h->scal.p, sizeof(double),
-                                       hipMemcpyDeviceToHost, h->stream));
+                DNS_TRY(dns::d2h_pinned(h->scal_host.p, h->scal.p, 1,
+                                        h->stream));
                 fin_batch = true;
             }
             DNS_TRY(h->read_header());
@@ -1454,7 +1450,7 @@ static int dns_imex_run_impl(dns_imex *st, int32_t nsteps, const dns_imex_coeffs
     if (fin_batch) {
         // (event and residual were enqueued behind the last batch and have
         // arrived with its header)
-        const double tr = std::sqrt(h->scal_host[0]);
+        const double tr = std::sqrt(h->scal_host.p[0]);
         sp->true_relres = sp->bnorm > 0 ? tr / sp->bnorm : tr;
         h->spmv_count++;
     } else {
@@ -1524,8 +1520,8 @@ static int dns_imex_get_state_impl(dns_imex *st, double *v, double *p) {
     DNS_TRY(st->gather_state());
     if (v) DNS_TRY(st->xs[st->cur].download(v, (size_t)h->nv, h->stream));
     if (p)
-        DNS_TRY(dns::staged_d2h(p, st->xs[st->cur].p + h->nv,
-                                (size_t)h->np * sizeof(double), h->stream));
+        DNS_TRY(dns::download_from(p, st->xs[st->cur].p + h->nv,
+                                   (size_t)h->np, h->stream));
     DNS_HIP(hipStreamSynchronize(h->stream));
     if (p)
         for (int i = 0; i < h->np; ++i) p[i] *= st->last_pscale;

@@ -224,11 +224,7 @@ int dns_saddle::build_mg_schur_rows(const dns::HostCsr &S0loc) {
         // sizes of the whole operators (byte counts of the roofline model)
         {
             double cnt = (double)Sloc.nnz();
-            DNS_TRY(upload_to(scal.p, &cnt, 1, stream));
-            DNS_TRY(comm->allreduce(scal.p, 1, stream));
-            DNS_HIP(hipMemcpyAsync(&cnt, scal.p, sizeof(double),
-                                   hipMemcpyDeviceToHost, stream));
-            DNS_HIP(hipStreamSynchronize(stream));
+            DNS_TRY(allreduce_host(&cnt, 1));
             lv.nnz_S = (int64_t)cnt;
             lv.nnz_P = Pm.nnz();
         }

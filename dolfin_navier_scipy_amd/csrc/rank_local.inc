@@ -38,7 +38,6 @@ int dns_saddle::all_ranks_max(double mine, double *out) {
     for (int r = 0; r <= P; ++r) st[r] = r;
     DNS_TRY(comm->allgatherv(buf.p, st, stream));
     DNS_TRY(buf.download(v.data(), v.size(), stream));
-    DNS_HIP(hipStreamSynchronize(stream));
     *out = *std::max_element(v.begin(), v.end());
     return DNS_OK;
 }
@@ -212,12 +211,7 @@ int dns_saddle::init_rows(int dev, dns_comm *c, int nv_all, int np_all,
             cnt[1] = (double)jt->nnz;
             cnt[2] = (double)j->nnz;
         }
-        DNS_TRY(scal.alloc(16));
-        DNS_TRY(upload_to(scal.p, cnt, 4, stream));
-        DNS_TRY(comm->allreduce(scal.p, 4, stream));
-        DNS_HIP(hipMemcpyAsync(cnt, scal.p, 4 * sizeof(double),
-                               hipMemcpyDeviceToHost, stream));
-        DNS_HIP(hipStreamSynchronize(stream));
+        DNS_TRY(allreduce_host(cnt, 4));
         if (bad != DNS_OK) return bad;
         if (cnt[3] > 0.0)
             return fail(DNS_ERR_BAD_ARGUMENT,

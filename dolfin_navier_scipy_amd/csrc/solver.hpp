@@ -53,13 +53,9 @@ inline int CsrDev::upload(const dns_csr *a, hipStream_t s) {
     DNS_TRY(vals.alloc((size_t)nnz + 2));
     DNS_HIP(hipMemsetAsync(colidx.p + nnz, 0, 2 * sizeof(int), s));
     DNS_HIP(hipMemsetAsync(vals.p + nnz, 0, 2 * sizeof(double), s));
-    {
-        // the caller's arrays outlive this call: one wait for the three
-        SyncOnExit arrived(s);
-        DNS_TRY(rowptr.upload_async(a->rowptr, (size_t)nrows + 1, s));
-        DNS_TRY(colidx.upload_async(a->colidx, (size_t)nnz, s));
-        DNS_TRY(vals.upload_async(a->vals, (size_t)nnz, s));
-    }
+    DNS_TRY(rowptr.upload(a->rowptr, (size_t)nrows + 1, s));
+    DNS_TRY(colidx.upload(a->colidx, (size_t)nnz, s));
+    DNS_TRY(vals.upload(a->vals, (size_t)nnz, s));
     // row blocks of the LDS-streaming kernel: consecutive rows with at most
     // TILE non-zeros and at most kBlock rows; a longer row stands alone
     // (tables for the three tile sizes the tuning variants use)
@@ -400,8 +396,8 @@ struct dns_saddle {
     dns::PinnedBuf<double> mstage;    // host side of solve_multi's blocks
     std::vector<std::vector<double>> col_history;
     dns::DevBuf<double> scal;        // small scalar scratch
-    dns::CtlHeader *hdr_host = nullptr;   // pinned
-    double *scal_host = nullptr;          // pinned
+    dns::PinnedBuf<dns::CtlHeaderAcc> hdr_host;   // read_header's copy of ctl
+    dns::PinnedBuf<double> scal_host;
     std::vector<double> history;
     int64_t spmv_count = 0;
     // row-partitioned solve (comm.hpp): this rank's row blocks of the n rows of
@@ -476,6 +472,9 @@ struct dns_saddle {
     // logical OR of a flag over the ranks of the communicator (one all-reduce
     // of one scalar, synchronises the stream; never inside a capture)
     int all_ranks_any(bool mine, bool *any);
+    // sum of `count` host doubles over the ranks, in place (through `scal`;
+    // synchronises the stream; never inside a capture)
+    int allreduce_host(double *v, int count);
     // a LOCAL verdict inside a collective routine of the set-up: every rank
     // enters, the failing rank returns its own status, the others
     // DNS_ERR_COMM -- nobody is left waiting in the exchange behind it

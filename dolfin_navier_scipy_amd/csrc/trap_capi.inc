@@ -233,8 +233,9 @@ static int dns_trap_traj_export_async_impl(dns_trap *t, int32_t which, int32_t s
     dns::log_host_copy("export (at the wait)", host, t->traj[which].p, bytes);
     DNS_HIP(hipEventRecord(e.ready, h->stream));
     DNS_HIP(hipStreamWaitEvent(e.cstream, e.ready, 0));
-    DNS_HIP(hipMemcpyAsync(stage, t->traj[which].p + (size_t)slot0 * h->nv,
-                           bytes, hipMemcpyDeviceToHost, e.cstream));
+    DNS_TRY(dns::d2h_pinned(static_cast<double *>(stage),
+                            t->traj[which].p + (size_t)slot0 * h->nv,
+                            (size_t)count * h->nv, e.cstream));
     DNS_HIP(hipEventRecord(e.done[which], e.cstream));
     e.pending[which] = true;
     return DNS_OK;
@@ -310,8 +311,8 @@ static int dns_trap_traj_read_impl(dns_trap *t, int32_t which, int32_t slot, dou
     DNS_HIP(hipSetDevice(h->device));
     DNS_TRY(t->flush_pending_upd());
     if (t->part.on) DNS_TRY(t->gather_slot(which, slot));
-    DNS_TRY(dns::staged_d2h(v, t->traj[which].p + (size_t)slot * h->nv,
-                            (size_t)h->nv * sizeof(double), h->stream));
+    DNS_TRY(dns::download_from(v, t->traj[which].p + (size_t)slot * h->nv,
+                               (size_t)h->nv, h->stream));
     return DNS_OK;
 }
 
@@ -832,10 +833,9 @@ int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
         hipLaunchKernelGGL(dns::k_sum_partials, 1, dns::kBlock, 0, s,
                            h->partC.p, gU, h->scal.p);
         DNS_HIP(hipGetLastError());
-        DNS_HIP(hipMemcpyAsync(h->scal_host, h->scal.p, sizeof(double),
-                               hipMemcpyDeviceToHost, s));
+        DNS_TRY(dns::d2h_pinned(h->scal_host.p, h->scal.p, 1, s));
         DNS_HIP(hipStreamSynchronize(s));
-        t->updnorm += dt * h->scal_host[0];
+        t->updnorm += dt * h->scal_host.p[0];
     }
     if (async) return DNS_OK;            // (device time: see dns_trap_poll)
     DNS_HIP(hipEventRecord(h->ev1, s));
@@ -870,8 +870,7 @@ static int dns_trap_poll_impl(dns_trap *t, int32_t *solves, int32_t *fails, int3
     dns_saddle *h = t->sys;
     DNS_HIP(hipSetDevice(h->device));
     DNS_TRY(h->read_header());                 // synchronises the stream
-    const dns::CtlHeaderAcc *ha =
-        reinterpret_cast<const dns::CtlHeaderAcc *>(h->hdr_host);
+    const dns::CtlHeaderAcc *ha = h->hdr_host.p;
     if (solves) *solves = ha->acc_solves;
     if (fails) *fails = ha->acc_fail;
     if (iters) *iters = ha->acc_iters;
@@ -991,8 +990,8 @@ static int dns_trap_get_state_impl(dns_trap *t, double *v, double *p) {
         DNS_TRY(h->comm->allgatherv(t->xs[t->cur].p, h->st_v, h->stream));
     if (v) DNS_TRY(t->xs[t->cur].download(v, (size_t)h->nv, h->stream));
     if (p) {
-        DNS_TRY(dns::staged_d2h(p, t->xs[t->cur].p + h->nv,
-                                (size_t)h->np * sizeof(double), h->stream));
+        DNS_TRY(dns::download_from(p, t->xs[t->cur].p + h->nv,
+                                   (size_t)h->np, h->stream));
         const double sc = t->last_dt > 0.0 ? -1.0 / t->last_dt : 1.0;
         for (int i = 0; i < h->np; ++i) p[i] *= sc;          // snu:1542
     }
@@ -1013,11 +1012,7 @@ static int dns_trap_update_norm_impl(dns_trap *t, double *out) {
         // collective -- all ranks ask together)
         DNS_HIP(hipSetDevice(h->device));
         double v = t->updnorm;
-        DNS_TRY(dns::upload_to(h->scal.p, &v, 1, h->stream));
-        DNS_TRY(h->comm->allreduce(h->scal.p, 1, h->stream));
-        DNS_HIP(hipMemcpyAsync(&v, h->scal.p, sizeof(double),
-                               hipMemcpyDeviceToHost, h->stream));
-        DNS_HIP(hipStreamSynchronize(h->stream));
+        DNS_TRY(h->allreduce_host(&v, 1));
         *out = v;
     }
     return DNS_OK;

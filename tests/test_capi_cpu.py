@@ -184,3 +184,38 @@ def test_spawn_retry_only_for_rendezvous_errors():
     assert not spawn_util.is_rendezvous_error(
         RuntimeError('process 1 terminated with signal SIGABRT'))
     assert not spawn_util.is_rendezvous_error(AssertionError('1e-3 > 1e-9'))
+
+
+def test_every_host_copy_goes_through_common_hpp():
+    """The DMA engine never sees a caller's or a stack's pageable memory:
+    outside `common.hpp` (the staged and pinned copies) no `hipMemcpy*` call
+    moves bytes between host and device, nothing pins host memory in place,
+    and the removed enqueue-only upload is not back"""
+    csrc = os.path.join(ROOT, 'dolfin_navier_scipy_amd', 'csrc')
+    paths = sorted(os.path.join(csrc, f) for f in os.listdir(csrc)
+                   if f.endswith(('.hip', '.inc', '.hpp')))
+    assert len(paths) > 10
+    bad = []
+    for path in paths:
+        name = os.path.basename(path)
+        text = open(path).read()
+        for word in ('hipHostRegister', 'upload_async', 'SyncOnExit'):
+            if word in text:
+                bad.append('%s: %s' % (name, word))
+        if name == 'common.hpp':
+            continue
+        code = re.sub(r'//[^\n]*|/\*.*?\*/', ' ', text, flags=re.S)
+        for m in re.finditer(r'\b(hipMemcpy\w*)\s*\(', code):
+            depth, end = 0, m.end() - 1
+            while True:                  # through to the closing parenthesis
+                depth += {'(': 1, ')': -1}.get(code[end], 0)
+                if depth == 0:
+                    break
+                end += 1
+            call = code[m.start():end + 1]
+            fn = m.group(1)
+            if (re.search(r'hipMemcpy(HostToDevice|DeviceToHost|Default)\b',
+                          call) or re.search(r'(To|From)Symbol|HtoD|DtoH', fn)):
+                line = code.count('\n', 0, m.start()) + 1
+                bad.append('%s:%d: %s' % (name, line, ' '.join(call.split())))
+    assert not bad, '\n'.join(bad)

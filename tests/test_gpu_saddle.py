@@ -691,8 +691,8 @@ def test_debug_uploads_prints_the_host_ranges_of_every_copy():
     """`DNS_DEBUG_UPLOADS=1` (round 5, after a GPU memory fault at a host
     address whose record held no ranges): every copy between host memory and
     the device says `[ptr, ptr + bytes)` on stderr before it is enqueued, the
-    blocks of `dns_saddle_solve_multi` included -- a fault address can then be
-    tied to a buffer and an offset"""
+    blocks of `dns_saddle_solve_multi` and the library's page-locked buffers
+    included -- a fault address can then be tied to a buffer and an offset"""
     import subprocess
     code = r'''
 import sys, numpy as np
@@ -720,6 +720,9 @@ system.close()
     assert len(lines) > 10
     kinds = set(ln.split()[2] for ln in lines)
     assert {'upload', 'download'} <= kinds
+    # (and the copies of the library's own page-locked buffers: the header
+    # read of every solve, the blocks of solve_multi)
+    assert {'pinned_h2d', 'pinned_d2h'} <= kinds
     assert any('multi rhs_v' in ln for ln in lines)
     assert any('multi out' in ln for ln in lines)
     # every line carries a well-formed half-open host range
