@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/dns_amd.h"
@@ -46,6 +47,19 @@ inline int guarded(Body body) noexcept {
         return fail(DNS_ERR_HOST, "host-side exception");
     }
 }
+
+// runs `f` when it goes out of scope: on every return and on an exception
+template <typename F>
+class ScopeExit {
+  public:
+    explicit ScopeExit(F f) : f_(std::move(f)) {}
+    ScopeExit(const ScopeExit &) = delete;
+    ScopeExit &operator=(const ScopeExit &) = delete;
+    ~ScopeExit() { f_(); }
+
+  private:
+    F f_;
+};
 
 #define DNS_HIP(call)                                                        \
     do {                                                                     \

@@ -1,5 +1,6 @@
 // Device-resident IMEX stepper state (CNAB / SBDF2 inner loops).
 #pragma once
+#include "batch_policy.hpp"
 #include "convection.hpp"
 #include "solver.hpp"
 #include "trap.hpp"
@@ -36,10 +37,22 @@ struct dns_imex {
     // two solution-space vectors [v; p~] (current, previous) + work
     // current and the four solutions before it, work
     dns::DevBuf<double> xs[6];
-    dns::DevBuf<double> ck[6];     // checkpoint of the history (and of the
-                                   // work buffer: it holds the warm start)
-                                   // for a batch
-    dns::DevBuf<double> ckn[2];    // ... and of the convection history
+    // checkpoint of a pipelined batch: the ring (the work buffer too: it
+    // holds the warm start), the convection history and, when residuals are
+    // carried, the last right-hand side and residual and the two residuals
+    // of the six-node / partitioned step.  `add` records each buffer once,
+    // as a pair in both directions: k_batch_begin copies it one way to save
+    // (with the reset of the batch accumulators; `copy` false: that alone)
+    // and the other way to restore
+    struct Checkpoint {
+        dns::DevBuf<double> ring[6], nfc[2], rc6[2], b, rcarry;
+        dns::CopyList fwd{}, back{};
+        static_assert(6 + 2 + 2 + 2 <= sizeof(fwd.n) / sizeof(fwd.n[0]));
+        void clear() { fwd.count = back.count = 0; }
+        int add(double *live, dns::DevBuf<double> &copy, size_t n);
+        int save(const dns_saddle *h, bool copy, double stop_frac) const;
+        int restore(const dns_saddle *h) const;
+    } ck;
     int cur = 0, prev = 1, pprev = 2, p3 = 3, p4 = 4, work = 5;
     int nsol = 0;                  // how many valid solution vectors (0..5)
     // the work buffer already holds this step's warm start (written by the
@@ -52,7 +65,7 @@ struct dns_imex {
     // `b_valid`: b holds the right-hand side whose solution is xs[cur];
     // `carry_ok`: kxs[prev..p4] are K times the ring as it stands (primed by
     // prime_carry or kept current by carry steps)
-    dns::DevBuf<double> kxs[6], rcarry, ckb, ckr;
+    dns::DevBuf<double> kxs[6], rcarry;
     bool b_valid = false, carry_ok = false;
     int prime_carry(bool zero_r);
     // six-node step (step_kernels.hpp): the warm start lives in x0buf[work & 1]
@@ -61,7 +74,7 @@ struct dns_imex {
     // by the tail of the step before.  `six_ok`: x0buf / cell values / rc6 are
     // those of the ring as it stands (primed by prime_six or kept by six-node
     // steps); DNS_STEP6=0 keeps the seven-node step
-    dns::DevBuf<double> x0buf[2], rc6[2], ckx0, ckrc[2], ckcell, kx6;
+    dns::DevBuf<double> x0buf[2], rc6[2], kx6;
     bool six_ok = false, env_six = true;
     bool env_dfront = true;   // DNS_DIST_FRONT: one-launch front of a partitioned step
     // row-partitioned step whose one-step cycle ends in k_arn_tail_lazy1: the
@@ -170,20 +183,7 @@ struct dns_imex {
     dns_conv *conv = nullptr;      // device convection: nfc_c = scale*N(v_c)v_c
     double conv_scale = -1.0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    // pipelined batches: what the last batch learnt is kept across
-    // dns_imex_run calls (a run is then 100 % graph replays from its first
-    // step on -- the driver's 20-step window sees what a 400-step window sees)
-    int cpred = -1;                // predicted cycle length of a batch
-    bool noslack = false;
-    int noslack_hold = 1;
-    // oversolve policy (multigrid Schur block, DnsCtl::stop_frac): `cpred` is
-    // then the cycle length itself; it comes down only when every solve of a
-    // batch stood a decade below the tolerance in FRONT of its last column
-    // and goes up, without a replay, when a batch ended close to it
-    int lower_hold = 0, lower_backoff = 2;
-    bool lowered_last = false, spiked = false;
-    int batch_len = 8;             // steps per batch: 8 -> 16 -> 32 while the
-                                   // predictions hold
+    dns::BatchPolicy policy;       // cycle length and length of the batches
     uint64_t prepared_sig = 0;     // configuration the graphs were captured for
     int chi_hi = 0;                // longest cycle length they cover (with hysteresis)
     // record of the last dns_imex_run (dns_imex_run_info)
@@ -192,9 +192,14 @@ struct dns_imex {
     // knobs read ONCE, when the stepper is created
     bool env_step_history = false, env_debug = false, env_slack_adapt = true;
     int env_group = 8;
-    double env_noslack_maxrel = 0.85;   // DNS_NOSLACK_MAXREL: no slack step
-                                        // while the batch maximum of
-                                        // residual / tolerance stays below
+    double env_noslack_maxrel = 0.85;   // DNS_NOSLACK_MAXREL (BatchParams)
+    // steps in the next graph of a batch with `left` steps to go: groups of
+    // env_group (at most 32), for the tail of a batch groups of half as many
+    // (from 4 on: a 20-step call is 8 + 8 + 4 = three launches), single steps
+    int group_for(int left) const {
+        const int g = std::max(1, std::min(env_group, 32));
+        return left >= g ? g : (g >= 4 && left >= g / 2) ? g / 2 : 1;
+    }
     struct HostState {
         int cur, prev, pprev, p3, p4, work, nsol, nc, no, tab_pos;
         long steps_enqueued;

@@ -761,7 +761,7 @@ int dns_imex::prepare_graphs(const dns_imex_coeffs *cf,
     // time it comes down by one; a prediction that has come down for good --
     // the long cycles of a start-up transient -- is followed, or the graphs of
     // cycle lengths nobody asks for any more crowd the cache)
-    const int needed = std::min(m, std::max(4, cpred + 1));
+    const int needed = std::min(m, std::max(4, policy.cpred + 1));
     if (needed > chi_hi)
         chi_hi = needed;
     else if (needed < chi_hi - 1)
@@ -770,40 +770,305 @@ int dns_imex::prepare_graphs(const dns_imex_coeffs *cf,
     sig = mix64(sig, (uint64_t)chi);
     if (sig == prepared_sig) return DNS_OK;
     prepare_attempted = true;
-    const int kGroup = std::max(1, std::min(env_group, 32));
+    const int big = group_for(1 << 30);
     const HostState s0 = host_state();
+    // (on every exit: no cycle length set, the ring as it was)
+    dns::ScopeExit reset([&] {
+        h->pipeline_c = 0;
+        set_host_state(s0);
+        preparing = false;
+    });
     preparing = true;          // (captures only: the tables are not consumed)
     for (int c = 1; c <= chi; ++c) {
         h->pipeline_c = c;
         set_host_state(s0);
         for (int r = 0; r < (s0.pre_ok ? 6 : 7); ++r) {
-            // groups of kGroup steps and, for the tail of a batch, of half
-            // as many (a 20-step call is 8 + 8 + 4 = three launches)
-            for (int gsz : {kGroup, kGroup / 2}) {
-                if (gsz <= 1 || (gsz == kGroup / 2 && kGroup < 4)) continue;
+            for (int gsz : {big, group_for(big / 2)}) {
+                if (gsz <= 1) continue;
                 const HostState sr = host_state();
                 const int rc = enqueue_group(cf, o, gsz, false);
                 set_host_state(sr);
-                if (rc != DNS_OK) {
-                    h->pipeline_c = 0;
-                    set_host_state(s0);
-                    preparing = false;
-                    return rc;
-                }
+                DNS_TRY(rc);
             }
-            const int rc = enqueue_group(cf, o, 1, false);   // advances by one
-            if (rc != DNS_OK) {
-                h->pipeline_c = 0;
-                set_host_state(s0);
-                preparing = false;
-                return rc;
-            }
+            DNS_TRY(enqueue_group(cf, o, 1, false));   // advances by one
         }
     }
-    h->pipeline_c = 0;
-    set_host_state(s0);
-    preparing = false;
     prepared_sig = sig;
+    return DNS_OK;
+}
+
+// k_batch_begin over the checkpoint's buffers (`ctl`: and the reset of the
+// batch accumulators)
+static int batch_begin(const dns_saddle *h, const dns::CopyList &cl,
+                       dns::DnsCtl *ctl, double stop_frac) {
+    const int gcp = (int)std::max<size_t>(
+        128, std::min<size_t>(2048, h->ld / 1024));
+    hipLaunchKernelGGL(dns::k_batch_begin, gcp, dns::kBlock, 0, h->stream, cl,
+                       ctl, stop_frac);
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+int dns_imex::Checkpoint::add(double *live, dns::DevBuf<double> &copy,
+                              size_t n) {
+    if (copy.n < n) DNS_TRY(copy.alloc(n));
+    const int q = fwd.count++;
+    back.count = fwd.count;
+    fwd.src[q] = back.dst[q] = live;
+    back.src[q] = fwd.dst[q] = copy.p;
+    fwd.n[q] = back.n[q] = (int)n;
+    return DNS_OK;
+}
+
+int dns_imex::Checkpoint::save(const dns_saddle *h, bool copy,
+                               double stop_frac) const {
+    dns::CopyList l = fwd;
+    if (!copy) l.count = 0;
+    return batch_begin(h, l, h->ctl.p, stop_frac);
+}
+
+int dns_imex::Checkpoint::restore(const dns_saddle *h) const {
+    return batch_begin(h, back, nullptr, 0.0);
+}
+
+// one dns_imex_run call: what its pieces share
+struct ImexRun {
+    dns_imex *st;
+    dns_saddle *h;
+    const dns_imex_coeffs *cf;
+    int nsteps;
+    dns_solve_stats *sp;
+    dns_solve_opts o, osync;       // batches / synchronous steps
+    int k = 0;                     // steps done
+    int64_t iters = 0;
+    bool pipelined = false;
+    bool fin_batch = false;        // the last batch carried the closing event
+    int sync_steps(int count);
+    int enter_pipeline();
+    int run_batch();
+    int finish_run(double *device_seconds, int64_t *total_iters);
+};
+
+// synchronous steps (plain launches, the host waits for every solve): the
+// start-up steps that establish the extrapolation history and the iteration
+// count, the non-pipelined configurations, and the last resort after a batch
+// that failed twice
+int ImexRun::sync_steps(int count) {
+    for (int q = 0; q < count && k < nsteps; ++q, ++k) {
+        DNS_TRY(st->step_device(cf, &osync, sp, false));
+        iters += sp->iters;
+        if (sp->status == DNS_NOT_CONVERGED) {
+            if (st->run_unconverged++ == 0) st->run_first_bad = k;
+        } else if (sp->status != DNS_OK) {
+            return sp->status;
+        }
+    }
+    return DNS_OK;
+}
+
+// from the start-up steps to the batches: what the captured steps expect to
+// find primed, the partition, and every graph the batches can ask for
+int ImexRun::enter_pipeline() {
+    if (st->six_ok && st->conv && st->six_conv_gen != st->conv->dbc_gen)
+        st->six_ok = false;       // boundary values changed in between
+    if (!st->six_ok) DNS_TRY(st->prime_six(cf, false));
+    if (!st->six_ok && cf->carry_residual && !st->carry_ok)
+        DNS_TRY(st->prime_carry(true));
+    DNS_HIP(hipEventRecord(st->e1, h->stream));
+    // (the stepper's row blocks and halo plan: host work and collectives
+    // that must not land inside a capture)
+    DNS_TRY(st->ensure_partition());
+    // (cell values a step of the run before has left are kept)
+    if (!(st->dcells_ok && st->conv && st->dcells_gen == st->conv->dbc_gen))
+        DNS_TRY(st->prime_dcells(&o));
+    st->prepare_attempted = false;
+    int prc = st->prepare_graphs(cf, &o);
+    if (h->dist() && st->prepare_attempted) {
+        // a capture can fail on ONE rank only (instantiation out of memory,
+        // an invalidated capture): replayed one-step cycles and plain
+        // synchronous steps issue different collective sequences, so the
+        // ranks agree on the branch before they take it -- whoever captured
+        // asks (the signatures, hence the decision to capture, are the same
+        // on every rank)
+        bool any = false;
+        DNS_TRY(h->all_ranks_any(prc != DNS_OK, &any));
+        if (any && prc == DNS_OK)
+            prc = dns::fail(DNS_ERR_COMM, "graph capture failed on another "
+                            "rank");
+    }
+    if (prc == DNS_OK || !h->dist()) return prc;
+    // a capture with collectives did not go through on this communicator:
+    // plain launches from here on, on every rank
+    if (st->env_debug)
+        fprintf(stderr, "[dns] graph capture of the partitioned step failed "
+                "(%s): plain launches\n", dns_last_error());
+    h->dist_graph_ok = false;
+    h->drop_graphs();
+    pipelined = false;
+    osync.use_graph = 0;
+    return sync_steps(nsteps - k);
+}
+
+// pipelined batches: every group of steps is ONE graph launch and nobody
+// waits; the device accumulates iteration counts and failures, the host
+// looks once per batch.  A batch in which some solve needed more Krylov
+// steps than predicted is restored from the checkpoint of the ring and
+// repeated with a longer cycle (once), then synchronously.
+int ImexRun::run_batch() {
+    dns::BatchPolicy &pol = st->policy;
+    const int nb = std::min(pol.batch_len, nsteps - k);
+    const bool sixing = st->six_ok;
+    // (partitioned stepper: its carried residuals live in the same buffers)
+    const bool dcar = h->dist() && st->part.on && cf->carry_residual != 0 &&
+                      st->rc6[0].p && st->rc6[1].p;
+    const bool carrying = cf->carry_residual != 0 && st->carry_ok;
+    dns_imex::Checkpoint &ck = st->ck;   // (saved by the first attempt)
+    ck.clear();
+    const int ring[6] = {st->cur, st->prev, st->pprev, st->p3, st->p4,
+                         st->work};
+    for (int q = 0; q < 6; ++q)
+        DNS_TRY(ck.add(st->xs[ring[q]].p, ck.ring[q], h->ld));
+    if (st->conv)
+        for (int q = 0; q < 2; ++q)
+            DNS_TRY(ck.add(st->nfc[q].p, ck.nfc[q], h->nv));
+    if ((sixing || dcar) && cf->carry_residual)
+        for (int q = 0; q < 2; ++q)
+            DNS_TRY(ck.add(st->rc6[q].p, ck.rc6[q], h->nv));
+    if (carrying) {
+        DNS_TRY(ck.add(st->b.p, ck.b, h->ld));
+        DNS_TRY(ck.add(st->rcarry.p, ck.rcarry, h->nv));
+    }
+    const dns_imex::HostState hs0 = st->host_state();
+    // back to the checkpoint, then what derives from it: K x products of the
+    // ring, device step counter, cell values (not in the ring), the six-node
+    // warm start and cell values (the counter is back at the first step)
+    auto restore = [&]() -> int {
+        DNS_TRY(ck.restore(h));
+        st->set_host_state(hs0);
+        if (carrying) DNS_TRY(st->prime_carry(false));
+        if (st->tables()) DNS_TRY(st->sync_counter());
+        DNS_TRY(st->prime_dcells(&o));
+        if (sixing) DNS_TRY(st->prime_six(cf, true));
+        return DNS_OK;
+    };
+    // oversolve (see DnsCtl::stop_frac): general cycles with the multigrid
+    // Schur block -- not the six-node step (its tail keeps no record of the
+    // columns a solve needed; it runs one column anyway)
+    const bool over = h->oversolve && !sixing;
+    const int cmax = std::max(1, std::min(o.restart, dns::kMaxRestart));
+    const int c_first = pol.cycle(over);
+    int c = std::min(c_first, cmax);
+    const dns::CtlHeaderAcc *ha = h->hdr_host.p;
+    bool batch_ok = false, replayed = false;
+    for (int attempt = 0; attempt < 2 && !batch_ok; ++attempt) {
+        if (attempt == 1) {
+            // restore the ring and try once more with a longer cycle
+            DNS_TRY(restore());
+            c = dns::BatchPolicy::longer(c, cmax);
+            st->run_replayed += nb;
+            replayed = true;
+        }
+        DNS_TRY(ck.save(h, attempt == 0, over ? h->oversolve_frac : 0.0));
+        h->pipeline_c = c;
+        for (int q = 0, g = 0; q < nb; q += g) {
+            g = st->group_for(nb - q);
+            DNS_TRY(st->enqueue_group(cf, &o, g, true));
+        }
+        h->pipeline_c = 0;
+        // the call's last batch: the closing event and the true residual of
+        // the last step (for the record) ride behind it, so that ONE
+        // synchronisation -- the header's -- ends the call
+        fin_batch = k + nb >= nsteps && !h->dist();
+        if (fin_batch) {
+            DNS_HIP(hipEventRecord(st->e1, h->stream));
+            DNS_LPR_SWITCH(
+                h->K.lpr,
+                hipLaunchKernelGGL(dns::k_resid_norm<L>, h->gridS, dns::kBlock,
+                                   0, h->stream, h->n, h->K.rowptr.p,
+                                   h->K.colidx.p, h->K.vals.p,
+                                   st->xs[st->cur].p, st->b.p, h->r.p,
+                                   h->partR.p, (double *)nullptr,
+                                   dns::RowMap{0, h->n, 0, 0}));
+            hipLaunchKernelGGL(dns::k_sum_partials, 1, dns::kBlock, 0,
+                               h->stream, h->partR.p, h->gridS, h->scal.p);
+            DNS_TRY(dns::d2h_pinned(h->scal_host.p, h->scal.p, 1, h->stream));
+        }
+        DNS_TRY(h->read_header());
+        if (st->env_debug)
+            fprintf(stderr,
+                    "[dns] batch at step %d (%d steps, attempt %d): c=%d "
+                    "solves=%d fail=%d iters=%d maxit=%d maxrel=%.2e "
+                    "need=%d prev=%.2e r0(last)=%.2e status=%d\n",
+                    k, nb, attempt, c, ha->acc_solves, ha->acc_fail,
+                    ha->acc_iters, ha->acc_maxit, ha->acc_maxrel,
+                    ha->acc_maxneed, ha->acc_maxprev,
+                    ha->h.tol > 0 ? ha->h.beta / ha->h.tol : 0.0,
+                    ha->h.status);
+        if (ha->h.status == dns::kGsFallback) o.reorth = osync.reorth = 0;
+        batch_ok = ha->acc_fail == 0 && ha->h.status == DNS_OK;
+        if (!batch_ok) fin_batch = false;
+    }
+    if (!batch_ok) {
+        // last resort: the batch step by step from the checkpoint
+        if (over) DNS_TRY(h->set_stop_frac(0.0));
+        DNS_TRY(restore());
+        st->run_replayed += nb;
+        const int rc = sync_steps(nb);
+        if (rc == DNS_OK) DNS_TRY(st->prime_six(cf, false));
+        if (!st->six_ok && cf->carry_residual && rc == DNS_OK)
+            DNS_TRY(st->prime_carry(true));
+        pol.after_fallback(h->last_iters);
+        return rc;
+    }
+    k += nb;
+    iters += ha->acc_iters;
+    pol.after_batch({over, c_first, c, replayed, ha->acc_maxit, ha->acc_maxrel,
+                     ha->acc_maxprev},
+                    {h->oversolve_cmin_eff(), h->oversolve_raise,
+                     h->oversolve_lower, h->mg_two_for(1) && !h->mg_two_for(2),
+                     st->env_slack_adapt, st->env_noslack_maxrel});
+    h->last_iters = ha->h.total_it;
+    sp->iters = ha->h.total_it;
+    sp->status = ha->h.conv ? DNS_OK : DNS_NOT_CONVERGED;
+    sp->bnorm = ha->h.bnorm;
+    sp->est_relres =
+        ha->h.bnorm > 0 ? ha->h.resnorm / ha->h.bnorm : ha->h.resnorm;
+    return DNS_OK;
+}
+
+// the closing event, the true residual of the last step, the timing and the
+// report of steps that ended unconverged
+int ImexRun::finish_run(double *device_seconds, int64_t *total_iters) {
+    if (fin_batch) {
+        // (event and residual were enqueued behind the last batch and have
+        // arrived with its header)
+        const double tr = std::sqrt(h->scal_host.p[0]);
+        sp->true_relres = sp->bnorm > 0 ? tr / sp->bnorm : tr;
+        h->spmv_count++;
+    } else {
+        DNS_HIP(hipEventRecord(st->e1, h->stream));
+        // true residual of the last step for the record: behind the closing
+        // event (not part of the stepping time), ONE synchronisation for both
+        if (nsteps > 0) {
+            double tr = 0.0;
+            DNS_TRY(h->true_residual(st->b.p, st->xs[st->cur].p, &tr));
+            sp->true_relres = sp->bnorm > 0 ? tr / sp->bnorm : tr;
+        } else {
+            DNS_HIP(hipEventSynchronize(st->e1));
+        }
+    }
+    float ms = 0.f;
+    DNS_HIP(hipEventElapsedTime(&ms, st->e0, st->e1));
+    if (device_seconds) *device_seconds = 1e-3 * ms;
+    if (total_iters) *total_iters = iters;
+    if (st->run_unconverged > 0) {
+        sp->status = DNS_NOT_CONVERGED;
+        return dns::fail(DNS_NOT_CONVERGED,
+                         "%d of %d time steps ended at maxiter without reaching "
+                         "the tolerance (first: step %d of this run); the state "
+                         "was advanced with the best iterates",
+                         st->run_unconverged, nsteps, st->run_first_bad);
+    }
     return DNS_OK;
 }
 
@@ -1068,416 +1333,46 @@ static int dns_imex_run_impl(dns_imex *st, int32_t nsteps, const dns_imex_coeffs
     else
         dns_default_solve_opts(&o);
     dns_solve_stats local;
-    dns_solve_stats *sp = last_stats ? last_stats : &local;
-    memset(sp, 0, sizeof(*sp));
+    ImexRun r{st, h, cf, nsteps, last_stats ? last_stats : &local, o, o};
+    memset(r.sp, 0, sizeof(*r.sp));
     if (st->tables() && st->rows_left() < nsteps)
         return dns::fail(DNS_ERR_NOT_READY,
                          "%d steps asked for, the per-step tables hold %d more",
                          (int)nsteps, st->rows_left());
-    int64_t iters = 0;
+    // the run's settings of the system, undone on every exit (the status of
+    // the oversolve reset is ignored: the first error is the one reported)
+    bool over = false;
+    dns::ScopeExit reset([&] {
+        h->want_history = true;
+        h->pipeline_c = 0;
+        if (over) (void)h->set_stop_frac(0.0);
+    });
     h->want_history = false;
     st->run_unconverged = 0;
     st->run_first_bad = -1;
     st->run_replayed = 0;
     const int64_t captures0 = h->graph_captures;
-    bool pipelined = o.method == DNS_METHOD_GMRES && o.use_graph != 0 &&
-                     h->graph_capable();
-    int k = 0;
-    // synchronous steps (plain launches, the host waits for every solve): the
-    // start-up steps that establish the extrapolation history and the
-    // iteration count, the non-pipelined configurations, and the last resort
-    // after a batch that failed twice
-    dns_solve_opts osync = o;
-    if (pipelined) osync.use_graph = 0;
-    auto sync_steps = [&](int count) -> int {
-        for (int q = 0; q < count && k < nsteps; ++q, ++k) {
-            DNS_TRY(st->step_device(cf, &osync, sp, false));
-            iters += sp->iters;
-            if (sp->status == DNS_NOT_CONVERGED) {
-                if (st->run_unconverged++ == 0) st->run_first_bad = k;
-            } else if (sp->status != DNS_OK) {
-                return sp->status;
-            }
-        }
-        return DNS_OK;
-    };
+    r.pipelined = r.o.method == DNS_METHOD_GMRES && r.o.use_graph != 0 &&
+                  h->graph_capable();
+    if (r.pipelined) r.osync.use_graph = 0;
     int rc = DNS_OK;
-    if (!pipelined) {
-        rc = sync_steps(nsteps);
+    if (!r.pipelined) {
+        rc = r.sync_steps(nsteps);
     } else {
-        // a stepper that has its history (five solutions for the quartic warm
-        // start, the iteration count of the last solve) goes straight to the
-        // batches; a fresh one does its first steps one by one
-        const int need = (st->nsol >= 5 && st->cpred > 0) ? 0
-                         : std::max(2, 5 - st->nsol);
+        // a fresh stepper does its first steps one by one
+        const int need = st->policy.startup_steps(st->nsol);
         if (need > 0) {
-            rc = sync_steps(need);
-            st->cpred = std::max(1, h->last_iters) + 1;
-            st->noslack = false;
-            st->noslack_hold = 1;
-            st->batch_len = 8;
+            rc = r.sync_steps(need);
+            st->policy.after_startup(h->last_iters);
         }
-        if (rc == DNS_OK && k < nsteps) {
-            if (st->six_ok && st->conv &&
-                st->six_conv_gen != st->conv->dbc_gen)
-                st->six_ok = false;       // boundary values changed in between
-            if (!st->six_ok) DNS_TRY(st->prime_six(cf, false));
-            if (!st->six_ok && cf->carry_residual && !st->carry_ok)
-                DNS_TRY(st->prime_carry(true));
-            DNS_HIP(hipEventRecord(st->e1, h->stream));
-            // (the stepper's row blocks and halo plan: host work and
-            // collectives that must not land inside a capture)
-            DNS_TRY(st->ensure_partition());
-            // (cell values a step of the run before has left are kept)
-            if (!(st->dcells_ok && st->conv &&
-                  st->dcells_gen == st->conv->dbc_gen))
-                DNS_TRY(st->prime_dcells(&o));
-            st->prepare_attempted = false;
-            int prc = st->prepare_graphs(cf, &o);
-            if (h->dist() && st->prepare_attempted) {
-                // a capture can fail on ONE rank only (instantiation out of
-                // memory, an invalidated capture): replayed one-step cycles
-                // and plain synchronous steps issue different collective
-                // sequences, so the ranks agree on the branch before they
-                // take it -- whoever captured asks (the signatures, hence the
-                // decision to capture, are the same on every rank)
-                bool any = false;
-                DNS_TRY(h->all_ranks_any(prc != DNS_OK, &any));
-                if (any && prc == DNS_OK)
-                    prc = dns::fail(DNS_ERR_COMM, "graph capture failed on "
-                                    "another rank");
-            }
-            if (prc != DNS_OK && h->dist()) {
-                // a capture with collectives did not go through on this
-                // communicator: plain launches from here on, on every rank
-                if (st->env_debug)
-                    fprintf(stderr, "[dns] graph capture of the partitioned "
-                            "step failed (%s): plain launches\n",
-                            dns_last_error());
-                h->dist_graph_ok = false;
-                h->drop_graphs();
-                pipelined = false;
-                osync.use_graph = 0;
-                rc = sync_steps(nsteps - k);
-            } else if (prc != DNS_OK) {
-                return prc;
-            }
-        }
+        if (rc == DNS_OK && r.k < nsteps) rc = r.enter_pipeline();
     }
-    DNS_HIP(hipEventRecord(st->e0, h->stream));
-    // pipelined batches: every kGroup steps are ONE graph launch and nobody
-    // waits; the device accumulates iteration counts and failures, the host
-    // looks once per batch.  A batch in which some solve needed more Krylov
-    // steps than predicted is restored from the checkpoint of the ring and
-    // repeated with a longer cycle (once), then synchronously.
-    const int kGroup = std::max(1, std::min(st->env_group, 32));
-    bool fin_batch = false;
-    while (rc == DNS_OK && pipelined && k < nsteps) {
-        const int nb = std::min(st->batch_len, nsteps - k);
-        const int hist5[6] = {st->cur, st->prev, st->pprev, st->p3, st->p4,
-                              st->work};
-        dns::CopyList save;
-        save.count = 0;
-        for (int q = 0; q < 6; ++q) {
-            if (st->ck[q].n < h->ld) DNS_TRY(st->ck[q].alloc(h->ld));
-            save.src[save.count] = st->xs[hist5[q]].p;
-            save.dst[save.count] = st->ck[q].p;
-            save.n[save.count++] = (int)h->ld;
-        }
-        const dns_imex::HostState hs0 = st->host_state();
-        if (st->conv) {
-            for (int q = 0; q < 2; ++q) {
-                if (st->ckn[q].n < (size_t)h->nv)
-                    DNS_TRY(st->ckn[q].alloc((size_t)h->nv));
-                save.src[save.count] = st->nfc[q].p;
-                save.dst[save.count] = st->ckn[q].p;
-                save.n[save.count++] = h->nv;
-            }
-        }
-        const bool sixing = st->six_ok;
-        // (partitioned stepper: its carried residuals live in the same two
-        // buffers)
-        const bool dcar = h->dist() && st->part.on && cf->carry_residual != 0 &&
-                          st->rc6[0].p && st->rc6[1].p;
-        if ((sixing || dcar) && cf->carry_residual) {
-            for (int q = 0; q < 2; ++q) {
-                if (st->ckrc[q].n < (size_t)h->nv)
-                    DNS_TRY(st->ckrc[q].alloc((size_t)h->nv));
-                save.src[save.count] = st->rc6[q].p;
-                save.dst[save.count] = st->ckrc[q].p;
-                save.n[save.count++] = h->nv;
-            }
-        }
-        const bool carrying = cf->carry_residual != 0 && st->carry_ok;
-        if (carrying) {
-            if (st->ckb.n < h->ld) DNS_TRY(st->ckb.alloc(h->ld));
-            if (st->ckr.n < (size_t)h->nv)
-                DNS_TRY(st->ckr.alloc((size_t)h->nv));
-            save.src[save.count] = st->b.p;
-            save.dst[save.count] = st->ckb.p;
-            save.n[save.count++] = (int)h->ld;
-            save.src[save.count] = st->rcarry.p;
-            save.dst[save.count] = st->ckr.p;
-            save.n[save.count++] = h->nv;
-        }
-        // back to the checkpoint: the ring, the convection history and -- when
-        // residuals are carried -- the last right-hand side, the last
-        // residual and the ring of K x products (recomputed)
-        auto restore = [&]() -> int {
-            for (int q = 0; q < 6; ++q)
-                DNS_HIP(hipMemcpyAsync(st->xs[hist5[q]].p, st->ck[q].p,
-                                       h->ld * sizeof(double),
-                                       hipMemcpyDeviceToDevice, h->stream));
-            if (st->conv)
-                for (int q = 0; q < 2; ++q)
-                    DNS_HIP(hipMemcpyAsync(st->nfc[q].p, st->ckn[q].p,
-                                           (size_t)h->nv * sizeof(double),
-                                           hipMemcpyDeviceToDevice,
-                                           h->stream));
-            st->set_host_state(hs0);
-            if (carrying) {
-                DNS_HIP(hipMemcpyAsync(st->b.p, st->ckb.p,
-                                       h->ld * sizeof(double),
-                                       hipMemcpyDeviceToDevice, h->stream));
-                DNS_HIP(hipMemcpyAsync(st->rcarry.p, st->ckr.p,
-                                       (size_t)h->nv * sizeof(double),
-                                       hipMemcpyDeviceToDevice, h->stream));
-                DNS_TRY(st->prime_carry(false));
-            }
-            if (st->tables()) DNS_TRY(st->sync_counter());
-            DNS_TRY(st->prime_dcells(&o));     // (cell values: not in the ring)
-            if (dcar)
-                for (int q = 0; q < 2; ++q)
-                    DNS_HIP(hipMemcpyAsync(st->rc6[q].p, st->ckrc[q].p,
-                                           (size_t)h->nv * sizeof(double),
-                                           hipMemcpyDeviceToDevice, h->stream));
-            if (sixing) {
-                // warm start and cell values again from the restored ring (the
-                // device counter is back at the batch's first step), the two
-                // carried residuals from the checkpoint
-                if (cf->carry_residual)
-                    for (int q = 0; q < 2; ++q)
-                        DNS_HIP(hipMemcpyAsync(st->rc6[q].p, st->ckrc[q].p,
-                                               (size_t)h->nv * sizeof(double),
-                                               hipMemcpyDeviceToDevice,
-                                               h->stream));
-                DNS_TRY(st->prime_six(cf, true));
-            }
-            return DNS_OK;
-        };
-        bool saved = false;           // (goes out with the first attempt)
-        const int replayed_before = st->run_replayed;
-        // no slack step while every solve of the last batch ended a factor
-        // four below the tolerance in as many steps as predicted (noslack)
-        // oversolve (see DnsCtl::stop_frac): general cycles with the
-        // multigrid Schur block -- not the six-node step (its tail keeps no
-        // record of the columns a solve needed; it runs one column anyway)
-        const bool over = h->oversolve && !sixing;
-        const double stop_frac = over ? h->oversolve_frac : 0.0;
-        int c_batch = over ? std::max(1, st->cpred)
-                      : st->noslack ? std::max(1, st->cpred - 1)
-                                    : std::max(2, st->cpred);
-        const int c_first = c_batch;
-        c_batch = std::min(c_batch, std::max(1, std::min(o.restart,
-                                                         dns::kMaxRestart)));
-        bool batch_ok = false;
-        const dns::CtlHeaderAcc *ha = h->hdr_host.p;
-        for (int attempt = 0; attempt < 2 && !batch_ok; ++attempt) {
-            if (attempt == 1) {
-                // restore the ring and try once more with a longer cycle
-                DNS_TRY(restore());
-                c_batch = std::min(c_batch + 2,
-                                   std::max(1, std::min(o.restart,
-                                                        dns::kMaxRestart)));
-                st->run_replayed += nb;
-            }
-            {
-                // checkpoint (first attempt) + reset of the accumulators
-                dns::CopyList cl = save;
-                if (saved) cl.count = 0;
-                const int gcp = (int)std::max<size_t>(
-                    128, std::min<size_t>(2048, h->ld / 1024));
-                hipLaunchKernelGGL(dns::k_batch_begin, gcp, dns::kBlock, 0,
-                                   h->stream, cl, h->ctl.p, stop_frac);
-                DNS_HIP(hipGetLastError());
-                saved = true;
-            }
-            h->pipeline_c = c_batch;
-            int prc = DNS_OK;
-            int q = 0;
-            while (q < nb && prc == DNS_OK) {
-                const int g = (nb - q >= kGroup)
-                                  ? kGroup
-                                  : ((kGroup >= 4 && nb - q >= kGroup / 2)
-                                         ? kGroup / 2
-                                         : 1);
-                prc = st->enqueue_group(cf, &o, g, true);
-                q += g;
-            }
-            h->pipeline_c = 0;
-            if (prc != DNS_OK) return prc;
-            // the call's last batch: the closing event and the true residual
-            // of the last step (for the record) ride behind it, so that ONE
-            // synchronisation -- the header's -- ends the call
-            fin_batch = false;
-            if (k + nb >= nsteps && !h->dist()) {
-                DNS_HIP(hipEventRecord(st->e1, h->stream));
-                DNS_LPR_SWITCH(
-                    h->K.lpr,
-                    hipLaunchKernelGGL(dns::k_resid_norm<L>, h->gridS,
-                                       dns::kBlock, 0, h->stream, h->n,
-                                       h->K.rowptr.p, h->K.colidx.p,
-                                       h->K.vals.p, st->xs[st->cur].p, st->b.p,
-                                       h->r.p, h->partR.p, (double *)nullptr,
-                                       dns::RowMap{0, h->n, 0, 0}));
-                hipLaunchKernelGGL(dns::k_sum_partials, 1, dns::kBlock, 0,
-                                   h->stream, h->partR.p, h->gridS, h->scal.p);
-                DNS_TRY(dns::d2h_pinned(h->scal_host.p, h->scal.p, 1,
-                                        h->stream));
-                fin_batch = true;
-            }
-            DNS_TRY(h->read_header());
-            if (st->env_debug)
-                fprintf(stderr,
-                        "[dns] batch at step %d (%d steps, attempt %d): c=%d "
-                        "solves=%d fail=%d iters=%d maxit=%d maxrel=%.2e "
-                        "need=%d prev=%.2e r0(last)=%.2e status=%d\n",
-                        k, nb, attempt, c_batch, ha->acc_solves, ha->acc_fail,
-                        ha->acc_iters, ha->acc_maxit, ha->acc_maxrel,
-                        ha->acc_maxneed, ha->acc_maxprev,
-                        ha->h.tol > 0 ? ha->h.beta / ha->h.tol : 0.0,
-                        ha->h.status);
-            if (ha->h.status == dns::kGsFallback) o.reorth = osync.reorth = 0;
-            batch_ok = ha->acc_fail == 0 && ha->h.status == DNS_OK;
-            if (!batch_ok) fin_batch = false;
-        }
-        if (!batch_ok) {
-            // last resort: the batch step by step from the checkpoint
-            if (over) DNS_TRY(h->set_stop_frac(0.0));
-            DNS_TRY(restore());
-            st->run_replayed += nb;
-            rc = sync_steps(nb);
-            if (rc == DNS_OK) DNS_TRY(st->prime_six(cf, false));
-            if (!st->six_ok && cf->carry_residual && rc == DNS_OK)
-                DNS_TRY(st->prime_carry(true));
-            st->cpred = std::max(1, h->last_iters) + 2;
-            st->noslack = false;
-            st->noslack_hold = 8;        // batches before it is tried again
-            st->batch_len = 8;
-            continue;
-        }
-        k += nb;
-        iters += ha->acc_iters;
-        st->cpred = ha->acc_maxit + 1;
-        // (a batch that needed its second attempt: the slack step stays for a
-        // few batches, so that a residual hovering at the tolerance does not
-        // cost a replay every other batch)
-        if (st->run_replayed > replayed_before) st->noslack_hold = 4;
-        if (st->noslack_hold > 0) --st->noslack_hold;
-        st->noslack = st->env_slack_adapt && st->noslack_hold == 0 &&
-                      ha->acc_maxrel > 0.0 &&
-                      ha->acc_maxrel < st->env_noslack_maxrel &&
-                      ha->acc_maxit <= c_batch;
-        if (over) {
-            const bool replayed = st->run_replayed > replayed_before;
-            int cnext = c_first;
-            bool trial = false;
-            if (replayed && !st->lowered_last && !st->spiked) {
-                // an established cycle length whose batch had to be replayed
-                // ONCE: a residual spike (one or two solves of a batch, then
-                // none for hundreds of steps at n = 2.8M) -- the replay has
-                // dealt with it, the cycle stays; twice in a row raises it
-                st->spiked = true;
-                cnext = c_first;
-            } else if (replayed || ha->acc_maxrel > h->oversolve_raise) {
-                // the cycle was too short (replayed) or ended close to the
-                // tolerance: one more column.  A cycle that had just been
-                // shortened: the next attempt waits twice as long (one
-                // column less is not a matter of margins: the warm start
-                // multiplies the final residuals of the last solves by its
-                // coefficients, and a cycle whose reduction does not beat
-                // that factor lets the start residuals grow step by step)
-                cnext = c_first + 1;
-                st->spiked = false;
-                if (st->lowered_last) {
-                    st->lower_backoff = std::min(1024, 2 * st->lower_backoff);
-                    st->lower_hold = st->lower_backoff;
-                } else {
-                    // (an established cycle length that failed once: a
-                    // residual spike -- back soon, on a trial batch)
-                    st->lower_hold = 4;
-                }
-            } else if (ha->acc_maxit < c_first) {
-                // every solve reached the floor (stop_frac x tol) before the
-                // end of the cycle: the columns behind that are no-ops
-                cnext = std::max(h->oversolve_cmin_eff(), ha->acc_maxit);
-            } else if (c_first > h->oversolve_cmin_eff() && st->lower_hold == 0 &&
-                       ha->acc_maxprev > 0.0 &&
-                       (ha->acc_maxprev < h->oversolve_lower ||
-                        (c_first == 2 && h->mg_two_for(1) &&
-                         !h->mg_two_for(2) && ha->acc_maxrel < 0.5))) {
-                // (second form: the one-column cycle applies TWO V-cycles
-                // where these two columns applied one each -- a different
-                // cycle, not this one cut short: what its first column left
-                // says little about it, so it is simply tried while the
-                // batch ended with a margin; a failed trial costs a replay
-                // of eight steps and doubles the wait for the next one)
-                // a decade below the tolerance in FRONT of the last column:
-                // try one column less, on a short batch (what a failed
-                // attempt replays)
-                cnext = c_first - 1;
-                trial = true;
-            }
-            if (!replayed) st->spiked = false;
-            st->lowered_last = trial;
-            if (st->lower_hold > 0) --st->lower_hold;
-            st->cpred = cnext;
-            st->noslack = false;
-            if (trial) st->batch_len = 4;     // (doubled below: 8 steps)
-        }
-        st->batch_len = std::min(32, 2 * st->batch_len);
-        h->last_iters = ha->h.total_it;
-        sp->iters = ha->h.total_it;
-        sp->status = ha->h.conv ? DNS_OK : DNS_NOT_CONVERGED;
-        sp->bnorm = ha->h.bnorm;
-        sp->est_relres =
-            ha->h.bnorm > 0 ? ha->h.resnorm / ha->h.bnorm : ha->h.resnorm;
-    }
-    if (h->oversolve && pipelined) DNS_TRY(h->set_stop_frac(0.0));
-    h->want_history = true;
+    over = h->oversolve && r.pipelined;
+    if (rc == DNS_OK) DNS_HIP(hipEventRecord(st->e0, h->stream));
+    while (rc == DNS_OK && r.pipelined && r.k < nsteps) rc = r.run_batch();
     st->run_captures = (int)(h->graph_captures - captures0);
     if (rc != DNS_OK && rc != DNS_NOT_CONVERGED) return rc;
-    if (fin_batch) {
-        // (event and residual were enqueued behind the last batch and have
-        // arrived with its header)
-        const double tr = std::sqrt(h->scal_host.p[0]);
-        sp->true_relres = sp->bnorm > 0 ? tr / sp->bnorm : tr;
-        h->spmv_count++;
-    } else {
-        DNS_HIP(hipEventRecord(st->e1, h->stream));
-        // true residual of the last step for the record: behind the closing
-        // event (not part of the stepping time), ONE synchronisation for both
-        if (nsteps > 0) {
-            double tr = 0.0;
-            DNS_TRY(h->true_residual(st->b.p, st->xs[st->cur].p, &tr));
-            sp->true_relres = sp->bnorm > 0 ? tr / sp->bnorm : tr;
-        } else {
-            DNS_HIP(hipEventSynchronize(st->e1));
-        }
-    }
-    float ms = 0.f;
-    DNS_HIP(hipEventElapsedTime(&ms, st->e0, st->e1));
-    if (device_seconds) *device_seconds = 1e-3 * ms;
-    if (total_iters) *total_iters = iters;
-    if (st->run_unconverged > 0) {
-        sp->status = DNS_NOT_CONVERGED;
-        return dns::fail(DNS_NOT_CONVERGED,
-                         "%d of %d time steps ended at maxiter without reaching "
-                         "the tolerance (first: step %d of this run); the state "
-                         "was advanced with the best iterates",
-                         st->run_unconverged, (int)nsteps, st->run_first_bad);
-    }
-    return DNS_OK;
+    return r.finish_run(device_seconds, total_iters);
 }
 
 int dns_imex_run(dns_imex *st, int32_t nsteps, const dns_imex_coeffs *cf,

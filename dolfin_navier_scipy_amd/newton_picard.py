@@ -442,23 +442,26 @@ class TrapezoidalStepper(object):
             else:
                 self.checkpoint()
                 self.set_pipeline(cycle)
-                if record:
-                    for kk in range(k, kend):
-                        one(kk)
-                else:
-                    # (uniform grid, no low-rank terms: the loop is the
-                    # library's)
-                    self.run(trange[k] - trange[k-1], lin_which, k, kend - k,
-                             newton, opts=opts, extrapolate=extrapolate)
-                acc = self.poll()
-                self.set_pipeline(0)
+                try:
+                    if record:
+                        for kk in range(k, kend):
+                            one(kk)
+                    else:
+                        # (uniform grid, no low-rank terms: the loop is the
+                        # library's)
+                        self.run(trange[k] - trange[k-1], lin_which, k,
+                                 kend - k, newton, opts=opts,
+                                 extrapolate=extrapolate)
+                    acc = self.poll()
+                finally:
+                    self.set_pipeline(0)
                 if os.environ.get('DNS_DEBUG'):
                     print('[sweep] steps {0}..{1} cycle {2}: {3}'.format(
                         k, kend, cycle, acc), file=sys.stderr)
                 if acc['fails'] == 0 and not over:
                     its, cycle = acc['iters'], max(2, acc['maxit'] + 1)
                 elif acc['fails'] == 0:
-                    # oversolve (as `dns_imex_run`, imex_capi.inc): every solve
+                    # oversolve (as csrc/batch_policy.hpp): every solve
                     # ran the `cycle` columns of the replayed graph.  The
                     # cycle grows when the batch ended close to the tolerance,
                     # shrinks to what was run when every solve reached the

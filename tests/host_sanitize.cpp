@@ -1,6 +1,7 @@
 // CPU-only sanitizer target for the HOST logic of the library (no HIP, no GPU):
 // hostcsr.hpp (SpGEMM, polynomial rows, transposes, slices), pair_host.hpp
-// (pair-format builder) and halo_host.hpp (partition, halo index lists) are
+// (pair-format builder), halo_host.hpp (partition, halo index lists) and
+// batch_policy.hpp (cycle and batch length of the pipelined batches) are
 // compiled as they are with
 //     g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover
 // and driven over a small saddle-point system with the structure of the
@@ -16,6 +17,7 @@
 #include <map>
 #include <vector>
 
+#include "../dolfin_navier_scipy_amd/csrc/batch_policy.hpp"
 #include "../dolfin_navier_scipy_amd/csrc/halo_host.hpp"
 #include "../dolfin_navier_scipy_amd/csrc/hostcsr.hpp"
 #include "../dolfin_navier_scipy_amd/csrc/pair_host.hpp"
@@ -437,7 +439,139 @@ static void test_misc(const HostCsr &F) {
     CHECK(Es.nrows == 0 && Es.nnz() == 0);
 }
 
+// every branch of the batch policy: state before, a batch that went through
+// (or the start-up / fallback), state after -- the expected values worked out
+// from the arithmetic as dns_imex_run had it inline
+static bool same(const dns::BatchPolicy &a, const dns::BatchPolicy &b) {
+    return a.cpred == b.cpred && a.noslack == b.noslack &&
+           a.noslack_hold == b.noslack_hold && a.lower_hold == b.lower_hold &&
+           a.lower_backoff == b.lower_backoff &&
+           a.lowered_last == b.lowered_last && a.spiked == b.spiked &&
+           a.batch_len == b.batch_len;
+}
+
+static void test_batch_policy() {
+    using dns::BatchPolicy;
+    // {cpred, noslack, noslack_hold, lower_hold, lower_backoff, lowered_last,
+    //  spiked, batch_len}
+    const BatchPolicy fresh;
+    CHECK(same(fresh, BatchPolicy{-1, false, 1, 0, 2, false, false, 8}));
+    // {cmin, raise, lower, two_one, slack_adapt, noslack_maxrel}
+    const dns::BatchParams P{1, 0.9, 0.25, false, true, 0.85};
+    const dns::BatchParams P2{2, 0.9, 0.25, false, true, 0.85};
+    const dns::BatchParams PT{1, 0.9, 0.25, true, true, 0.85};
+    const dns::BatchParams PN{1, 0.9, 0.25, false, false, 0.85};
+    const bool F = false, T = true;
+    struct Case {
+        const char *what;
+        BatchPolicy before;
+        dns::BatchOutcome r;   // {over, c_first, c, replayed, maxit, maxrel, maxprev}
+        dns::BatchParams p;
+        BatchPolicy after;
+    };
+    const Case cases[] = {
+        // slack step (no oversolve)
+        {"no slack: a margin below the bound", {4, F, 1, 0, 2, F, F, 8},
+         {F, 4, 4, F, 3, 0.5, 0.0}, P, {4, T, 0, 0, 2, F, F, 16}},
+        {"no slack: as many steps as the cycle", {4, F, 1, 0, 2, F, F, 8},
+         {F, 4, 4, F, 4, 0.5, 0.0}, P, {5, T, 0, 0, 2, F, F, 16}},
+        {"slack: batch maximum at the bound", {4, T, 0, 0, 2, F, F, 16},
+         {F, 3, 3, F, 3, 0.85, 0.0}, P, {4, F, 0, 0, 2, F, F, 32}},
+        {"slack: more steps than the cycle", {4, F, 0, 0, 2, F, F, 32},
+         {F, 4, 4, F, 5, 0.5, 0.0}, P, {6, F, 0, 0, 2, F, F, 32}},
+        {"slack: no residual recorded", {4, F, 0, 0, 2, F, F, 8},
+         {F, 4, 4, F, 3, 0.0, 0.0}, P, {4, F, 0, 0, 2, F, F, 16}},
+        {"slack: DNS_SLACK_ADAPT=0", {4, F, 0, 0, 2, F, F, 8},
+         {F, 4, 4, F, 3, 0.5, 0.0}, PN, {4, F, 0, 0, 2, F, F, 16}},
+        {"hold: a replayed batch keeps the slack step", {4, T, 0, 0, 2, F, F, 16},
+         {F, 3, 5, T, 4, 0.5, 0.0}, P, {5, F, 3, 0, 2, F, F, 32}},
+        {"hold: counts down", {5, F, 3, 0, 2, F, F, 32},
+         {F, 5, 5, F, 4, 0.5, 0.0}, P, {5, F, 2, 0, 2, F, F, 32}},
+        {"hold: runs out", {5, F, 1, 0, 2, F, F, 32},
+         {F, 5, 5, F, 4, 0.5, 0.0}, P, {5, T, 0, 0, 2, F, F, 32}},
+        // oversolve
+        {"spike: the first replay keeps the cycle", {2, F, 0, 0, 2, F, F, 16},
+         {T, 2, 4, T, 3, 0.5, 0.1}, P, {2, F, 3, 0, 2, F, T, 32}},
+        {"spike twice: raise", {2, F, 3, 0, 2, F, T, 32},
+         {T, 2, 4, T, 3, 0.5, 0.1}, P, {3, F, 3, 3, 2, F, F, 32}},
+        {"spike: cleared by a batch without a replay", {2, F, 0, 0, 2, F, T, 16},
+         {T, 2, 2, F, 2, 0.5, 0.3}, P, {2, F, 0, 0, 2, F, F, 32}},
+        {"raise: ended close to the tolerance", {2, F, 0, 0, 2, F, F, 8},
+         {T, 2, 2, F, 2, 0.95, 0.3}, P, {3, F, 0, 3, 2, F, F, 16}},
+        {"floor: down to what was run", {4, F, 0, 0, 2, F, F, 8},
+         {T, 4, 4, F, 2, 0.01, 0.001}, P, {2, F, 0, 0, 2, F, F, 16}},
+        {"floor: not below cmin", {4, F, 0, 0, 2, F, F, 8},
+         {T, 4, 4, F, 1, 0.01, 0.001}, P2, {2, F, 0, 0, 2, F, F, 16}},
+        {"trial: a decade below in front of the last column",
+         {3, F, 0, 0, 2, F, F, 32}, {T, 3, 3, F, 3, 0.5, 0.1}, P,
+         {2, F, 0, 0, 2, T, F, 8}},
+        {"trial, second form: two V-cycles in one column",
+         {2, F, 0, 0, 2, F, F, 32}, {T, 2, 2, F, 2, 0.4, 0.5}, PT,
+         {1, F, 0, 0, 2, T, F, 8}},
+        {"second form: only with two V-cycles", {2, F, 0, 0, 2, F, F, 32},
+         {T, 2, 2, F, 2, 0.4, 0.5}, P, {2, F, 0, 0, 2, F, F, 32}},
+        {"second form: only with a margin", {2, F, 0, 0, 2, F, F, 32},
+         {T, 2, 2, F, 2, 0.6, 0.5}, PT, {2, F, 0, 0, 2, F, F, 32}},
+        {"no trial while held", {3, F, 0, 2, 2, F, F, 32},
+         {T, 3, 3, F, 3, 0.5, 0.1}, P, {3, F, 0, 1, 2, F, F, 32}},
+        {"no trial at cmin", {2, F, 0, 0, 2, F, F, 32},
+         {T, 2, 2, F, 2, 0.5, 0.1}, P2, {2, F, 0, 0, 2, F, F, 32}},
+        {"no trial without a residual in front", {3, F, 0, 0, 2, F, F, 32},
+         {T, 3, 3, F, 3, 0.5, 0.0}, P, {3, F, 0, 0, 2, F, F, 32}},
+        {"failed trial: the back-off doubles", {2, F, 0, 0, 2, T, F, 8},
+         {T, 2, 4, T, 3, 0.5, 0.1}, P, {3, F, 3, 3, 4, F, F, 16}},
+        {"trial ended close: the back-off doubles", {2, F, 0, 0, 2, T, F, 8},
+         {T, 2, 2, F, 2, 0.95, 0.3}, P, {3, F, 0, 3, 4, F, F, 16}},
+        {"back-off capped at 1024", {2, F, 0, 0, 600, T, F, 8},
+         {T, 2, 4, T, 3, 0.5, 0.1}, P, {3, F, 3, 1023, 1024, F, F, 16}},
+        {"back-off stays at 1024", {2, F, 0, 0, 1024, T, F, 8},
+         {T, 2, 4, T, 3, 0.5, 0.1}, P, {3, F, 3, 1023, 1024, F, F, 16}},
+    };
+    for (const Case &c : cases) {
+        BatchPolicy pol = c.before;
+        pol.after_batch(c.r, c.p);
+        if (!same(pol, c.after)) {
+            fprintf(stderr, "batch policy: %s\n", c.what);
+            ++g_fail;
+        }
+    }
+    // start-up: a stepper without its history steps synchronously first
+    CHECK(fresh.startup_steps(0) == 5 && fresh.startup_steps(3) == 2);
+    CHECK(fresh.startup_steps(4) == 2 && fresh.startup_steps(5) == 2);
+    BatchPolicy pol{3, T, 0, 5, 8, T, T, 32};
+    CHECK(pol.startup_steps(5) == 0 && pol.startup_steps(4) == 2);
+    pol.after_startup(3);
+    CHECK(same(pol, BatchPolicy{4, F, 1, 5, 8, T, T, 8}));
+    pol.after_startup(-1);
+    CHECK(pol.cpred == 2);
+    // fallback: a batch that failed twice and ran step by step
+    pol = BatchPolicy{3, T, 0, 5, 8, T, T, 32};
+    pol.after_fallback(5);
+    CHECK(same(pol, BatchPolicy{7, F, 8, 5, 8, T, T, 8}));
+    pol.after_fallback(0);
+    CHECK(pol.cpred == 3);
+    // first attempt's cycle (oversolve / no slack step / slack step) and the
+    // second attempt's
+    CHECK(fresh.cycle(true) == 1 && fresh.cycle(false) == 2);
+    CHECK((BatchPolicy{3, F}.cycle(true) == 3));
+    CHECK((BatchPolicy{3, F}.cycle(false) == 3));
+    CHECK((BatchPolicy{4, T}.cycle(false) == 3));
+    CHECK((BatchPolicy{1, T}.cycle(false) == 1));
+    CHECK((BatchPolicy{4, T}.cycle(true) == 4));   // (no slack step to drop)
+    CHECK(BatchPolicy::longer(3, 64) == 5 && BatchPolicy::longer(63, 64) == 64);
+    CHECK(BatchPolicy::longer(1, 1) == 1);
+    // batch length 8 -> 16 -> 32 while the predictions hold
+    pol = fresh;
+    pol.after_startup(2);
+    const dns::BatchOutcome good{F, 3, 3, F, 2, 0.5, 0.0};
+    for (int len : {16, 32, 32}) {
+        pol.after_batch(good, P);
+        CHECK(pol.batch_len == len);
+    }
+}
+
 int main() {
+    test_batch_policy();
     for (const auto &dims : {std::pair<int, int>{7, 5}, {12, 9}, {3, 2}}) {
         HostCsr F, J;
         build_system(dims.first, dims.second, F, J);
