@@ -2,11 +2,14 @@
 #pragma once
 #include "batch_policy.hpp"
 #include "convection.hpp"
+#include "ring.hpp"
 #include "solver.hpp"
 #include "trap.hpp"
 #include "step_kernels.hpp"
 
-struct dns_imex {
+// (dns::Ring: the ring indices of xs, nsol, and whether the work buffer holds
+// the warm start already)
+struct dns_imex : dns::Ring {
     dns_saddle *sys = nullptr;
     dns::CsrDev R1;                // all rows, or this rank's (partitioned)
     dns::HostCsr R1h;              // host copy (row blocks are cut from it)
@@ -34,32 +37,13 @@ struct dns_imex {
     } part;
     int ensure_partition();
     int gather_state();
-    // two solution-space vectors [v; p~] (current, previous) + work
     // current and the four solutions before it, work
     dns::DevBuf<double> xs[6];
     // checkpoint of a pipelined batch: the ring (the work buffer too: it
     // holds the warm start), the convection history and, when residuals are
     // carried, the last right-hand side and residual and the two residuals
-    // of the six-node / partitioned step.  `add` records each buffer once,
-    // as a pair in both directions: k_batch_begin copies it one way to save
-    // (with the reset of the batch accumulators; `copy` false: that alone)
-    // and the other way to restore
-    struct Checkpoint {
-        dns::DevBuf<double> ring[6], nfc[2], rc6[2], b, rcarry;
-        dns::CopyList fwd{}, back{};
-        static_assert(6 + 2 + 2 + 2 <= sizeof(fwd.n) / sizeof(fwd.n[0]));
-        void clear() { fwd.count = back.count = 0; }
-        int add(double *live, dns::DevBuf<double> &copy, size_t n);
-        int save(const dns_saddle *h, bool copy, double stop_frac) const;
-        int restore(const dns_saddle *h) const;
-    } ck;
-    int cur = 0, prev = 1, pprev = 2, p3 = 3, p4 = 4, work = 5;
-    int nsol = 0;                  // how many valid solution vectors (0..5)
-    // the work buffer already holds this step's warm start (written by the
-    // previous step's tail kernel, dns::TailExtrap) for the coefficient set
-    // `pre_sig` = extrap_sig(nsol, order)
-    bool pre_ok = false;
-    int pre_sig = -1;
+    // of the six-node / partitioned step
+    dns::Checkpoint ck;
     // residual carry-over (dns_imex_coeffs.carry_residual, k_step_front MODE 2):
     // K xs[i] per ring slot and the velocity residual of the previous solve;
     // `b_valid`: b holds the right-hand side whose solution is xs[cur];
@@ -93,54 +77,8 @@ struct dns_imex {
     int prime_dcells(const dns_solve_opts *o);
     uint64_t six_conv_gen = 0;     // conv->dbc_gen the cell values belong to
     int prime_six(const dns_imex_coeffs *cf, bool keep_r);
-    // coefficients of the polynomial warm start from `nsol_` solutions
-    static constexpr int kExtrapFit35 = 13;
-    static int extrap_coeffs(int nsol_, int order, double e[5]) {
-        e[0] = 1.0;
-        e[1] = e[2] = e[3] = e[4] = 0.0;
-        if (nsol_ >= 5 && order == kExtrapFit35) {
-            // value at the new time of the CUBIC least-squares fit through the
-            // last FIVE solutions.  A warm start multiplies the final
-            // residuals of the solves it is built from by its coefficients:
-            // sqrt(sum c^2) = 4.9 here against 15.8 for the interpolating
-            // quartic (8.3 cubic), for 1.8 x the cubic's truncation error --
-            // once the start residual consists of those residuals rather
-            // than of the truncation error (dt <= 1e-3: scripts/
-            // recycle_probe.py) that is the better trade
-            e[0] = 3.2; e[1] = -2.8; e[2] = -0.8; e[3] = 2.2; e[4] = -0.8;
-            return 3;
-        }
-        if (order == kExtrapFit35) order = 3;      // (history still filling)
-        if (nsol_ >= 5 && order >= 4) {
-            e[0] = 5.0; e[1] = -10.0; e[2] = 10.0; e[3] = -5.0; e[4] = 1.0;
-            return 4;
-        }
-        if (nsol_ >= 4 && order >= 3) {
-            e[0] = 4.0; e[1] = -6.0; e[2] = 4.0; e[3] = -1.0;
-            return 3;
-        }
-        if (nsol_ >= 3 && order >= 2) {
-            e[0] = 3.0; e[1] = -3.0; e[2] = 1.0;
-            return 2;
-        }
-        if (nsol_ >= 2 && order >= 1) {
-            e[0] = 2.0; e[1] = -1.0;
-            return 1;
-        }
-        return 0;
-    }
     long steps_enqueued = 0;       // counts step_device calls (graph replay
                                    // must advance the host state itself)
-    void rotate_host() {           // p4 <- p3 <- pprev <- prev <- cur <- new
-        const int old = p4;
-        p4 = p3;
-        p3 = pprev;
-        pprev = prev;
-        prev = cur;
-        cur = work;
-        work = old;
-        if (nsol < 5) nsol++;
-    }
     dns::DevBuf<double> nfc[2];
     int nc = 0, no = 1;
     dns::DevBuf<double> g, gp, b;
@@ -201,24 +139,21 @@ struct dns_imex {
         return left >= g ? g : (g >= 4 && left >= g / 2) ? g / 2 : 1;
     }
     struct HostState {
-        int cur, prev, pprev, p3, p4, work, nsol, nc, no, tab_pos;
+        dns::Ring ring;
+        int nc, no, tab_pos;
         long steps_enqueued;
-        bool pre_ok;
-        int pre_sig;
         bool b_valid, carry_ok, six_ok, dcells_ok;
     };
     HostState host_state() const {
-        return {cur, prev, pprev, p3, p4, work, nsol, nc, no, tab_pos,
-                steps_enqueued, pre_ok, pre_sig, b_valid, carry_ok, six_ok,
-                dcells_ok};
+        return {*this, nc, no, tab_pos, steps_enqueued, b_valid, carry_ok,
+                six_ok, dcells_ok};
     }
     void set_host_state(const HostState &s) {
-        cur = s.cur; prev = s.prev; pprev = s.pprev; p3 = s.p3; p4 = s.p4;
-        work = s.work; nsol = s.nsol; nc = s.nc; no = s.no;
+        static_cast<dns::Ring &>(*this) = s.ring;
+        nc = s.nc;
+        no = s.no;
         tab_pos = s.tab_pos;
         steps_enqueued = s.steps_enqueued;
-        pre_ok = s.pre_ok;
-        pre_sig = s.pre_sig;
         b_valid = s.b_valid;
         carry_ok = s.carry_ok;
         six_ok = s.six_ok;

@@ -100,11 +100,11 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
     const bool fused = !h->dist() && !h->streams(h->K);
     // the previous step's tail kernel has left this step's warm start in the
     // work buffer (same coefficient set)?
-    const int my_sig = 8 * std::min(nsol, 5) + std::min(cf->extrapolate_x0, 7);
     // (row-partitioned with the stepper's own halo plan: the tails of the
     // partitioned cycle extrapolate over own entries and halo alike)
     const bool can_pre = !h->dist() || part.on;
-    const bool use_pre = can_pre && pre_ok && pre_sig == my_sig;
+    const bool use_pre = can_pre && pre_ok &&
+                         pre_sig == dns::extrap_sig(nsol, cf->extrapolate_x0);
     // residual carry-over: a PRE step whose ring of K x products is current
     // six-node step: pipelined GMRES steps of the fused path whose warm start,
     // cell values and residuals the step before (or prime_six) has left
@@ -152,7 +152,7 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
         }
         if (fused) {
             double ee[5];
-            extrap_coeffs(nsol, ex, ee);
+            dns::extrap_coeffs(nsol, ex, ee);
             const double e_c = ee[0], e_p = ee[1], e_pp = ee[2], e_p3 = ee[3],
                          e_p4 = ee[4];
             // front: convection cells || (x0, K x0, R1 v) -- one launch; back:
@@ -213,34 +213,18 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
         const bool stream_rows = rows_only && h->streams(R1);
         // (the kernels below carry the interpolating coefficients: the
         // least-squares fit, whose warm start the tail kernels write, falls
-        // back to the cubic where a step has to form x0 itself)
-        const int exq = cf->extrapolate_x0 == dns_imex::kExtrapFit35
-                            ? 3 : cf->extrapolate_x0;
+        // back to the cubic where a step has to form x0 itself.  A negative
+        // extrapolate_x0 gives the LINEAR start here but x0 = x_c on the
+        // fused path (extrap_coeffs): kept as it is, not yet reconciled)
+        const int exq = cf->extrapolate_x0 == dns::kExtrapFit35 ? 3
+                        : cf->extrapolate_x0 < 0                ? 1
+                                                                : cf->extrapolate_x0;
         auto warm_start = [&]() -> int {
-            if (use_pre) {
-                // the previous step's tail kernel has left x0 in `x`
-            } else if (nsol >= 5 && exq >= 4) {
-                hipLaunchKernelGGL(dns::k_lincomb5, dns::grid_for_elems(n),
-                                   dns::kBlock, 0, s, n, xs[cur].p, xs[prev].p,
-                                   xs[pprev].p, xs[p3].p, xs[p4].p, x);
-            } else if (nsol >= 4 && exq >= 3) {
-                hipLaunchKernelGGL(dns::k_lincomb4, dns::grid_for_elems(n),
-                                   dns::kBlock, 0, s, n, xs[cur].p, xs[prev].p,
-                                   xs[pprev].p, xs[p3].p, x);
-            } else if (nsol >= 3 && exq >= 2) {
-                hipLaunchKernelGGL(dns::k_lincomb3, dns::grid_for_elems(n),
-                                   dns::kBlock, 0, s, n, xs[cur].p, xs[prev].p,
-                                   xs[pprev].p, x);
-            } else if (nsol >= 2 && exq) {
-                hipLaunchKernelGGL(dns::k_lincomb2, dns::grid_for_elems(n),
-                                   dns::kBlock, 0, s, n, 2.0, xs[cur].p, -1.0,
-                                   xs[prev].p, x);
-            } else {
-                DNS_HIP(hipMemcpyAsync(x, xs[cur].p, (size_t)n * sizeof(double),
-                                       hipMemcpyDeviceToDevice, s));
-            }
-            DNS_HIP(hipGetLastError());
-            return DNS_OK;
+            // (use_pre: the previous step's tail kernel has left x0 in `x`)
+            if (use_pre) return DNS_OK;
+            double e[5];
+            return dns::enqueue_extrap(dns::extrap_coeffs(nsol, exq, e), xs,
+                                       *this, x, n, s);
         };
         if (dfront && rows_only) {
             // (the tail of the step before has left the cell values of this
@@ -363,7 +347,7 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
         h->tail_extrap = dns::TailExtrap{};
         if (can_pre) {
             double en[5];
-            extrap_coeffs(next_nsol, cf->extrapolate_x0, en);
+            dns::extrap_coeffs(next_nsol, cf->extrapolate_x0, en);
             h->tail_extrap = dns::TailExtrap{xs[cur].p, xs[prev].p, xs[pprev].p,
                                              xs[p3].p,  en[0], en[1], en[2],
                                              en[3],     en[4], xs[p4].p};
@@ -441,7 +425,7 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
         DNS_TRY(grc);
         if (can_pre && !six) {
             pre_ok = true;
-            pre_sig = 8 * next_nsol + std::min(cf->extrapolate_x0, 7);
+            pre_sig = dns::extrap_sig(next_nsol, cf->extrapolate_x0);
         }
         // row-partitioned: the next step's right-hand side, convection and
         // warm start read this rank's rows and their halo
@@ -462,7 +446,7 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
         DNS_TRY(h->true_residual(b.p, x, &tr));
         st->true_relres = st->bnorm > 0 ? tr / st->bnorm : tr;
     }
-    rotate_host();
+    rotate();
     steps_enqueued++;
     last_pscale = cf->pscale;
     b_valid = true;
@@ -503,27 +487,13 @@ int dns_imex::prime_six(const dns_imex_coeffs *cf, bool keep_r) {
         h->drop_graphs();
         DNS_TRY(h->Wcols.alloc((size_t)m * ld));
     }
+    // (nsol == 5 here.  With kExtrapFit35 this launches the QUARTIC, not the
+    // least-squares fit the tails write: kept as it is, not yet reconciled)
     double e[5];
-    extrap_coeffs(nsol, cf->extrapolate_x0, e);
-    double *out = x0buf[work & 1].p;
-    const int n = h->n;
-    if (e[4] != 0.0)
-        hipLaunchKernelGGL(dns::k_lincomb5, dns::grid_for_elems(n), dns::kBlock,
-                           0, h->stream, n, xs[cur].p, xs[prev].p, xs[pprev].p,
-                           xs[p3].p, xs[p4].p, out);
-    else if (e[3] != 0.0)
-        hipLaunchKernelGGL(dns::k_lincomb4, dns::grid_for_elems(n), dns::kBlock,
-                           0, h->stream, n, xs[cur].p, xs[prev].p, xs[pprev].p,
-                           xs[p3].p, out);
-    else if (e[2] != 0.0)
-        hipLaunchKernelGGL(dns::k_lincomb3, dns::grid_for_elems(n), dns::kBlock,
-                           0, h->stream, n, xs[cur].p, xs[prev].p, xs[pprev].p,
-                           out);
-    else
-        hipLaunchKernelGGL(dns::k_lincomb2, dns::grid_for_elems(n), dns::kBlock,
-                           0, h->stream, n, e[0], xs[cur].p, e[1], xs[prev].p,
-                           out);
-    DNS_HIP(hipGetLastError());
+    const int order = cf->extrapolate_x0 == dns::kExtrapFit35
+                          ? 4 : dns::extrap_coeffs(nsol, cf->extrapolate_x0, e);
+    DNS_TRY(dns::enqueue_extrap(order, xs, *this, x0buf[work & 1].p, h->n,
+                                h->stream));
     if (conv) {
         conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
         DNS_TRY(conv->enqueue_cells(xs[cur].p, h->stream));
@@ -703,11 +673,11 @@ int dns_imex::enqueue_group(const dns_imex_coeffs *cf, const dns_solve_opts *o,
         // the graph existed: move the host's view of the ring along
         for (int g = 0; g < group; ++g) {
             if (conv) std::swap(nc, no);
-            rotate_host();
+            rotate();
         }
         // (replayed steps are fused GMRES steps: they leave a warm start)
         pre_ok = true;
-        pre_sig = 8 * std::min(nsol, 5) + std::min(cf->extrapolate_x0, 7);
+        pre_sig = dns::extrap_sig(nsol, cf->extrapolate_x0);
         steps_enqueued += group;
         if (tables()) tab_pos += group;
         b_valid = true;       // (carry_ok is part of the key: it stays as is)
@@ -782,7 +752,7 @@ int dns_imex::prepare_graphs(const dns_imex_coeffs *cf,
     for (int c = 1; c <= chi; ++c) {
         h->pipeline_c = c;
         set_host_state(s0);
-        for (int r = 0; r < (s0.pre_ok ? 6 : 7); ++r) {
+        for (int r = 0; r < (s0.ring.pre_ok ? 6 : 7); ++r) {
             for (int gsz : {big, group_for(big / 2)}) {
                 if (gsz <= 1) continue;
                 const HostState sr = host_state();
@@ -795,40 +765,6 @@ int dns_imex::prepare_graphs(const dns_imex_coeffs *cf,
     }
     prepared_sig = sig;
     return DNS_OK;
-}
-
-// k_batch_begin over the checkpoint's buffers (`ctl`: and the reset of the
-// batch accumulators)
-static int batch_begin(const dns_saddle *h, const dns::CopyList &cl,
-                       dns::DnsCtl *ctl, double stop_frac) {
-    const int gcp = (int)std::max<size_t>(
-        128, std::min<size_t>(2048, h->ld / 1024));
-    hipLaunchKernelGGL(dns::k_batch_begin, gcp, dns::kBlock, 0, h->stream, cl,
-                       ctl, stop_frac);
-    DNS_HIP(hipGetLastError());
-    return DNS_OK;
-}
-
-int dns_imex::Checkpoint::add(double *live, dns::DevBuf<double> &copy,
-                              size_t n) {
-    if (copy.n < n) DNS_TRY(copy.alloc(n));
-    const int q = fwd.count++;
-    back.count = fwd.count;
-    fwd.src[q] = back.dst[q] = live;
-    back.src[q] = fwd.dst[q] = copy.p;
-    fwd.n[q] = back.n[q] = (int)n;
-    return DNS_OK;
-}
-
-int dns_imex::Checkpoint::save(const dns_saddle *h, bool copy,
-                               double stop_frac) const {
-    dns::CopyList l = fwd;
-    if (!copy) l.count = 0;
-    return batch_begin(h, l, h->ctl.p, stop_frac);
-}
-
-int dns_imex::Checkpoint::restore(const dns_saddle *h) const {
-    return batch_begin(h, back, nullptr, 0.0);
 }
 
 // one dns_imex_run call: what its pieces share
@@ -922,28 +858,24 @@ int ImexRun::run_batch() {
     const bool dcar = h->dist() && st->part.on && cf->carry_residual != 0 &&
                       st->rc6[0].p && st->rc6[1].p;
     const bool carrying = cf->carry_residual != 0 && st->carry_ok;
-    dns_imex::Checkpoint &ck = st->ck;   // (saved by the first attempt)
+    dns::Checkpoint &ck = st->ck;        // (saved by the first attempt)
     ck.clear();
-    const int ring[6] = {st->cur, st->prev, st->pprev, st->p3, st->p4,
-                         st->work};
-    for (int q = 0; q < 6; ++q)
-        DNS_TRY(ck.add(st->xs[ring[q]].p, ck.ring[q], h->ld));
+    for (int q : {st->cur, st->prev, st->pprev, st->p3, st->p4, st->work})
+        DNS_TRY(ck.add(st->xs[q].p, h->ld));
     if (st->conv)
-        for (int q = 0; q < 2; ++q)
-            DNS_TRY(ck.add(st->nfc[q].p, ck.nfc[q], h->nv));
+        for (int q = 0; q < 2; ++q) DNS_TRY(ck.add(st->nfc[q].p, h->nv));
     if ((sixing || dcar) && cf->carry_residual)
-        for (int q = 0; q < 2; ++q)
-            DNS_TRY(ck.add(st->rc6[q].p, ck.rc6[q], h->nv));
+        for (int q = 0; q < 2; ++q) DNS_TRY(ck.add(st->rc6[q].p, h->nv));
     if (carrying) {
-        DNS_TRY(ck.add(st->b.p, ck.b, h->ld));
-        DNS_TRY(ck.add(st->rcarry.p, ck.rcarry, h->nv));
+        DNS_TRY(ck.add(st->b.p, h->ld));
+        DNS_TRY(ck.add(st->rcarry.p, h->nv));
     }
     const dns_imex::HostState hs0 = st->host_state();
     // back to the checkpoint, then what derives from it: K x products of the
     // ring, device step counter, cell values (not in the ring), the six-node
     // warm start and cell values (the counter is back at the first step)
     auto restore = [&]() -> int {
-        DNS_TRY(ck.restore(h));
+        DNS_TRY(ck.restore(h->stream));
         st->set_host_state(hs0);
         if (carrying) DNS_TRY(st->prime_carry(false));
         if (st->tables()) DNS_TRY(st->sync_counter());
@@ -968,7 +900,8 @@ int ImexRun::run_batch() {
             st->run_replayed += nb;
             replayed = true;
         }
-        DNS_TRY(ck.save(h, attempt == 0, over ? h->oversolve_frac : 0.0));
+        DNS_TRY(ck.save(h->stream, h->ctl.p, over ? h->oversolve_frac : 0.0,
+                        attempt == 0));
         h->pipeline_c = c;
         for (int q = 0, g = 0; q < nb; q += g) {
             g = st->group_for(nb - q);
@@ -1176,12 +1109,7 @@ static int dns_imex_set_state_impl(dns_imex *st, const double *v_c, const double
     dns_saddle *h = st->sys;
     DNS_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    st->cur = 0;
-    st->prev = 1;
-    st->pprev = 2;
-    st->p3 = 3;
-    st->p4 = 4;
-    st->work = 5;
+    st->reset(1);
     for (int i = 0; i < 6; ++i) DNS_TRY(st->xs[i].zero(s));
     DNS_TRY(st->xs[0].upload(v_c, (size_t)h->nv, s));
     if (ptilde_c)
@@ -1189,8 +1117,6 @@ static int dns_imex_set_state_impl(dns_imex *st, const double *v_c, const double
                                s));
     for (int q = 0; q < 2; ++q)
         if (st->rc6[q].p) DNS_TRY(st->rc6[q].zero(s));   // a new trajectory
-    st->nsol = 1;
-    st->pre_ok = false;
     st->b_valid = false;
     st->carry_ok = false;
     st->six_ok = false;

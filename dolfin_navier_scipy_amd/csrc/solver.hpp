@@ -16,6 +16,7 @@
 #include "hostcsr.hpp"
 #include "kernels.hpp"
 #include "pair.hpp"
+#include "ring.hpp"
 
 namespace dns {
 
@@ -38,6 +39,31 @@ inline int grid_for_rows(int nrows, int lpr) {
 inline int grid_for_elems(int64_t n) {
     int64_t g = (n + kBlock - 1) / kBlock;
     return (int)std::max<int64_t>(1, std::min<int64_t>(g, 2048));
+}
+
+// out = warm start of order 4 / 3 / 2 / 1 from the ring's last solutions --
+// the interpolating coefficients of extrap_coeffs, k_lincomb5 / 4 / 3 / 2
+// (bicgstab_kernels.hpp) -- or, order 0, a copy of the current solution
+inline int enqueue_extrap(int order, const DevBuf<double> xs[6], const Ring &r,
+                          double *out, int n, hipStream_t s) {
+    const double *c = xs[r.cur].p, *p = xs[r.prev].p, *pp = xs[r.pprev].p;
+    const int g = grid_for_elems(n);
+    if (order >= 4)
+        hipLaunchKernelGGL(k_lincomb5, g, kBlock, 0, s, n, c, p, pp,
+                           xs[r.p3].p, xs[r.p4].p, out);
+    else if (order == 3)
+        hipLaunchKernelGGL(k_lincomb4, g, kBlock, 0, s, n, c, p, pp,
+                           xs[r.p3].p, out);
+    else if (order == 2)
+        hipLaunchKernelGGL(k_lincomb3, g, kBlock, 0, s, n, c, p, pp, out);
+    else if (order == 1)
+        hipLaunchKernelGGL(k_lincomb2, g, kBlock, 0, s, n, 2.0, c, -1.0, p,
+                           out);
+    else
+        DNS_HIP(hipMemcpyAsync(out, c, (size_t)n * sizeof(double),
+                               hipMemcpyDeviceToDevice, s));
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
 }
 
 inline int CsrDev::upload(const dns_csr *a, hipStream_t s) {

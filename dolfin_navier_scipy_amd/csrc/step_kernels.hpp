@@ -768,6 +768,51 @@ k_batch_begin(CopyList cl, DnsCtl *ctl, double stop_frac) {
     }
 }
 
+// Checkpoint of a pipelined batch (dns_imex_run, dns_trap_checkpoint): `add`
+// copies a live buffer into a buffer of the checkpoint's own (allocated when
+// it grows: call it outside a stream capture) and records the pair in both
+// directions.  save() is ONE k_batch_begin launch over the list (with `ctl`:
+// and the reset of the batch accumulators; `copy` false: that alone),
+// restore() the same launch with the list reversed and no control block.
+struct Checkpoint {
+    static constexpr int kMax = sizeof(CopyList::n) / sizeof(CopyList::n[0]);
+    DevBuf<double> buf[kMax];
+    CopyList fwd{}, back{};
+    size_t nmax = 0;                   // (sizes the grid: the ring's ld)
+    void clear() {
+        fwd.count = back.count = 0;
+        nmax = 0;
+    }
+    int add(double *live, size_t n) {
+        const int q = fwd.count;
+        if (q >= kMax) return fail(DNS_ERR_BAD_ARGUMENT, "checkpoint full");
+        if (buf[q].n < n) DNS_TRY(buf[q].alloc(n));
+        fwd.count = back.count = q + 1;
+        fwd.src[q] = back.dst[q] = live;
+        back.src[q] = fwd.dst[q] = buf[q].p;
+        fwd.n[q] = back.n[q] = (int)n;
+        nmax = std::max(nmax, n);
+        return DNS_OK;
+    }
+    int save(hipStream_t s, DnsCtl *ctl = nullptr, double stop_frac = 0.0,
+             bool copy = true) const {
+        CopyList l = fwd;
+        if (!copy) l.count = 0;
+        return launch(l, s, ctl, stop_frac);
+    }
+    int restore(hipStream_t s) const { return launch(back, s, nullptr, 0.0); }
+
+  private:
+    int launch(const CopyList &l, hipStream_t s, DnsCtl *ctl,
+               double stop_frac) const {
+        const int g = (int)std::max<size_t>(
+            128, std::min<size_t>(2048, nmax / 1024));
+        hipLaunchKernelGGL(k_batch_begin, g, kBlock, 0, s, l, ctl, stop_frac);
+        DNS_HIP(hipGetLastError());
+        return DNS_OK;
+    }
+};
+
 // ---------------------------------------------------------------------------
 // Front of a ROW-PARTITIONED IMEX step in the latency regime: for this rank's
 // rows of K (velocity rows, then pressure rows; RowMap) ONE launch forms

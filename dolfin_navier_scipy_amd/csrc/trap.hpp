@@ -16,7 +16,9 @@
 #include <mutex>
 #include "convection.hpp"
 #include "halo.hpp"
+#include "ring.hpp"
 #include "solver.hpp"
+#include "step_kernels.hpp"
 
 namespace dns {
 
@@ -114,14 +116,15 @@ k_trap_diff(int n, const double *__restrict__ x, const double *__restrict__ y,
 
 }  // namespace dns
 
-struct dns_trap {
+// (dns::Ring: the ring indices of xs, nsol, and whether the work buffer
+// holds the warm start already -- written by the tail kernel of the step
+// before, for the step size `pre_dt`)
+struct dns_trap : dns::Ring {
     dns_saddle *sys = nullptr;
     dns_conv *conv = nullptr;
     int nslots = 0;
     dns::DevBuf<double> mvals, avals, nn_vals;
     dns::DevBuf<double> xs[6];                 // ring of [v; p~] solutions
-    int cur = 0, prev = 1, pprev = 2, p3 = 3, p4 = 4, work = 5;
-    int nsol = 0;
     dns::DevBuf<double> fv, fp, fvn_n, rhsbc, rhscon, b, dtmp, mtmp;
     dns::DevBuf<double> traj[2];
     // asynchronous export of trajectory slots to the host (the "async writer"
@@ -152,6 +155,7 @@ struct dns_trap {
     int upd_slot = 0, upd_stride = 0;
     static constexpr int kUpdSlots = 128;
     int flush_updnorm();
+    int collect_updnorm();                     // updnorm += what the device holds
     // the update norm of the last pipelined step, not launched yet: the
     // element launch of the next step carries it (dns::UpdJob); whoever
     // reads its results first (the partials, the trajectory slot) launches
@@ -181,11 +185,6 @@ struct dns_trap {
     dns::DevBuf<double> fv_tab, fp_tab, mbc_tab;
     bool have_fv_tab = false, have_fp_tab = false, have_mbc_tab = false;
     int cur_slot = 0;                          // time instance of xs[cur]
-    // the work buffer holds this step's warm start already: the tail kernel of
-    // the step before wrote it (dns::TailExtrap) for `pre_sig` = 8 nsol + order
-    // and the step size `pre_dt`
-    bool pre_ok = false;
-    int pre_sig = -1;
     double pre_dt = 0.0;
     // position of every non-zero of F in the assembled K (un-partitioned
     // handle): the assembly kernel writes both
@@ -227,12 +226,13 @@ struct dns_trap {
                   int newton, int extrapolate_x0, const dns_solve_opts *opts,
                   dns_solve_stats *stats, const Feedback *fb);
     // checkpoint of the ring (a pipelined batch that did not converge within
-    // its cycle length is repeated from here): the three solutions behind
+    // its cycle length is repeated from here): the five solutions up to
     // `cur`, the host's bookkeeping; N_c / f_c are re-assembled on restore
-    dns::DevBuf<double> ck[5];
+    dns::Checkpoint ck;
     struct {
         bool valid = false;
-        int nsol = 0, cur_slot = 0;
+        dns::Ring ring;
+        int cur_slot = 0;
         double last_dt = 0.0, updnorm = 0.0;
     } ckh;
 };

@@ -104,6 +104,17 @@ int dns_trap::flush_updnorm() {
     return DNS_OK;
 }
 
+// the part of the update norm still on the device, added to `updnorm`
+// (synchronises the stream)
+int dns_trap::collect_updnorm() {
+    double dd = 0.0;
+    DNS_TRY(flush_updnorm());
+    DNS_TRY(updnorm_dev.download(&dd, 1, sys->stream));
+    DNS_HIP(hipStreamSynchronize(sys->stream));
+    updnorm += dd;
+    return updnorm_dev.zero(sys->stream);
+}
+
 extern "C" {
 
 static int dns_trap_create_impl(dns_saddle *sys, dns_conv *conv, const double *m_vals,
@@ -324,16 +335,9 @@ static int dns_trap_start_impl(dns_trap *t, const double *iniv, int32_t newton) 
     if (!t || !iniv) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = t->sys;
     DNS_HIP(hipSetDevice(h->device));
-    t->cur = 0;
-    t->prev = 1;
-    t->pprev = 2;
-    t->p3 = 3;
-    t->p4 = 4;
-    t->work = 5;
+    t->reset(1);
     for (int i = 0; i < 6; ++i) DNS_TRY(t->xs[i].zero(h->stream));
     DNS_TRY(t->xs[0].upload(iniv, (size_t)h->nv, h->stream));
-    t->nsol = 1;
-    t->pre_ok = false;
     t->updnorm = 0.0;
     t->pipeline_c = 0;
     t->cur_slot = 0;
@@ -533,35 +537,18 @@ int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
     double *x = t->xs[t->work].p;
     const bool same_dt = t->last_dt > 0.0 &&
                          std::fabs(dt - t->last_dt) <= 1e-12 * dt;
-    const int my_sig = 8 * t->nsol + std::min(extrapolate_x0, 7);
-    const bool use_pre = t->pre_ok && t->pre_sig == my_sig && same_dt &&
-                         std::fabs(dt - t->pre_dt) <= 1e-12 * dt;
+    // (the order is capped at the quartic: kExtrapFit35 runs as the quartic)
+    const int ex = std::min(extrapolate_x0, 4);
+    const bool use_pre = t->pre_ok &&
+                         t->pre_sig == dns::extrap_sig(t->nsol, extrapolate_x0) &&
+                         same_dt && std::fabs(dt - t->pre_dt) <= 1e-12 * dt;
     t->pre_ok = false;
-    if (use_pre) {
-        // (the tail of the step before has left the warm start in `x`)
-    } else if (extrapolate_x0 >= 4 && t->nsol >= 5 && same_dt) {
-        // (quartic: 5 x_c - 10 x_p + 10 x_pp - 5 x_p3 + x_p4)
-        hipLaunchKernelGGL(dns::k_lincomb5, dns::grid_for_elems(n), dns::kBlock,
-                           0, s, n, t->xs[t->cur].p, t->xs[t->prev].p,
-                           t->xs[t->pprev].p, t->xs[t->p3].p, t->xs[t->p4].p, x);
-    } else if (extrapolate_x0 >= 3 && t->nsol >= 4 && same_dt) {
-        // (cubic: one order above the quadratic, a decade less start residual)
-        hipLaunchKernelGGL(dns::k_lincomb4, dns::grid_for_elems(n), dns::kBlock,
-                           0, s, n, t->xs[t->cur].p, t->xs[t->prev].p,
-                           t->xs[t->pprev].p, t->xs[t->p3].p, x);
-    } else if (extrapolate_x0 >= 2 && t->nsol >= 3 && same_dt) {
-        hipLaunchKernelGGL(dns::k_lincomb3, dns::grid_for_elems(n), dns::kBlock,
-                           0, s, n, t->xs[t->cur].p, t->xs[t->prev].p,
-                           t->xs[t->pprev].p, x);
-    } else if (extrapolate_x0 >= 1 && t->nsol >= 2 && same_dt) {
-        hipLaunchKernelGGL(dns::k_lincomb2, dns::grid_for_elems(n), dns::kBlock,
-                           0, s, n, 2.0, t->xs[t->cur].p, -1.0,
-                           t->xs[t->prev].p, x);
-    } else {
-        DNS_HIP(hipMemcpyAsync(x, t->xs[t->cur].p, (size_t)n * sizeof(double),
-                               hipMemcpyDeviceToDevice, s));
+    if (!use_pre) {
+        // (else the tail of the step before has left the warm start in `x`)
+        double e[5];
+        const int order = same_dt ? dns::extrap_coeffs(t->nsol, ex, e) : 0;
+        DNS_TRY(dns::enqueue_extrap(order, t->xs, *t, x, n, s));
     }
-    DNS_HIP(hipGetLastError());
     // ONE launch for the element work: local matrices about v_lin, the cell
     // values of the CURRENT velocity (f_c - N_c v_c, with the boundary values
     // of its own time instance) and -- Newton -- those of v_lin
@@ -673,21 +660,12 @@ int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
         // on a partitioned handle the solution is gathered behind the solve,
         // the warm start stays a kernel of its own there
         const int nn = std::min(t->nsol + 1, 5);
+        double e[5];
         h->tail_extrap = dns::TailExtrap{};
-        if (!h->dist() && !fb && extrapolate_x0 >= 1 && nn >= 2) {
-            dns::TailExtrap te = {t->xs[t->cur].p, t->xs[t->prev].p,
-                                  t->xs[t->pprev].p, t->xs[t->p3].p,
-                                  2.0, -1.0, 0.0, 0.0, 0.0, t->xs[t->p4].p};
-            if (extrapolate_x0 >= 4 && nn >= 5) {
-                te.e0 = 5.0; te.e1 = -10.0; te.e2 = 10.0; te.e3 = -5.0;
-                te.e4 = 1.0;
-            } else if (extrapolate_x0 >= 3 && nn >= 4) {
-                te.e0 = 4.0; te.e1 = -6.0; te.e2 = 4.0; te.e3 = -1.0;
-            } else if (extrapolate_x0 >= 2 && nn >= 3) {
-                te.e0 = 3.0; te.e1 = -3.0; te.e2 = 1.0;
-            }
-            h->tail_extrap = te;
-        }
+        if (!h->dist() && !fb && dns::extrap_coeffs(nn, ex, e) >= 1)
+            h->tail_extrap = dns::TailExtrap{
+                t->xs[t->cur].p, t->xs[t->prev].p, t->xs[t->pprev].p,
+                t->xs[t->p3].p,  e[0], e[1], e[2], e[3], e[4], t->xs[t->p4].p};
         // pipelined sweep: one cycle of the agreed length, nobody waits; the
         // device counts steps / failures for dns_trap_poll (as dns_imex_run)
         if (async) h->pipeline_c = t->pipeline_c;
@@ -706,7 +684,7 @@ int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
         h->pipeline_c = 0;
         if (h->tail_extrap.out && rc == DNS_OK) {
             t->pre_ok = true;
-            t->pre_sig = 8 * nn + std::min(extrapolate_x0, 7);
+            t->pre_sig = dns::extrap_sig(nn, extrapolate_x0);
             t->pre_dt = dt;
         }
         h->tail_extrap = dns::TailExtrap{};
@@ -766,15 +744,7 @@ int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
                                t->fb_y.p + (size_t)j * h->ld, 1.0, x);
         DNS_HIP(hipGetLastError());
     }
-    // rotate the ring; the new solution is current
-    const int oldest = t->p4;
-    t->p4 = t->p3;
-    t->p3 = t->pprev;
-    t->pprev = t->prev;
-    t->prev = t->cur;
-    t->cur = t->work;
-    t->work = oldest;
-    if (t->nsol < 5) t->nsol++;
+    t->rotate();                       // the new solution is current
     t->last_dt = dt;
     t->cur_slot = lin_slot;
     // (N_c, f_c at the new velocity, snu:1529-1537: taken when the next step
@@ -875,12 +845,7 @@ static int dns_trap_poll_impl(dns_trap *t, int32_t *solves, int32_t *fails, int3
     if (fails) *fails = ha->acc_fail;
     if (iters) *iters = ha->acc_iters;
     if (maxit) *maxit = ha->acc_maxit;
-    double dd = 0.0;
-    DNS_TRY(t->flush_updnorm());
-    DNS_TRY(t->updnorm_dev.download(&dd, 1, h->stream));
-    DNS_HIP(hipStreamSynchronize(h->stream));
-    t->updnorm += dd;
-    DNS_TRY(t->updnorm_dev.zero(h->stream));
+    DNS_TRY(t->collect_updnorm());
     if (ext_i) {
         ext_i[0] = ha->acc_maxneed;
         ext_i[1] = ha->acc_sumneed;
@@ -917,23 +882,16 @@ static int dns_trap_checkpoint_impl(dns_trap *t) {
     if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = t->sys;
     DNS_HIP(hipSetDevice(h->device));
-    const int src[5] = {t->cur, t->prev, t->pprev, t->p3, t->p4};
-    for (int i = 0; i < 5; ++i) {
-        if (t->ck[i].n < (size_t)h->ld) DNS_TRY(t->ck[i].alloc((size_t)h->ld));
-        DNS_HIP(hipMemcpyAsync(t->ck[i].p, t->xs[src[i]].p,
-                               (size_t)h->ld * sizeof(double),
-                               hipMemcpyDeviceToDevice, h->stream));
-    }
+    // (the work buffer is not part of it: restore clears pre_ok)
+    t->ck.clear();
+    for (int q : {t->cur, t->prev, t->pprev, t->p3, t->p4})
+        DNS_TRY(t->ck.add(t->xs[q].p, h->ld));
+    DNS_TRY(t->ck.save(h->stream));
     // (the part of the update norm still on the device belongs to the steps
     // before the checkpoint)
-    double dd = 0.0;
-    DNS_TRY(t->flush_updnorm());
-    DNS_TRY(t->updnorm_dev.download(&dd, 1, h->stream));
-    DNS_HIP(hipStreamSynchronize(h->stream));
-    t->updnorm += dd;
-    DNS_TRY(t->updnorm_dev.zero(h->stream));
+    DNS_TRY(t->collect_updnorm());
     t->ckh.valid = true;
-    t->ckh.nsol = t->nsol;
+    t->ckh.ring = *t;
     t->ckh.cur_slot = t->cur_slot;
     t->ckh.last_dt = t->last_dt;
     t->ckh.updnorm = t->updnorm;
@@ -951,17 +909,9 @@ static int dns_trap_restore_impl(dns_trap *t, int32_t newton) {
     dns_saddle *h = t->sys;
     DNS_HIP(hipSetDevice(h->device));
     DNS_HIP(hipStreamSynchronize(h->stream));
-    t->cur = 0;
-    t->prev = 1;
-    t->pprev = 2;
-    t->p3 = 3;
-    t->p4 = 4;
-    t->work = 5;
-    for (int i = 0; i < 5; ++i)
-        DNS_HIP(hipMemcpyAsync(t->xs[i].p, t->ck[i].p,
-                               (size_t)h->ld * sizeof(double),
-                               hipMemcpyDeviceToDevice, h->stream));
-    t->nsol = t->ckh.nsol;
+    // (the ring as it was: one of its six rotations, as a reset ring is)
+    DNS_TRY(t->ck.restore(h->stream));
+    static_cast<dns::Ring &>(*t) = t->ckh.ring;
     t->pre_ok = false;       // (the work buffer is not part of the checkpoint)
     t->cur_slot = t->ckh.cur_slot;
     t->last_dt = t->ckh.last_dt;

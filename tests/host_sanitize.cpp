@@ -1,8 +1,9 @@
 // CPU-only sanitizer target for the HOST logic of the library (no HIP, no GPU):
 // hostcsr.hpp (SpGEMM, polynomial rows, transposes, slices), pair_host.hpp
-// (pair-format builder), halo_host.hpp (partition, halo index lists) and
-// batch_policy.hpp (cycle and batch length of the pipelined batches) are
-// compiled as they are with
+// (pair-format builder), halo_host.hpp (partition, halo index lists),
+// batch_policy.hpp (cycle and batch length of the pipelined batches) and
+// ring.hpp (solution ring and warm-start coefficients of the resident time
+// steppers) are compiled as they are with
 //     g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover
 // and driven over a small saddle-point system with the structure of the
 // package's matrices (2x2 velocity node blocks, pressure rows on node
@@ -21,6 +22,7 @@
 #include "../dolfin_navier_scipy_amd/csrc/halo_host.hpp"
 #include "../dolfin_navier_scipy_amd/csrc/hostcsr.hpp"
 #include "../dolfin_navier_scipy_amd/csrc/pair_host.hpp"
+#include "../dolfin_navier_scipy_amd/csrc/ring.hpp"
 
 using dns::HostCsr;
 
@@ -570,7 +572,109 @@ static void test_batch_policy() {
     }
 }
 
+// the ring: every rotation moves each solution back by one and makes the
+// oldest the work buffer; the indices stay a permutation of 0..5, nsol
+// saturates at 5, and six rotations are the identity
+static bool is_reset(const dns::Ring &r) {
+    return r.cur == 0 && r.prev == 1 && r.pprev == 2 && r.p3 == 3 &&
+           r.p4 == 4 && r.work == 5;
+}
+
+static void test_ring() {
+    dns::Ring r;
+    CHECK(is_reset(r) && r.nsol == 0 && !r.pre_ok);
+    r.reset(1);
+    CHECK(is_reset(r) && r.nsol == 1 && !r.pre_ok);
+    for (int k = 1; k <= 13; ++k) {
+        const dns::Ring b = r;
+        r.rotate();
+        CHECK(r.cur == b.work && r.prev == b.cur && r.pprev == b.prev &&
+              r.p3 == b.pprev && r.p4 == b.p3 && r.work == b.p4);
+        const int idx[6] = {r.cur, r.prev, r.pprev, r.p3, r.p4, r.work};
+        int seen = 0;
+        for (int i : idx) {
+            CHECK(i >= 0 && i < 6);
+            if (i >= 0 && i < 6) seen |= 1 << i;
+        }
+        CHECK(seen == 63);
+        CHECK(r.nsol == std::min(1 + k, 5));
+        CHECK(r.cur == (6 - k % 6) % 6);
+        CHECK(is_reset(r) == (k % 6 == 0));
+    }
+    r.pre_ok = true;
+    r.pre_sig = 7;
+    r.reset(2);
+    CHECK(is_reset(r) && r.nsol == 2 && !r.pre_ok);
+    // one signature per (nsol, order up to 7); nsol saturates at 5 like the ring
+    for (int n = 0; n <= 5; ++n)
+        for (int x = 0; x <= 13; ++x) {
+            CHECK(dns::extrap_sig(n, x) == 8 * n + std::min(x, 7));
+            CHECK(dns::extrap_sig(n + 3, x) == dns::extrap_sig(std::min(n + 3, 5), x));
+        }
+}
+
+// sum_i e_i q(-i) for q(t) = t^d: the solutions sit at t = 0, -1, .., -4 (cur
+// first), the warm start is their value at t = 1
+static double extrap_moment(const double e[5], int d) {
+    double s = 0.0;
+    for (int i = 0; i < 5; ++i) s += e[i] * std::pow(-(double)i, d);
+    return s;
+}
+
+// the warm-start coefficients: they sum to one, order p reproduces degree p
+// at the integer nodes exactly (the least-squares fit: a cubic), and capped
+// at the quartic they are the ladder the trapezoidal stepper had on its own
+static void test_extrap_coeffs() {
+    // the trapezoidal ladder, order by [nsol - 1][extrapolate_x0 = 0..13]
+    static const int kTrapOrder[5][14] = {
+        {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+        {0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1},
+        {0, 1, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2},
+        {0, 1, 2, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3},
+        {0, 1, 2, 3, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4},
+    };
+    // ... and its coefficients by order (0: a copy of x_c)
+    static const double kTrapCoef[5][5] = {
+        {1.0, 0.0, 0.0, 0.0, 0.0},
+        {2.0, -1.0, 0.0, 0.0, 0.0},
+        {3.0, -3.0, 1.0, 0.0, 0.0},
+        {4.0, -6.0, 4.0, -1.0, 0.0},
+        {5.0, -10.0, 10.0, -5.0, 1.0},
+    };
+    for (int n = 1; n <= 5; ++n)
+        for (int x = -1; x <= 13; ++x) {
+            double e[5];
+            const int p = dns::extrap_coeffs(n, x, e);
+            const bool fit = x == dns::kExtrapFit35 && n >= 5;
+            const int want = x == dns::kExtrapFit35
+                                 ? std::min(3, n - 1)
+                                 : std::max(0, std::min({x, 4, n - 1}));
+            CHECK(p == want);
+            double sum = 0.0;
+            for (int i = 0; i < 5; ++i) sum += e[i];
+            CHECK(std::fabs(sum - 1.0) <= 1e-14);
+            for (int d = 0; d <= p; ++d) {
+                const double m = extrap_moment(e, d);
+                if (fit)
+                    CHECK(std::fabs(m - 1.0) <= 1e-12);
+                else
+                    CHECK(m == 1.0);
+            }
+            if (!fit) {
+                // (interpolating: order p and no more, on the last p + 1)
+                CHECK(extrap_moment(e, p + 1) != 1.0);
+                for (int i = p + 1; i < 5; ++i) CHECK(e[i] == 0.0);
+            }
+            if (x < 0) continue;
+            const int pt = dns::extrap_coeffs(n, std::min(x, 4), e);
+            CHECK(pt == kTrapOrder[n - 1][x]);
+            for (int i = 0; i < 5; ++i) CHECK(e[i] == kTrapCoef[pt][i]);
+        }
+}
+
 int main() {
+    test_ring();
+    test_extrap_coeffs();
     test_batch_policy();
     for (const auto &dims : {std::pair<int, int>{7, 5}, {12, 9}, {3, 2}}) {
         HostCsr F, J;

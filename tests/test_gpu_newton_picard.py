@@ -187,6 +187,61 @@ def test_library_time_loop_equals_the_per_step_calls(toy_prob, picard):
     cv.close()
 
 
+def test_restore_brings_back_a_rotated_ring(toy_prob):
+    """`dns_trap_checkpoint` / `dns_trap_restore` with the ring rotated away
+    from its start order (seven steps: `cur` is no longer buffer 0): restore
+    gives back the state and the update norm bit for bit, and the pipelined
+    batch run again from there gives what it gave the first time (to
+    rounding: its first warm start is now formed by the host's launch, not
+    by the tail kernel of the step before)"""
+    from dolfin_navier_scipy_amd import convection, newton_picard as dnp, saddle
+    s = _setup(toy_prob, Nts=40, tE=0.1)
+    tr = s['trange']
+    dt = tr[1] - tr[0]
+    cv = convection.ConvectionP2.from_taylor_hood(s['th'], s['inv'],
+                                                  s['dbcinds'], s['dbcvals'])
+    stp = dnp.TrapezoidalStepper(s['M'], s['A'], s['J'], cv, nslots=tr.size,
+                                 dt=dt, precond=dict(cheb_degree=4))
+    stp.set_rhs(s['fv'], s['fp'])
+    for k, t in enumerate(tr):
+        stp.write_linpoint(0, k, s['lin0'][t])
+    opts = saddle.solve_opts(rtol=1e-12, maxiter=400, use_graph=True)
+    stp.start(s['iniv'], False)
+    for k in range(1, 8):
+        stp.step(dt, 0, k, k, False, opts=opts)
+    stp.checkpoint()
+    v0, p0 = stp.state()
+    upd0 = stp.update_norm()
+
+    def batch():
+        stp.set_pipeline(3)
+        try:
+            stp.run(dt, 0, 8, 8, False, opts=opts)
+            stp.poll()
+        finally:
+            stp.set_pipeline(0)
+        slots = [stp.read_traj(1, k) for k in range(8, 16)]
+        return slots, stp.state(), stp.update_norm()
+
+    slots1, (v1, p1), upd1 = batch()
+    assert upd1 > upd0
+    stp.restore(False)
+    v, p = stp.state()
+    assert np.array_equal(v, v0) and np.array_equal(p, p0)
+    assert stp.update_norm() == upd0
+    slots2, (v2, p2), upd2 = batch()
+
+    def close(a, b):
+        return np.abs(a - b).max() <= 1e-9*np.abs(b).max()
+
+    for a, b in zip(slots2, slots1):
+        assert close(a, b)
+    assert close(v2, v1) and close(p2, p1)
+    assert abs(upd2 - upd1) <= 1e-9*abs(upd1)
+    stp.close()
+    cv.close()
+
+
 def test_async_trajectory_writer(setup, cvop, tmp_path):
     """the trajectory of a sweep travels to the host (and to
     `.npy` files, what `dou.save_npa` writes per step in the reference,

@@ -1,10 +1,11 @@
 """The host logic of the library -- SpGEMM and polynomial rows of the set-up
 (`hostcsr.hpp`), the pair-format builder (`pair_host.hpp`), partition and halo
 index lists (`halo_host.hpp`), the policy of the pipelined batches
-(`batch_policy.hpp`) -- compiled WITHOUT HIP under AddressSanitizer +
+(`batch_policy.hpp`), the solution ring and warm-start coefficients of the
+time steppers (`ring.hpp`) -- compiled WITHOUT HIP under AddressSanitizer +
 UndefinedBehaviorSanitizer and driven over a small saddle system, whole and in
-row blocks of 1..4 ranks, and the policy over a table of batches
-(`tests/host_sanitize.cpp`).  CPU only: GPU sanitizer
+row blocks of 1..4 ranks, the policy over a table of batches and the ring and
+coefficients over tables of their own (`tests/host_sanitize.cpp`).  CPU only: GPU sanitizer
 runs are not available on the pool, and the round-3 memory fault was a
 host-side lifetime bug."""
 import os
