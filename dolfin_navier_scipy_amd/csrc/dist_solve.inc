@@ -491,80 +491,27 @@ int dns_saddle::setup_dist_mg() {
         ++Lp;
     mg_nparts = Lp;
     if (Lp == 0) return DNS_OK;
-    for (int l = 0; l <= Lp && l < L; ++l) {
-        MgLevel &lv = mg[l];
-        if (l == 0) {
-            lv.st = st_p;
-        } else {
-            lv.st.assign((size_t)P + 1, 0);
-            for (int r = 0; r < P; ++r) {
-                int a = 0, b = 0;
-                dns_partition_range(lv.n, P, r, &a, &b);
-                lv.st[r] = a;
-                lv.st[r + 1] = b;
-            }
-        }
-    }
-    auto add_cols = [](const HostCsr &A, int r0, int r1, int clo, int chi,
-                       int shift, std::vector<unsigned char> &mark) {
-        // columns in [clo, chi) of the rows [r0, r1), as entry c - shift
-        for (int r = r0; r < r1; ++r)
-            for (int k = A.rowptr[r]; k < A.rowptr[r + 1]; ++k) {
-                const int c = A.colidx[k];
-                if (c >= clo && c < chi) mark[c - shift] = 1;
-            }
-    };
-    auto to_need = [&](const std::vector<unsigned char> &mark,
-                       const std::vector<int> &st, int r,
-                       std::vector<std::vector<int>> &need) {
-        need.assign((size_t)P, std::vector<int>());
-        for (int q = 0; q < P; ++q) {
-            if (q == r) continue;
-            for (int c = st[q]; c < st[q + 1]; ++c)
-                if (mark[c]) need[q].push_back(c);
-        }
-    };
+    for (int l = 0; l <= Lp; ++l)
+        mg[l].st = (l == 0) ? st_p : partition_starts(mg[l].n, P);
     for (int l = 0; l < Lp; ++l) {
         MgLevel &lv = mg[l];
-        const int nl = lv.n, nc = mg[l + 1].n;
         const std::vector<int> &st = lv.st, &stc = mg[l + 1].st;
         lv.coarse_replicated = (l + 1 == Lp);
         std::vector<std::vector<std::vector<int>>> needF((size_t)P),
             needC((size_t)P);
-        for (int r = 0; r < P; ++r) {
-            std::vector<unsigned char> mf((size_t)nl, 0), mc((size_t)nc, 0);
-            add_cols(lv.Apreh, st[r], st[r + 1], 0, nl, 0, mf);
-            add_cols(lv.Sh, st[r], st[r + 1], 0, nl, 0, mf);
-            add_cols(lv.Qqh, st[r], st[r + 1], 0, nl, 0, mf);
-            add_cols(lv.Qqh, st[r], st[r + 1], nl, nl + nc, nl, mc);
-            // Rr = [P^T, -P^T S]: both column halves index level-l vectors
-            add_cols(lv.Rrh, stc[r], stc[r + 1], 0, nl, 0, mf);
-            add_cols(lv.Rrh, stc[r], stc[r + 1], nl, 2 * nl, nl, mf);
-            to_need(mf, st, r, needF[r]);
-            if (!lv.coarse_replicated) to_need(mc, stc, r, needC[r]);
-            else needC[r].assign((size_t)P, std::vector<int>());
-        }
+        for (int r = 0; r < P; ++r)
+            mg_need_lists(lv.Sh, lv.Apreh, lv.Qqh, st[r], st[r + 1], lv.Rrh,
+                          stc[r], stc[r + 1], st, stc, r, lv.coarse_replicated,
+                          needF[r], needC[r]);
         DNS_TRY(lv.planF.build(needF, me, P, stream));
         DNS_TRY(lv.planC.build(needC, me, P, stream));
-        {
-            const HostCsr a = host_row_slice(lv.Sh, st[me], st[me + 1]);
-            const HostCsr b = host_row_slice(lv.Apreh, st[me], st[me + 1]);
-            const HostCsr c = host_row_slice(lv.Rrh, stc[me], stc[me + 1]);
-            const HostCsr d = host_row_slice(lv.Qqh, st[me], st[me + 1]);
-            const dns_csr av = a.view(), bv = b.view(), cv = c.view(),
-                          dv = d.view();
-            DNS_TRY(lv.S.upload(&av, stream));
-            DNS_TRY(lv.Apre.upload(&bv, stream));
-            DNS_TRY(lv.Rr.upload(&cv, stream));
-            DNS_TRY(lv.Qq.upload(&dv, stream));
-            // (row blocks that are streamed cross the HBM as fp32, like the
-            // whole operators on one GPU)
-            if (fp32_store)
-                for (CsrDev *o : {&lv.Apre, &lv.Rr, &lv.Qq, &lv.S})
-                    if (streams(*o))
-                        DNS_TRY(to_f32(o->vals.p, o->vals32,
-                                       (size_t)o->nnz + 2));
-        }
+        // (row blocks that are streamed cross the HBM as fp32, like the whole
+        // operators on one GPU)
+        const HostCsr a = host_row_slice(lv.Sh, st[me], st[me + 1]);
+        const HostCsr b = host_row_slice(lv.Apreh, st[me], st[me + 1]);
+        const HostCsr c = host_row_slice(lv.Rrh, stc[me], stc[me + 1]);
+        const HostCsr d = host_row_slice(lv.Qqh, st[me], st[me + 1]);
+        DNS_TRY(upload_mg_ops(lv, &a, &b, &c, &d, false));
         lv.part = true;
     }
     DNS_HIP(hipStreamSynchronize(stream));
@@ -668,10 +615,7 @@ int dns_saddle::schur_mg_apply_dist(const double *in, double *zp,
     }
     {
         MgLevel &lc = mg[L - 1];
-        const DnsCtl *gctl = (guard && guard == done_ptr())
-                                 ? (const DnsCtl *)ctl.p
-                                 : (const DnsCtl *)nullptr;
-        DNS_TRY(mg_coarse_apply(lc.b.p, lc.x.p, gctl));
+        DNS_TRY(mg_coarse_apply(lc.b.p, lc.x.p, guard));
     }
     for (int l = L - 2; l >= Lp; --l) {
         MgLevel &lv = mg[l];

@@ -1,6 +1,7 @@
 // C-ABI implementation of include/dns_amd.h -- single translation unit for
 // hipcc --offload-arch=gfx950.
 #include "imex.hpp"
+#include "mg_host.hpp"
 #include "solver.hpp"
 
 using namespace dns;
@@ -802,122 +803,76 @@ int dns_saddle::build_mg_levels(int l0, HostCsr Sl) {
             return fail(DNS_ERR_BAD_ARGUMENT,
                         "prolongation %d has %d rows, level has %d", l, P.nrows,
                         lv.n);
-        std::vector<double> dv((size_t)lv.n, 1.0);
-        for (int i = 0; i < lv.n; ++i) {
-            double d = 0.0;
-            for (int k = Sl.rowptr[i]; k < Sl.rowptr[i + 1]; ++k)
-                if (Sl.colidx[k] == i) d += Sl.vals[k];
-            dv[i] = (d != 0.0) ? 1.0 / d : 1.0;
-        }
-        {
-            const double lmax = std::max(1e-300, host_jacobi_lmax(Sl));
-            lv.omega = lv.omega2 = 4.0 / (3.0 * lmax);
-            if (mg_cheb && mg_nu == 2) {
-                // two Richardson steps at the Chebyshev roots of
-                // [lmax / alpha, 1.05 lmax]
-                const double hi = 1.05 * lmax, lo = lmax / mg_cheb_alpha;
-                const double mid = 0.5 * (hi + lo), rad = 0.5 * (hi - lo);
-                const double c = 0.70710678118654752;    // cos(pi / 4)
-                lv.omega = 1.0 / (mid + rad * c);
-                lv.omega2 = 1.0 / (mid - rad * c);
-            }
-        }
+        std::vector<double> dv, dj;
+        mg_diagonals(Sl, 0, lv.n, dv, dj);
+        double lmax = 1.0;
+        mg_jacobi_lmax(Sl, 0, lv.n, dj, [](std::vector<double> &) { return 0; },
+                       &lmax);
+        mg_damping(lmax, mg_cheb && mg_nu == 2, mg_cheb_alpha, &lv.omega,
+                   &lv.omega2);
         HostCsr PT = host_transpose(P);
-        dns_csr sv = Sl.view(), pv = P.view(), tv = PT.view();
-        DNS_TRY(lv.S.upload(&sv, stream));
+        dns_csr pv = P.view(), tv = PT.view();
+        if (!mg_fused) {
+            const dns_csr sv = Sl.view();
+            DNS_TRY(lv.S.upload(&sv, stream));
+        }
         DNS_TRY(lv.P.upload(&pv, stream));
         DNS_TRY(lv.PT.upload(&tv, stream));
         DNS_TRY(lv.dinv.alloc((size_t)lv.n));
         DNS_TRY(lv.dinv.upload(dv.data(), dv.size(), stream));
         DNS_HIP(hipStreamSynchronize(stream));
         const HostCsr SP = host_spgemm(Sl, P);
-        if (mg_fused11) {
-            // (solver.hpp, mg_fused11) one sweep each way, w = 4 / (3 lmax)
-            lv.omega = lv.omega2 = 4.0 / (3.0 * std::max(
-                                              1e-300, host_jacobi_lmax(Sl)));
-            std::vector<double> wd((size_t)lv.n);
-            for (int i = 0; i < lv.n; ++i) wd[i] = lv.omega * dv[i];
-            const HostCsr I = host_diag(std::vector<double>((size_t)lv.n, 1.0));
-            HostCsr WS = Sl;
-            host_scale_rows(wd, WS);                       // w D^-1 S
-            // (I + T) w D^-1 = (2 I - w D^-1 S) w D^-1
-            HostCsr Ap = host_add(2.0, I, -1.0, WS);
-            for (size_t k = 0; k < Ap.vals.size(); ++k)
-                Ap.vals[k] *= wd[Ap.colidx[k]];
-            // Rd = P^T - (P^T S) w D^-1
-            HostCsr PTSw = host_spgemm(PT, Sl);
-            for (size_t k = 0; k < PTSw.vals.size(); ++k)
-                PTSw.vals[k] *= wd[PTSw.colidx[k]];
-            const HostCsr Rd = host_add(1.0, PT, -1.0, PTSw);
-            HostCsr WSP = SP;
-            host_scale_rows(wd, WSP);
-            HostCsr U = host_hstack(Ap, host_add(1.0, P, -1.0, WSP));
-            if (l == 0)                                    // zp = -x
-                for (double &v : U.vals) v = -v;
-            dns_csr rv = Rd.view(), qv = U.view();
-            DNS_TRY(lv.Rr.upload(&rv, stream));
-            DNS_TRY(lv.Qq.upload(&qv, stream));
-            if (fp32_store)
-                for (CsrDev *op : {&lv.Rr, &lv.Qq})
-                    if (streams_mg(*op))
-                        DNS_TRY(to_f32(op->vals.p, op->vals32,
-                                       (size_t)op->nnz + 2));
+        if (mg_fused || mg_fused11) {
+            // the operators of the fused cycle (solver.hpp, MgLevel;
+            // mg_fused11: one sweep each way, w = 4 / (3 lmax))
+            MgOps o = mg_fused ? mg_fused22_ops(Sl, SP, P, PT, 0, lv.n, dv,
+                                                lv.omega, lv.omega2)
+                               : mg_fused11_ops(Sl, SP, P, PT, 0, lv.n, dv,
+                                                lv.omega, l == 0);
+            // (the cycle is part of the preconditioner: its operators cross
+            // the HBM as fp32 where they are streamed, 6 B per non-zero; a
+            // level that is row-partitioned later uploads its row blocks,
+            // which drops the copy: those levels stream fp64)
+            DNS_TRY(upload_mg_ops(lv, mg_fused ? &Sl : nullptr,
+                                  mg_fused ? &o.Apre : nullptr, &o.Rr, &o.Qq,
+                                  true));
             DNS_HIP(hipStreamSynchronize(stream));
+            // the prolongation itself is not applied by the fused cycles
             lv.nnz_P = lv.P.nnz;
             lv.nnz_S = lv.S.nnz;
             lv.P.release_all();
             lv.PT.release_all();
-        }
-        if (mg_fused) {
-            // the operators of the fused cycle (solver.hpp, MgLevel)
-            // first sweep of a pair with w1 = omega, second with w2 = omega2:
-            //   T   = I - w1 D^-1 S
-            //   pre = ((w1 + w2) I - w2 (w1 D^-1 S)) D^-1   (two sweeps from 0)
-            std::vector<double> wd((size_t)lv.n);
-            for (int i = 0; i < lv.n; ++i) wd[i] = lv.omega * dv[i];
-            const HostCsr I = host_diag(std::vector<double>((size_t)lv.n, 1.0));
-            HostCsr WS = Sl;
-            host_scale_rows(wd, WS);                       // w1 D^-1 S
-            const HostCsr T = host_add(1.0, I, -1.0, WS);
-            HostCsr Ap = host_add(lv.omega + lv.omega2, I, -lv.omega2, WS);
-            for (size_t k = 0; k < Ap.vals.size(); ++k)    // ... D^-1
-                Ap.vals[k] *= dv[Ap.colidx[k]];
-            HostCsr mPTS = host_spgemm(PT, Sl);
-            for (double &v : mPTS.vals) v = -v;
-            const HostCsr Rr = host_hstack(PT, mPTS);
-            HostCsr WSP = SP;
-            host_scale_rows(wd, WSP);
-            const HostCsr Qq = host_hstack(T, host_add(1.0, P, -1.0, WSP));
-            dns_csr av = Ap.view(), rv = Rr.view(), qv = Qq.view();
-            DNS_TRY(lv.Apre.upload(&av, stream));
-            DNS_TRY(lv.Rr.upload(&rv, stream));
-            DNS_TRY(lv.Qq.upload(&qv, stream));
-            if (fp32_store) {
-                // the cycle is part of the preconditioner: its operators cross
-                // the HBM as fp32 where they are streamed (6 B per non-zero;
-                // a level that is row-partitioned later uploads its row blocks,
-                // which drops the copy: those levels stream fp64)
-                for (CsrDev *op : {&lv.Apre, &lv.Rr, &lv.Qq, &lv.S})
-                    if (streams_mg(*op))
-                        DNS_TRY(to_f32(op->vals.p, op->vals32,
-                                       (size_t)op->nnz + 2));
-            }
-            DNS_HIP(hipStreamSynchronize(stream));
-            // the prolongation itself is not applied by the fused cycle
-            lv.nnz_P = lv.P.nnz;
-            lv.nnz_S = lv.S.nnz;
-            lv.P.release_all();
-            lv.PT.release_all();
-            if (comm) {
+            if (comm && mg_fused) {
                 lv.Sh = Sl;
-                lv.Apreh = std::move(Ap);
-                lv.Rrh = Rr;
-                lv.Qqh = Qq;
+                lv.Apreh = std::move(o.Apre);
+                lv.Rrh = std::move(o.Rr);
+                lv.Qqh = std::move(o.Qq);
             }
         }
         Sl = host_spgemm(PT, SP);
     }
     mg_ready = true;
+    return DNS_OK;
+}
+
+// a level's cycle operators in HBM (a null host operator leaves its slot as
+// it is) and, with fp32_store, the fp32 copy of each one uploaded that is
+// streamed: whole operators by streams_mg, row blocks by streams
+int dns_saddle::upload_mg_ops(MgLevel &lv, const HostCsr *S,
+                              const HostCsr *Apre, const HostCsr *Rr,
+                              const HostCsr *Qq, bool whole) {
+    const std::pair<CsrDev *, const HostCsr *> ops[] = {
+        {&lv.S, S}, {&lv.Apre, Apre}, {&lv.Rr, Rr}, {&lv.Qq, Qq}};
+    for (const auto &o : ops)
+        if (o.second) {
+            const dns_csr v = o.second->view();
+            DNS_TRY(o.first->upload(&v, stream));
+        }
+    if (fp32_store)
+        for (const auto &o : ops)
+            if (o.second && (whole ? streams_mg(*o.first) : streams(*o.first)))
+                DNS_TRY(to_f32(o.first->vals.p, o.first->vals32,
+                               (size_t)o.first->nnz + 2));
     return DNS_OK;
 }
 
@@ -977,11 +932,7 @@ int dns_saddle::schur_mg_apply(const double *in, double *zp, double *xacc,
     {
         MgLevel &lc = mg[L - 1];
         const double *b = (L == 1) ? in : lc.b.p;
-        // (the dense kernel's own guard is the solve's control block)
-        const DnsCtl *gctl = (guard && guard == done_ptr())
-                                 ? (const DnsCtl *)ctl.p
-                                 : (const DnsCtl *)nullptr;
-        DNS_TRY(mg_coarse_apply(b, lc.x.p, gctl));
+        DNS_TRY(mg_coarse_apply(b, lc.x.p, guard));
         xat[L - 1] = lc.x.p;
     }
     for (int l = L - 2; l >= 0; --l) {
@@ -1041,11 +992,12 @@ int dns_saddle::mg_op(const CsrDev &A, const double *xa, int nsplit,
     return DNS_OK;
 }
 
-// the V(2,2) cycle on the fused operators: per level two launches down
-// (x_pre = Apre b; b_c = Rr [b; x_pre]) and two up (x' = Qq [x_pre; e] + c(b);
-// one more sweep -- the finest level's writes zp = -x'' itself)
 int dns_saddle::mg_coarse_apply(const double *b, double *x,
-                                const DnsCtl *gctl) {
+                                const int *guard) {
+    // (the dense kernel's own guard is the solve's control block)
+    const DnsCtl *gctl = (guard && guard == done_ptr())
+                             ? (const DnsCtl *)ctl.p
+                             : (const DnsCtl *)nullptr;
     const int nc = mg.back().n;
     const int gg = std::max(1, std::min((nc + 3) / 4, 2048));
     if (mg_cinv16.p)
@@ -1062,6 +1014,9 @@ int dns_saddle::mg_coarse_apply(const double *b, double *x,
     return DNS_OK;
 }
 
+// the V(2,2) cycle on the fused operators: per level two launches down
+// (x_pre = Apre b; b_c = Rr [b; x_pre]) and two up (x' = Qq [x_pre; e] + c(b);
+// one more sweep -- the finest level's writes zp = -x'' itself)
 int dns_saddle::mg_cycle_fused(const double *in, double *zp, double *xacc,
                                 const int *guard, double scale) {
     // zp = -scale * V(in)  (and xacc += zp)
@@ -1076,10 +1031,7 @@ int dns_saddle::mg_cycle_fused(const double *in, double *zp, double *xacc,
     }
     {
         MgLevel &lc = mg[L - 1];
-        const DnsCtl *gctl = (guard && guard == done_ptr())
-                                 ? (const DnsCtl *)ctl.p
-                                 : (const DnsCtl *)nullptr;
-        DNS_TRY(mg_coarse_apply(lc.b.p, lc.x.p, gctl));
+        DNS_TRY(mg_coarse_apply(lc.b.p, lc.x.p, guard));
     }
     for (int l = L - 2; l >= 0; --l) {
         MgLevel &lv = mg[l];
@@ -1131,10 +1083,7 @@ int dns_saddle::mg_cycle_fused11(const double *in, double *zp, double *xacc,
     }
     {
         MgLevel &lc = mg[L - 1];
-        const DnsCtl *gctl = (guard && guard == done_ptr())
-                                 ? (const DnsCtl *)ctl.p
-                                 : (const DnsCtl *)nullptr;
-        DNS_TRY(mg_coarse_apply(lc.b.p, lc.x.p, gctl));
+        DNS_TRY(mg_coarse_apply(lc.b.p, lc.x.p, guard));
     }
     for (int l = L - 2; l >= 0; --l) {
         MgLevel &lv = mg[l];

@@ -21,23 +21,37 @@ inline std::vector<int> partition_starts(int n, int nranks) {
     return st;
 }
 
+// mark[c - shift] = 1 for every column c in [lo, hi) of the rows [row0, row1)
+inline void mark_cols(const dns_csr &a, int row0, int row1, int lo, int hi,
+                      int shift, std::vector<unsigned char> &mark) {
+    for (int r = row0; r < row1; ++r)
+        for (int k = a.rowptr[r]; k < a.rowptr[r + 1]; ++k) {
+            const int c = a.colidx[k];
+            if (c >= lo && c < hi) mark[c - shift] = 1;
+        }
+}
+
+// need[q]: the marked entries in every rank's range starts[q] .. starts[q+1]
+// (sorted); own range left empty
+inline void marked_need(const std::vector<unsigned char> &mark,
+                        const int *starts, int nranks, int rank,
+                        std::vector<std::vector<int>> &need) {
+    need.assign((size_t)nranks, std::vector<int>());
+    for (int q = 0; q < nranks; ++q) {
+        if (q == rank) continue;
+        for (int c = starts[q]; c < starts[q + 1]; ++c)
+            if (mark[c]) need[q].push_back(c);
+    }
+}
+
 // sorted distinct columns < ncols_part that the rows [row0, row1) of `a`
 // reference in every rank's column range (need[q]); own range left empty
 inline void halo_need(const dns_csr *a, int row0, int row1, int nranks,
                       int rank, const int *col_starts, int ncols_part,
                       std::vector<std::vector<int>> &need) {
-    need.assign((size_t)nranks, std::vector<int>());
     std::vector<unsigned char> mark((size_t)std::max(1, ncols_part), 0);
-    for (int r = row0; r < row1; ++r)
-        for (int k = a->rowptr[r]; k < a->rowptr[r + 1]; ++k) {
-            const int c = a->colidx[k];
-            if (c < ncols_part) mark[c] = 1;
-        }
-    for (int q = 0; q < nranks; ++q) {
-        if (q == rank) continue;
-        for (int c = col_starts[q]; c < col_starts[q + 1]; ++c)
-            if (mark[c]) need[q].push_back(c);
-    }
+    mark_cols(*a, row0, row1, 0, ncols_part, 0, mark);
+    marked_need(mark, col_starts, nranks, rank, need);
 }
 
 }  // namespace dns

@@ -421,32 +421,6 @@ inline HostCsr host_transpose(const HostCsr &A) {
     return T;
 }
 
-// largest eigenvalue (in modulus) of D^-1 A by power iterations, D = diag(A)
-inline double host_jacobi_lmax(const HostCsr &A, int iters = 20) {
-    const int n = A.nrows;
-    std::vector<double> d((size_t)n, 1.0), x((size_t)n), y((size_t)n);
-    for (int i = 0; i < n; ++i)
-        for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k)
-            if (A.colidx[k] == i && A.vals[k] != 0.0) d[i] = 1.0 / A.vals[k];
-    for (int i = 0; i < n; ++i) x[i] = 1.0 + 0.5 * std::sin(0.37 * i + 1.0);
-    double lam = 1.0;
-    for (int it = 0; it < iters; ++it) {
-        double nx = 0.0, ny = 0.0;
-        for (int i = 0; i < n; ++i) {
-            double s = 0.0;
-            for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k)
-                s += A.vals[k] * x[A.colidx[k]];
-            y[i] = d[i] * s;
-            nx += x[i] * x[i];
-            ny += y[i] * y[i];
-        }
-        lam = std::sqrt(ny / nx);
-        const double sc = 1.0 / std::sqrt(ny);
-        for (int i = 0; i < n; ++i) x[i] = y[i] * sc;
-    }
-    return lam;
-}
-
 // y = A x (host, set-up time only)
 inline void host_spmv(const HostCsr &A, const std::vector<double> &x,
                       std::vector<double> &y) {

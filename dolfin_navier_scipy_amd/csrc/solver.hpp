@@ -635,7 +635,9 @@ struct dns_saddle {
     dns::DevBuf<double> mg_cscale;
     int mg_cld16 = 0;                     // its leading dimension (8 | ld)
     // x = (coarsest level)^-1 b in whichever store the set-up chose
-    int mg_coarse_apply(const double *b, double *x, const dns::DnsCtl *gctl);
+    // (guard: the device flag of the cycle; the solve's own turns on the
+    // dense kernel's guard, the control block)
+    int mg_coarse_apply(const double *b, double *x, const int *guard);
     int mg_nu = 2;
     bool mg_cheb = true;                  // DNS_MG_CHEB (read once, at create)
     double mg_cheb_alpha = 3.0;           // DNS_MG_CHEB_ALPHA (measured: 3
@@ -644,6 +646,9 @@ struct dns_saddle {
     int build_mg_schur(const dns::HostCsr &S0);
     int mg_prepare(int n0);               // level count, fresh levels
     int build_mg_levels(int l0, dns::HostCsr Sl);
+    int upload_mg_ops(MgLevel &lv, const dns::HostCsr *S,
+                      const dns::HostCsr *Apre, const dns::HostCsr *Rr,
+                      const dns::HostCsr *Qq, bool whole);
     // the hierarchy formed BY ROWS (mg_rows.inc): the levels that run row-
     // partitioned never exist as whole matrices; the first replicated level is
     // all-gathered, the rest is built from it as on one GPU

@@ -1,6 +1,7 @@
 // CPU-only sanitizer target for the HOST logic of the library (no HIP, no GPU):
 // hostcsr.hpp (SpGEMM, polynomial rows, transposes, slices), pair_host.hpp
 // (pair-format builder), halo_host.hpp (partition, halo index lists),
+// mg_host.hpp (multigrid level operators, damping, halo lists),
 // batch_policy.hpp (cycle and batch length of the pipelined batches) and
 // ring.hpp (solution ring and warm-start coefficients of the resident time
 // steppers) are compiled as they are with
@@ -13,14 +14,18 @@
 // inside its allocation is caught as well.  tests/test_host_sanitized.py
 // builds and runs it.
 #include <cmath>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
+#include <mutex>
+#include <thread>
 #include <vector>
 
 #include "../dolfin_navier_scipy_amd/csrc/batch_policy.hpp"
 #include "../dolfin_navier_scipy_amd/csrc/halo_host.hpp"
 #include "../dolfin_navier_scipy_amd/csrc/hostcsr.hpp"
+#include "../dolfin_navier_scipy_amd/csrc/mg_host.hpp"
 #include "../dolfin_navier_scipy_amd/csrc/pair_host.hpp"
 #include "../dolfin_navier_scipy_amd/csrc/ring.hpp"
 
@@ -441,6 +446,280 @@ static void test_misc(const HostCsr &F) {
     CHECK(Es.nrows == 0 && Es.nnz() == 0);
 }
 
+// ---- multigrid levels (mg_host.hpp) ----
+
+// y = A x, dense restatement
+static std::vector<double> matvec(const HostCsr &A, const std::vector<double> &x) {
+    std::vector<double> y((size_t)A.nrows, 0.0);
+    const std::vector<double> d = dense(A);
+    for (int i = 0; i < A.nrows; ++i)
+        for (int j = 0; j < A.ncols; ++j)
+            y[i] += d[(size_t)i * A.ncols + j] * x[j];
+    return y;
+}
+
+static std::vector<double> cat(const std::vector<double> &a,
+                               const std::vector<double> &b) {
+    std::vector<double> c = a;
+    c.insert(c.end(), b.begin(), b.end());
+    return c;
+}
+
+static bool close_to(const std::vector<double> &a, const std::vector<double> &b) {
+    if (a.size() != b.size()) return false;
+    for (size_t i = 0; i < a.size(); ++i)
+        if (std::fabs(a[i] - b[i]) > 1e-12 * (1.0 + std::fabs(b[i])))
+            return false;
+    return true;
+}
+
+static bool same_csr(const HostCsr &a, const HostCsr &b) {
+    return a.nrows == b.nrows && a.ncols == b.ncols && a.rowptr == b.rowptr &&
+           a.colidx == b.colidx && a.vals == b.vals;
+}
+
+// the rows of `blk` below those of `acc`
+static void append_rows(HostCsr &acc, const HostCsr &blk) {
+    if (acc.rowptr.empty()) acc.rowptr.push_back(0);
+    acc.ncols = blk.ncols;
+    for (int i = 0; i < blk.nrows; ++i)
+        acc.rowptr.push_back(acc.rowptr.back() + blk.rowptr[i + 1] -
+                             blk.rowptr[i]);
+    acc.nrows += blk.nrows;
+    acc.colidx.insert(acc.colidx.end(), blk.colidx.begin(), blk.colidx.end());
+    acc.vals.insert(acc.vals.end(), blk.vals.begin(), blk.vals.end());
+}
+
+// a pressure-like Schur operator S = J diag(F)^-1 J^T and an aggregation
+// prolongation: aggregates of 3 (the last one shorter), weights around 1,
+// column 1 an empty aggregate
+static void build_level(const HostCsr &F, const HostCsr &J, HostCsr &S,
+                        HostCsr &P) {
+    std::vector<double> df((size_t)F.nrows, 1.0);
+    for (int i = 0; i < F.nrows; ++i)
+        for (int k = F.rowptr[i]; k < F.rowptr[i + 1]; ++k)
+            if (F.colidx[k] == i) df[i] = 1.0 / F.vals[k];
+    HostCsr JD = J;
+    for (int64_t k = 0; k < JD.nnz(); ++k) JD.vals[k] *= df[JD.colidx[k]];
+    S = dns::host_spgemm(JD, dns::host_transpose(J));
+    const int n = S.nrows, nagg = (n + 2) / 3;
+    unsigned seed = 777u;
+    std::vector<std::map<int, double>> pr((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int a = i / 3;
+        pr[i][a < 1 ? a : a + 1] = 1.0 + 0.2 * lcg(seed);
+    }
+    P = from_map(n, nagg + 1, pr);
+}
+
+// all-gather of host vectors between threads that stand for ranks
+struct HostAllgather {
+    std::mutex m;
+    std::condition_variable cv;
+    int nranks = 1, arrived = 0, generation = 0;
+    std::vector<double> buf;
+    void barrier() {
+        std::unique_lock<std::mutex> lk(m);
+        const int g = generation;
+        if (++arrived == nranks) {
+            arrived = 0;
+            ++generation;
+            cv.notify_all();
+        } else {
+            cv.wait(lk, [&] { return generation != g; });
+        }
+    }
+    int operator()(std::vector<double> &v, const std::vector<int> &st, int me) {
+        {
+            std::lock_guard<std::mutex> lk(m);
+            buf.resize(v.size());
+            for (int i = st[me]; i < st[me + 1]; ++i) buf[i] = v[i];
+        }
+        barrier();
+        {
+            std::lock_guard<std::mutex> lk(m);
+            v = buf;
+        }
+        barrier();
+        return 0;
+    }
+};
+
+static void test_mg_levels(const HostCsr &F, const HostCsr &J) {
+    HostCsr S, P;
+    build_level(F, J, S, P);
+    const int n = S.nrows, nc = P.ncols;
+    const HostCsr PT = dns::host_transpose(P), SP = dns::host_spgemm(S, P);
+    // the whole level
+    std::vector<double> dv, dj;
+    dns::mg_diagonals(S, 0, n, dv, dj);
+    double lmax = 0.0;
+    CHECK(dns::mg_jacobi_lmax(S, 0, n, dj,
+                              [](std::vector<double> &) { return 0; },
+                              &lmax) == 0);
+    double w1 = 0.0, w2 = 0.0, w = 0.0, wj = 0.0;
+    dns::mg_damping(lmax, true, 3.0, &w1, &w2);
+    dns::mg_damping(lmax, false, 3.0, &w, &wj);
+    const dns::MgOps o = dns::mg_fused22_ops(S, SP, P, PT, 0, n, dv, w1, w2);
+    const HostCsr Sc = dns::host_spgemm(PT, SP);
+    // damping: the closed forms
+    CHECK(lmax > 0.0 && w == 4.0 / (3.0 * lmax) && wj == w);
+    {
+        const double hi = 1.05 * lmax, lo = lmax / 3.0;
+        const double mid = 0.5 * (hi + lo), rad = 0.5 * (hi - lo);
+        // (1 - w1 t)(1 - w2 t) = T_2((mid - t) / rad) / T_2(mid / rad)
+        for (double t : {lo, 0.5 * (lo + hi), hi, 0.1 * lmax}) {
+            const double s = (mid - t) / rad, s0 = mid / rad;
+            const double ref = (2 * s * s - 1) / (2 * s0 * s0 - 1);
+            CHECK(std::fabs((1 - w1 * t) * (1 - w2 * t) - ref) <= 1e-12);
+        }
+        CHECK(w1 < w2 && w1 > 0.0);
+        double a = 0.0, b = 0.0;
+        dns::mg_damping(0.0, false, 3.0, &a, &b);
+        CHECK(a == 4.0 / 3e-300 && b == a);
+    }
+    // the operators do what their comments say, against dense loops
+    unsigned seed = 99u;
+    std::vector<double> b((size_t)n), x((size_t)n), e((size_t)nc);
+    for (double &v : b) v = lcg(seed);
+    for (double &v : x) v = lcg(seed);
+    for (double &v : e) v = lcg(seed);
+    auto sweep = [&](const std::vector<double> &x0, double om) {
+        const std::vector<double> sx = matvec(S, x0);
+        std::vector<double> y = x0;
+        for (int i = 0; i < n; ++i) y[i] += om * dv[i] * (b[i] - sx[i]);
+        return y;
+    };
+    auto restrict_ = [&](const std::vector<double> &r) { return matvec(PT, r); };
+    {
+        // Apre b: two damped Jacobi sweeps from zero
+        CHECK(close_to(matvec(o.Apre, b),
+                   sweep(sweep(std::vector<double>((size_t)n, 0.0), w1), w2)));
+        // Rr [b; x] = P^T (b - S x)
+        std::vector<double> r = matvec(S, x);
+        for (int i = 0; i < n; ++i) r[i] = b[i] - r[i];
+        CHECK(close_to(matvec(o.Rr, cat(b, x)), restrict_(r)));
+        // Qq [x; e] + w1 D^-1 b = one sweep on x + P e
+        std::vector<double> q = matvec(o.Qq, cat(x, e));
+        std::vector<double> xp = matvec(P, e);
+        for (int i = 0; i < n; ++i) {
+            q[i] += w1 * dv[i] * b[i];
+            xp[i] += x[i];
+        }
+        CHECK(close_to(q, sweep(xp, w1)));
+    }
+    for (bool finest : {true, false}) {
+        const dns::MgOps u =
+            dns::mg_fused11_ops(S, SP, P, PT, 0, n, dv, w, finest);
+        CHECK(u.Apre.nrows == 0);
+        // Rd b = P^T (b - S w D^-1 b)
+        std::vector<double> c((size_t)n);
+        for (int i = 0; i < n; ++i) c[i] = w * dv[i] * b[i];
+        std::vector<double> r = matvec(S, c);
+        for (int i = 0; i < n; ++i) r[i] = b[i] - r[i];
+        CHECK(close_to(matvec(u.Rr, b), restrict_(r)));
+        // U [b; e] = (I + T) w D^-1 b + T P e, T = I - w D^-1 S
+        std::vector<double> y = matvec(P, e);
+        for (int i = 0; i < n; ++i) y[i] += c[i];
+        const std::vector<double> sy = matvec(S, y);
+        for (int i = 0; i < n; ++i) {
+            y[i] += c[i] - w * dv[i] * sy[i];
+            if (finest) y[i] = -y[i];
+        }
+        CHECK(close_to(matvec(u.Qq, cat(b, e)), y));
+    }
+    for (int R = 1; R <= 4; ++R) {
+        const std::vector<int> st = dns::partition_starts(n, R),
+                               stc = dns::partition_starts(nc, R);
+        // rows equal whole: every rank's set-up as mg_rows.inc runs it, the
+        // all-gathers between threads
+        std::vector<dns::MgOps> ops((size_t)R);
+        std::vector<HostCsr> next((size_t)R);
+        std::vector<std::vector<double>> dvs((size_t)R);
+        std::vector<double> lm((size_t)R, 0.0), om1((size_t)R), om2((size_t)R);
+        HostAllgather ag;
+        ag.nranks = R;
+        auto rank = [&](int me) {
+            const int f0 = st[me], f1 = st[me + 1];
+            const HostCsr Sloc = host_row_slice(S, f0, f1);
+            const dns_csr slv = Sloc.view();
+            const HostCsr Sg = dns::host_embed_rows(&slv, f0, n);
+            std::vector<double> djr;
+            dns::mg_diagonals(Sg, f0, f1, dvs[me], djr);
+            ag(dvs[me], st, me);
+            auto ex = [&](std::vector<double> &y) { return ag(y, st, me); };
+            CHECK(dns::mg_jacobi_lmax(Sg, f0, f1, djr, ex, &lm[me]) == 0);
+            dns::mg_damping(lm[me], true, 3.0, &om1[me], &om2[me]);
+            const HostCsr PTc = host_row_slice(PT, stc[me], stc[me + 1]);
+            // own rows + the rows the own rows of P^T reference
+            std::vector<char> keep((size_t)n, 0);
+            for (int i = f0; i < f1; ++i) keep[i] = 1;
+            for (int c : PTc.colidx) keep[c] = 1;
+            HostCsr Sx = S;
+            for (int i = 0, k = 0; i < n; ++i) {
+                if (!keep[i]) {
+                    const int len = Sx.rowptr[i + 1] - Sx.rowptr[i];
+                    Sx.colidx.erase(Sx.colidx.begin() + k,
+                                    Sx.colidx.begin() + k + len);
+                    Sx.vals.erase(Sx.vals.begin() + k, Sx.vals.begin() + k + len);
+                    for (int j = i + 1; j <= n; ++j) Sx.rowptr[j] -= len;
+                }
+                k = Sx.rowptr[i + 1];
+            }
+            const HostCsr SPx = dns::host_spgemm(Sx, P);
+            ops[me] = dns::mg_fused22_ops(Sx, SPx, P, PTc, f0, f1, dvs[me],
+                                          om1[me], om2[me]);
+            next[me] = dns::host_spgemm(PTc, SPx);
+        };
+        std::vector<std::thread> th;
+        for (int me = 0; me < R; ++me) th.emplace_back(rank, me);
+        for (auto &t : th) t.join();
+        HostCsr Ap, Rr, Qq, Sn;
+        for (int me = 0; me < R; ++me) {
+            CHECK(dvs[me] == dv && lm[me] == lmax);
+            CHECK(om1[me] == w1 && om2[me] == w2);
+            append_rows(Ap, ops[me].Apre);
+            append_rows(Rr, ops[me].Rr);
+            append_rows(Qq, ops[me].Qq);
+            append_rows(Sn, next[me]);
+        }
+        CHECK(same_csr(Ap, o.Apre) && same_csr(Rr, o.Rr));
+        CHECK(same_csr(Qq, o.Qq) && same_csr(Sn, Sc));
+        // need lists: whole operators cut by ranges (setup_dist_mg) and the
+        // rank's own blocks (mg_rows.inc) against a scan of every column
+        for (bool crep : {true, false})
+            for (int me = 0; me < R; ++me) {
+                const int f0 = st[me], f1 = st[me + 1], c0 = stc[me],
+                          c1 = stc[me + 1];
+                std::vector<std::vector<int>> nf, ncl, nf2, ncl2;
+                dns::mg_need_lists(S, o.Apre, o.Qq, f0, f1, o.Rr, c0, c1, st,
+                                   stc, me, crep, nf, ncl);
+                dns::mg_need_lists(host_row_slice(S, f0, f1), ops[me].Apre,
+                                   ops[me].Qq, 0, f1 - f0, ops[me].Rr, 0,
+                                   c1 - c0, st, stc, me, crep, nf2, ncl2);
+                CHECK(nf == nf2 && ncl == ncl2);
+                auto refs = [](const HostCsr &A, int r0, int r1, int c) {
+                    for (int i = r0; i < r1; ++i)
+                        for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k)
+                            if (A.colidx[k] == c) return true;
+                    return false;
+                };
+                for (int q = 0; q < R; ++q) {
+                    std::vector<int> wf, wc;
+                    for (int c = st[q]; q != me && c < st[q + 1]; ++c)
+                        if (refs(S, f0, f1, c) || refs(o.Apre, f0, f1, c) ||
+                            refs(o.Qq, f0, f1, c) || refs(o.Rr, c0, c1, c) ||
+                            refs(o.Rr, c0, c1, n + c))
+                            wf.push_back(c);
+                    for (int c = stc[q]; !crep && q != me && c < stc[q + 1]; ++c)
+                        if (refs(o.Qq, f0, f1, n + c)) wc.push_back(c);
+                    CHECK((int)nf.size() == R && (int)ncl.size() == R);
+                    CHECK(nf[q] == wf && ncl[q] == wc);
+                }
+            }
+    }
+}
+
 // every branch of the batch policy: state before, a batch that went through
 // (or the start-up / fallback), state after -- the expected values worked out
 // from the arithmetic as dns_imex_run had it inline
@@ -684,6 +963,7 @@ int main() {
         test_rows_on_their_reach(F);
         test_pair_format(F, J);
         test_halo_lists(F, J);
+        test_mg_levels(F, J);
         test_misc(F);
     }
     if (g_fail) {

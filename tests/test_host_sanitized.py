@@ -1,6 +1,7 @@
 """The host logic of the library -- SpGEMM and polynomial rows of the set-up
 (`hostcsr.hpp`), the pair-format builder (`pair_host.hpp`), partition and halo
-index lists (`halo_host.hpp`), the policy of the pipelined batches
+index lists (`halo_host.hpp`), the multigrid level operators, whole and by rows
+(`mg_host.hpp`), the policy of the pipelined batches
 (`batch_policy.hpp`), the solution ring and warm-start coefficients of the
 time steppers (`ring.hpp`) -- compiled WITHOUT HIP under AddressSanitizer +
 UndefinedBehaviorSanitizer and driven over a small saddle system, whole and in
