@@ -114,6 +114,7 @@ int dns_saddle::init_device(int dev) {
     if (const char *sn = getenv("DNS_PART_SETUP")) part_setup = sn[0] != '0';
     if (const char *sn = getenv("DNS_MG_ROWS")) mg_rows_knob = sn[0] != '0';
     if (const char *sn = getenv("DNS_DIST_GRAPH")) dist_graph_ok = sn[0] != '0';
+    if (const char *sn = getenv("DNS_STEP6_LAZY")) step6_lazy = sn[0] != '0';
     if (const char *sn = getenv("DNS_MG_CHEB")) mg_cheb = sn[0] != '0';
     if (const char *sn = getenv("DNS_MG_CYCLES"))
         mg_cycles_knob = std::max(0, std::min(2, atoi(sn)));
@@ -1583,6 +1584,54 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
     auto wcol = [&](int jj) -> double * {
         return s6 ? Wcols.p + (size_t)jj * ld : w.p;
     };
+    // six-node step: r = b - kx with its norms and tau(r) in ONE launch
+    auto tau_first = [&]() {
+        const int gt = std::max(1, std::min((np + 1) / 2, 4096));
+        hipLaunchKernelGGL(k_tau_first, gt + gridD, kBlock, 0, stream, gt, n,
+                           np, nv, JG.rowptr.p, JG.colidx.p, JG.vals.p, b,
+                           step6.kx, tau.p, r.p, partR.p, partB.p);
+    };
+    if (s6 && step6_lazy_for(c) && first == 1 && dense && step6.kx &&
+        have_jg) {
+        // lazy one-column cycle (the time step's usual one): the same six
+        // nodes and data flow, but the head is the dense Schur product alone,
+        // Gc and K read r where the tau kernel left it, and the tail forms the
+        // step from the four sums -- nothing is normalised, no guard is read
+        tau_first();
+        double *zp = Z.p + nv;
+        if (fp32_store)
+            hipLaunchKernelGGL(k_arn_head_lazy<2>, gridA, kBlock, 0, stream, np,
+                               (const void *)sinv32.p, tau.p, zp, sld,
+                               step_counter);
+        else
+            hipLaunchKernelGGL(k_arn_head_lazy<1>, gridA, kBlock, 0, stream, np,
+                               (const void *)sinv.p, tau.p, zp, 0,
+                               step_counter);
+        DNS_TRY(apply_fhat_part(r.p, zp, Z.p, zero_ptr(), nullptr));
+        // K z with <r, w>, <w, w> folded to at most kBlock partials of each
+        // (kLazyRows consecutive rows per sub-wave and pass)
+        const int rows_wg = kLazyRows * (kLazyBlock / K.lpr);
+        const int gridL = std::max(1, std::min((n + rows_wg - 1) / rows_wg,
+                                               kBlock));
+        DNS_LPR_SWITCH(
+            K.lpr,
+            hipLaunchKernelGGL((k_spmv_rw<L, kLazyRows, kLazyBlock>), gridL,
+                               kLazyBlock, 0, stream, n, K.rowptr.p,
+                               K.colidx.p, K.vals.p, Z.p, Wcols.p, r.p,
+                               partA.p));
+        Tail6 t6 = step6.t6;
+        t6.r0 = r.p;
+        t6.W = Wcols.p;
+        t6.nv = nv;
+        hipLaunchKernelGGL(k_arn_tail6<true>, gridD + step6.cells.nblocks,
+                           kBlock, 0, stream, 1, n, gridD, partA.p, gridL,
+                           ctl.p, histdev.p, (int)hist_cap, o->maxiter, Z.p,
+                           ld, t6, tail_extrap, step6.cells,
+                           TailLazy{partR.p, partB.p, gridD, o->rtol,
+                                    o->atol});
+        DNS_HIP(hipGetLastError());
+        return DNS_OK;
+    }
     for (int j = 0; j < c; ++j) {
         // the preconditioned vectors are kept (Z_j) for the correction behind
         // the cycle
@@ -1598,10 +1647,7 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
         if (s6 && j == 0 && step6.kx && have_jg && !mgs) {
             // six-node step: r = b - kx is formed HERE (extra workgroups),
             // the Schur rows gather b - kx themselves
-            const int gt = std::max(1, std::min((np + 1) / 2, 4096));
-            hipLaunchKernelGGL(k_tau_first, gt + gridD, kBlock, 0, stream, gt, n,
-                               np, nv, JG.rowptr.p, JG.colidx.p, JG.vals.p, b,
-                               step6.kx, tau.p, r.p, partR.p, partB.p);
+            tau_first();
             tin = tau.p;
         } else if (have_jg && !mgs) {
             const int jt = (fusedgs && j > 0) ? j : 0;
@@ -1763,10 +1809,11 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
         t6.r0 = r.p;
         t6.W = Wcols.p;
         t6.nv = nv;
-        hipLaunchKernelGGL(k_arn_tail6, gridD + step6.cells.nblocks, kBlock, 0,
-                           stream, c, n, gridD, partA.p, kparts(c - 1), ctl.p,
-                           histdev.p, (int)hist_cap, o->maxiter, Z.p, ld, t6,
-                           tail_extrap, step6.cells);
+        hipLaunchKernelGGL(k_arn_tail6<false>, gridD + step6.cells.nblocks,
+                           kBlock, 0, stream, c, n, gridD, partA.p,
+                           kparts(c - 1), ctl.p, histdev.p, (int)hist_cap,
+                           o->maxiter, Z.p, ld, t6, tail_extrap, step6.cells,
+                           TailLazy{});
         DNS_HIP(hipGetLastError());
         return DNS_OK;
     }
@@ -1861,7 +1908,8 @@ int dns_saddle::gmres(const double *b, double *x, const dns_solve_opts *o,
             (uint64_t)popts.cheb_degree, (uint64_t)popts.schur,
             (uint64_t)first + 2u * (uint64_t)reset, (uint64_t)fhat_explicit,
             (uint64_t)fuse_dots, (uint64_t)(uintptr_t)z_plan_override,
-            (uint64_t)dist_x0_exchange + 2u * (uint64_t)dist_lazy1,
+            (uint64_t)dist_x0_exchange + 2u * (uint64_t)dist_lazy1 +
+                4u * (uint64_t)step6_lazy,
             (uint64_t)(uintptr_t)dist_rnew};
         DNS_TRY(run_cached(key, graph, [&]() -> int {
             if (first && prologue) DNS_TRY(prologue());
@@ -2200,6 +2248,12 @@ static int dns_saddle_set_option_impl(dns_saddle *h, const char *name, double va
     else if (k == "mg_rows") h->mg_rows_knob = value != 0.0;
     else if (k == "dist_x0_exchange") h->dist_x0_exchange = value != 0.0;
     else if (k == "dist_lazy1") h->dist_lazy1 = value != 0.0;
+    else if (k == "step6_lazy") {
+        // (looked at per cycle and part of every graph key: the
+        // preconditioner and the captured graphs stay)
+        h->step6_lazy = value != 0.0;
+        return DNS_OK;
+    }
     else if (k == "cycle_first") h->cycle_first = (int)value;
     else if (k == "mg_dense_max") h->mg_dense_max = (int)value;
     else if (k == "mg_dense_half_max") h->mg_dense_half_max = (int)value;

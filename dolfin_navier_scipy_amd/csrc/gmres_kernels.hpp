@@ -245,6 +245,121 @@ k_arn_head(int n, int nv, int np, int j, const double *__restrict__ src,
     }
 }
 
+// Head of the LAZY one-column cycle of the six-node step (k_arn_tail6<true>
+// closes it): nothing but the dense Schur product zp = -Sinv tau, one wave per
+// row.  z = P^-1 r is linear in r and the minimal-residual step x0 + alpha z,
+// alpha = <r, K z> / <K z, K z>, does not depend on the scaling of r -- so no
+// norm is reduced, no V_0 = r / ||r|| is written and no control block is
+// touched in front of the rows; the tail commits all of a solve's bookkeeping.
+//   SK 1: fp64 rows, SK 2: fp32 rows (sld > 0: padded, 16-byte aligned)
+// stepctr: the device step counter behind the rhs / boundary-value tables
+// (every kernel of the step that reads a table row with the OLD count has run
+// before this one, the tail's cell workgroups read the new one: as k_arn_head)
+template <int SK>
+__global__ void __launch_bounds__(kBlock)
+k_arn_head_lazy(int np, const void *__restrict__ sinv,
+                const double *__restrict__ tau, double *__restrict__ zp,
+                int sld, int *stepctr) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int gwave = blockIdx.x * (kBlock / 64) + wave;
+    const int nwaves = gridDim.x * (kBlock / 64);
+    const size_t rst = sld ? (size_t)sld : (size_t)np;
+    for (int row = gwave; row < np; row += nwaves) {
+        const double s =
+            (SK == 1) ? dense_row_wave<double>((const double *)sinv + row * rst,
+                                               tau, np, lane)
+                      : (sld ? dense_row_wave_f4((const float *)sinv + row * rst,
+                                                 tau, np, lane)
+                             : dense_row_wave<float>(
+                                   (const float *)sinv + row * rst, tau, np,
+                                   lane));
+        if (lane == 0) zp[row] = -s;
+    }
+    if (stepctr && blockIdx.x == 0 && threadIdx.x == 0) *stepctr += 1;
+}
+
+// w = K z of the lazy one-column cycle with the partials of <r, w> and <w, w>
+//   part[wg] = <r, w>,  part[nparts + wg] = <w, w>      (nparts = gridDim.x)
+// folded to at most kBlock workgroups, so that a thread of the tail needs ONE
+// load per scalar: every sub-wave takes R CONSECUTIVE rows per pass, with the
+// pointers of all of them, then the first two chunks of all of them, in
+// flight before anything is summed (fewer, fatter workgroups: the row loads
+// hoisted).  No guard is read (the cycle never stops early); the sums run in
+// a fixed order, so the partials are the same bits run to run.
+// (measured at n = 1e4, 32 lanes per row: 3 rows x 512 threads, 222
+// workgroups, against 6 x 256, 4 x 512 and 2 x 1024: profiles/HISTORY.md)
+constexpr int kLazyRows = 3, kLazyBlock = 512;
+template <int LPR, int R, int BS>
+__global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(8)))
+k_spmv_rw(int nrows, const int *__restrict__ rowptr,
+          const int *__restrict__ colidx, const double *__restrict__ vals,
+          const double *__restrict__ z, double *__restrict__ w,
+          const double *__restrict__ r, double *__restrict__ part) {
+    __shared__ double red[BS / 64][2];
+    const int sub = (blockIdx.x * BS + threadIdx.x) / LPR;
+    const int sublane = threadIdx.x % LPR;
+    const int nsub = gridDim.x * (BS / LPR);
+    double awr = 0.0, aww = 0.0;
+    for (int base = sub * R; base < nrows; base += nsub * R) {
+        int k0[R], k1[R];
+        double rv[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            const bool on = base + q < nrows;
+            k0[q] = on ? rowptr[base + q] : 0;
+            k1[q] = on ? rowptr[base + q + 1] : 0;
+            rv[q] = on ? r[base + q] : 0.0;
+        }
+        int c0[R], c1[R];
+        double v0[R], v1[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            const int k = k0[q] + sublane;
+            const bool on0 = k < k1[q], on1 = k + LPR < k1[q];
+            c0[q] = on0 ? colidx[k] : -1;
+            v0[q] = on0 ? vals[k] : 0.0;
+            c1[q] = on1 ? colidx[k + LPR] : -1;
+            v1[q] = on1 ? vals[k + LPR] : 0.0;
+        }
+        double s[R];
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            const double z0 = c0[q] >= 0 ? z[c0[q]] : 0.0;
+            const double z1 = c1[q] >= 0 ? z[c1[q]] : 0.0;
+            s[q] = fma(v1[q], z1, v0[q] * z0);
+        }
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            // (rows longer than two chunks: rare, one entry at a time)
+            for (int k = k0[q] + sublane + 2 * LPR; k < k1[q]; k += LPR)
+                s[q] = fma(vals[k], z[colidx[k]], s[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < R; ++q) s[q] = subwave_sum<LPR>(s[q]);
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            if (sublane == 0 && base + q < nrows) {
+                w[base + q] = s[q];
+                awr = fma(rv[q], s[q], awr);
+                aww = fma(s[q], s[q], aww);
+            }
+        }
+    }
+    awr = wave_sum(awr);
+    aww = wave_sum(aww);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+        red[wave][0] = awr;
+        red[wave][1] = aww;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        double a = 0.0;
+        for (int ww = 0; ww < BS / 64; ++ww) a += red[ww][threadIdx.x];
+        part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = a;
+    }
+}
+
 // w = K z fused with the Gram-Schmidt dots  part[i*nparts + wg] = <V_i, w>
 // (i <= j).  After the row sum is known in all LPR lanes of the sub-wave,
 // lane l accumulates the dots with V_i, i = l (mod LPR).

@@ -126,6 +126,9 @@ struct dns_imex : dns::Ring {
     int chi_hi = 0;                // longest cycle length they cover (with hysteresis)
     // record of the last dns_imex_run (dns_imex_run_info)
     int run_unconverged = 0, run_first_bad = -1, run_replayed = 0;
+    // six-node steps of the accepted batches of the last run, by the kind of
+    // their cycle (lazy one-column / general)
+    int64_t run_lazy_steps = 0, run_eager_steps = 0;
     int run_captures = 0;          // graphs captured inside the last run
     // knobs read ONCE, when the stepper is created
     bool env_step_history = false, env_debug = false, env_slack_adapt = true;

@@ -653,7 +653,8 @@ std::vector<uint64_t> dns_imex::group_key(const dns_imex_coeffs *cf,
     return {9u, step_key(cf), (uint64_t)h->pipeline_c, (uint64_t)o->reorth,
             (uint64_t)o->maxiter, bits_of(o->rtol), bits_of(o->atol),
             (uint64_t)h->popts.cheb_degree, (uint64_t)h->popts.schur,
-            (uint64_t)h->fhat_explicit, (uint64_t)group, (uint64_t)o->restart};
+            (uint64_t)h->fhat_explicit, (uint64_t)group, (uint64_t)o->restart,
+            (uint64_t)h->step6_lazy};
 }
 
 // `group` pipelined steps as ONE graph (sys->pipeline_c = cycle length must be
@@ -725,6 +726,7 @@ int dns_imex::prepare_graphs(const dns_imex_coeffs *cf,
     sig = mix64(sig, bits_of(o->atol));
     sig = mix64(sig, (uint64_t)(o->reorth + 8 * o->maxiter));
     sig = mix64(sig, (uint64_t)o->restart);
+    sig = mix64(sig, (uint64_t)h->step6_lazy);     // (the kind of the c = 1 cycle)
     const int m = std::max(1, std::min(o->restart, dns::kMaxRestart));
     // (hysteresis: a prediction that moves between 3 and 4 Krylov steps -- the
     // bandwidth regime -- must not capture all ~80 graphs of a run again every
@@ -955,6 +957,8 @@ int ImexRun::run_batch() {
     }
     k += nb;
     iters += ha->acc_iters;
+    if (sixing)
+        (h->step6_lazy_for(c) ? st->run_lazy_steps : st->run_eager_steps) += nb;
     pol.after_batch({over, c_first, c, replayed, ha->acc_maxit, ha->acc_maxrel,
                      ha->acc_maxprev},
                     {h->oversolve_cmin_eff(), h->oversolve_raise,
@@ -1277,6 +1281,7 @@ static int dns_imex_run_impl(dns_imex *st, int32_t nsteps, const dns_imex_coeffs
     st->run_unconverged = 0;
     st->run_first_bad = -1;
     st->run_replayed = 0;
+    st->run_lazy_steps = st->run_eager_steps = 0;
     const int64_t captures0 = h->graph_captures;
     r.pipelined = r.o.method == DNS_METHOD_GMRES && r.o.use_graph != 0 &&
                   h->graph_capable();
@@ -1332,6 +1337,17 @@ static int dns_imex_run_info_impl(dns_imex *st, int32_t *unconverged, int32_t *f
 int dns_imex_run_info(dns_imex *st, int32_t *unconverged, int32_t *first_bad,
                       int32_t *replayed, int32_t *captures) {
     return dns::guarded([&]() -> int { return dns_imex_run_info_impl(st, unconverged, first_bad, replayed, captures); });
+}
+
+static int dns_imex_run_cycles_impl(dns_imex *st, int64_t *out2) {
+    if (!st || !out2) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    out2[0] = st->run_lazy_steps;
+    out2[1] = st->run_eager_steps;
+    return DNS_OK;
+}
+
+int dns_imex_run_cycles(dns_imex *st, int64_t *out2) {
+    return dns::guarded([&]() -> int { return dns_imex_run_cycles_impl(st, out2); });
 }
 
 static int dns_imex_get_state_impl(dns_imex *st, double *v, double *p) {

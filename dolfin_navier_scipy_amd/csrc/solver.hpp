@@ -478,6 +478,16 @@ struct dns_saddle {
     // one-step cycles without the all-reduce of the residual norm
     // (k_arn_tail_lazy1); the constants 1, 0 the head reads as "norms"
     bool dist_lazy1 = true;
+    // six-node step, one-column cycle: the head scales nothing and reduces
+    // nothing, the tail forms the step from <r, K z>, <K z, K z>, ||r||^2
+    // (k_arn_head_lazy, k_spmv_rw, k_arn_tail6<true>); longer cycles run the
+    // general nodes
+    bool step6_lazy = true;
+    // (a six-node cycle of c columns is the lazy one; the tail reads one
+    // partial of ||r||^2 per thread)
+    bool step6_lazy_for(int c) const {
+        return step6_lazy && c == 1 && gridD <= dns::kBlock;
+    }
     int cycle_first = 0;              // > 0: length of a solve's first cycle
     dns::DevBuf<double> lazy_one;
     const struct dns_halo_plan *z_plan_override = nullptr;

@@ -529,19 +529,65 @@ k_tau_first(int gt, int n, int np, int nv, const int *__restrict__ rowptr,
     }
 }
 
+// what the LAZY one-column tail reads beside the partials of the K apply:
+// the partials of ||r||^2 and ||b||^2 (k_tau_first) and the tolerances
+struct TailLazy {
+    const double *part_rr, *part_bb;
+    int nrb;                            // partials of each (<= kBlock)
+    double rtol, atol;
+};
+
+// One block-wide reduction for the four sums of the lazy tail: every thread
+// brings at most one partial of each, the result is valid in every thread and
+// the same bits in every workgroup (fixed order); `red` holds 16 doubles
+__device__ __forceinline__ void block_sum4(double &a, double &b, double &c,
+                                           double &d, double *red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        b += __shfl_xor(b, o, 64);
+        c += __shfl_xor(c, o, 64);
+        d += __shfl_xor(d, o, 64);
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+        red[4 * wave] = a;
+        red[4 * wave + 1] = b;
+        red[4 * wave + 2] = c;
+        red[4 * wave + 3] = d;
+    }
+    __syncthreads();
+    a = (red[0] + red[4]) + (red[8] + red[12]);
+    b = (red[1] + red[5]) + (red[9] + red[13]);
+    c = (red[2] + red[6]) + (red[10] + red[14]);
+    d = (red[3] + red[7]) + (red[11] + red[15]);
+}
+
 // (the first `nrow_blocks` workgroups do the rows, the rest the cells; every
 // workgroup repeats the tiny tail computation in its own LDS, workgroup 0
 // alone commits the bookkeeping -- as k_arn_tail_acc)
+// LAZY: the tail of the one-column cycle whose head scaled nothing
+// (k_arn_head_lazy, k_spmv_rw): norm_part = [<r,w> | <w,w>], nparts <= kBlock
+// partials each.  Every thread asks for its row or cell values and for one
+// partial of each of the four sums at once, ONE reduction gives
+//   alpha = <r,w> / <w,w>,   ||r - alpha w||^2 = ||r||^2 (1 - <r,w>^2 / (<w,w> ||r||^2))
+// and the stores follow; no control-block entry is read in front of them.
+// Workgroup 0 commits what k_arn_head (j = 0, first = 1) and the general tail
+// leave in the control block AFTER its stores.  A start residual inside the
+// tolerance takes no step (as the head would have stopped the cycle), r = 0
+// among them; the six-node step never oversolves (stop_frac is not read).
+template <bool LAZY>
 __global__ void __launch_bounds__(kBlock)
 k_arn_tail6(int c, int n, int nrow_blocks,
             const double *__restrict__ norm_part, int nparts, DnsCtl *ctl,
             double *__restrict__ histbuf, int hist_cap, int maxiter,
             const double *__restrict__ Z, size_t ld, Tail6 t6, TailExtrap te,
-            TailCells tc) {
+            TailCells tc, TailLazy tl) {
     __shared__ double sc[kMaxRestart + 2];
     __shared__ double yl[kMaxRestart];
     __shared__ int jl;
-    const bool open_col = !ctl->done && c > 0;
+    if (LAZY) c = 1;
+    const bool open_col = LAZY ? true : (!ctl->done && c > 0);
     const bool rowblk = (int)blockIdx.x < nrow_blocks;
     const int ef = blockIdx.x * kBlock + threadIdx.x;
     double pfx = 0.0, pz0 = 0.0, ph1 = 0.0, ph2 = 0.0, ph3 = 0.0, ph4 = 0.0,
@@ -600,8 +646,43 @@ k_arn_tail6(int c, int n, int nrow_blocks,
             if (c > 0) pw0 = t6.W[ef];
         }
     }
-    if (open_col) reduce_partials(norm_part, nparts, nparts, c + 1, sc);
-    if (threadIdx.x == 0) {
+    // lazy cycle: what workgroup 0 commits behind its stores
+    int lz_status = DNS_OK, lz_conv = 0, lz_tot = 0;
+    double lz_rho = 0.0, lz_bn = 0.0, lz_tol = 0.0, lz_res = 0.0,
+           lz_alpha = 0.0;
+    if (LAZY) {
+        const int t = threadIdx.x;
+        double wr = t < nparts ? norm_part[t] : 0.0;
+        double ww = t < nparts ? norm_part[nparts + t] : 0.0;
+        double rr = t < tl.nrb ? tl.part_rr[t] : 0.0;
+        double bb = t < tl.nrb ? tl.part_bb[t] : 0.0;
+        block_sum4(wr, ww, rr, bb, sc);
+        lz_rho = sqrt(rr);
+        lz_bn = sqrt(bb);
+        lz_tol = fmax(tl.rtol * lz_bn, tl.atol);
+        lz_res = lz_rho;
+        if (!(lz_rho > lz_tol)) {
+            // nothing to do (or NaN): the head would have stopped the cycle
+            lz_conv = lz_rho <= lz_tol;
+            if (isnan(lz_rho) || isnan(lz_tol)) lz_status = DNS_BREAKDOWN;
+        } else {
+            // (ratios, not products: <w,w> ||r||^2 may leave the range)
+            const double a = wr / ww;
+            const double d = 1.0 - a * (wr / rr);
+            if (!(d > 1e-8)) {
+                // the guard of the fused Gram-Schmidt (pythagoras_norm): the
+                // norm has lost its digits -- or w = 0, or NaN: no step
+                lz_status = kGsFallback;
+            } else {
+                lz_alpha = a;
+                lz_res = lz_rho * sqrt(d);
+                lz_tot = 1;
+                lz_conv = lz_res <= lz_tol;
+            }
+        }
+    }
+    if (!LAZY && open_col) reduce_partials(norm_part, nparts, nparts, c + 1, sc);
+    if (!LAZY && threadIdx.x == 0) {
         // (the column being closed lives in LDS: as a local array indexed
         // at run time it went to scratch memory, 528 bytes per lane of every
         // wave of the launch for one thread's use)
@@ -683,20 +764,20 @@ k_arn_tail6(int c, int n, int nrow_blocks,
             if (!nowconv) ctl->acc_fail += 1;
         }
     }
-    __syncthreads();
-    const int jcols = jl;
+    if (!LAZY) __syncthreads();
+    const int jcols = LAZY ? lz_tot : jl;
+    const double y0 = LAZY ? lz_alpha : (jcols > 0 ? yl[0] : 0.0);
     if (!rowblk) {
         // convection cells of the new velocity x0 + Z y, from the values that
         // arrived meanwhile (further columns: rare, gathered now)
         if (tc.nblocks > 0) {
-            const double y0 = jcols > 0 ? yl[0] : 0.0;
 #pragma unroll
             for (int a = 0; a < 6; ++a)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     double v = fma(y0, uz[a][i], u0[a][i]);
                     const int m = cmap[2 * a + i];
-                    if (m >= 0)
+                    if (!LAZY && m >= 0)
                         for (int j = 1; j < jcols; ++j)
                             v = fma(yl[j], Z[(size_t)j * ld + m], v);
                     u0[a][i] = v;
@@ -710,8 +791,10 @@ k_arn_tail6(int c, int n, int nrow_blocks,
     for (int e = ef; e < n; e += stride) {
         const bool first = e == ef;
         double s = first ? pfx : t6.x0[e];
-        if (jcols > 0) s = fma(yl[0], first ? pz0 : Z[e], s);
-        for (int i = 1; i < jcols; ++i) s = fma(yl[i], Z[(size_t)i * ld + e], s);
+        if (jcols > 0) s = fma(y0, first ? pz0 : Z[e], s);
+        if (!LAZY)
+            for (int i = 1; i < jcols; ++i)
+                s = fma(yl[i], Z[(size_t)i * ld + e], s);
         t6.xout[e] = s;
         if (te.out) {
             if (first) {
@@ -727,11 +810,43 @@ k_arn_tail6(int c, int n, int nrow_blocks,
         }
         if (t6.rnew && e < t6.nv) {
             double rr = first ? pr0 : t6.r0[e];
-            if (jcols > 0) rr = fma(-yl[0], first ? pw0 : t6.W[e], rr);
-            for (int i = 1; i < jcols; ++i)
-                rr = fma(-yl[i], t6.W[(size_t)i * ld + e], rr);
+            if (jcols > 0) rr = fma(-y0, first ? pw0 : t6.W[e], rr);
+            if (!LAZY)
+                for (int i = 1; i < jcols; ++i)
+                    rr = fma(-yl[i], t6.W[(size_t)i * ld + e], rr);
             t6.rnew[e] = rr;
         }
+    }
+    if (LAZY && blockIdx.x == 0 && threadIdx.x == 0) {
+        // the solve's record, behind this workgroup's stores: what k_arn_head
+        // (j = 0, first = 1) and the general tail above leave
+        ctl->predone = 0;
+        ctl->jdone = lz_tot;
+        ctl->zero = 0;
+        ctl->done = 1;
+        ctl->status = lz_status;
+        ctl->total_it = lz_tot;
+        ctl->conv = lz_conv;
+        ctl->need_it = lz_conv ? lz_tot : -1;
+        ctl->beta = lz_rho;
+        ctl->tol = lz_tol;
+        ctl->resnorm = lz_res;
+        ctl->bnorm = lz_bn;
+        ctl->g[0] = lz_rho;
+        ctl->hist[0] = lz_rho;
+        ctl->hist[1] = lz_res;
+        int hl = 0;
+        if (hl < hist_cap) histbuf[hl++] = lz_rho;
+        if (lz_tot > 0 && hl < hist_cap) histbuf[hl++] = lz_res;
+        ctl->hist_len = hl;
+        ctl->acc_solves += 1;
+        ctl->acc_iters += lz_tot;
+        if (lz_tot > ctl->acc_maxit) ctl->acc_maxit = lz_tot;
+        if (lz_conv && lz_tol > 0.0) {
+            const double rel = lz_res / lz_tol;
+            if (rel > ctl->acc_maxrel) ctl->acc_maxrel = rel;
+        }
+        if (!lz_conv) ctl->acc_fail += 1;
     }
 }
 

@@ -420,7 +420,9 @@ class ImexStepper(object):
         `(device_seconds, total_iters, last_stats)`.  `last_run` then holds the
         record of the call: time steps whose solve ended at `maxiter`
         (`unconverged`, `first_bad`), steps repeated after a mispredicted
-        batch (`replayed`) and graphs captured inside the call (`captures`).
+        batch (`replayed`), graphs captured inside the call (`captures`) and
+        the six-node steps by the kind of their cycle (`lazy_steps`,
+        `eager_steps`).
         Raises `NotConverged` if any step did not converge, like `step()`."""
         o = solve_opts() if opts is None else opts
         st = C.dns_solve_stats()
@@ -439,6 +441,10 @@ class ImexStepper(object):
                                            *[ct.byref(v) for v in vals]))
         self.last_run = dict(zip(('unconverged', 'first_bad', 'replayed',
                                   'captures'), [v.value for v in vals]))
+        kinds = (ct.c_int64*2)()
+        C.check(self.lib.dns_imex_run_cycles(self._h, kinds))
+        self.last_run['lazy_steps'] = int(kinds[0])
+        self.last_run['eager_steps'] = int(kinds[1])
         if status == C.DNS_NOT_CONVERGED and raise_on_fail:
             C.check(status)
         return secs.value, its.value, self.last_stats

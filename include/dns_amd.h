@@ -418,6 +418,10 @@ int dns_imex_run_info(dns_imex *st, int32_t *unconverged, int32_t *first_bad,
  * velocity in its tail, out[2] = the steps that left the cell kernel out
  * because the tail before had run it */
 int dns_imex_step_counters(dns_imex *st, int64_t *out3);
+/* six-node steps of the accepted batches of the last dns_imex_run by the kind
+ * of their Krylov cycle: out[0] = lazy one-column cycles ("step6_lazy"),
+ * out[1] = general cycles */
+int dns_imex_run_cycles(dns_imex *st, int64_t *out2);
 /* v (NV) and p = pscale*p~ (NP) of the current state */
 int dns_imex_get_state(dns_imex *st, double *v, double *p);
 /* ||v||_2 of the current velocity (blow-up guard, tiu:94-103) */
@@ -524,6 +528,10 @@ int dns_saddle_set_schur_mg(dns_saddle *h, int32_t nprol, const dns_csr *prol,
  *   "dist_lazy1"    0/1: one-step cycles of a partitioned solve leave the
  *                   first basis vector un-normalised; ||r||, ||b|| travel with
  *                   the step's dots (one all-reduce per time step less)
+ *   "step6_lazy"    0/1: one-column cycles of the six-node resident step
+ *                   normalise nothing: the head is the Schur product alone,
+ *                   the tail forms the step from <r,Kz>, <Kz,Kz>, ||r||^2
+ *                   (default 1, DNS_STEP6_LAZY; longer cycles are general)
  *   "dist_x0_exchange"  0/1: halo exchange of the start vector at the head of
  *                   every cycle of a partitioned solve (default 0: it is valid)
  *   "part_setup"    0/1: with a communicator, every rank forms only the rows
