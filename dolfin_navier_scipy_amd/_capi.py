@@ -167,6 +167,19 @@ SIGNATURES = {
                                 ct.POINTER(ct.c_int64)]),
     'dns_imex_get_state': (ct.c_int, [_VP, c_double_p, c_double_p]),
     'dns_imex_vnorm': (ct.c_int, [_VP, c_double_p]),
+    'dns_imex_set_feedback': (ct.c_int, [_VP, ct.POINTER(dns_csr),
+                                         ct.POINTER(dns_csr), c_double_p,
+                                         c_double_p, c_double_p, ct.c_int32,
+                                         ct.c_int32, ct.c_int32, ct.c_double,
+                                         ct.c_double, ct.c_double]),
+    'dns_imex_set_feedback_state': (ct.c_int, [_VP, c_double_p, c_double_p,
+                                               c_double_p]),
+    'dns_imex_get_feedback_state': (ct.c_int, [_VP, c_double_p, c_double_p,
+                                               c_double_p]),
+    'dns_imex_set_feedback_table': (ct.c_int, [_VP, ct.c_int32, c_double_p]),
+    'dns_imex_get_feedback_log': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
+                                             c_double_p, c_double_p]),
+    'dns_imex_clear_feedback': (ct.c_int, [_VP]),
     'dns_imex_run_info': (ct.c_int, [_VP, c_int32_p, c_int32_p, c_int32_p,
                                      c_int32_p]),
     'dns_imex_step_counters': (ct.c_int, [_VP, ct.POINTER(ct.c_int64)]),

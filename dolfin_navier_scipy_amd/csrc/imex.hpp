@@ -2,6 +2,7 @@
 #pragma once
 #include "batch_policy.hpp"
 #include "convection.hpp"
+#include "feedback.hpp"
 #include "ring.hpp"
 #include "solver.hpp"
 #include "trap.hpp"
@@ -96,20 +97,45 @@ struct dns_imex : dns::Ring {
     // the last prepare_graphs call went past its "already prepared" exit, i.e.
     // it captured (or tried to): the same on every rank of a partitioned run
     bool prepare_attempted = false;
+    // observer feedback (feedback.hpp): k_lti_step runs in front of every
+    // step and leaves the right-hand side with the actuation in `geff`, which
+    // the front kernels then read through g_ref().  The state slot that holds
+    // the current hx / f_last / u_c is `tab_pos & 1`: the step counter selects
+    // the slot, the drift row and the log row alike, so a restored batch
+    // (HostState::tab_pos, sync_counter) replays all three.
+    struct Feedback {
+        bool on = false;
+        int hN = 0, Ny = 0, Nu = 0;
+        int rows = 0;              // drift rows = log capacity (0: no table yet)
+        bool has_drift = false;
+        double dt = 0.0, c_n = 0.0, c_c = 0.0;
+        dns::CsrDev C, B;
+        dns::DevBuf<double> haT, hbT, hc, drift, state, ylog, ulog, geff;
+        int stride() const { return 2 * hN + Nu; }
+    } fb;
+    int fb_rebase();               // current slot -> slot 0 (counter reset)
+    int fb_launch(hipStream_t s);  // k_lti_step for the step about to run
+    uint64_t fb_key() const;
     // a step counter is needed as soon as anything is tabulated
     bool tables() const {
-        return tab_rows > 0 || (conv && conv->dbc_rows > 0);
+        return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on;
     }
     int rows_left() const {
         int lim = 1 << 30;
         if (tab_rows > 0) lim = std::min(lim, tab_rows);
+        if (fb.on) lim = std::min(lim, fb.rows);
         if (conv && conv->dbc_rows > 0) lim = std::min(lim, conv->dbc_rows);
         return lim - tab_pos;
     }
-    dns::TabRef g_ref() const {
+    dns::TabRef g_src() const {
         if (tab_rows > 0 && tab_v)
             return {gtab.p, stepctr.p, sys->nv, tab_rows};
         return {g.p, nullptr, 0, 1};
+    }
+    // (with feedback: what k_lti_step has made of g_src() for this step)
+    dns::TabRef g_ref() const {
+        if (fb.on) return {fb.geff.p, nullptr, 0, 1};
+        return g_src();
     }
     dns::TabRef gp_ref() const {
         if (tab_rows > 0 && tab_p)

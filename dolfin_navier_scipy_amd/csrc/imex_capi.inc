@@ -30,7 +30,57 @@ uint64_t dns_imex::step_key(const dns_imex_coeffs *cf) const {
     pkey = mix64(pkey, (uint64_t)tab_rows);
     pkey = mix64(pkey, (uint64_t)((cf->carry_residual != 0) + 2 * carry_ok +
                                   4 * six_ok + 8 * dcells_ok));
+    if (fb.on) pkey = mix64(pkey, fb_key());
     return pkey;
+}
+
+// "feedback on", its shape, its coefficients and every buffer k_lti_step is
+// handed: a graph captured for another set must not be replayed
+uint64_t dns_imex::fb_key() const {
+    uint64_t k = 0xfb;
+    k = mix64(k, (uint64_t)(fb.hN + 256 * fb.Ny + 65536 * fb.Nu));
+    k = mix64(k, (uint64_t)fb.rows + ((uint64_t)fb.has_drift << 40));
+    k = mix64(k, bits_of(fb.dt));
+    k = mix64(k, bits_of(fb.c_n));
+    k = mix64(k, bits_of(fb.c_c));
+    for (const void *q : {(const void *)fb.C.vals.p, (const void *)fb.B.vals.p,
+                          (const void *)fb.haT.p, (const void *)fb.drift.p,
+                          (const void *)fb.state.p, (const void *)fb.ylog.p,
+                          (const void *)fb.ulog.p, (const void *)fb.geff.p,
+                          (const void *)g.p})
+        k = mix64(k, (uint64_t)(uintptr_t)q);
+    return k;
+}
+
+int dns_imex::fb_launch(hipStream_t s) {
+    if (fb.rows < 1)
+        return dns::fail(DNS_ERR_NOT_READY, "observer feedback without a "
+                         "table (dns_imex_set_feedback_table)");
+    const dns::LtiArgs a{stepctr.p, fb.rows, fb.hN, fb.Ny, fb.Nu, sys->nv,
+                         fb.C.rowptr.p, fb.C.colidx.p, fb.C.vals.p,
+                         fb.B.rowptr.p, fb.B.colidx.p, fb.B.vals.p,
+                         fb.haT.p, fb.hbT.p, fb.hc.p,
+                         fb.has_drift ? fb.drift.p : (const double *)nullptr,
+                         fb.state.p, fb.ylog.p, fb.ulog.p, fb.dt, fb.c_n,
+                         fb.c_c, g_src(), xs[cur].p, fb.geff.p};
+    if (dns::lti_staged(fb.hN, fb.Ny, fb.Nu))
+        hipLaunchKernelGGL(dns::k_lti_step<true>, dns::lti_grid(sys->nv),
+                           dns::kBlock, 0, s, a);
+    else
+        hipLaunchKernelGGL(dns::k_lti_step<false>, dns::lti_grid(sys->nv),
+                           dns::kBlock, 0, s, a);
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+// The step counter is about to be set back to 0 (new tables): the slot of the
+// current observer state is `tab_pos & 1`, slot 0 from then on.
+int dns_imex::fb_rebase() {
+    if (!fb.on || (tab_pos & 1) == 0) return DNS_OK;
+    const size_t n = (size_t)fb.stride();
+    DNS_HIP(hipMemcpyAsync(fb.state.p, fb.state.p + n, n * sizeof(double),
+                           hipMemcpyDeviceToDevice, sys->stream));
+    return DNS_OK;
 }
 
 // R1 (or this rank's rows of it, starting at the even global row `v0`) in the
@@ -120,6 +170,9 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
     // blocks are known (ensure_partition below)
     bool dfront = false, dcarry = false, dtail = false, have_cells = false;
     auto prologue = [&]() -> int {
+        // observer feedback: the first node of the step, whatever its form
+        // (xs[cur] is complete: the tail of the step before has finished)
+        if (fb.on) DNS_TRY(fb_launch(s));
         const double *vc = xs[cur].p;
         const double *vp = (nsol >= 2) ? xs[prev].p : xs[cur].p;
         const int ex = cf->extrapolate_x0;
@@ -326,6 +379,10 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
              nsol >= 2;
     dtail = dfront && dtail_wanted(o) && x0c.p != nullptr;
     have_cells = dfront && conv && dcells_ok && dcells_gen == conv->dbc_gen;
+    if (fb.on && (h->dist() || part.on))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "observer feedback on a partitioned system: the "
+                         "outputs y = C v would need an all-reduce");
     if (tables()) {
         if (o->method != DNS_METHOD_GMRES)
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
@@ -334,7 +391,8 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
             return dns::fail(DNS_ERR_NOT_READY,
                              "the per-step tables are used up after %d steps: "
                              "upload the next ones (dns_imex_set_rhs_table / "
-                             "dns_conv_set_dbc_table)", tab_pos);
+                             "dns_conv_set_dbc_table / "
+                             "dns_imex_set_feedback_table)", tab_pos);
     }
     if (conv) conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
     if (o->method == DNS_METHOD_GMRES) {
@@ -718,6 +776,7 @@ int dns_imex::prepare_graphs(const dns_imex_coeffs *cf,
     sig = mix64(sig, (uint64_t)(uintptr_t)gtab.p);
     sig = mix64(sig, (uint64_t)(uintptr_t)gptab.p);
     sig = mix64(sig, (uint64_t)tab_rows);
+    if (fb.on) sig = mix64(sig, fb_key());
     if (conv) {
         sig = mix64(sig, (uint64_t)conv->dbc_rows);
         sig = mix64(sig, (uint64_t)(uintptr_t)conv->dbc_tab.p);
@@ -871,6 +930,13 @@ int ImexRun::run_batch() {
     if (carrying) {
         DNS_TRY(ck.add(st->b.p, h->ld));
         DNS_TRY(ck.add(st->rcarry.p, h->nv));
+    }
+    // observer feedback: both slots of the state and the right-hand side it
+    // left (the slot, the drift row and the log row come back with the step
+    // counter; the log rows of a discarded batch are overwritten)
+    if (st->fb.on) {
+        DNS_TRY(ck.add(st->fb.state.p, (size_t)2 * st->fb.stride()));
+        DNS_TRY(ck.add(st->fb.geff.p, h->nv));
     }
     const dns_imex::HostState hs0 = st->host_state();
     // back to the checkpoint, then what derives from it: K x products of the
@@ -1185,6 +1251,7 @@ static int dns_imex_set_rhs_table_impl(dns_imex *st, int32_t nsteps, const doubl
     st->tab_v = gv != nullptr;
     st->tab_p = gp != nullptr;
     st->tab_rows = nsteps;
+    DNS_TRY(st->fb_rebase());
     st->tab_pos = 0;
     st->six_ok = false;      // (cell values belong to a row of the old tables)
     st->dcells_ok = false;
@@ -1348,6 +1415,211 @@ static int dns_imex_run_cycles_impl(dns_imex *st, int64_t *out2) {
 
 int dns_imex_run_cycles(dns_imex *st, int64_t *out2) {
     return dns::guarded([&]() -> int { return dns_imex_run_cycles_impl(st, out2); });
+}
+
+// ---- observer feedback (feedback.hpp) --------------------------------------
+
+static int dns_imex_set_feedback_impl(dns_imex *st, const dns_csr *cmat,
+                                      const dns_csr *bmat, const double *ha,
+                                      const double *hb, const double *hc,
+                                      int32_t hN, int32_t Ny, int32_t Nu,
+                                      double c_n, double c_c, double dt) {
+    if (!st || !cmat || !bmat || !ha || !hb || !hc)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_saddle *h = st->sys;
+    if (st->r1_rows || st->part.on || h->dist())
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "observer feedback on a row-partitioned stepper: the "
+                         "outputs y = C v would need an all-reduce (multi-rank "
+                         "feedback is not supported)");
+    if (hN < 1 || hN > dns::kFbMaxState || Ny < 1 || Ny > dns::kFbMaxOut ||
+        Nu < 1 || Nu > dns::kFbMaxIn)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "observer feedback: hN = %d, Ny = %d, Nu = %d outside "
+                         "the limits 1..%d, 1..%d, 1..%d of the one-launch "
+                         "observer step", (int)hN, (int)Ny, (int)Nu,
+                         dns::kFbMaxState, dns::kFbMaxOut, dns::kFbMaxIn);
+    DNS_TRY(dns::check_csr(cmat, "C"));
+    DNS_TRY(dns::check_csr(bmat, "B"));
+    if (cmat->nrows != Ny || cmat->ncols != h->nv)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "C must be Ny x NV (%d x %d)",
+                         (int)Ny, h->nv);
+    if (bmat->nrows != h->nv || bmat->ncols != Nu)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "B must be NV x Nu (%d x %d)",
+                         h->nv, (int)Nu);
+    if (cmat->nnz > dns::kFbMaxNnzC)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "observer feedback: C has %lld non-zeros, the "
+                         "one-launch observer step takes at most %d",
+                         (long long)cmat->nnz, dns::kFbMaxNnzC);
+    if (!(dt > 0.0))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "observer feedback: dt <= 0");
+    DNS_HIP(hipSetDevice(h->device));
+    DNS_HIP(hipStreamSynchronize(h->stream));   // replays may still read it
+    dns_imex::Feedback &f = st->fb;
+    f.on = false;
+    hipStream_t s = h->stream;
+    DNS_TRY(f.C.upload(cmat, s));
+    DNS_TRY(f.B.upload(bmat, s));
+    const size_t n = (size_t)hN;
+    std::vector<double> haT(n * n), hbT(n * Ny);
+    for (size_t i = 0; i < n; ++i) {
+        for (size_t j = 0; j < n; ++j) haT[j * n + i] = ha[i * n + j];
+        for (size_t k = 0; k < (size_t)Ny; ++k) hbT[k * n + i] = hb[i * Ny + k];
+    }
+    DNS_TRY(f.haT.alloc(n * n));
+    DNS_TRY(f.haT.upload(haT.data(), n * n, s));
+    DNS_TRY(f.hbT.alloc(n * Ny));
+    DNS_TRY(f.hbT.upload(hbT.data(), n * Ny, s));
+    DNS_TRY(f.hc.alloc(n * Nu));
+    DNS_TRY(f.hc.upload(hc, n * Nu, s));
+    f.hN = hN;
+    f.Ny = Ny;
+    f.Nu = Nu;
+    DNS_TRY(f.state.alloc((size_t)2 * f.stride()));
+    DNS_TRY(f.state.zero(s));
+    if (f.geff.n < (size_t)h->nv) DNS_TRY(f.geff.alloc((size_t)h->nv));
+    DNS_TRY(f.geff.zero(s));
+    f.rows = 0;
+    f.has_drift = false;
+    f.dt = dt;
+    f.c_n = c_n;
+    f.c_c = c_c;
+    DNS_HIP(hipStreamSynchronize(s));
+    f.on = true;
+    return DNS_OK;
+}
+
+int dns_imex_set_feedback(dns_imex *st, const dns_csr *cmat, const dns_csr *bmat,
+                          const double *ha, const double *hb, const double *hc,
+                          int32_t hN, int32_t Ny, int32_t Nu, double c_n,
+                          double c_c, double dt) {
+    return dns::guarded([&]() -> int { return dns_imex_set_feedback_impl(st, cmat, bmat, ha, hb, hc, hN, Ny, Nu, c_n, c_c, dt); });
+}
+
+static int fb_need(dns_imex *st) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (!st->fb.on)
+        return dns::fail(DNS_ERR_NOT_READY, "no observer feedback is set "
+                         "(dns_imex_set_feedback)");
+    return hipSetDevice(st->sys->device) == hipSuccess
+               ? DNS_OK : dns::fail(DNS_ERR_HIP, "hipSetDevice failed");
+}
+
+static int dns_imex_set_feedback_state_impl(dns_imex *st, const double *hx,
+                                            const double *f_last,
+                                            const double *u_c) {
+    DNS_TRY(fb_need(st));
+    if (!hx || !f_last || !u_c)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_imex::Feedback &f = st->fb;
+    hipStream_t s = st->sys->stream;
+    DNS_HIP(hipStreamSynchronize(s));
+    double *slot = f.state.p + (size_t)(st->tab_pos & 1) * f.stride();
+    DNS_TRY(dns::upload_to(slot, hx, (size_t)f.hN, s));
+    DNS_TRY(dns::upload_to(slot + f.hN, f_last, (size_t)f.hN, s));
+    DNS_TRY(dns::upload_to(slot + 2 * f.hN, u_c, (size_t)f.Nu, s));
+    return DNS_OK;
+}
+
+int dns_imex_set_feedback_state(dns_imex *st, const double *hx,
+                                const double *f_last, const double *u_c) {
+    return dns::guarded([&]() -> int { return dns_imex_set_feedback_state_impl(st, hx, f_last, u_c); });
+}
+
+static int dns_imex_get_feedback_state_impl(dns_imex *st, double *hx,
+                                            double *f_last, double *u_c) {
+    DNS_TRY(fb_need(st));
+    const dns_imex::Feedback &f = st->fb;
+    hipStream_t s = st->sys->stream;
+    const double *slot = f.state.p + (size_t)(st->tab_pos & 1) * f.stride();
+    if (hx) DNS_TRY(dns::download_from(hx, slot, (size_t)f.hN, s));
+    if (f_last)
+        DNS_TRY(dns::download_from(f_last, slot + f.hN, (size_t)f.hN, s));
+    if (u_c) DNS_TRY(dns::download_from(u_c, slot + 2 * f.hN, (size_t)f.Nu, s));
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+}
+
+int dns_imex_get_feedback_state(dns_imex *st, double *hx, double *f_last,
+                                double *u_c) {
+    return dns::guarded([&]() -> int { return dns_imex_get_feedback_state_impl(st, hx, f_last, u_c); });
+}
+
+static int dns_imex_set_feedback_table_impl(dns_imex *st, int32_t nsteps,
+                                            const double *drift) {
+    DNS_TRY(fb_need(st));
+    if (nsteps < 1) return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
+    dns_imex::Feedback &f = st->fb;
+    dns_saddle *h = st->sys;
+    hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still read it
+    const size_t ns = (size_t)nsteps;
+    if (drift) {
+        if (f.drift.n < ns * f.hN) DNS_TRY(f.drift.alloc(ns * f.hN));
+        DNS_TRY(f.drift.upload(drift, ns * f.hN, s));
+    }
+    if (f.ylog.n < ns * f.Ny) DNS_TRY(f.ylog.alloc(ns * f.Ny));
+    if (f.ulog.n < ns * f.Nu) DNS_TRY(f.ulog.alloc(ns * f.Nu));
+    DNS_TRY(f.ylog.zero(s));
+    DNS_TRY(f.ulog.zero(s));
+    f.has_drift = drift != nullptr;
+    f.rows = nsteps;
+    // the step counter selects the drift row, the log row and the state slot
+    // (and the rows of the other tables): back to 0, as after
+    // dns_imex_set_rhs_table
+    DNS_TRY(st->fb_rebase());
+    st->tab_pos = 0;
+    st->six_ok = false;
+    st->dcells_ok = false;
+    DNS_TRY(st->sync_counter());
+    if (st->conv && st->conv->dbc_rows > 0) st->conv->dbc_row = 0;
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+}
+
+int dns_imex_set_feedback_table(dns_imex *st, int32_t nsteps,
+                                const double *drift) {
+    return dns::guarded([&]() -> int { return dns_imex_set_feedback_table_impl(st, nsteps, drift); });
+}
+
+static int dns_imex_get_feedback_log_impl(dns_imex *st, int32_t first,
+                                          int32_t count, double *y, double *u) {
+    DNS_TRY(fb_need(st));
+    const dns_imex::Feedback &f = st->fb;
+    if (first < 0 || count < 0 || first + count > f.rows)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "log rows [%d, %d) asked for, the table holds %d",
+                         (int)first, (int)(first + count), f.rows);
+    hipStream_t s = st->sys->stream;
+    if (y && count)
+        DNS_TRY(dns::download_from(y, f.ylog.p + (size_t)first * f.Ny,
+                                   (size_t)count * f.Ny, s));
+    if (u && count)
+        DNS_TRY(dns::download_from(u, f.ulog.p + (size_t)first * f.Nu,
+                                   (size_t)count * f.Nu, s));
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+}
+
+int dns_imex_get_feedback_log(dns_imex *st, int32_t first, int32_t count,
+                              double *y, double *u) {
+    return dns::guarded([&]() -> int { return dns_imex_get_feedback_log_impl(st, first, count, y, u); });
+}
+
+static int dns_imex_clear_feedback_impl(dns_imex *st) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (!st->fb.on) return DNS_OK;
+    DNS_HIP(hipSetDevice(st->sys->device));
+    DNS_HIP(hipStreamSynchronize(st->sys->stream));
+    st->fb.on = false;
+    st->fb.rows = 0;
+    // (the counter goes on counting for the other tables, if any)
+    return DNS_OK;
+}
+
+int dns_imex_clear_feedback(dns_imex *st) {
+    return dns::guarded([&]() -> int { return dns_imex_clear_feedback_impl(st); });
 }
 
 static int dns_imex_get_state_impl(dns_imex *st, double *v, double *p) {

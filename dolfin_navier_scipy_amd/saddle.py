@@ -456,6 +456,74 @@ class ImexStepper(object):
         C.check(self.lib.dns_imex_step_counters(self._h, buf))
         return tuple(int(b) for b in buf)
 
+    # ---- observer feedback (`dns_imex_set_feedback*`) ----------------------
+    def set_feedback(self, cv_mat, b_mat, ha, hb, hc, c_n, c_c, dt):
+        """closed loop with a linear observer on the device: before every step
+        `y = cv_mat v_c`, `hx' = ha hx + hb y + drift` (AB2), `u = hc hx` and
+        `dt*(c_n b_mat u_n + c_c b_mat u_c)` added to the right-hand side
+        (`include/dns_amd.h`; CNAB `c_n = c_c = 1/2`, SBDF2 `2/3, 0`).  The
+        observer state and the drift / log table follow through
+        `set_feedback_state` and `set_feedback_table`."""
+        ha = np.ascontiguousarray(ha, dtype=np.float64)
+        hN = ha.shape[0]
+        hb = np.ascontiguousarray(np.asarray(hb, dtype=np.float64)
+                                  .reshape((hN, -1)))
+        hc = np.ascontiguousarray(np.asarray(hc, dtype=np.float64)
+                                  .reshape((-1, hN)))
+        Ny, Nu = hb.shape[1], hc.shape[0]
+        if ha.shape != (hN, hN):
+            raise ValueError('ha must be square')
+        cview, bview = C.CsrView(cv_mat), C.CsrView(b_mat)
+        if cview.shape != (Ny, self.sys.NV) or bview.shape != (self.sys.NV, Nu):
+            raise ValueError('cv_mat must be Ny x NV and b_mat NV x Nu')
+        C.check(self.lib.dns_imex_set_feedback(
+            self._h, cview.byref(), bview.byref(), C.dptr(ha.reshape(-1)),
+            C.dptr(hb.reshape(-1)), C.dptr(hc.reshape(-1)), hN, Ny, Nu,
+            float(c_n), float(c_c), float(dt)))
+        self._fb_shape = (hN, Ny, Nu)
+
+    def clear_feedback(self):
+        C.check(self.lib.dns_imex_clear_feedback(self._h))
+        self._fb_shape = None
+
+    def set_feedback_state(self, hx, f_last, u_c):
+        hN, _, Nu = self._fb_shape
+        args = [C.as_f64(hx, hN), C.as_f64(f_last, hN), C.as_f64(u_c, Nu)]
+        C.check(self.lib.dns_imex_set_feedback_state(
+            self._h, *[C.dptr(a) for a in args]))
+
+    def feedback_state(self):
+        """`(hx, f_last, u_c)` of the current time"""
+        hN, _, Nu = self._fb_shape
+        hx, fl, uc = np.empty(hN), np.empty(hN), np.empty(Nu)
+        C.check(self.lib.dns_imex_get_feedback_state(
+            self._h, C.dptr(hx), C.dptr(fl), C.dptr(uc)))
+        return hx, fl, uc
+
+    def set_feedback_table(self, nsteps, drift=None):
+        """room for `nsteps` steps: their drift rows `(nsteps, hN)` (None: no
+        drift) and as many rows of the `y` / `u` logs; resets the step counter
+        like `set_rhs_table` (call it after that one)"""
+        hN = self._fb_shape[0]
+        tab = None if drift is None else np.ascontiguousarray(
+            drift, dtype=np.float64).reshape((int(nsteps), hN))
+        C.check(self.lib.dns_imex_set_feedback_table(
+            self._h, int(nsteps), C.dptr(None if tab is None
+                                         else tab.reshape(-1))))
+
+    def feedback_log(self, first=0, count=None):
+        """`(y, u)`: rows `first .. first + count` of the logs -- what the
+        steps since `set_feedback_table` measured and actuated (default: all
+        steps taken since)"""
+        _, Ny, Nu = self._fb_shape
+        if count is None:
+            count = self.table_position()[0] - first
+        y, u = np.empty((count, Ny)), np.empty((count, Nu))
+        C.check(self.lib.dns_imex_get_feedback_log(
+            self._h, int(first), int(count), C.dptr(y.reshape(-1)),
+            C.dptr(u.reshape(-1))))
+        return y, u
+
     def get_state(self):
         v = np.empty(self.sys.NV)
         p = np.empty(self.sys.NP)

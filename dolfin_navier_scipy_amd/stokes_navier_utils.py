@@ -353,6 +353,7 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
               check_ff_maxv=1e8, verbose=False, start_ssstokes=False,
               closed_loop=False, dynamic_feedback=False, static_feedback=False,
               b_mat=None, feedbackthroughdict=None,
+              dyn_fb_dict=None, dyn_fb_disc='trapezoidal',
               vp_output=False, vp_out_fun=None, vp_output_dict=None,
               solver=None, device=0, bcs_time_only=False,
               applybcs_literal=True, **kw):
@@ -369,8 +370,18 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     sides and the low-rank term `dt/2 b_mat mtxtb^T` to the system
     (`TrapezoidalStepper.step(feedback=)`, Sherman-Morrison-Woodbury on the
     device).  In the explicit schemes the reference's static feedback does
-    nothing (snu:1261-1262) and neither does it here; `dynamic_feedback`
-    (observer helpers of `tiu`, SURVEY section 2: out of scope) raises.
+    nothing (snu:1261-1262) and neither does it here.  `dynamic_feedback`
+    with `closed_loop` and `dyn_fb_disc='AB2'` (snu:566-567, 1237-1247): output
+    feedback through the linear observer of `dyn_fb_dict` (`ha, hb, hc, inihx`
+    and the callable `drift`; `hx' = ha hx + hb cv_mat v + drift(t)`,
+    `b_mat hc hx` added to the right-hand side, Heun start + AB2) -- a
+    `time_int_utils.LinearFeedback` handed to `cnab` / `sbdftwo`, which run it
+    device resident whenever the open loop would run resident
+    (`time_int_utils.LAST_RUN['feedback']`).  `dyn_fb_disc='linear_implicit'`
+    (the extended system of `nse_include_lnrcntrllr`) raises
+    `NotImplementedError`, and so does the default `'trapezoidal'`: there the
+    reference builds `implicit_dynamic_rhs` and never hands it to the
+    integrator (snu:1231-1235, 1267-1272), so there is nothing to match.
     Extra keywords: `solver`
     (overrides `time_int_utils.SOLVER`), `device`, `bcs_time_only` (the
     control functions `diricontfuncs` ignore `vel`/`p`: the explicit loop may
@@ -379,10 +390,24 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     reference's does with snu:1112 commented out; False: the controlled values
     are written into the auxiliary vector, see `bcs.make_applybcs`).
     """
-    if dynamic_feedback:
-        raise NotImplementedError('observer-based (dynamic) feedback is '
-                                  'outside the MI355X path (SURVEY.md '
-                                  'section 2)')
+    if dynamic_feedback and dyn_fb_disc == 'linear_implicit':
+        raise NotImplementedError("`dyn_fb_disc='linear_implicit'` (the "
+                                  'extended system of '
+                                  '`nse_include_lnrcntrllr`) is outside the '
+                                  "MI355X path; `'AB2'` is supported")
+    if dynamic_feedback and dyn_fb_disc != 'AB2':
+        raise NotImplementedError(
+            "`dyn_fb_disc={0!r}`: for 'trapezoidal' the reference builds "
+            '`implicit_dynamic_rhs` and never hands it to the integrator '
+            '(snu:1231-1235, 1267-1272), so there is nothing to match; '
+            "`'AB2'` is supported".format(dyn_fb_disc))
+    dyn_fb = bool(closed_loop and dynamic_feedback)   # (snu:1224-1225)
+    if dyn_fb and not (treat_nonl_explicit and lin_vel_point is None):
+        raise NotImplementedError('observer feedback (`dynamic_feedback`) '
+                                  'needs the explicit schemes (cnab / sbdf2)')
+    if dyn_fb and (dyn_fb_dict is None or b_mat is None or cv_mat is None):
+        raise ValueError('`dynamic_feedback` needs `dyn_fb_dict`, `b_mat` '
+                         'and `cv_mat`')
     if closed_loop and not treat_nonl_explicit and \
             (b_mat is None or feedbackthroughdict is None):
         raise ValueError('`closed_loop` in the Newton/Picard sweeps needs '
@@ -526,6 +551,11 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
                    solver=solver)
         if time_int_scheme == 'cnab':
             icd.update(f_tvdp=fvtvd)
+        if dyn_fb:
+            dfb = dyn_fb_dict
+            icd.update(dynamic_rhs=tiu.LinearFeedback(
+                cv_mat, b_mat, dfb['ha'], dfb['hb'], dfb['hc'], dfb['inihx'],
+                drift=dfb.get('drift')), dynamic_rhs_memory={})
         static_bcs = len(loccnt) == 0
         if cvop is not None and (static_bcs or bcs_time_only):
             # the loop may evaluate N(v)v itself and, the callbacks being

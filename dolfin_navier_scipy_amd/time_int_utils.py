@@ -11,10 +11,14 @@ Krylov iteration of `csrc/` (instead of `spsla.factorized`, tiu:89-91,134).
  * `semi_implicit_euler` (tiu:566-635)
  * `_onestepheun`        (tiu:366-477)  two boundary solves via `lin_alg_utils`
  * `_inittimegrid`       (tiu:480-489)
+ * `LinearFeedback`      (tiu:148-196 composed as in snu:1243-1247) observer
+                         feedback as a `dynamic_rhs` the loops can run resident
 
 Per step the host still evaluates the reference's callbacks (`f_vdp`, `getbcs`,
 `applybcs`, `f_tdp`, `g_tdp`, `dynamic_rhs`, `savevp`) because they are the
-caller's Python code; everything between them is on the device.
+caller's Python code; everything between them is on the device.  A
+`dynamic_rhs` that is a `LinearFeedback` is no such callback: its arithmetic is
+known, and `cnab` / `sbdftwo` hand it to the device with the rest of the step.
 """
 import logging
 
@@ -24,7 +28,8 @@ import scipy.sparse as sps
 from . import lin_alg_utils as lau
 from .saddle import SaddleSystem, ImexStepper, solve_opts, choose_schur
 
-__all__ = ['cnab', 'sbdftwo', 'semi_implicit_euler', 'SOLVER']
+__all__ = ['cnab', 'sbdftwo', 'semi_implicit_euler', 'SOLVER',
+           'LinearFeedback']
 
 # solver settings of the time loops; `rtol` is relative to ||rhs||.  `None`:
 # `lin_alg_utils.default_rtol` of the system at hand -- 1e-12, and 1e-13 where
@@ -43,16 +48,153 @@ SOLVER = dict(method='gmres', rtol=None, maxiter=400, restart=60,
 LAST_RUN = {}
 
 
-def _record_run(name, system, stepper):
+def _record_run(name, system, stepper, feedback=None, fb_logs=None):
+    """`feedback`: 'resident' (observer on the device), 'host' (a
+    `dynamic_rhs` called every step) or None (open loop); `fb_logs`: the
+    `(y, u)` rows of the AB2 steps where the loop knows them"""
     LAST_RUN.clear()
     try:        # (runs in a `finally`: never in the way of the real error)
+        ylog, ulog = fb_logs if fb_logs is not None else (None, None)
         LAST_RUN.update(
             integrator=name, time_steps=stepper.total_steps,
             krylov_steps=stepper.total_iters,
             schur_hierarchy=getattr(system, 'schur_hierarchy', None),
-            precond=system.precond_info())
+            precond=system.precond_info(), feedback=feedback,
+            feedback_y=ylog, feedback_u=ulog)
     except Exception:
         pass
+
+
+class LinearFeedback(object):
+    """Output feedback through a linear observer as a `dynamic_rhs`
+
+        y = cv_mat v,   hx' = ha hx + hb y + drift(t),   u = hc hx,
+        returns b_mat u
+
+    with the Heun / Adams-Bashforth-2 discretisation of the reference's
+    `get_heunab_lti` (tiu:148-196), composed with `cv_mat` and `b_mat` as
+    `solve_nse` does (snu:1243-1247).  Signature and modes (`init`,
+    `heunpred`, `heuncorr`, `abtwo`) and the keys of `memory` (`lastt`,
+    `lasthx`, `lastrhs`, `lastdt`, `hphx`) are the reference's, so any loop
+    that takes a `dynamic_rhs` can call it.
+
+    `cnab` / `sbdftwo` recognise an instance: with `device_convection` and
+    `resident=` the AB2 steps are not called back but evaluated on the device
+    (`ImexStepper.set_feedback`), with the constant step `dt` of the grid where
+    the reference recomputes `t - lastt` (a difference of rounding only).
+
+    `calls` counts the calls by mode; `history` lists `(t, mode, y, u)` of
+    every call that was made on the host."""
+
+    def __init__(self, cv_mat, b_mat, ha, hb, hc, inihx, drift=None):
+        self.cv_mat = sps.csr_matrix(cv_mat)
+        self.b_mat = sps.csr_matrix(b_mat)
+        self.ha = np.array(ha, dtype=np.float64)
+        hN = self.ha.shape[0]
+        self.hb = np.array(hb, dtype=np.float64).reshape((hN, -1))
+        self.hc = np.array(hc, dtype=np.float64).reshape((-1, hN))
+        self.inihx = np.array(inihx, dtype=np.float64).reshape((hN, 1))
+        self.hN, self.Ny, self.Nu = hN, self.hb.shape[1], self.hc.shape[0]
+        if self.cv_mat.shape[0] != self.Ny or self.b_mat.shape[1] != self.Nu:
+            raise ValueError('cv_mat / b_mat do not fit hb / hc')
+        self._drift = drift
+        self.calls = dict(init=0, heunpred=0, heuncorr=0, abtwo=0)
+        self.history = []
+
+    def drift(self, t):
+        if self._drift is None:
+            return np.zeros((self.hN, 1))
+        return np.asarray(self._drift(t), dtype=np.float64).reshape(
+            (self.hN, 1))
+
+    def _out(self, t, mode, y, chx, memory):
+        u = self.hc @ chx
+        self.history.append((t, mode, None if y is None else y.reshape(-1),
+                             u.reshape(-1)))
+        return self.b_mat @ u, memory
+
+    def __call__(self, t, vc=None, memory={}, mode='abtwo'):
+        self.calls[mode] += 1
+        ha, hb, inihx = self.ha, self.hb, self.inihx
+        if mode == 'init':
+            memory.update(dict(lastt=t, lasthx=inihx))
+            return self._out(t, mode, None, inihx, memory)
+        y = self.cv_mat @ np.asarray(vc).reshape((-1, 1))
+        curdt = t - memory['lastt']
+        if mode == 'heunpred':
+            currhs = ha @ inihx + hb @ y + self.drift(memory['lastt'])
+            chx = inihx + curdt*currhs
+            memory.update(dict(lastrhs=currhs, hphx=chx))
+        elif mode == 'heuncorr':
+            currhs = ha @ memory['hphx'] + hb @ y + self.drift(t)
+            chx = inihx + .5*curdt*(currhs + memory['lastrhs'])
+            memory.update(dict(lastt=t, lasthx=chx, lastdt=curdt))
+        elif mode == 'abtwo':
+            currhs = ha @ memory['lasthx'] + hb @ y \
+                + self.drift(memory['lastt'])
+            chx = memory['lasthx'] + 1.5*curdt*currhs \
+                - .5*memory['lastdt']*memory['lastrhs']
+            memory.update(dict(lastt=t, lasthx=chx, lastrhs=currhs,
+                               lastdt=curdt))
+        else:
+            raise ValueError('unknown mode {0}'.format(mode))
+        return self._out(t, mode, y, chx, memory)
+
+
+class _ResidentFeedback(object):
+    """the device side of a `LinearFeedback` inside `cnab` / `sbdftwo`: takes
+    the observer over from the Heun start, tabulates the drift per slice,
+    collects the logs and hands the final state back to the memory dict"""
+
+    def __init__(self, fb, stepper, drm, c_n, c_c, dt, tstart):
+        self.fb, self.stepper, self.dt = fb, stepper, dt
+        self.tlast = tstart
+        self.ylog, self.ulog = [], []
+        stepper.set_feedback(fb.cv_mat, fb.b_mat, fb.ha, fb.hb, fb.hc,
+                             c_n=c_n, c_c=c_c, dt=dt)
+        # corrector state, the PREDICTOR's right-hand side (tiu:171-174)
+        stepper.set_feedback_state(drm['lasthx'], drm['lastrhs'],
+                                   fb.hc @ drm['lasthx'])
+
+    def table(self, ctrange):
+        """after `set_rhs_table`: the drift the step towards `ctrange[s]`
+        sees is the one at the time before it (tiu:187-188)"""
+        befores = [self.tlast] + list(ctrange[:-1])
+        drift = None if self.fb._drift is None else \
+            np.array([self.fb.drift(t)[:, 0] for t in befores])
+        self.stepper.set_feedback_table(len(ctrange), drift)
+        self.tlast = ctrange[-1]
+
+    def collect(self):
+        y, u = self.stepper.feedback_log()
+        self.ylog.append(y)
+        self.ulog.append(u)
+
+    def logs(self):
+        if not self.ylog:
+            return np.zeros((0, self.fb.Ny)), np.zeros((0, self.fb.Nu))
+        return np.vstack(self.ylog), np.vstack(self.ulog)
+
+    def finish(self, drm):
+        hx, flast, _ = self.stepper.feedback_state()
+        drm.update(dict(lastt=self.tlast, lasthx=hx.reshape((-1, 1)),
+                        lastrhs=flast.reshape((-1, 1)), lastdt=self.dt))
+
+
+def _feedback_record(rfb, lti, state_dependent):
+    """`feedback=` and `fb_logs=` of `_record_run`"""
+    if rfb is not None:
+        return 'resident', rfb.logs()
+    if lti is not None:
+        return 'host', _host_feedback_logs(lti)
+    return ('host' if state_dependent else None), None
+
+
+def _host_feedback_logs(fb):
+    rows = [h for h in fb.history if h[1] == 'abtwo']
+    if not rows:
+        return np.zeros((0, fb.Ny)), np.zeros((0, fb.Nu))
+    return np.array([h[2] for h in rows]), np.array([h[3] for h in rows])
 
 
 def _checkuniformgrid(trange):
@@ -194,11 +336,22 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
     tabulated per slice and uploaded (`dns_imex_set_rhs_table`,
     `dns_conv_set_dbc_table`); the blow-up guard stays at the slice starts.
     Not possible (falls back to one host round trip per step) with a
-    `dynamic_rhs` or `f_tvdp`, which depend on the state.
+    `dynamic_rhs` or `f_tvdp`, which depend on the state -- except a
+    `dynamic_rhs` that is a `LinearFeedback` (without `f_tvdp`): the Heun start
+    calls it on the host, then the observer state is handed to the stepper,
+    the drift is tabulated per slice next to the right-hand sides, and after
+    the loop the final observer state is written back into the memory dict;
+    `LAST_RUN['feedback']` says 'resident' then and `LAST_RUN['feedback_y']`,
+    `['feedback_u']` hold the outputs and inputs of the AB2 steps.
     Returns `v_n, p_n, ffflag` like the reference.
     """
     prm = _solver_settings(solver)
-    state_dependent = dynamic_rhs is not None or f_tvdp is not None
+    # a `LinearFeedback` is evaluated on the device with the step itself
+    lti = dynamic_rhs if isinstance(dynamic_rhs, LinearFeedback) else None
+    fb_dev = (lti is not None and f_tvdp is None
+              and device_convection is not None and resident is not None)
+    state_dependent = (dynamic_rhs is not None and not fb_dev) \
+        or f_tvdp is not None
     dt, listofts = _inittimegrid(trange, ntimeslices=ntimeslices)
     NP, NV = J.shape
     ffflag = 0
@@ -236,7 +389,10 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                  and (not moving or rsd.get('bcs_time_only', False)))
     savetimes = rsd.get('savevp_times', None)
     savetimes = None if savetimes is None else set(savetimes)
+    rfb = None
     try:
+        if fb_dev and on_device:
+            rfb = _ResidentFeedback(lti, stepper, drm, .5, .5, dt, trange[1])
         for kck, ctrange in enumerate(listofts):
             nrmvc = stepper.vnorm()
             if verbose:
@@ -268,6 +424,8 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                 stepper.set_rhs_table(gvt, gpt)
                 if moving:
                     device_convection.set_dbc_table(dbt)
+                if rfb is not None:
+                    rfb.table(ctrange)
                 done = 0
                 for s, ctime in enumerate(ctrange):
                     if (savetimes is None or ctime in savetimes
@@ -281,6 +439,8 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                             savevp(appndbcs(v_n, bcs_at), p_n, time=ctime)
                 if moving:
                     device_convection.set_dbcvals(statvals + list(bcs_n))
+                if rfb is not None:
+                    rfb.collect()
                 stepper.set_rhs(_col(0., NV), _col(0., NP))
                 continue
             for ctime in ctrange:
@@ -303,8 +463,11 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                 stepper.step(cf, nfc_new=nfc_new, opts=opts)
                 v_n, p_n = stepper.get_state()
                 savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
+        if rfb is not None:
+            rfb.finish(drm)
     finally:
-        _record_run('cnab', system, stepper)
+        _record_run('cnab', system, stepper, *_feedback_record(
+            rfb, lti, state_dependent))
         stepper.close()
         system.close()
     return v_n, p_n, ffflag
@@ -325,7 +488,10 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
     step when the callbacks depend on the time only (rhs / boundary-value
     tables)."""
     prm = _solver_settings(solver)
-    state_dependent = dynamic_rhs is not None
+    lti = dynamic_rhs if isinstance(dynamic_rhs, LinearFeedback) else None
+    fb_dev = (lti is not None and device_convection is not None
+              and resident is not None)
+    state_dependent = dynamic_rhs is not None and not fb_dev
     dt, listofts = _inittimegrid(trange, ntimeslices=ntimeslices)
     NP, NV = J.shape
     if device_convection is not None and f_vdp is None:
@@ -363,7 +529,11 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
     savetimes = rsd.get('savevp_times', None)
     savetimes = None if savetimes is None else set(savetimes)
     ffflag = 0
+    rfb = None
     try:
+        if fb_dev and on_device:
+            rfb = _ResidentFeedback(lti, stepper, drm, 2./3, 0., dt,
+                                    trange[1])
         for kck, ctrange in enumerate(listofts):
             nrmvc = np.linalg.norm(v_c)
             if nrmvc > check_ff_maxv or np.isnan(nrmvc):
@@ -388,6 +558,8 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                 stepper.set_rhs_table(gvt, gpt)
                 if moving:
                     device_convection.set_dbc_table(dbt)
+                if rfb is not None:
+                    rfb.table(ctrange)
                 done = 0
                 v_start = v_n
                 for s, ctime in enumerate(ctrange):
@@ -411,6 +583,8 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                     v_c = v_start
                 if moving:
                     device_convection.set_dbcvals(statvals + list(bcs_n))
+                if rfb is not None:
+                    rfb.collect()
                 stepper.set_rhs(_col(0., NV), _col(0., NP))
                 continue
             for ctime in ctrange:
@@ -433,8 +607,11 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                 stepper.step(cf, nfc_new=nfc_new, opts=opts)
                 v_n, p_n = stepper.get_state()
                 savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
+        if rfb is not None:
+            rfb.finish(drm)
     finally:
-        _record_run('sbdftwo', system, stepper)
+        _record_run('sbdftwo', system, stepper, *_feedback_record(
+            rfb, lti, state_dependent))
         stepper.close()
         system.close()
     return v_n, p_n, ffflag

@@ -424,6 +424,45 @@ int dns_imex_step_counters(dns_imex *st, int64_t *out3);
 int dns_imex_run_cycles(dns_imex *st, int64_t *out2);
 /* v (NV) and p = pscale*p~ (NP) of the current state */
 int dns_imex_get_state(dns_imex *st, double *v, double *p);
+/* ---- observer feedback of the explicit loops ------------------------------
+ * The reference's `dynamic_rhs` of a closed loop with a linear observer
+ * (`get_heunab_lti`, tiu:148-196, composed as in snu:1243-1247), resident:
+ *     y    = C v_c                          C: Ny x NV CSR (sensors)
+ *     f    = ha hx + hb y + drift(t_c)      ha: hN x hN, hb: hN x Ny, row major
+ *     hx_n = hx + 1.5 dt f - 0.5 dt f_last  (AB2)
+ *     u_n  = hc hx_n                        hc: Nu x hN, row major
+ *     g   += dt (c_n B u_n + c_c B u_c)     B: NV x Nu CSR (actuators)
+ * evaluated by one kernel in front of every step (dns_imex_step and
+ * dns_imex_run alike), so that closed-loop steps are replayed as graphs like
+ * open-loop ones.  CNAB: c_n = c_c = 1/2; SBDF2: c_n = 2/3, c_c = 0.
+ * Limits (DNS_ERR_BAD_ARGUMENT beyond them): hN <= 128, Ny <= 32, Nu <= 32,
+ * nnz(C) <= 16384, one GPU (not on a row-partitioned stepper).  A call that
+ * fails leaves the stepper as it was.  After this call the observer state is
+ * zero and no table is set: dns_imex_set_feedback_table must follow. */
+int dns_imex_set_feedback(dns_imex *st, const dns_csr *cmat, const dns_csr *bmat,
+                          const double *ha, const double *hb, const double *hc,
+                          int32_t hN, int32_t Ny, int32_t Nu, double c_n,
+                          double c_c, double dt);
+/* observer state of the current time: hx (hN), the last observer right-hand
+ * side f_last (hN) and the current input u_c (Nu) -- the hand-over from a
+ * start-up scheme on the host (Heun: `lasthx`, `lastrhs`, hc lasthx) */
+int dns_imex_set_feedback_state(dns_imex *st, const double *hx,
+                                const double *f_last, const double *u_c);
+/* the same, read back (any pointer may be NULL) */
+int dns_imex_get_feedback_state(dns_imex *st, double *hx, double *f_last,
+                                double *u_c);
+/* drift rows: row s of `drift` (nsteps x hN, NULL: no drift) enters the s-th
+ * step after this call; `nsteps` is also the capacity of the logs.  Resets
+ * the step counter like dns_imex_set_rhs_table (upload the tables of a slice
+ * together); stepping past the last row fails with DNS_ERR_NOT_READY. */
+int dns_imex_set_feedback_table(dns_imex *st, int32_t nsteps,
+                                const double *drift);
+/* rows [first, first + count) of the logs: y (count x Ny) = C v_c the s-th
+ * step saw, u (count x Nu) = the input u_n it computed (either may be NULL) */
+int dns_imex_get_feedback_log(dns_imex *st, int32_t first, int32_t count,
+                              double *y, double *u);
+/* back to open-loop steps */
+int dns_imex_clear_feedback(dns_imex *st);
 /* ||v||_2 of the current velocity (blow-up guard, tiu:94-103) */
 int dns_imex_vnorm(dns_imex *st, double *out);
 
