@@ -180,6 +180,13 @@ SIGNATURES = {
     'dns_imex_get_feedback_log': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
                                              c_double_p, c_double_p]),
     'dns_imex_clear_feedback': (ct.c_int, [_VP]),
+    'dns_imex_set_recorder': (ct.c_int, [_VP, ct.POINTER(dns_csr), ct.c_int32,
+                                         c_int32_p, ct.c_int32]),
+    'dns_imex_get_record_outputs': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
+                                               c_double_p]),
+    'dns_imex_get_record_snapshots': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
+                                                 c_double_p, c_double_p]),
+    'dns_imex_clear_recorder': (ct.c_int, [_VP]),
     'dns_imex_run_info': (ct.c_int, [_VP, c_int32_p, c_int32_p, c_int32_p,
                                      c_int32_p]),
     'dns_imex_step_counters': (ct.c_int, [_VP, ct.POINTER(ct.c_int64)]),

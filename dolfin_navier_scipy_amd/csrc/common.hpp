@@ -203,6 +203,38 @@ inline int download_from(T *host, const T *dev, size_t count, hipStream_t s) {
     return staged_d2h("download_from", host, dev, count * sizeof(T), s);
 }
 
+// staged, `rows` pieces of `width` entries that lie `dstride` entries apart on
+// the device (a column block of a row-major table) into consecutive rows of
+// `host`: only the pieces cross the bus, one 2D copy and one synchronisation
+// per bounce chunk
+template <typename T>
+inline int download_rows(T *host, const T *dev, size_t rows, size_t width,
+                         size_t dstride, hipStream_t s) {
+    if (rows == 0 || width == 0) return DNS_OK;
+    if (dstride == width)
+        return staged_d2h("download_rows", host, dev, rows * width * sizeof(T),
+                          s);
+    const size_t wb = width * sizeof(T);
+    if (wb > kBounceChunk) {
+        for (size_t r = 0; r < rows; ++r)
+            DNS_TRY(staged_d2h("download_rows", host + r * width,
+                               dev + r * dstride, wb, s));
+        return DNS_OK;
+    }
+    DNS_TRY(staged_prologue("download_rows", host, dev, rows * wb, s));
+    const size_t per = std::max<size_t>(1, kBounceChunk / wb);
+    DNS_TRY(g_bounce.reserve(std::min(rows, per) * wb));
+    for (size_t r = 0; r < rows; r += per) {
+        const size_t nr = std::min(per, rows - r);
+        DNS_HIP(hipMemcpy2DAsync(g_bounce.p, wb, dev + r * dstride,
+                                 dstride * sizeof(T), wb, nr,
+                                 hipMemcpyDeviceToHost, s));
+        DNS_HIP(hipStreamSynchronize(s));
+        memcpy(host + r * width, g_bounce.p, nr * wb);
+    }
+    return DNS_OK;
+}
+
 // pinned: only enqueued on `s`
 template <typename T>
 inline int h2d_pinned(T *dev, const T *pinned, size_t count, hipStream_t s) {

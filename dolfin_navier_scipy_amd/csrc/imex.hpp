@@ -3,10 +3,12 @@
 #include "batch_policy.hpp"
 #include "convection.hpp"
 #include "feedback.hpp"
+#include "record.hpp"
 #include "ring.hpp"
 #include "solver.hpp"
 #include "trap.hpp"
 #include "step_kernels.hpp"
+#include <memory>
 
 // (dns::Ring: the ring indices of xs, nsol, and whether the work buffer holds
 // the warm start already)
@@ -116,14 +118,31 @@ struct dns_imex : dns::Ring {
     int fb_rebase();               // current slot -> slot 0 (counter reset)
     int fb_launch(hipStream_t s);  // k_lti_step for the step about to run
     uint64_t fb_key() const;
+    // trajectory recorder (record.hpp): k_record_step runs in front of every
+    // step (behind k_lti_step) and once behind the last step of a call; it
+    // writes row `counter - 1`, so a restored batch overwrites its own rows
+    // and the buffers need no checkpoint.  Present = on.
+    struct Recorder {
+        int rows = 0;              // steps the slot table / the y log cover
+        int Ny = 0, nslots = 0;    // 0: no outputs / no snapshots
+        std::unique_ptr<dns::CsrDev> C;
+        dns::HostCsr Ch;           // (what C holds: the same matrix set again
+                                   // keeps the device copy)
+        dns::DevBuf<int> slot;
+        dns::DevBuf<double> snap, ylog;
+    };
+    std::unique_ptr<Recorder> rec;
+    int rec_launch(hipStream_t s); // k_record_step for the state as it stands
+    uint64_t rec_key() const;
     // a step counter is needed as soon as anything is tabulated
     bool tables() const {
-        return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on;
+        return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on || rec;
     }
     int rows_left() const {
         int lim = 1 << 30;
         if (tab_rows > 0) lim = std::min(lim, tab_rows);
         if (fb.on) lim = std::min(lim, fb.rows);
+        if (rec) lim = std::min(lim, rec->rows);
         if (conv && conv->dbc_rows > 0) lim = std::min(lim, conv->dbc_rows);
         return lim - tab_pos;
     }
@@ -172,10 +191,11 @@ struct dns_imex : dns::Ring {
         int nc, no, tab_pos;
         long steps_enqueued;
         bool b_valid, carry_ok, six_ok, dcells_ok;
+        double last_pscale;        // (the recorder scales the pressure by it)
     };
     HostState host_state() const {
         return {*this, nc, no, tab_pos, steps_enqueued, b_valid, carry_ok,
-                six_ok, dcells_ok};
+                six_ok, dcells_ok, last_pscale};
     }
     void set_host_state(const HostState &s) {
         static_cast<dns::Ring &>(*this) = s.ring;
@@ -187,6 +207,7 @@ struct dns_imex : dns::Ring {
         carry_ok = s.carry_ok;
         six_ok = s.six_ok;
         dcells_ok = s.dcells_ok;
+        last_pscale = s.last_pscale;
     }
     std::vector<uint64_t> group_key(const dns_imex_coeffs *cf,
                                     const dns_solve_opts *o, int group) const;

@@ -31,6 +31,7 @@ uint64_t dns_imex::step_key(const dns_imex_coeffs *cf) const {
     pkey = mix64(pkey, (uint64_t)((cf->carry_residual != 0) + 2 * carry_ok +
                                   4 * six_ok + 8 * dcells_ok));
     if (fb.on) pkey = mix64(pkey, fb_key());
+    if (rec) pkey = mix64(pkey, rec_key());
     return pkey;
 }
 
@@ -50,6 +51,37 @@ uint64_t dns_imex::fb_key() const {
                           (const void *)g.p})
         k = mix64(k, (uint64_t)(uintptr_t)q);
     return k;
+}
+
+// "recorder on", its shape, every buffer k_record_step is handed and the
+// pressure scale of the state it is about to write down
+uint64_t dns_imex::rec_key() const {
+    uint64_t k = 0x7ec;
+    k = mix64(k, (uint64_t)rec->rows);
+    k = mix64(k, (uint64_t)rec->Ny + ((uint64_t)rec->nslots << 32));
+    k = mix64(k, bits_of(last_pscale));
+    for (const void *q : {(const void *)(rec->C ? rec->C->vals.p : nullptr),
+                          (const void *)rec->slot.p, (const void *)rec->snap.p,
+                          (const void *)rec->ylog.p})
+        k = mix64(k, (uint64_t)(uintptr_t)q);
+    return k;
+}
+
+int dns_imex::rec_launch(hipStream_t s) {
+    const Recorder &r = *rec;
+    const bool snaps = r.nslots > 0, outs = r.Ny > 0;
+    const dns::RecArgs a{stepctr.p, r.rows, xs[cur].p, sys->nv, sys->n,
+                         (int)sys->ld, last_pscale, r.slot.p,
+                         snaps ? r.snap.p : (double *)nullptr, r.nslots, r.Ny,
+                         outs ? r.C->rowptr.p : (const int *)nullptr,
+                         outs ? r.C->colidx.p : (const int *)nullptr,
+                         outs ? r.C->vals.p : (const double *)nullptr,
+                         outs ? r.ylog.p : (double *)nullptr};
+    hipLaunchKernelGGL(dns::k_record_step,
+                       dns::record_grid((int)sys->ld, snaps, r.Ny),
+                       dns::kBlock, 0, s, a);
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
 }
 
 int dns_imex::fb_launch(hipStream_t s) {
@@ -173,6 +205,8 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
         // observer feedback: the first node of the step, whatever its form
         // (xs[cur] is complete: the tail of the step before has finished)
         if (fb.on) DNS_TRY(fb_launch(s));
+        // recorder: xs[cur] is the state after the step before (row s - 1)
+        if (rec) DNS_TRY(rec_launch(s));
         const double *vc = xs[cur].p;
         const double *vp = (nsol >= 2) ? xs[prev].p : xs[cur].p;
         const int ex = cf->extrapolate_x0;
@@ -383,6 +417,10 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "observer feedback on a partitioned system: the "
                          "outputs y = C v would need an all-reduce");
+    if (rec && (h->dist() || part.on))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "recorder on a partitioned system: the outputs y = C v "
+                         "would need an all-reduce, the snapshots a gather");
     if (tables()) {
         if (o->method != DNS_METHOD_GMRES)
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
@@ -392,7 +430,8 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
                              "the per-step tables are used up after %d steps: "
                              "upload the next ones (dns_imex_set_rhs_table / "
                              "dns_conv_set_dbc_table / "
-                             "dns_imex_set_feedback_table)", tab_pos);
+                             "dns_imex_set_feedback_table / "
+                             "dns_imex_set_recorder)", tab_pos);
     }
     if (conv) conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
     if (o->method == DNS_METHOD_GMRES) {
@@ -739,6 +778,7 @@ int dns_imex::enqueue_group(const dns_imex_coeffs *cf, const dns_solve_opts *o,
         pre_sig = dns::extrap_sig(nsol, cf->extrapolate_x0);
         steps_enqueued += group;
         if (tables()) tab_pos += group;
+        last_pscale = cf->pscale;
         b_valid = true;       // (carry_ok is part of the key: it stays as is)
         if (six_ok) pre_ok = false;   // (six-node steps leave x0 elsewhere)
         // (the tails of the replayed steps were the captured ones': they left
@@ -777,6 +817,7 @@ int dns_imex::prepare_graphs(const dns_imex_coeffs *cf,
     sig = mix64(sig, (uint64_t)(uintptr_t)gptab.p);
     sig = mix64(sig, (uint64_t)tab_rows);
     if (fb.on) sig = mix64(sig, fb_key());
+    if (rec) sig = mix64(sig, rec_key());
     if (conv) {
         sig = mix64(sig, (uint64_t)conv->dbc_rows);
         sig = mix64(sig, (uint64_t)(uintptr_t)conv->dbc_tab.p);
@@ -981,6 +1022,8 @@ int ImexRun::run_batch() {
         // synchronisation -- the header's -- ends the call
         fin_batch = k + nb >= nsteps && !h->dist();
         if (fin_batch) {
+            // (the recorder's last row: nobody runs a prologue behind it)
+            if (st->rec) DNS_TRY(st->rec_launch(h->stream));
             DNS_HIP(hipEventRecord(st->e1, h->stream));
             DNS_LPR_SWITCH(
                 h->K.lpr,
@@ -1049,6 +1092,7 @@ int ImexRun::finish_run(double *device_seconds, int64_t *total_iters) {
         sp->true_relres = sp->bnorm > 0 ? tr / sp->bnorm : tr;
         h->spmv_count++;
     } else {
+        if (st->rec && nsteps > 0) DNS_TRY(st->rec_launch(h->stream));
         DNS_HIP(hipEventRecord(st->e1, h->stream));
         // true residual of the last step for the record: behind the closing
         // event (not part of the stepping time), ONE synchronisation for both
@@ -1295,6 +1339,12 @@ static int dns_imex_step_impl(dns_imex *st, const double *nfc_new,
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "a device convection operator is attached: the "
                          "convection vector must not be supplied by the host");
+    // (refused before the convection history is touched: the stepper stays
+    // as it was)
+    if (st->tables() && st->rows_left() < 1)
+        return dns::fail(DNS_ERR_NOT_READY,
+                         "the per-step tables are used up after %d steps: "
+                         "upload the next ones", st->tab_pos);
     if (nfc_new) {
         std::swap(st->nc, st->no);
         DNS_TRY(st->nfc[st->nc].upload(nfc_new, (size_t)h->nv, h->stream));
@@ -1307,6 +1357,7 @@ static int dns_imex_step_impl(dns_imex *st, const double *nfc_new,
     const int src = st->step_device(cf, &o, sp, true);
     h->want_history = true;
     if (src != DNS_OK) return src;
+    if (st->rec) DNS_TRY(st->rec_launch(h->stream));    // the row of this step
     DNS_HIP(hipStreamSynchronize(h->stream));
     return DNS_OK;
 }
@@ -1620,6 +1671,198 @@ static int dns_imex_clear_feedback_impl(dns_imex *st) {
 
 int dns_imex_clear_feedback(dns_imex *st) {
     return dns::guarded([&]() -> int { return dns_imex_clear_feedback_impl(st); });
+}
+
+// ---- trajectory recorder (record.hpp) --------------------------------------
+
+static int dns_imex_set_recorder_impl(dns_imex *st, const dns_csr *cmat,
+                                      int32_t nrows, const int32_t *snap_slot,
+                                      int32_t nslots) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_saddle *h = st->sys;
+    if (st->r1_rows || st->part.on || h->dist())
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "recorder on a row-partitioned stepper: the outputs "
+                         "y = C v would need an all-reduce, the snapshots a "
+                         "gather (multi-rank recording is not supported)");
+    if (!cmat && !snap_slot)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "recorder: neither outputs (cmat) nor snapshots "
+                         "(snap_slot) asked for");
+    if (nrows < 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "recorder: nrows = %d < 1",
+                         (int)nrows);
+    if (cmat) {
+        DNS_TRY(dns::check_csr(cmat, "C"));
+        if (cmat->nrows < 1 || cmat->ncols != h->nv)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "recorder: C must be Ny x NV (%d columns), it is "
+                             "%d x %d", h->nv, (int)cmat->nrows,
+                             (int)cmat->ncols);
+    }
+    if (snap_slot) {
+        if (nslots < 1)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "recorder: a slot table with nslots = %d < 1",
+                             (int)nslots);
+        for (int r = 0; r < nrows; ++r)
+            if (snap_slot[r] < -1 || snap_slot[r] >= nslots)
+                return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                                 "recorder: snap_slot[%d] = %d outside -1..%d",
+                                 r, (int)snap_slot[r], (int)nslots - 1);
+    }
+    DNS_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
+    // Built aside: a refusal below leaves the recorder that was there.  What
+    // that one holds is taken over where it is large enough (and C where it is
+    // the same matrix), so that the slices of a time loop, which set the
+    // recorder again and again, keep their buffers -- and with them the
+    // graphs that were captured for these buffers.
+    dns_imex::Recorder *old = st->rec.get();
+    std::unique_ptr<dns_imex::Recorder> r(new (std::nothrow)
+                                              dns_imex::Recorder());
+    if (!r) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    r->rows = nrows;
+    auto fits = [](const dns::DevBuf<double> &b, size_t need) {
+        return b.p != nullptr && b.n >= need;
+    };
+    const size_t need_y = cmat ? (size_t)nrows * cmat->nrows : 0;
+    const size_t need_s = snap_slot ? (size_t)nslots * h->ld : 0;
+    bool keep_c = false, keep_y = false, keep_s = false, keep_t = false;
+    if (cmat) {
+        r->Ny = cmat->nrows;
+        const dns::HostCsr &oc = old ? old->Ch : r->Ch;
+        keep_c = old && old->C && oc.nrows == cmat->nrows &&
+                 oc.nnz() == cmat->nnz &&
+                 std::equal(oc.rowptr.begin(), oc.rowptr.end(), cmat->rowptr) &&
+                 std::equal(oc.colidx.begin(), oc.colidx.end(), cmat->colidx) &&
+                 std::equal(oc.vals.begin(), oc.vals.end(), cmat->vals);
+        if (!keep_c) {
+            r->C.reset(new (std::nothrow) dns::CsrDev());
+            if (!r->C) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+            DNS_TRY(r->C->upload(cmat, s));
+            r->Ch = dns::host_copy(cmat);
+        }
+        keep_y = old && fits(old->ylog, need_y);
+        if (!keep_y) DNS_TRY(r->ylog.alloc(need_y));
+    }
+    if (snap_slot) {
+        r->nslots = nslots;
+        keep_t = old && old->slot.p && old->slot.n >= (size_t)nrows;
+        if (!keep_t) DNS_TRY(r->slot.alloc((size_t)nrows));
+        keep_s = old && fits(old->snap, need_s);
+        if (!keep_s) DNS_TRY(r->snap.alloc(need_s));
+    }
+    // (nothing is refused from here on)
+    auto take = [](auto &dst, auto &src) {
+        std::swap(dst.p, src.p);
+        std::swap(dst.n, src.n);
+    };
+    if (keep_c) {
+        r->C = std::move(old->C);
+        r->Ch = std::move(old->Ch);
+    }
+    if (keep_y) take(r->ylog, old->ylog);
+    if (keep_t) take(r->slot, old->slot);
+    if (keep_s) take(r->snap, old->snap);
+    if (cmat) DNS_TRY(r->ylog.zero(s));
+    if (snap_slot) {
+        DNS_TRY(r->slot.upload(snap_slot, (size_t)nrows, s));
+        DNS_TRY(r->snap.zero(s));
+    }
+    st->rec = std::move(r);
+    // rows are selected by the step counter: back to 0, as after
+    // dns_imex_set_rhs_table
+    DNS_TRY(st->fb_rebase());
+    st->tab_pos = 0;
+    st->six_ok = false;
+    st->dcells_ok = false;
+    DNS_TRY(st->sync_counter());
+    if (st->conv && st->conv->dbc_rows > 0) st->conv->dbc_row = 0;
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+}
+
+int dns_imex_set_recorder(dns_imex *st, const dns_csr *cmat, int32_t nrows,
+                          const int32_t *snap_slot, int32_t nslots) {
+    return dns::guarded([&]() -> int { return dns_imex_set_recorder_impl(st, cmat, nrows, snap_slot, nslots); });
+}
+
+static int rec_need(dns_imex *st) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (!st->rec)
+        return dns::fail(DNS_ERR_NOT_READY, "no recorder is set "
+                         "(dns_imex_set_recorder)");
+    return hipSetDevice(st->sys->device) == hipSuccess
+               ? DNS_OK : dns::fail(DNS_ERR_HIP, "hipSetDevice failed");
+}
+
+static int dns_imex_get_record_outputs_impl(dns_imex *st, int32_t first,
+                                            int32_t count, double *y) {
+    DNS_TRY(rec_need(st));
+    const dns_imex::Recorder &r = *st->rec;
+    if (r.Ny < 1)
+        return dns::fail(DNS_ERR_NOT_READY, "the recorder keeps no outputs");
+    if (!y) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (first < 0 || count < 0 || first + count > r.rows)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "output rows [%d, %d) asked for, the recorder holds "
+                         "%d", (int)first, (int)(first + count), r.rows);
+    hipStream_t s = st->sys->stream;
+    if (count)
+        DNS_TRY(dns::download_from(y, r.ylog.p + (size_t)first * r.Ny,
+                                   (size_t)count * r.Ny, s));
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+}
+
+int dns_imex_get_record_outputs(dns_imex *st, int32_t first, int32_t count,
+                                double *y) {
+    return dns::guarded([&]() -> int { return dns_imex_get_record_outputs_impl(st, first, count, y); });
+}
+
+static int dns_imex_get_record_snapshots_impl(dns_imex *st, int32_t first_slot,
+                                              int32_t count, double *v,
+                                              double *p) {
+    DNS_TRY(rec_need(st));
+    const dns_imex::Recorder &r = *st->rec;
+    if (r.nslots < 1)
+        return dns::fail(DNS_ERR_NOT_READY, "the recorder keeps no snapshots");
+    if (first_slot < 0 || count < 0 || first_slot + count > r.nslots)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "slots [%d, %d) asked for, the recorder holds %d",
+                         (int)first_slot, (int)(first_slot + count), r.nslots);
+    const dns_saddle *h = st->sys;
+    hipStream_t s = h->stream;
+    const double *base = r.snap.p + (size_t)first_slot * h->ld;
+    if (v)
+        DNS_TRY(dns::download_rows(v, base, (size_t)count, (size_t)h->nv,
+                                   h->ld, s));
+    if (p)
+        DNS_TRY(dns::download_rows(p, base + h->nv, (size_t)count,
+                                   (size_t)h->np, h->ld, s));
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+}
+
+int dns_imex_get_record_snapshots(dns_imex *st, int32_t first_slot,
+                                  int32_t count, double *v, double *p) {
+    return dns::guarded([&]() -> int { return dns_imex_get_record_snapshots_impl(st, first_slot, count, v, p); });
+}
+
+static int dns_imex_clear_recorder_impl(dns_imex *st) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (!st->rec) return DNS_OK;
+    DNS_HIP(hipSetDevice(st->sys->device));
+    DNS_HIP(hipStreamSynchronize(st->sys->stream));
+    st->rec.reset();
+    // (the counter goes on counting for the other tables, if any)
+    return DNS_OK;
+}
+
+int dns_imex_clear_recorder(dns_imex *st) {
+    return dns::guarded([&]() -> int { return dns_imex_clear_recorder_impl(st); });
 }
 
 static int dns_imex_get_state_impl(dns_imex *st, double *v, double *p) {

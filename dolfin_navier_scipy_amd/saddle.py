@@ -332,6 +332,7 @@ class ImexStepper(object):
         self.last_stats = None
         # time steps and Krylov steps since the stepper exists
         self.total_steps, self.total_iters = 0, 0
+        self.run_calls = 0          # `run` calls since the stepper exists
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h:
@@ -433,6 +434,7 @@ class ImexStepper(object):
                                        ct.byref(secs), ct.byref(its))
         if status != C.DNS_NOT_CONVERGED:
             C.check(status)
+        self.run_calls += 1
         self.last_stats = st.asdict()
         self.total_steps += int(nsteps)
         self.total_iters += int(its.value)
@@ -523,6 +525,85 @@ class ImexStepper(object):
             self._h, int(first), int(count), C.dptr(y.reshape(-1)),
             C.dptr(u.reshape(-1))))
         return y, u
+
+    # ---- trajectory recorder (`dns_imex_set_recorder`) ----------------------
+    def set_recorder(self, nrows, cv_mat=None, snap_slots=None):
+        """the next `nrows` steps (`step` and `run` alike) write themselves
+        down on the device: the outputs `y = cv_mat v` of every step
+        (`cv_mat`: `Ny x NV`, None: no outputs) and / or the state `[v; p]` of
+        the steps `s` with `snap_slots[s] >= 0` into that slot of a snapshot
+        buffer (`snap_slots`: `nrows` integers, `-1`: not kept, None: no
+        snapshots; `'all'`: every step, slot `s`).  Row `s` is what `get_state`
+        would have returned after the `(s+1)`-th step from now.  Resets the
+        step counter like `set_rhs_table` (call it after that one, and collect
+        with `record_outputs` / `record_snapshots` before the next tables)."""
+        nrows = int(nrows)
+        if nrows < 1:
+            raise ValueError('`nrows` must be positive')
+        if cv_mat is None and snap_slots is None:
+            raise ValueError('neither `cv_mat` nor `snap_slots`: nothing to '
+                             'record')
+        cview = None
+        if cv_mat is not None:
+            cview = C.CsrView(cv_mat)
+            if len(cview.shape) != 2 or cview.shape[1] != self.sys.NV \
+                    or cview.shape[0] < 1:
+                raise ValueError('cv_mat must be Ny x NV (NV = {0}), it is '
+                                 '{1}'.format(self.sys.NV, cview.shape))
+        slots, nslots = None, 0
+        if snap_slots is not None:
+            if isinstance(snap_slots, str):
+                if snap_slots != 'all':
+                    raise ValueError("snap_slots: an array or 'all'")
+                snap_slots = np.arange(nrows)
+            slots = np.ascontiguousarray(snap_slots, dtype=np.int32).reshape(-1)
+            if slots.size != nrows:
+                raise ValueError('snap_slots must have `nrows` entries')
+            if slots.min() < -1:
+                raise ValueError('snap_slots: entries are slots or -1')
+            nslots = int(slots.max()) + 1
+            if nslots < 1:
+                raise ValueError('snap_slots keeps no step at all')
+        C.check(self.lib.dns_imex_set_recorder(
+            self._h, None if cview is None else cview.byref(), nrows,
+            None if slots is None else slots.ctypes.data_as(C.c_int32_p),
+            nslots))
+        self._rec_shape = (nrows, 0 if cview is None else cview.shape[0],
+                           nslots)
+
+    def clear_recorder(self):
+        C.check(self.lib.dns_imex_clear_recorder(self._h))
+        self._rec_shape = None
+
+    def _rec_need(self):
+        shape = getattr(self, '_rec_shape', None)
+        if shape is None:
+            raise ValueError('no recorder is set (`set_recorder`)')
+        return shape
+
+    def record_outputs(self, first=0, count=None):
+        """rows `first .. first + count` of `y = cv_mat v` (default: of all
+        steps taken since `set_recorder`), `(count, Ny)`"""
+        _, Ny, _ = self._rec_need()
+        if count is None:
+            count = self.table_position()[0] - first
+        y = np.empty((int(count), Ny))
+        C.check(self.lib.dns_imex_get_record_outputs(
+            self._h, int(first), int(count), C.dptr(y.reshape(-1))))
+        return y
+
+    def record_snapshots(self, first=0, count=None):
+        """slots `first .. first + count` of the snapshot buffer (default: all
+        slots): `(v (count, NV), p (count, NP))`"""
+        _, _, nslots = self._rec_need()
+        if count is None:
+            count = nslots - first
+        v = np.empty((int(count), self.sys.NV))
+        p = np.empty((int(count), self.sys.NP))
+        C.check(self.lib.dns_imex_get_record_snapshots(
+            self._h, int(first), int(count), C.dptr(v.reshape(-1)),
+            C.dptr(p.reshape(-1))))
+        return v, p
 
     def get_state(self):
         v = np.empty(self.sys.NV)

@@ -356,7 +356,7 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
               dyn_fb_dict=None, dyn_fb_disc='trapezoidal',
               vp_output=False, vp_out_fun=None, vp_output_dict=None,
               solver=None, device=0, bcs_time_only=False,
-              applybcs_literal=True, **kw):
+              applybcs_literal=True, record_on_device=False, **kw):
     """time-dependent Navier-Stokes on the device (reference snu:548-1600)
 
     Keyword names and meaning follow the reference.  `V`: object with the P2
@@ -388,7 +388,16 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     then run device resident over whole time slices), `applybcs_literal`
     (default True: the `applybcs` closure returns zeros exactly as the
     reference's does with snu:1112 commented out; False: the controlled values
-    are written into the auxiliary vector, see `bcs.make_applybcs`).
+    are written into the auxiliary vector, see `bcs.make_applybcs`),
+    `record_on_device` (default False; explicit schemes): where the loop runs
+    device resident, the device writes the trajectory down while it replays
+    whole time slices (`time_int_utils` `resident=dict(record=True)`) and the
+    results are filled from its snapshots instead of one host round trip per
+    data point; when all that is asked for is `return_y_list` with a `cv_mat`
+    on the inner dofs, the device records `y = cv_mat v` of every step and
+    keeps no snapshot but the slices' last.  Where the loop does not run
+    resident it takes the usual path; `time_int_utils.LAST_RUN['record']`
+    says `'device'` or `'host'`.
     """
     if dynamic_feedback and dyn_fb_disc == 'linear_implicit':
         raise NotImplementedError("`dyn_fb_disc='linear_implicit'` (the "
@@ -557,6 +566,13 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
                 cv_mat, b_mat, dfb['ha'], dfb['hb'], dfb['hc'], dfb['inihx'],
                 drift=dfb.get('drift')), dynamic_rhs_memory={})
         static_bcs = len(loccnt) == 0
+        # all that is asked for is `y = cv_mat v` on the inner dofs: the
+        # device's y rows do, no snapshot has to travel
+        y_only = bool(record_on_device and return_y_list
+                      and cv_mat is not None
+                      and not (vp_output or return_vp_dict
+                               or return_dictofvelstrs)
+                      and cv_mat.shape[1] == cnv)
         if cvop is not None and (static_bcs or bcs_time_only):
             # the loop may evaluate N(v)v itself and, the callbacks being
             # functions of the time only, run whole time slices resident
@@ -567,9 +583,23 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
                            static_dbcvals=list(dbcvals),
                            savevp_times=(None if return_vp_dict
                                          else list(datatrange))))
+            if record_on_device:
+                icd['resident'].update(record=True)
+            if y_only:
+                # (a loop that does not run resident after all calls `savevp`
+                # at every step whatever `savevp_times` says)
+                icd['resident'].update(outputs=cv_mat, savevp_times=())
         v_end, p_end, ffflag = timintsc(trange=trange, inip=inip, scalep=-1.,
                                         g_tdp=rhsp, bcs_ini=inicdbcvals,
                                         check_ff_maxv=check_ff_maxv, **icd)
+        if y_only and tiu.LAST_RUN.get('record') == 'device':
+            # the points of the Heun start came from the host; the rest are
+            # rows of the device's record
+            for rt, ry in zip(tiu.LAST_RUN['record_t'],
+                              tiu.LAST_RUN['record_y']):
+                if datatrange and rt == datatrange[0]:
+                    datatrange.pop(0)
+                    ylist.append(ry.reshape((-1, 1)))
 
         def _flag(thing):
             return (thing, ffflag) if check_ff else thing

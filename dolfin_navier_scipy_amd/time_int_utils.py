@@ -48,13 +48,19 @@ SOLVER = dict(method='gmres', rtol=None, maxiter=400, restart=60,
 LAST_RUN = {}
 
 
-def _record_run(name, system, stepper, feedback=None, fb_logs=None):
+def _record_run(name, system, stepper, feedback=None, fb_logs=None,
+                rec=None):
     """`feedback`: 'resident' (observer on the device), 'host' (a
     `dynamic_rhs` called every step) or None (open loop); `fb_logs`: the
-    `(y, u)` rows of the AB2 steps where the loop knows them"""
+    `(y, u)` rows of the AB2 steps where the loop knows them; `rec`: the
+    `_DeviceRecord` of a loop whose trajectory the device wrote down"""
     LAST_RUN.clear()
     try:        # (runs in a `finally`: never in the way of the real error)
         ylog, ulog = fb_logs if fb_logs is not None else (None, None)
+        rec_y, rec_t = rec.result() if rec is not None else (None, None)
+        LAST_RUN.update(record='device' if rec is not None else 'host',
+                        run_calls=getattr(stepper, 'run_calls', 0),
+                        record_y=rec_y, record_t=rec_t)
         LAST_RUN.update(
             integrator=name, time_steps=stepper.total_steps,
             krylov_steps=stepper.total_iters,
@@ -197,6 +203,98 @@ def _host_feedback_logs(fb):
     return np.array([h[2] for h in rows]), np.array([h[3] for h in rows])
 
 
+RECORD_BYTES = 1 << 30      # default cap of a slice's snapshot buffer
+
+
+def plan_record(ctrange, savetimes, snap_bytes, record_bytes=RECORD_BYTES,
+                keep_prev=False):
+    """Slots and chunks of a recorded time slice (`resident=dict(record=True)`)
+
+    Kept are the steps whose time is in `savetimes` (None: every step), the
+    last step of the slice always, and with `keep_prev` the step before it.
+    A snapshot takes `snap_bytes`; a chunk keeps at most `record_bytes //
+    snap_bytes` of them, so a slice that keeps more is cut into chunks, each
+    ending with a kept step.  Returns the chunks in time order as dicts
+    `first`, `nsteps` (steps `first .. first + nsteps` of the slice), `slots`
+    (int32, `nsteps` entries: slot of the step or -1) and `kept` (list of
+    `(step of the slice, slot)`); an empty slice has none."""
+    ns = len(ctrange)
+    cap = int(record_bytes) // int(snap_bytes)
+    if cap < 1:
+        raise ValueError('record_bytes = {0} is below one snapshot ({1} '
+                         'bytes)'.format(record_bytes, snap_bytes))
+    keep = [savetimes is None or t in savetimes for t in ctrange]
+    if ns:
+        keep[-1] = True
+    if keep_prev and ns > 1:
+        keep[-2] = True
+    chunks, first = [], 0
+    while first < ns:
+        slots, kept, s = [], [], first
+        while s < ns:
+            if keep[s]:
+                slots.append(len(kept))
+                kept.append((s, len(kept)))
+            else:
+                slots.append(-1)
+            s += 1
+            if len(kept) == cap:
+                break
+        chunks.append(dict(first=first, nsteps=s - first,
+                           slots=np.array(slots, dtype=np.int32), kept=kept))
+        first = s
+    return chunks
+
+
+class _DeviceRecord(object):
+    """`resident=dict(record=True)` of `cnab` / `sbdftwo`: runs a slice as one
+    `stepper.run` per chunk of `plan_record` with the recorder on and hands
+    back the kept states; collects `y = outputs v` of every step"""
+
+    def __init__(self, stepper, rsd, NV, NP):
+        self.stepper = stepper
+        out = rsd.get('outputs', None)
+        self.outputs = None if out is None else sps.csr_matrix(out)
+        self.record_bytes = int(rsd.get('record_bytes', RECORD_BYTES))
+        # (a slot is a ring vector: NV + NP padded to 64 entries)
+        self.snap_bytes = 8*(-(-(NV + NP)//64)*64)
+        self.ys, self.ts = [], []
+        self.run_calls = 0
+
+    def run_slice(self, cf, opts, ctrange, savetimes, upload, keep_prev=False,
+                  after_chunk=None):
+        """`upload(a, b)`: set the tables of the steps `a .. b` of the slice;
+        returns `{step of the slice: (v, p)}` of the kept steps"""
+        states = {}
+        for ch in plan_record(ctrange, savetimes, self.snap_bytes,
+                              self.record_bytes, keep_prev=keep_prev):
+            a, n = ch['first'], ch['nsteps']
+            upload(a, a + n)
+            self.stepper.set_recorder(n, cv_mat=self.outputs,
+                                      snap_slots=ch['slots'])
+            self.stepper.run(n, cf, opts)
+            self.run_calls += 1
+            vs, ps = self.stepper.record_snapshots(0, len(ch['kept']))
+            for s, slot in ch['kept']:
+                states[s] = (vs[slot].reshape((-1, 1)),
+                             ps[slot].reshape((-1, 1)))
+            if self.outputs is not None:
+                self.ys.append(self.stepper.record_outputs(0, n))
+                self.ts.extend(ctrange[a:a + n])
+            if after_chunk is not None:
+                after_chunk()
+        # (the recorder stays set: the next slice takes its buffers over, and
+        # with them the graphs that were captured for them)
+        return states
+
+    def result(self):
+        if self.outputs is None:
+            return None, None
+        ny = self.outputs.shape[0]
+        y = np.vstack(self.ys) if self.ys else np.zeros((0, ny))
+        return y, np.array(self.ts, dtype=np.float64)
+
+
 def _checkuniformgrid(trange):
     steps = np.diff(np.asarray(trange, dtype=np.float64))
     if not np.allclose(np.linalg.norm(np.diff(steps)), 0):
@@ -332,6 +430,19 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
       `static_dbcvals`  values of the operator's leading (static) Dirichlet
                         dofs; the controlled values `bcs` follow them
       `savevp_times`    the only times `savevp` has to see (None: all)
+      `record`          True: the device writes the states of these times down
+                        while it replays the slice (`ImexStepper.set_recorder`)
+                        and `savevp` is called afterwards, in time order, with
+                        the arguments it gets otherwise -- ONE `stepper.run`
+                        per slice instead of one per saved time
+      `outputs`         with `record`: a sparse `C` (Ny x NV); `y = C v` of
+                        every step of the loop ends up in
+                        `LAST_RUN['record_y']`, its times in `['record_t']`
+      `record_bytes`    with `record`: cap of a slice's snapshot buffer
+                        (default 1 GiB); a slice that keeps more runs in
+                        chunks (`plan_record`)
+    `LAST_RUN['record']` says 'device' or 'host', `LAST_RUN['run_calls']`
+    counts the `stepper.run` calls of the loop.
     The per-step data the callbacks return (`f_tdp`, `g_tdp`, `applybcs`) are
     tabulated per slice and uploaded (`dns_imex_set_rhs_table`,
     `dns_conv_set_dbc_table`); the blow-up guard stays at the slice starts.
@@ -390,6 +501,10 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
     savetimes = rsd.get('savevp_times', None)
     savetimes = None if savetimes is None else set(savetimes)
     rfb = None
+    # `record=True`: the device writes the trajectory down (where the loop
+    # runs resident at all)
+    drec = _DeviceRecord(stepper, rsd, NV, NP) \
+        if (on_device and rsd.get('record', False)) else None
     try:
         if fb_dev and on_device:
             rfb = _ResidentFeedback(lti, stepper, drm, .5, .5, dt, trange[1])
@@ -421,6 +536,28 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                     gpt[s] = _col(fp_n + bfp_n, NP)[:, 0]
                     if moving:       # N(v_c) sees the CURRENT boundary values
                         dbt[s] = statvals + list(bcs_c)
+                if drec is not None:
+                    # the device writes the slice down; the host collects it
+                    def upload(a, b):
+                        stepper.set_rhs_table(gvt[a:b], gpt[a:b])
+                        if moving:
+                            device_convection.set_dbc_table(dbt[a:b])
+                        if rfb is not None:
+                            rfb.table(ctrange[a:b])
+                    states = drec.run_slice(
+                        cf, opts, ctrange, savetimes, upload,
+                        after_chunk=None if rfb is None else rfb.collect)
+                    for s, ctime in enumerate(ctrange):
+                        if savetimes is None or ctime in savetimes:
+                            bcs_at = dbt[s + 1][len(statvals):].tolist() \
+                                if (moving and s + 1 < ns) else bcs_n
+                            savevp(appndbcs(states[s][0], bcs_at),
+                                   states[s][1], time=ctime)
+                    v_n, p_n = states[ns - 1]
+                    if moving:
+                        device_convection.set_dbcvals(statvals + list(bcs_n))
+                    stepper.set_rhs(_col(0., NV), _col(0., NP))
+                    continue
                 stepper.set_rhs_table(gvt, gpt)
                 if moving:
                     device_convection.set_dbc_table(dbt)
@@ -467,7 +604,7 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
             rfb.finish(drm)
     finally:
         _record_run('cnab', system, stepper, *_feedback_record(
-            rfb, lti, state_dependent))
+            rfb, lti, state_dependent), rec=drec)
         stepper.close()
         system.close()
     return v_n, p_n, ffflag
@@ -530,6 +667,8 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
     savetimes = None if savetimes is None else set(savetimes)
     ffflag = 0
     rfb = None
+    drec = _DeviceRecord(stepper, rsd, NV, NP) \
+        if (on_device and rsd.get('record', False)) else None
     try:
         if fb_dev and on_device:
             rfb = _ResidentFeedback(lti, stepper, drm, 2./3, 0., dt,
@@ -555,6 +694,31 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                     gpt[s] = _col(fp_n + bfp_n, NP)[:, 0]
                     if moving:
                         dbt[s] = statvals + list(bcs_c)
+                if drec is not None:
+                    def upload(a, b):
+                        stepper.set_rhs_table(gvt[a:b], gpt[a:b])
+                        if moving:
+                            device_convection.set_dbc_table(dbt[a:b])
+                        if rfb is not None:
+                            rfb.table(ctrange[a:b])
+                    # (kept too: the velocity BEFORE the slice's last step, for
+                    # the blow-up guard of the next slice, tiu:317,322)
+                    v_start = v_n
+                    states = drec.run_slice(
+                        cf, opts, ctrange, savetimes, upload, keep_prev=True,
+                        after_chunk=None if rfb is None else rfb.collect)
+                    for s, ctime in enumerate(ctrange):
+                        if savetimes is None or ctime in savetimes:
+                            bcs_at = dbt[s + 1][len(statvals):].tolist() \
+                                if (moving and s + 1 < ns) else bcs_n
+                            savevp(appndbcs(states[s][0], bcs_at),
+                                   states[s][1], time=ctime)
+                    v_c = states[ns - 2][0] if ns > 1 else v_start
+                    v_n, p_n = states[ns - 1]
+                    if moving:
+                        device_convection.set_dbcvals(statvals + list(bcs_n))
+                    stepper.set_rhs(_col(0., NV), _col(0., NP))
+                    continue
                 stepper.set_rhs_table(gvt, gpt)
                 if moving:
                     device_convection.set_dbc_table(dbt)
@@ -611,7 +775,7 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
             rfb.finish(drm)
     finally:
         _record_run('sbdftwo', system, stepper, *_feedback_record(
-            rfb, lti, state_dependent))
+            rfb, lti, state_dependent), rec=drec)
         stepper.close()
         system.close()
     return v_n, p_n, ffflag

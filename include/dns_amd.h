@@ -463,6 +463,34 @@ int dns_imex_get_feedback_log(dns_imex *st, int32_t first, int32_t count,
                               double *y, double *u);
 /* back to open-loop steps */
 int dns_imex_clear_feedback(dns_imex *st);
+/* ---- trajectory recorder of the explicit loops ----------------------------
+ * While dns_imex_step / dns_imex_run step (and replay their graphs), one more
+ * kernel per step writes down the trajectory on the device:
+ *     y row r    = C v          C: Ny x NV CSR (`cmat`, NULL: no outputs)
+ *     slot[r]    = [v; p]       `snap_slot` (nrows entries, NULL: no
+ *                               snapshots): the slot (0 .. nslots-1) that keeps
+ *                               the state of row r, -1: not kept
+ * Row r holds what dns_imex_get_state would have returned after the (r+1)-th
+ * step since the step counter was last reset (p = pscale*p~, the same bits).
+ * `nrows` is a table length like the others: this call resets the step counter
+ * like dns_imex_set_rhs_table (upload the tables of a slice together -- and
+ * collect the rows before the next upload: any of those calls rewinds them),
+ * stepping past the last row fails with DNS_ERR_NOT_READY.  Works with and
+ * without observer feedback.  No limit on Ny, nnz(C), nrows or nslots other
+ * than memory (nslots x (NV + NP, padded to 64) doubles).  One GPU: a
+ * row-partitioned stepper refuses it.  A call that fails leaves the stepper
+ * and an earlier recorder as they were. */
+int dns_imex_set_recorder(dns_imex *st, const dns_csr *cmat, int32_t nrows,
+                          const int32_t *snap_slot, int32_t nslots);
+/* rows [first, first + count) of the outputs: y (count x Ny) */
+int dns_imex_get_record_outputs(dns_imex *st, int32_t first, int32_t count,
+                                double *y);
+/* slots [first_slot, first_slot + count): v (count x NV) and p (count x NP),
+ * either may be NULL */
+int dns_imex_get_record_snapshots(dns_imex *st, int32_t first_slot,
+                                  int32_t count, double *v, double *p);
+/* recorder off (the step is what it was before dns_imex_set_recorder) */
+int dns_imex_clear_recorder(dns_imex *st);
 /* ||v||_2 of the current velocity (blow-up guard, tiu:94-103) */
 int dns_imex_vnorm(dns_imex *st, double *out);
 
