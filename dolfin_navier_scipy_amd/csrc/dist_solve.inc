@@ -687,7 +687,7 @@ int dns_saddle::update_values_dist() {
 
 int dns_saddle::enqueue_cycle_dist(const double *b, double *x, int c,
                                    const dns_solve_opts *o, int first,
-                                   bool have_resid) {
+                                   bool have_resid, const dns::StepHooks &hk) {
     using namespace dns;
     dns_dist_data *D = dd;
     // fused Gram-Schmidt (norm by Pythagoras: ONE all-reduce per step) unless
@@ -714,17 +714,17 @@ int dns_saddle::enqueue_cycle_dist(const double *b, double *x, int c,
     // the preconditioned vectors are exchanged over the caller's halo when it
     // has a wider one (IMEX stepper: rows of R1 and convection cells as well),
     // so that the new iterate needs no exchange of its own behind the solve
-    const dns_halo_plan *zplan = z_plan_override ? z_plan_override : &D->planK;
+    const dns_halo_plan *zplan = hk.z_plan ? hk.z_plan : &D->planK;
     // bandwidth regime: the row blocks go through the streaming kernels too
     // (local CSR rows -> global rows through the RowMap of the epilogue)
     const bool big = streams(K);
     // (have_resid: the caller's prologue kernel has left r = b - K x and the
-    // partials of both norms -- prologue_nparts of them -- behind)
-    const bool pre_r = have_resid && prologue_nparts > 0;
+    // partials of both norms -- resid_nparts of them -- behind)
+    const bool pre_r = have_resid && hk.resid_nparts > 0;
     const int gS = big ? (Kp.ready ? pair_grid(Kp, sgrid)
                                    : stream_grid(K, sgrid))
                        : gK;
-    const int gR = pre_r ? prologue_nparts : gS;    // partials of ||r||, ||b||
+    const int gR = pre_r ? hk.resid_nparts : gS;    // partials of ||r||, ||b||
     if (pre_r) {
     } else if (big) {
         StreamEpi ep = stream_epi_plain(-1.0, 1.0, b);
@@ -807,7 +807,7 @@ int dns_saddle::enqueue_cycle_dist(const double *b, double *x, int c,
                                (const void *)(SINV), zp, ctl.p, o->rtol,      \
                                o->atol, bb_in, 1, o->maxiter, q0, q1,         \
                                first, mgs ? nullptr : tin,                    \
-                               first == 1 ? step_counter : nullptr,           \
+                               first == 1 ? hk.stepctr : nullptr,        \
                                ((SK) == 2 || (SK) == 1) ? sstride : 0, sc0,   \
                                scn);                                          \
         else if (!fused)                                                      \
@@ -957,29 +957,29 @@ int dns_saddle::enqueue_cycle_dist(const double *b, double *x, int c,
         DNS_TRY(comm->allreduce(dnorm, 1, stream));
     }
     if (lazy) {
-        const bool cells = dist_tail.on && dist_tail.cells.nblocks > 0;
+        const bool cells = hk.dist_tail.on && hk.dist_tail.cells.nblocks > 0;
         hipLaunchKernelGGL(k_arn_tail_lazy1,
-                           gridD + (cells ? dist_tail.cells.nblocks : 0), kBlock,
+                           gridD + (cells ? hk.dist_tail.cells.nblocks : 0), kBlock,
                            0, stream, n, hsum, ctl.p, histdev.p, (int)hist_cap,
-                           o->maxiter, o->rtol, o->atol, Z.p, x, tail_extrap,
-                           r.p, w.p, dist_rnew, nv, gridD,
-                           cells ? dist_tail.x0copy : (const double *)nullptr,
-                           cells ? dist_tail.cells : TailCells{});
-        dist_tail.ran = cells;
+                           o->maxiter, o->rtol, o->atol, Z.p, x, hk.tail_extrap,
+                           r.p, w.p, hk.carry_rnew, nv, gridD,
+                           cells ? hk.dist_tail.x0copy : (const double *)nullptr,
+                           cells ? hk.dist_tail.cells : TailCells{});
+        if (cells) hk.dist_tail_ran = true;
     } else if (fused) {
         hipLaunchKernelGGL(k_arn_tail_acc, gridD, kBlock, 0, stream, c, n, hsum,
                            1, ctl.p, histdev.p, (int)hist_cap, o->maxiter, Z.p,
-                           ld, x, tail_extrap);
+                           ld, x, hk.tail_extrap);
     } else {
         hipLaunchKernelGGL(k_arn_tail, 1, kBlock, 0, stream, c, dnorm, 1, ctl.p,
                            histdev.p, (int)hist_cap, o->maxiter, 0);
         hipLaunchKernelGGL(k_basis_combine_acc, gridD, kBlock, 0, stream, n,
-                           Z.p, ld, ctl.p, x, tail_extrap);
+                           Z.p, ld, ctl.p, x, hk.tail_extrap);
     }
     // (residual carry-over: only the one-step cycle knows the true residual
     // behind it; a solve that ends with a general cycle carries none)
-    if (!lazy && dist_rnew)
-        DNS_HIP(hipMemsetAsync(dist_rnew, 0, (size_t)nv * sizeof(double),
+    if (!lazy && hk.carry_rnew)
+        DNS_HIP(hipMemsetAsync(hk.carry_rnew, 0, (size_t)nv * sizeof(double),
                                stream));
     DNS_HIP(hipGetLastError());
     return DNS_OK;

@@ -1515,13 +1515,47 @@ static inline uint64_t bits_of(double v) {
     return u;
 }
 
+// one word of a graph key per pointer, per count or flag, per coefficient
+static inline uint64_t kw(const void *p) { return (uint64_t)(uintptr_t)p; }
+static inline uint64_t kw(double v) { return bits_of(v); }
+template <typename T,
+          typename = typename std::enable_if<std::is_integral<T>::value>::type>
+static inline uint64_t kw(T v) { return (uint64_t)v; }
+
+static inline uint64_t mix64(uint64_t h, std::initializer_list<uint64_t> words) {
+    for (uint64_t v : words) h ^= v + 0x9e3779b97f4a7c15ULL + (h << 6) + (h >> 2);
+    return h;
+}
+
+// The tail kernel of EVERY cycle writes the next time step's warm start: a
+// second cycle captured while the history was still filling (cubic
+// coefficients) must not be replayed once it is full (the carry-over front
+// kernel relies on x0 being exactly the combination it computes K x0 for).
+uint64_t dns::StepHooks::key(bool first) const {
+    const TailExtrap &te = tail_extrap;
+    uint64_t k = mix64(0x7e, {kw(te.e0), kw(te.e1), kw(te.e2), kw(te.e3),
+                              kw(te.e4), kw(te.h1), kw(te.h2), kw(te.h3),
+                              kw(te.h4), kw(te.out), kw(z_plan), kw(carry_rnew)});
+    if (!first) return k;
+    k = mix64(k, {prologue_key, kw(prologue_has_resid), kw(resid_nparts),
+                  kw(stepctr), kw(step6.on), kw(step6.t6.x0), kw(step6.t6.xout),
+                  kw(step6.t6.rnew), kw(step6.kx), kw(dist_tail.on),
+                  kw(dist_tail.x0copy)});
+    for (const TailCells *c : {&step6.cells, &dist_tail.cells})
+        k = mix64(k, {kw(c->ncells), kw(c->nblocks), kw(c->cellmap), kw(c->glam),
+                      kw(c->area), kw(c->dbctab.base), kw(c->dbctab.ctr),
+                      kw(c->dbctab.stride), kw(c->dbctab.rows), kw(c->cellvals),
+                      kw(c->sel), kw(c->nsel)});
+    return k;
+}
+
 // One restart cycle of right-preconditioned GMRES with `c` Arnoldi steps:
 // residual, start, c x (precondition, K apply, Gram-Schmidt, close), then the
 // correction x += P^-1 (V y).  Kernels after convergence return at once
 // (ctl->done), so `c` may overshoot.  Nothing here synchronises or allocates.
 int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
                               const dns_solve_opts *o, int first,
-                              bool have_resid) {
+                              bool have_resid, const dns::StepHooks &hk) {
     // (cycles per application of the multigrid block in THIS Krylov cycle:
     // part of what a captured graph of length c holds)
     mg_two_now = mg_two_for(c);
@@ -1557,8 +1591,8 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
     }
     // the consumers of a reduction read the per-workgroup partials
     const double *rr_part = partR.p, *bb_part = partB.p;
-    const int rr_np =
-        (have_resid && prologue_nparts > 0) ? prologue_nparts : resid_np;
+    const int rr_np = (have_resid && hk.resid_nparts > 0)
+                          ? hk.resid_nparts : resid_np;
     const bool dense = popts.schur == DNS_SCHUR_DENSE;
     const int q0 = 0, q1 = np;
     // (dense Schur rows: one wave each, four per workgroup)
@@ -1579,8 +1613,15 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
     };
     // six-node step: K z_j is kept per column (the tail forms the new
     // residual r0 - sum y_j K z_j from them)
+    const StepHooks::Step6 &step6 = hk.step6;
+    // (the first head kernel of a solve bumps the stepper's step counter)
+    int *const ctr0 = first == 1 ? hk.stepctr : nullptr;
     const bool s6 = step6.on && fusedgs && !stream_k && have_resid &&
                     Wcols.n >= (size_t)c * ld;
+    Tail6 t6 = step6.t6;
+    t6.r0 = r.p;
+    t6.W = Wcols.p;
+    t6.nv = nv;
     auto wcol = [&](int jj) -> double * {
         return s6 ? Wcols.p + (size_t)jj * ld : w.p;
     };
@@ -1601,12 +1642,10 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
         double *zp = Z.p + nv;
         if (fp32_store)
             hipLaunchKernelGGL(k_arn_head_lazy<2>, gridA, kBlock, 0, stream, np,
-                               (const void *)sinv32.p, tau.p, zp, sld,
-                               step_counter);
+                               (const void *)sinv32.p, tau.p, zp, sld, ctr0);
         else
             hipLaunchKernelGGL(k_arn_head_lazy<1>, gridA, kBlock, 0, stream, np,
-                               (const void *)sinv.p, tau.p, zp, 0,
-                               step_counter);
+                               (const void *)sinv.p, tau.p, zp, 0, ctr0);
         DNS_TRY(apply_fhat_part(r.p, zp, Z.p, zero_ptr(), nullptr));
         // K z with <r, w>, <w, w> folded to at most kBlock partials of each
         // (kLazyRows consecutive rows per sub-wave and pass)
@@ -1619,14 +1658,10 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
                                kLazyBlock, 0, stream, n, K.rowptr.p,
                                K.colidx.p, K.vals.p, Z.p, Wcols.p, r.p,
                                partA.p));
-        Tail6 t6 = step6.t6;
-        t6.r0 = r.p;
-        t6.W = Wcols.p;
-        t6.nv = nv;
         hipLaunchKernelGGL(k_arn_tail6<true>, gridD + step6.cells.nblocks,
                            kBlock, 0, stream, 1, n, gridD, partA.p, gridL,
                            ctl.p, histdev.p, (int)hist_cap, o->maxiter, Z.p,
-                           ld, t6, tail_extrap, step6.cells,
+                           ld, t6, hk.tail_extrap, step6.cells,
                            TailLazy{partR.p, partB.p, gridD, o->rtol,
                                     o->atol});
         DNS_HIP(hipGetLastError());
@@ -1673,7 +1708,7 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
                                (const void *)nullptr, zp, ctl.p, o->rtol,
                                o->atol, bb_part, rr_np, o->maxiter, q0, q1,
                                (j == 0) ? first : 0, (const double *)nullptr,
-                               (j == 0 && first == 1) ? step_counter : nullptr);
+                               j == 0 ? ctr0 : nullptr);
         } else if (fusedgs && j > 0) {
             if (dense && fp32_store)
                 hipLaunchKernelGGL(k_arn_head_f<2>, gridA, kBlock, 0, stream, n,
@@ -1699,7 +1734,7 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
                                (const void *)sinv32.p, zp, ctl.p, o->rtol,
                                o->atol, bb_part, rr_np, o->maxiter, q0, q1,
                                (j == 0) ? first : 0, tin,
-                               (j == 0 && first == 1) ? step_counter : nullptr,
+                               j == 0 ? ctr0 : nullptr,
                                sld);
         else if (dense)
             hipLaunchKernelGGL(k_arn_head<1>, gridA, kBlock, 0, stream, n, nv,
@@ -1707,14 +1742,14 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
                                (const void *)sinv.p, zp, ctl.p, o->rtol,
                                o->atol, bb_part, rr_np, o->maxiter, q0, q1,
                                (j == 0) ? first : 0, tin,
-                               (j == 0 && first == 1) ? step_counter : nullptr);
+                               j == 0 ? ctr0 : nullptr);
         else
             hipLaunchKernelGGL(k_arn_head<0>, gridA, kBlock, 0, stream, n, nv,
                                np, j, src, spart, snp, V.p, ld,
                                (const void *)sinv.p, zp, ctl.p, o->rtol,
                                o->atol, bb_part, rr_np, o->maxiter, q0, q1,
                                (j == 0) ? first : 0, tin,
-                               (j == 0 && first == 1) ? step_counter : nullptr);
+                               j == 0 ? ctr0 : nullptr);
         if (mgs) {
             // Schur block = V-cycle on V_j,p (or tau(V_j))
             const double *sin = V.p + (size_t)j * ld + nv;
@@ -1805,14 +1840,10 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
     }
     if (s6) {
         // six-node step: out-of-place tail + new residual + convection cells
-        Tail6 t6 = step6.t6;
-        t6.r0 = r.p;
-        t6.W = Wcols.p;
-        t6.nv = nv;
         hipLaunchKernelGGL(k_arn_tail6<false>, gridD + step6.cells.nblocks,
                            kBlock, 0, stream, c, n, gridD, partA.p,
                            kparts(c - 1), ctl.p, histdev.p, (int)hist_cap,
-                           o->maxiter, Z.p, ld, t6, tail_extrap, step6.cells,
+                           o->maxiter, Z.p, ld, t6, hk.tail_extrap, step6.cells,
                            TailLazy{});
         DNS_HIP(hipGetLastError());
         return DNS_OK;
@@ -1821,14 +1852,14 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
         // one GPU, fused Gram-Schmidt: tail and correction in ONE launch
         hipLaunchKernelGGL(k_arn_tail_acc, gridD, kBlock, 0, stream, c, n,
                            partA.p, kparts(c - 1), ctl.p, histdev.p,
-                           (int)hist_cap, o->maxiter, Z.p, ld, x, tail_extrap);
+                           (int)hist_cap, o->maxiter, Z.p, ld, x, hk.tail_extrap);
         DNS_HIP(hipGetLastError());
         return DNS_OK;
     }
     hipLaunchKernelGGL(k_arn_tail, 1, kBlock, 0, stream, c, partN.p, gridD,
                        ctl.p, histdev.p, (int)hist_cap, o->maxiter, 0);
     hipLaunchKernelGGL(k_basis_combine_acc, gridD, kBlock, 0, stream, n, Z.p,
-                       ld, ctl.p, x, tail_extrap);
+                       ld, ctl.p, x, hk.tail_extrap);
     DNS_HIP(hipGetLastError());
     return DNS_OK;
 }
@@ -1851,8 +1882,9 @@ int dns_saddle::ensure_solver_buffers(const dns_solve_opts *o) {
 }
 
 int dns_saddle::gmres(const double *b, double *x, const dns_solve_opts *o,
-                      dns_solve_stats *st, const std::function<int()> &prologue,
-                      uint64_t prologue_key, bool prologue_has_resid) {
+                      dns_solve_stats *st, const dns::StepHooks *hooks) {
+    static const StepHooks none;
+    const StepHooks &hk = hooks ? *hooks : none;
     const int m = std::max(1, std::min(o->restart, kMaxRestart));
     DNS_TRY(ensure_solver_buffers(o));
     // (RCCL calls are captured with the kernels; host-callback communicators
@@ -1875,49 +1907,24 @@ int dns_saddle::gmres(const double *b, double *x, const dns_solve_opts *o,
     // dots fused into the K apply while the system is launch-latency bound
     fuse_dots = n <= 400000;
     int restarts = 0;
-    int dist_stalls = 0;
     bool first = true;          // prologue + first cycle of the solve
     int reset = 1;              // what the head kernel resets (k_arn_head)
     dns_solve_opts oo = *o;
     // (eight solves in a row that fell back: stop trying on this system)
     if (gs_fallbacks >= 8 && oo.reorth == 2) oo.reorth = 0;
-    // the tail kernel of EVERY cycle writes the next time step's warm start
-    // (tail_extrap): its coefficients and pointers are baked into the captured
-    // node, so they are part of every cycle's key -- a second cycle captured
-    // while the history was still filling (cubic coefficients) must not be
-    // replayed once it is full (the carry-over front kernel relies on x0
-    // being exactly the combination it computes K x0 for)
-    uint64_t tek = 0x7e;
-    {
-        const double te_c[5] = {tail_extrap.e0, tail_extrap.e1, tail_extrap.e2,
-                                tail_extrap.e3, tail_extrap.e4};
-        for (int i = 0; i < 5; ++i) {
-            uint64_t u;
-            memcpy(&u, &te_c[i], sizeof(u));
-            tek ^= u + 0x9e3779b97f4a7c15ULL + (tek << 6) + (tek >> 2);
-        }
-        tek ^= (uint64_t)(uintptr_t)tail_extrap.out + 0x9e3779b97f4a7c15ULL +
-               (tek << 6) + (tek >> 2);
-    }
     const CtlHeader &hdr = hdr_host.p->h;        // (filled by read_header)
     while (true) {
-        std::vector<uint64_t> key = {
-            1u, tek, (uint64_t)(uintptr_t)b, (uint64_t)(uintptr_t)x, (uint64_t)c,
-            (uint64_t)oo.reorth, (uint64_t)oo.maxiter, bits_of(oo.rtol),
-            bits_of(oo.atol), first ? prologue_key : 0u,
-            (uint64_t)popts.cheb_degree, (uint64_t)popts.schur,
-            (uint64_t)first + 2u * (uint64_t)reset, (uint64_t)fhat_explicit,
-            (uint64_t)fuse_dots, (uint64_t)(uintptr_t)z_plan_override,
-            (uint64_t)dist_x0_exchange + 2u * (uint64_t)dist_lazy1 +
-                4u * (uint64_t)step6_lazy,
-            (uint64_t)(uintptr_t)dist_rnew};
+        const std::vector<uint64_t> key = {
+            1u, hk.key(first), kw(b), kw(x), kw(c), kw(oo.reorth),
+            kw(oo.maxiter), kw(oo.rtol), kw(oo.atol), kw(popts.cheb_degree),
+            kw(popts.schur), kw(first + 2 * reset), kw(fhat_explicit),
+            kw(fuse_dots), kw(dist_x0_exchange + 2 * dist_lazy1 + 4 * step6_lazy)};
         DNS_TRY(run_cached(key, graph, [&]() -> int {
-            if (first && prologue) DNS_TRY(prologue());
+            if (first && hk.prologue) DNS_TRY(hk.prologue());
+            const bool have_resid = first && hk.prologue_has_resid;
             if (dist())
-                return enqueue_cycle_dist(b, x, c, &oo, reset,
-                                          first && prologue_has_resid);
-            return enqueue_cycle(b, x, c, &oo, reset,
-                                 first && prologue_has_resid);
+                return enqueue_cycle_dist(b, x, c, &oo, reset, have_resid, hk);
+            return enqueue_cycle(b, x, c, &oo, reset, have_resid, hk);
         }));
         first = false;
         reset = 0;
@@ -1933,7 +1940,6 @@ int dns_saddle::gmres(const double *b, double *x, const dns_solve_opts *o,
             // the fused Gram-Schmidt gave up on its norm: go on from the
             // current iterate with the explicit kernel (row-partitioned: with
             // a new fused cycle -- it restarts from a fresh, orthonormal basis)
-            (void)dist_stalls;
             gs_fallbacks++;
             oo.reorth = 0;
             reset = 2;

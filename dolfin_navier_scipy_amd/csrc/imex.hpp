@@ -10,6 +10,27 @@
 #include "step_kernels.hpp"
 #include <memory>
 
+// The form of one resident step, decided ONCE (dns_imex::plan): the front of
+// the step, the hooks the solver is handed and the bookkeeping behind a
+// replayed graph all read it.
+struct StepPlan {
+    // the front of the step: k_step_one2; k_step_front (MODE `mode`: 0 plain,
+    // 1 PRE, 2 carry) + k_step_back; k_dist_front; kernels of their own
+    enum Form { Plain, Six, Fused, DistFront, Rows, StreamRhs, StreamRows };
+    Form form = Plain;
+    int mode = 0;
+    // (each flag is said where it is decided: dns_imex::plan)
+    bool can_pre = false, use_pre = false, carry = false, dcarry = false,
+         dtail = false, have_cells = false, zwide = false;
+    // injective: three bits of form, two of mode, one per flag
+    uint64_t key() const {
+        return (uint64_t)form | (uint64_t)mode << 3 | (uint64_t)can_pre << 5 |
+               (uint64_t)use_pre << 6 | (uint64_t)carry << 7 |
+               (uint64_t)dcarry << 8 | (uint64_t)dtail << 9 |
+               (uint64_t)have_cells << 10 | (uint64_t)zwide << 11;
+    }
+};
+
 // (dns::Ring: the ring indices of xs, nsol, and whether the work buffer holds
 // the warm start already)
 struct dns_imex : dns::Ring {
@@ -76,9 +97,9 @@ struct dns_imex : dns::Ring {
     // them: with the cells in the tail / with the cell kernel left out because
     // the tail before had run it (dns_imex_step_counters: tests)
     int64_t n_steps_built = 0, n_steps_tail_cells = 0, n_steps_cells_reused = 0;
-    bool dtail_wanted(const dns_solve_opts *o) const;
-    int prime_dcells(const dns_solve_opts *o);
+    int prime_dcells(const dns_imex_coeffs *cf, const dns_solve_opts *o);
     uint64_t six_conv_gen = 0;     // conv->dbc_gen the cell values belong to
+    bool six_capable() const;
     int prime_six(const dns_imex_coeffs *cf, bool keep_r);
     long steps_enqueued = 0;       // counts step_device calls (graph replay
                                    // must advance the host state itself)
@@ -218,7 +239,29 @@ struct dns_imex : dns::Ring {
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
     }
+    uint64_t config_key(const dns_imex_coeffs *cf) const;
     uint64_t step_key(const dns_imex_coeffs *cf) const;
+    // gather lists and cell values of the device convection (nulls: none)
+    struct ConvGather {
+        const int *gptr = nullptr, *gidx = nullptr;
+        const double *cellvals = nullptr;
+    };
+    ConvGather conv_gather() const {
+        if (!conv) return {};
+        return {conv->gptr.p, conv->gidx.p, conv->cellvals.p};
+    }
+    StepPlan plan(const dns_imex_coeffs *cf, const dns_solve_opts *o,
+                  int cycle_len) const;
+    // the front of a step by its form, and what they share
+    int front_nparts(const StepPlan &pl) const;
+    int warm_start(const dns_imex_coeffs *cf, const StepPlan &pl);
+    int front_six(const dns_imex_coeffs *cf, const StepPlan &pl);
+    int front_fused(const dns_imex_coeffs *cf, const StepPlan &pl);
+    int front_dist(const dns_imex_coeffs *cf, const StepPlan &pl);
+    int front_rows(const dns_imex_coeffs *cf, const StepPlan &pl);
+    int front_stream(const dns_imex_coeffs *cf, const StepPlan &pl);
+    int prologue(const dns_imex_coeffs *cf, const StepPlan &pl);
+    dns::StepHooks hooks(const dns_imex_coeffs *cf, const StepPlan &pl);
     int step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
                     dns_solve_stats *st, bool with_true_residual);
 };

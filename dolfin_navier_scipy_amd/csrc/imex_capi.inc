@@ -1,70 +1,46 @@
 // extern "C" entry points of the device-resident IMEX loop (included by
 // dns_amd.hip).
 
-static inline uint64_t mix64(uint64_t h, uint64_t v) {
-    h ^= v + 0x9e3779b97f4a7c15ULL + (h << 6) + (h >> 2);
-    return h;
+// The ring-independent part of everything a captured step depends on besides
+// the solver options: coefficients, this stepper and its convection, tables,
+// the primed-state flags, feedback and recorder
+uint64_t dns_imex::config_key(const dns_imex_coeffs *cf) const {
+    uint64_t k = mix64(
+        0x1234, {kw(cf->a_c), kw(cf->a_p), kw(cf->cn_c), kw(cf->cn_o),
+                 kw(conv_scale), kw(cf->extrapolate_x0), kw(this), kw(conv),
+                 kw(tables() ? 1 + 2 * tab_v + 4 * tab_p : 0), kw(gtab.p),
+                 kw(gptab.p), kw(tab_rows),
+                 kw((cf->carry_residual != 0) + 2 * carry_ok + 4 * six_ok +
+                    8 * dcells_ok)});
+    if (conv) k = mix64(k, {kw(conv->dbc_rows), kw(conv->dbc_tab.p)});
+    if (fb.on) k = mix64(k, {fb_key()});
+    if (rec) k = mix64(k, {rec_key()});
+    return k;
 }
 
-// everything the captured graph of a step depends on besides the solver options
+// ... and the ring as it stands
 uint64_t dns_imex::step_key(const dns_imex_coeffs *cf) const {
-    uint64_t pkey = 0x1234;
-    pkey = mix64(pkey, (uint64_t)(cur + 8 * prev + 64 * pprev + 512 * p3 +
-                                  4096 * p4 + 32768 * work));
-    pkey = mix64(pkey, (uint64_t)(nc + 2 * std::min(nsol, 5) +
-                                  16 * cf->extrapolate_x0));
-    pkey = mix64(pkey, bits_of(cf->a_c));
-    pkey = mix64(pkey, bits_of(cf->a_p));
-    pkey = mix64(pkey, bits_of(cf->cn_c));
-    pkey = mix64(pkey, bits_of(cf->cn_o));
-    pkey = mix64(pkey, (uint64_t)(uintptr_t)this);
-    pkey = mix64(pkey, (uint64_t)(uintptr_t)conv);
-    pkey = mix64(pkey, bits_of(conv_scale));
-    pkey = mix64(pkey, (uint64_t)(tables() ? 1 + 2 * tab_v + 4 * tab_p : 0));
-    if (conv) {
-        pkey = mix64(pkey, (uint64_t)conv->dbc_rows);
-        pkey = mix64(pkey, (uint64_t)(uintptr_t)conv->dbc_tab.p);
-    }
-    pkey = mix64(pkey, (uint64_t)(uintptr_t)gtab.p);
-    pkey = mix64(pkey, (uint64_t)(uintptr_t)gptab.p);
-    pkey = mix64(pkey, (uint64_t)tab_rows);
-    pkey = mix64(pkey, (uint64_t)((cf->carry_residual != 0) + 2 * carry_ok +
-                                  4 * six_ok + 8 * dcells_ok));
-    if (fb.on) pkey = mix64(pkey, fb_key());
-    if (rec) pkey = mix64(pkey, rec_key());
-    return pkey;
+    return mix64(config_key(cf), {kw(cur + 8 * prev + 64 * pprev + 512 * p3 +
+                                     4096 * p4 + 32768 * work),
+                                  kw(nc + 2 * std::min(nsol, 5))});
 }
 
 // "feedback on", its shape, its coefficients and every buffer k_lti_step is
 // handed: a graph captured for another set must not be replayed
 uint64_t dns_imex::fb_key() const {
-    uint64_t k = 0xfb;
-    k = mix64(k, (uint64_t)(fb.hN + 256 * fb.Ny + 65536 * fb.Nu));
-    k = mix64(k, (uint64_t)fb.rows + ((uint64_t)fb.has_drift << 40));
-    k = mix64(k, bits_of(fb.dt));
-    k = mix64(k, bits_of(fb.c_n));
-    k = mix64(k, bits_of(fb.c_c));
-    for (const void *q : {(const void *)fb.C.vals.p, (const void *)fb.B.vals.p,
-                          (const void *)fb.haT.p, (const void *)fb.drift.p,
-                          (const void *)fb.state.p, (const void *)fb.ylog.p,
-                          (const void *)fb.ulog.p, (const void *)fb.geff.p,
-                          (const void *)g.p})
-        k = mix64(k, (uint64_t)(uintptr_t)q);
-    return k;
+    return mix64(0xfb, {kw(fb.hN), kw(fb.Ny), kw(fb.Nu), kw(fb.rows),
+                        kw(fb.has_drift), kw(fb.dt), kw(fb.c_n), kw(fb.c_c),
+                        kw(fb.C.vals.p), kw(fb.B.vals.p), kw(fb.haT.p),
+                        kw(fb.drift.p), kw(fb.state.p), kw(fb.ylog.p),
+                        kw(fb.ulog.p), kw(fb.geff.p), kw(g.p)});
 }
 
 // "recorder on", its shape, every buffer k_record_step is handed and the
 // pressure scale of the state it is about to write down
 uint64_t dns_imex::rec_key() const {
-    uint64_t k = 0x7ec;
-    k = mix64(k, (uint64_t)rec->rows);
-    k = mix64(k, (uint64_t)rec->Ny + ((uint64_t)rec->nslots << 32));
-    k = mix64(k, bits_of(last_pscale));
-    for (const void *q : {(const void *)(rec->C ? rec->C->vals.p : nullptr),
-                          (const void *)rec->slot.p, (const void *)rec->snap.p,
-                          (const void *)rec->ylog.p})
-        k = mix64(k, (uint64_t)(uintptr_t)q);
-    return k;
+    return mix64(0x7ec, {kw(rec->rows), kw(rec->Ny), kw(rec->nslots),
+                         kw(last_pscale), kw(rec->C ? rec->C->vals.p : nullptr),
+                         kw(rec->slot.p), kw(rec->snap.p), kw(rec->ylog.p)});
 }
 
 int dns_imex::rec_launch(hipStream_t s) {
@@ -130,33 +106,73 @@ int dns_imex::build_r1_pair(const dns::HostCsr &rows, int v0) {
     return DNS_OK;
 }
 
-// a row-partitioned step of the latency regime whose (pipelined, one-step)
-// cycle ends in k_arn_tail_lazy1: its tail evaluates the convection cells of
-// the new velocity (the conditions of `dfront` in step_device and of `lazy`
-// in enqueue_cycle_dist, for the state as it stands)
-bool dns_imex::dtail_wanted(const dns_solve_opts *o) const {
+// what the six-node step asks of the system, whatever the solve
+bool dns_imex::six_capable() const {
+    return env_six && !sys->dist() && !sys->streams(sys->K) &&
+           !sys->streams(R1) && sys->have_jg &&
+           sys->popts.schur == DNS_SCHUR_DENSE;
+}
+
+// The form of the step about to be built (or replayed).  `cycle_len`: its
+// sys->pipeline_c (0: a synchronous solve, first cycle sys->cycle_first long)
+StepPlan dns_imex::plan(const dns_imex_coeffs *cf, const dns_solve_opts *o,
+                        int cycle_len) const {
     const dns_saddle *h = sys;
-    return env_dtail && conv && h->dist() && part.on && env_dfront &&
-           !h->streams(R1) && !h->streams(h->K) &&
-           o->method == DNS_METHOD_GMRES && h->dist_lazy1 && o->reorth == 2 &&
-           o->atol < 1.0 && o->maxiter > 0 &&
-           // a pipelined one-step cycle, or a synchronous solve whose first
-           // cycle is one step long (its cell values count only if that
-           // cycle was the whole solve: step_device)
-           (h->pipeline_c == 1 || (h->pipeline_c == 0 && h->cycle_first == 1));
+    const bool gm = o->method == DNS_METHOD_GMRES, cr = cf->carry_residual != 0;
+    const bool rows = h->dist() && part.on;
+    const bool sk = h->streams(h->K), sr = h->streams(R1);
+    StepPlan p;
+    // one-launch prologue on one GPU while the system is latency bound (it
+    // gathers K's columns from up to five history vectors; beyond ~4e5
+    // unknowns forming x0 first and gathering once is cheaper)
+    const bool fused = !h->dist() && !sk;
+    // the tail before has left this step's warm start in the work buffer (same
+    // coefficient set)?  (row-partitioned with the stepper's own halo plan: the
+    // tails of the partitioned cycle extrapolate over own entries and halo)
+    p.can_pre = !h->dist() || part.on;
+    p.use_pre = p.can_pre && pre_ok &&
+                pre_sig == dns::extrap_sig(nsol, cf->extrapolate_x0);
+    // six-node step: pipelined, primed by prime_six or by the step before
+    const bool six = six_capable() && six_ok && cycle_len > 0 && gm &&
+                     o->reorth == 2 && nsol >= 5;
+    // residual carry-over: a PRE step whose ring of K x products is current
+    p.carry = !six && cr && fused && p.use_pre && carry_ok && b_valid && gm;
+    // row-partitioned, latency regime: ONE front kernel (convection gather,
+    // right-hand side, residual and its norms)
+    const bool dfront = rows && env_dfront && !sr && !sk && gm;
+    // (the residual of every one-step solve is carried into the next
+    // right-hand side, as on one GPU: k_dist_front / k_arn_tail_lazy1)
+    p.dcarry = dfront && cr && rc6[0].p && rc6[1].p && nsol >= 2;
+    // ... whose cycle ends in k_arn_tail_lazy1 with the convection cells of
+    // the new velocity (the conditions of `lazy` in enqueue_cycle_dist): a
+    // pipelined one-step cycle, or a synchronous solve whose first cycle is one
+    // step long (its cells count only if it was the whole solve: step_device)
+    const bool one = cycle_len == 1 || (cycle_len == 0 && h->cycle_first == 1);
+    p.dtail = dfront && env_dtail && conv && h->dist_lazy1 && o->reorth == 2 &&
+              o->atol < 1.0 && o->maxiter > 0 && one && x0c.p != nullptr;
+    p.have_cells = dfront && conv && dcells_ok && dcells_gen == conv->dbc_gen;
+    // row-partitioned: the preconditioned vectors travel over THIS stepper's
+    // halo (rows of K, of R1 and the convection cells): the new solution is
+    // valid on it, the next step's front and warm start need no exchange
+    p.zwide = rows;
+    p.form = six      ? StepPlan::Six
+             : fused  ? StepPlan::Fused
+             : dfront ? StepPlan::DistFront
+             : rows   ? (sr ? StepPlan::StreamRows : StepPlan::Rows)
+             : sr && !h->dist() ? StepPlan::StreamRhs
+                                : StepPlan::Plain;
+    if (p.form == StepPlan::Fused) p.mode = p.carry ? 2 : p.use_pre ? 1 : 0;
+    return p;
 }
 
 // the cell values of the current velocity by a plain launch (start of a
 // pipelined phase, after a batch has been restored): the first step then
 // already is the seven-kernel step the graphs were captured for
-int dns_imex::prime_dcells(const dns_solve_opts *o) {
+int dns_imex::prime_dcells(const dns_imex_coeffs *cf, const dns_solve_opts *o) {
     dns_saddle *h = sys;
     dcells_ok = false;
-    const int pc = h->pipeline_c;
-    h->pipeline_c = 1;                 // (asked before the batches set it)
-    const bool want = dtail_wanted(o);
-    h->pipeline_c = pc;
-    if (!want) return DNS_OK;
+    // (asked before the batches set the cycle length: a one-step cycle?)
+    if (!plan(cf, o, 1).dtail) return DNS_OK;
     conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
     DNS_TRY(conv->enqueue_cells(xs[cur].p, h->stream, part.conv_sel.p,
                                 part.nsel));
@@ -165,254 +181,269 @@ int dns_imex::prime_dcells(const dns_solve_opts *o) {
     return DNS_OK;
 }
 
+// partials of ||r||^2, ||b||^2 the front leaves (0: no residual)
+int dns_imex::front_nparts(const StepPlan &pl) const {
+    const dns_saddle *h = sys;
+    if (pl.form == StepPlan::Six) return h->gridD;
+    if (pl.form == StepPlan::Fused)
+        return std::max(1, std::min((h->n + 31) / 32, 1024));
+    if (pl.form != StepPlan::DistFront) return 0;
+    const dns::RowMap rm = h->dist_rowmap();
+    return std::max(1, std::min(dns::grid_for_rows(rm.len1 + rm.len2, h->K.lpr),
+                                2048));
+}
+
+// six-node step, ONE launch: K x0, R1 v, convection gather, b, r, norms
+int dns_imex::front_six(const dns_imex_coeffs *cf, const StepPlan &) {
+    dns_saddle *h = sys;
+    const int par = work & 1;
+    // (residuals that do not exist yet are zeros: prime_six)
+    const double *rcc = cf->carry_residual ? rc6[par].p : nullptr;
+    const double *rcp = cf->carry_residual ? rc6[1 - par].p : nullptr;
+    // K x0 side by side with b; r = b - kx and the norms are formed by the
+    // first tau kernel (gridD partials)
+    const int gk = h->gridS, gb = dns::grid_for_rows(h->n, h->K.lpr);
+    const ConvGather cg = conv_gather();
+    DNS_LPR_SWITCH(
+        h->K.lpr,
+        hipLaunchKernelGGL(
+            (dns::k_step_one2<L>), gk + gb, dns::kBlock, 0, h->stream, gk, h->n,
+            h->nv, h->K.rowptr.p, h->K.colidx.p, h->K.vals.p, R1.rowptr.p,
+            R1.colidx.p, R1.vals.p, x0buf[par].p, xs[cur].p, xs[prev].p,
+            cf->a_c, (nsol >= 2) ? cf->a_p : 0.0, nfc[nc].p, nfc[no].p,
+            cf->cn_c, cf->cn_o, g_ref(), gp_ref(), cg.gptr, cg.gidx,
+            cg.cellvals, conv_scale, rcc, rcp, b.p, kx6.p));
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+// front: convection cells || (x0, K x0, R1 v) -- one launch; back: convection
+// gather, b, r = b - K x0, norms (step_kernels.hpp)
+int dns_imex::front_fused(const dns_imex_coeffs *cf, const StepPlan &pl) {
+    dns_saddle *h = sys;
+    hipStream_t s = h->stream;
+    const int n = h->n, nv = h->nv;
+    double *x = xs[work].p;
+    double e[5];
+    dns::extrap_coeffs(nsol, cf->extrapolate_x0, e);
+    const int nconv =
+        conv ? (8 * conv->ncells + dns::kBlock - 1) / dns::kBlock : 0;
+    const dns::CarryRef cr =
+        pl.carry ? dns::CarryRef{kxs[cur].p,  kxs[prev].p, kxs[pprev].p,
+                                 kxs[p3].p,   kxs[p4].p,   rcarry.p}
+                 : dns::CarryRef{nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr};
+#define DNS_FRONT(MODE)                                                        \
+    DNS_LPR_SWITCH(                                                            \
+        h->K.lpr,                                                              \
+        hipLaunchKernelGGL(                                                    \
+            (dns::k_step_front<L, MODE>), nconv + h->gridS, dns::kBlock, 0, s, \
+            nconv, conv ? conv->ncells : 0,                                    \
+            conv ? conv->cellmap.p : (const int *)nullptr,                     \
+            conv ? conv->glam.p : (const double *)nullptr,                     \
+            conv ? conv->area.p : (const double *)nullptr,                     \
+            conv ? conv->dbc_ref() : dns::TabRef{nullptr, nullptr, 0, 1},      \
+            conv ? conv->cellvals.p : (double *)nullptr, n, nv,                \
+            h->K.rowptr.p, h->K.colidx.p, h->K.vals.p, R1.rowptr.p,            \
+            R1.colidx.p, R1.vals.p, xs[cur].p, xs[prev].p, xs[pprev].p,        \
+            xs[p3].p, xs[p4].p, e[0], e[1], e[2], e[3], e[4], cf->a_c,         \
+            (nsol >= 2) ? cf->a_p : 0.0, x, h->r.p, b.p, cr))
+    switch (pl.mode) {
+        case 2: DNS_FRONT(2); break;
+        case 1: DNS_FRONT(1); break;
+        default: DNS_FRONT(0);
+    }
+#undef DNS_FRONT
+    const ConvGather cg = conv_gather();
+    hipLaunchKernelGGL(dns::k_step_back<8>, front_nparts(pl), dns::kBlock, 0, s,
+                       n, nv, nfc[nc].p, nfc[no].p, cf->cn_c, cf->cn_o, g_ref(),
+                       gp_ref(), cg.gptr, cg.gidx, cg.cellvals, conv_scale, b.p,
+                       h->r.p, h->partR.p, h->partB.p);
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+// x0 by a kernel of its own, unless the tail before has left it in the work
+// buffer.  (The kernels carry the interpolating coefficients: the least-squares
+// fit, whose warm start the tail kernels write, falls back to the cubic here.
+// A negative extrapolate_x0 gives the LINEAR start here but x0 = x_c on the
+// fused path (extrap_coeffs): kept as it is, not yet reconciled)
+int dns_imex::warm_start(const dns_imex_coeffs *cf, const StepPlan &pl) {
+    if (pl.use_pre) return DNS_OK;
+    const int ex = cf->extrapolate_x0;
+    const int exq = ex == dns::kExtrapFit35 ? 3 : ex < 0 ? 1 : ex;
+    double e[5];
+    return dns::enqueue_extrap(dns::extrap_coeffs(nsol, exq, e), xs, *this,
+                               xs[work].p, sys->n, sys->stream);
+}
+
+// row-partitioned, latency regime: cells (unless the tail before has left
+// them: seven kernels instead of eight), warm start, ONE front kernel
+int dns_imex::front_dist(const dns_imex_coeffs *cf, const StepPlan &pl) {
+    dns_saddle *h = sys;
+    hipStream_t s = h->stream;
+    const int par = work & 1;
+    if (conv && !pl.have_cells)
+        DNS_TRY(conv->enqueue_cells(xs[cur].p, s, part.conv_sel.p, part.nsel));
+    DNS_TRY(warm_start(cf, pl));
+    const ConvGather cg = conv_gather();
+    DNS_LPR_SWITCH(
+        h->K.lpr,
+        hipLaunchKernelGGL(
+            (dns::k_dist_front<L>), front_nparts(pl), dns::kBlock, 0, s,
+            h->dist_rowmap(), h->nv, h->K.rowptr.p, h->K.colidx.p, h->K.vals.p,
+            xs[work].p, R1.rowptr.p, R1.colidx.p, R1.vals.p, xs[cur].p,
+            (nsol >= 2) ? xs[prev].p : xs[cur].p, cf->a_c,
+            (nsol >= 2) ? cf->a_p : 0.0, nfc[nc].p, nfc[no].p, cf->cn_c,
+            cf->cn_o, g_ref(), gp_ref(), cg.gptr, cg.gidx, cg.cellvals,
+            conv_scale, b.p, h->r.p, h->partR.p, h->partB.p,
+            pl.dcarry ? rc6[par].p : (const double *)nullptr,
+            pl.dcarry ? rc6[1 - par].p : (const double *)nullptr,
+            pl.dtail ? x0c.p : (double *)nullptr, h->n));
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+// convection and right-hand side by kernels of their own (Plain; Rows: this
+// rank's rows), then the warm start
+int dns_imex::front_rows(const dns_imex_coeffs *cf, const StepPlan &pl) {
+    dns_saddle *h = sys;
+    hipStream_t s = h->stream;
+    const bool own = pl.form == StepPlan::Rows;
+    const int rv0 = own ? h->dd->v0 : 0, rv1 = own ? h->dd->v1 : h->nv;
+    const int rp0 = own ? h->dd->p0 : 0, rp1 = own ? h->dd->p1 : h->np;
+    if (conv && own)
+        DNS_TRY(conv->enqueue_rows(xs[cur].p, conv_scale, nfc[nc].p, rv0, rv1,
+                                   part.conv_sel.p, part.nsel, s));
+    else if (conv)
+        DNS_TRY(conv->enqueue(xs[cur].p, conv_scale, nfc[nc].p, s));
+    const int grid = dns::grid_for_rows(std::max(1, rv1 - rv0), R1.lpr);
+    DNS_LPR_SWITCH(
+        R1.lpr,
+        hipLaunchKernelGGL(dns::k_imex_rhs<L>, grid, dns::kBlock, 0, s,
+                           rv1 - rv0, h->np, R1.rowptr.p, R1.colidx.p,
+                           R1.vals.p, xs[cur].p,
+                           (nsol >= 2) ? xs[prev].p : xs[cur].p, cf->a_c,
+                           cf->a_p, nfc[nc].p, nfc[no].p, cf->cn_c, cf->cn_o,
+                           g_ref(), gp_ref(), b.p, rv0, h->nv, rp0, rp1));
+    return warm_start(cf, pl);
+}
+
+// bandwidth regime: vector part first (StreamRhs: with the convection gather),
+// then b_v += R1 xin through the streaming kernel (xin in the solver's scratch
+// vector u; StreamRows: this rank's rows, mapped to their global numbers)
+int dns_imex::front_stream(const dns_imex_coeffs *cf, const StepPlan &pl) {
+    dns_saddle *h = sys;
+    hipStream_t s = h->stream;
+    const bool own = pl.form == StepPlan::StreamRows;
+    if (conv && own)
+        DNS_TRY(conv->enqueue_rows(xs[cur].p, conv_scale, nfc[nc].p, h->dd->v0,
+                                   h->dd->v1, part.conv_sel.p, part.nsel, s));
+    else if (conv)
+        DNS_TRY(conv->enqueue_cells(xs[cur].p, s));   // gather: in bvec
+    const ConvGather cg = own ? ConvGather{} : conv_gather();
+    hipLaunchKernelGGL(dns::k_imex_bvec, dns::grid_for_elems(h->n), dns::kBlock,
+                       0, s, h->nv, h->np, xs[cur].p,
+                       (nsol >= 2) ? xs[prev].p : xs[cur].p, cf->a_c,
+                       (nsol >= 2) ? cf->a_p : 0.0, nfc[nc].p, nfc[no].p,
+                       cf->cn_c, cf->cn_o, g_ref(), gp_ref(), b.p, h->u.p,
+                       cg.gptr, cg.gidx, cg.cellvals, conv_scale);
+    dns::StreamEpi ep = dns::stream_epi_plain(1.0, 1.0, b.p);
+    if (R1p.ready) {
+        // (the pair format knows its global rows: PairDev::aoff)
+        DNS_TRY(dns::launch_pair16x(R1p, h->u.p, b.p, ep, s, nullptr));
+    } else {
+        if (own) {
+            ep.map_on = 1;
+            ep.rm = dns::RowMap{h->dd->v0, h->dd->v1 - h->dd->v0, 0, 0};
+        }
+        DNS_TRY(dns::launch_stream16x<double>(R1, R1.vals.p, h->u.p, b.p, ep, s,
+                                              nullptr));
+    }
+    return warm_start(cf, pl);
+}
+
+// Right-hand side and warm start, enqueued in front of the first Krylov cycle
+// so that a whole time step is ONE captured graph
+int dns_imex::prologue(const dns_imex_coeffs *cf, const StepPlan &pl) {
+    // observer feedback, then the recorder: the first nodes of the step,
+    // whatever its form (xs[cur] is complete: the state after the step before)
+    if (fb.on) DNS_TRY(fb_launch(sys->stream));
+    if (rec) DNS_TRY(rec_launch(sys->stream));
+    switch (pl.form) {
+        case StepPlan::Six: return front_six(cf, pl);
+        case StepPlan::Fused: return front_fused(cf, pl);
+        case StepPlan::DistFront: return front_dist(cf, pl);
+        case StepPlan::StreamRhs:
+        case StepPlan::StreamRows: return front_stream(cf, pl);
+        default: return front_rows(cf, pl);
+    }
+}
+
+// what the solver is handed for the solve of this step
+dns::StepHooks dns_imex::hooks(const dns_imex_coeffs *cf, const StepPlan &pl) {
+    const int par = work & 1;
+    dns::StepHooks hk;
+    hk.prologue = [this, cf, pl]() -> int { return prologue(cf, pl); };
+    hk.prologue_key = mix64(step_key(cf), {pl.key()});
+    hk.resid_nparts = front_nparts(pl);
+    hk.prologue_has_resid = hk.resid_nparts > 0;
+    hk.stepctr = tables() ? stepctr.p : nullptr;
+    // the tail kernels leave the NEXT step's warm start in its work buffer
+    // (= this step's p4: not read after this step's front kernel)
+    if (pl.can_pre) {
+        double en[5];
+        dns::extrap_coeffs(std::min(nsol + 1, 5), cf->extrapolate_x0, en);
+        hk.tail_extrap = dns::TailExtrap{xs[cur].p, xs[prev].p, xs[pprev].p,
+                                         xs[p3].p,  en[0], en[1], en[2],
+                                         en[3],     en[4], xs[p4].p};
+    }
+    if (pl.form == StepPlan::Six) {
+        // the cycle starts from x0buf[par], its tail writes the solution into
+        // the work buffer, the next warm start into x0buf[1 - par], the new
+        // residual into rc6[1 - par] (the next step's `current`)
+        hk.tail_extrap.out = x0buf[1 - par].p;
+        hk.step6.on = true;
+        hk.step6.t6 = dns::Tail6{
+            x0buf[par].p, xs[work].p, nullptr, nullptr,
+            cf->carry_residual ? rc6[1 - par].p : (double *)nullptr, sys->nv};
+        hk.step6.kx = kx6.p;
+        if (conv)
+            hk.step6.cells = dns::TailCells{
+                conv->ncells,
+                (8 * conv->ncells + dns::kBlock - 1) / dns::kBlock,
+                conv->cellmap.p, conv->glam.p, conv->area.p, conv->dbc_ref(),
+                conv->cellvals.p};
+    }
+    hk.z_plan = pl.zwide ? &part.planX : nullptr;
+    hk.carry_rnew = pl.dcarry ? rc6[1 - par].p : nullptr;
+    if (pl.dtail) {
+        hk.dist_tail.on = true;
+        hk.dist_tail.x0copy = x0c.p;
+        hk.dist_tail.cells = dns::TailCells{
+            conv->ncells, (8 * part.nsel + dns::kBlock - 1) / dns::kBlock,
+            conv->cellmap.p, conv->glam.p, conv->area.p, conv->dbc_ref(),
+            conv->cellvals.p, part.conv_sel.p, part.nsel};
+    }
+    return hk;
+}
+
 int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
                           dns_solve_stats *st, bool with_true_residual) {
     dns_saddle *h = sys;
-    const int nv = h->nv, np = h->np, n = h->n;
-    hipStream_t s = h->stream;
     double *x = xs[work].p;
     // device convection: the old nfc_c becomes nfc_o, the new one is
     // evaluated from the current velocity inside the step's graph
     if (conv) std::swap(nc, no);
-    // right-hand side and warm start; enqueued in front of the first Krylov
-    // cycle so that a whole time step is ONE captured graph
-    // one-launch prologue on one GPU while the system is latency bound (it
-    // gathers K's columns from up to five history vectors; beyond ~4e5
-    // unknowns forming x0 first and gathering once is cheaper)
-    const bool fused = !h->dist() && !h->streams(h->K);
-    // the previous step's tail kernel has left this step's warm start in the
-    // work buffer (same coefficient set)?
-    // (row-partitioned with the stepper's own halo plan: the tails of the
-    // partitioned cycle extrapolate over own entries and halo alike)
-    const bool can_pre = !h->dist() || part.on;
-    const bool use_pre = can_pre && pre_ok &&
-                         pre_sig == dns::extrap_sig(nsol, cf->extrapolate_x0);
-    // residual carry-over: a PRE step whose ring of K x products is current
-    // six-node step: pipelined GMRES steps of the fused path whose warm start,
-    // cell values and residuals the step before (or prime_six) has left
-    const bool six = env_six && fused && six_ok && h->pipeline_c > 0 &&
-                     o->method == DNS_METHOD_GMRES && o->reorth == 2 &&
-                     std::min(nsol, 5) >= 5 && h->have_jg &&
-                     h->popts.schur == DNS_SCHUR_DENSE;
-    const bool carry = !six && cf->carry_residual != 0 && fused && use_pre &&
-                       carry_ok && b_valid && o->method == DNS_METHOD_GMRES;
-    const int par = work & 1;
-    // row-partitioned, latency regime: ONE front kernel (convection gather,
-    // right-hand side, residual and its norms); set once the stepper's row
-    // blocks are known (ensure_partition below)
-    bool dfront = false, dcarry = false, dtail = false, have_cells = false;
-    auto prologue = [&]() -> int {
-        // observer feedback: the first node of the step, whatever its form
-        // (xs[cur] is complete: the tail of the step before has finished)
-        if (fb.on) DNS_TRY(fb_launch(s));
-        // recorder: xs[cur] is the state after the step before (row s - 1)
-        if (rec) DNS_TRY(rec_launch(s));
-        const double *vc = xs[cur].p;
-        const double *vp = (nsol >= 2) ? xs[prev].p : xs[cur].p;
-        const int ex = cf->extrapolate_x0;
-        if (six) {
-            // ONE launch: K x0, R1 v, convection gather, b, r, norms
-            const bool cr = cf->carry_residual != 0;
-            // (residuals that do not exist yet are zeros: prime_six)
-            const double *rcc = cr ? rc6[par].p : nullptr;
-            const double *rcp = cr ? rc6[1 - par].p : nullptr;
-            // K x0 side by side with b; r = b - kx and the norms are formed
-            // by the first tau kernel (gridD partials)
-            const int gk = h->gridS;
-            const int gb = dns::grid_for_rows(n, h->K.lpr);
-            const int g1 = h->gridD;
-            DNS_LPR_SWITCH(
-                h->K.lpr,
-                hipLaunchKernelGGL(
-                    (dns::k_step_one2<L>), gk + gb, dns::kBlock, 0, s, gk, n, nv,
-                    h->K.rowptr.p, h->K.colidx.p, h->K.vals.p, R1.rowptr.p,
-                    R1.colidx.p, R1.vals.p, x0buf[par].p, xs[cur].p, xs[prev].p,
-                    cf->a_c, (nsol >= 2) ? cf->a_p : 0.0, nfc[nc].p, nfc[no].p,
-                    cf->cn_c, cf->cn_o, g_ref(), gp_ref(),
-                    conv ? conv->gptr.p : (const int *)nullptr,
-                    conv ? conv->gidx.p : (const int *)nullptr,
-                    conv ? conv->cellvals.p : (const double *)nullptr,
-                    conv_scale, rcc, rcp, b.p, kx6.p));
-            h->prologue_nparts = g1;
-            DNS_HIP(hipGetLastError());
-            return DNS_OK;
-        }
-        if (fused) {
-            double ee[5];
-            dns::extrap_coeffs(nsol, ex, ee);
-            const double e_c = ee[0], e_p = ee[1], e_pp = ee[2], e_p3 = ee[3],
-                         e_p4 = ee[4];
-            // front: convection cells || (x0, K x0, R1 v) -- one launch; back:
-            // convection gather, b, r = b - K x0, norms (step_kernels.hpp)
-            const int nconv =
-                conv ? (8 * conv->ncells + dns::kBlock - 1) / dns::kBlock : 0;
-            const dns::CarryRef cr =
-                carry ? dns::CarryRef{kxs[cur].p,  kxs[prev].p, kxs[pprev].p,
-                                      kxs[p3].p,   kxs[p4].p,   rcarry.p}
-                      : dns::CarryRef{nullptr, nullptr, nullptr,
-                                      nullptr, nullptr, nullptr};
-#define DNS_FRONT(MODE)                                                        \
-            DNS_LPR_SWITCH(                                                    \
-                h->K.lpr,                                                      \
-                hipLaunchKernelGGL(                                            \
-                    (dns::k_step_front<L, MODE>), nconv + h->gridS,            \
-                    dns::kBlock, 0, s,                                         \
-                    nconv, conv ? conv->ncells : 0,                            \
-                    conv ? conv->cellmap.p : (const int *)nullptr,             \
-                    conv ? conv->glam.p : (const double *)nullptr,             \
-                    conv ? conv->area.p : (const double *)nullptr,             \
-                    conv ? conv->dbc_ref()                                     \
-                         : dns::TabRef{nullptr, nullptr, 0, 1},                \
-                    conv ? conv->cellvals.p : (double *)nullptr, n, nv,        \
-                    h->K.rowptr.p, h->K.colidx.p, h->K.vals.p, R1.rowptr.p,    \
-                    R1.colidx.p, R1.vals.p, xs[cur].p, xs[prev].p,             \
-                    xs[pprev].p, xs[p3].p, xs[p4].p, e_c, e_p, e_pp, e_p3,     \
-                    e_p4, cf->a_c, (nsol >= 2) ? cf->a_p : 0.0, x, h->r.p,     \
-                    b.p, cr))
-            if (carry) {
-                DNS_FRONT(2);
-            } else if (use_pre) {
-                DNS_FRONT(1);
-            } else {
-                DNS_FRONT(0);
-            }
-#undef DNS_FRONT
-            const int gback = std::max(1, std::min((n + 31) / 32, 1024));
-            hipLaunchKernelGGL(
-                dns::k_step_back<8>, gback, dns::kBlock, 0, s, n, nv,
-                nfc[nc].p, nfc[no].p, cf->cn_c, cf->cn_o, g_ref(), gp_ref(),
-                conv ? conv->gptr.p : (const int *)nullptr,
-                conv ? conv->gidx.p : (const int *)nullptr,
-                conv ? conv->cellvals.p : (const double *)nullptr, conv_scale,
-                b.p, h->r.p, h->partR.p, h->partB.p);
-            h->prologue_nparts = gback;
-            DNS_HIP(hipGetLastError());
-            return DNS_OK;
-        }
-        const bool rows_only = h->dist() && part.on;
-        const int rv0 = rows_only ? h->dd->v0 : 0;
-        const int rv1 = rows_only ? h->dd->v1 : nv;
-        const int rp0 = rows_only ? h->dd->p0 : 0;
-        const int rp1 = rows_only ? h->dd->p1 : np;
-        const bool stream_rhs = !h->dist() && h->streams(R1);
-        // (row block of a partitioned run in the bandwidth regime: the same
-        // two launches, the rows mapped to their global numbers)
-        const bool stream_rows = rows_only && h->streams(R1);
-        // (the kernels below carry the interpolating coefficients: the
-        // least-squares fit, whose warm start the tail kernels write, falls
-        // back to the cubic where a step has to form x0 itself.  A negative
-        // extrapolate_x0 gives the LINEAR start here but x0 = x_c on the
-        // fused path (extrap_coeffs): kept as it is, not yet reconciled)
-        const int exq = cf->extrapolate_x0 == dns::kExtrapFit35 ? 3
-                        : cf->extrapolate_x0 < 0                ? 1
-                                                                : cf->extrapolate_x0;
-        auto warm_start = [&]() -> int {
-            // (use_pre: the previous step's tail kernel has left x0 in `x`)
-            if (use_pre) return DNS_OK;
-            double e[5];
-            return dns::enqueue_extrap(dns::extrap_coeffs(nsol, exq, e), xs,
-                                       *this, x, n, s);
-        };
-        if (dfront && rows_only) {
-            // (the tail of the step before has left the cell values of this
-            // velocity: seven kernels instead of eight)
-            if (conv && !have_cells)
-                DNS_TRY(conv->enqueue_cells(xs[cur].p, s, part.conv_sel.p,
-                                            part.nsel));
-            DNS_TRY(warm_start());
-            const dns::RowMap rm = h->dist_rowmap();
-            const int nloc = rm.len1 + rm.len2;
-            const int gF = std::max(
-                1, std::min(dns::grid_for_rows(nloc, h->K.lpr), 2048));
-            DNS_LPR_SWITCH(
-                h->K.lpr,
-                hipLaunchKernelGGL(
-                    (dns::k_dist_front<L>), gF, dns::kBlock, 0, s, rm, nv,
-                    h->K.rowptr.p, h->K.colidx.p, h->K.vals.p, x, R1.rowptr.p,
-                    R1.colidx.p, R1.vals.p, vc, vp, cf->a_c,
-                    (nsol >= 2) ? cf->a_p : 0.0, nfc[nc].p, nfc[no].p, cf->cn_c,
-                    cf->cn_o, g_ref(), gp_ref(),
-                    conv ? conv->gptr.p : (const int *)nullptr,
-                    conv ? conv->gidx.p : (const int *)nullptr,
-                    conv ? conv->cellvals.p : (const double *)nullptr,
-                    conv_scale, b.p, h->r.p, h->partR.p, h->partB.p,
-                    dcarry ? rc6[par].p : (const double *)nullptr,
-                    dcarry ? rc6[1 - par].p : (const double *)nullptr,
-                    dtail ? x0c.p : (double *)nullptr, n));
-            h->prologue_nparts = gF;
-            DNS_HIP(hipGetLastError());
-            return DNS_OK;
-        }
-        if (conv && rows_only)
-            DNS_TRY(conv->enqueue_rows(xs[cur].p, conv_scale, nfc[nc].p, rv0,
-                                       rv1, part.conv_sel.p, part.nsel, s));
-        else if (conv && stream_rhs)
-            DNS_TRY(conv->enqueue_cells(xs[cur].p, s));   // gather: in bvec
-        else if (conv)
-            DNS_TRY(conv->enqueue(xs[cur].p, conv_scale, nfc[nc].p, s));
-        if (stream_rhs) {
-            // bandwidth regime: vector part first, then b_v += R1 xin through
-            // the streaming kernel (xin in the solver's scratch vector u)
-            hipLaunchKernelGGL(dns::k_imex_bvec, dns::grid_for_elems(n),
-                               dns::kBlock, 0, s, nv, np, vc, vp, cf->a_c,
-                               (nsol >= 2) ? cf->a_p : 0.0, nfc[nc].p,
-                               nfc[no].p, cf->cn_c, cf->cn_o, g_ref(), gp_ref(),
-                               b.p, h->u.p,
-                               conv ? conv->gptr.p : (const int *)nullptr,
-                               conv ? conv->gidx.p : (const int *)nullptr,
-                               conv ? conv->cellvals.p : (const double *)nullptr,
-                               conv_scale);
-            if (R1p.ready)
-                DNS_TRY(dns::launch_pair16x(R1p, h->u.p, b.p,
-                                            dns::stream_epi_plain(1.0, 1.0, b.p),
-                                            s, nullptr));
-            else
-                DNS_TRY(dns::launch_stream16x<double>(
-                    R1, R1.vals.p, h->u.p, b.p,
-                    dns::stream_epi_plain(1.0, 1.0, b.p), s, nullptr));
-        } else if (stream_rows) {
-            hipLaunchKernelGGL(dns::k_imex_bvec, dns::grid_for_elems(n),
-                               dns::kBlock, 0, s, nv, np, vc, vp, cf->a_c,
-                               (nsol >= 2) ? cf->a_p : 0.0, nfc[nc].p,
-                               nfc[no].p, cf->cn_c, cf->cn_o, g_ref(), gp_ref(),
-                               b.p, h->u.p, (const int *)nullptr,
-                               (const int *)nullptr, (const double *)nullptr,
-                               conv_scale);
-            dns::StreamEpi ep = dns::stream_epi_plain(1.0, 1.0, b.p);
-            if (R1p.ready) {
-                // (the pair format knows its global rows: PairDev::aoff)
-                DNS_TRY(dns::launch_pair16x(R1p, h->u.p, b.p, ep, s, nullptr));
-            } else {
-                ep.map_on = 1;
-                ep.rm = dns::RowMap{rv0, rv1 - rv0, 0, 0};
-                DNS_TRY(dns::launch_stream16x<double>(R1, R1.vals.p, h->u.p,
-                                                      b.p, ep, s, nullptr));
-            }
-        } else {
-            const int grid = dns::grid_for_rows(std::max(1, rv1 - rv0), R1.lpr);
-            DNS_LPR_SWITCH(
-                R1.lpr,
-                hipLaunchKernelGGL(dns::k_imex_rhs<L>, grid, dns::kBlock, 0, s,
-                                   rv1 - rv0, np, R1.rowptr.p, R1.colidx.p,
-                                   R1.vals.p, vc, vp, cf->a_c, cf->a_p,
-                                   nfc[nc].p, nfc[no].p, cf->cn_c, cf->cn_o,
-                                   g_ref(), gp_ref(), b.p, rv0, nv, rp0, rp1));
-        }
-        return warm_start();
-    };
-    const uint64_t pkey = step_key(cf) ^ (use_pre ? 0x5bd1e995u : 0u) ^
-                          (carry ? 0x27d4eb2fu : 0u) ^ (six ? 0x165667b1u : 0u);
     if (!h->precond_ready)
         return dns::fail(DNS_ERR_NOT_READY, "preconditioner not set up");
+    // (a step that has to cut the stepper's row blocks first neither trusts
+    // nor leaves a tail's warm start: kept as it is)
+    const bool cut = h->dist() && !part.on;
     DNS_TRY(ensure_partition());
-    dfront = h->dist() && part.on && env_dfront && !h->streams(R1) &&
-             !h->streams(h->K) && o->method == DNS_METHOD_GMRES;
-    // (the residual of every one-step solve is carried into the next
-    // right-hand side, as on one GPU: k_dist_front / k_arn_tail_lazy1)
-    dcarry = dfront && cf->carry_residual != 0 && rc6[0].p && rc6[1].p &&
-             nsol >= 2;
-    dtail = dfront && dtail_wanted(o) && x0c.p != nullptr;
-    have_cells = dfront && conv && dcells_ok && dcells_gen == conv->dbc_gen;
+    StepPlan pl = plan(cf, o, h->pipeline_c);
+    if (cut) pl.can_pre = pl.use_pre = false;
+    const bool six = pl.form == StepPlan::Six;
     if (fb.on && (h->dist() || part.on))
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "observer feedback on a partitioned system: the "
@@ -434,107 +465,43 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
                              "dns_imex_set_recorder)", tab_pos);
     }
     if (conv) conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
+    const int next_nsol = std::min(nsol + 1, 5);
     if (o->method == DNS_METHOD_GMRES) {
-        // the first head kernel of the solve bumps the device step counter
-        h->step_counter = tables() ? stepctr.p : nullptr;
-        h->prologue_nparts = 0;
-        // the tail kernels leave the NEXT step's warm start in its work buffer
-        // (= this step's p4: not read after this step's front kernel)
-        const int next_nsol = std::min(nsol + 1, 5);
-        h->tail_extrap = dns::TailExtrap{};
-        if (can_pre) {
-            double en[5];
-            dns::extrap_coeffs(next_nsol, cf->extrapolate_x0, en);
-            h->tail_extrap = dns::TailExtrap{xs[cur].p, xs[prev].p, xs[pprev].p,
-                                             xs[p3].p,  en[0], en[1], en[2],
-                                             en[3],     en[4], xs[p4].p};
-        }
-        double *xstart = x;
-        if (six) {
-            // the cycle starts from x0buf[par], its tail writes the solution
-            // into the work buffer, the next warm start into x0buf[1 - par],
-            // the new residual into rc6[1 - par] (the next step's `current`)
-            h->tail_extrap.out = x0buf[1 - par].p;
-            h->step6.on = true;
-            h->step6.t6 = dns::Tail6{x0buf[par].p, x, nullptr, nullptr,
-                                     cf->carry_residual ? rc6[1 - par].p
-                                                        : (double *)nullptr,
-                                     nv};
-            h->step6.kx = kx6.p;
-            h->step6.cells = dns::TailCells{};
-            if (conv) {
-                const int nb = (8 * conv->ncells + dns::kBlock - 1) /
-                               dns::kBlock;
-                h->step6.cells = dns::TailCells{
-                    conv->ncells, nb, conv->cellmap.p, conv->glam.p,
-                    conv->area.p, conv->dbc_ref(), conv->cellvals.p};
-            }
-            xstart = x0buf[par].p;
-        }
-        // row-partitioned: the preconditioned vectors travel over THIS
-        // stepper's halo (rows of K, of R1 and the convection cells), so the
-        // new solution is valid on it when the tail has run -- the next step's
-        // right-hand side, convection and warm start need no exchange
-        const bool zwide = h->dist() && part.on;
-        h->z_plan_override = zwide ? &part.planX : nullptr;
-        h->dist_rnew = dcarry ? rc6[1 - par].p : nullptr;
-        h->dist_tail = dns_saddle::DistTail{};
-        if (dtail) {
-            const int live = part.nsel;
-            h->dist_tail.on = true;
-            h->dist_tail.x0copy = x0c.p;
-            h->dist_tail.cells = dns::TailCells{
-                conv->ncells, (8 * live + dns::kBlock - 1) / dns::kBlock,
-                conv->cellmap.p, conv->glam.p, conv->area.p, conv->dbc_ref(),
-                conv->cellvals.p, part.conv_sel.p, live};
-        }
-        const int grc = h->gmres(b.p, xstart, o, st, prologue,
-                                 pkey ^ (dfront ? 0x85ebca6bu : 0u) ^
-                                     (dcarry ? 0xc2b2ae35u : 0u) ^
-                                     (dtail ? 0x9e3779b1u : 0u) ^
-                                     (have_cells ? 0x7f4a7c15u : 0u),
-                                 fused || dfront);
+        const dns::StepHooks hk = hooks(cf, pl);
+        const int grc = h->gmres(b.p, six ? x0buf[work & 1].p : x, o, st, &hk);
         // (the cell values on the device are those of the NEW velocity if
         // the cycle that was enqueued ended in the lazy tail)
-        dcells_ok = dtail && h->dist_tail.ran &&
+        dcells_ok = pl.dtail && hk.dist_tail_ran &&
                     (h->pipeline_c > 0 ||
                      (st->restarts == 0 && st->status == DNS_OK));
         if (dcells_ok) dcells_gen = conv->dbc_gen;
         n_steps_built++;
         n_steps_tail_cells += dcells_ok ? 1 : 0;
-        n_steps_cells_reused += have_cells ? 1 : 0;
+        n_steps_cells_reused += pl.have_cells ? 1 : 0;
         if (env_debug) {
             static int said = 0;
-            if (said < 6 && (dfront || h->dist()))
-                fprintf(stderr, "[dns] partitioned step %d: front %d, cells by "
-                        "the tail before %d, tail with cells %d (cycle %d, "
-                        "wanted %d)\n", said++, (int)dfront, (int)have_cells,
-                        (int)dcells_ok, h->pipeline_c, (int)dtail_wanted(o));
+            if (said < 6 && h->dist())
+                fprintf(stderr, "[dns] partitioned step %d: form %d, cells by "
+                        "the tail before %d, tail with cells %d of %d (cycle "
+                        "%d)\n", said++, (int)pl.form, (int)pl.have_cells,
+                        (int)dcells_ok, (int)pl.dtail, h->pipeline_c);
         }
-        h->dist_tail = dns_saddle::DistTail{};
-        h->z_plan_override = nullptr;
-        h->dist_rnew = nullptr;
-        h->step6.on = false;
-        h->tail_extrap = dns::TailExtrap{};
-        h->step_counter = nullptr;
-        h->prologue_nparts = 0;
         pre_ok = false;
         DNS_TRY(grc);
-        if (can_pre && !six) {
+        if (pl.can_pre && !six) {
             pre_ok = true;
             pre_sig = dns::extrap_sig(next_nsol, cf->extrapolate_x0);
         }
         // row-partitioned: the next step's right-hand side, convection and
         // warm start read this rank's rows and their halo
-        if (h->dist() && part.on) {
+        if (pl.zwide)
             part.state_full = false;
-        } else if (h->dist()) {
-            DNS_TRY(h->comm->allgatherv(x, h->st_v, s));
-        }
+        else if (h->dist())
+            DNS_TRY(h->comm->allgatherv(x, h->st_v, h->stream));
     } else {
         pre_ok = false;
         dcells_ok = false;
-        DNS_TRY(prologue());
+        DNS_TRY(prologue(cf, pl));
         DNS_TRY(h->bicgstab(b.p, x, o, st));
     }
     if (tables()) tab_pos++;
@@ -549,7 +516,7 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
     b_valid = true;
     // a carry step has left K x_c of ITS current solution in the ring: after
     // the rotation kxs[prev..p4] are current again; any other step breaks it
-    carry_ok = carry;
+    carry_ok = pl.carry;
     // a six-node step has left the next warm start, the cell values of the new
     // velocity and the new residual behind
     six_ok = six;
@@ -563,11 +530,8 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
 int dns_imex::prime_six(const dns_imex_coeffs *cf, bool keep_r) {
     dns_saddle *h = sys;
     six_ok = false;
-    if (!env_six || nsol < 5 || h->dist() || h->streams(h->K) ||
-        h->streams(R1))
-        return DNS_OK;
+    if (!six_capable() || nsol < 5) return DNS_OK;
     const size_t ld = h->ld;
-    if (!h->have_jg || h->popts.schur != DNS_SCHUR_DENSE) return DNS_OK;
     if (kx6.n < ld) DNS_TRY(kx6.alloc(ld));
     for (int q = 0; q < 2; ++q) {
         if (x0buf[q].n < ld) DNS_TRY(x0buf[q].alloc(ld));
@@ -747,11 +711,10 @@ std::vector<uint64_t> dns_imex::group_key(const dns_imex_coeffs *cf,
                                           const dns_solve_opts *o,
                                           int group) const {
     const dns_saddle *h = sys;
-    return {9u, step_key(cf), (uint64_t)h->pipeline_c, (uint64_t)o->reorth,
-            (uint64_t)o->maxiter, bits_of(o->rtol), bits_of(o->atol),
-            (uint64_t)h->popts.cheb_degree, (uint64_t)h->popts.schur,
-            (uint64_t)h->fhat_explicit, (uint64_t)group, (uint64_t)o->restart,
-            (uint64_t)h->step6_lazy};
+    return {9u, step_key(cf), kw(h->pipeline_c), kw(o->reorth), kw(o->maxiter),
+            kw(o->rtol), kw(o->atol), kw(h->popts.cheb_degree),
+            kw(h->popts.schur), kw(h->fhat_explicit), kw(group),
+            kw(o->restart), kw(h->step6_lazy)};
 }
 
 // `group` pipelined steps as ONE graph (sys->pipeline_c = cycle length must be
@@ -783,7 +746,7 @@ int dns_imex::enqueue_group(const dns_imex_coeffs *cf, const dns_solve_opts *o,
         if (six_ok) pre_ok = false;   // (six-node steps leave x0 elsewhere)
         // (the tails of the replayed steps were the captured ones': they left
         // the cell values of the new velocity iff such a step would now)
-        dcells_ok = dtail_wanted(o) && x0c.p != nullptr;
+        dcells_ok = plan(cf, o, h->pipeline_c).dtail;
         if (dcells_ok) dcells_gen = conv->dbc_gen;
         // (partitioned: a replayed step leaves own rows + halo, like a
         // launched one)
@@ -801,32 +764,11 @@ int dns_imex::prepare_graphs(const dns_imex_coeffs *cf,
     dns_saddle *h = sys;
     DNS_TRY(h->ensure_solver_buffers(o));    // no allocation inside a capture
     // (the ring positions are not part of the signature: all six are captured)
-    uint64_t sig = 0x51;
-    sig = mix64(sig, (uint64_t)h->graph_generation);
-    sig = mix64(sig, bits_of(cf->a_c));
-    sig = mix64(sig, bits_of(cf->a_p));
-    sig = mix64(sig, bits_of(cf->cn_c));
-    sig = mix64(sig, bits_of(cf->cn_o));
-    sig = mix64(sig, (uint64_t)cf->extrapolate_x0);
-    sig = mix64(sig, (uint64_t)((cf->carry_residual != 0) + 2 * carry_ok +
-                                4 * six_ok + 8 * dcells_ok));
-    sig = mix64(sig, (uint64_t)(uintptr_t)conv);
-    sig = mix64(sig, bits_of(conv_scale));
-    sig = mix64(sig, (uint64_t)(tables() ? 1 + 2 * tab_v + 4 * tab_p : 0));
-    sig = mix64(sig, (uint64_t)(uintptr_t)gtab.p);
-    sig = mix64(sig, (uint64_t)(uintptr_t)gptab.p);
-    sig = mix64(sig, (uint64_t)tab_rows);
-    if (fb.on) sig = mix64(sig, fb_key());
-    if (rec) sig = mix64(sig, rec_key());
-    if (conv) {
-        sig = mix64(sig, (uint64_t)conv->dbc_rows);
-        sig = mix64(sig, (uint64_t)(uintptr_t)conv->dbc_tab.p);
-    }
-    sig = mix64(sig, bits_of(o->rtol));
-    sig = mix64(sig, bits_of(o->atol));
-    sig = mix64(sig, (uint64_t)(o->reorth + 8 * o->maxiter));
-    sig = mix64(sig, (uint64_t)o->restart);
-    sig = mix64(sig, (uint64_t)h->step6_lazy);     // (the kind of the c = 1 cycle)
+    // (step6_lazy: the kind of the c = 1 cycle)
+    uint64_t sig = mix64(config_key(cf),
+                         {kw(h->graph_generation), kw(o->rtol), kw(o->atol),
+                          kw(o->reorth), kw(o->maxiter), kw(o->restart),
+                          kw(h->step6_lazy)});
     const int m = std::max(1, std::min(o->restart, dns::kMaxRestart));
     // (hysteresis: a prediction that moves between 3 and 4 Krylov steps -- the
     // bandwidth regime -- must not capture all ~80 graphs of a run again every
@@ -839,7 +781,7 @@ int dns_imex::prepare_graphs(const dns_imex_coeffs *cf,
     else if (needed < chi_hi - 1)
         chi_hi = needed + 1;
     const int chi = chi_hi;
-    sig = mix64(sig, (uint64_t)chi);
+    sig = mix64(sig, {kw(chi)});
     if (sig == prepared_sig) return DNS_OK;
     prepare_attempted = true;
     const int big = group_for(1 << 30);
@@ -918,7 +860,7 @@ int ImexRun::enter_pipeline() {
     DNS_TRY(st->ensure_partition());
     // (cell values a step of the run before has left are kept)
     if (!(st->dcells_ok && st->conv && st->dcells_gen == st->conv->dbc_gen))
-        DNS_TRY(st->prime_dcells(&o));
+        DNS_TRY(st->prime_dcells(cf, &o));
     st->prepare_attempted = false;
     int prc = st->prepare_graphs(cf, &o);
     if (h->dist() && st->prepare_attempted) {
@@ -988,7 +930,7 @@ int ImexRun::run_batch() {
         st->set_host_state(hs0);
         if (carrying) DNS_TRY(st->prime_carry(false));
         if (st->tables()) DNS_TRY(st->sync_counter());
-        DNS_TRY(st->prime_dcells(&o));
+        DNS_TRY(st->prime_dcells(cf, &o));
         if (sixing) DNS_TRY(st->prime_six(cf, true));
         return DNS_OK;
     };

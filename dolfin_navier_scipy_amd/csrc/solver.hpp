@@ -350,6 +350,49 @@ struct GraphEntry {
     int64_t d_bytes_a2a = 0, d_bytes_ag = 0;
 };
 
+// What a time stepper hands the solver for ONE solve (dns_saddle::gmres): the
+// work in front of the first cycle and all the nodes of its cycles bake in
+// beyond b, x and the solve options.  It ends with the call.  RULE: what a
+// captured node reads from here is hashed by key(), and a cycle's graph key
+// names the hooks through key() alone.
+struct StepHooks {
+    // caller work (e.g. the IMEX right-hand side) enqueued in front of the
+    // first cycle, captured into the same graph, and what names it
+    std::function<int()> prologue;
+    uint64_t prologue_key = 0;
+    // it has left r = b - K x (six-node step: K x0 in step6.kx) and
+    // `resid_nparts` partials of ||r||^2, ||b||^2 behind
+    bool prologue_has_resid = false;
+    int resid_nparts = 0;
+    int *stepctr = nullptr;      // device step counter: the first head bumps it
+    TailExtrap tail_extrap = {}; // next step's warm start, written by the tails
+    // row-partitioned: halo plan of the preconditioned vectors when the
+    // caller's is wider than the rows of K need; residual carry-over
+    const dns_halo_plan *z_plan = nullptr;
+    double *carry_rnew = nullptr;
+    // six-node resident step: out-of-place tail with the new residual and the
+    // convection cells, K z_j kept per column in Wcols
+    struct Step6 {
+        bool on = false;
+        Tail6 t6 = {};
+        TailCells cells = {};
+        const double *kx = nullptr;   // K x0 of the step's first kernel:
+                                      // k_tau_first forms r = b - kx
+    } step6;
+    // row-partitioned stepper: the tail of a ONE-step cycle (k_arn_tail_lazy1)
+    // also evaluates the convection cells of the new velocity, in extra
+    // workgroups, from `x0copy` (the warm start as the step's front kernel has
+    // copied it) and Z_0; OUT `dist_tail_ran`: the cycle that was enqueued did
+    struct DistTail {
+        bool on = false;
+        const double *x0copy = nullptr;
+        TailCells cells = {};
+    } dist_tail;
+    mutable bool dist_tail_ran = false;
+    // (`first` cycle of the solve: prologue, counter, partials, step6, dist_tail)
+    uint64_t key(bool first) const;
+};
+
 }  // namespace dns
 
 // the opaque handle of the C-ABI
@@ -467,13 +510,12 @@ struct dns_saddle {
                               std::vector<double> &dv);
     int skew_bound_rows(const dns::HostCsr &Fx, double *eta);
     int enqueue_cycle_dist(const double *b, double *x, int c,
-                           const dns_solve_opts *o, int first,
-                           bool have_resid = false);
+                           const dns_solve_opts *o, int first, bool have_resid,
+                           const dns::StepHooks &hk);
     dns::RowMap dist_rowmap() const;
     dns::HostCsr tmp_Gch, tmp_JGh;    // handed from build_explicit to setup_dist
     // row-partitioned cycle: exchange the start vector's halo (not needed, see
-    // enqueue_cycle_dist); halo plan for the preconditioned vectors when the
-    // caller's is wider than the rows of K need
+    // enqueue_cycle_dist)
     bool dist_x0_exchange = false;
     // one-step cycles without the all-reduce of the residual norm
     // (k_arn_tail_lazy1); the constants 1, 0 the head reads as "norms"
@@ -490,8 +532,6 @@ struct dns_saddle {
     }
     int cycle_first = 0;              // > 0: length of a solve's first cycle
     dns::DevBuf<double> lazy_one;
-    const struct dns_halo_plan *z_plan_override = nullptr;
-    double *dist_rnew = nullptr;      // residual carry-over of the stepper
     bool tmp_presliced = false;       // ... already this rank's rows only
     bool part_setup = true;           // DNS_PART_SETUP: partitioned set-up
     std::vector<int> st_v, st_p;      // block partitions of the velocity /
@@ -518,41 +558,13 @@ struct dns_saddle {
     bool graph_capable() const {
         return !dist() || (comm->nccl != nullptr && dist_graph_ok);
     }
-    int *step_counter = nullptr;      // device step counter of the attached
-                                      // stepper (tables of per-step data);
-                                      // bumped by the first head kernel of
-                                      // a solve
     // pair format of K (pair.hpp): the K applies of the bandwidth regime run
     // on it when the velocity block has the two-component structure
     dns::PairDev Kp;
     bool pair_knob = true;            // DNS_PAIR (read once, at create)
     int build_pair();
-    // six-node resident step (set by dns_imex around a solve): out-of-place
-    // tail with the new residual and the convection cells, K z_j kept per
-    // column in Wcols
-    struct Step6 {
-        bool on = false;
-        dns::Tail6 t6 = {};
-        dns::TailCells cells = {};
-        const double *kx = nullptr;   // K x0 of the step's first kernel: the
-                                      // residual r = b - kx is formed by the
-                                      // first tau kernel (k_tau_first)
-    } step6;
-    // row-partitioned time stepper (set by dns_imex around a solve): the tail
-    // of a ONE-step cycle (k_arn_tail_lazy1) also evaluates the convection
-    // cells of the new velocity, in extra workgroups, from `x0copy` (the warm
-    // start as the step's front kernel has copied it) and Z_0; `ran` says
-    // whether the cycle that was enqueued did
-    struct DistTail {
-        bool on = false, ran = false;
-        const double *x0copy = nullptr;
-        dns::TailCells cells = {};
-    } dist_tail;
+    // K z_j per column of a six-node step (dns::StepHooks::Step6)
     dns::DevBuf<double> Wcols;
-    dns::TailExtrap tail_extrap = {}; // warm start of the next step, written
-                                      // by the tail kernels (set by dns_imex)
-    int prologue_nparts = 0;          // > 0: partials of ||r||^2, ||b||^2 the
-                                      // caller's prologue kernel has written
     bool mg_fused = false;            // the V-cycle runs on the fused operators
     // V(1,1) on TWO fused operators per level (one GPU): down b_c = Rd b with
     // Rd = P^T (I - w S D^-1), up x = U [b; e] with U = [(I + T) w D^-1, T P]
@@ -735,10 +747,10 @@ struct dns_saddle {
     bool want_history = true;         // copy the residual history back
     size_t hist_cap = 0;
     std::vector<dns::GraphEntry> graphs;
-    typedef int (*enqueue_fn)(void *ctx);
     // enqueue one GMRES cycle of `c` iterations (capturable: no sync inside)
     int enqueue_cycle(const double *b, double *x, int c,
-                      const dns_solve_opts *o, int first, bool have_resid);
+                      const dns_solve_opts *o, int first, bool have_resid,
+                      const dns::StepHooks &hk);
     // run `body` eagerly or as a cached graph identified by `key`
     // launch == false: capture + instantiate only (set-up time), nothing runs
     template <typename Body>
@@ -774,12 +786,9 @@ struct dns_saddle {
     int read_header();
     int solve_device(const double *b, double *x, const dns_solve_opts *o,
                      dns_solve_stats *st);
-    // `prologue` enqueues caller work (e.g. the IMEX right-hand side) in front
-    // of the first cycle so that it is captured into the same graph
+    // `hooks`: what a time stepper adds to this one solve (dns::StepHooks)
     int gmres(const double *b, double *x, const dns_solve_opts *o,
-              dns_solve_stats *st,
-              const std::function<int()> &prologue = nullptr,
-              uint64_t prologue_key = 0, bool prologue_has_resid = false);
+              dns_solve_stats *st, const dns::StepHooks *hooks = nullptr);
     int bicgstab(const double *b, double *x, const dns_solve_opts *o,
                  dns_solve_stats *st);
     int true_residual(const double *b, const double *x, double *out);

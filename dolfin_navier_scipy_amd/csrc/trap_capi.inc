@@ -661,9 +661,9 @@ int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
         // the warm start stays a kernel of its own there
         const int nn = std::min(t->nsol + 1, 5);
         double e[5];
-        h->tail_extrap = dns::TailExtrap{};
+        dns::StepHooks hk;
         if (!h->dist() && !fb && dns::extrap_coeffs(nn, ex, e) >= 1)
-            h->tail_extrap = dns::TailExtrap{
+            hk.tail_extrap = dns::TailExtrap{
                 t->xs[t->cur].p, t->xs[t->prev].p, t->xs[t->pprev].p,
                 t->xs[t->p3].p,  e[0], e[1], e[2], e[3], e[4], t->xs[t->p4].p};
         // pipelined sweep: one cycle of the agreed length, nobody waits; the
@@ -672,22 +672,20 @@ int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
         if (async && !h->dist() && !t->env_graph) o.use_graph = 0;
         // (partitioned assembly: the preconditioned vectors travel over the
         // stepper's halo, the new iterate is valid wherever this rank reads)
-        h->z_plan_override = pon ? &t->part.planX : nullptr;
+        hk.z_plan = pon ? &t->part.planX : nullptr;
         if (fuse_r) {
-            h->prologue_nparts = gb_rows;
-            rc = h->gmres(t->b.p, x, &o, st, []() -> int { return DNS_OK; },
-                          0x7f05u, true);
-        } else {
-            rc = h->gmres(t->b.p, x, &o, st);
+            // (the assembly launch has left r and the partials of both norms)
+            hk.prologue_key = 0x7f05u;
+            hk.prologue_has_resid = true;
+            hk.resid_nparts = gb_rows;
         }
-        h->z_plan_override = nullptr;
+        rc = h->gmres(t->b.p, x, &o, st, &hk);
         h->pipeline_c = 0;
-        if (h->tail_extrap.out && rc == DNS_OK) {
+        if (hk.tail_extrap.out && rc == DNS_OK) {
             t->pre_ok = true;
             t->pre_sig = dns::extrap_sig(nn, extrapolate_x0);
             t->pre_dt = dt;
         }
-        h->tail_extrap = dns::TailExtrap{};
     } else {
         rc = h->bicgstab(t->b.p, x, &o, st);
     }
