@@ -109,6 +109,8 @@ static int dns_conv_create_p2_impl(int device, int32_t ncells, const int32_t *ce
     cv->device = device;
     if (const char *e = getenv("DNS_CONV_LANE_MIN")) cv->lane_min = atoi(e);
     cv->cmap_host = cmap;
+    cv->cpos_host.resize((size_t)ncells);
+    for (int c = 0; c < ncells; ++c) cv->cpos_host[order[c]] = c;
     cv->gptr_host = cnt;
     cv->gidx_host = gidx;
     cv->ncells = ncells;

@@ -120,13 +120,29 @@ conv_cells_compute(const double (&ul)[6][2], int ncells, int cc, int c, int q,
     }
 }
 
-template <typename VAL>
+// where the twelve local sums of a cell go: lane q of the cell's eight holds
+// the sums of slots q (`mine`) and, q < 4, q + 8 (`mine8`).  k_conv_cells and
+// the tail kernels store them cell-contiguously; k_functional_step
+// (functional.hpp) weights them instead.
+struct ConvStoreCells {
+    double *__restrict__ cellvals;                          // [12][ncells]
+    int ncells;
+    __device__ __forceinline__ void operator()(bool live, int slot, int c,
+                                               int q, double mine,
+                                               double mine8) const {
+        if (live) {
+            cellvals[(size_t)q * ncells + c] = mine;
+            if (q < 4) cellvals[(size_t)(q + 8) * ncells + c] = mine8;
+        }
+    }
+};
+
+template <typename VAL, typename SINK>
 __device__ __forceinline__ void
-conv_cells_block(int bid, int ncells, const int *__restrict__ cellmap,   // [12][ncells]
+conv_cells_block_to(int bid, int ncells, const int *__restrict__ cellmap,   // [12][ncells]
              const double *__restrict__ glam,               // [6][ncells]
              const double *__restrict__ area,
-             const VAL vsrc, TabRef dbctab,
-             double *__restrict__ cellvals,                 // [12][ncells]
+             const VAL vsrc, TabRef dbctab, const SINK sink,
              const int *__restrict__ sel = nullptr, int nsel = 0) {
 #pragma clang fp contract(off)
     // sel: only the cells sel[0..nsel) (row-partitioned time steppers: the
@@ -180,10 +196,19 @@ conv_cells_block(int bid, int ncells, const int *__restrict__ cellmap,   // [12]
             if (q == sl - 8) mine8 = v;
         }
     }
-    if (live) {
-        cellvals[(size_t)q * ncells + c] = mine;
-        if (q < 4) cellvals[(size_t)(q + 8) * ncells + c] = mine8;
-    }
+    sink(live, slot, c, q, mine, mine8);
+}
+
+template <typename VAL>
+__device__ __forceinline__ void
+conv_cells_block(int bid, int ncells, const int *__restrict__ cellmap,   // [12][ncells]
+             const double *__restrict__ glam,               // [6][ncells]
+             const double *__restrict__ area,
+             const VAL vsrc, TabRef dbctab,
+             double *__restrict__ cellvals,                 // [12][ncells]
+             const int *__restrict__ sel = nullptr, int nsel = 0) {
+    conv_cells_block_to(bid, ncells, cellmap, glam, area, vsrc, dbctab,
+                        ConvStoreCells{cellvals, ncells}, sel, nsel);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -381,6 +406,8 @@ struct dns_conv {
                            const double *x0 = nullptr,
                            const dns::UpdJob *upd = nullptr);
     std::vector<int> cmap_host;            // [12][ncells], as on the device
+    std::vector<int> cpos_host;            // the caller's cell -> internal cell
+                                           // (cell lists of the functionals)
     std::vector<int> gptr_host, gidx_host; // the inverted index, as on the device
     struct dns_conv_mat *mat = nullptr;    // bound matrix pattern (optional)
     ~dns_conv();

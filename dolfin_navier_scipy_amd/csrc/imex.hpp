@@ -3,6 +3,7 @@
 #include "batch_policy.hpp"
 #include "convection.hpp"
 #include "feedback.hpp"
+#include "functional.hpp"
 #include "record.hpp"
 #include "ring.hpp"
 #include "solver.hpp"
@@ -155,15 +156,40 @@ struct dns_imex : dns::Ring {
     std::unique_ptr<Recorder> rec;
     int rec_launch(hipStream_t s); // k_record_step for the state as it stands
     uint64_t rec_key() const;
+    // force functionals (functional.hpp): k_functional_step runs in front of
+    // every step (behind k_lti_step and k_record_step) and once behind the
+    // last step of a call; it writes row `counter - 1` of the log, so a
+    // restored batch overwrites its own rows and the log needs no checkpoint.
+    // Present = on.
+    struct Functionals {
+        int nF = 0, G = 1, rows = 0;
+        int ncl = 0;               // listed cells (all functionals)
+        double dt = 1.0;
+        dns::DevBuf<int> rp, ci;   // the 3 nF sparse rows (k, term)
+        dns::DevBuf<double> va;
+        dns::DevBuf<int> cptr, cidx;
+        dns::DevBuf<double> cw, scale, c0;
+        dns::DevBuf<double> log;   // rows x G x nF
+        // the convection operator whose cell order `cidx` refers to (a step
+        // with another one attached is refused)
+        const dns_conv *conv = nullptr;
+        int ncells = 0;
+        const int *cellmap = nullptr;
+    };
+    std::unique_ptr<Functionals> fn;
+    int fn_launch(hipStream_t s);  // k_functional_step for the state as it stands
+    uint64_t fn_key() const;
     // a step counter is needed as soon as anything is tabulated
     bool tables() const {
-        return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on || rec;
+        return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on || rec ||
+               fn;
     }
     int rows_left() const {
         int lim = 1 << 30;
         if (tab_rows > 0) lim = std::min(lim, tab_rows);
         if (fb.on) lim = std::min(lim, fb.rows);
         if (rec) lim = std::min(lim, rec->rows);
+        if (fn) lim = std::min(lim, fn->rows);
         if (conv && conv->dbc_rows > 0) lim = std::min(lim, conv->dbc_rows);
         return lim - tab_pos;
     }

@@ -15,6 +15,7 @@ uint64_t dns_imex::config_key(const dns_imex_coeffs *cf) const {
     if (conv) k = mix64(k, {kw(conv->dbc_rows), kw(conv->dbc_tab.p)});
     if (fb.on) k = mix64(k, {fb_key()});
     if (rec) k = mix64(k, {rec_key()});
+    if (fn) k = mix64(k, {fn_key()});
     return k;
 }
 
@@ -56,6 +57,38 @@ int dns_imex::rec_launch(hipStream_t s) {
     hipLaunchKernelGGL(dns::k_record_step,
                        dns::record_grid((int)sys->ld, snaps, r.Ny),
                        dns::kBlock, 0, s, a);
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+// "functionals on", their shape, every buffer k_functional_step is handed
+// (the ring vectors come with the step key) and the pressure scale
+uint64_t dns_imex::fn_key() const {
+    const Functionals &f = *fn;
+    return mix64(mix64(0xf6, {kw(f.nF), kw(f.G), kw(f.rows), kw(f.ncl),
+                              kw(f.dt), kw(last_pscale), kw(f.rp.p),
+                              kw(f.ci.p), kw(f.va.p), kw(f.cptr.p)}),
+                 {kw(f.cidx.p), kw(f.cw.p), kw(f.scale.p), kw(f.c0.p),
+                  kw(f.log.p), kw(stepctr.p), kw(conv ? conv->ncells : 0),
+                  kw(conv ? conv->cellmap.p : nullptr),
+                  kw(conv ? conv->glam.p : nullptr),
+                  kw(conv ? conv->area.p : nullptr),
+                  kw(conv ? conv->dbcvals.p : nullptr)});
+}
+
+int dns_imex::fn_launch(hipStream_t s) {
+    const Functionals &f = *fn;
+    const bool cells = f.ncl > 0;
+    const dns::FnArgs a{stepctr.p, f.rows, xs[cur].p, xs[prev].p, sys->nv,
+                        last_pscale, f.dt, f.nF, f.G, f.rp.p, f.ci.p, f.va.p,
+                        f.ncl, f.cptr.p, f.cidx.p, f.cw.p,
+                        cells ? conv->ncells : 0,
+                        cells ? conv->cellmap.p : (const int *)nullptr,
+                        cells ? conv->glam.p : (const double *)nullptr,
+                        cells ? conv->area.p : (const double *)nullptr,
+                        cells ? conv->dbcvals.p : (const double *)nullptr,
+                        f.scale.p, f.c0.p, f.log.p};
+    hipLaunchKernelGGL(dns::k_functional_step, f.G, dns::kBlock, 0, s, a);
     DNS_HIP(hipGetLastError());
     return DNS_OK;
 }
@@ -366,10 +399,12 @@ int dns_imex::front_stream(const dns_imex_coeffs *cf, const StepPlan &pl) {
 // Right-hand side and warm start, enqueued in front of the first Krylov cycle
 // so that a whole time step is ONE captured graph
 int dns_imex::prologue(const dns_imex_coeffs *cf, const StepPlan &pl) {
-    // observer feedback, then the recorder: the first nodes of the step,
-    // whatever its form (xs[cur] is complete: the state after the step before)
+    // observer feedback, the recorder, the functionals: the first nodes of
+    // the step, whatever its form (xs[cur] is complete: the state after the
+    // step before)
     if (fb.on) DNS_TRY(fb_launch(sys->stream));
     if (rec) DNS_TRY(rec_launch(sys->stream));
+    if (fn) DNS_TRY(fn_launch(sys->stream));
     switch (pl.form) {
         case StepPlan::Six: return front_six(cf, pl);
         case StepPlan::Fused: return front_fused(cf, pl);
@@ -452,6 +487,29 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "recorder on a partitioned system: the outputs y = C v "
                          "would need an all-reduce, the snapshots a gather");
+    if (fn) {
+        if (h->dist() || part.on)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals on a partitioned system: the sums "
+                             "would need an all-reduce");
+        if (fn->ncl > 0 && !conv)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals with cells need the device "
+                             "convection operator they were set with "
+                             "(dns_imex_set_convection)");
+        // (the listed cells are positions in that operator's cell order)
+        if (fn->ncl > 0 && (conv != fn->conv || conv->ncells != fn->ncells ||
+                            conv->cellmap.p != fn->cellmap))
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals with cells were set with another "
+                             "convection operator than the one attached now: "
+                             "set them again (dns_imex_set_functionals)");
+        if (conv && conv->dbc_rows > 0)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals with a per-step Dirichlet table on "
+                             "the convection operator: the moving-boundary "
+                             "terms are not part of the functional");
+    }
     if (tables()) {
         if (o->method != DNS_METHOD_GMRES)
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
@@ -462,7 +520,8 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
                              "upload the next ones (dns_imex_set_rhs_table / "
                              "dns_conv_set_dbc_table / "
                              "dns_imex_set_feedback_table / "
-                             "dns_imex_set_recorder)", tab_pos);
+                             "dns_imex_set_recorder / "
+                             "dns_imex_set_functionals)", tab_pos);
     }
     if (conv) conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
     const int next_nsol = std::min(nsol + 1, 5);
@@ -966,6 +1025,7 @@ int ImexRun::run_batch() {
         if (fin_batch) {
             // (the recorder's last row: nobody runs a prologue behind it)
             if (st->rec) DNS_TRY(st->rec_launch(h->stream));
+            if (st->fn) DNS_TRY(st->fn_launch(h->stream));
             DNS_HIP(hipEventRecord(st->e1, h->stream));
             DNS_LPR_SWITCH(
                 h->K.lpr,
@@ -1035,6 +1095,7 @@ int ImexRun::finish_run(double *device_seconds, int64_t *total_iters) {
         h->spmv_count++;
     } else {
         if (st->rec && nsteps > 0) DNS_TRY(st->rec_launch(h->stream));
+        if (st->fn && nsteps > 0) DNS_TRY(st->fn_launch(h->stream));
         DNS_HIP(hipEventRecord(st->e1, h->stream));
         // true residual of the last step for the record: behind the closing
         // event (not part of the stepping time), ONE synchronisation for both
@@ -1286,7 +1347,8 @@ static int dns_imex_step_impl(dns_imex *st, const double *nfc_new,
     if (st->tables() && st->rows_left() < 1)
         return dns::fail(DNS_ERR_NOT_READY,
                          "the per-step tables are used up after %d steps: "
-                         "upload the next ones", st->tab_pos);
+                         "upload the next ones (dns_imex_set_rhs_table / ... / "
+                         "dns_imex_set_functionals)", st->tab_pos);
     if (nfc_new) {
         std::swap(st->nc, st->no);
         DNS_TRY(st->nfc[st->nc].upload(nfc_new, (size_t)h->nv, h->stream));
@@ -1300,6 +1362,7 @@ static int dns_imex_step_impl(dns_imex *st, const double *nfc_new,
     h->want_history = true;
     if (src != DNS_OK) return src;
     if (st->rec) DNS_TRY(st->rec_launch(h->stream));    // the row of this step
+    if (st->fn) DNS_TRY(st->fn_launch(h->stream));
     DNS_HIP(hipStreamSynchronize(h->stream));
     return DNS_OK;
 }
@@ -1327,7 +1390,9 @@ static int dns_imex_run_impl(dns_imex *st, int32_t nsteps, const dns_imex_coeffs
     memset(r.sp, 0, sizeof(*r.sp));
     if (st->tables() && st->rows_left() < nsteps)
         return dns::fail(DNS_ERR_NOT_READY,
-                         "%d steps asked for, the per-step tables hold %d more",
+                         "%d steps asked for, the per-step tables hold %d more "
+                         "(dns_imex_set_rhs_table / ... / "
+                         "dns_imex_set_functionals)",
                          (int)nsteps, st->rows_left());
     // the run's settings of the system, undone on every exit (the status of
     // the oversolve reset is ignored: the first error is the one reported)
@@ -1805,6 +1870,206 @@ static int dns_imex_clear_recorder_impl(dns_imex *st) {
 
 int dns_imex_clear_recorder(dns_imex *st) {
     return dns::guarded([&]() -> int { return dns_imex_clear_recorder_impl(st); });
+}
+
+// ---- force functionals (functional.hpp) ------------------------------------
+
+static int dns_imex_set_functionals_impl(
+    dns_imex *st, int32_t nF, const dns_csr *ca, const dns_csr *cm,
+    const dns_csr *cp, const double *c0, const double *scale,
+    const int32_t *cell_ptr, const int32_t *cell_idx, const double *cell_w,
+    double dt, int32_t nrows) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_saddle *h = st->sys;
+    if (st->r1_rows || st->part.on || h->dist())
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals on a row-partitioned stepper: the sums "
+                         "would need an all-reduce");
+    if (nF < 1 || nF > dns::kFnMax)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals: nF = %d outside 1..%d", (int)nF,
+                         dns::kFnMax);
+    if (nrows < 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "functionals: nrows = %d < 1",
+                         (int)nrows);
+    if (!(dt > 0.0))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "functionals: dt must be "
+                         "positive");
+    const dns_csr *terms[3] = {ca, cm, cp};
+    const char *names[3] = {"ca", "cm", "cp"};
+    for (int t = 0; t < 3; ++t) {
+        if (!terms[t]) continue;
+        DNS_TRY(dns::check_csr(terms[t], names[t]));
+        const int want = t == 2 ? h->np : h->nv;
+        if (terms[t]->nrows != nF || terms[t]->ncols != want)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals: %s must be nF x %d, it is %d x %d",
+                             names[t], want, (int)terms[t]->nrows,
+                             (int)terms[t]->ncols);
+    }
+    const int ncl = cell_ptr ? cell_ptr[nF] : 0;
+    if (cell_ptr) {
+        if (cell_ptr[0] != 0)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals: cell_ptr[0] must be 0");
+        for (int k = 0; k < nF; ++k)
+            if (cell_ptr[k + 1] < cell_ptr[k])
+                return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                                 "functionals: cell_ptr not monotone");
+    }
+    if (ncl > 0) {
+        if (!cell_idx || !cell_w)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals: cells without cell_idx / cell_w");
+        if (!st->conv)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals with cells need a device convection "
+                             "operator (dns_imex_set_convection)");
+        for (int j = 0; j < ncl; ++j)
+            if (cell_idx[j] < 0 || cell_idx[j] >= st->conv->ncells)
+                return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                                 "functionals: cell index %d at %d outside "
+                                 "0..%d (ncells of the convection operator)",
+                                 (int)cell_idx[j], j, st->conv->ncells - 1);
+    }
+    if (st->conv && st->conv->dbc_rows > 0)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals with a per-step Dirichlet table on the "
+                         "convection operator (dns_conv_set_dbc_table): the "
+                         "moving-boundary terms are not part of the "
+                         "functional");
+    // the 3 nF sparse rows (k, term) in one CSR; a null term is an empty row
+    std::vector<int> rp(3 * (size_t)nF + 1, 0), ci;
+    std::vector<double> va;
+    for (int k = 0; k < nF; ++k)
+        for (int t = 0; t < 3; ++t) {
+            if (terms[t])
+                for (int64_t z = terms[t]->rowptr[k];
+                     z < terms[t]->rowptr[k + 1]; ++z) {
+                    ci.push_back(terms[t]->colidx[z]);
+                    va.push_back(terms[t]->vals[z]);
+                }
+            rp[3 * (size_t)k + t + 1] = (int)ci.size();
+        }
+    std::vector<int> cptr(nF + 1, 0);
+    if (cell_ptr) cptr.assign(cell_ptr, cell_ptr + nF + 1);
+    std::vector<double> sc(nF, 1.0), cc(nF, 0.0);
+    if (scale) sc.assign(scale, scale + nF);
+    if (c0) cc.assign(c0, c0 + nF);
+    DNS_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
+    // Buffers that are large enough are kept, so that the slices of a time
+    // loop, which set the functionals again and again, replay the graphs that
+    // were captured for these buffers.  (Everything was checked above; a
+    // failed allocation leaves the stepper without functionals.)
+    std::unique_ptr<dns_imex::Functionals> f = std::move(st->fn);
+    if (!f) f.reset(new (std::nothrow) dns_imex::Functionals());
+    if (!f) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    const int G = dns::functional_grid(nF, ncl);
+    auto put = [&](auto &buf, const auto &host) -> int {
+        if (buf.p == nullptr || buf.n < host.size())
+            DNS_TRY(buf.alloc(host.size()));
+        if (!host.empty()) DNS_TRY(buf.upload(host.data(), host.size(), s));
+        return DNS_OK;
+    };
+    DNS_TRY(put(f->rp, rp));
+    DNS_TRY(put(f->ci, ci));
+    DNS_TRY(put(f->va, va));
+    DNS_TRY(put(f->cptr, cptr));
+    DNS_TRY(put(f->scale, sc));
+    DNS_TRY(put(f->c0, cc));
+    if (f->cidx.p == nullptr || f->cidx.n < (size_t)ncl)
+        DNS_TRY(f->cidx.alloc((size_t)ncl));
+    if (f->cw.p == nullptr || f->cw.n < (size_t)12 * ncl)
+        DNS_TRY(f->cw.alloc((size_t)12 * ncl));
+    if (ncl > 0) {
+        // (the operator keeps its cells in an order of its own)
+        std::vector<int> cint((size_t)ncl);
+        for (int j = 0; j < ncl; ++j)
+            cint[j] = st->conv->cpos_host[cell_idx[j]];
+        DNS_TRY(f->cidx.upload(cint.data(), (size_t)ncl, s));
+        DNS_TRY(f->cw.upload(cell_w, (size_t)12 * ncl, s));
+    }
+    const size_t need = (size_t)nrows * G * nF;
+    if (f->log.p == nullptr || f->log.n < need) DNS_TRY(f->log.alloc(need));
+    DNS_TRY(f->log.zero(s));
+    f->nF = nF;
+    f->G = G;
+    f->rows = nrows;
+    f->ncl = ncl;
+    f->dt = dt;
+    f->conv = ncl > 0 ? st->conv : nullptr;
+    f->ncells = ncl > 0 ? st->conv->ncells : 0;
+    f->cellmap = ncl > 0 ? st->conv->cellmap.p : nullptr;
+    st->fn = std::move(f);
+    // rows are selected by the step counter: back to 0, as after
+    // dns_imex_set_rhs_table
+    DNS_TRY(st->fb_rebase());
+    st->tab_pos = 0;
+    st->six_ok = false;
+    st->dcells_ok = false;
+    DNS_TRY(st->sync_counter());
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+}
+
+int dns_imex_set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
+                             const dns_csr *cm, const dns_csr *cp,
+                             const double *c0, const double *scale,
+                             const int32_t *cell_ptr, const int32_t *cell_idx,
+                             const double *cell_w, double dt, int32_t nrows) {
+    return dns::guarded([&]() -> int { return dns_imex_set_functionals_impl(st, nF, ca, cm, cp, c0, scale, cell_ptr, cell_idx, cell_w, dt, nrows); });
+}
+
+static int dns_imex_get_functionals_impl(dns_imex *st, int32_t first,
+                                         int32_t count, double *out) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (!st->fn)
+        return dns::fail(DNS_ERR_NOT_READY, "no functionals are set "
+                         "(dns_imex_set_functionals)");
+    const dns_imex::Functionals &f = *st->fn;
+    if (!out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (first < 0 || count < 0 || first + count > f.rows)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functional rows [%d, %d) asked for, the log holds "
+                         "%d", (int)first, (int)(first + count), f.rows);
+    DNS_HIP(hipSetDevice(st->sys->device));
+    hipStream_t s = st->sys->stream;
+    const size_t per = (size_t)f.G * f.nF;
+    std::vector<double> part((size_t)count * per);
+    if (count)
+        DNS_TRY(dns::download_from(part.data(), f.log.p + (size_t)first * per,
+                                   part.size(), s));
+    DNS_HIP(hipStreamSynchronize(s));
+    // the workgroups' shares, in index order
+    for (int r = 0; r < count; ++r)
+        for (int k = 0; k < f.nF; ++k) {
+            double y = 0.0;
+            for (int g = 0; g < f.G; ++g)
+                y += part[(size_t)r * per + (size_t)g * f.nF + k];
+            out[(size_t)r * f.nF + k] = y;
+        }
+    return DNS_OK;
+}
+
+int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,
+                             double *out) {
+    return dns::guarded([&]() -> int { return dns_imex_get_functionals_impl(st, first, count, out); });
+}
+
+static int dns_imex_clear_functionals_impl(dns_imex *st) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (!st->fn) return DNS_OK;
+    DNS_HIP(hipSetDevice(st->sys->device));
+    DNS_HIP(hipStreamSynchronize(st->sys->stream));
+    st->fn.reset();
+    // (the counter goes on counting for the other tables, if any)
+    return DNS_OK;
+}
+
+int dns_imex_clear_functionals(dns_imex *st) {
+    return dns::guarded([&]() -> int { return dns_imex_clear_functionals_impl(st); });
 }
 
 static int dns_imex_get_state_impl(dns_imex *st, double *v, double *p) {

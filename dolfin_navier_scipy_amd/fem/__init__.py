@@ -6,3 +6,5 @@ from .problem_setups import (get_sysmats, condense_sysmatsbybcs,
                              cylinder_mesh, cylinder_mesh_hierarchy,
                              pressure_prolongations, DATA_DIR,
                              gen_bccont_fems, classify_boundary)
+from .functionals import (MomentumFunctionals, boundary_forces,
+                          pressure_difference, cylinder_nodes)

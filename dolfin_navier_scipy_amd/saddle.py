@@ -605,6 +605,67 @@ class ImexStepper(object):
             C.dptr(p.reshape(-1))))
         return v, p
 
+    # ---- force functionals (`dns_imex_set_functionals`) ---------------------
+    def set_functionals(self, fn, nrows, dt):
+        """the next `nrows` steps (`step` and `run` alike) evaluate the
+        momentum-balance functionals `fn` (`fem.MomentumFunctionals`: drag,
+        lift, pressure differences, ...; at most 16) of the state they leave,
+        on the device, into a log of `nrows` rows; `dt`: the time step of the
+        backward difference `(v - v_prev)/dt`.  Row `s` is `fn.evaluate` of
+        what `get_state` would have returned after the `(s+1)`-th step from
+        now and the state before it.  Resets the step counter like
+        `set_rhs_table` (call it after that one, and collect with
+        `get_functionals` before the next tables).  Functionals with cells
+        need the convection operator attached (`set_convection`) with
+        constant Dirichlet values; their cells refer to that operator, so
+        after attaching another one they are set again."""
+        nrows = int(nrows)
+        if nrows < 1:
+            raise ValueError('`nrows` must be positive')
+        args = fn.device_args()
+        nF = int(args['scale'].size)
+        views = []
+        for name, ncol in (('ca', self.sys.NV), ('cm', self.sys.NV),
+                           ('cp', self.sys.NP)):
+            mat = args[name]
+            if mat.nnz == 0 and mat.shape[1] != ncol:
+                views.append(None)           # (pressure-only functionals)
+                continue
+            if mat.shape != (nF, ncol):
+                raise ValueError('{0} must be {1} x {2}, it is {3}'.format(
+                    name, nF, ncol, mat.shape))
+            views.append(C.CsrView(mat))
+        cptr = np.ascontiguousarray(args['cell_ptr'], dtype=np.int32)
+        cidx = np.ascontiguousarray(args['cell_idx'], dtype=np.int32)
+        cw = C.as_f64(args['cell_w']) if args['cell_w'].size else np.zeros(1)
+        if cidx.size == 0:
+            cidx = np.zeros(1, dtype=np.int32)
+        c0, scale = C.as_f64(args['c0'], nF), C.as_f64(args['scale'], nF)
+        C.check(self.lib.dns_imex_set_functionals(
+            self._h, nF, *[None if v is None else v.byref() for v in views],
+            C.dptr(c0), C.dptr(scale),
+            cptr.ctypes.data_as(C.c_int32_p), cidx.ctypes.data_as(C.c_int32_p),
+            C.dptr(cw), float(dt), nrows))
+        self._fn_shape = (nrows, nF)
+
+    def clear_functionals(self):
+        C.check(self.lib.dns_imex_clear_functionals(self._h))
+        self._fn_shape = None
+
+    def get_functionals(self, first=0, count=None):
+        """rows `first .. first + count` of the functionals' log (default: of
+        all steps taken since `set_functionals`), `(count, nF)`"""
+        shape = getattr(self, '_fn_shape', None)
+        if shape is None:
+            raise ValueError('no functionals are set (`set_functionals`)')
+        if count is None:
+            count = self.table_position()[0] - first
+        out = np.empty((int(count), shape[1]))
+        C.check(self.lib.dns_imex_get_functionals(
+            self._h, int(first), int(count),
+            C.dptr(out.reshape(-1) if out.size else np.zeros(1))))
+        return out
+
     def get_state(self):
         v = np.empty(self.sys.NV)
         p = np.empty(self.sys.NP)

@@ -356,7 +356,8 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
               dyn_fb_dict=None, dyn_fb_disc='trapezoidal',
               vp_output=False, vp_out_fun=None, vp_output_dict=None,
               solver=None, device=0, bcs_time_only=False,
-              applybcs_literal=True, record_on_device=False, **kw):
+              applybcs_literal=True, record_on_device=False,
+              functionals=None, **kw):
     """time-dependent Navier-Stokes on the device (reference snu:548-1600)
 
     Keyword names and meaning follow the reference.  `V`: object with the P2
@@ -397,8 +398,17 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     on the inner dofs, the device records `y = cv_mat v` of every step and
     keeps no snapshot but the slices' last.  Where the loop does not run
     resident it takes the usual path; `time_int_utils.LAST_RUN['record']`
-    says `'device'` or `'host'`.
+    says `'device'` or `'host'`.  `functionals` (explicit schemes, static
+    boundaries): a `fem.MomentumFunctionals` of the condensed problem (drag,
+    lift, pressure differences, ...) -- handed down to the loop
+    (`resident=dict(functionals=...)`), which evaluates it after every AB2 /
+    BDF2 step, on the device where it runs resident;
+    `time_int_utils.LAST_RUN['functionals']`, `['functionals_t']`,
+    `['functionals_on']` hold the rows, their times and where they came from.
     """
+    if functionals is not None and not (treat_nonl_explicit
+                                        and lin_vel_point is None):
+        raise NotImplementedError('`functionals`: explicit schemes only')
     if dynamic_feedback and dyn_fb_disc == 'linear_implicit':
         raise NotImplementedError("`dyn_fb_disc='linear_implicit'` (the "
                                   'extended system of '
@@ -589,6 +599,8 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
                 # (a loop that does not run resident after all calls `savevp`
                 # at every step whatever `savevp_times` says)
                 icd['resident'].update(outputs=cv_mat, savevp_times=())
+        if functionals is not None:
+            icd.setdefault('resident', {}).update(functionals=functionals)
         v_end, p_end, ffflag = timintsc(trange=trange, inip=inip, scalep=-1.,
                                         g_tdp=rhsp, bcs_ini=inicdbcvals,
                                         check_ff_maxv=check_ff_maxv, **icd)

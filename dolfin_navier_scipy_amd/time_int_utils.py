@@ -49,11 +49,12 @@ LAST_RUN = {}
 
 
 def _record_run(name, system, stepper, feedback=None, fb_logs=None,
-                rec=None):
+                rec=None, flog=None):
     """`feedback`: 'resident' (observer on the device), 'host' (a
     `dynamic_rhs` called every step) or None (open loop); `fb_logs`: the
     `(y, u)` rows of the AB2 steps where the loop knows them; `rec`: the
-    `_DeviceRecord` of a loop whose trajectory the device wrote down"""
+    `_DeviceRecord` of a loop whose trajectory the device wrote down; `flog`:
+    the `_FunctionalLog` of a loop with `resident=dict(functionals=...)`"""
     LAST_RUN.clear()
     try:        # (runs in a `finally`: never in the way of the real error)
         ylog, ulog = fb_logs if fb_logs is not None else (None, None)
@@ -61,6 +62,11 @@ def _record_run(name, system, stepper, feedback=None, fb_logs=None,
         LAST_RUN.update(record='device' if rec is not None else 'host',
                         run_calls=getattr(stepper, 'run_calls', 0),
                         record_y=rec_y, record_t=rec_t)
+        if flog is not None:
+            fy, ft = flog.result()
+            LAST_RUN.update(functionals=fy, functionals_t=ft,
+                            functionals_on=flog.where,
+                            functionals_names=flog.names)
         LAST_RUN.update(
             integrator=name, time_steps=stepper.total_steps,
             krylov_steps=stepper.total_iters,
@@ -295,6 +301,51 @@ class _DeviceRecord(object):
         return y, np.array(self.ts, dtype=np.float64)
 
 
+class _FunctionalLog(object):
+    """`resident=dict(functionals=fn)` of `cnab` / `sbdftwo`: arms the
+    stepper's functionals per slice (or chunk) next to the tables, collects
+    the rows of the device's log and their times; where the loop takes one
+    step at a time the same rows come from `fn.evaluate` on the host"""
+
+    def __init__(self, stepper, fn, dt):
+        self.stepper, self.fn, self.dt = stepper, fn, dt
+        self.ys, self.ts = [], []
+        self.where = None
+        self.names = None if fn is None else list(fn.names)
+
+    def arm(self, nsteps):
+        self.stepper.set_functionals(self.fn, nsteps, self.dt)
+
+    def collect(self, times):
+        self.add(self.stepper.get_functionals(0, len(times)), times)
+        self.where = 'device'
+
+    def add(self, rows, times):
+        self.ys.append(np.asarray(rows, dtype=np.float64))
+        self.ts.extend(times)
+
+    def host_row(self, v, v_prev, p, time):
+        self.add(self.fn.evaluate(v, v_prev, p, self.dt).reshape((1, -1)),
+                 [time])
+        self.where = 'host'
+
+    def result(self):
+        nf = 0 if self.fn is None else self.fn.nF
+        y = np.vstack(self.ys) if self.ys else np.zeros((0, nf))
+        return y, np.array(self.ts, dtype=np.float64)
+
+
+def _functional_log(rsd, stepper, dt, moving):
+    fn = rsd.get('functionals', None)
+    if fn is None:
+        return None
+    if moving:
+        raise ValueError('`functionals` with controlled (moving) Dirichlet '
+                         'values: the terms `A_bc g(t)`, `M_bc g\'(t)` are not '
+                         'part of the functional')
+    return _FunctionalLog(stepper, fn, dt)
+
+
 def _checkuniformgrid(trange):
     steps = np.diff(np.asarray(trange, dtype=np.float64))
     if not np.allclose(np.linalg.norm(np.diff(steps)), 0):
@@ -441,6 +492,17 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
       `record_bytes`    with `record`: cap of a slice's snapshot buffer
                         (default 1 GiB); a slice that keeps more runs in
                         chunks (`plan_record`)
+      `functionals`     a `fem.MomentumFunctionals` (drag, lift, pressure
+                        differences, ...; static boundaries only): evaluated
+                        on the device after every step of a slice
+                        (`ImexStepper.set_functionals`), with and without
+                        `record`; `LAST_RUN['functionals']` is `nsteps x nF`,
+                        `['functionals_t']` its times.  The rows cover the
+                        AB2 / BDF2 steps of the loop, `trange[2:]`: the Heun
+                        start runs on the host and has no row.  Where the
+                        loop does not run resident the same rows come from
+                        `fn.evaluate` on the host;
+                        `LAST_RUN['functionals_on']` says 'device' or 'host'
     `LAST_RUN['record']` says 'device' or 'host', `LAST_RUN['run_calls']`
     counts the `stepper.run` calls of the loop.
     The per-step data the callbacks return (`f_tdp`, `g_tdp`, `applybcs`) are
@@ -505,7 +567,9 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
     # runs resident at all)
     drec = _DeviceRecord(stepper, rsd, NV, NP) \
         if (on_device and rsd.get('record', False)) else None
+    flog = None
     try:
+        flog = _functional_log(rsd, stepper, dt, moving)
         if fb_dev and on_device:
             rfb = _ResidentFeedback(lti, stepper, drm, .5, .5, dt, trange[1])
         for kck, ctrange in enumerate(listofts):
@@ -538,15 +602,26 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                         dbt[s] = statvals + list(bcs_c)
                 if drec is not None:
                     # the device writes the slice down; the host collects it
+                    chunk = [0, 0]
+
                     def upload(a, b):
                         stepper.set_rhs_table(gvt[a:b], gpt[a:b])
                         if moving:
                             device_convection.set_dbc_table(dbt[a:b])
                         if rfb is not None:
                             rfb.table(ctrange[a:b])
+                        if flog is not None:
+                            flog.arm(b - a)
+                            chunk[:] = [a, b]
+
+                    def after_chunk():
+                        if rfb is not None:
+                            rfb.collect()
+                        if flog is not None:
+                            flog.collect(ctrange[chunk[0]:chunk[1]])
                     states = drec.run_slice(
                         cf, opts, ctrange, savetimes, upload,
-                        after_chunk=None if rfb is None else rfb.collect)
+                        after_chunk=after_chunk)
                     for s, ctime in enumerate(ctrange):
                         if savetimes is None or ctime in savetimes:
                             bcs_at = dbt[s + 1][len(statvals):].tolist() \
@@ -563,6 +638,8 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                     device_convection.set_dbc_table(dbt)
                 if rfb is not None:
                     rfb.table(ctrange)
+                if flog is not None:
+                    flog.arm(ns)
                 done = 0
                 for s, ctime in enumerate(ctrange):
                     if (savetimes is None or ctime in savetimes
@@ -578,6 +655,8 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                     device_convection.set_dbcvals(statvals + list(bcs_n))
                 if rfb is not None:
                     rfb.collect()
+                if flog is not None:
+                    flog.collect(ctrange)
                 stepper.set_rhs(_col(0., NV), _col(0., NP))
                 continue
             for ctime in ctrange:
@@ -599,12 +678,14 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                 stepper.set_rhs(_col(gvec, NV), _col(fp_n + bfp_n, NP))
                 stepper.step(cf, nfc_new=nfc_new, opts=opts)
                 v_n, p_n = stepper.get_state()
+                if flog is not None:
+                    flog.host_row(v_n, v_c, p_n, ctime)
                 savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
         if rfb is not None:
             rfb.finish(drm)
     finally:
         _record_run('cnab', system, stepper, *_feedback_record(
-            rfb, lti, state_dependent), rec=drec)
+            rfb, lti, state_dependent), rec=drec, flog=flog)
         stepper.close()
         system.close()
     return v_n, p_n, ffflag
@@ -669,7 +750,9 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
     rfb = None
     drec = _DeviceRecord(stepper, rsd, NV, NP) \
         if (on_device and rsd.get('record', False)) else None
+    flog = None
     try:
+        flog = _functional_log(rsd, stepper, dt, moving)
         if fb_dev and on_device:
             rfb = _ResidentFeedback(lti, stepper, drm, 2./3, 0., dt,
                                     trange[1])
@@ -695,18 +778,29 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                     if moving:
                         dbt[s] = statvals + list(bcs_c)
                 if drec is not None:
+                    chunk = [0, 0]
+
                     def upload(a, b):
                         stepper.set_rhs_table(gvt[a:b], gpt[a:b])
                         if moving:
                             device_convection.set_dbc_table(dbt[a:b])
                         if rfb is not None:
                             rfb.table(ctrange[a:b])
+                        if flog is not None:
+                            flog.arm(b - a)
+                            chunk[:] = [a, b]
+
+                    def after_chunk():
+                        if rfb is not None:
+                            rfb.collect()
+                        if flog is not None:
+                            flog.collect(ctrange[chunk[0]:chunk[1]])
                     # (kept too: the velocity BEFORE the slice's last step, for
                     # the blow-up guard of the next slice, tiu:317,322)
                     v_start = v_n
                     states = drec.run_slice(
                         cf, opts, ctrange, savetimes, upload, keep_prev=True,
-                        after_chunk=None if rfb is None else rfb.collect)
+                        after_chunk=after_chunk)
                     for s, ctime in enumerate(ctrange):
                         if savetimes is None or ctime in savetimes:
                             bcs_at = dbt[s + 1][len(statvals):].tolist() \
@@ -724,6 +818,8 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                     device_convection.set_dbc_table(dbt)
                 if rfb is not None:
                     rfb.table(ctrange)
+                if flog is not None:
+                    flog.arm(ns)
                 done = 0
                 v_start = v_n
                 for s, ctime in enumerate(ctrange):
@@ -749,6 +845,8 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                     device_convection.set_dbcvals(statvals + list(bcs_n))
                 if rfb is not None:
                     rfb.collect()
+                if flog is not None:
+                    flog.collect(ctrange)
                 stepper.set_rhs(_col(0., NV), _col(0., NP))
                 continue
             for ctime in ctrange:
@@ -770,12 +868,14 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                 stepper.set_rhs(_col(gvec, NV), _col(fp_n + bfp_n, NP))
                 stepper.step(cf, nfc_new=nfc_new, opts=opts)
                 v_n, p_n = stepper.get_state()
+                if flog is not None:
+                    flog.host_row(v_n, v_c, p_n, ctime)
                 savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
         if rfb is not None:
             rfb.finish(drm)
     finally:
         _record_run('sbdftwo', system, stepper, *_feedback_record(
-            rfb, lti, state_dependent), rec=drec)
+            rfb, lti, state_dependent), rec=drec, flog=flog)
         stepper.close()
         system.close()
     return v_n, p_n, ffflag

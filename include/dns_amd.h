@@ -491,6 +491,42 @@ int dns_imex_get_record_snapshots(dns_imex *st, int32_t first_slot,
                                   int32_t count, double *v, double *p);
 /* recorder off (the step is what it was before dns_imex_set_recorder) */
 int dns_imex_clear_recorder(dns_imex *st);
+/* ---- force functionals of the explicit loops (drag, lift, dp, ...) --------
+ * While dns_imex_step / dns_imex_run step (and replay their graphs), one more
+ * kernel per step evaluates nF momentum-balance functionals of the state the
+ * step has left, v = current velocity, v_prev = the one before, p = pressure
+ * as dns_imex_get_state returns it:
+ *     y_k = scale_k * ( ca_k . v + cm_k . (v - v_prev) / dt + cp_k . p
+ *                       + sum_{c in cells_k} sum_{sl < 12} w_k[c][sl] N_loc(c; v)[sl]
+ *                       + c0_k )
+ * ca, cm: nF x NV, cp: nF x NP (host CSR, NULL: no such term).  The cells of
+ * functional k are cell_idx[cell_ptr[k] .. cell_ptr[k+1]) (cells of the
+ * attached convection operator, numbered as in the cell_vdofs it was created
+ * with; NULL cell_ptr: none), cell_w holds twelve
+ * weights per listed cell, slot = 2 * node + component; N_loc are the twelve
+ * local sums of N(v)v on that cell with the operator's constant Dirichlet
+ * values.  c0 / scale: nF values (NULL: 0 / 1).  With the rows of the test
+ * vector phi in M, A, -J^T and phi's local values as weights, scale = -1
+ * gives the consistent nodal force -phi^T (M dv/dt + A v + N(v)v - J^T p).
+ * Row r of the log belongs to the (r+1)-th step after this call, which
+ * resets the step counter like dns_imex_set_rhs_table (call it after that
+ * one); stepping past the last row fails with DNS_ERR_NOT_READY.  Calling it
+ * again re-arms it (buffers that are large enough are kept).
+ * Limits (DNS_ERR_BAD_ARGUMENT beyond them): 1 <= nF <= 16; cell indices
+ * below the operator's ncells; cells need an attached convection operator;
+ * an operator with a per-step Dirichlet table (dns_conv_set_dbc_table) and
+ * a row-partitioned stepper are refused.  Any nnz, any number of cells.
+ * Works with and without observer feedback and the recorder. */
+int dns_imex_set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
+                             const dns_csr *cm, const dns_csr *cp,
+                             const double *c0, const double *scale,
+                             const int32_t *cell_ptr, const int32_t *cell_idx,
+                             const double *cell_w, double dt, int32_t nrows);
+/* rows [first, first + count) of the log: out (count x nF) */
+int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,
+                             double *out);
+/* functionals off (the step is what it was before) */
+int dns_imex_clear_functionals(dns_imex *st);
 /* ||v||_2 of the current velocity (blow-up guard, tiu:94-103) */
 int dns_imex_vnorm(dns_imex *st, double *out);
 

@@ -12,6 +12,14 @@ One command per leg (profiles/r08_recorder/README.md):
   --leg snap      `run(steps)` with a snapshot of every step, then ONE download
   --leg outputs   `run(steps)` with `y = C v` of every step (the three box
                   means of scripts/feedback_bench.py, nnz(C) = 977)
+  --leg forces    `run(steps)` with drag, lift and dp of every step evaluated
+                  on the device (`ImexStepper.set_functionals`), then ONE
+                  download of the rows; `--with-outputs`: the recorder's `y`
+                  log on as well
+  --leg forces_stepwise  `run(1)` + `get_state()` + the same functionals
+                  evaluated on the host (`MomentumFunctionals.evaluate`) per
+                  step: what scripts/schaefer_turek_unsteady.py does without
+                  the device log
   --refine R      the same legs on the mesh refined R times (multigrid Schur
                   block, dt = 1/(512 2^R), start from rest, as refined_bench.py)
 
@@ -173,10 +181,85 @@ def leg_outputs(su, steps, spin):
     return _leg_recorded(su, steps, spin, False, True)
 
 
+def _functionals(su):
+    """drag and lift coefficients and the pressure difference"""
+    from dolfin_navier_scipy_amd import fem
+    femp = su.femp
+    th = femp['V']
+    return fem.boundary_forces(th, femp, names=('cD', 'cL')).scaled(
+        2./((2./3)**2*0.1)) \
+        + fem.pressure_difference(th, (0.15, 0.2), (0.25, 0.2))
+
+
+def leg_forces(su, steps, spin, with_outputs=False):
+    stp, cf, opts, close = su.stepper()
+    try:
+        fn = _functionals(su)
+        dt = getattr(su, 'dt', 1./512)
+        # (set before the spin-up, rows for up to three windows: as
+        # _leg_recorded)
+        if with_outputs:
+            stp.set_recorder(spin + 3*steps, cv_mat=su.C)
+        stp.set_functionals(fn, spin + 3*steps, dt)
+        stp.run(spin, cf, opts)
+        secs, its, n = _timed_window(stp, cf, opts, steps)
+        out = _record(stp, steps, secs, its)
+        out['windows'] = n
+        spin += (n - 1)*steps
+        t0 = time.perf_counter()
+        rows = stp.get_functionals(spin, steps)
+        # (what crosses the bus: every workgroup's share of every row; the
+        # getter sums them; `functional_grid` of csrc/functional.hpp)
+        ncl = sum(int(c.size) for c in fn.cells)
+        grid = max(1, min(64, max(-(-3*fn.nF//4), -(-ncl//32))))
+        nbytes = steps*grid*fn.nF*8
+        if with_outputs:
+            y = stp.record_outputs(spin, steps)
+            nbytes += y.nbytes
+        dl = time.perf_counter() - t0
+        out.update(download_seconds=dl, download_bytes=int(nbytes),
+                   steps_per_s_with_download=steps/(secs + dl),
+                   rows_bytes=int(rows.nbytes), workgroups=grid,
+                   names=fn.names, row_last=rows[-1].tolist(),
+                   body_cells=int(fn.cells[0].size))
+    finally:
+        close()
+    return out
+
+
+def leg_forces_outputs(su, steps, spin):
+    return leg_forces(su, steps, spin, with_outputs=True)
+
+
+def leg_forces_stepwise(su, steps, spin):
+    stp, cf, opts, close = su.stepper()
+    try:
+        fn = _functionals(su)
+        dt = getattr(su, 'dt', 1./512)
+        stp.run(spin, cf, opts)
+        vprev = stp.get_state()[0][:, 0]
+        rows = np.empty((steps, fn.nF))
+        t0 = time.perf_counter()
+        for k in range(steps):
+            stp.run(1, cf, opts)
+            v, p = stp.get_state()
+            rows[k] = fn.evaluate(v[:, 0], vprev, p[:, 0], dt)
+            vprev = v[:, 0]
+        secs = time.perf_counter() - t0
+        out = dict(seconds=secs, steps_per_s=steps/secs, vnorm=stp.vnorm(),
+                   names=fn.names, row_last=rows[-1].tolist())
+    finally:
+        close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--leg', choices=('stepwise', 'open', 'snap', 'outputs'),
+    ap.add_argument('--leg', choices=('stepwise', 'open', 'snap', 'outputs',
+                                      'forces', 'forces_stepwise'),
                     required=True)
+    ap.add_argument('--with-outputs', action='store_true',
+                    help="leg forces: the recorder's y log on as well")
     ap.add_argument('--steps', type=int, default=400)
     ap.add_argument('--spin', type=int, default=64)
     ap.add_argument('--repeats', type=int, default=3)
@@ -193,9 +276,12 @@ def main():
         import feedback_bench as fbb
         su = fbb.Setup()
     fn = dict(stepwise=leg_stepwise, open=leg_open, snap=leg_snap,
-              outputs=leg_outputs)[args.leg]
+              outputs=leg_outputs, forces_stepwise=leg_forces_stepwise,
+              forces=(leg_forces_outputs if args.with_outputs
+                      else leg_forces))[args.leg]
     reps = [fn(su, args.steps, args.spin) for _ in range(args.repeats)]
-    key = 'steps_per_s_with_download' if args.leg in ('snap', 'outputs') \
+    key = 'steps_per_s_with_download' \
+        if args.leg in ('snap', 'outputs', 'forces') \
         else 'steps_per_s'
     rates = [r['steps_per_s'] for r in reps]
     out = dict(leg=args.leg, label=args.label, steps=args.steps,

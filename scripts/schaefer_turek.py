@@ -41,7 +41,17 @@ def p1_eval(mesh, pvert, pt):
     return float(lam @ pvert[c[k]]), float(worst[k])
 
 
-def run(N=2, refine=0, nts=512, tend=8.0, Re=30., verbose=True):
+def run(N=2, refine=0, nts=512, tend=8.0, Re=30., verbose=True,
+        device_forces=False, steady_tol=1e-8, rtol=1e-10):
+    """`steady_tol`: the march stops once the velocity changes by less than
+    this (relative, over `nts` steps).  `rtol`: the relative residual every
+    step's solve ends at.  `device_forces`: c_D and c_L also
+    from the device's log of force functionals
+    (`ImexStepper.set_functionals`, the row of the last step) --
+    `cD_device`, `cL_device`: the steady force `A v + N(v) v - J^T p` the
+    host evaluates below for the same state; `cD_device_dvdt`,
+    `cL_device_dvdt`: with the `M dv/dt` term of the unsteady force, which at
+    the steady state is the solver's noise divided by `dt`"""
     femp, sm, rhsd = get_sysmats(problem='cylinderwake', N=N, refine=refine,
                                  Re=Re)
     th, inv, mesh = femp['V'], femp['invinds'], femp['mesh']
@@ -64,13 +74,22 @@ def run(N=2, refine=0, nts=512, tend=8.0, Re=30., verbose=True):
     stp.set_convection(cv, scale=-1.0)
     cf = saddle.ImexStepper.coeffs(a_c=1., cn_c=1.5*dt, cn_o=-.5*dt,
                                    pscale=-1./dt, extrapolate=4)
-    opts = saddle.solve_opts(rtol=1e-10, maxiter=400, use_graph=True, reorth=2)
+    opts = saddle.solve_opts(rtol=rtol, maxiter=400, use_graph=True, reorth=2)
     nsteps, chunk = int(round(tend*nts)), nts
+    ubar, diam = 2./3, 0.1
+    fn = None
+    if device_forces:
+        from dolfin_navier_scipy_amd.fem import boundary_forces
+        full = boundary_forces(th, femp, names=('cD_dvdt', 'cL_dvdt')).scaled(
+            2./(ubar**2*diam))
+        fn = full.without_rate(names=('cD', 'cL')) + full
     vprev = v0
     done = 0
     secs = 0.
     while done < nsteps:
         n = min(chunk, nsteps - done)
+        if fn is not None:
+            stp.set_functionals(fn, n, dt)
         ds, its, last = stp.run(n, cf, opts)
         secs += ds
         done += n
@@ -82,8 +101,9 @@ def run(N=2, refine=0, nts=512, tend=8.0, Re=30., verbose=True):
                              '{2:.2e}\n'.format(done*dt, n, chg))
         if not np.isfinite(chg):
             raise RuntimeError('diverged')
-        if chg < 1e-8:
+        if chg < steady_tol:
             break
+    dev = None if fn is None else stp.get_functionals(n - 1, 1)[0]
     stp.close()
     system.close()
     # consistent nodal forces from the un-condensed operators
@@ -95,7 +115,6 @@ def run(N=2, refine=0, nts=512, tend=8.0, Re=30., verbose=True):
     nodes, xy = th.boundary_nodes()
     r = np.sqrt((xy[:, 0] - 0.2)**2 + (xy[:, 1] - 0.2)**2)
     cyl = nodes[r < 0.05 + 1e-3]
-    ubar, diam = 2./3, 0.1
     fx = -res[2*cyl, 0].sum()
     fy = -res[2*cyl + 1, 0].sum()
     cD, cL = 2*fx/(ubar**2*diam), 2*fy/(ubar**2*diam)
@@ -105,13 +124,16 @@ def run(N=2, refine=0, nts=512, tend=8.0, Re=30., verbose=True):
     pe, we = p1_eval(mesh, pvert, (0.25, 0.2))
     dp = (pa - pe)*(0.2/ubar)**2          # in the benchmark's units
     cv.close()
+    extra = {} if dev is None else dict(
+        cD_device=float(dev[0]), cL_device=float(dev[1]),
+        cD_device_dvdt=float(dev[2]), cL_device_dvdt=float(dev[3]))
     return dict(level=N, refine=refine, NV=int(NV), NP=int(NP), dt=dt,
                 t_end=done*dt, steps=done, device_seconds=secs,
                 last_change=float(chg), cD=float(cD), cL=float(cL),
                 dp=float(dp), reference=REF,
                 rel_err=dict(cD=abs(cD/REF['cD'] - 1),
                              dp=abs(dp/REF['dp'] - 1)),
-                point_in_cell=[wa, we])
+                point_in_cell=[wa, we], **extra)
 
 
 if __name__ == '__main__':

@@ -76,7 +76,11 @@ class CylinderForces(object):
         return out
 
 
-def run(N=3, nts=1024, tend=18.0, Re=150., verbose=True):
+def run(N=3, nts=1024, tend=18.0, Re=150., verbose=True,
+        device_forces=False):
+    """`device_forces`: the force history of the last third comes from the
+    device's log of force functionals (`ImexStepper.set_functionals`): ONE
+    `run` and one small download instead of a host round trip per step"""
     femp, sm, rhsd = get_sysmats(problem='cylinderwake', N=N, Re=Re)
     th, inv = femp['V'], femp['invinds']
     M, A, J = sm['M'], sm['A'], sm['J']
@@ -107,18 +111,30 @@ def run(N=3, nts=1024, tend=18.0, Re=150., verbose=True):
     stp.run(nfree, cf, opts)
     vprev = stp.get_state()[0][:, 0]
     ts, cds, cls = [], [], []
-    for k in range(nfree, nsteps):
-        stp.run(1, cf, opts)
-        v, p = stp.get_state()
-        v, p = v[:, 0], p[:, 0]
-        if not np.isfinite(v).all():
-            raise RuntimeError('diverged at step {0}'.format(k))
-        # p belongs to the step's end; dv/dt by the backward difference
-        fx, fy = forces(v, (v - vprev)/dt, p)
-        vprev = v
-        ts.append((k + 1)*dt)
-        cds.append(2*fx/(ubar**2*diam))
-        cls.append(2*fy/(ubar**2*diam))
+    if device_forces:
+        from dolfin_navier_scipy_amd.fem import boundary_forces
+        fn = boundary_forces(th, femp, names=('cD', 'cL')).scaled(
+            2./(ubar**2*diam))
+        stp.set_functionals(fn, nsteps - nfree, dt)
+        stp.run(nsteps - nfree, cf, opts)
+        rows = stp.get_functionals()
+        if not np.isfinite(rows).all():
+            raise RuntimeError('diverged')
+        ts = [(k + 1)*dt for k in range(nfree, nsteps)]
+        cds, cls = rows[:, 0], rows[:, 1]
+    else:
+        for k in range(nfree, nsteps):
+            stp.run(1, cf, opts)
+            v, p = stp.get_state()
+            v, p = v[:, 0], p[:, 0]
+            if not np.isfinite(v).all():
+                raise RuntimeError('diverged at step {0}'.format(k))
+            # p belongs to the step's end; dv/dt by the backward difference
+            fx, fy = forces(v, (v - vprev)/dt, p)
+            vprev = v
+            ts.append((k + 1)*dt)
+            cds.append(2*fx/(ubar**2*diam))
+            cls.append(2*fy/(ubar**2*diam))
     stp.close()
     system.close()
     cv.close()
