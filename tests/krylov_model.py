@@ -84,9 +84,8 @@ class BlockTriPrecond(object):
             JTd = np.asarray(self.JT.todense())
             FiJT = np.stack([self.cheb.apply(JTd[:, c])
                              for c in range(self.NP)], axis=1)
-            S = self.J @ FiJT
-            S = 0.5*(S + S.T)
-            schur_inv = np.linalg.inv(S)
+            # (not symmetrised: the device inverts J Fh^-1 JT as it comes)
+            schur_inv = np.linalg.inv(self.J @ FiJT)
         self.Sinv = schur_inv
 
     def apply(self, r):

@@ -8,6 +8,7 @@ import pytest
 import scipy.sparse as sps
 
 import krylov_model as km
+import precond_model as pm
 from oracle import saddle_oracle
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +43,13 @@ def small(toy_prob):
     return dict(F=F, J=J, M=M, A=A, rhsv=rhsv, rhsp=rhsp, ref=ref, dt=dt)
 
 
+@pytest.fixture(scope='module')
+def bench(small):
+    """the fp64 model of the preconditioner apply and its tolerance
+    (`tests/precond_model.py`, `tests/test_precond_model_cpu.py`)"""
+    return pm.Bench(small['M'], small['F'], small['J'])
+
+
 def test_apply_K_and_bounds(sad, small):
     F, J = small['F'], small['J']
     system = sad.SaddleSystem(F, J)
@@ -59,18 +67,15 @@ def test_apply_K_and_bounds(sad, small):
 
 @pytest.mark.parametrize('fhat', ['cheb', 'explicit'])
 @pytest.mark.parametrize('degree', [1, 2, 4])
-def test_precond_matches_model(sad, small, degree, fhat):
+def test_precond_matches_model(sad, small, bench, degree, fhat):
     F, J = small['F'], small['J']
     system = sad.SaddleSystem(F, J)
     system.setup_precond(cheb_degree=degree, schur='dense', fhat=fhat,
                          fp32_store=False, drop_tol=0.)
-    lo, hi = system.cheb_bounds()
-    cheb = km.ChebJacobi(F, degree=degree, lmin=lo, lmax=hi)
-    P = km.BlockTriPrecond(F, J, cheb=cheb)
-    r = np.random.default_rng(3).standard_normal(system.n)
-    z = system.apply_precond(r)
-    zm = P.apply(r)
-    assert np.linalg.norm(z - zm) <= 1e-8*np.linalg.norm(zm)
+    # (rounding level, per block and right-hand side: 1e-12 or less of |z|)
+    ex, _ = bench.apply_excess(system, pm.form_of(degree=degree, fhat=fhat))
+    print('degree %d, %s: error / tolerance %.3f' % (degree, fhat, ex))
+    assert ex <= 1.0
     system.close()
 
 
@@ -119,7 +124,7 @@ def test_gmres_iteration_count_matches_model(sad, small):
 
 
 @pytest.mark.parametrize('schur', ['dense', 'jacobi'])
-def test_full_block_factorisation(sad, small, schur):
+def test_full_block_factorisation(sad, small, bench, schur):
     """`factorization='full'` (block LDU): the apply matches the NumPy model,
     every Krylov variant converges to the oracle's answer, and with the dense
     Schur block it needs far fewer steps than the triangular form"""
@@ -137,9 +142,9 @@ def test_full_block_factorisation(sad, small, schur):
     else:
         sd = 1.0/np.asarray((J.multiply(J) @ (1.0/F.diagonal()))).reshape(-1)
         P = km.BlockFullPrecond(F, J, cheb=cheb, schur_inv=np.diag(sd))
-    r = np.random.default_rng(3).standard_normal(system.n)
-    z, zm = system.apply_precond(r), P.apply(r)
-    assert np.linalg.norm(z - zm) <= 1e-8*np.linalg.norm(zm)
+    ex, _ = bench.apply_excess(system, pm.form_of(schur=schur, fact='full'))
+    print('full, %s: error / tolerance %.3f' % (schur, ex))
+    assert ex <= 1.0
     its = {}
     for method, reorth, graph in (('gmres', 1, True), ('gmres', 0, True),
                                   ('gmres', 2, True), ('gmres', 1, False),
