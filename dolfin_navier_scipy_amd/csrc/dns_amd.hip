@@ -3311,6 +3311,7 @@ int dns_hbm_probe(int device, int64_t bytes, int32_t kind, int32_t reps,
 static void free_dist_data(dns_dist_data *d) { delete d; }
 dns::RowMap dns_saddle::dist_rowmap() const { return dd->kmap; }
 #include "imex_capi.inc"
+#include "imex_attach_capi.inc"
 #include "trap_capi.inc"
 #include "ops_capi.inc"
 #include "conv_capi.inc"

@@ -116,7 +116,7 @@ struct dns_imex : dns::Ring {
     dns::DevBuf<int> stepctr;
     int tab_rows = 0;              // 0: no table, g / gp are used
     bool tab_v = false, tab_p = false;
-    int tab_pos = 0;               // host copy of the counter
+    int tab_pos{0};                // host copy of the counter
     bool preparing = false;        // prepare_graphs is capturing (no launch)
     // the last prepare_graphs call went past its "already prepared" exit, i.e.
     // it captured (or tried to): the same on every rank of a partitioned run
@@ -137,7 +137,6 @@ struct dns_imex : dns::Ring {
         dns::DevBuf<double> haT, hbT, hc, drift, state, ylog, ulog, geff;
         int stride() const { return 2 * hN + Nu; }
     } fb;
-    int fb_rebase();               // current slot -> slot 0 (counter reset)
     int fb_launch(hipStream_t s);  // k_lti_step for the step about to run
     uint64_t fb_key() const;
     // trajectory recorder (record.hpp): k_record_step runs in front of every
@@ -179,20 +178,19 @@ struct dns_imex : dns::Ring {
     std::unique_ptr<Functionals> fn;
     int fn_launch(hipStream_t s);  // k_functional_step for the state as it stands
     uint64_t fn_key() const;
+    // What the three have in common (imex_attach_capi.inc): which of them
+    // run in front of a step and which behind the last step of a call, what
+    // they add to the key of a captured step, the refusals a step makes on
+    // their behalf, and what they mean for the step counter.
+    int launch_front_nodes(hipStream_t s);
+    int launch_closing_nodes(hipStream_t s);
+    uint64_t attachments_key(uint64_t k) const;
+    int refuse_partitioned(const char *noun, const char *reason) const;
+    int check_attachments() const;
     // a step counter is needed as soon as anything is tabulated
-    bool tables() const {
-        return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on || rec ||
-               fn;
-    }
-    int rows_left() const {
-        int lim = 1 << 30;
-        if (tab_rows > 0) lim = std::min(lim, tab_rows);
-        if (fb.on) lim = std::min(lim, fb.rows);
-        if (rec) lim = std::min(lim, rec->rows);
-        if (fn) lim = std::min(lim, fn->rows);
-        if (conv && conv->dbc_rows > 0) lim = std::min(lim, conv->dbc_rows);
-        return lim - tab_pos;
-    }
+    bool tables() const;
+    int rows_left() const;
+    int rewind_tables();           // new tables: the counter back to 0
     dns::TabRef g_src() const {
         if (tab_rows > 0 && tab_v)
             return {gtab.p, stepctr.p, sys->nv, tab_rows};

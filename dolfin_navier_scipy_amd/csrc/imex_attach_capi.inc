@@ -1,0 +1,738 @@
+// The attachments of the resident IMEX loop -- observer feedback
+// (feedback.hpp), trajectory recorder (record.hpp), force functionals
+// (functional.hpp): one node each in front of every step -- and their extern
+// "C" entry points (included by dns_amd.hip behind imex_capi.inc).
+
+// "feedback on", its shape, its coefficients and every buffer k_lti_step is
+// handed: a graph captured for another set must not be replayed
+uint64_t dns_imex::fb_key() const {
+    return mix64(0xfb, {kw(fb.hN), kw(fb.Ny), kw(fb.Nu), kw(fb.rows),
+                        kw(fb.has_drift), kw(fb.dt), kw(fb.c_n), kw(fb.c_c),
+                        kw(fb.C.vals.p), kw(fb.B.vals.p), kw(fb.haT.p),
+                        kw(fb.drift.p), kw(fb.state.p), kw(fb.ylog.p),
+                        kw(fb.ulog.p), kw(fb.geff.p), kw(g.p)});
+}
+
+// "recorder on", its shape, every buffer k_record_step is handed and the
+// pressure scale of the state it is about to write down
+uint64_t dns_imex::rec_key() const {
+    return mix64(0x7ec, {kw(rec->rows), kw(rec->Ny), kw(rec->nslots),
+                         kw(last_pscale), kw(rec->C ? rec->C->vals.p : nullptr),
+                         kw(rec->slot.p), kw(rec->snap.p), kw(rec->ylog.p)});
+}
+
+int dns_imex::rec_launch(hipStream_t s) {
+    const Recorder &r = *rec;
+    const bool snaps = r.nslots > 0, outs = r.Ny > 0;
+    const dns::RecArgs a{stepctr.p, r.rows, xs[cur].p, sys->nv, sys->n,
+                         (int)sys->ld, last_pscale, r.slot.p,
+                         snaps ? r.snap.p : (double *)nullptr, r.nslots, r.Ny,
+                         outs ? r.C->rowptr.p : (const int *)nullptr,
+                         outs ? r.C->colidx.p : (const int *)nullptr,
+                         outs ? r.C->vals.p : (const double *)nullptr,
+                         outs ? r.ylog.p : (double *)nullptr};
+    hipLaunchKernelGGL(dns::k_record_step,
+                       dns::record_grid((int)sys->ld, snaps, r.Ny),
+                       dns::kBlock, 0, s, a);
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+// "functionals on", their shape, every buffer k_functional_step is handed
+// (the ring vectors come with the step key) and the pressure scale
+uint64_t dns_imex::fn_key() const {
+    const Functionals &f = *fn;
+    return mix64(mix64(0xf6, {kw(f.nF), kw(f.G), kw(f.rows), kw(f.ncl),
+                              kw(f.dt), kw(last_pscale), kw(f.rp.p),
+                              kw(f.ci.p), kw(f.va.p), kw(f.cptr.p)}),
+                 {kw(f.cidx.p), kw(f.cw.p), kw(f.scale.p), kw(f.c0.p),
+                  kw(f.log.p), kw(stepctr.p), kw(conv ? conv->ncells : 0),
+                  kw(conv ? conv->cellmap.p : nullptr),
+                  kw(conv ? conv->glam.p : nullptr),
+                  kw(conv ? conv->area.p : nullptr),
+                  kw(conv ? conv->dbcvals.p : nullptr)});
+}
+
+int dns_imex::fn_launch(hipStream_t s) {
+    const Functionals &f = *fn;
+    const bool cells = f.ncl > 0;
+    const dns::FnArgs a{stepctr.p, f.rows, xs[cur].p, xs[prev].p, sys->nv,
+                        last_pscale, f.dt, f.nF, f.G, f.rp.p, f.ci.p, f.va.p,
+                        f.ncl, f.cptr.p, f.cidx.p, f.cw.p,
+                        cells ? conv->ncells : 0,
+                        cells ? conv->cellmap.p : (const int *)nullptr,
+                        cells ? conv->glam.p : (const double *)nullptr,
+                        cells ? conv->area.p : (const double *)nullptr,
+                        cells ? conv->dbcvals.p : (const double *)nullptr,
+                        f.scale.p, f.c0.p, f.log.p};
+    hipLaunchKernelGGL(dns::k_functional_step, f.G, dns::kBlock, 0, s, a);
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+int dns_imex::fb_launch(hipStream_t s) {
+    if (fb.rows < 1)
+        return dns::fail(DNS_ERR_NOT_READY, "observer feedback without a "
+                         "table (dns_imex_set_feedback_table)");
+    const dns::LtiArgs a{stepctr.p, fb.rows, fb.hN, fb.Ny, fb.Nu, sys->nv,
+                         fb.C.rowptr.p, fb.C.colidx.p, fb.C.vals.p,
+                         fb.B.rowptr.p, fb.B.colidx.p, fb.B.vals.p,
+                         fb.haT.p, fb.hbT.p, fb.hc.p,
+                         fb.has_drift ? fb.drift.p : (const double *)nullptr,
+                         fb.state.p, fb.ylog.p, fb.ulog.p, fb.dt, fb.c_n,
+                         fb.c_c, g_src(), xs[cur].p, fb.geff.p};
+    if (dns::lti_staged(fb.hN, fb.Ny, fb.Nu))
+        hipLaunchKernelGGL(dns::k_lti_step<true>, dns::lti_grid(sys->nv),
+                           dns::kBlock, 0, s, a);
+    else
+        hipLaunchKernelGGL(dns::k_lti_step<false>, dns::lti_grid(sys->nv),
+                           dns::kBlock, 0, s, a);
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+// ---- what the three have in common ------------------------------------------
+
+// In front of every step, in this order: k_lti_step leaves the right-hand
+// side the front kernels read, the other two write the row of the step before.
+int dns_imex::launch_front_nodes(hipStream_t s) {
+    if (fb.on) DNS_TRY(fb_launch(s));
+    if (rec) DNS_TRY(rec_launch(s));
+    if (fn) DNS_TRY(fn_launch(s));
+    return DNS_OK;
+}
+
+// Behind the last step of a call: the rows nobody runs a prologue for.
+int dns_imex::launch_closing_nodes(hipStream_t s) {
+    if (rec) DNS_TRY(rec_launch(s));
+    if (fn) DNS_TRY(fn_launch(s));
+    return DNS_OK;
+}
+
+uint64_t dns_imex::attachments_key(uint64_t k) const {
+    if (fb.on) k = mix64(k, {fb_key()});
+    if (rec) k = mix64(k, {rec_key()});
+    if (fn) k = mix64(k, {fn_key()});
+    return k;
+}
+
+bool dns_imex::tables() const {
+    return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on || rec || fn;
+}
+
+int dns_imex::rows_left() const {
+    int lim = 1 << 30;
+    if (tab_rows > 0) lim = std::min(lim, tab_rows);
+    if (fb.on) lim = std::min(lim, fb.rows);
+    if (rec) lim = std::min(lim, rec->rows);
+    if (fn) lim = std::min(lim, fn->rows);
+    if (conv && conv->dbc_rows > 0) lim = std::min(lim, conv->dbc_rows);
+    return lim - tab_pos;
+}
+
+// New tables: the step counter, which selects the row of every table, the log
+// rows and the slot of the observer state (`tab_pos & 1`, slot 0 from here
+// on), goes back to 0 -- here and nowhere else; complete on return.
+int dns_imex::rewind_tables() {
+    if (fb.on && (tab_pos & 1)) {
+        const size_t n = (size_t)fb.stride();
+        DNS_HIP(hipMemcpyAsync(fb.state.p, fb.state.p + n, n * sizeof(double),
+                               hipMemcpyDeviceToDevice, sys->stream));
+    }
+    tab_pos = 0;
+    six_ok = false;          // (cell values belong to a row of the old tables)
+    dcells_ok = false;
+    if (conv && conv->dbc_rows > 0) conv->dbc_row = 0;
+    DNS_TRY(sync_counter());
+    DNS_HIP(hipStreamSynchronize(sys->stream));
+    return DNS_OK;
+}
+
+// None of the three runs on a row-partitioned / distributed stepper: refused
+// when it is set and, should the stepper be partitioned later, by the step.
+int dns_imex::refuse_partitioned(const char *noun, const char *reason) const {
+    if (!(r1_rows || part.on || sys->dist())) return DNS_OK;
+    return dns::fail(DNS_ERR_BAD_ARGUMENT, "%s on a row-partitioned stepper: %s",
+                     noun, reason);
+}
+
+static const char *const kFbPartitioned =
+    "the outputs y = C v would need an all-reduce (multi-rank feedback is not "
+    "supported)";
+static const char *const kRecPartitioned =
+    "the outputs y = C v would need an all-reduce, the snapshots a gather "
+    "(multi-rank recording is not supported)";
+static const char *const kFnPartitioned = "the sums would need an all-reduce";
+
+// what a step refuses on their behalf
+int dns_imex::check_attachments() const {
+    if (fb.on) DNS_TRY(refuse_partitioned("observer feedback", kFbPartitioned));
+    if (rec) DNS_TRY(refuse_partitioned("recorder", kRecPartitioned));
+    if (!fn) return DNS_OK;
+    DNS_TRY(refuse_partitioned("functionals", kFnPartitioned));
+    if (fn->ncl > 0 && !conv)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals with cells need the device convection "
+                         "operator they were set with "
+                         "(dns_imex_set_convection)");
+    // (the listed cells are positions in that operator's cell order)
+    if (fn->ncl > 0 && (conv != fn->conv || conv->ncells != fn->ncells ||
+                        conv->cellmap.p != fn->cellmap))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals with cells were set with another "
+                         "convection operator than the one attached now: "
+                         "set them again (dns_imex_set_functionals)");
+    if (conv && conv->dbc_rows > 0)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals with a per-step Dirichlet table on "
+                         "the convection operator: the moving-boundary "
+                         "terms are not part of the functional");
+    return DNS_OK;
+}
+
+// the handle, the attachment (`what`: "... is" / "... are") and the device
+static int need(dns_imex *st, bool present, const char *what,
+                const char *setter) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (!present)
+        return dns::fail(DNS_ERR_NOT_READY, "no %s set (%s)", what, setter);
+    return hipSetDevice(st->sys->device) == hipSuccess
+               ? DNS_OK : dns::fail(DNS_ERR_HIP, "hipSetDevice failed");
+}
+
+// Rows [first, first + count) of a log of `rows` rows, `width` entries each
+// (`ld` apart on the device), into `dst` (null: the range is checked only);
+// complete on return.
+static int download_log_rows(dns_imex *st, double *dst, const double *buf,
+                             int first, int count, size_t width, int rows,
+                             const char *what, const char *holder,
+                             size_t ld = 0) {
+    if (first < 0 || count < 0 || first + count > rows)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "%s [%d, %d) asked for, the %s holds %d", what, first,
+                         first + count, holder, rows);
+    if (ld == 0) ld = width;
+    hipStream_t s = st->sys->stream;
+    if (dst)
+        DNS_TRY(dns::download_rows(dst, buf + (size_t)first * ld,
+                                   (size_t)count, width, ld, s));
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+}
+
+// A buffer that is large enough is kept, and with it the graphs that were
+// captured for it: the slices of a time loop set their attachments again and
+// again.  `dst` gets room for `need` entries -- a fresh buffer now, unless
+// `old` (which may be `dst` itself) holds one that will do: adopt() takes that
+// one over, once nothing can be refused any more.
+template <typename T>
+static int keep_or_alloc(dns::DevBuf<T> &dst, const dns::DevBuf<T> &old,
+                         size_t need) {
+    if (old.p != nullptr && old.n >= need) return DNS_OK;
+    return dst.alloc(need);
+}
+
+template <typename T>
+static void adopt(dns::DevBuf<T> &dst, dns::DevBuf<T> &old) {
+    if (dst.p != nullptr) return;
+    std::swap(dst.p, old.p);
+    std::swap(dst.n, old.n);
+}
+
+// Before an attachment is taken off: replays may still use its buffers.  (The
+// counter goes on counting for the other tables, if any.)
+static int quiesce(dns_imex *st) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_HIP(hipSetDevice(st->sys->device));
+    DNS_HIP(hipStreamSynchronize(st->sys->stream));
+    return DNS_OK;
+}
+
+extern "C" {
+
+// ---- observer feedback (feedback.hpp) --------------------------------------
+
+static int dns_imex_set_feedback_impl(dns_imex *st, const dns_csr *cmat,
+                                      const dns_csr *bmat, const double *ha,
+                                      const double *hb, const double *hc,
+                                      int32_t hN, int32_t Ny, int32_t Nu,
+                                      double c_n, double c_c, double dt) {
+    if (!st || !cmat || !bmat || !ha || !hb || !hc)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_saddle *h = st->sys;
+    DNS_TRY(st->refuse_partitioned("observer feedback", kFbPartitioned));
+    if (hN < 1 || hN > dns::kFbMaxState || Ny < 1 || Ny > dns::kFbMaxOut ||
+        Nu < 1 || Nu > dns::kFbMaxIn)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "observer feedback: hN = %d, Ny = %d, Nu = %d outside "
+                         "the limits 1..%d, 1..%d, 1..%d of the one-launch "
+                         "observer step", (int)hN, (int)Ny, (int)Nu,
+                         dns::kFbMaxState, dns::kFbMaxOut, dns::kFbMaxIn);
+    DNS_TRY(dns::check_csr(cmat, "C"));
+    DNS_TRY(dns::check_csr(bmat, "B"));
+    if (cmat->nrows != Ny || cmat->ncols != h->nv)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "C must be Ny x NV (%d x %d)",
+                         (int)Ny, h->nv);
+    if (bmat->nrows != h->nv || bmat->ncols != Nu)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "B must be NV x Nu (%d x %d)",
+                         h->nv, (int)Nu);
+    if (cmat->nnz > dns::kFbMaxNnzC)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "observer feedback: C has %lld non-zeros, the "
+                         "one-launch observer step takes at most %d",
+                         (long long)cmat->nnz, dns::kFbMaxNnzC);
+    if (!(dt > 0.0))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "observer feedback: dt <= 0");
+    DNS_HIP(hipSetDevice(h->device));
+    DNS_HIP(hipStreamSynchronize(h->stream));   // replays may still read it
+    dns_imex::Feedback &f = st->fb;
+    f.on = false;
+    hipStream_t s = h->stream;
+    DNS_TRY(f.C.upload(cmat, s));
+    DNS_TRY(f.B.upload(bmat, s));
+    const size_t n = (size_t)hN;
+    std::vector<double> haT(n * n), hbT(n * Ny);
+    for (size_t i = 0; i < n; ++i) {
+        for (size_t j = 0; j < n; ++j) haT[j * n + i] = ha[i * n + j];
+        for (size_t k = 0; k < (size_t)Ny; ++k) hbT[k * n + i] = hb[i * Ny + k];
+    }
+    DNS_TRY(f.haT.alloc(n * n));
+    DNS_TRY(f.haT.upload(haT.data(), n * n, s));
+    DNS_TRY(f.hbT.alloc(n * Ny));
+    DNS_TRY(f.hbT.upload(hbT.data(), n * Ny, s));
+    DNS_TRY(f.hc.alloc(n * Nu));
+    DNS_TRY(f.hc.upload(hc, n * Nu, s));
+    f.hN = hN;
+    f.Ny = Ny;
+    f.Nu = Nu;
+    DNS_TRY(f.state.alloc((size_t)2 * f.stride()));
+    DNS_TRY(f.state.zero(s));
+    if (f.geff.n < (size_t)h->nv) DNS_TRY(f.geff.alloc((size_t)h->nv));
+    DNS_TRY(f.geff.zero(s));
+    f.rows = 0;
+    f.has_drift = false;
+    f.dt = dt;
+    f.c_n = c_n;
+    f.c_c = c_c;
+    DNS_HIP(hipStreamSynchronize(s));
+    f.on = true;
+    return DNS_OK;
+}
+
+int dns_imex_set_feedback(dns_imex *st, const dns_csr *cmat, const dns_csr *bmat,
+                          const double *ha, const double *hb, const double *hc,
+                          int32_t hN, int32_t Ny, int32_t Nu, double c_n,
+                          double c_c, double dt) {
+    return dns::guarded([&]() -> int { return dns_imex_set_feedback_impl(st, cmat, bmat, ha, hb, hc, hN, Ny, Nu, c_n, c_c, dt); });
+}
+
+static int fb_need(dns_imex *st) {
+    return need(st, st && st->fb.on, "observer feedback is",
+                "dns_imex_set_feedback");
+}
+
+static int dns_imex_set_feedback_state_impl(dns_imex *st, const double *hx,
+                                            const double *f_last,
+                                            const double *u_c) {
+    DNS_TRY(fb_need(st));
+    if (!hx || !f_last || !u_c)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_imex::Feedback &f = st->fb;
+    hipStream_t s = st->sys->stream;
+    DNS_HIP(hipStreamSynchronize(s));
+    double *slot = f.state.p + (size_t)(st->tab_pos & 1) * f.stride();
+    DNS_TRY(dns::upload_to(slot, hx, (size_t)f.hN, s));
+    DNS_TRY(dns::upload_to(slot + f.hN, f_last, (size_t)f.hN, s));
+    DNS_TRY(dns::upload_to(slot + 2 * f.hN, u_c, (size_t)f.Nu, s));
+    return DNS_OK;
+}
+
+int dns_imex_set_feedback_state(dns_imex *st, const double *hx,
+                                const double *f_last, const double *u_c) {
+    return dns::guarded([&]() -> int { return dns_imex_set_feedback_state_impl(st, hx, f_last, u_c); });
+}
+
+static int dns_imex_get_feedback_state_impl(dns_imex *st, double *hx,
+                                            double *f_last, double *u_c) {
+    DNS_TRY(fb_need(st));
+    const dns_imex::Feedback &f = st->fb;
+    hipStream_t s = st->sys->stream;
+    const double *slot = f.state.p + (size_t)(st->tab_pos & 1) * f.stride();
+    if (hx) DNS_TRY(dns::download_from(hx, slot, (size_t)f.hN, s));
+    if (f_last)
+        DNS_TRY(dns::download_from(f_last, slot + f.hN, (size_t)f.hN, s));
+    if (u_c) DNS_TRY(dns::download_from(u_c, slot + 2 * f.hN, (size_t)f.Nu, s));
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+}
+
+int dns_imex_get_feedback_state(dns_imex *st, double *hx, double *f_last,
+                                double *u_c) {
+    return dns::guarded([&]() -> int { return dns_imex_get_feedback_state_impl(st, hx, f_last, u_c); });
+}
+
+static int dns_imex_set_feedback_table_impl(dns_imex *st, int32_t nsteps,
+                                            const double *drift) {
+    DNS_TRY(fb_need(st));
+    if (nsteps < 1) return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
+    dns_imex::Feedback &f = st->fb;
+    dns_saddle *h = st->sys;
+    hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still read it
+    const size_t ns = (size_t)nsteps;
+    if (drift) {
+        if (f.drift.n < ns * f.hN) DNS_TRY(f.drift.alloc(ns * f.hN));
+        DNS_TRY(f.drift.upload(drift, ns * f.hN, s));
+    }
+    if (f.ylog.n < ns * f.Ny) DNS_TRY(f.ylog.alloc(ns * f.Ny));
+    if (f.ulog.n < ns * f.Nu) DNS_TRY(f.ulog.alloc(ns * f.Nu));
+    DNS_TRY(f.ylog.zero(s));
+    DNS_TRY(f.ulog.zero(s));
+    f.has_drift = drift != nullptr;
+    f.rows = nsteps;
+    return st->rewind_tables();
+}
+
+int dns_imex_set_feedback_table(dns_imex *st, int32_t nsteps,
+                                const double *drift) {
+    return dns::guarded([&]() -> int { return dns_imex_set_feedback_table_impl(st, nsteps, drift); });
+}
+
+static int dns_imex_get_feedback_log_impl(dns_imex *st, int32_t first,
+                                          int32_t count, double *y, double *u) {
+    DNS_TRY(fb_need(st));
+    const dns_imex::Feedback &f = st->fb;
+    DNS_TRY(download_log_rows(st, y, f.ylog.p, first, count, (size_t)f.Ny,
+                              f.rows, "log rows", "table"));
+    return download_log_rows(st, u, f.ulog.p, first, count, (size_t)f.Nu,
+                             f.rows, "log rows", "table");
+}
+
+int dns_imex_get_feedback_log(dns_imex *st, int32_t first, int32_t count,
+                              double *y, double *u) {
+    return dns::guarded([&]() -> int { return dns_imex_get_feedback_log_impl(st, first, count, y, u); });
+}
+
+static int dns_imex_clear_feedback_impl(dns_imex *st) {
+    DNS_TRY(quiesce(st));
+    st->fb.on = false;
+    st->fb.rows = 0;
+    return DNS_OK;
+}
+
+int dns_imex_clear_feedback(dns_imex *st) {
+    return dns::guarded([&]() -> int { return dns_imex_clear_feedback_impl(st); });
+}
+
+// ---- trajectory recorder (record.hpp) --------------------------------------
+
+static int dns_imex_set_recorder_impl(dns_imex *st, const dns_csr *cmat,
+                                      int32_t nrows, const int32_t *snap_slot,
+                                      int32_t nslots) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_saddle *h = st->sys;
+    DNS_TRY(st->refuse_partitioned("recorder", kRecPartitioned));
+    if (!cmat && !snap_slot)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "recorder: neither outputs (cmat) nor snapshots "
+                         "(snap_slot) asked for");
+    if (nrows < 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "recorder: nrows = %d < 1",
+                         (int)nrows);
+    if (cmat) {
+        DNS_TRY(dns::check_csr(cmat, "C"));
+        if (cmat->nrows < 1 || cmat->ncols != h->nv)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "recorder: C must be Ny x NV (%d columns), it is "
+                             "%d x %d", h->nv, (int)cmat->nrows,
+                             (int)cmat->ncols);
+    }
+    if (snap_slot) {
+        if (nslots < 1)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "recorder: a slot table with nslots = %d < 1",
+                             (int)nslots);
+        for (int r = 0; r < nrows; ++r)
+            if (snap_slot[r] < -1 || snap_slot[r] >= nslots)
+                return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                                 "recorder: snap_slot[%d] = %d outside -1..%d",
+                                 r, (int)snap_slot[r], (int)nslots - 1);
+    }
+    DNS_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
+    // Built aside: a refusal below leaves the recorder that was there.  What
+    // that one holds is taken over where it is large enough (keep_or_alloc;
+    // C where it is the same matrix).
+    dns_imex::Recorder none;
+    dns_imex::Recorder &old = st->rec ? *st->rec : none;
+    std::unique_ptr<dns_imex::Recorder> r(new (std::nothrow)
+                                              dns_imex::Recorder());
+    if (!r) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    r->rows = nrows;
+    bool keep_c = false;
+    if (cmat) {
+        r->Ny = cmat->nrows;
+        const dns::HostCsr &oc = old.Ch;
+        keep_c = old.C && oc.nrows == cmat->nrows && oc.nnz() == cmat->nnz &&
+                 std::equal(oc.rowptr.begin(), oc.rowptr.end(), cmat->rowptr) &&
+                 std::equal(oc.colidx.begin(), oc.colidx.end(), cmat->colidx) &&
+                 std::equal(oc.vals.begin(), oc.vals.end(), cmat->vals);
+        if (!keep_c) {
+            r->C.reset(new (std::nothrow) dns::CsrDev());
+            if (!r->C) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+            DNS_TRY(r->C->upload(cmat, s));
+            r->Ch = dns::host_copy(cmat);
+        }
+        DNS_TRY(keep_or_alloc(r->ylog, old.ylog, (size_t)nrows * cmat->nrows));
+    }
+    if (snap_slot) {
+        r->nslots = nslots;
+        DNS_TRY(keep_or_alloc(r->slot, old.slot, (size_t)nrows));
+        DNS_TRY(keep_or_alloc(r->snap, old.snap, (size_t)nslots * h->ld));
+    }
+    // (nothing is refused from here on)
+    if (keep_c) {
+        r->C = std::move(old.C);
+        r->Ch = std::move(old.Ch);
+    }
+    if (cmat) {
+        adopt(r->ylog, old.ylog);
+        DNS_TRY(r->ylog.zero(s));
+    }
+    if (snap_slot) {
+        adopt(r->slot, old.slot);
+        adopt(r->snap, old.snap);
+        DNS_TRY(r->slot.upload(snap_slot, (size_t)nrows, s));
+        DNS_TRY(r->snap.zero(s));
+    }
+    st->rec = std::move(r);
+    return st->rewind_tables();
+}
+
+int dns_imex_set_recorder(dns_imex *st, const dns_csr *cmat, int32_t nrows,
+                          const int32_t *snap_slot, int32_t nslots) {
+    return dns::guarded([&]() -> int { return dns_imex_set_recorder_impl(st, cmat, nrows, snap_slot, nslots); });
+}
+
+static int rec_need(dns_imex *st) {
+    return need(st, st && st->rec, "recorder is", "dns_imex_set_recorder");
+}
+
+static int dns_imex_get_record_outputs_impl(dns_imex *st, int32_t first,
+                                            int32_t count, double *y) {
+    DNS_TRY(rec_need(st));
+    const dns_imex::Recorder &r = *st->rec;
+    if (r.Ny < 1)
+        return dns::fail(DNS_ERR_NOT_READY, "the recorder keeps no outputs");
+    if (!y) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    return download_log_rows(st, y, r.ylog.p, first, count, (size_t)r.Ny,
+                             r.rows, "output rows", "recorder");
+}
+
+int dns_imex_get_record_outputs(dns_imex *st, int32_t first, int32_t count,
+                                double *y) {
+    return dns::guarded([&]() -> int { return dns_imex_get_record_outputs_impl(st, first, count, y); });
+}
+
+static int dns_imex_get_record_snapshots_impl(dns_imex *st, int32_t first_slot,
+                                              int32_t count, double *v,
+                                              double *p) {
+    DNS_TRY(rec_need(st));
+    const dns_imex::Recorder &r = *st->rec;
+    if (r.nslots < 1)
+        return dns::fail(DNS_ERR_NOT_READY, "the recorder keeps no snapshots");
+    const dns_saddle *h = st->sys;
+    DNS_TRY(download_log_rows(st, v, r.snap.p, first_slot, count,
+                              (size_t)h->nv, r.nslots, "slots", "recorder",
+                              h->ld));
+    return download_log_rows(st, p, r.snap.p + h->nv, first_slot, count,
+                             (size_t)h->np, r.nslots, "slots", "recorder",
+                             h->ld);
+}
+
+int dns_imex_get_record_snapshots(dns_imex *st, int32_t first_slot,
+                                  int32_t count, double *v, double *p) {
+    return dns::guarded([&]() -> int { return dns_imex_get_record_snapshots_impl(st, first_slot, count, v, p); });
+}
+
+static int dns_imex_clear_recorder_impl(dns_imex *st) {
+    DNS_TRY(quiesce(st));
+    st->rec.reset();
+    return DNS_OK;
+}
+
+int dns_imex_clear_recorder(dns_imex *st) {
+    return dns::guarded([&]() -> int { return dns_imex_clear_recorder_impl(st); });
+}
+
+// ---- force functionals (functional.hpp) ------------------------------------
+
+static int dns_imex_set_functionals_impl(
+    dns_imex *st, int32_t nF, const dns_csr *ca, const dns_csr *cm,
+    const dns_csr *cp, const double *c0, const double *scale,
+    const int32_t *cell_ptr, const int32_t *cell_idx, const double *cell_w,
+    double dt, int32_t nrows) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_saddle *h = st->sys;
+    DNS_TRY(st->refuse_partitioned("functionals", kFnPartitioned));
+    if (nF < 1 || nF > dns::kFnMax)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals: nF = %d outside 1..%d", (int)nF,
+                         dns::kFnMax);
+    if (nrows < 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "functionals: nrows = %d < 1",
+                         (int)nrows);
+    if (!(dt > 0.0))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "functionals: dt must be "
+                         "positive");
+    const dns_csr *terms[3] = {ca, cm, cp};
+    const char *names[3] = {"ca", "cm", "cp"};
+    for (int t = 0; t < 3; ++t) {
+        if (!terms[t]) continue;
+        DNS_TRY(dns::check_csr(terms[t], names[t]));
+        const int want = t == 2 ? h->np : h->nv;
+        if (terms[t]->nrows != nF || terms[t]->ncols != want)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals: %s must be nF x %d, it is %d x %d",
+                             names[t], want, (int)terms[t]->nrows,
+                             (int)terms[t]->ncols);
+    }
+    const int ncl = cell_ptr ? cell_ptr[nF] : 0;
+    if (cell_ptr) {
+        if (cell_ptr[0] != 0)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals: cell_ptr[0] must be 0");
+        for (int k = 0; k < nF; ++k)
+            if (cell_ptr[k + 1] < cell_ptr[k])
+                return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                                 "functionals: cell_ptr not monotone");
+    }
+    if (ncl > 0) {
+        if (!cell_idx || !cell_w)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals: cells without cell_idx / cell_w");
+        if (!st->conv)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals with cells need a device convection "
+                             "operator (dns_imex_set_convection)");
+        for (int j = 0; j < ncl; ++j)
+            if (cell_idx[j] < 0 || cell_idx[j] >= st->conv->ncells)
+                return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                                 "functionals: cell index %d at %d outside "
+                                 "0..%d (ncells of the convection operator)",
+                                 (int)cell_idx[j], j, st->conv->ncells - 1);
+    }
+    if (st->conv && st->conv->dbc_rows > 0)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals with a per-step Dirichlet table on the "
+                         "convection operator (dns_conv_set_dbc_table): the "
+                         "moving-boundary terms are not part of the "
+                         "functional");
+    // the 3 nF sparse rows (k, term) in one CSR; a null term is an empty row
+    std::vector<int> rp(3 * (size_t)nF + 1, 0), ci;
+    std::vector<double> va;
+    for (int k = 0; k < nF; ++k)
+        for (int t = 0; t < 3; ++t) {
+            if (terms[t])
+                for (int64_t z = terms[t]->rowptr[k];
+                     z < terms[t]->rowptr[k + 1]; ++z) {
+                    ci.push_back(terms[t]->colidx[z]);
+                    va.push_back(terms[t]->vals[z]);
+                }
+            rp[3 * (size_t)k + t + 1] = (int)ci.size();
+        }
+    std::vector<int> cptr(nF + 1, 0);
+    if (cell_ptr) cptr.assign(cell_ptr, cell_ptr + nF + 1);
+    std::vector<double> sc(nF, 1.0), cc(nF, 0.0);
+    if (scale) sc.assign(scale, scale + nF);
+    if (c0) cc.assign(c0, c0 + nF);
+    DNS_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
+    // In place (keep_or_alloc; everything was checked above: a failed
+    // allocation leaves the stepper without functionals).
+    std::unique_ptr<dns_imex::Functionals> f = std::move(st->fn);
+    if (!f) f.reset(new (std::nothrow) dns_imex::Functionals());
+    if (!f) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    const int G = dns::functional_grid(nF, ncl);
+    auto put = [&](auto &buf, const auto &host) -> int {
+        DNS_TRY(keep_or_alloc(buf, buf, host.size()));
+        if (!host.empty()) DNS_TRY(buf.upload(host.data(), host.size(), s));
+        return DNS_OK;
+    };
+    DNS_TRY(put(f->rp, rp));
+    DNS_TRY(put(f->ci, ci));
+    DNS_TRY(put(f->va, va));
+    DNS_TRY(put(f->cptr, cptr));
+    DNS_TRY(put(f->scale, sc));
+    DNS_TRY(put(f->c0, cc));
+    DNS_TRY(keep_or_alloc(f->cidx, f->cidx, (size_t)ncl));
+    DNS_TRY(keep_or_alloc(f->cw, f->cw, (size_t)12 * ncl));
+    if (ncl > 0) {
+        // (the operator keeps its cells in an order of its own)
+        std::vector<int> cint((size_t)ncl);
+        for (int j = 0; j < ncl; ++j)
+            cint[j] = st->conv->cpos_host[cell_idx[j]];
+        DNS_TRY(f->cidx.upload(cint.data(), (size_t)ncl, s));
+        DNS_TRY(f->cw.upload(cell_w, (size_t)12 * ncl, s));
+    }
+    DNS_TRY(keep_or_alloc(f->log, f->log, (size_t)nrows * G * nF));
+    DNS_TRY(f->log.zero(s));
+    f->nF = nF;
+    f->G = G;
+    f->rows = nrows;
+    f->ncl = ncl;
+    f->dt = dt;
+    f->conv = ncl > 0 ? st->conv : nullptr;
+    f->ncells = ncl > 0 ? st->conv->ncells : 0;
+    f->cellmap = ncl > 0 ? st->conv->cellmap.p : nullptr;
+    st->fn = std::move(f);
+    return st->rewind_tables();
+}
+
+int dns_imex_set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
+                             const dns_csr *cm, const dns_csr *cp,
+                             const double *c0, const double *scale,
+                             const int32_t *cell_ptr, const int32_t *cell_idx,
+                             const double *cell_w, double dt, int32_t nrows) {
+    return dns::guarded([&]() -> int { return dns_imex_set_functionals_impl(st, nF, ca, cm, cp, c0, scale, cell_ptr, cell_idx, cell_w, dt, nrows); });
+}
+
+static int dns_imex_get_functionals_impl(dns_imex *st, int32_t first,
+                                         int32_t count, double *out) {
+    DNS_TRY(need(st, st && st->fn, "functionals are",
+                 "dns_imex_set_functionals"));
+    const dns_imex::Functionals &f = *st->fn;
+    if (!out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    const size_t per = (size_t)f.G * f.nF;
+    std::vector<double> part((size_t)std::min(std::max(count, 0), f.rows) * per);
+    DNS_TRY(download_log_rows(st, part.data(), f.log.p, first, count, per,
+                              f.rows, "functional rows", "log"));
+    // the workgroups' shares, in index order
+    for (int r = 0; r < count; ++r)
+        for (int k = 0; k < f.nF; ++k) {
+            double y = 0.0;
+            for (int g = 0; g < f.G; ++g)
+                y += part[(size_t)r * per + (size_t)g * f.nF + k];
+            out[(size_t)r * f.nF + k] = y;
+        }
+    return DNS_OK;
+}
+
+int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,
+                             double *out) {
+    return dns::guarded([&]() -> int { return dns_imex_get_functionals_impl(st, first, count, out); });
+}
+
+static int dns_imex_clear_functionals_impl(dns_imex *st) {
+    DNS_TRY(quiesce(st));
+    st->fn.reset();
+    return DNS_OK;
+}
+
+int dns_imex_clear_functionals(dns_imex *st) {
+    return dns::guarded([&]() -> int { return dns_imex_clear_functionals_impl(st); });
+}
+
+}  // extern "C"

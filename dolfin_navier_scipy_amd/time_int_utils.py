@@ -20,6 +20,7 @@ caller's Python code; everything between them is on the device.  A
 `dynamic_rhs` that is a `LinearFeedback` is no such callback: its arithmetic is
 known, and `cnab` / `sbdftwo` hand it to the device with the rest of the step.
 """
+import collections
 import logging
 
 import numpy as np
@@ -168,16 +169,17 @@ class _ResidentFeedback(object):
         stepper.set_feedback_state(drm['lasthx'], drm['lastrhs'],
                                    fb.hc @ drm['lasthx'])
 
-    def table(self, ctrange):
-        """after `set_rhs_table`: the drift the step towards `ctrange[s]`
-        sees is the one at the time before it (tiu:187-188)"""
+    def arm(self, ctrange):
+        """after `set_rhs_table`, for the steps towards `ctrange`: the drift
+        the step towards `ctrange[s]` sees is the one at the time before it
+        (tiu:187-188)"""
         befores = [self.tlast] + list(ctrange[:-1])
         drift = None if self.fb._drift is None else \
             np.array([self.fb.drift(t)[:, 0] for t in befores])
         self.stepper.set_feedback_table(len(ctrange), drift)
         self.tlast = ctrange[-1]
 
-    def collect(self):
+    def collect(self, ctrange):
         y, u = self.stepper.feedback_log()
         self.ylog.append(y)
         self.ulog.append(u)
@@ -212,13 +214,22 @@ def _host_feedback_logs(fb):
 RECORD_BYTES = 1 << 30      # default cap of a slice's snapshot buffer
 
 
+def stop_steps(ctrange, savetimes, keep_prev=False):
+    """Steps of a resident time slice whose state the host gets to see: those
+    whose time is in `savetimes` (None: every step), the last step of the
+    slice always (the loop goes on from it), and with `keep_prev` the step
+    before it; in time order"""
+    ns = len(ctrange)
+    return [s for s, t in enumerate(ctrange)
+            if savetimes is None or t in savetimes
+            or s >= ns - 1 - bool(keep_prev)]
+
+
 def plan_record(ctrange, savetimes, snap_bytes, record_bytes=RECORD_BYTES,
                 keep_prev=False):
     """Slots and chunks of a recorded time slice (`resident=dict(record=True)`)
 
-    Kept are the steps whose time is in `savetimes` (None: every step), the
-    last step of the slice always, and with `keep_prev` the step before it.
-    A snapshot takes `snap_bytes`; a chunk keeps at most `record_bytes //
+    Kept are the `stop_steps` of the slice.  A snapshot takes `snap_bytes`; a chunk keeps at most `record_bytes //
     snap_bytes` of them, so a slice that keeps more is cut into chunks, each
     ending with a kept step.  Returns the chunks in time order as dicts
     `first`, `nsteps` (steps `first .. first + nsteps` of the slice), `slots`
@@ -229,16 +240,12 @@ def plan_record(ctrange, savetimes, snap_bytes, record_bytes=RECORD_BYTES,
     if cap < 1:
         raise ValueError('record_bytes = {0} is below one snapshot ({1} '
                          'bytes)'.format(record_bytes, snap_bytes))
-    keep = [savetimes is None or t in savetimes for t in ctrange]
-    if ns:
-        keep[-1] = True
-    if keep_prev and ns > 1:
-        keep[-2] = True
+    keep = set(stop_steps(ctrange, savetimes, keep_prev))
     chunks, first = [], 0
     while first < ns:
         slots, kept, s = [], [], first
         while s < ns:
-            if keep[s]:
+            if s in keep:
                 slots.append(len(kept))
                 kept.append((s, len(kept)))
             else:
@@ -313,8 +320,8 @@ class _FunctionalLog(object):
         self.where = None
         self.names = None if fn is None else list(fn.names)
 
-    def arm(self, nsteps):
-        self.stepper.set_functionals(self.fn, nsteps, self.dt)
+    def arm(self, times):
+        self.stepper.set_functionals(self.fn, len(times), self.dt)
 
     def collect(self, times):
         self.add(self.stepper.get_functionals(0, len(times)), times)
@@ -344,6 +351,116 @@ def _functional_log(rsd, stepper, dt, moving):
                          'values: the terms `A_bc g(t)`, `M_bc g\'(t)` are not '
                          'part of the functional')
     return _FunctionalLog(stepper, fn, dt)
+
+
+# boundary values, the terms `applybcs` makes of them, the forcing at one time
+_Terms = collections.namedtuple('_Terms', 'bcs bfv mbc fv')
+
+
+class _ResidentSlices(object):
+    """What `cnab` and `sbdftwo` share where they run resident: how they read
+    `resident=`, and a time slice as tabulate / upload / replay / collect.
+    The scheme hands over what differs: `row(prev, cur, nxt)`, the `gvt` row
+    of a step from the `_Terms` at the two times before it and at its own,
+    and `keep_prev`, whether the state before a slice's last step is a stop"""
+
+    def __init__(self, stepper, cf, opts, dt, resident, conv, bcs_ini,
+                 state_dependent, prev=None, cur=None, row=None,
+                 keep_prev=False, getbcs=None, applybcs=None, appndbcs=None,
+                 f_tdp=None, g_tdp=None, savevp=None):
+        self.stepper, self.cf, self.opts, self.dt = stepper, cf, opts, dt
+        self.conv, self.row, self.keep_prev = conv, row, keep_prev
+        self.prev, self.cur = prev, cur
+        self.getbcs, self.applybcs, self.appndbcs = getbcs, applybcs, appndbcs
+        self.f_tdp, self.g_tdp, self.savevp = f_tdp, g_tdp, savevp
+        self.rsd = rsd = dict(resident or {})
+        self.statvals = list(rsd.get('static_dbcvals', []) or [])
+        self.moving = len(bcs_ini) > 0
+        if conv is not None:
+            stepper.set_convection(conv, scale=-1.0)
+            if self.moving or self.statvals:
+                conv.set_dbcvals(self.statvals + list(cur.bcs))
+        self.on_device = (conv is not None and resident is not None
+                          and not state_dependent
+                          and (not self.moving
+                               or rsd.get('bcs_time_only', False)))
+        savetimes = rsd.get('savevp_times', None)
+        self.savetimes = None if savetimes is None else set(savetimes)
+        # `record=True`: the device writes the trajectory down (where the loop
+        # runs resident at all)
+        self.drec = _DeviceRecord(stepper, rsd, stepper.sys.NV,
+                                  stepper.sys.NP) \
+            if (self.on_device and rsd.get('record', False)) else None
+        self.flog = self.rfb = None
+        self.attachments = []
+
+    def attach(self, lti, c_n, c_c, drm, tstart):
+        """the functionals and, for a `LinearFeedback` that can run resident,
+        the observer (inside the loop's `try`: both may refuse)"""
+        self.flog = _functional_log(self.rsd, self.stepper, self.dt,
+                                    self.moving)
+        if lti is not None and self.on_device:
+            self.rfb = _ResidentFeedback(lti, self.stepper, drm, c_n, c_c,
+                                         self.dt, tstart)
+        self.attachments = [a for a in (self.rfb, self.flog) if a is not None]
+
+    def run(self, ctrange):
+        """the whole slice: tabulate what the callbacks return, upload,
+        replay; the host sees the `stop_steps` only, `savevp` the save times.
+        Returns `{step of the slice: (v, p)}` of the stops"""
+        stepper, statvals, moving = self.stepper, self.statvals, self.moving
+        NV, NP = stepper.sys.NV, stepper.sys.NP
+        ns = len(ctrange)
+        gvt, gpt = np.empty((ns, NV)), np.empty((ns, NP))
+        dbt = np.empty((ns, len(statvals) + len(self.cur.bcs))) \
+            if moving else None
+        for s, ctime in enumerate(ctrange):
+            bcs_n = self.getbcs(ctime, None, None, mode='abtwo')
+            bfv_n, bfp_n, mbc_n = self.applybcs(bcs_n)
+            fv_n, fp_n = self.f_tdp(ctime), self.g_tdp(ctime)
+            nxt = _Terms(bcs_n, bfv_n, mbc_n, fv_n)
+            gvt[s] = _col(self.row(self.prev, self.cur, nxt), NV)[:, 0]
+            gpt[s] = _col(fp_n + bfp_n, NP)[:, 0]
+            if moving:       # N(v_c) sees the CURRENT boundary values
+                dbt[s] = statvals + list(self.cur.bcs)
+            self.prev, self.cur = self.cur, nxt
+        bcs_n = self.cur.bcs
+        span = [0, 0]
+
+        def upload(a, b):
+            stepper.set_rhs_table(gvt[a:b], gpt[a:b])
+            if moving:
+                self.conv.set_dbc_table(dbt[a:b])
+            for att in self.attachments:
+                att.arm(ctrange[a:b])
+            span[:] = [a, b]
+
+        def after_chunk():
+            for att in self.attachments:
+                att.collect(ctrange[span[0]:span[1]])
+        if self.drec is not None:
+            # the device writes the slice down; the host collects it
+            states = self.drec.run_slice(
+                self.cf, self.opts, ctrange, self.savetimes, upload,
+                keep_prev=self.keep_prev, after_chunk=after_chunk)
+        else:
+            upload(0, ns)
+            states, done = {}, 0
+            for s in stop_steps(ctrange, self.savetimes, self.keep_prev):
+                stepper.run(s + 1 - done, self.cf, self.opts)
+                done = s + 1
+                states[s] = stepper.get_state()
+            after_chunk()
+        for s, ctime in enumerate(ctrange):
+            if self.savetimes is None or ctime in self.savetimes:
+                bcs_at = dbt[s + 1][len(statvals):].tolist() \
+                    if (moving and s + 1 < ns) else bcs_n
+                self.savevp(self.appndbcs(states[s][0], bcs_at),
+                            states[s][1], time=ctime)
+        if moving:
+            self.conv.set_dbcvals(statvals + list(bcs_n))
+        stepper.set_rhs(_col(0., NV), _col(0., NP))
+        return states
 
 
 def _checkuniformgrid(trange):
@@ -550,28 +667,18 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                             pscale=scalep/dt, extrapolate=prm['extrapolate'],
                             carry_residual=prm['carry_residual'])
     stepper.set_state(v_n, ptilde_c=p_n*dt/scalep, nfc_c=nfc_c)
-    rsd = dict(resident or {})
-    statvals = list(rsd.get('static_dbcvals', []) or [])
-    moving = len(bcs_ini) > 0
-    if device_convection is not None:
-        stepper.set_convection(device_convection, scale=-1.0)
-        if moving or statvals:
-            device_convection.set_dbcvals(statvals + list(bcs_n))
-    on_device = (device_convection is not None and resident is not None
-                 and not state_dependent
-                 and (not moving or rsd.get('bcs_time_only', False)))
-    savetimes = rsd.get('savevp_times', None)
-    savetimes = None if savetimes is None else set(savetimes)
-    rfb = None
-    # `record=True`: the device writes the trajectory down (where the loop
-    # runs resident at all)
-    drec = _DeviceRecord(stepper, rsd, NV, NP) \
-        if (on_device and rsd.get('record', False)) else None
-    flog = None
+    # (a row: everything that is not `M v - dt/2 A v` or convection)
+    rs = _ResidentSlices(
+        stepper, cf, opts, dt, resident, device_convection, bcs_ini,
+        state_dependent, prev=_Terms(None, None, mbc_c, None),
+        cur=_Terms(bcs_n, bfv_n, mbc_n, fv_n),
+        row=lambda p, c, n: (-(n.mbc - c.mbc)
+                             + .5*dt*(c.fv + n.fv + n.bfv + c.bfv)),
+        getbcs=getbcs, applybcs=applybcs, appndbcs=appndbcs, f_tdp=f_tdp,
+        g_tdp=g_tdp, savevp=savevp)
+    statvals, moving = rs.statvals, rs.moving
     try:
-        flog = _functional_log(rsd, stepper, dt, moving)
-        if fb_dev and on_device:
-            rfb = _ResidentFeedback(lti, stepper, drm, .5, .5, dt, trange[1])
+        rs.attach(lti if fb_dev else None, .5, .5, drm, trange[1])
         for kck, ctrange in enumerate(listofts):
             nrmvc = stepper.vnorm()
             if verbose:
@@ -581,83 +688,8 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                 logging.warning('BREAK: |v| is `NaN` or |v| > threshhold')
                 ffflag = 1
                 break
-            if on_device and len(ctrange) > 0:
-                # the whole slice: tabulate what the callbacks return, upload,
-                # replay; the host sees the state at the save times only
-                ns = len(ctrange)
-                gvt, gpt = np.empty((ns, NV)), np.empty((ns, NP))
-                dbt = np.empty((ns, len(statvals) + len(bcs_n))) \
-                    if moving else None
-                for s, ctime in enumerate(ctrange):
-                    bcs_c, bfv_c, mbc_c = bcs_n, bfv_n, mbc_n
-                    fv_c = fv_n
-                    bcs_n = getbcs(ctime, None, None, mode='abtwo')
-                    bfv_n, bfp_n, mbc_n = applybcs(bcs_n)
-                    fv_n, fp_n = f_tdp(ctime), g_tdp(ctime)
-                    gvt[s] = _col(-(mbc_n - mbc_c)
-                                  + .5*dt*(fv_c + fv_n + bfv_n + bfv_c),
-                                  NV)[:, 0]
-                    gpt[s] = _col(fp_n + bfp_n, NP)[:, 0]
-                    if moving:       # N(v_c) sees the CURRENT boundary values
-                        dbt[s] = statvals + list(bcs_c)
-                if drec is not None:
-                    # the device writes the slice down; the host collects it
-                    chunk = [0, 0]
-
-                    def upload(a, b):
-                        stepper.set_rhs_table(gvt[a:b], gpt[a:b])
-                        if moving:
-                            device_convection.set_dbc_table(dbt[a:b])
-                        if rfb is not None:
-                            rfb.table(ctrange[a:b])
-                        if flog is not None:
-                            flog.arm(b - a)
-                            chunk[:] = [a, b]
-
-                    def after_chunk():
-                        if rfb is not None:
-                            rfb.collect()
-                        if flog is not None:
-                            flog.collect(ctrange[chunk[0]:chunk[1]])
-                    states = drec.run_slice(
-                        cf, opts, ctrange, savetimes, upload,
-                        after_chunk=after_chunk)
-                    for s, ctime in enumerate(ctrange):
-                        if savetimes is None or ctime in savetimes:
-                            bcs_at = dbt[s + 1][len(statvals):].tolist() \
-                                if (moving and s + 1 < ns) else bcs_n
-                            savevp(appndbcs(states[s][0], bcs_at),
-                                   states[s][1], time=ctime)
-                    v_n, p_n = states[ns - 1]
-                    if moving:
-                        device_convection.set_dbcvals(statvals + list(bcs_n))
-                    stepper.set_rhs(_col(0., NV), _col(0., NP))
-                    continue
-                stepper.set_rhs_table(gvt, gpt)
-                if moving:
-                    device_convection.set_dbc_table(dbt)
-                if rfb is not None:
-                    rfb.table(ctrange)
-                if flog is not None:
-                    flog.arm(ns)
-                done = 0
-                for s, ctime in enumerate(ctrange):
-                    if (savetimes is None or ctime in savetimes
-                            or s == ns - 1):
-                        stepper.run(s + 1 - done, cf, opts)
-                        done = s + 1
-                        v_n, p_n = stepper.get_state()
-                        bcs_at = dbt[s + 1][len(statvals):].tolist() \
-                            if (moving and s + 1 < ns) else bcs_n
-                        if savetimes is None or ctime in savetimes:
-                            savevp(appndbcs(v_n, bcs_at), p_n, time=ctime)
-                if moving:
-                    device_convection.set_dbcvals(statvals + list(bcs_n))
-                if rfb is not None:
-                    rfb.collect()
-                if flog is not None:
-                    flog.collect(ctrange)
-                stepper.set_rhs(_col(0., NV), _col(0., NP))
+            if rs.on_device and len(ctrange) > 0:
+                v_n, p_n = rs.run(ctrange)[len(ctrange) - 1]
                 continue
             for ctime in ctrange:
                 v_c, p_c = v_n, p_n
@@ -678,14 +710,14 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                 stepper.set_rhs(_col(gvec, NV), _col(fp_n + bfp_n, NP))
                 stepper.step(cf, nfc_new=nfc_new, opts=opts)
                 v_n, p_n = stepper.get_state()
-                if flog is not None:
-                    flog.host_row(v_n, v_c, p_n, ctime)
+                if rs.flog is not None:
+                    rs.flog.host_row(v_n, v_c, p_n, ctime)
                 savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
-        if rfb is not None:
-            rfb.finish(drm)
+        if rs.rfb is not None:
+            rs.rfb.finish(drm)
     finally:
         _record_run('cnab', system, stepper, *_feedback_record(
-            rfb, lti, state_dependent), rec=drec, flog=flog)
+            rs.rfb, lti, state_dependent), rec=rs.drec, flog=rs.flog)
         stepper.close()
         system.close()
     return v_n, p_n, ffflag
@@ -734,120 +766,30 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                             pscale=scalep/dt, extrapolate=prm['extrapolate'],
                             carry_residual=prm['carry_residual'])
     stepper.set_state(v_n, v_p=v_c, ptilde_c=p_n*dt/scalep, nfc_c=nfc_c)
-    rsd = dict(resident or {})
-    statvals = list(rsd.get('static_dbcvals', []) or [])
-    moving = len(bcs_ini) > 0
-    if device_convection is not None:
-        stepper.set_convection(device_convection, scale=-1.0)
-        if moving or statvals:
-            device_convection.set_dbcvals(statvals + list(bcs_n))
-    on_device = (device_convection is not None and resident is not None
-                 and not state_dependent
-                 and (not moving or rsd.get('bcs_time_only', False)))
-    savetimes = rsd.get('savevp_times', None)
-    savetimes = None if savetimes is None else set(savetimes)
+    # (kept too: the velocity BEFORE a slice's last step, for the blow-up guard
+    # of the next slice, tiu:317,322)
+    rs = _ResidentSlices(
+        stepper, cf, opts, dt, resident, device_convection, bcs_ini,
+        state_dependent, prev=_Terms(None, None, mbc_c, None),
+        cur=_Terms(bcs_n, bfv_n, mbc_n, fv_n), keep_prev=True,
+        row=lambda p, c, n: (-(n.mbc - 4/3*c.mbc + 1/3*p.mbc)
+                             + 2/3*dt*n.bfv + 2/3*dt*n.fv),
+        getbcs=getbcs, applybcs=applybcs, appndbcs=appndbcs, f_tdp=f_tdp,
+        g_tdp=g_tdp, savevp=savevp)
+    statvals, moving = rs.statvals, rs.moving
     ffflag = 0
-    rfb = None
-    drec = _DeviceRecord(stepper, rsd, NV, NP) \
-        if (on_device and rsd.get('record', False)) else None
-    flog = None
     try:
-        flog = _functional_log(rsd, stepper, dt, moving)
-        if fb_dev and on_device:
-            rfb = _ResidentFeedback(lti, stepper, drm, 2./3, 0., dt,
-                                    trange[1])
+        rs.attach(lti if fb_dev else None, 2./3, 0., drm, trange[1])
         for kck, ctrange in enumerate(listofts):
             nrmvc = np.linalg.norm(v_c)
             if nrmvc > check_ff_maxv or np.isnan(nrmvc):
                 ffflag = 1
                 break
-            if on_device and len(ctrange) > 0:
+            if rs.on_device and len(ctrange) > 0:
                 ns = len(ctrange)
-                gvt, gpt = np.empty((ns, NV)), np.empty((ns, NP))
-                dbt = np.empty((ns, len(statvals) + len(bcs_n))) \
-                    if moving else None
-                for s, ctime in enumerate(ctrange):
-                    mbc_p = mbc_c
-                    bcs_c, mbc_c = bcs_n, mbc_n
-                    bcs_n = getbcs(ctime, None, None, mode='abtwo')
-                    bfv_n, bfp_n, mbc_n = applybcs(bcs_n)
-                    fv_n, fp_n = f_tdp(ctime), g_tdp(ctime)
-                    gvt[s] = _col(-(mbc_n - 4/3*mbc_c + 1/3*mbc_p)
-                                  + 2/3*dt*bfv_n + 2/3*dt*fv_n, NV)[:, 0]
-                    gpt[s] = _col(fp_n + bfp_n, NP)[:, 0]
-                    if moving:
-                        dbt[s] = statvals + list(bcs_c)
-                if drec is not None:
-                    chunk = [0, 0]
-
-                    def upload(a, b):
-                        stepper.set_rhs_table(gvt[a:b], gpt[a:b])
-                        if moving:
-                            device_convection.set_dbc_table(dbt[a:b])
-                        if rfb is not None:
-                            rfb.table(ctrange[a:b])
-                        if flog is not None:
-                            flog.arm(b - a)
-                            chunk[:] = [a, b]
-
-                    def after_chunk():
-                        if rfb is not None:
-                            rfb.collect()
-                        if flog is not None:
-                            flog.collect(ctrange[chunk[0]:chunk[1]])
-                    # (kept too: the velocity BEFORE the slice's last step, for
-                    # the blow-up guard of the next slice, tiu:317,322)
-                    v_start = v_n
-                    states = drec.run_slice(
-                        cf, opts, ctrange, savetimes, upload, keep_prev=True,
-                        after_chunk=after_chunk)
-                    for s, ctime in enumerate(ctrange):
-                        if savetimes is None or ctime in savetimes:
-                            bcs_at = dbt[s + 1][len(statvals):].tolist() \
-                                if (moving and s + 1 < ns) else bcs_n
-                            savevp(appndbcs(states[s][0], bcs_at),
-                                   states[s][1], time=ctime)
-                    v_c = states[ns - 2][0] if ns > 1 else v_start
-                    v_n, p_n = states[ns - 1]
-                    if moving:
-                        device_convection.set_dbcvals(statvals + list(bcs_n))
-                    stepper.set_rhs(_col(0., NV), _col(0., NP))
-                    continue
-                stepper.set_rhs_table(gvt, gpt)
-                if moving:
-                    device_convection.set_dbc_table(dbt)
-                if rfb is not None:
-                    rfb.table(ctrange)
-                if flog is not None:
-                    flog.arm(ns)
-                done = 0
-                v_start = v_n
-                for s, ctime in enumerate(ctrange):
-                    wanted = savetimes is None or ctime in savetimes
-                    # the blow-up guard of the next slice looks at the velocity
-                    # BEFORE this slice's last step (tiu:317,322)
-                    if not (wanted or s >= ns - 2):
-                        continue
-                    stepper.run(s + 1 - done, cf, opts)
-                    done = s + 1
-                    v_s, p_s = stepper.get_state()
-                    if s == ns - 2:
-                        v_c = v_s
-                    if s == ns - 1:
-                        v_n, p_n = v_s, p_s
-                    if wanted:
-                        bcs_at = dbt[s + 1][len(statvals):].tolist() \
-                            if (moving and s + 1 < ns) else bcs_n
-                        savevp(appndbcs(v_s, bcs_at), p_s, time=ctime)
-                if ns == 1:
-                    v_c = v_start
-                if moving:
-                    device_convection.set_dbcvals(statvals + list(bcs_n))
-                if rfb is not None:
-                    rfb.collect()
-                if flog is not None:
-                    flog.collect(ctrange)
-                stepper.set_rhs(_col(0., NV), _col(0., NP))
+                states = rs.run(ctrange)
+                v_c = states[ns - 2][0] if ns > 1 else v_n
+                v_n, p_n = states[ns - 1]
                 continue
             for ctime in ctrange:
                 v_p, mbc_p = v_c, mbc_c
@@ -868,14 +810,14 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                 stepper.set_rhs(_col(gvec, NV), _col(fp_n + bfp_n, NP))
                 stepper.step(cf, nfc_new=nfc_new, opts=opts)
                 v_n, p_n = stepper.get_state()
-                if flog is not None:
-                    flog.host_row(v_n, v_c, p_n, ctime)
+                if rs.flog is not None:
+                    rs.flog.host_row(v_n, v_c, p_n, ctime)
                 savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
-        if rfb is not None:
-            rfb.finish(drm)
+        if rs.rfb is not None:
+            rs.rfb.finish(drm)
     finally:
         _record_run('sbdftwo', system, stepper, *_feedback_record(
-            rfb, lti, state_dependent), rec=drec, flog=flog)
+            rs.rfb, lti, state_dependent), rec=rs.drec, flog=rs.flog)
         stepper.close()
         system.close()
     return v_n, p_n, ffflag

@@ -90,6 +90,34 @@ def test_plan_keeps_the_save_times_and_always_the_last_step():
     _check_plan(plan_record(t, {t[9]}, 800), 10, [9])
 
 
+def test_stop_steps_of_a_slice():
+    """step `s` of an `ns`-step slice is a stop iff `savetimes` is None, its
+    time is in `savetimes`, or `s >= ns - 1 - keep_prev`; the expected sets are
+    written out by hand"""
+    from dolfin_navier_scipy_amd.time_int_utils import stop_steps
+    t = (0.5 + 0.01*np.arange(5)).tolist()
+    expected = {
+        # (ns, keep_prev): the stops for `savetimes` None, empty, and a subset
+        # that misses the last two steps: {17.0}, and for ns = 5 t[0], t[2] too
+        (1, False): ([0], [0], [0]),
+        (1, True): ([0], [0], [0]),
+        (2, False): ([0, 1], [1], [1]),
+        (2, True): ([0, 1], [0, 1], [0, 1]),
+        (5, False): ([0, 1, 2, 3, 4], [4], [0, 2, 4]),
+        (5, True): ([0, 1, 2, 3, 4], [3, 4], [0, 2, 3, 4]),
+    }
+    for (ns, keep_prev), wants in expected.items():
+        subset = set(t[:max(ns - 2, 0):2]) | {17.0}
+        assert not subset & set(t[:ns][-2:])
+        for savetimes, want in zip((None, set(), subset), wants):
+            got = stop_steps(t[:ns], savetimes, keep_prev)
+            assert got == want, (ns, keep_prev, savetimes)
+            assert got[-1] == ns - 1              # the loop goes on from it
+            if keep_prev and ns > 1:
+                assert got[-2] == ns - 2          # SBDF2's blow-up guard
+    assert stop_steps([], None, True) == []
+
+
 def test_plan_of_an_empty_slice_is_empty():
     from dolfin_navier_scipy_amd.time_int_utils import plan_record
     assert plan_record([], None, snap_bytes=800) == []
