@@ -1,7 +1,5 @@
 // Shared host-side plumbing for the gfx950 saddle-point library.
 #pragma once
-#include <exception>
-#include <new>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,11 +7,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "../../include/dns_amd.h"
+#include "status.hpp"
 
 namespace dns {
 
@@ -21,58 +21,12 @@ constexpr int kBlock = 256;      // 4 wavefronts of 64 lanes
 constexpr int kWave = 64;
 constexpr int kMaxRestart = 64;  // GMRES cycle length bound (DnsCtl arrays)
 
-inline thread_local std::string g_last_error;
-
-inline int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-// the C-ABI is an exception barrier: `body` (a lambda returning a status) runs
-// inside try/catch, a C++ exception becomes DNS_ERR_HOST with its message
-template <typename Body>
-inline int guarded(Body body) noexcept {
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        return fail(DNS_ERR_HOST, "out of host memory");
-    } catch (const std::exception &e) {
-        return fail(DNS_ERR_HOST, "host-side exception: %s", e.what());
-    } catch (...) {
-        return fail(DNS_ERR_HOST, "host-side exception");
-    }
-}
-
-// runs `f` when it goes out of scope: on every return and on an exception
-template <typename F>
-class ScopeExit {
-  public:
-    explicit ScopeExit(F f) : f_(std::move(f)) {}
-    ScopeExit(const ScopeExit &) = delete;
-    ScopeExit &operator=(const ScopeExit &) = delete;
-    ~ScopeExit() { f_(); }
-
-  private:
-    F f_;
-};
-
 #define DNS_HIP(call)                                                        \
     do {                                                                     \
         hipError_t e__ = (call);                                             \
         if (e__ != hipSuccess)                                               \
             return dns::fail(DNS_ERR_HIP, "%s failed: %s (%s:%d)", #call,    \
                              hipGetErrorString(e__), __FILE__, __LINE__);    \
-    } while (0)
-
-#define DNS_TRY(call)                                                        \
-    do {                                                                     \
-        int s__ = (call);                                                    \
-        if (s__ != DNS_OK) return s__;                                       \
     } while (0)
 
 // DNS_DEBUG_UPLOADS=1: every copy between HOST memory and the device says

@@ -39,11 +39,11 @@ static int upload_conv_tables() {
 
 extern "C" {
 
-static int dns_conv_create_p2_impl(int device, int32_t ncells, const int32_t *cell_vdofs,
+int dns_conv_create_p2(int device, int32_t ncells, const int32_t *cell_vdofs,
                        const double *glam, const double *area, int32_t vdim,
                        int32_t nv_inner, const int32_t *invinds, int32_t ndbc,
                        const int32_t *dbcinds, const double *dbcvals,
-                       dns_conv **out) {
+                       dns_conv **out) try {
     if (!out || !cell_vdofs || !glam || !area || !invinds || ncells < 1 ||
         vdim < 1 || nv_inner < 0 || ndbc < 0 || (ndbc > 0 && (!dbcinds || !dbcvals)))
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
@@ -104,8 +104,7 @@ static int dns_conv_create_p2_impl(int device, int32_t ncells, const int32_t *ce
         }
     DNS_HIP(hipSetDevice(device));
     DNS_TRY(upload_conv_tables());
-    dns_conv *cv = new (std::nothrow) dns_conv();
-    if (!cv) return fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    auto cv = std::make_unique<dns_conv>();
     cv->device = device;
     if (const char *e = getenv("DNS_CONV_LANE_MIN")) cv->lane_min = atoi(e);
     cv->cmap_host = cmap;
@@ -116,42 +115,25 @@ static int dns_conv_create_p2_impl(int device, int32_t ncells, const int32_t *ce
     cv->ncells = ncells;
     cv->nv_inner = nv_inner;
     cv->ndbc = ndbc;
-    int rc = DNS_OK;
-    auto ok = [&](int s) {
-        if (rc == DNS_OK) rc = s;
-    };
-    ok(cv->cellmap.alloc(cmap.size()));
-    ok(cv->gptr.alloc(cnt.size()));
-    ok(cv->gidx.alloc(gidx.size()));
-    ok(cv->glam.alloc(gl.size()));
-    ok(cv->area.alloc((size_t)ncells));
-    ok(cv->dbcvals.alloc((size_t)std::max(1, ndbc)));
-    ok(cv->cellvals.alloc((size_t)12 * ncells));
-    if (rc == DNS_OK) {
-        ok(cv->cellmap.upload(cmap.data(), cmap.size(), nullptr));
-        ok(cv->gptr.upload(cnt.data(), cnt.size(), nullptr));
-        ok(cv->gidx.upload(gidx.data(), gidx.size(), nullptr));
-        ok(cv->glam.upload(gl.data(), gl.size(), nullptr));
-        ok(cv->area.upload(ar.data(), (size_t)ncells, nullptr));
-        if (ndbc > 0) ok(cv->dbcvals.upload(dbcvals, (size_t)ndbc, nullptr));
-    }
-    if (rc == DNS_OK && hipDeviceSynchronize() != hipSuccess)
-        rc = fail(DNS_ERR_HIP, "device sync failed");
-    if (rc != DNS_OK) {
-        delete cv;
-        return rc;
-    }
-    *out = cv;
+    DNS_TRY(cv->cellmap.alloc(cmap.size()));
+    DNS_TRY(cv->gptr.alloc(cnt.size()));
+    DNS_TRY(cv->gidx.alloc(gidx.size()));
+    DNS_TRY(cv->glam.alloc(gl.size()));
+    DNS_TRY(cv->area.alloc((size_t)ncells));
+    DNS_TRY(cv->dbcvals.alloc((size_t)std::max(1, ndbc)));
+    DNS_TRY(cv->cellvals.alloc((size_t)12 * ncells));
+    DNS_TRY(cv->cellmap.upload(cmap.data(), cmap.size(), nullptr));
+    DNS_TRY(cv->gptr.upload(cnt.data(), cnt.size(), nullptr));
+    DNS_TRY(cv->gidx.upload(gidx.data(), gidx.size(), nullptr));
+    DNS_TRY(cv->glam.upload(gl.data(), gl.size(), nullptr));
+    DNS_TRY(cv->area.upload(ar.data(), (size_t)ncells, nullptr));
+    if (ndbc > 0)
+        DNS_TRY(cv->dbcvals.upload(dbcvals, (size_t)ndbc, nullptr));
+    if (hipDeviceSynchronize() != hipSuccess)
+        return fail(DNS_ERR_HIP, "device sync failed");
+    *out = cv.release();
     return DNS_OK;
-}
-
-int dns_conv_create_p2(int device, int32_t ncells, const int32_t *cell_vdofs,
-                       const double *glam, const double *area, int32_t vdim,
-                       int32_t nv_inner, const int32_t *invinds, int32_t ndbc,
-                       const int32_t *dbcinds, const double *dbcvals,
-                       dns_conv **out) {
-    return dns::guarded([&]() -> int { return dns_conv_create_p2_impl(device, ncells, cell_vdofs, glam, area, vdim, nv_inner, invinds, ndbc, dbcinds, dbcvals, out); });
-}
+} DNS_CAPI_CATCH
 
 void dns_conv_destroy(dns_conv *cv) {
     if (!cv) return;
@@ -160,7 +142,7 @@ void dns_conv_destroy(dns_conv *cv) {
     delete cv;
 }
 
-static int dns_conv_set_dbcvals_impl(dns_conv *cv, const double *dbcvals) {
+int dns_conv_set_dbcvals(dns_conv *cv, const double *dbcvals) try {
     if (!cv || !dbcvals) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(cv->device));
     if (cv->ndbc > 0)
@@ -170,13 +152,10 @@ static int dns_conv_set_dbcvals_impl(dns_conv *cv, const double *dbcvals) {
     cv->dbc_gen++;
     cv->dbc_ctr = nullptr;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_conv_set_dbcvals(dns_conv *cv, const double *dbcvals) {
-    return dns::guarded([&]() -> int { return dns_conv_set_dbcvals_impl(cv, dbcvals); });
-}
-
-static int dns_conv_set_dbc_table_impl(dns_conv *cv, int32_t nrows, const double *vals) {
+int dns_conv_set_dbc_table(dns_conv *cv, int32_t nrows,
+                           const double *vals) try {
     if (!cv || nrows < 1 || !vals)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     DNS_HIP(hipSetDevice(cv->device));
@@ -190,26 +169,18 @@ static int dns_conv_set_dbc_table_impl(dns_conv *cv, int32_t nrows, const double
     cv->dbc_row = 0;
     cv->dbc_gen++;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_conv_set_dbc_table(dns_conv *cv, int32_t nrows, const double *vals) {
-    return dns::guarded([&]() -> int { return dns_conv_set_dbc_table_impl(cv, nrows, vals); });
-}
-
-static int dns_conv_set_dbc_row_impl(dns_conv *cv, int32_t row) {
+int dns_conv_set_dbc_row(dns_conv *cv, int32_t row) try {
     if (!cv || row < 0 || (cv->dbc_rows > 0 && row >= cv->dbc_rows))
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     cv->dbc_row = row;
     cv->dbc_gen++;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_conv_set_dbc_row(dns_conv *cv, int32_t row) {
-    return dns::guarded([&]() -> int { return dns_conv_set_dbc_row_impl(cv, row); });
-}
-
-static int dns_conv_apply_impl(dns_conv *cv, const double *v_inner, double scale,
-                   double *outv) {
+int dns_conv_apply(dns_conv *cv, const double *v_inner, double scale,
+                   double *outv) try {
     if (!cv || !v_inner || !outv)
         return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(cv->device));
@@ -221,14 +192,9 @@ static int dns_conv_apply_impl(dns_conv *cv, const double *v_inner, double scale
     DNS_TRY(dout.download(outv, (size_t)cv->nv_inner, nullptr));
     DNS_HIP(hipDeviceSynchronize());
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_conv_apply(dns_conv *cv, const double *v_inner, double scale,
-                   double *outv) {
-    return dns::guarded([&]() -> int { return dns_conv_apply_impl(cv, v_inner, scale, outv); });
-}
-
-static int dns_conv_bind_pattern_impl(dns_conv *cv, const dns_csr *pat) {
+int dns_conv_bind_pattern(dns_conv *cv, const dns_csr *pat) try {
     if (!cv || !pat || !pat->rowptr || !pat->colidx)
         return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     if (pat->nrows != cv->nv_inner || pat->ncols != cv->nv_inner)
@@ -289,43 +255,28 @@ static int dns_conv_bind_pattern_impl(dns_conv *cv, const dns_csr *pat) {
                     bbc[bpos[mr]++] = -mc - 1;
                 }
             }
-    dns_conv_mat *m = new (std::nothrow) dns_conv_mat();
-    if (!m) return fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    auto m = std::make_unique<dns_conv_mat>();
     m->nnz = (int)nnz;
-    int rc = DNS_OK;
-    auto ok = [&](int s) {
-        if (rc == DNS_OK) rc = s;
-    };
-    ok(m->mptr.alloc(mcnt.size()));
-    ok(m->midx.alloc(std::max<size_t>(1, midx.size())));
-    ok(m->bptr.alloc(bcnt.size()));
-    ok(m->bidx.alloc(std::max<size_t>(1, bidx.size())));
-    ok(m->bbc.alloc(std::max<size_t>(1, bbc.size())));
-    ok(m->L.alloc((size_t)144 * nc));
-    if (rc == DNS_OK) {
-        ok(m->mptr.upload(mcnt.data(), mcnt.size(), nullptr));
-        ok(m->midx.upload(midx.data(), midx.size(), nullptr));
-        ok(m->bptr.upload(bcnt.data(), bcnt.size(), nullptr));
-        ok(m->bidx.upload(bidx.data(), bidx.size(), nullptr));
-        ok(m->bbc.upload(bbc.data(), bbc.size(), nullptr));
-    }
-    if (rc == DNS_OK && hipDeviceSynchronize() != hipSuccess)
-        rc = fail(DNS_ERR_HIP, "device sync failed");
-    if (rc != DNS_OK) {
-        delete m;
-        return rc;
-    }
+    DNS_TRY(m->mptr.alloc(mcnt.size()));
+    DNS_TRY(m->midx.alloc(std::max<size_t>(1, midx.size())));
+    DNS_TRY(m->bptr.alloc(bcnt.size()));
+    DNS_TRY(m->bidx.alloc(std::max<size_t>(1, bidx.size())));
+    DNS_TRY(m->bbc.alloc(std::max<size_t>(1, bbc.size())));
+    DNS_TRY(m->L.alloc((size_t)144 * nc));
+    DNS_TRY(m->mptr.upload(mcnt.data(), mcnt.size(), nullptr));
+    DNS_TRY(m->midx.upload(midx.data(), midx.size(), nullptr));
+    DNS_TRY(m->bptr.upload(bcnt.data(), bcnt.size(), nullptr));
+    DNS_TRY(m->bidx.upload(bidx.data(), bidx.size(), nullptr));
+    DNS_TRY(m->bbc.upload(bbc.data(), bbc.size(), nullptr));
+    if (hipDeviceSynchronize() != hipSuccess)
+        return fail(DNS_ERR_HIP, "device sync failed");
     delete cv->mat;
-    cv->mat = m;
+    cv->mat = m.release();
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_conv_bind_pattern(dns_conv *cv, const dns_csr *pat) {
-    return dns::guarded([&]() -> int { return dns_conv_bind_pattern_impl(cv, pat); });
-}
-
-static int dns_conv_assemble_impl(dns_conv *cv, const double *u_inner, int32_t newton,
-                      double *nvals, double *rhsbc, double *rhscon) {
+int dns_conv_assemble(dns_conv *cv, const double *u_inner, int32_t newton,
+                      double *nvals, double *rhsbc, double *rhscon) try {
     if (!cv || !u_inner || !nvals)
         return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     if (!cv->mat) return fail(DNS_ERR_NOT_READY, "no pattern bound");
@@ -351,17 +302,12 @@ static int dns_conv_assemble_impl(dns_conv *cv, const double *u_inner, int32_t n
     }
     DNS_HIP(hipDeviceSynchronize());
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_conv_assemble(dns_conv *cv, const double *u_inner, int32_t newton,
-                      double *nvals, double *rhsbc, double *rhscon) {
-    return dns::guarded([&]() -> int { return dns_conv_assemble_impl(cv, u_inner, newton, nvals, rhsbc, rhscon); });
-}
-
-static int dns_conv_assemble2_impl(dns_conv *cv, const double *u_inner,
+int dns_conv_assemble2(dns_conv *cv, const double *u_inner,
                        const double *dbcvals_lin, const double *dbcvals_rhs,
                        int32_t newton, double *nvals, double *rhsbc,
-                       double *rhscon) {
+                       double *rhscon) try {
     if (!cv || !u_inner || !nvals || !dbcvals_lin)
         return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     if (!cv->mat) return fail(DNS_ERR_NOT_READY, "no pattern bound");
@@ -414,16 +360,9 @@ static int dns_conv_assemble2_impl(dns_conv *cv, const double *u_inner,
     DNS_HIP(hipGetLastError());
     DNS_HIP(hipDeviceSynchronize());
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_conv_assemble2(dns_conv *cv, const double *u_inner,
-                       const double *dbcvals_lin, const double *dbcvals_rhs,
-                       int32_t newton, double *nvals, double *rhsbc,
-                       double *rhscon) {
-    return dns::guarded([&]() -> int { return dns_conv_assemble2_impl(cv, u_inner, dbcvals_lin, dbcvals_rhs, newton, nvals, rhsbc, rhscon); });
-}
-
-static int dns_imex_set_convection_impl(dns_imex *st, dns_conv *cv, double scale) {
+int dns_imex_set_convection(dns_imex *st, dns_conv *cv, double scale) try {
     if (!st) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     if (cv && cv->nv_inner != st->sys->nv)
         return fail(DNS_ERR_BAD_ARGUMENT,
@@ -435,10 +374,6 @@ static int dns_imex_set_convection_impl(dns_imex *st, dns_conv *cv, double scale
     st->six_ok = false;        // (cell values of another operator / none)
     st->dcells_ok = false;
     return DNS_OK;
-}
-
-int dns_imex_set_convection(dns_imex *st, dns_conv *cv, double scale) {
-    return dns::guarded([&]() -> int { return dns_imex_set_convection_impl(st, cv, scale); });
-}
+} DNS_CAPI_CATCH
 
 }  // extern "C"

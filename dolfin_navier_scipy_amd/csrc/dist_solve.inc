@@ -987,17 +987,13 @@ int dns_saddle::enqueue_cycle_dist(const double *b, double *x, int c,
 
 extern "C" {
 
-static int dns_comm_set_alltoallv_cb_impl(dns_comm *c, dns_alltoallv_cb cb) {
+int dns_comm_set_alltoallv_cb(dns_comm *c, dns_alltoallv_cb cb) try {
     if (!c) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     c->a2a_cb = cb;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_comm_set_alltoallv_cb(dns_comm *c, dns_alltoallv_cb cb) {
-    return dns::guarded([&]() -> int { return dns_comm_set_alltoallv_cb_impl(c, cb); });
-}
-
-static int dns_comm_stats2_impl(dns_comm *c, int64_t *out5) {
+int dns_comm_stats2(dns_comm *c, int64_t *out5) try {
     if (!c || !out5) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     out5[0] = c->n_allreduce;
     out5[1] = c->n_allgather;
@@ -1005,13 +1001,9 @@ static int dns_comm_stats2_impl(dns_comm *c, int64_t *out5) {
     out5[3] = c->bytes_alltoall;
     out5[4] = c->bytes_allgather;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_comm_stats2(dns_comm *c, int64_t *out5) {
-    return dns::guarded([&]() -> int { return dns_comm_stats2_impl(c, out5); });
-}
-
-static int dns_comm_set_timing_impl(dns_comm *c, int on) {
+int dns_comm_set_timing(dns_comm *c, int on) try {
     if (!c) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(c->device));
     DNS_TRY(c->timing_collect());
@@ -1022,13 +1014,9 @@ static int dns_comm_set_timing_impl(dns_comm *c, int on) {
             c->timed_calls[k] = 0;
         }
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_comm_set_timing(dns_comm *c, int on) {
-    return dns::guarded([&]() -> int { return dns_comm_set_timing_impl(c, on); });
-}
-
-static int dns_comm_timing_impl(dns_comm *c, double *ms3, int64_t *calls3) {
+int dns_comm_timing(dns_comm *c, double *ms3, int64_t *calls3) try {
     if (!c || !ms3 || !calls3)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(c->device));
@@ -1038,16 +1026,12 @@ static int dns_comm_timing_impl(dns_comm *c, double *ms3, int64_t *calls3) {
         calls3[k] = c->timed_calls[k];
     }
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_comm_timing(dns_comm *c, double *ms3, int64_t *calls3) {
-    return dns::guarded([&]() -> int { return dns_comm_timing_impl(c, ms3, calls3); });
-}
-
-static int dns_halo_lists_impl(const dns_csr *a, int32_t row0, int32_t row1,
+int dns_halo_lists(const dns_csr *a, int32_t row0, int32_t row1,
                    int32_t nranks, int32_t rank, const int32_t *col_starts,
                    int32_t ncols_part, int32_t *counts, int32_t *lists,
-                   int64_t cap, int64_t *total) {
+                   int64_t cap, int64_t *total) try {
     DNS_TRY(dns::check_csr(a, "A"));
     if (!col_starts || !counts || !total || nranks < 1 || rank < 0 ||
         rank >= nranks || row0 < 0 || row1 > a->nrows || row0 > row1 ||
@@ -1065,16 +1049,9 @@ static int dns_halo_lists_impl(const dns_csr *a, int32_t row0, int32_t row1,
     }
     *total = pos;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_halo_lists(const dns_csr *a, int32_t row0, int32_t row1,
-                   int32_t nranks, int32_t rank, const int32_t *col_starts,
-                   int32_t ncols_part, int32_t *counts, int32_t *lists,
-                   int64_t cap, int64_t *total) {
-    return dns::guarded([&]() -> int { return dns_halo_lists_impl(a, row0, row1, nranks, rank, col_starts, ncols_part, counts, lists, cap, total); });
-}
-
-static int dns_saddle_device_bytes_impl(dns_saddle *h, int64_t *matrix_bytes) {
+int dns_saddle_device_bytes(dns_saddle *h, int64_t *matrix_bytes) try {
     if (!h || !matrix_bytes)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     auto csr = [](const dns::CsrDev &A) -> int64_t {
@@ -1095,10 +1072,6 @@ static int dns_saddle_device_bytes_impl(dns_saddle *h, int64_t *matrix_bytes) {
          (int64_t)(h->mg_cinv16.p ? h->mg_cinv16.n : 0) * 2;
     *matrix_bytes = b;
     return DNS_OK;
-}
-
-int dns_saddle_device_bytes(dns_saddle *h, int64_t *matrix_bytes) {
-    return dns::guarded([&]() -> int { return dns_saddle_device_bytes_impl(h, matrix_bytes); });
-}
+} DNS_CAPI_CATCH
 
 }  // extern "C"

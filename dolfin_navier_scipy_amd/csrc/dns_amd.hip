@@ -2112,7 +2112,7 @@ const char *dns_status_string(int status) {
 
 const char *dns_last_error(void) { return g_last_error.c_str(); }
 
-static int dns_device_count_impl(int *count) {
+int dns_device_count(int *count) try {
     if (!count) return fail(DNS_ERR_BAD_ARGUMENT, "null count");
     int c = 0;
     hipError_t e = hipGetDeviceCount(&c);
@@ -2123,34 +2123,22 @@ static int dns_device_count_impl(int *count) {
     }
     *count = c;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_device_count(int *count) {
-    return dns::guarded([&]() -> int { return dns_device_count_impl(count); });
-}
-
-static int dns_device_name_impl(int device, char *buf, size_t buflen) {
+int dns_device_name(int device, char *buf, size_t buflen) try {
     if (!buf || buflen == 0) return fail(DNS_ERR_BAD_ARGUMENT, "null buffer");
     hipDeviceProp_t prop;
     DNS_HIP(hipGetDeviceProperties(&prop, device));
     snprintf(buf, buflen, "%s (%s, %d CUs)", prop.name, prop.gcnArchName,
              prop.multiProcessorCount);
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_device_name(int device, char *buf, size_t buflen) {
-    return dns::guarded([&]() -> int { return dns_device_name_impl(device, buf, buflen); });
-}
-
-static int dns_device_synchronize_impl(int device) {
+int dns_device_synchronize(int device) try {
     DNS_HIP(hipSetDevice(device));
     DNS_HIP(hipDeviceSynchronize());
     return DNS_OK;
-}
-
-int dns_device_synchronize(int device) {
-    return dns::guarded([&]() -> int { return dns_device_synchronize_impl(device); });
-}
+} DNS_CAPI_CATCH
 
 void dns_default_precond_opts(dns_precond_opts *o) {
     o->cheb_degree = 4;
@@ -2177,25 +2165,15 @@ void dns_default_solve_opts(dns_solve_opts *o) {
     o->use_graph = 0;
 }
 
-static int dns_saddle_create_impl(int device, const dns_csr *f, const dns_csr *j,
-                      const dns_csr *jt, dns_saddle **out) {
+int dns_saddle_create(int device, const dns_csr *f, const dns_csr *j,
+                      const dns_csr *jt, dns_saddle **out) try {
     if (!out) return fail(DNS_ERR_BAD_ARGUMENT, "null output handle");
     *out = nullptr;
-    dns_saddle *h = new (std::nothrow) dns_saddle();
-    if (!h) return fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
-    const int s = h->init(device, f, j, jt);
-    if (s != DNS_OK) {
-        delete h;
-        return s;
-    }
-    *out = h;
+    auto h = std::make_unique<dns_saddle>();
+    DNS_TRY(h->init(device, f, j, jt));
+    *out = h.release();
     return DNS_OK;
-}
-
-int dns_saddle_create(int device, const dns_csr *f, const dns_csr *j,
-                      const dns_csr *jt, dns_saddle **out) {
-    return dns::guarded([&]() -> int { return dns_saddle_create_impl(device, f, j, jt, out); });
-}
+} DNS_CAPI_CATCH
 
 void dns_saddle_destroy(dns_saddle *h) {
     if (!h) return;
@@ -2204,17 +2182,13 @@ void dns_saddle_destroy(dns_saddle *h) {
     delete h;
 }
 
-static int dns_saddle_update_values_impl(dns_saddle *h, const double *f_vals) {
+int dns_saddle_update_values(dns_saddle *h, const double *f_vals) try {
     if (!h || !f_vals) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     return h->update_values(f_vals);
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_update_values(dns_saddle *h, const double *f_vals) {
-    return dns::guarded([&]() -> int { return dns_saddle_update_values_impl(h, f_vals); });
-}
-
-static int dns_saddle_set_schur_mg_impl(dns_saddle *h, int32_t nprol, const dns_csr *prol,
-                            int32_t smooth_steps) {
+int dns_saddle_set_schur_mg(dns_saddle *h, int32_t nprol, const dns_csr *prol,
+                            int32_t smooth_steps) try {
     if (!h || nprol < 0 || (nprol > 0 && !prol) || smooth_steps < 1 ||
         smooth_steps > 8)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
@@ -2237,14 +2211,9 @@ static int dns_saddle_set_schur_mg_impl(dns_saddle *h, int32_t nprol, const dns_
     h->mg_ready = false;
     if (h->popts.schur == DNS_SCHUR_MG) h->precond_ready = false;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_set_schur_mg(dns_saddle *h, int32_t nprol, const dns_csr *prol,
-                            int32_t smooth_steps) {
-    return dns::guarded([&]() -> int { return dns_saddle_set_schur_mg_impl(h, nprol, prol, smooth_steps); });
-}
-
-static int dns_saddle_set_option_impl(dns_saddle *h, const char *name, double value) {
+int dns_saddle_set_option(dns_saddle *h, const char *name, double value) try {
     if (!h || !name) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     const std::string k(name);
     if (k == "stream_nnz") h->stream_nnz = (int64_t)value;
@@ -2278,24 +2247,16 @@ static int dns_saddle_set_option_impl(dns_saddle *h, const char *name, double va
     h->precond_ready = false;        // (set up again with the new setting)
     h->drop_graphs();
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_set_option(dns_saddle *h, const char *name, double value) {
-    return dns::guarded([&]() -> int { return dns_saddle_set_option_impl(h, name, value); });
-}
-
-static int dns_saddle_setup_precond_impl(dns_saddle *h, const dns_precond_opts *opts) {
+int dns_saddle_setup_precond(dns_saddle *h, const dns_precond_opts *opts) try {
     if (!h) return fail(DNS_ERR_BAD_ARGUMENT, "null handle");
     return h->setup_precond(opts);
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_setup_precond(dns_saddle *h, const dns_precond_opts *opts) {
-    return dns::guarded([&]() -> int { return dns_saddle_setup_precond_impl(h, opts); });
-}
-
-static int dns_saddle_solve_impl(dns_saddle *h, const double *rhs_v, const double *rhs_p,
+int dns_saddle_solve(dns_saddle *h, const double *rhs_v, const double *rhs_p,
                      const double *x0, double *out_vp,
-                     const dns_solve_opts *opts, dns_solve_stats *stats) {
+                     const dns_solve_opts *opts, dns_solve_stats *stats) try {
     if (!h || !rhs_v || !out_vp)
         return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_solve_opts o;
@@ -2323,13 +2284,7 @@ static int dns_saddle_solve_impl(dns_saddle *h, const double *rhs_v, const doubl
     DNS_TRY(h->xdev.download(out_vp, (size_t)h->n, h->stream));
     DNS_HIP(hipStreamSynchronize(h->stream));
     return DNS_OK;
-}
-
-int dns_saddle_solve(dns_saddle *h, const double *rhs_v, const double *rhs_p,
-                     const double *x0, double *out_vp,
-                     const dns_solve_opts *opts, dns_solve_stats *stats) {
-    return dns::guarded([&]() -> int { return dns_saddle_solve_impl(h, rhs_v, rhs_p, x0, out_vp, opts, stats); });
-}
+} DNS_CAPI_CATCH
 
 // `ncols` right-hand sides in ONE call: the blocks travel to the device once,
 // the solves run back to back on the resident system (same graphs, same
@@ -2337,12 +2292,11 @@ int dns_saddle_solve(dns_saddle *h, const double *rhs_v, const double *rhs_p,
 // rhs_v + c NV, of `rhs_p` at rhs_p + c NP (NULL: zero), of `out_vp` at
 // out_vp + c (NV + NP); `x0` holds `x0_cols` start vectors (0: none, 1: the
 // same for every column, else one per column).
-static int dns_saddle_solve_multi_impl(dns_saddle *h, int32_t ncols,
-                                       const double *rhs_v, const double *rhs_p,
-                                       const double *x0, int32_t x0_cols,
-                                       double *out_vp,
-                                       const dns_solve_opts *opts,
-                                       dns_solve_stats *stats) {
+int dns_saddle_solve_multi(dns_saddle *h, int32_t ncols, const double *rhs_v,
+                           const double *rhs_p, const double *x0,
+                           int32_t x0_cols, double *out_vp,
+                           const dns_solve_opts *opts,
+                           dns_solve_stats *stats) try {
     if (!h || !rhs_v || !out_vp || ncols < 1 || x0_cols < 0 ||
         (x0_cols > 1 && x0_cols != ncols) || (x0_cols > 0 && !x0))
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
@@ -2409,18 +2363,10 @@ static int dns_saddle_solve_multi_impl(dns_saddle *h, int32_t ncols,
         memcpy(out_vp + c * n, h->mstage.p + c * ld, n * sizeof(double));
     (void)worst;       // (per-column statuses are in `stats`, like the single solve)
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_solve_multi(dns_saddle *h, int32_t ncols, const double *rhs_v,
-                           const double *rhs_p, const double *x0,
-                           int32_t x0_cols, double *out_vp,
-                           const dns_solve_opts *opts, dns_solve_stats *stats) {
-    return dns::guarded([&]() -> int { return dns_saddle_solve_multi_impl(h, ncols, rhs_v, rhs_p, x0, x0_cols, out_vp, opts, stats); });
-}
-
-static int dns_saddle_residual_history_col_impl(dns_saddle *h, int32_t col,
-                                                double *out, int32_t cap,
-                                                int32_t *count) {
+int dns_saddle_residual_history_col(dns_saddle *h, int32_t col, double *out,
+                                    int32_t cap, int32_t *count) try {
     if (!h || !count || col < 0 || (size_t)col >= h->col_history.size())
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     const std::vector<double> &hist = h->col_history[(size_t)col];
@@ -2428,29 +2374,19 @@ static int dns_saddle_residual_history_col_impl(dns_saddle *h, int32_t col,
     if (out)
         for (int32_t i = 0; i < std::min(*count, cap); ++i) out[i] = hist[i];
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_residual_history_col(dns_saddle *h, int32_t col, double *out,
-                                    int32_t cap, int32_t *count) {
-    return dns::guarded([&]() -> int { return dns_saddle_residual_history_col_impl(h, col, out, cap, count); });
-}
-
-static int dns_saddle_residual_history_impl(dns_saddle *h, double *out, int32_t cap,
-                                int32_t *count) {
+int dns_saddle_residual_history(dns_saddle *h, double *out, int32_t cap,
+                                int32_t *count) try {
     if (!h || !count) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     const int32_t nh = (int32_t)h->history.size();
     *count = nh;
     if (out)
         for (int32_t i = 0; i < std::min(nh, cap); ++i) out[i] = h->history[i];
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_residual_history(dns_saddle *h, double *out, int32_t cap,
-                                int32_t *count) {
-    return dns::guarded([&]() -> int { return dns_saddle_residual_history_impl(h, out, cap, count); });
-}
-
-static int dns_saddle_apply_impl(dns_saddle *h, const double *x, double *y) {
+int dns_saddle_apply(dns_saddle *h, const double *x, double *y) try {
     if (!h || !x || !y) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(h->device));
     DNS_TRY(h->xdev.upload(x, (size_t)h->n, h->stream));
@@ -2459,13 +2395,9 @@ static int dns_saddle_apply_impl(dns_saddle *h, const double *x, double *y) {
     DNS_TRY(h->w.download(y, (size_t)h->n, h->stream));
     DNS_HIP(hipStreamSynchronize(h->stream));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_apply(dns_saddle *h, const double *x, double *y) {
-    return dns::guarded([&]() -> int { return dns_saddle_apply_impl(h, x, y); });
-}
-
-static int dns_saddle_apply_precond_impl(dns_saddle *h, const double *r, double *z) {
+int dns_saddle_apply_precond(dns_saddle *h, const double *r, double *z) try {
     if (!h || !r || !z) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     if (!h->precond_ready)
         return fail(DNS_ERR_NOT_READY, "preconditioner not set up");
@@ -2476,13 +2408,9 @@ static int dns_saddle_apply_precond_impl(dns_saddle *h, const double *r, double 
     DNS_TRY(h->z.download(z, (size_t)h->n, h->stream));
     DNS_HIP(hipStreamSynchronize(h->stream));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_apply_precond(dns_saddle *h, const double *r, double *z) {
-    return dns::guarded([&]() -> int { return dns_saddle_apply_precond_impl(h, r, z); });
-}
-
-static int dns_comm_unique_id_impl(char *out) {
+int dns_comm_unique_id(char *out) try {
     if (!out) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     static_assert(sizeof(ncclUniqueId) <= DNS_UNIQUE_ID_BYTES, "id size");
     ncclUniqueId id;
@@ -2492,20 +2420,15 @@ static int dns_comm_unique_id_impl(char *out) {
     memset(out, 0, DNS_UNIQUE_ID_BYTES);
     memcpy(out, &id, sizeof(id));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_comm_unique_id(char *out) {
-    return dns::guarded([&]() -> int { return dns_comm_unique_id_impl(out); });
-}
-
-static int dns_comm_create_rccl_impl(int device, int32_t nranks, int32_t rank,
-                         const char *uid, dns_comm **out) {
+int dns_comm_create_rccl(int device, int32_t nranks, int32_t rank,
+                         const char *uid, dns_comm **out) try {
     if (!out || !uid || nranks < 1 || rank < 0 || rank >= nranks)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     *out = nullptr;
     DNS_HIP(hipSetDevice(device));
-    dns_comm *c = new (std::nothrow) dns_comm();
-    if (!c) return fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    auto c = std::make_unique<dns_comm>();
     c->rank = rank;
     c->nranks = nranks;
     c->device = device;
@@ -2514,59 +2437,43 @@ static int dns_comm_create_rccl_impl(int device, int32_t nranks, int32_t rank,
     ncclResult_t r = ncclCommInitRank(&c->nccl, nranks, id, rank);
     if (r != ncclSuccess) {
         c->nccl = nullptr;
-        delete c;
         return fail(DNS_ERR_COMM, "ncclCommInitRank: %s", ncclGetErrorString(r));
     }
     if (const char *form = getenv("DNS_COMM_ALLGATHER"))
         c->ag_form = strcmp(form, "bcast") == 0 ? 1
                      : strcmp(form, "staged") == 0 ? 2 : 0;
-    *out = c;
+    *out = c.release();
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_comm_create_rccl(int device, int32_t nranks, int32_t rank,
-                         const char *uid, dns_comm **out) {
-    return dns::guarded([&]() -> int { return dns_comm_create_rccl_impl(device, nranks, rank, uid, out); });
-}
-
-static int dns_comm_create_callbacks_impl(int device, int32_t nranks, int32_t rank,
+int dns_comm_create_callbacks(int device, int32_t nranks, int32_t rank,
                               dns_allreduce_cb allreduce,
                               dns_allgatherv_cb allgatherv, void *ctx,
-                              dns_comm **out) {
+                              dns_comm **out) try {
     if (!out || !allreduce || !allgatherv || nranks < 1 || rank < 0 ||
         rank >= nranks)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
-    dns_comm *c = new (std::nothrow) dns_comm();
-    if (!c) return fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    *out = nullptr;
+    auto c = std::make_unique<dns_comm>();
     c->rank = rank;
     c->nranks = nranks;
     c->device = device;
     c->ar_cb = allreduce;
     c->ag_cb = allgatherv;
     c->ctx = ctx;
-    *out = c;
+    *out = c.release();
     return DNS_OK;
-}
-
-int dns_comm_create_callbacks(int device, int32_t nranks, int32_t rank,
-                              dns_allreduce_cb allreduce,
-                              dns_allgatherv_cb allgatherv, void *ctx,
-                              dns_comm **out) {
-    return dns::guarded([&]() -> int { return dns_comm_create_callbacks_impl(device, nranks, rank, allreduce, allgatherv, ctx, out); });
-}
+} DNS_CAPI_CATCH
 
 void dns_comm_destroy(dns_comm *c) { delete c; }
 
-static int dns_comm_stats_impl(dns_comm *c, int64_t *n_allreduce, int64_t *n_allgather) {
+int dns_comm_stats(dns_comm *c, int64_t *n_allreduce,
+                   int64_t *n_allgather) try {
     if (!c) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     if (n_allreduce) *n_allreduce = c->n_allreduce;
     if (n_allgather) *n_allgather = c->n_allgather;
     return DNS_OK;
-}
-
-int dns_comm_stats(dns_comm *c, int64_t *n_allreduce, int64_t *n_allgather) {
-    return dns::guarded([&]() -> int { return dns_comm_stats_impl(c, n_allreduce, n_allgather); });
-}
+} DNS_CAPI_CATCH
 
 // ---- first-contact self-test of the communicator -------------------------
 // ONE primitive per call, so that the caller can say which one did not come
@@ -2579,9 +2486,8 @@ int dns_comm_stats(dns_comm *c, int64_t *n_allreduce, int64_t *n_allgather) {
 // ranks must have produced (*ok), then `reps` calls are timed with an event
 // pair on the launch stream (*us_per_call; the wait for the slowest peer
 // included).  Collective: every rank calls with the same arguments.
-static int dns_comm_selftest_impl(dns_comm *c, int32_t which, int32_t graph,
-                                  int32_t count, int32_t reps, int32_t *ok,
-                                  double *us_per_call) {
+int dns_comm_selftest(dns_comm *c, int32_t which, int32_t graph, int32_t count,
+                      int32_t reps, int32_t *ok, double *us_per_call) try {
     if (!c || !ok || !us_per_call || which < 0 || which > 3 || count < 1 ||
         reps < 1)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
@@ -2699,31 +2605,26 @@ static int dns_comm_selftest_impl(dns_comm *c, int32_t which, int32_t graph,
     DNS_HIP(hipEventElapsedTime(&ms, guard.a, guard.b));
     *us_per_call = 1e3 * (double)ms / reps;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_comm_selftest(dns_comm *c, int32_t which, int32_t graph, int32_t count,
-                      int32_t reps, int32_t *ok, double *us_per_call) {
-    return dns::guarded([&]() -> int { return dns_comm_selftest_impl(c, which, graph, count, reps, ok, us_per_call); });
-}
-
-int dns_comm_set_gather_form(dns_comm *c, int32_t form) {
+int dns_comm_set_gather_form(dns_comm *c, int32_t form) try {
     if (!c || form < 0 || form > 2)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     c->ag_form = form;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
 // how the all-gathers of this communicator were issued: out[0..2] = in-place
 // ncclAllGather, staged ncclAllGather, group of ncclBroadcasts
-int dns_comm_gather_forms(dns_comm *c, int64_t *out3) {
+int dns_comm_gather_forms(dns_comm *c, int64_t *out3) try {
     if (!c || !out3) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     out3[0] = c->n_ag_inplace;
     out3[1] = c->n_ag_staged;
     out3[2] = c->n_ag_bcast;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-static int dns_saddle_set_comm_impl(dns_saddle *h, dns_comm *c) {
+int dns_saddle_set_comm(dns_saddle *h, dns_comm *c) try {
     if (!h) return fail(DNS_ERR_BAD_ARGUMENT, "null handle");
     if (h->rank_local && c != h->comm)
         return fail(DNS_ERR_BAD_ARGUMENT,
@@ -2740,53 +2641,37 @@ static int dns_saddle_set_comm_impl(dns_saddle *h, dns_comm *c) {
         h->st_p = partition_starts(h->np, c->nranks);
     }
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_set_comm(dns_saddle *h, dns_comm *c) {
-    return dns::guarded([&]() -> int { return dns_saddle_set_comm_impl(h, c); });
-}
-
-static int dns_partition_range_impl(int32_t n, int32_t nranks, int32_t rank,
-                        int32_t *start, int32_t *end) {
+int dns_partition_range(int32_t n, int32_t nranks, int32_t rank,
+                        int32_t *start, int32_t *end) try {
     if (!start || !end || n < 0 || nranks < 1 || rank < 0 || rank >= nranks)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     const std::vector<int> st = partition_starts(n, nranks);
     *start = st[rank];
     *end = st[rank + 1];
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_partition_range(int32_t n, int32_t nranks, int32_t rank,
-                        int32_t *start, int32_t *end) {
-    return dns::guarded([&]() -> int { return dns_partition_range_impl(n, nranks, rank, start, end); });
-}
-
-static int dns_device_read_impl(int device, const void *dev, void *host, size_t bytes) {
+int dns_device_read(int device, const void *dev, void *host, size_t bytes) try {
     if (!dev || !host) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(device));
     DNS_HIP(hipDeviceSynchronize());
     DNS_TRY(dns::staged_d2h("device_read", host, dev, bytes, nullptr));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_device_read(int device, const void *dev, void *host, size_t bytes) {
-    return dns::guarded([&]() -> int { return dns_device_read_impl(device, dev, host, bytes); });
-}
-
-static int dns_device_write_impl(int device, void *dev, const void *host, size_t bytes) {
+int dns_device_write(int device, void *dev, const void *host,
+                     size_t bytes) try {
     if (!dev || !host) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(device));
     DNS_HIP(hipDeviceSynchronize());
     DNS_TRY(dns::staged_h2d("device_write", dev, host, bytes, nullptr));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_device_write(int device, void *dev, const void *host, size_t bytes) {
-    return dns::guarded([&]() -> int { return dns_device_write_impl(device, dev, host, bytes); });
-}
-
-static int dns_saddle_probe_impl(dns_saddle *h, int32_t which, int32_t chain,
-                     int32_t reps, double *us_per_launch) {
+int dns_saddle_probe(dns_saddle *h, int32_t which, int32_t chain,
+                     int32_t reps, double *us_per_launch) try {
     if (!h || !us_per_launch || chain < 1 || reps < 1)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     if (!h->precond_ready) return fail(DNS_ERR_NOT_READY, "no preconditioner");
@@ -2925,26 +2810,17 @@ static int dns_saddle_probe_impl(dns_saddle *h, int32_t which, int32_t chain,
         (which == 7) ? 2 : (which == 8 ? 4 : (which >= 1000 ? 2 : 1));
     *us_per_launch = 1e3 * ms / ((double)reps * chain * per);
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_probe(dns_saddle *h, int32_t which, int32_t chain,
-                     int32_t reps, double *us_per_launch) {
-    return dns::guarded([&]() -> int { return dns_saddle_probe_impl(h, which, chain, reps, us_per_launch); });
-}
-
-static int dns_saddle_cheb_bounds_impl(dns_saddle *h, double *lo, double *hi) {
+int dns_saddle_cheb_bounds(dns_saddle *h, double *lo, double *hi) try {
     if (!h || !lo || !hi) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     *lo = h->lam_lo;
     *hi = h->lam_hi;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_saddle_cheb_bounds(dns_saddle *h, double *lo, double *hi) {
-    return dns::guarded([&]() -> int { return dns_saddle_cheb_bounds_impl(h, lo, hi); });
-}
-
-static int dns_saddle_precond_info_impl(dns_saddle *h, int32_t cap, int64_t *out,
-                            int32_t *count) {
+int dns_saddle_precond_info(dns_saddle *h, int32_t cap, int64_t *out,
+                            int32_t *count) try {
     if (!h || !count) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     if (!h->precond_ready)
         return fail(DNS_ERR_NOT_READY, "preconditioner not set up");
@@ -2984,12 +2860,7 @@ static int dns_saddle_precond_info_impl(dns_saddle *h, int32_t cap, int64_t *out
         for (int32_t i = 0; i < std::min<int32_t>(cap, *count); ++i)
             out[i] = v[i];
     return DNS_OK;
-}
-
-int dns_saddle_precond_info(dns_saddle *h, int32_t cap, int64_t *out,
-                            int32_t *count) {
-    return dns::guarded([&]() -> int { return dns_saddle_precond_info_impl(h, cap, out, count); });
-}
+} DNS_CAPI_CATCH
 
 // ---- standalone kernels ----------------------------------------------------
 struct ScopedStream {
@@ -2999,8 +2870,8 @@ struct ScopedStream {
     }
 };
 
-static int dns_spmv_impl(int device, const dns_csr *a, const double *x, double *y,
-             double alpha, double beta, int32_t variant) {
+int dns_spmv(int device, const dns_csr *a, const double *x, double *y,
+             double alpha, double beta, int32_t variant) try {
     DNS_TRY(check_csr(a, "A"));
     if (!x || !y) return fail(DNS_ERR_BAD_ARGUMENT, "null vector");
     DNS_HIP(hipSetDevice(device));
@@ -3019,15 +2890,10 @@ static int dns_spmv_impl(int device, const dns_csr *a, const double *x, double *
     DNS_TRY(dy.download(y, (size_t)a->nrows, ss.s));
     DNS_HIP(hipStreamSynchronize(ss.s));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_spmv(int device, const dns_csr *a, const double *x, double *y,
-             double alpha, double beta, int32_t variant) {
-    return dns::guarded([&]() -> int { return dns_spmv_impl(device, a, x, y, alpha, beta, variant); });
-}
-
-static int dns_dot_impl(int device, int64_t n, const double *x, const double *y,
-            double *out) {
+int dns_dot(int device, int64_t n, const double *x, const double *y,
+            double *out) try {
     if (!x || !y || !out || n < 0)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     DNS_HIP(hipSetDevice(device));
@@ -3048,14 +2914,9 @@ static int dns_dot_impl(int device, int64_t n, const double *x, const double *y,
     DNS_TRY(res.download(out, 1, ss.s));
     DNS_HIP(hipStreamSynchronize(ss.s));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_dot(int device, int64_t n, const double *x, const double *y,
-            double *out) {
-    return dns::guarded([&]() -> int { return dns_dot_impl(device, n, x, y, out); });
-}
-
-static int dns_axpy_impl(int device, int64_t n, double a, const double *x, double *y) {
+int dns_axpy(int device, int64_t n, double a, const double *x, double *y) try {
     if (!x || !y || n < 0) return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     DNS_HIP(hipSetDevice(device));
     ScopedStream ss;
@@ -3071,14 +2932,10 @@ static int dns_axpy_impl(int device, int64_t n, double a, const double *x, doubl
     DNS_TRY(dy.download(y, (size_t)n, ss.s));
     DNS_HIP(hipStreamSynchronize(ss.s));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_axpy(int device, int64_t n, double a, const double *x, double *y) {
-    return dns::guarded([&]() -> int { return dns_axpy_impl(device, n, a, x, y); });
-}
-
-static int dns_gemv_impl(int device, int32_t n, const double *a_rowmajor, const double *x,
-             double *y, double alpha) {
+int dns_gemv(int device, int32_t n, const double *a_rowmajor, const double *x,
+             double *y, double alpha) try {
     if (!a_rowmajor || !x || !y || n < 0)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     DNS_HIP(hipSetDevice(device));
@@ -3098,14 +2955,9 @@ static int dns_gemv_impl(int device, int32_t n, const double *a_rowmajor, const 
     DNS_TRY(dy.download(y, (size_t)n, ss.s));
     DNS_HIP(hipStreamSynchronize(ss.s));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_gemv(int device, int32_t n, const double *a_rowmajor, const double *x,
-             double *y, double alpha) {
-    return dns::guarded([&]() -> int { return dns_gemv_impl(device, n, a_rowmajor, x, y, alpha); });
-}
-
-static int dns_dense_inverse_impl(int device, int32_t n, double *a_rowmajor) {
+int dns_dense_inverse(int device, int32_t n, double *a_rowmajor) try {
     if (!a_rowmajor || n < 1)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     DNS_HIP(hipSetDevice(device));
@@ -3119,14 +2971,10 @@ static int dns_dense_inverse_impl(int device, int32_t n, double *a_rowmajor) {
     DNS_TRY(da.download(a_rowmajor, (size_t)n * n, tmp.stream));
     DNS_HIP(hipStreamSynchronize(tmp.stream));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_dense_inverse(int device, int32_t n, double *a_rowmajor) {
-    return dns::guarded([&]() -> int { return dns_dense_inverse_impl(device, n, a_rowmajor); });
-}
-
-static int dns_spmv_bench_impl(int device, const dns_csr *a, int32_t variant, int32_t reps,
-                   int32_t warmup, double *avg_seconds, double *checksum) {
+int dns_spmv_bench(int device, const dns_csr *a, int32_t variant, int32_t reps,
+                   int32_t warmup, double *avg_seconds, double *checksum) try {
     DNS_TRY(check_csr(a, "A"));
     if (!avg_seconds || reps < 1)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
@@ -3167,19 +3015,14 @@ static int dns_spmv_bench_impl(int device, const dns_csr *a, int32_t variant, in
         DNS_HIP(hipStreamSynchronize(ss.s));
     }
     return DNS_OK;
-}
-
-int dns_spmv_bench(int device, const dns_csr *a, int32_t variant, int32_t reps,
-                   int32_t warmup, double *avg_seconds, double *checksum) {
-    return dns::guarded([&]() -> int { return dns_spmv_bench_impl(device, a, variant, reps, warmup, avg_seconds, checksum); });
-}
+} DNS_CAPI_CATCH
 
 // y = K x through the pair format (pair.hpp); DNS_ERR_BAD_ARGUMENT for odd
 // sizes.  reps > 0: timed like dns_spmv_bench
 // (HIP events on the launch stream), *avg_seconds = seconds per launch
-static int dns_spmv_pair_impl(int device, const dns_csr *k, int32_t nv, const double *x,
+int dns_spmv_pair(int device, const dns_csr *k, int32_t nv, const double *x,
                   double *y, int32_t reps, int32_t warmup, double *avg_seconds,
-                  int64_t *format_bytes) {
+                  int64_t *format_bytes) try {
     DNS_TRY(check_csr(k, "K"));
     if (!x || !y) return fail(DNS_ERR_BAD_ARGUMENT, "null vector");
     if (k->nrows != k->ncols)
@@ -3229,16 +3072,10 @@ static int dns_spmv_pair_impl(int device, const dns_csr *k, int32_t nv, const do
     DNS_TRY(dy.download(y, (size_t)k->nrows, ss.s));
     DNS_HIP(hipStreamSynchronize(ss.s));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_spmv_pair(int device, const dns_csr *k, int32_t nv, const double *x,
-                  double *y, int32_t reps, int32_t warmup, double *avg_seconds,
-                  int64_t *format_bytes) {
-    return dns::guarded([&]() -> int { return dns_spmv_pair_impl(device, k, nv, x, y, reps, warmup, avg_seconds, format_bytes); });
-}
-
-static int dns_hbm_probe_impl(int device, int64_t bytes, int32_t kind, int32_t reps,
-                  double *gbytes_per_s) {
+int dns_hbm_probe(int device, int64_t bytes, int32_t kind, int32_t reps,
+                  double *gbytes_per_s) try {
     if (!gbytes_per_s || reps < 1 || bytes < 4096 || kind < 0 || kind > 8)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     DNS_HIP(hipSetDevice(device));
@@ -3296,12 +3133,7 @@ static int dns_hbm_probe_impl(int device, int64_t bytes, int32_t kind, int32_t r
     DNS_HIP(hipGetLastError());
     *gbytes_per_s = (double)(16 * n2 * narr) * reps / (1e-3 * ms) * 1e-9;
     return DNS_OK;
-}
-
-int dns_hbm_probe(int device, int64_t bytes, int32_t kind, int32_t reps,
-                  double *gbytes_per_s) {
-    return dns::guarded([&]() -> int { return dns_hbm_probe_impl(device, bytes, kind, reps, gbytes_per_s); });
-}
+} DNS_CAPI_CATCH
 
 }  // extern "C"
 

@@ -252,11 +252,10 @@ extern "C" {
 
 // ---- observer feedback (feedback.hpp) --------------------------------------
 
-static int dns_imex_set_feedback_impl(dns_imex *st, const dns_csr *cmat,
-                                      const dns_csr *bmat, const double *ha,
-                                      const double *hb, const double *hc,
-                                      int32_t hN, int32_t Ny, int32_t Nu,
-                                      double c_n, double c_c, double dt) {
+int dns_imex_set_feedback(dns_imex *st, const dns_csr *cmat, const dns_csr *bmat,
+                          const double *ha, const double *hb, const double *hc,
+                          int32_t hN, int32_t Ny, int32_t Nu, double c_n,
+                          double c_c, double dt) try {
     if (!st || !cmat || !bmat || !ha || !hb || !hc)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
@@ -317,23 +316,15 @@ static int dns_imex_set_feedback_impl(dns_imex *st, const dns_csr *cmat,
     DNS_HIP(hipStreamSynchronize(s));
     f.on = true;
     return DNS_OK;
-}
-
-int dns_imex_set_feedback(dns_imex *st, const dns_csr *cmat, const dns_csr *bmat,
-                          const double *ha, const double *hb, const double *hc,
-                          int32_t hN, int32_t Ny, int32_t Nu, double c_n,
-                          double c_c, double dt) {
-    return dns::guarded([&]() -> int { return dns_imex_set_feedback_impl(st, cmat, bmat, ha, hb, hc, hN, Ny, Nu, c_n, c_c, dt); });
-}
+} DNS_CAPI_CATCH
 
 static int fb_need(dns_imex *st) {
     return need(st, st && st->fb.on, "observer feedback is",
                 "dns_imex_set_feedback");
 }
 
-static int dns_imex_set_feedback_state_impl(dns_imex *st, const double *hx,
-                                            const double *f_last,
-                                            const double *u_c) {
+int dns_imex_set_feedback_state(dns_imex *st, const double *hx,
+                                const double *f_last, const double *u_c) try {
     DNS_TRY(fb_need(st));
     if (!hx || !f_last || !u_c)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
@@ -345,15 +336,10 @@ static int dns_imex_set_feedback_state_impl(dns_imex *st, const double *hx,
     DNS_TRY(dns::upload_to(slot + f.hN, f_last, (size_t)f.hN, s));
     DNS_TRY(dns::upload_to(slot + 2 * f.hN, u_c, (size_t)f.Nu, s));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_set_feedback_state(dns_imex *st, const double *hx,
-                                const double *f_last, const double *u_c) {
-    return dns::guarded([&]() -> int { return dns_imex_set_feedback_state_impl(st, hx, f_last, u_c); });
-}
-
-static int dns_imex_get_feedback_state_impl(dns_imex *st, double *hx,
-                                            double *f_last, double *u_c) {
+int dns_imex_get_feedback_state(dns_imex *st, double *hx, double *f_last,
+                                double *u_c) try {
     DNS_TRY(fb_need(st));
     const dns_imex::Feedback &f = st->fb;
     hipStream_t s = st->sys->stream;
@@ -364,15 +350,10 @@ static int dns_imex_get_feedback_state_impl(dns_imex *st, double *hx,
     if (u_c) DNS_TRY(dns::download_from(u_c, slot + 2 * f.hN, (size_t)f.Nu, s));
     DNS_HIP(hipStreamSynchronize(s));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_get_feedback_state(dns_imex *st, double *hx, double *f_last,
-                                double *u_c) {
-    return dns::guarded([&]() -> int { return dns_imex_get_feedback_state_impl(st, hx, f_last, u_c); });
-}
-
-static int dns_imex_set_feedback_table_impl(dns_imex *st, int32_t nsteps,
-                                            const double *drift) {
+int dns_imex_set_feedback_table(dns_imex *st, int32_t nsteps,
+                                const double *drift) try {
     DNS_TRY(fb_need(st));
     if (nsteps < 1) return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     dns_imex::Feedback &f = st->fb;
@@ -391,44 +372,29 @@ static int dns_imex_set_feedback_table_impl(dns_imex *st, int32_t nsteps,
     f.has_drift = drift != nullptr;
     f.rows = nsteps;
     return st->rewind_tables();
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_set_feedback_table(dns_imex *st, int32_t nsteps,
-                                const double *drift) {
-    return dns::guarded([&]() -> int { return dns_imex_set_feedback_table_impl(st, nsteps, drift); });
-}
-
-static int dns_imex_get_feedback_log_impl(dns_imex *st, int32_t first,
-                                          int32_t count, double *y, double *u) {
+int dns_imex_get_feedback_log(dns_imex *st, int32_t first, int32_t count,
+                              double *y, double *u) try {
     DNS_TRY(fb_need(st));
     const dns_imex::Feedback &f = st->fb;
     DNS_TRY(download_log_rows(st, y, f.ylog.p, first, count, (size_t)f.Ny,
                               f.rows, "log rows", "table"));
     return download_log_rows(st, u, f.ulog.p, first, count, (size_t)f.Nu,
                              f.rows, "log rows", "table");
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_get_feedback_log(dns_imex *st, int32_t first, int32_t count,
-                              double *y, double *u) {
-    return dns::guarded([&]() -> int { return dns_imex_get_feedback_log_impl(st, first, count, y, u); });
-}
-
-static int dns_imex_clear_feedback_impl(dns_imex *st) {
+int dns_imex_clear_feedback(dns_imex *st) try {
     DNS_TRY(quiesce(st));
     st->fb.on = false;
     st->fb.rows = 0;
     return DNS_OK;
-}
-
-int dns_imex_clear_feedback(dns_imex *st) {
-    return dns::guarded([&]() -> int { return dns_imex_clear_feedback_impl(st); });
-}
+} DNS_CAPI_CATCH
 
 // ---- trajectory recorder (record.hpp) --------------------------------------
 
-static int dns_imex_set_recorder_impl(dns_imex *st, const dns_csr *cmat,
-                                      int32_t nrows, const int32_t *snap_slot,
-                                      int32_t nslots) {
+int dns_imex_set_recorder(dns_imex *st, const dns_csr *cmat, int32_t nrows,
+                          const int32_t *snap_slot, int32_t nslots) try {
     if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
     DNS_TRY(st->refuse_partitioned("recorder", kRecPartitioned));
@@ -508,19 +474,14 @@ static int dns_imex_set_recorder_impl(dns_imex *st, const dns_csr *cmat,
     }
     st->rec = std::move(r);
     return st->rewind_tables();
-}
-
-int dns_imex_set_recorder(dns_imex *st, const dns_csr *cmat, int32_t nrows,
-                          const int32_t *snap_slot, int32_t nslots) {
-    return dns::guarded([&]() -> int { return dns_imex_set_recorder_impl(st, cmat, nrows, snap_slot, nslots); });
-}
+} DNS_CAPI_CATCH
 
 static int rec_need(dns_imex *st) {
     return need(st, st && st->rec, "recorder is", "dns_imex_set_recorder");
 }
 
-static int dns_imex_get_record_outputs_impl(dns_imex *st, int32_t first,
-                                            int32_t count, double *y) {
+int dns_imex_get_record_outputs(dns_imex *st, int32_t first, int32_t count,
+                                double *y) try {
     DNS_TRY(rec_need(st));
     const dns_imex::Recorder &r = *st->rec;
     if (r.Ny < 1)
@@ -528,16 +489,10 @@ static int dns_imex_get_record_outputs_impl(dns_imex *st, int32_t first,
     if (!y) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     return download_log_rows(st, y, r.ylog.p, first, count, (size_t)r.Ny,
                              r.rows, "output rows", "recorder");
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_get_record_outputs(dns_imex *st, int32_t first, int32_t count,
-                                double *y) {
-    return dns::guarded([&]() -> int { return dns_imex_get_record_outputs_impl(st, first, count, y); });
-}
-
-static int dns_imex_get_record_snapshots_impl(dns_imex *st, int32_t first_slot,
-                                              int32_t count, double *v,
-                                              double *p) {
+int dns_imex_get_record_snapshots(dns_imex *st, int32_t first_slot,
+                                  int32_t count, double *v, double *p) try {
     DNS_TRY(rec_need(st));
     const dns_imex::Recorder &r = *st->rec;
     if (r.nslots < 1)
@@ -549,30 +504,22 @@ static int dns_imex_get_record_snapshots_impl(dns_imex *st, int32_t first_slot,
     return download_log_rows(st, p, r.snap.p + h->nv, first_slot, count,
                              (size_t)h->np, r.nslots, "slots", "recorder",
                              h->ld);
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_get_record_snapshots(dns_imex *st, int32_t first_slot,
-                                  int32_t count, double *v, double *p) {
-    return dns::guarded([&]() -> int { return dns_imex_get_record_snapshots_impl(st, first_slot, count, v, p); });
-}
-
-static int dns_imex_clear_recorder_impl(dns_imex *st) {
+int dns_imex_clear_recorder(dns_imex *st) try {
     DNS_TRY(quiesce(st));
     st->rec.reset();
     return DNS_OK;
-}
-
-int dns_imex_clear_recorder(dns_imex *st) {
-    return dns::guarded([&]() -> int { return dns_imex_clear_recorder_impl(st); });
-}
+} DNS_CAPI_CATCH
 
 // ---- force functionals (functional.hpp) ------------------------------------
 
-static int dns_imex_set_functionals_impl(
-    dns_imex *st, int32_t nF, const dns_csr *ca, const dns_csr *cm,
-    const dns_csr *cp, const double *c0, const double *scale,
-    const int32_t *cell_ptr, const int32_t *cell_idx, const double *cell_w,
-    double dt, int32_t nrows) {
+int dns_imex_set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
+                             const dns_csr *cm, const dns_csr *cp,
+                             const double *c0, const double *scale,
+                             const int32_t *cell_ptr, const int32_t *cell_idx,
+                             const double *cell_w, double dt,
+                             int32_t nrows) try {
     if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
     DNS_TRY(st->refuse_partitioned("functionals", kFnPartitioned));
@@ -689,18 +636,10 @@ static int dns_imex_set_functionals_impl(
     f->cellmap = ncl > 0 ? st->conv->cellmap.p : nullptr;
     st->fn = std::move(f);
     return st->rewind_tables();
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
-                             const dns_csr *cm, const dns_csr *cp,
-                             const double *c0, const double *scale,
-                             const int32_t *cell_ptr, const int32_t *cell_idx,
-                             const double *cell_w, double dt, int32_t nrows) {
-    return dns::guarded([&]() -> int { return dns_imex_set_functionals_impl(st, nF, ca, cm, cp, c0, scale, cell_ptr, cell_idx, cell_w, dt, nrows); });
-}
-
-static int dns_imex_get_functionals_impl(dns_imex *st, int32_t first,
-                                         int32_t count, double *out) {
+int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,
+                             double *out) try {
     DNS_TRY(need(st, st && st->fn, "functionals are",
                  "dns_imex_set_functionals"));
     const dns_imex::Functionals &f = *st->fn;
@@ -718,21 +657,12 @@ static int dns_imex_get_functionals_impl(dns_imex *st, int32_t first,
             out[(size_t)r * f.nF + k] = y;
         }
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,
-                             double *out) {
-    return dns::guarded([&]() -> int { return dns_imex_get_functionals_impl(st, first, count, out); });
-}
-
-static int dns_imex_clear_functionals_impl(dns_imex *st) {
+int dns_imex_clear_functionals(dns_imex *st) try {
     DNS_TRY(quiesce(st));
     st->fn.reset();
     return DNS_OK;
-}
-
-int dns_imex_clear_functionals(dns_imex *st) {
-    return dns::guarded([&]() -> int { return dns_imex_clear_functionals_impl(st); });
-}
+} DNS_CAPI_CATCH
 
 }  // extern "C"

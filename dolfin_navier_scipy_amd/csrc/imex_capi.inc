@@ -988,8 +988,9 @@ int ImexRun::finish_run(double *device_seconds, int64_t *total_iters) {
 
 extern "C" {
 
-static int dns_imex_create_impl(dns_saddle *sys, const dns_csr *r1, dns_imex **out,
-                                bool by_rows) {
+// both creates: `r1` is all of R1, or with `by_rows` this rank's rows of it
+static int build_imex(dns_saddle *sys, const dns_csr *r1, dns_imex **out,
+                      bool by_rows) {
     if (!sys || !out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     *out = nullptr;
     DNS_TRY(dns::check_csr(r1, "R1"));
@@ -1008,8 +1009,7 @@ static int dns_imex_create_impl(dns_saddle *sys, const dns_csr *r1, dns_imex **o
     } else if (r1->nrows != sys->nv || r1->ncols != sys->nv)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "R1 must be NV x NV");
     DNS_HIP(hipSetDevice(sys->device));
-    dns_imex *st = new (std::nothrow) dns_imex();
-    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    auto st = std::make_unique<dns_imex>();
     st->sys = sys;
     st->env_step_history = getenv("DNS_STEP_HISTORY") != nullptr;
     st->env_debug = getenv("DNS_DEBUG") != nullptr;
@@ -1024,57 +1024,48 @@ static int dns_imex_create_impl(dns_saddle *sys, const dns_csr *r1, dns_imex **o
         st->env_dtail = senv[0] != '0';
     if (const char *genv = getenv("DNS_STEP_GROUP"))
         st->env_group = std::max(1, atoi(genv));
-    int rc = DNS_OK;
-    auto ok = [&](int s) {
-        if (rc == DNS_OK) rc = s;
-    };
     st->r1_rows = by_rows;
     if (by_rows) {
         // (uploaded by ensure_partition, as every row block is)
         st->R1h = dns::host_embed_rows(r1, row0, sys->nv);
     } else {
-        ok(st->R1.upload(r1, sys->stream));
+        DNS_TRY(st->R1.upload(r1, sys->stream));
         st->R1h = dns::host_copy(r1);
-        if (rc == DNS_OK) ok(st->build_r1_pair(st->R1h, 0));
+        DNS_TRY(st->build_r1_pair(st->R1h, 0));
     }
-    for (int i = 0; i < 6 && rc == DNS_OK; ++i) {
-        ok(st->xs[i].alloc(sys->ld));
-        ok(st->xs[i].zero(sys->stream));
+    for (int i = 0; i < 6; ++i) {
+        DNS_TRY(st->xs[i].alloc(sys->ld));
+        DNS_TRY(st->xs[i].zero(sys->stream));
     }
-    for (int i = 0; i < 2 && rc == DNS_OK; ++i) {
-        ok(st->nfc[i].alloc((size_t)sys->nv));
-        ok(st->nfc[i].zero(sys->stream));
+    for (int i = 0; i < 2; ++i) {
+        DNS_TRY(st->nfc[i].alloc((size_t)sys->nv));
+        DNS_TRY(st->nfc[i].zero(sys->stream));
     }
-    ok(st->g.alloc((size_t)sys->nv));
-    ok(st->gp.alloc((size_t)sys->np));
-    ok(st->b.alloc(sys->ld));
-    ok(st->stepctr.alloc(1));
-    if (rc == DNS_OK) ok(st->stepctr.zero(sys->stream));
-    if (rc == DNS_OK) {
-        ok(st->g.zero(sys->stream));
-        ok(st->gp.zero(sys->stream));
-    }
-    if (rc == DNS_OK && hipEventCreate(&st->e0) != hipSuccess)
-        rc = dns::fail(DNS_ERR_HIP, "hipEventCreate failed");
-    if (rc == DNS_OK && hipEventCreate(&st->e1) != hipSuccess)
-        rc = dns::fail(DNS_ERR_HIP, "hipEventCreate failed");
-    if (rc == DNS_OK && hipStreamSynchronize(sys->stream) != hipSuccess)
-        rc = dns::fail(DNS_ERR_HIP, "stream sync failed");
-    if (rc != DNS_OK) {
-        delete st;
-        return rc;
-    }
-    *out = st;
+    DNS_TRY(st->g.alloc((size_t)sys->nv));
+    DNS_TRY(st->gp.alloc((size_t)sys->np));
+    DNS_TRY(st->b.alloc(sys->ld));
+    DNS_TRY(st->stepctr.alloc(1));
+    DNS_TRY(st->stepctr.zero(sys->stream));
+    DNS_TRY(st->g.zero(sys->stream));
+    DNS_TRY(st->gp.zero(sys->stream));
+    if (hipEventCreate(&st->e0) != hipSuccess)
+        return dns::fail(DNS_ERR_HIP, "hipEventCreate failed");
+    if (hipEventCreate(&st->e1) != hipSuccess)
+        return dns::fail(DNS_ERR_HIP, "hipEventCreate failed");
+    if (hipStreamSynchronize(sys->stream) != hipSuccess)
+        return dns::fail(DNS_ERR_HIP, "stream sync failed");
+    *out = st.release();
     return DNS_OK;
 }
 
-int dns_imex_create(dns_saddle *sys, const dns_csr *r1, dns_imex **out) {
-    return dns::guarded([&]() -> int { return dns_imex_create_impl(sys, r1, out, false); });
-}
+int dns_imex_create(dns_saddle *sys, const dns_csr *r1, dns_imex **out) try {
+    return build_imex(sys, r1, out, false);
+} DNS_CAPI_CATCH
 
-int dns_imex_create_rows(dns_saddle *sys, const dns_csr *r1_rows, dns_imex **out) {
-    return dns::guarded([&]() -> int { return dns_imex_create_impl(sys, r1_rows, out, true); });
-}
+int dns_imex_create_rows(dns_saddle *sys, const dns_csr *r1_rows,
+                         dns_imex **out) try {
+    return build_imex(sys, r1_rows, out, true);
+} DNS_CAPI_CATCH
 
 void dns_imex_destroy(dns_imex *st) {
     if (!st) return;
@@ -1083,9 +1074,9 @@ void dns_imex_destroy(dns_imex *st) {
     delete st;
 }
 
-static int dns_imex_set_state_impl(dns_imex *st, const double *v_c, const double *v_p,
+int dns_imex_set_state(dns_imex *st, const double *v_c, const double *v_p,
                        const double *ptilde_c, const double *nfc_c,
-                       const double *nfc_o) {
+                       const double *nfc_o) try {
     if (!st || !v_c) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -1119,15 +1110,10 @@ static int dns_imex_set_state_impl(dns_imex *st, const double *v_c, const double
         DNS_TRY(st->nfc[1].zero(s));
     DNS_HIP(hipStreamSynchronize(s));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_set_state(dns_imex *st, const double *v_c, const double *v_p,
-                       const double *ptilde_c, const double *nfc_c,
-                       const double *nfc_o) {
-    return dns::guarded([&]() -> int { return dns_imex_set_state_impl(st, v_c, v_p, ptilde_c, nfc_c, nfc_o); });
-}
-
-static int dns_imex_set_rhs_impl(dns_imex *st, const double *gvec, const double *rhs_p) {
+int dns_imex_set_rhs(dns_imex *st, const double *gvec,
+                     const double *rhs_p) try {
     if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -1137,14 +1123,10 @@ static int dns_imex_set_rhs_impl(dns_imex *st, const double *gvec, const double 
     st->tab_rows = 0;                 // constant vectors from here on
     st->tab_v = st->tab_p = false;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_set_rhs(dns_imex *st, const double *gvec, const double *rhs_p) {
-    return dns::guarded([&]() -> int { return dns_imex_set_rhs_impl(st, gvec, rhs_p); });
-}
-
-static int dns_imex_set_rhs_table_impl(dns_imex *st, int32_t nsteps, const double *gv,
-                           const double *gp) {
+int dns_imex_set_rhs_table(dns_imex *st, int32_t nsteps, const double *gv,
+                           const double *gp) try {
     if (!st || nsteps < 1 || (!gv && !gp))
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     dns_saddle *h = st->sys;
@@ -1163,27 +1145,18 @@ static int dns_imex_set_rhs_table_impl(dns_imex *st, int32_t nsteps, const doubl
     st->tab_p = gp != nullptr;
     st->tab_rows = nsteps;
     return st->rewind_tables();
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_set_rhs_table(dns_imex *st, int32_t nsteps, const double *gv,
-                           const double *gp) {
-    return dns::guarded([&]() -> int { return dns_imex_set_rhs_table_impl(st, nsteps, gv, gp); });
-}
-
-static int dns_imex_table_position_impl(dns_imex *st, int32_t *pos, int32_t *left) {
+int dns_imex_table_position(dns_imex *st, int32_t *pos, int32_t *left) try {
     if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     if (pos) *pos = st->tab_pos;
     if (left) *left = st->tables() ? st->rows_left() : -1;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_table_position(dns_imex *st, int32_t *pos, int32_t *left) {
-    return dns::guarded([&]() -> int { return dns_imex_table_position_impl(st, pos, left); });
-}
-
-static int dns_imex_step_impl(dns_imex *st, const double *nfc_new,
+int dns_imex_step(dns_imex *st, const double *nfc_new,
                   const dns_imex_coeffs *cf, const dns_solve_opts *opts,
-                  dns_solve_stats *stats) {
+                  dns_solve_stats *stats) try {
     if (!st || !cf) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -1221,17 +1194,11 @@ static int dns_imex_step_impl(dns_imex *st, const double *nfc_new,
     DNS_TRY(st->launch_closing_nodes(h->stream));       // the row of this step
     DNS_HIP(hipStreamSynchronize(h->stream));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_step(dns_imex *st, const double *nfc_new,
-                  const dns_imex_coeffs *cf, const dns_solve_opts *opts,
-                  dns_solve_stats *stats) {
-    return dns::guarded([&]() -> int { return dns_imex_step_impl(st, nfc_new, cf, opts, stats); });
-}
-
-static int dns_imex_run_impl(dns_imex *st, int32_t nsteps, const dns_imex_coeffs *cf,
+int dns_imex_run(dns_imex *st, int32_t nsteps, const dns_imex_coeffs *cf,
                  const dns_solve_opts *opts, dns_solve_stats *last_stats,
-                 double *device_seconds, int64_t *total_iters) {
+                 double *device_seconds, int64_t *total_iters) try {
     if (!st || !cf || nsteps < 0)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     dns_saddle *h = st->sys;
@@ -1285,53 +1252,34 @@ static int dns_imex_run_impl(dns_imex *st, int32_t nsteps, const dns_imex_coeffs
     st->run_captures = (int)(h->graph_captures - captures0);
     if (rc != DNS_OK && rc != DNS_NOT_CONVERGED) return rc;
     return r.finish_run(device_seconds, total_iters);
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_run(dns_imex *st, int32_t nsteps, const dns_imex_coeffs *cf,
-                 const dns_solve_opts *opts, dns_solve_stats *last_stats,
-                 double *device_seconds, int64_t *total_iters) {
-    return dns::guarded([&]() -> int { return dns_imex_run_impl(st, nsteps, cf, opts, last_stats, device_seconds, total_iters); });
-}
-
-static int dns_imex_step_counters_impl(dns_imex *st, int64_t *out3) {
+int dns_imex_step_counters(dns_imex *st, int64_t *out3) try {
     if (!st || !out3) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     out3[0] = st->n_steps_built;
     out3[1] = st->n_steps_tail_cells;
     out3[2] = st->n_steps_cells_reused;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_step_counters(dns_imex *st, int64_t *out3) {
-    return dns::guarded([&]() -> int { return dns_imex_step_counters_impl(st, out3); });
-}
-
-static int dns_imex_run_info_impl(dns_imex *st, int32_t *unconverged, int32_t *first_bad,
-                      int32_t *replayed, int32_t *captures) {
+int dns_imex_run_info(dns_imex *st, int32_t *unconverged, int32_t *first_bad,
+                      int32_t *replayed, int32_t *captures) try {
     if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     if (unconverged) *unconverged = st->run_unconverged;
     if (first_bad) *first_bad = st->run_first_bad;
     if (replayed) *replayed = st->run_replayed;
     if (captures) *captures = st->run_captures;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_run_info(dns_imex *st, int32_t *unconverged, int32_t *first_bad,
-                      int32_t *replayed, int32_t *captures) {
-    return dns::guarded([&]() -> int { return dns_imex_run_info_impl(st, unconverged, first_bad, replayed, captures); });
-}
-
-static int dns_imex_run_cycles_impl(dns_imex *st, int64_t *out2) {
+int dns_imex_run_cycles(dns_imex *st, int64_t *out2) try {
     if (!st || !out2) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     out2[0] = st->run_lazy_steps;
     out2[1] = st->run_eager_steps;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_run_cycles(dns_imex *st, int64_t *out2) {
-    return dns::guarded([&]() -> int { return dns_imex_run_cycles_impl(st, out2); });
-}
-
-static int dns_imex_get_state_impl(dns_imex *st, double *v, double *p) {
+int dns_imex_get_state(dns_imex *st, double *v, double *p) try {
     if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -1344,13 +1292,9 @@ static int dns_imex_get_state_impl(dns_imex *st, double *v, double *p) {
     if (p)
         for (int i = 0; i < h->np; ++i) p[i] *= st->last_pscale;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_imex_get_state(dns_imex *st, double *v, double *p) {
-    return dns::guarded([&]() -> int { return dns_imex_get_state_impl(st, v, p); });
-}
-
-static int dns_imex_vnorm_impl(dns_imex *st, double *out) {
+int dns_imex_vnorm(dns_imex *st, double *out) try {
     if (!st || !out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -1359,10 +1303,6 @@ static int dns_imex_vnorm_impl(dns_imex *st, double *out) {
     DNS_TRY(h->dot_host(h->nv, st->xs[st->cur].p, st->xs[st->cur].p, &s2));
     *out = std::sqrt(s2);
     return DNS_OK;
-}
-
-int dns_imex_vnorm(dns_imex *st, double *out) {
-    return dns::guarded([&]() -> int { return dns_imex_vnorm_impl(st, out); });
-}
+} DNS_CAPI_CATCH
 
 }  // extern "C"

@@ -58,33 +58,23 @@ struct dns_bcmap {
 
 extern "C" {
 
-static int dns_op_create_impl(int device, const dns_csr *a, dns_op **out) {
+int dns_op_create(int device, const dns_csr *a, dns_op **out) try {
     if (!out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null output handle");
     *out = nullptr;
     DNS_TRY(dns::check_csr(a, "A"));
     DNS_HIP(hipSetDevice(device));
-    dns_op *op = new (std::nothrow) dns_op();
-    if (!op) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    auto op = std::make_unique<dns_op>();
     op->device = device;
-    int rc = DNS_OK;
     if (hipStreamCreateWithFlags(&op->stream, hipStreamNonBlocking) != hipSuccess)
-        rc = dns::fail(DNS_ERR_HIP, "hipStreamCreate failed");
-    if (rc == DNS_OK) rc = op->A.upload(a, op->stream);
-    if (rc == DNS_OK) rc = op->x.alloc((size_t)std::max(1, a->ncols));
-    if (rc == DNS_OK) rc = op->y.alloc((size_t)std::max(1, a->nrows));
-    if (rc == DNS_OK && hipStreamSynchronize(op->stream) != hipSuccess)
-        rc = dns::fail(DNS_ERR_HIP, "stream sync failed");
-    if (rc != DNS_OK) {
-        delete op;
-        return rc;
-    }
-    *out = op;
+        return dns::fail(DNS_ERR_HIP, "hipStreamCreate failed");
+    DNS_TRY(op->A.upload(a, op->stream));
+    DNS_TRY(op->x.alloc((size_t)std::max(1, a->ncols)));
+    DNS_TRY(op->y.alloc((size_t)std::max(1, a->nrows)));
+    if (hipStreamSynchronize(op->stream) != hipSuccess)
+        return dns::fail(DNS_ERR_HIP, "stream sync failed");
+    *out = op.release();
     return DNS_OK;
-}
-
-int dns_op_create(int device, const dns_csr *a, dns_op **out) {
-    return dns::guarded([&]() -> int { return dns_op_create_impl(device, a, out); });
-}
+} DNS_CAPI_CATCH
 
 void dns_op_destroy(dns_op *op) {
     if (!op) return;
@@ -93,8 +83,8 @@ void dns_op_destroy(dns_op *op) {
     delete op;
 }
 
-static int dns_op_apply_impl(dns_op *op, const double *x, double *y, double alpha,
-                 double beta) {
+int dns_op_apply(dns_op *op, const double *x, double *y, double alpha,
+                 double beta) try {
     if (!op || !x || !y) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(op->device));
     const size_t nr = (size_t)op->A.nrows, nc = (size_t)op->A.ncols;
@@ -110,16 +100,11 @@ static int dns_op_apply_impl(dns_op *op, const double *x, double *y, double alph
     DNS_TRY(op->y.download(y, nr, op->stream));
     DNS_HIP(hipStreamSynchronize(op->stream));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_op_apply(dns_op *op, const double *x, double *y, double alpha,
-                 double beta) {
-    return dns::guarded([&]() -> int { return dns_op_apply_impl(op, x, y, alpha, beta); });
-}
-
-static int dns_bcmap_create_impl(int device, int32_t vdim, int32_t ninv,
+int dns_bcmap_create(int device, int32_t vdim, int32_t ninv,
                      const int32_t *invinds, int32_t nbc, const int32_t *bcinds,
-                     dns_bcmap **out) {
+                     dns_bcmap **out) try {
     if (!out || vdim < 1 || ninv < 0 || nbc < 0 || (ninv > 0 && !invinds) ||
         (nbc > 0 && !bcinds))
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
@@ -151,48 +136,32 @@ static int dns_bcmap_create_impl(int device, int32_t vdim, int32_t ninv,
     for (int i = 0; i < ninv; ++i)
         shadowed[i] = isbc[invinds[i]] || lastinv[invinds[i]] != i;
     DNS_HIP(hipSetDevice(device));
-    dns_bcmap *m = new (std::nothrow) dns_bcmap();
-    if (!m) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    auto m = std::make_unique<dns_bcmap>();
     m->device = device;
     m->vdim = vdim;
     m->ninv = ninv;
     m->nbc = nbc;
-    int rc = DNS_OK;
-    auto ok = [&](int s) {
-        if (rc == DNS_OK) rc = s;
-    };
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess)
-        rc = dns::fail(DNS_ERR_HIP, "hipStreamCreate failed");
-    ok(m->invinds.alloc((size_t)std::max(1, ninv)));
-    ok(m->bcinds.alloc((size_t)std::max(1, nbc)));
-    ok(m->last.alloc(last.size()));
-    ok(m->shadowed.alloc(shadowed.size()));
-    ok(m->covered.alloc(covered.size()));
-    ok(m->v.alloc((size_t)std::max(1, ninv)));
-    ok(m->bcvals.alloc((size_t)std::max(1, nbc)));
-    ok(m->full.alloc((size_t)vdim));
-    if (rc == DNS_OK) {
-        if (ninv > 0) ok(m->invinds.upload(invinds, (size_t)ninv, m->stream));
-        if (nbc > 0) ok(m->bcinds.upload(bcinds, (size_t)nbc, m->stream));
-        ok(m->last.upload(last.data(), last.size(), m->stream));
-        ok(m->shadowed.upload(shadowed.data(), shadowed.size(), m->stream));
-        ok(m->covered.upload(covered.data(), covered.size(), m->stream));
-    }
-    if (rc == DNS_OK && hipStreamSynchronize(m->stream) != hipSuccess)
-        rc = dns::fail(DNS_ERR_HIP, "stream sync failed");
-    if (rc != DNS_OK) {
-        delete m;
-        return rc;
-    }
-    *out = m;
+        return dns::fail(DNS_ERR_HIP, "hipStreamCreate failed");
+    DNS_TRY(m->invinds.alloc((size_t)std::max(1, ninv)));
+    DNS_TRY(m->bcinds.alloc((size_t)std::max(1, nbc)));
+    DNS_TRY(m->last.alloc(last.size()));
+    DNS_TRY(m->shadowed.alloc(shadowed.size()));
+    DNS_TRY(m->covered.alloc(covered.size()));
+    DNS_TRY(m->v.alloc((size_t)std::max(1, ninv)));
+    DNS_TRY(m->bcvals.alloc((size_t)std::max(1, nbc)));
+    DNS_TRY(m->full.alloc((size_t)vdim));
+    if (ninv > 0)
+        DNS_TRY(m->invinds.upload(invinds, (size_t)ninv, m->stream));
+    if (nbc > 0) DNS_TRY(m->bcinds.upload(bcinds, (size_t)nbc, m->stream));
+    DNS_TRY(m->last.upload(last.data(), last.size(), m->stream));
+    DNS_TRY(m->shadowed.upload(shadowed.data(), shadowed.size(), m->stream));
+    DNS_TRY(m->covered.upload(covered.data(), covered.size(), m->stream));
+    if (hipStreamSynchronize(m->stream) != hipSuccess)
+        return dns::fail(DNS_ERR_HIP, "stream sync failed");
+    *out = m.release();
     return DNS_OK;
-}
-
-int dns_bcmap_create(int device, int32_t vdim, int32_t ninv,
-                     const int32_t *invinds, int32_t nbc, const int32_t *bcinds,
-                     dns_bcmap **out) {
-    return dns::guarded([&]() -> int { return dns_bcmap_create_impl(device, vdim, ninv, invinds, nbc, bcinds, out); });
-}
+} DNS_CAPI_CATCH
 
 void dns_bcmap_destroy(dns_bcmap *m) {
     if (!m) return;
@@ -201,8 +170,8 @@ void dns_bcmap_destroy(dns_bcmap *m) {
     delete m;
 }
 
-static int dns_bc_scatter_impl(dns_bcmap *m, const double *v_inner, const double *bcvals,
-                   double *out_full) {
+int dns_bc_scatter(dns_bcmap *m, const double *v_inner, const double *bcvals,
+                   double *out_full) try {
     if (!m || !out_full || (m->ninv > 0 && !v_inner) || (m->nbc > 0 && !bcvals))
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(m->device));
@@ -220,11 +189,6 @@ static int dns_bc_scatter_impl(dns_bcmap *m, const double *v_inner, const double
     DNS_TRY(m->full.download(out_full, (size_t)m->vdim, m->stream));
     DNS_HIP(hipStreamSynchronize(m->stream));
     return DNS_OK;
-}
-
-int dns_bc_scatter(dns_bcmap *m, const double *v_inner, const double *bcvals,
-                   double *out_full) {
-    return dns::guarded([&]() -> int { return dns_bc_scatter_impl(m, v_inner, bcvals, out_full); });
-}
+} DNS_CAPI_CATCH
 
 }  // extern "C"

@@ -435,8 +435,7 @@ static int64_t host_csr_bytes(const dns::HostCsr &a) {
            8 * (int64_t)a.vals.size();
 }
 
-static int dns_saddle_host_bytes_impl(dns_saddle *h, int64_t *kept,
-                                      int64_t *setup) {
+int dns_saddle_host_bytes(dns_saddle *h, int64_t *kept, int64_t *setup) try {
     if (!h) return fail(DNS_ERR_BAD_ARGUMENT, "null handle");
     int64_t b = host_csr_bytes(h->Fh) + host_csr_bytes(h->Jh) +
                 host_csr_bytes(h->JTh) + host_csr_bytes(h->Fpc_h);
@@ -447,36 +446,15 @@ static int dns_saddle_host_bytes_impl(dns_saddle *h, int64_t *kept,
     if (kept) *kept = b;
     if (setup) *setup = h->host_setup_bytes;
     return DNS_OK;
-}
-
-int dns_saddle_host_bytes(dns_saddle *h, int64_t *kept, int64_t *setup) {
-    return dns::guarded([&]() -> int {
-        return dns_saddle_host_bytes_impl(h, kept, setup);
-    });
-}
-
-static int dns_saddle_create_rows_impl(int device, dns_comm *comm, int32_t nv,
-                                       int32_t np, const dns_csr *f_rows,
-                                       const dns_csr *jt_rows,
-                                       const dns_csr *j_rows, dns_saddle **out) {
-    if (!out) return fail(DNS_ERR_BAD_ARGUMENT, "null output handle");
-    *out = nullptr;
-    dns_saddle *h = new (std::nothrow) dns_saddle();
-    if (!h) return fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
-    const int s = h->init_rows(device, comm, nv, np, f_rows, jt_rows, j_rows);
-    if (s != DNS_OK) {
-        delete h;
-        return s;
-    }
-    *out = h;
-    return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
 int dns_saddle_create_rows(int device, dns_comm *comm, int32_t nv, int32_t np,
                            const dns_csr *f_rows, const dns_csr *jt_rows,
-                           const dns_csr *j_rows, dns_saddle **out) {
-    return dns::guarded([&]() -> int {
-        return dns_saddle_create_rows_impl(device, comm, nv, np, f_rows,
-                                           jt_rows, j_rows, out);
-    });
-}
+                           const dns_csr *j_rows, dns_saddle **out) try {
+    if (!out) return fail(DNS_ERR_BAD_ARGUMENT, "null output handle");
+    *out = nullptr;
+    auto h = std::make_unique<dns_saddle>();
+    DNS_TRY(h->init_rows(device, comm, nv, np, f_rows, jt_rows, j_rows));
+    *out = h.release();
+    return DNS_OK;
+} DNS_CAPI_CATCH

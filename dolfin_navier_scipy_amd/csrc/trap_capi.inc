@@ -117,8 +117,8 @@ int dns_trap::collect_updnorm() {
 
 extern "C" {
 
-static int dns_trap_create_impl(dns_saddle *sys, dns_conv *conv, const double *m_vals,
-                    const double *a_vals, int32_t nslots, dns_trap **out) {
+int dns_trap_create(dns_saddle *sys, dns_conv *conv, const double *m_vals,
+                    const double *a_vals, int32_t nslots, dns_trap **out) try {
     if (!sys || !conv || !m_vals || !a_vals || !out || nslots < 1)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     *out = nullptr;
@@ -133,8 +133,7 @@ static int dns_trap_create_impl(dns_saddle *sys, dns_conv *conv, const double *m
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "bind the convection operator to the pattern of the "
                          "system's F block first (dns_conv_bind_pattern)");
-    dns_trap *t = new (std::nothrow) dns_trap();
-    if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    auto t = std::make_unique<dns_trap>();
     t->sys = sys;
     t->conv = conv;
     t->nslots = nslots;
@@ -143,53 +142,38 @@ static int dns_trap_create_impl(dns_saddle *sys, dns_conv *conv, const double *m
     if (const char *ue = getenv("DNS_TRAP_UPD_RIDE"))
         t->env_upd_ride = ue[0] != '0';
     const size_t nnz = (size_t)sys->F.nnz, nv = (size_t)sys->nv;
-    int rc = DNS_OK;
-    auto ok = [&](int s) {
-        if (rc == DNS_OK) rc = s;
-    };
-    ok(t->mvals.alloc(nnz));
-    ok(t->avals.alloc(nnz));
-    ok(t->nn_vals.alloc(nnz));
-    for (int i = 0; i < 6; ++i) ok(t->xs[i].alloc(sys->ld));
-    ok(t->fv.alloc(nv));
-    ok(t->fp.alloc((size_t)std::max(1, sys->np)));
-    ok(t->fvn_n.alloc(nv));
-    ok(t->rhsbc.alloc(nv));
-    ok(t->rhscon.alloc(nv));
-    ok(t->b.alloc(sys->ld));
-    ok(t->dtmp.alloc(nv));
-    ok(t->mtmp.alloc(nv));
-    for (int w = 0; w < 2; ++w) ok(t->traj[w].alloc((size_t)nslots * nv));
-    ok(t->updnorm_dev.alloc(1));
-    if (rc == DNS_OK) {
-        ok(t->mvals.upload(m_vals, nnz, sys->stream));
-        ok(t->avals.upload(a_vals, nnz, sys->stream));
-        ok(t->fv.zero(sys->stream));
-        ok(t->fp.zero(sys->stream));
-        for (int w = 0; w < 2; ++w) ok(t->traj[w].zero(sys->stream));
-        ok(t->updnorm_dev.zero(sys->stream));
+    DNS_TRY(t->mvals.alloc(nnz));
+    DNS_TRY(t->avals.alloc(nnz));
+    DNS_TRY(t->nn_vals.alloc(nnz));
+    for (int i = 0; i < 6; ++i) DNS_TRY(t->xs[i].alloc(sys->ld));
+    DNS_TRY(t->fv.alloc(nv));
+    DNS_TRY(t->fp.alloc((size_t)std::max(1, sys->np)));
+    DNS_TRY(t->fvn_n.alloc(nv));
+    DNS_TRY(t->rhsbc.alloc(nv));
+    DNS_TRY(t->rhscon.alloc(nv));
+    DNS_TRY(t->b.alloc(sys->ld));
+    DNS_TRY(t->dtmp.alloc(nv));
+    DNS_TRY(t->mtmp.alloc(nv));
+    for (int w = 0; w < 2; ++w)
+        DNS_TRY(t->traj[w].alloc((size_t)nslots * nv));
+    DNS_TRY(t->updnorm_dev.alloc(1));
+    DNS_TRY(t->mvals.upload(m_vals, nnz, sys->stream));
+    DNS_TRY(t->avals.upload(a_vals, nnz, sys->stream));
+    DNS_TRY(t->fv.zero(sys->stream));
+    DNS_TRY(t->fp.zero(sys->stream));
+    for (int w = 0; w < 2; ++w) DNS_TRY(t->traj[w].zero(sys->stream));
+    DNS_TRY(t->updnorm_dev.zero(sys->stream));
+    if (!sys->dist_sliced) {
+        DNS_TRY(t->kpos.alloc(nnz));
+        hipLaunchKernelGGL(dns::k_trap_kpos, dns::grid_for_rows(sys->nv, 8),
+                           dns::kBlock, 0, sys->stream, sys->nv,
+                           sys->F.rowptr.p, sys->K.rowptr.p, t->kpos.p);
     }
-    if (rc == DNS_OK && !sys->dist_sliced) {
-        ok(t->kpos.alloc(nnz));
-        if (rc == DNS_OK)
-            hipLaunchKernelGGL(dns::k_trap_kpos, dns::grid_for_rows(sys->nv, 8),
-                               dns::kBlock, 0, sys->stream, sys->nv,
-                               sys->F.rowptr.p, sys->K.rowptr.p, t->kpos.p);
-    }
-    if (rc == DNS_OK && hipStreamSynchronize(sys->stream) != hipSuccess)
-        rc = dns::fail(DNS_ERR_HIP, "stream sync failed");
-    if (rc != DNS_OK) {
-        delete t;
-        return rc;
-    }
-    *out = t;
+    if (hipStreamSynchronize(sys->stream) != hipSuccess)
+        return dns::fail(DNS_ERR_HIP, "stream sync failed");
+    *out = t.release();
     return DNS_OK;
-}
-
-int dns_trap_create(dns_saddle *sys, dns_conv *conv, const double *m_vals,
-                    const double *a_vals, int32_t nslots, dns_trap **out) {
-    return dns::guarded([&]() -> int { return dns_trap_create_impl(sys, conv, m_vals, a_vals, nslots, out); });
-}
+} DNS_CAPI_CATCH
 
 void dns_trap_destroy(dns_trap *t) {
     if (!t) return;
@@ -214,8 +198,8 @@ void dns_trap_destroy(dns_trap *t) {
 // dns_trap_traj_export_wait) on the copy stream, behind everything the
 // solver's stream has been given so far.  Returns at once; the solver's stream goes on with the
 // next sweep and only waits if it is about to overwrite traj[which].
-static int dns_trap_traj_export_async_impl(dns_trap *t, int32_t which, int32_t slot0,
-                               int32_t count, double *host) {
+int dns_trap_traj_export_async(dns_trap *t, int32_t which, int32_t slot0,
+                               int32_t count, double *host) try {
     if (!t || !host || which < 0 || which > 1 || slot0 < 0 || count < 1 ||
         slot0 + count > t->nslots)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
@@ -250,15 +234,10 @@ static int dns_trap_traj_export_async_impl(dns_trap *t, int32_t which, int32_t s
     DNS_HIP(hipEventRecord(e.done[which], e.cstream));
     e.pending[which] = true;
     return DNS_OK;
-}
-
-int dns_trap_traj_export_async(dns_trap *t, int32_t which, int32_t slot0,
-                               int32_t count, double *host) {
-    return dns::guarded([&]() -> int { return dns_trap_traj_export_async_impl(t, which, slot0, count, host); });
-}
+} DNS_CAPI_CATCH
 
 // blocks until every queued export has arrived (any host thread may call it)
-static int dns_trap_traj_export_wait_impl(dns_trap *t) {
+int dns_trap_traj_export_wait(dns_trap *t) try {
     if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(t->sys->device));
     std::lock_guard<std::mutex> lock(t->exp_.mu);
@@ -271,13 +250,9 @@ static int dns_trap_traj_export_wait_impl(dns_trap *t) {
     e.jobs.clear();
     e.pending[0] = e.pending[1] = false;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_trap_traj_export_wait(dns_trap *t) {
-    return dns::guarded([&]() -> int { return dns_trap_traj_export_wait_impl(t); });
-}
-
-static int dns_trap_set_rhs_impl(dns_trap *t, const double *fv, const double *fp) {
+int dns_trap_set_rhs(dns_trap *t, const double *fv, const double *fp) try {
     if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = t->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -291,14 +266,10 @@ static int dns_trap_set_rhs_impl(dns_trap *t, const double *fv, const double *fp
         DNS_TRY(t->fp.zero(h->stream));
     DNS_HIP(hipStreamSynchronize(h->stream));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_trap_set_rhs(dns_trap *t, const double *fv, const double *fp) {
-    return dns::guarded([&]() -> int { return dns_trap_set_rhs_impl(t, fv, fp); });
-}
-
-static int dns_trap_traj_write_impl(dns_trap *t, int32_t which, int32_t slot,
-                        const double *v) {
+int dns_trap_traj_write(dns_trap *t, int32_t which, int32_t slot,
+                        const double *v) try {
     if (!t || !v || which < 0 || which > 1 || slot < 0 || slot >= t->nslots)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     dns_saddle *h = t->sys;
@@ -308,14 +279,10 @@ static int dns_trap_traj_write_impl(dns_trap *t, int32_t which, int32_t slot,
     DNS_TRY(dns::upload_to(t->traj[which].p + (size_t)slot * h->nv, v,
                            (size_t)h->nv, h->stream));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_trap_traj_write(dns_trap *t, int32_t which, int32_t slot,
-                        const double *v) {
-    return dns::guarded([&]() -> int { return dns_trap_traj_write_impl(t, which, slot, v); });
-}
-
-static int dns_trap_traj_read_impl(dns_trap *t, int32_t which, int32_t slot, double *v) {
+int dns_trap_traj_read(dns_trap *t, int32_t which, int32_t slot,
+                       double *v) try {
     if (!t || !v || which < 0 || which > 1 || slot < 0 || slot >= t->nslots)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     dns_saddle *h = t->sys;
@@ -325,13 +292,9 @@ static int dns_trap_traj_read_impl(dns_trap *t, int32_t which, int32_t slot, dou
     DNS_TRY(dns::download_from(v, t->traj[which].p + (size_t)slot * h->nv,
                                (size_t)h->nv, h->stream));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_trap_traj_read(dns_trap *t, int32_t which, int32_t slot, double *v) {
-    return dns::guarded([&]() -> int { return dns_trap_traj_read_impl(t, which, slot, v); });
-}
-
-static int dns_trap_start_impl(dns_trap *t, const double *iniv, int32_t newton) {
+int dns_trap_start(dns_trap *t, const double *iniv, int32_t newton) try {
     if (!t || !iniv) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = t->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -349,35 +312,24 @@ static int dns_trap_start_impl(dns_trap *t, const double *iniv, int32_t newton) 
     (void)newton;            // (N_c, f_c: taken by the first step, snu:1351,1364)
     DNS_HIP(hipStreamSynchronize(h->stream));
     return DNS_OK;
-}
-
-int dns_trap_start(dns_trap *t, const double *iniv, int32_t newton) {
-    return dns::guarded([&]() -> int { return dns_trap_start_impl(t, iniv, newton); });
-}
-
-static int dns_trap_step_impl(dns_trap *t, double dt, int32_t lin_which, int32_t lin_slot,
-                  int32_t out_slot, int32_t newton, int32_t extrapolate_x0,
-                  const dns_solve_opts *opts, dns_solve_stats *stats) {
-    if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
-    return t->step_impl(dt, lin_which, lin_slot, out_slot, newton,
-                        extrapolate_x0, opts, stats, nullptr);
-}
+} DNS_CAPI_CATCH
 
 int dns_trap_step(dns_trap *t, double dt, int32_t lin_which, int32_t lin_slot,
                   int32_t out_slot, int32_t newton, int32_t extrapolate_x0,
-                  const dns_solve_opts *opts, dns_solve_stats *stats) {
-    return dns::guarded([&]() -> int { return dns_trap_step_impl(t, dt, lin_which, lin_slot, out_slot, newton, extrapolate_x0, opts, stats); });
-}
+                  const dns_solve_opts *opts, dns_solve_stats *stats) try {
+    if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    return t->step_impl(dt, lin_which, lin_slot, out_slot, newton,
+                        extrapolate_x0, opts, stats, nullptr);
+} DNS_CAPI_CATCH
 
 // `count` pipelined steps of one step size in a row, slots slot0 ..
 // slot0 + count - 1 (linearisation point and output slot of a step are its
 // time instance, as the sweeps of the reference have it): the per-step trip
 // through the caller's language (15-20 us in Python, a fifth of a step at
 // N = 2) happens once per batch
-static int dns_trap_run_impl(dns_trap *t, double dt, int32_t lin_which,
-                             int32_t slot0, int32_t count, int32_t newton,
-                             int32_t extrapolate_x0,
-                             const dns_solve_opts *opts) {
+int dns_trap_run(dns_trap *t, double dt, int32_t lin_which, int32_t slot0,
+                 int32_t count, int32_t newton, int32_t extrapolate_x0,
+                 const dns_solve_opts *opts) try {
     if (!t || count < 0 || slot0 < 0 || slot0 + count > t->nslots)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     if (t->pipeline_c <= 0)
@@ -389,19 +341,13 @@ static int dns_trap_run_impl(dns_trap *t, double dt, int32_t lin_which,
         DNS_TRY(t->step_impl(dt, lin_which, slot0 + k, slot0 + k, newton,
                              extrapolate_x0, opts, &st, nullptr));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_trap_run(dns_trap *t, double dt, int32_t lin_which, int32_t slot0,
-                 int32_t count, int32_t newton, int32_t extrapolate_x0,
-                 const dns_solve_opts *opts) {
-    return dns::guarded([&]() -> int { return dns_trap_run_impl(t, dt, lin_which, slot0, count, newton, extrapolate_x0, opts); });
-}
-
-static int dns_trap_step_fb_impl(dns_trap *t, double dt, int32_t lin_which,
+int dns_trap_step_fb(dns_trap *t, double dt, int32_t lin_which,
                      int32_t lin_slot, int32_t out_slot, int32_t newton,
                      int32_t extrapolate_x0, const dns_solve_opts *opts,
                      dns_solve_stats *stats, int32_t r, const double *umat,
-                     const double *vmat_c, const double *vmat_n) {
+                     const double *vmat_c, const double *vmat_n) try {
     if (!t || r < 1 || r > 64 || !umat || !vmat_n)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     if (t->pipeline_c > 0)
@@ -410,18 +356,10 @@ static int dns_trap_step_fb_impl(dns_trap *t, double dt, int32_t lin_which,
     const dns_trap::Feedback fb = {r, umat, vmat_c, vmat_n};
     return t->step_impl(dt, lin_which, lin_slot, out_slot, newton,
                         extrapolate_x0, opts, stats, &fb);
-}
+} DNS_CAPI_CATCH
 
-int dns_trap_step_fb(dns_trap *t, double dt, int32_t lin_which,
-                     int32_t lin_slot, int32_t out_slot, int32_t newton,
-                     int32_t extrapolate_x0, const dns_solve_opts *opts,
-                     dns_solve_stats *stats, int32_t r, const double *umat,
-                     const double *vmat_c, const double *vmat_n) {
-    return dns::guarded([&]() -> int { return dns_trap_step_fb_impl(t, dt, lin_which, lin_slot, out_slot, newton, extrapolate_x0, opts, stats, r, umat, vmat_c, vmat_n); });
-}
-
-static int dns_trap_set_tables_impl(dns_trap *t, const double *fv_tab, const double *fp_tab,
-                        const double *mbc_tab) {
+int dns_trap_set_tables(dns_trap *t, const double *fv_tab, const double *fp_tab,
+                        const double *mbc_tab) try {
     if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = t->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -445,12 +383,7 @@ static int dns_trap_set_tables_impl(dns_trap *t, const double *fv_tab, const dou
     }
     DNS_HIP(hipStreamSynchronize(h->stream));
     return DNS_OK;
-}
-
-int dns_trap_set_tables(dns_trap *t, const double *fv_tab, const double *fp_tab,
-                        const double *mbc_tab) {
-    return dns::guarded([&]() -> int { return dns_trap_set_tables_impl(t, fv_tab, fp_tab, mbc_tab); });
-}
+} DNS_CAPI_CATCH
 
 }  // extern "C"
 
@@ -816,7 +749,7 @@ int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
 
 extern "C" {
 
-static int dns_trap_set_pipeline_impl(dns_trap *t, int32_t cycle_len) {
+int dns_trap_set_pipeline(dns_trap *t, int32_t cycle_len) try {
     if (!t || cycle_len < 0) return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     dns_saddle *h = t->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -825,15 +758,14 @@ static int dns_trap_set_pipeline_impl(dns_trap *t, int32_t cycle_len) {
     // batch accumulators of the control block start from zero; inside a
     // pipelined batch the solves may run their whole cycle (oversolve)
     return h->set_stop_frac(cycle_len > 0 ? t->over_frac : 0.0);
-}
+} DNS_CAPI_CATCH
 
-int dns_trap_set_pipeline(dns_trap *t, int32_t cycle_len) {
-    return dns::guarded([&]() -> int { return dns_trap_set_pipeline_impl(t, cycle_len); });
-}
-
-static int dns_trap_poll_impl(dns_trap *t, int32_t *solves, int32_t *fails, int32_t *iters,
-                  int32_t *maxit, int32_t *ext_i = nullptr,
-                  double *ext_d = nullptr) {
+// both polls: the batch accumulators of the control block (and, with `ext_i`,
+// the extended ones), the update norm collected, the stop fraction re-armed
+static int read_batch_accumulators(dns_trap *t, int32_t *solves,
+                                   int32_t *fails, int32_t *iters,
+                                   int32_t *maxit, int32_t *ext_i = nullptr,
+                                   double *ext_d = nullptr) {
     if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = t->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -856,27 +788,24 @@ static int dns_trap_poll_impl(dns_trap *t, int32_t *solves, int32_t *fails, int3
 }
 
 int dns_trap_poll(dns_trap *t, int32_t *solves, int32_t *fails, int32_t *iters,
-                  int32_t *maxit) {
-    return dns::guarded([&]() -> int { return dns_trap_poll_impl(t, solves, fails, iters, maxit); });
-}
+                  int32_t *maxit) try {
+    return read_batch_accumulators(t, solves, fails, iters, maxit);
+} DNS_CAPI_CATCH
 
-int dns_trap_poll_ext(dns_trap *t, int32_t *out6, double *out2) {
-    return dns::guarded([&]() -> int {
-        if (!out6 || !out2)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
-        return dns_trap_poll_impl(t, out6, out6 + 1, out6 + 2, out6 + 3,
-                                  out6 + 4, out2);
-    });
-}
+int dns_trap_poll_ext(dns_trap *t, int32_t *out6, double *out2) try {
+    if (!out6 || !out2) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    return read_batch_accumulators(t, out6, out6 + 1, out6 + 2, out6 + 3,
+                                   out6 + 4, out2);
+} DNS_CAPI_CATCH
 
-int dns_trap_set_oversolve(dns_trap *t, double stop_frac) {
+int dns_trap_set_oversolve(dns_trap *t, double stop_frac) try {
     if (!t || !(stop_frac >= 0.0) || stop_frac > 1.0)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     t->over_frac = stop_frac;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-static int dns_trap_checkpoint_impl(dns_trap *t) {
+int dns_trap_checkpoint(dns_trap *t) try {
     if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = t->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -894,13 +823,9 @@ static int dns_trap_checkpoint_impl(dns_trap *t) {
     t->ckh.last_dt = t->last_dt;
     t->ckh.updnorm = t->updnorm;
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_trap_checkpoint(dns_trap *t) {
-    return dns::guarded([&]() -> int { return dns_trap_checkpoint_impl(t); });
-}
-
-static int dns_trap_restore_impl(dns_trap *t, int32_t newton) {
+int dns_trap_restore(dns_trap *t, int32_t newton) try {
     if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     if (!t->ckh.valid)
         return dns::fail(DNS_ERR_NOT_READY, "no checkpoint to restore");
@@ -924,13 +849,9 @@ static int dns_trap_restore_impl(dns_trap *t, int32_t newton) {
     (void)newton;
     DNS_HIP(hipStreamSynchronize(h->stream));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_trap_restore(dns_trap *t, int32_t newton) {
-    return dns::guarded([&]() -> int { return dns_trap_restore_impl(t, newton); });
-}
-
-static int dns_trap_get_state_impl(dns_trap *t, double *v, double *p) {
+int dns_trap_get_state(dns_trap *t, double *v, double *p) try {
     if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = t->sys;
     DNS_HIP(hipSetDevice(h->device));
@@ -945,13 +866,9 @@ static int dns_trap_get_state_impl(dns_trap *t, double *v, double *p) {
     }
     DNS_HIP(hipStreamSynchronize(h->stream));
     return DNS_OK;
-}
+} DNS_CAPI_CATCH
 
-int dns_trap_get_state(dns_trap *t, double *v, double *p) {
-    return dns::guarded([&]() -> int { return dns_trap_get_state_impl(t, v, p); });
-}
-
-static int dns_trap_update_norm_impl(dns_trap *t, double *out) {
+int dns_trap_update_norm(dns_trap *t, double *out) try {
     if (!t || !out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     *out = t->updnorm;
     dns_saddle *h = t->sys;
@@ -964,10 +881,6 @@ static int dns_trap_update_norm_impl(dns_trap *t, double *out) {
         *out = v;
     }
     return DNS_OK;
-}
-
-int dns_trap_update_norm(dns_trap *t, double *out) {
-    return dns::guarded([&]() -> int { return dns_trap_update_norm_impl(t, out); });
-}
+} DNS_CAPI_CATCH
 
 }  // extern "C"

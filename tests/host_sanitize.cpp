@@ -2,9 +2,10 @@
 // hostcsr.hpp (SpGEMM, polynomial rows, transposes, slices), pair_host.hpp
 // (pair-format builder), halo_host.hpp (partition, halo index lists),
 // mg_host.hpp (multigrid level operators, damping, halo lists),
-// batch_policy.hpp (cycle and batch length of the pipelined batches) and
+// batch_policy.hpp (cycle and batch length of the pipelined batches),
 // ring.hpp (solution ring and warm-start coefficients of the resident time
-// steppers) are compiled as they are with
+// steppers) and status.hpp (the exception barrier of the C-ABI) are compiled
+// as they are with
 //     g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover
 // and driven over a small saddle-point system with the structure of the
 // package's matrices (2x2 velocity node blocks, pressure rows on node
@@ -18,7 +19,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <mutex>
+#include <new>
+#include <stdexcept>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -28,6 +33,7 @@
 #include "../dolfin_navier_scipy_amd/csrc/mg_host.hpp"
 #include "../dolfin_navier_scipy_amd/csrc/pair_host.hpp"
 #include "../dolfin_navier_scipy_amd/csrc/ring.hpp"
+#include "../dolfin_navier_scipy_amd/csrc/status.hpp"
 
 using dns::HostCsr;
 
@@ -951,7 +957,100 @@ static void test_extrap_coeffs() {
         }
 }
 
+// ---- the exception barrier (status.hpp) ----
+// local functions written exactly like an export: a function-try-block with
+// the body in place, closed by the macro
+
+static int g_exits = 0;   // ScopeExit bodies that have run
+static int g_live = 0;    // Counted objects alive
+
+struct Counted {
+    Counted() { ++g_live; }
+    ~Counted() { --g_live; }
+    std::vector<double> payload = std::vector<double>(64, 1.0);
+};
+
+extern "C" {
+
+int barrier_throws(int what) try {
+    dns::ScopeExit leave([] { ++g_exits; });
+    if (what == 0) throw std::bad_alloc();
+    if (what == 1) throw std::runtime_error("boom");
+    if (what == 2) throw 5;
+    if (what == 3) return (int)std::vector<int>(2).at(7);
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+static int refuses() { return dns::fail(DNS_ERR_NOT_READY, "not set up"); }
+
+int barrier_passes_status(int *after) try {
+    dns::ScopeExit leave([] { ++g_exits; });
+    DNS_TRY(refuses());
+    *after = 1;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// a create function: the handle is owned until it is handed out
+int barrier_create(int fail_how, Counted **out) try {
+    if (!out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null output handle");
+    *out = nullptr;
+    auto h = std::make_unique<Counted>();
+    if (fail_how == 1) throw std::runtime_error("set-up thread failed");
+    if (fail_how == 2) DNS_TRY(refuses());
+    *out = h.release();
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+}  // extern "C"
+
+static void test_barrier() {
+    // (dns::g_last_error is the string dns_last_error() hands out; the export
+    // itself lives in the HIP translation unit and cannot be linked here)
+    const struct {
+        int what;
+        const char *msg;
+        bool whole;
+    } throwers[] = {{0, "out of host memory", true},
+                    {1, "boom", false},
+                    {2, "host-side exception", true}};
+    for (const auto &c : throwers) {
+        dns::g_last_error.clear();
+        g_exits = 0;
+        CHECK(barrier_throws(c.what) == DNS_ERR_HOST);
+        CHECK(g_exits == 1);
+        if (c.whole)
+            CHECK(dns::g_last_error == c.msg);
+        else
+            CHECK(dns::g_last_error.find(c.msg) != std::string::npos);
+    }
+    // a library exception (std::out_of_range) by its what()
+    CHECK(barrier_throws(3) == DNS_ERR_HOST);
+    CHECK(dns::g_last_error.find("host-side exception: ") == 0);
+    g_exits = 0;
+    CHECK(barrier_throws(4) == DNS_OK && g_exits == 1);
+    // a failing status passes through unchanged, with its own message, and
+    // the ScopeExit has run by the time it is returned
+    int after = 0;
+    g_exits = 0;
+    CHECK(barrier_passes_status(&after) == DNS_ERR_NOT_READY);
+    CHECK(after == 0 && g_exits == 1);
+    CHECK(dns::g_last_error == "not set up");
+    // an owned handle: freed on an exception and on a status, handed out once
+    Counted *h = reinterpret_cast<Counted *>(&after);
+    CHECK(barrier_create(1, &h) == DNS_ERR_HOST && h == nullptr);
+    CHECK(g_live == 0);
+    CHECK(dns::g_last_error.find("set-up thread failed") != std::string::npos);
+    h = reinterpret_cast<Counted *>(&after);
+    CHECK(barrier_create(2, &h) == DNS_ERR_NOT_READY && h == nullptr);
+    CHECK(g_live == 0);
+    CHECK(barrier_create(0, &h) == DNS_OK && h != nullptr && g_live == 1);
+    delete h;
+    CHECK(g_live == 0);
+    CHECK(barrier_create(0, nullptr) == DNS_ERR_BAD_ARGUMENT);
+}
+
 int main() {
+    test_barrier();
     test_ring();
     test_extrap_coeffs();
     test_batch_policy();

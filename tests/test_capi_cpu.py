@@ -219,3 +219,79 @@ def test_every_host_copy_goes_through_common_hpp():
                 line = code.count('\n', 0, m.start()) + 1
                 bad.append('%s:%d: %s' % (name, line, ' '.join(call.split())))
     assert not bad, '\n'.join(bad)
+
+
+def _csrc_code():
+    """{file name: text without comments} of every source file of the library"""
+    csrc = os.path.join(ROOT, 'dolfin_navier_scipy_amd', 'csrc')
+    return {f: re.sub(r'//[^\n]*|/\*.*?\*/', ' ',
+                      open(os.path.join(csrc, f)).read(), flags=re.S)
+            for f in sorted(os.listdir(csrc))
+            if f.endswith(('.hip', '.inc', '.hpp'))}
+
+
+def test_every_status_export_is_an_exception_barrier():
+    """`DNS_ERR_HOST`: no C++ exception crosses the boundary.  Every export
+    that returns a status is a function-try-block closed by DNS_CAPI_CATCH
+    (status.hpp), with its body in place: no `_impl` twin behind a forwarding
+    wrapper, no `dns::guarded` lambda"""
+    import ctypes as ct
+    from dolfin_navier_scipy_amd import _capi
+    code = _csrc_code()
+    assert len(code) > 10
+    names = [n for n, (restype, _) in _capi.SIGNATURES.items()
+             if restype is ct.c_int and n != 'dns_version']
+    assert len(names) > 90
+    bad = []
+    for name in names:
+        found = [(f, m) for f, text in code.items()
+                 for m in re.finditer(r'^int %s\(' % name, text, flags=re.M)]
+        if len(found) != 1:
+            bad.append('%s: %d definitions' % (name, len(found)))
+            continue
+        f, m = found[0]
+        text = code[f]
+        brace = text.index('{', m.start())
+        if not re.search(r'\)\s*try\s*$', text[m.start():brace]):
+            bad.append('%s (%s): no function-try-block' % (name, f))
+            continue
+        # the body ends at the first brace in column 0
+        close = re.compile(r'^\}.*$', flags=re.M).search(text, brace)
+        if close.group(0).split() != ['}', 'DNS_CAPI_CATCH']:
+            bad.append('%s (%s): closed by %r' % (name, f, close.group(0)))
+    for f, text in code.items():
+        for m in re.finditer(r'\bdns_\w+_impl\b|\bdns::guarded\b|'
+                             r'\bint guarded\s*\(', text):
+            bad.append('%s:%d: %s' % (f, text.count('\n', 0, m.start()) + 1,
+                                      m.group(0)))
+    assert not bad, '\n'.join(bad)
+
+
+def test_create_functions_own_their_handle():
+    """A handle is held in a `std::unique_ptr` from `std::make_unique` until it
+    is released into `*out`: an exception on the way (it arrives as
+    DNS_ERR_HOST) does not leak it.  No raw `new` of a handle type is left
+    where the create functions live"""
+    code = _csrc_code()
+    handles = ('dns_saddle', 'dns_imex', 'dns_trap', 'dns_conv', 'dns_conv_mat',
+               'dns_op', 'dns_bcmap', 'dns_comm')
+    files = [f for f in code if f.endswith('_capi.inc')] \
+        + ['rank_local.inc', 'dns_amd.hip']
+    assert len(files) == 7
+    bad, made = [], set()
+    for f in files:
+        text = code[f]
+        for m in re.finditer(r'\bnew\b\s*(\(\s*std::nothrow\s*\))?\s*([\w:]+)',
+                             text):
+            if m.group(2) in handles + ('T',):
+                bad.append('%s:%d: %s' % (f, text.count('\n', 0, m.start()) + 1,
+                                          m.group(0)))
+        made.update(re.findall(r'std::make_unique<(\w+)>\(\)', text))
+        # inside a create function: no `new` at all
+        for m in re.finditer(r'^(?:static )?int (\w*create\w*)\(', text,
+                             flags=re.M):
+            end = re.compile(r'^\}', flags=re.M).search(text, m.end()).start()
+            if re.search(r'\bnew\b', text[m.end():end]):
+                bad.append('%s: new in %s' % (f, m.group(1)))
+    assert not bad, '\n'.join(bad)
+    assert made == set(handles), made

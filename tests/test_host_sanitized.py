@@ -3,7 +3,8 @@
 index lists (`halo_host.hpp`), the multigrid level operators, whole and by rows
 (`mg_host.hpp`), the policy of the pipelined batches
 (`batch_policy.hpp`), the solution ring and warm-start coefficients of the
-time steppers (`ring.hpp`) -- compiled WITHOUT HIP under AddressSanitizer +
+time steppers (`ring.hpp`), the exception barrier of the C-ABI with an owned
+handle behind it (`status.hpp`) -- compiled WITHOUT HIP under AddressSanitizer +
 UndefinedBehaviorSanitizer and driven over a small saddle system, whole and in
 row blocks of 1..4 ranks, the policy over a table of batches and the ring and
 coefficients over tables of their own (`tests/host_sanitize.cpp`).  CPU only: GPU sanitizer
