@@ -193,6 +193,17 @@ SIGNATURES = {
                                             ct.POINTER(dns_csr), c_double_p, c_double_p,
                                             c_int32_p, c_int32_p, c_double_p,
                                             ct.c_double, ct.c_int32]),
+    'dns_imex_set_functionals_bc': (ct.c_int, [_VP, ct.c_int32,
+                                               ct.POINTER(dns_csr),
+                                               ct.POINTER(dns_csr),
+                                               ct.POINTER(dns_csr),
+                                               ct.POINTER(dns_csr),
+                                               ct.POINTER(dns_csr),
+                                               c_double_p, c_double_p,
+                                               c_int32_p, c_int32_p,
+                                               c_double_p, ct.c_double,
+                                               ct.c_int32, ct.c_int32,
+                                               c_double_p]),
     'dns_imex_get_functionals': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
                                             c_double_p]),
     'dns_imex_clear_functionals': (ct.c_int, [_VP]),

@@ -158,17 +158,23 @@ struct dns_imex : dns::Ring {
     // force functionals (functional.hpp): k_functional_step runs in front of
     // every step (behind k_lti_step and k_record_step) and once behind the
     // last step of a call; it writes row `counter - 1` of the log, so a
-    // restored batch overwrites its own rows and the log needs no checkpoint.
+    // restored batch overwrites its own rows and the log needs no checkpoint
+    // (with moving Dirichlet values the counter selects their table rows too).
     // Present = on.
     struct Functionals {
         int nF = 0, G = 1, rows = 0;
         int ncl = 0;               // listed cells (all functionals)
         double dt = 1.0;
-        dns::DevBuf<int> rp, ci;   // the 3 nF sparse rows (k, term)
-        dns::DevBuf<double> va;
+        dns::DevBuf<int> rp, ci;   // the 3 nF (moving: 5 nF) sparse rows
+        dns::DevBuf<double> va;    // (k, term)
         dns::DevBuf<int> cptr, cidx;
         dns::DevBuf<double> cw, scale, c0;
         dns::DevBuf<double> log;   // rows x G x nF
+        // moving Dirichlet values (dns_imex_set_functionals_bc): the table of
+        // their own, (rows + 1) x ndbc; ndbc = 0: constant values
+        int ndbc = 0;
+        dns::DevBuf<double> gtab;
+        bool moving() const { return ndbc > 0; }
         // the convection operator whose cell order `cidx` refers to (a step
         // with another one attached is refused)
         const dns_conv *conv = nullptr;

@@ -38,13 +38,16 @@ int dns_imex::rec_launch(hipStream_t s) {
     return DNS_OK;
 }
 
-// "functionals on", their shape, every buffer k_functional_step is handed
+// "functionals on", their shape and instance (constant or moving Dirichlet
+// values: the table and its width), every buffer k_functional_step is handed
 // (the ring vectors come with the step key) and the pressure scale
 uint64_t dns_imex::fn_key() const {
     const Functionals &f = *fn;
-    return mix64(mix64(0xf6, {kw(f.nF), kw(f.G), kw(f.rows), kw(f.ncl),
+    uint64_t k = mix64(0xf6, {kw(f.nF), kw(f.G), kw(f.rows), kw(f.ncl),
                               kw(f.dt), kw(last_pscale), kw(f.rp.p),
-                              kw(f.ci.p), kw(f.va.p), kw(f.cptr.p)}),
+                              kw(f.ci.p), kw(f.va.p), kw(f.cptr.p)});
+    if (f.moving()) k = mix64(k, {kw(0xbc), kw(f.ndbc), kw(f.gtab.p)});
+    return mix64(k,
                  {kw(f.cidx.p), kw(f.cw.p), kw(f.scale.p), kw(f.c0.p),
                   kw(f.log.p), kw(stepctr.p), kw(conv ? conv->ncells : 0),
                   kw(conv ? conv->cellmap.p : nullptr),
@@ -65,7 +68,17 @@ int dns_imex::fn_launch(hipStream_t s) {
                         cells ? conv->area.p : (const double *)nullptr,
                         cells ? conv->dbcvals.p : (const double *)nullptr,
                         f.scale.p, f.c0.p, f.log.p};
-    hipLaunchKernelGGL(dns::k_functional_step, f.G, dns::kBlock, 0, s, a);
+    if (f.moving()) {
+        dns::FnBcArgs b;
+        static_cast<dns::FnArgs &>(b) = a;
+        b.gtab = f.gtab.p;
+        b.ndbc = f.ndbc;
+        hipLaunchKernelGGL(dns::k_functional_step<dns::FnBcArgs>, f.G,
+                           dns::kBlock, 0, s, b);
+    } else {
+        hipLaunchKernelGGL(dns::k_functional_step<dns::FnArgs>, f.G,
+                           dns::kBlock, 0, s, a);
+    }
     DNS_HIP(hipGetLastError());
     return DNS_OK;
 }
@@ -182,11 +195,19 @@ int dns_imex::check_attachments() const {
                          "functionals with cells were set with another "
                          "convection operator than the one attached now: "
                          "set them again (dns_imex_set_functionals)");
-    if (conv && conv->dbc_rows > 0)
+    if (!fn->moving() && conv && conv->dbc_rows > 0)
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "functionals with a per-step Dirichlet table on "
                          "the convection operator: the moving-boundary "
                          "terms are not part of the functional");
+    // (their table rows and the cells' Dirichlet slots are that wide)
+    if (fn->moving() && conv && conv->ndbc != fn->ndbc)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals with moving Dirichlet values were set "
+                         "for %d values, the convection operator attached "
+                         "now has %d: set them again "
+                         "(dns_imex_set_functionals_bc)", fn->ndbc,
+                         conv->ndbc);
     return DNS_OK;
 }
 
@@ -246,6 +267,157 @@ static int quiesce(dns_imex *st) {
     DNS_HIP(hipSetDevice(st->sys->device));
     DNS_HIP(hipStreamSynchronize(st->sys->stream));
     return DNS_OK;
+}
+
+// What dns_imex_set_functionals (`moving` false: constant Dirichlet values,
+// three sparse rows per functional) and dns_imex_set_functionals_bc (`moving`:
+// five rows and a table of the values, (nrows + 1) x ndbc) share: every check
+// first -- a refusal leaves the functionals that were there --, then the
+// upload.  Called inside the exports' exception barrier.
+static int set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
+                           const dns_csr *cm, const dns_csr *cp,
+                           const dns_csr *cab, const dns_csr *cmb,
+                           const double *c0, const double *scale,
+                           const int32_t *cell_ptr, const int32_t *cell_idx,
+                           const double *cell_w, double dt, int32_t nrows,
+                           int32_t ndbc, const double *dbc_table,
+                           bool moving) {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_saddle *h = st->sys;
+    DNS_TRY(st->refuse_partitioned("functionals", kFnPartitioned));
+    if (nF < 1 || nF > dns::kFnMax)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals: nF = %d outside 1..%d", (int)nF,
+                         dns::kFnMax);
+    if (nrows < 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "functionals: nrows = %d < 1",
+                         (int)nrows);
+    if (!(dt > 0.0))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "functionals: dt must be "
+                         "positive");
+    if (moving && ndbc < 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals: ndbc = %d < 1 (constant Dirichlet "
+                         "values: dns_imex_set_functionals)", (int)ndbc);
+    if (moving && !dbc_table)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals: no table of the Dirichlet values");
+    const int nterms = moving ? 5 : 3;
+    const dns_csr *terms[5] = {ca, cm, cp, cab, cmb};
+    const char *names[5] = {"ca", "cm", "cp", "cab", "cmb"};
+    for (int t = 0; t < nterms; ++t) {
+        if (!terms[t]) continue;
+        DNS_TRY(dns::check_csr(terms[t], names[t]));
+        const int want = t == 2 ? h->np : (t > 2 ? (int)ndbc : h->nv);
+        if (terms[t]->nrows != nF || terms[t]->ncols != want)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals: %s must be nF x %d, it is %d x %d",
+                             names[t], want, (int)terms[t]->nrows,
+                             (int)terms[t]->ncols);
+    }
+    const int ncl = cell_ptr ? cell_ptr[nF] : 0;
+    if (cell_ptr) {
+        if (cell_ptr[0] != 0)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals: cell_ptr[0] must be 0");
+        for (int k = 0; k < nF; ++k)
+            if (cell_ptr[k + 1] < cell_ptr[k])
+                return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                                 "functionals: cell_ptr not monotone");
+    }
+    if (ncl > 0) {
+        if (!cell_idx || !cell_w)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals: cells without cell_idx / cell_w");
+        if (!st->conv)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "functionals with cells need a device convection "
+                             "operator (dns_imex_set_convection)");
+        for (int j = 0; j < ncl; ++j)
+            if (cell_idx[j] < 0 || cell_idx[j] >= st->conv->ncells)
+                return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                                 "functionals: cell index %d at %d outside "
+                                 "0..%d (ncells of the convection operator)",
+                                 (int)cell_idx[j], j, st->conv->ncells - 1);
+    }
+    if (moving && ncl > 0 && st->conv->ndbc != ndbc)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals: ndbc = %d, the convection operator of "
+                         "the listed cells has %d Dirichlet values",
+                         (int)ndbc, st->conv->ndbc);
+    if (!moving && st->conv && st->conv->dbc_rows > 0)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "functionals with a per-step Dirichlet table on the "
+                         "convection operator (dns_conv_set_dbc_table): the "
+                         "moving-boundary terms are not part of the "
+                         "functional");
+    // the 3 nF (5 nF) sparse rows (k, term) in one CSR; a null term is an
+    // empty row
+    std::vector<int> rp((size_t)nterms * nF + 1, 0), ci;
+    std::vector<double> va;
+    for (int k = 0; k < nF; ++k)
+        for (int t = 0; t < nterms; ++t) {
+            if (terms[t])
+                for (int64_t z = terms[t]->rowptr[k];
+                     z < terms[t]->rowptr[k + 1]; ++z) {
+                    ci.push_back(terms[t]->colidx[z]);
+                    va.push_back(terms[t]->vals[z]);
+                }
+            rp[(size_t)nterms * k + t + 1] = (int)ci.size();
+        }
+    std::vector<int> cptr(nF + 1, 0);
+    if (cell_ptr) cptr.assign(cell_ptr, cell_ptr + nF + 1);
+    std::vector<double> sc(nF, 1.0), cc(nF, 0.0);
+    if (scale) sc.assign(scale, scale + nF);
+    if (c0) cc.assign(c0, c0 + nF);
+    DNS_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
+    // In place (keep_or_alloc; everything was checked above: a failed
+    // allocation leaves the stepper without functionals).
+    std::unique_ptr<dns_imex::Functionals> f = std::move(st->fn);
+    if (!f) f.reset(new (std::nothrow) dns_imex::Functionals());
+    if (!f) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    const int G = dns::functional_grid(nF, ncl, nterms);
+    auto put = [&](auto &buf, const auto &host) -> int {
+        DNS_TRY(keep_or_alloc(buf, buf, host.size()));
+        if (!host.empty()) DNS_TRY(buf.upload(host.data(), host.size(), s));
+        return DNS_OK;
+    };
+    DNS_TRY(put(f->rp, rp));
+    DNS_TRY(put(f->ci, ci));
+    DNS_TRY(put(f->va, va));
+    DNS_TRY(put(f->cptr, cptr));
+    DNS_TRY(put(f->scale, sc));
+    DNS_TRY(put(f->c0, cc));
+    DNS_TRY(keep_or_alloc(f->cidx, f->cidx, (size_t)ncl));
+    DNS_TRY(keep_or_alloc(f->cw, f->cw, (size_t)12 * ncl));
+    if (ncl > 0) {
+        // (the operator keeps its cells in an order of its own)
+        std::vector<int> cint((size_t)ncl);
+        for (int j = 0; j < ncl; ++j)
+            cint[j] = st->conv->cpos_host[cell_idx[j]];
+        DNS_TRY(f->cidx.upload(cint.data(), (size_t)ncl, s));
+        DNS_TRY(f->cw.upload(cell_w, (size_t)12 * ncl, s));
+    }
+    DNS_TRY(keep_or_alloc(f->log, f->log, (size_t)nrows * G * nF));
+    DNS_TRY(f->log.zero(s));
+    if (moving) {
+        const size_t ng = ((size_t)nrows + 1) * ndbc;
+        DNS_TRY(keep_or_alloc(f->gtab, f->gtab, ng));
+        DNS_TRY(f->gtab.upload(dbc_table, ng, s));
+    }
+    f->ndbc = moving ? ndbc : 0;
+    f->nF = nF;
+    f->G = G;
+    f->rows = nrows;
+    f->ncl = ncl;
+    f->dt = dt;
+    f->conv = ncl > 0 ? st->conv : nullptr;
+    f->ncells = ncl > 0 ? st->conv->ncells : 0;
+    f->cellmap = ncl > 0 ? st->conv->cellmap.p : nullptr;
+    st->fn = std::move(f);
+    return st->rewind_tables();
 }
 
 extern "C" {
@@ -520,122 +692,21 @@ int dns_imex_set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
                              const int32_t *cell_ptr, const int32_t *cell_idx,
                              const double *cell_w, double dt,
                              int32_t nrows) try {
-    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
-    dns_saddle *h = st->sys;
-    DNS_TRY(st->refuse_partitioned("functionals", kFnPartitioned));
-    if (nF < 1 || nF > dns::kFnMax)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "functionals: nF = %d outside 1..%d", (int)nF,
-                         dns::kFnMax);
-    if (nrows < 1)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT, "functionals: nrows = %d < 1",
-                         (int)nrows);
-    if (!(dt > 0.0))
-        return dns::fail(DNS_ERR_BAD_ARGUMENT, "functionals: dt must be "
-                         "positive");
-    const dns_csr *terms[3] = {ca, cm, cp};
-    const char *names[3] = {"ca", "cm", "cp"};
-    for (int t = 0; t < 3; ++t) {
-        if (!terms[t]) continue;
-        DNS_TRY(dns::check_csr(terms[t], names[t]));
-        const int want = t == 2 ? h->np : h->nv;
-        if (terms[t]->nrows != nF || terms[t]->ncols != want)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "functionals: %s must be nF x %d, it is %d x %d",
-                             names[t], want, (int)terms[t]->nrows,
-                             (int)terms[t]->ncols);
-    }
-    const int ncl = cell_ptr ? cell_ptr[nF] : 0;
-    if (cell_ptr) {
-        if (cell_ptr[0] != 0)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "functionals: cell_ptr[0] must be 0");
-        for (int k = 0; k < nF; ++k)
-            if (cell_ptr[k + 1] < cell_ptr[k])
-                return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                                 "functionals: cell_ptr not monotone");
-    }
-    if (ncl > 0) {
-        if (!cell_idx || !cell_w)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "functionals: cells without cell_idx / cell_w");
-        if (!st->conv)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "functionals with cells need a device convection "
-                             "operator (dns_imex_set_convection)");
-        for (int j = 0; j < ncl; ++j)
-            if (cell_idx[j] < 0 || cell_idx[j] >= st->conv->ncells)
-                return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                                 "functionals: cell index %d at %d outside "
-                                 "0..%d (ncells of the convection operator)",
-                                 (int)cell_idx[j], j, st->conv->ncells - 1);
-    }
-    if (st->conv && st->conv->dbc_rows > 0)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "functionals with a per-step Dirichlet table on the "
-                         "convection operator (dns_conv_set_dbc_table): the "
-                         "moving-boundary terms are not part of the "
-                         "functional");
-    // the 3 nF sparse rows (k, term) in one CSR; a null term is an empty row
-    std::vector<int> rp(3 * (size_t)nF + 1, 0), ci;
-    std::vector<double> va;
-    for (int k = 0; k < nF; ++k)
-        for (int t = 0; t < 3; ++t) {
-            if (terms[t])
-                for (int64_t z = terms[t]->rowptr[k];
-                     z < terms[t]->rowptr[k + 1]; ++z) {
-                    ci.push_back(terms[t]->colidx[z]);
-                    va.push_back(terms[t]->vals[z]);
-                }
-            rp[3 * (size_t)k + t + 1] = (int)ci.size();
-        }
-    std::vector<int> cptr(nF + 1, 0);
-    if (cell_ptr) cptr.assign(cell_ptr, cell_ptr + nF + 1);
-    std::vector<double> sc(nF, 1.0), cc(nF, 0.0);
-    if (scale) sc.assign(scale, scale + nF);
-    if (c0) cc.assign(c0, c0 + nF);
-    DNS_HIP(hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
-    // In place (keep_or_alloc; everything was checked above: a failed
-    // allocation leaves the stepper without functionals).
-    std::unique_ptr<dns_imex::Functionals> f = std::move(st->fn);
-    if (!f) f.reset(new (std::nothrow) dns_imex::Functionals());
-    if (!f) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
-    const int G = dns::functional_grid(nF, ncl);
-    auto put = [&](auto &buf, const auto &host) -> int {
-        DNS_TRY(keep_or_alloc(buf, buf, host.size()));
-        if (!host.empty()) DNS_TRY(buf.upload(host.data(), host.size(), s));
-        return DNS_OK;
-    };
-    DNS_TRY(put(f->rp, rp));
-    DNS_TRY(put(f->ci, ci));
-    DNS_TRY(put(f->va, va));
-    DNS_TRY(put(f->cptr, cptr));
-    DNS_TRY(put(f->scale, sc));
-    DNS_TRY(put(f->c0, cc));
-    DNS_TRY(keep_or_alloc(f->cidx, f->cidx, (size_t)ncl));
-    DNS_TRY(keep_or_alloc(f->cw, f->cw, (size_t)12 * ncl));
-    if (ncl > 0) {
-        // (the operator keeps its cells in an order of its own)
-        std::vector<int> cint((size_t)ncl);
-        for (int j = 0; j < ncl; ++j)
-            cint[j] = st->conv->cpos_host[cell_idx[j]];
-        DNS_TRY(f->cidx.upload(cint.data(), (size_t)ncl, s));
-        DNS_TRY(f->cw.upload(cell_w, (size_t)12 * ncl, s));
-    }
-    DNS_TRY(keep_or_alloc(f->log, f->log, (size_t)nrows * G * nF));
-    DNS_TRY(f->log.zero(s));
-    f->nF = nF;
-    f->G = G;
-    f->rows = nrows;
-    f->ncl = ncl;
-    f->dt = dt;
-    f->conv = ncl > 0 ? st->conv : nullptr;
-    f->ncells = ncl > 0 ? st->conv->ncells : 0;
-    f->cellmap = ncl > 0 ? st->conv->cellmap.p : nullptr;
-    st->fn = std::move(f);
-    return st->rewind_tables();
+    return set_functionals(st, nF, ca, cm, cp, nullptr, nullptr, c0, scale,
+                           cell_ptr, cell_idx, cell_w, dt, nrows, 0, nullptr,
+                           false);
+} DNS_CAPI_CATCH
+
+int dns_imex_set_functionals_bc(dns_imex *st, int32_t nF, const dns_csr *ca,
+                                const dns_csr *cm, const dns_csr *cp,
+                                const dns_csr *cab, const dns_csr *cmb,
+                                const double *c0, const double *scale,
+                                const int32_t *cell_ptr,
+                                const int32_t *cell_idx, const double *cell_w,
+                                double dt, int32_t nrows, int32_t ndbc,
+                                const double *dbc_table) try {
+    return set_functionals(st, nF, ca, cm, cp, cab, cmb, c0, scale, cell_ptr,
+                           cell_idx, cell_w, dt, nrows, ndbc, dbc_table, true);
 } DNS_CAPI_CATCH
 
 int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,

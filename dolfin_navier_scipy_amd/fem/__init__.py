@@ -7,4 +7,5 @@ from .problem_setups import (get_sysmats, condense_sysmatsbybcs,
                              pressure_prolongations, DATA_DIR,
                              gen_bccont_fems, classify_boundary)
 from .functionals import (MomentumFunctionals, boundary_forces,
-                          pressure_difference, cylinder_nodes)
+                          boundary_torque, pressure_difference,
+                          cylinder_nodes)

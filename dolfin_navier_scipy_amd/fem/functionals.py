@@ -18,14 +18,29 @@ of the `M` term and enter `A` through `c0` and `N` through the cells) -- the
 form `ImexStepper.set_functionals` evaluates on the device after every step
 of a resident loop (`dns_imex_set_functionals`).  `evaluate` is the NumPy
 statement of the same sum.
+
+With Dirichlet values `g` that change from step to step (controlled
+boundaries: a rotating body, a modulated inflow; `g` in the order of
+`femp['dbcinds']`) they stay where they are in the balance:
+
+    y_k = scale_k * ( ca_k . v + cm_k . (v - v_prev)/dt + cp_k . p
+                      + cab_k . g + cmb_k . (g - g_prev)/dt
+                      + sum_{c in cells_k} sum_{sl<12} w_k[c][sl] N_loc(c; v, g)[sl]
+                      + c0b_k )
+
+with `cab`, `cmb` the Dirichlet columns of `phi^T A`, `phi^T M` and `c0b` the
+constants that are no boundary terms (zero for test vectors, the caller's for
+`from_rows`) -- `evaluate(..., dbc=g, dbc_prev=g_prev)`, on the device
+`set_functionals(..., dbc_table=)` (`dns_imex_set_functionals_bc`).  With
+constant `g` it is the first form: `cab . g` is its `c0`, the `cmb` term zero.
 """
 import numpy as np
 import scipy.sparse as sps
 
 from . import taylor_hood as thm
 
-__all__ = ['MomentumFunctionals', 'boundary_forces', 'pressure_difference',
-           'cylinder_nodes']
+__all__ = ['MomentumFunctionals', 'boundary_forces', 'boundary_torque',
+           'pressure_difference', 'cylinder_nodes']
 
 
 class MomentumFunctionals(object):
@@ -44,17 +59,24 @@ class MomentumFunctionals(object):
             if phis is not None:
                 raise ValueError('test vectors need the problem dict `femp`')
             self.inv, self.bcs, self.NV = None, None, 0
+            self.dbi = None
         else:
             self.inv = np.asarray(femp['invinds'])
             self.bcs = np.zeros(th.vdim)
             self.bcs[np.asarray(femp['dbcinds'], dtype=np.int64)] = \
                 np.asarray(femp['dbcvals'], dtype=np.float64).reshape(-1)
             self.NV = self.inv.size
+            # (the Dirichlet dofs, in the order their values come in)
+            self.dbi = np.asarray(femp['dbcinds'], dtype=np.int64)
         self.NP = th.pdim
+        self.ndbc = 0 if self.dbi is None else self.dbi.size
         self.ca = sps.csr_matrix((0, self.NV))
         self.cm = sps.csr_matrix((0, self.NV))
         self.cp = sps.csr_matrix((0, self.NP))
+        self.cab = sps.csr_matrix((0, self.ndbc))
+        self.cmb = sps.csr_matrix((0, self.ndbc))
         self.c0, self.scale = np.zeros(0), np.zeros(0)
+        self.c0b = np.zeros(0)
         self.cells, self.weights, self.names = [], [], []
         if phis is None:
             return
@@ -69,7 +91,10 @@ class MomentumFunctionals(object):
         self.ca = sps.csr_matrix(arows[:, self.inv])
         self.cm = sps.csr_matrix(mrows[:, self.inv])
         self.cp = sps.csr_matrix(-jrows)
+        self.cab = sps.csr_matrix(arows[:, self.dbi])
+        self.cmb = sps.csr_matrix(mrows[:, self.dbi])
         self.c0 = np.asarray(arows @ self.bcs).reshape(-1)
+        self.c0b = np.zeros(nF)
         self.scale = -np.ones(nF)
         vd = th._vdofs().reshape((-1, 12))        # slot = 2*node + component
         for k in range(nF):
@@ -85,7 +110,7 @@ class MomentumFunctionals(object):
         self._tidy()
 
     def _tidy(self):
-        for name in ('ca', 'cm', 'cp'):
+        for name in ('ca', 'cm', 'cp', 'cab', 'cmb'):
             mat = sps.csr_matrix(getattr(self, name))
             mat.sum_duplicates()
             mat.sort_indices()
@@ -99,6 +124,7 @@ class MomentumFunctionals(object):
         new = MomentumFunctionals.__new__(MomentumFunctionals)
         new.th, new.inv, new.bcs = self.th, self.inv, self.bcs
         new.NV, new.NP = self.NV, self.NP
+        new.dbi, new.ndbc = self.dbi, self.ndbc
         return new
 
     @classmethod
@@ -124,6 +150,10 @@ class MomentumFunctionals(object):
                     mat.shape, (nF, ncol)))
         new.c0 = np.zeros(nF) if c0 is None else \
             np.asarray(c0, dtype=np.float64).reshape(nF)
+        # (rows have no boundary terms: the constant is the caller's)
+        new.cab = sps.csr_matrix((nF, new.ndbc))
+        new.cmb = sps.csr_matrix((nF, new.ndbc))
+        new.c0b = new.c0.copy()
         new.scale = np.ones(nF) if scale is None else \
             np.asarray(scale, dtype=np.float64).reshape(nF)
         new.cells = [np.zeros(0, dtype=np.int32) for _ in range(nF)]
@@ -143,12 +173,24 @@ class MomentumFunctionals(object):
         def wide(fn, mat):      # (pressure-only rows in the velocity space)
             return mat if fn.inv is not None or new.inv is None \
                 else sps.csr_matrix((fn.nF, new.NV))
+
+        def wideb(fn, mat):
+            return mat if fn.inv is not None or new.inv is None \
+                else sps.csr_matrix((fn.nF, new.ndbc))
+        if self.inv is not None and other.inv is not None and not \
+                np.array_equal(self.dbi, other.dbi):
+            raise ValueError('functionals with different Dirichlet dofs')
         new.ca = sps.vstack([wide(self, self.ca),
                              wide(other, other.ca)]).tocsr()
         new.cm = sps.vstack([wide(self, self.cm),
                              wide(other, other.cm)]).tocsr()
         new.cp = sps.vstack([self.cp, other.cp]).tocsr()
+        new.cab = sps.vstack([wideb(self, self.cab),
+                              wideb(other, other.cab)]).tocsr()
+        new.cmb = sps.vstack([wideb(self, self.cmb),
+                              wideb(other, other.cmb)]).tocsr()
         new.c0 = np.concatenate([self.c0, other.c0])
+        new.c0b = np.concatenate([self.c0b, other.c0b])
         new.scale = np.concatenate([self.scale, other.scale])
         new.cells = list(self.cells) + list(other.cells)
         new.weights = list(self.weights) + list(other.weights)
@@ -161,6 +203,7 @@ class MomentumFunctionals(object):
         per functional): force coefficients `2 F/(Ubar^2 D)`"""
         new = self._empty_like()
         new.ca, new.cm, new.cp = self.ca, self.cm, self.cp
+        new.cab, new.cmb, new.c0b = self.cab, self.cmb, self.c0b
         new.c0, new.cells, new.weights = self.c0, self.cells, self.weights
         new.names = list(self.names)
         new.scale = self.scale*np.asarray(factors, dtype=np.float64)
@@ -171,35 +214,45 @@ class MomentumFunctionals(object):
         `-phi^T (A v + N(v) v - J^T p)`"""
         new = self.scaled(1.)
         new.cm = sps.csr_matrix(self.cm.shape)
+        new.cmb = sps.csr_matrix(self.cmb.shape)
         if names is not None:
             new.names = list(names)
         return new
 
     # -- what the device is handed ---------------------------------------
-    def device_args(self):
+    def device_args(self, moving=False):
         """`dict(ca, cm, cp, c0, scale, cell_ptr, cell_idx, cell_w)` in the
-        layout of `dns_imex_set_functionals`"""
+        layout of `dns_imex_set_functionals`; `moving`: with `cab`, `cmb`
+        (`nF x ndbc`) and the boundary-free constant for `c0`, the layout of
+        `dns_imex_set_functionals_bc`"""
         cell_ptr = np.zeros(self.nF + 1, dtype=np.int32)
         cell_ptr[1:] = np.cumsum([c.size for c in self.cells])
         cell_idx = np.concatenate(self.cells).astype(np.int32) \
             if self.nF else np.zeros(0, dtype=np.int32)
         cell_w = np.vstack(self.weights).reshape(-1) if self.nF \
             else np.zeros(0)
-        return dict(ca=self.ca, cm=self.cm, cp=self.cp,
+        args = dict(ca=self.ca, cm=self.cm, cp=self.cp,
                     c0=np.ascontiguousarray(self.c0),
                     scale=np.ascontiguousarray(self.scale),
                     cell_ptr=cell_ptr, cell_idx=cell_idx,
                     cell_w=np.ascontiguousarray(cell_w, dtype=np.float64))
+        if moving:
+            args.update(cab=self.cab, cmb=self.cmb,
+                        c0=np.ascontiguousarray(self.c0b))
+        return args
 
     # -- the NumPy statement ----------------------------------------------
-    def _cell_sums(self, v):
+    def _cell_sums(self, v, dbc=None):
         """`(N_loc, |N_loc|)` of the listed cells of every functional:
         `(k, 12)` local convection sums and the sums of the absolute values
-        of their quadrature products"""
+        of their quadrature products; `dbc`: Dirichlet values other than the
+        problem's"""
         th = self.th
         out = []
         if self.inv is not None:
             full = self.bcs.copy()
+            if dbc is not None:
+                full[self.dbi] = dbc
             full[self.inv] = v
         for cells in self.cells:
             if cells.size == 0:
@@ -217,11 +270,16 @@ class MomentumFunctionals(object):
             out.append((floc.reshape((-1, 12)), fabs.reshape((-1, 12))))
         return out
 
-    def evaluate(self, v, v_prev, p, dt, return_scale=False):
+    def evaluate(self, v, v_prev, p, dt, return_scale=False, dbc=None,
+                 dbc_prev=None):
         """`y (nF,)` for inner velocities `v`, `v_prev` and the pressure `p`;
         with `return_scale` also `T_k = |scale_k| (sum of the absolute values
         of every product + |c0_k|)`, the size rounding errors are relative
-        to (for the cells: of the products of the quadrature sums)"""
+        to (for the cells: of the products of the quadrature sums).  `dbc`,
+        `dbc_prev` (`ndbc` values in the order of `dbcinds`; `dbc_prev`
+        defaults to `dbc`): the Dirichlet values that belong to `v` and to
+        `v_prev` where they change with time -- the second form of the module
+        docstring; `T_k` then counts the products of `cab`, `cmb` too"""
         v = np.asarray(v, dtype=np.float64).reshape(-1)[:self.ca.shape[1]]
         vp = np.asarray(v_prev,
                         dtype=np.float64).reshape(-1)[:self.ca.shape[1]]
@@ -230,13 +288,30 @@ class MomentumFunctionals(object):
         lin = self.ca @ v + self.cm @ vdot + self.cp @ p
         big = abs(self.ca) @ np.abs(v) + abs(self.cm) @ np.abs(vdot) \
             + abs(self.cp) @ np.abs(p)
+        const = self.c0
+        if dbc is not None and self.inv is None:
+            const = self.c0b         # (pressure-only rows: no boundary terms)
+        elif dbc is not None:
+            g = np.asarray(dbc, dtype=np.float64).reshape(-1)
+            gp = g if dbc_prev is None else \
+                np.asarray(dbc_prev, dtype=np.float64).reshape(-1)
+            if g.size != self.ndbc or gp.size != self.ndbc:
+                raise ValueError('`dbc` must hold {0} values'.format(
+                    self.ndbc))
+            gdot = (g - gp)/dt
+            lin = lin + self.cab @ g + self.cmb @ gdot
+            big = big + abs(self.cab) @ np.abs(g) \
+                + abs(self.cmb) @ np.abs(gdot)
+            const = self.c0b
+        elif dbc_prev is not None:
+            raise ValueError('`dbc_prev` without `dbc`')
         nl, nlbig = np.zeros(self.nF), np.zeros(self.nF)
-        for k, (floc, fabs) in enumerate(self._cell_sums(v)):
+        for k, (floc, fabs) in enumerate(self._cell_sums(v, dbc)):
             nl[k] = float((self.weights[k]*floc).sum())
             nlbig[k] = float((np.abs(self.weights[k])*fabs).sum())
-        y = self.scale*(lin + nl + self.c0)
+        y = self.scale*(lin + nl + const)
         if return_scale:
-            return y, np.abs(self.scale)*(big + nlbig + np.abs(self.c0))
+            return y, np.abs(self.scale)*(big + nlbig + np.abs(const))
         return y
 
 
@@ -257,6 +332,22 @@ def boundary_forces(th, femp, nodes=None, names=('fx', 'fy')):
         (np.ones(2*n), (np.concatenate([2*nodes, 2*nodes + 1]),
                         np.repeat([0, 1], n))), shape=(th.vdim, 2))
     return MomentumFunctionals(th, femp, phis, names=names)
+
+
+def boundary_torque(th, femp, nodes=None, center=(0.2, 0.2), name='torque'):
+    """the moment about `center` the fluid exerts on `nodes` (default: the
+    cylinder of the wake meshes): `phi = (-(y - yc), x - xc)` on them -- what
+    a rotating body needs"""
+    nodes = cylinder_nodes(th) if nodes is None else \
+        np.asarray(nodes, dtype=np.int64)
+    xy = th.nodecoords[nodes]
+    n = nodes.size
+    vals = np.concatenate([-(xy[:, 1] - center[1]), xy[:, 0] - center[0]])
+    phis = sps.csc_matrix(
+        (vals, (np.concatenate([2*nodes, 2*nodes + 1]),
+                np.zeros(2*n, dtype=np.int64))),
+        shape=(th.vdim, 1))
+    return MomentumFunctionals(th, femp, phis, names=[name])
 
 
 def _pressure_dof(th, where):

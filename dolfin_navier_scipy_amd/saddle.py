@@ -606,7 +606,7 @@ class ImexStepper(object):
         return v, p
 
     # ---- force functionals (`dns_imex_set_functionals`) ---------------------
-    def set_functionals(self, fn, nrows, dt):
+    def set_functionals(self, fn, nrows, dt, dbc_table=None):
         """the next `nrows` steps (`step` and `run` alike) evaluate the
         momentum-balance functionals `fn` (`fem.MomentumFunctionals`: drag,
         lift, pressure differences, ...; at most 16) of the state they leave,
@@ -618,15 +618,32 @@ class ImexStepper(object):
         `get_functionals` before the next tables).  Functionals with cells
         need the convection operator attached (`set_convection`) with
         constant Dirichlet values; their cells refer to that operator, so
-        after attaching another one they are set again."""
+        after attaching another one they are set again.
+
+        `dbc_table` (`(nrows + 1, ndbc)`): Dirichlet values that change from
+        step to step, in the order of the operator's `dbcinds` (static first,
+        controlled behind them).  Row `j` holds the values of the state
+        BEFORE the `j`-th step from now, row `nrows` those of the state after
+        the last one; row `s` of the log is then `fn.evaluate(..., dbc=
+        dbc_table[s + 1], dbc_prev=dbc_table[s])`
+        (`dns_imex_set_functionals_bc`).  The table is the functionals' own:
+        the operator's (`set_dbc_table`) keeps its meaning and length."""
         nrows = int(nrows)
         if nrows < 1:
             raise ValueError('`nrows` must be positive')
-        args = fn.device_args()
+        moving = dbc_table is not None
+        args = fn.device_args(moving=True) if moving else fn.device_args()
         nF = int(args['scale'].size)
+        terms = [('ca', self.sys.NV), ('cm', self.sys.NV), ('cp', self.sys.NP)]
+        if moving:
+            tab = np.ascontiguousarray(dbc_table, dtype=np.float64)
+            if tab.ndim != 2 or tab.shape[0] != nrows + 1:
+                raise ValueError('`dbc_table` must have nrows + 1 = {0} rows, '
+                                 'it is {1}'.format(nrows + 1, tab.shape))
+            ndbc = int(tab.shape[1])
+            terms += [('cab', ndbc), ('cmb', ndbc)]
         views = []
-        for name, ncol in (('ca', self.sys.NV), ('cm', self.sys.NV),
-                           ('cp', self.sys.NP)):
+        for name, ncol in terms:
             mat = args[name]
             if mat.nnz == 0 and mat.shape[1] != ncol:
                 views.append(None)           # (pressure-only functionals)
@@ -641,11 +658,15 @@ class ImexStepper(object):
         if cidx.size == 0:
             cidx = np.zeros(1, dtype=np.int32)
         c0, scale = C.as_f64(args['c0'], nF), C.as_f64(args['scale'], nF)
-        C.check(self.lib.dns_imex_set_functionals(
-            self._h, nF, *[None if v is None else v.byref() for v in views],
-            C.dptr(c0), C.dptr(scale),
-            cptr.ctypes.data_as(C.c_int32_p), cidx.ctypes.data_as(C.c_int32_p),
-            C.dptr(cw), float(dt), nrows))
+        refs = [None if v is None else v.byref() for v in views]
+        tail = (C.dptr(c0), C.dptr(scale), cptr.ctypes.data_as(C.c_int32_p),
+                cidx.ctypes.data_as(C.c_int32_p), C.dptr(cw), float(dt), nrows)
+        if moving:
+            C.check(self.lib.dns_imex_set_functionals_bc(
+                self._h, nF, *refs, *tail, ndbc, C.dptr(tab.reshape(-1))))
+        else:
+            C.check(self.lib.dns_imex_set_functionals(self._h, nF, *refs,
+                                                      *tail))
         self._fn_shape = (nrows, nF)
 
     def clear_functionals(self):

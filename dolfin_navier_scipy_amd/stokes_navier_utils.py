@@ -398,13 +398,21 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     on the inner dofs, the device records `y = cv_mat v` of every step and
     keeps no snapshot but the slices' last.  Where the loop does not run
     resident it takes the usual path; `time_int_utils.LAST_RUN['record']`
-    says `'device'` or `'host'`.  `functionals` (explicit schemes, static
-    boundaries): a `fem.MomentumFunctionals` of the condensed problem (drag,
-    lift, pressure differences, ...) -- handed down to the loop
+    says `'device'` or `'host'`.  `functionals` (explicit schemes): a
+    `fem.MomentumFunctionals` of the condensed problem (drag, lift, torque,
+    pressure differences, ...) -- handed down to the loop
     (`resident=dict(functionals=...)`), which evaluates it after every AB2 /
     BDF2 step, on the device where it runs resident;
     `time_int_utils.LAST_RUN['functionals']`, `['functionals_t']`,
     `['functionals_on']` hold the rows, their times and where they came from.
+    With controlled boundaries (`diricontbcinds` / `diricontfuncs`) the
+    functionals are those of the inner dofs that are left, built with
+    `invinds` = the inner dofs without the controlled ones and `dbcinds` =
+    `dbcinds` then the dofs of `diricontbcinds` in their order (the order of
+    the Dirichlet values of the device convection operator; `ValueError`
+    otherwise): the boundary terms follow the controlled values of every
+    state, on the device with `bcs_time_only=True` (one `run` per time
+    slice), on the host otherwise.
     """
     if functionals is not None and not (treat_nonl_explicit
                                         and lin_vel_point is None):
@@ -600,7 +608,19 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
                 # at every step whatever `savevp_times` says)
                 icd['resident'].update(outputs=cv_mat, savevp_times=())
         if functionals is not None:
+            fdbi = getattr(functionals, 'dbi', None)
+            want = np.asarray(list(dbcinds) + list(glb), dtype=np.int64)
+            if not static_bcs and fdbi is not None and not (
+                    fdbi.size == want.size and np.array_equal(fdbi, want)):
+                raise ValueError(
+                    '`functionals` with controlled Dirichlet values must be '
+                    'built with `dbcinds` = the static dofs then the '
+                    'controlled ones ({0} + {1} in the order of '
+                    '`diricontbcinds`); they have {2}, or another '
+                    'order'.format(len(dbcinds), len(glb), fdbi.size))
             icd.setdefault('resident', {}).update(functionals=functionals)
+            if not static_bcs:
+                icd['resident'].setdefault('static_dbcvals', list(dbcvals))
         v_end, p_end, ffflag = timintsc(trange=trange, inip=inip, scalep=-1.,
                                         g_tdp=rhsp, bcs_ini=inicdbcvals,
                                         check_ff_maxv=check_ff_maxv, **icd)

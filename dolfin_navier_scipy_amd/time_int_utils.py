@@ -312,7 +312,10 @@ class _FunctionalLog(object):
     """`resident=dict(functionals=fn)` of `cnab` / `sbdftwo`: arms the
     stepper's functionals per slice (or chunk) next to the tables, collects
     the rows of the device's log and their times; where the loop takes one
-    step at a time the same rows come from `fn.evaluate` on the host"""
+    step at a time the same rows come from `fn.evaluate` on the host.  With
+    controlled (moving) Dirichlet values `arm` is handed their table rows --
+    one more than steps: the values of the state before each step and of the
+    state after the last --, `host_row` the values of the two states"""
 
     def __init__(self, stepper, fn, dt):
         self.stepper, self.fn, self.dt = stepper, fn, dt
@@ -320,8 +323,16 @@ class _FunctionalLog(object):
         self.where = None
         self.names = None if fn is None else list(fn.names)
 
-    def arm(self, times):
-        self.stepper.set_functionals(self.fn, len(times), self.dt)
+    def arm(self, times, dbc_rows=None):
+        if dbc_rows is None:
+            self.stepper.set_functionals(self.fn, len(times), self.dt)
+            return
+        if len(dbc_rows) != len(times) + 1:
+            raise ValueError('{0} steps need {1} rows of Dirichlet values, '
+                             'got {2}'.format(len(times), len(times) + 1,
+                                              len(dbc_rows)))
+        self.stepper.set_functionals(self.fn, len(times), self.dt,
+                                     dbc_table=dbc_rows)
 
     def collect(self, times):
         self.add(self.stepper.get_functionals(0, len(times)), times)
@@ -331,8 +342,9 @@ class _FunctionalLog(object):
         self.ys.append(np.asarray(rows, dtype=np.float64))
         self.ts.extend(times)
 
-    def host_row(self, v, v_prev, p, time):
-        self.add(self.fn.evaluate(v, v_prev, p, self.dt).reshape((1, -1)),
+    def host_row(self, v, v_prev, p, time, dbc=None, dbc_prev=None):
+        self.add(self.fn.evaluate(v, v_prev, p, self.dt, dbc=dbc,
+                                  dbc_prev=dbc_prev).reshape((1, -1)),
                  [time])
         self.where = 'host'
 
@@ -342,14 +354,19 @@ class _FunctionalLog(object):
         return y, np.array(self.ts, dtype=np.float64)
 
 
-def _functional_log(rsd, stepper, dt, moving):
+def _functional_log(rsd, stepper, dt, moving, ndbc=0):
+    """`ndbc`: static and controlled Dirichlet values of a loop with
+    controlled (`moving`) ones: the functionals' boundary rows `cab`, `cmb`
+    must be as wide, in that order"""
     fn = rsd.get('functionals', None)
     if fn is None:
         return None
-    if moving:
-        raise ValueError('`functionals` with controlled (moving) Dirichlet '
-                         'values: the terms `A_bc g(t)`, `M_bc g\'(t)` are not '
-                         'part of the functional')
+    if moving and fn.inv is not None and fn.cab.shape[1] != ndbc:
+        raise ValueError(
+            '`functionals` with controlled (moving) Dirichlet values: they '
+            'were built for {0} Dirichlet dofs, the loop has {1} '
+            '(`static_dbcvals` then the controlled ones: build them with '
+            '`dbcinds` in that order)'.format(fn.cab.shape[1], ndbc))
     return _FunctionalLog(stepper, fn, dt)
 
 
@@ -376,6 +393,7 @@ class _ResidentSlices(object):
         self.rsd = rsd = dict(resident or {})
         self.statvals = list(rsd.get('static_dbcvals', []) or [])
         self.moving = len(bcs_ini) > 0
+        self.nbcs = len(bcs_ini)
         if conv is not None:
             stepper.set_convection(conv, scale=-1.0)
             if self.moving or self.statvals:
@@ -397,8 +415,9 @@ class _ResidentSlices(object):
     def attach(self, lti, c_n, c_c, drm, tstart):
         """the functionals and, for a `LinearFeedback` that can run resident,
         the observer (inside the loop's `try`: both may refuse)"""
-        self.flog = _functional_log(self.rsd, self.stepper, self.dt,
-                                    self.moving)
+        self.flog = _functional_log(
+            self.rsd, self.stepper, self.dt, self.moving,
+            len(self.statvals) + self.nbcs)
         if lti is not None and self.on_device:
             self.rfb = _ResidentFeedback(lti, self.stepper, drm, c_n, c_c,
                                          self.dt, tstart)
@@ -426,13 +445,20 @@ class _ResidentSlices(object):
             self.prev, self.cur = self.cur, nxt
         bcs_n = self.cur.bcs
         span = [0, 0]
+        # (the functionals see the values of the state a step LEAVES: one row
+        # more, the values behind the slice's last step)
+        dbt_end = np.vstack([dbt, [statvals + list(bcs_n)]]) if moving \
+            else None
 
         def upload(a, b):
             stepper.set_rhs_table(gvt[a:b], gpt[a:b])
             if moving:
                 self.conv.set_dbc_table(dbt[a:b])
             for att in self.attachments:
-                att.arm(ctrange[a:b])
+                if att is self.flog and moving:
+                    att.arm(ctrange[a:b], dbt_end[a:b + 1])
+                else:
+                    att.arm(ctrange[a:b])
             span[:] = [a, b]
 
         def after_chunk():
@@ -609,8 +635,8 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
       `record_bytes`    with `record`: cap of a slice's snapshot buffer
                         (default 1 GiB); a slice that keeps more runs in
                         chunks (`plan_record`)
-      `functionals`     a `fem.MomentumFunctionals` (drag, lift, pressure
-                        differences, ...; static boundaries only): evaluated
+      `functionals`     a `fem.MomentumFunctionals` (drag, lift, torque,
+                        pressure differences, ...): evaluated
                         on the device after every step of a slice
                         (`ImexStepper.set_functionals`), with and without
                         `record`; `LAST_RUN['functionals']` is `nsteps x nF`,
@@ -619,7 +645,15 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                         start runs on the host and has no row.  Where the
                         loop does not run resident the same rows come from
                         `fn.evaluate` on the host;
-                        `LAST_RUN['functionals_on']` says 'device' or 'host'
+                        `LAST_RUN['functionals_on']` says 'device' or
+                        'host'.  With controlled Dirichlet values (`bcs_ini`
+                        not empty) the functionals must be built with
+                        `dbcinds` = the static dofs then the controlled ones
+                        (the order of `static_dbcvals + bcs`; `ValueError`
+                        otherwise): the boundary terms `cab . g + cmb .
+                        (g - g_prev)/dt` go by the values of each state, on
+                        the device with `bcs_time_only` (a table of their own
+                        per slice), on the host otherwise
     `LAST_RUN['record']` says 'device' or 'host', `LAST_RUN['run_calls']`
     counts the `stepper.run` calls of the loop.
     The per-step data the callbacks return (`f_tdp`, `g_tdp`, `applybcs`) are
@@ -710,7 +744,11 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                 stepper.set_rhs(_col(gvec, NV), _col(fp_n + bfp_n, NP))
                 stepper.step(cf, nfc_new=nfc_new, opts=opts)
                 v_n, p_n = stepper.get_state()
-                if rs.flog is not None:
+                if rs.flog is not None and moving:
+                    rs.flog.host_row(v_n, v_c, p_n, ctime,
+                                     dbc=statvals + list(bcs_n),
+                                     dbc_prev=statvals + list(bcs_c))
+                elif rs.flog is not None:
                     rs.flog.host_row(v_n, v_c, p_n, ctime)
                 savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
         if rs.rfb is not None:
@@ -810,7 +848,11 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                 stepper.set_rhs(_col(gvec, NV), _col(fp_n + bfp_n, NP))
                 stepper.step(cf, nfc_new=nfc_new, opts=opts)
                 v_n, p_n = stepper.get_state()
-                if rs.flog is not None:
+                if rs.flog is not None and moving:
+                    rs.flog.host_row(v_n, v_c, p_n, ctime,
+                                     dbc=statvals + list(bcs_n),
+                                     dbc_prev=statvals + list(bcs_c))
+                elif rs.flog is not None:
                     rs.flog.host_row(v_n, v_c, p_n, ctime)
                 savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
         if rs.rfb is not None:

@@ -514,14 +514,39 @@ int dns_imex_clear_recorder(dns_imex *st);
  * again re-arms it (buffers that are large enough are kept).
  * Limits (DNS_ERR_BAD_ARGUMENT beyond them): 1 <= nF <= 16; cell indices
  * below the operator's ncells; cells need an attached convection operator;
- * an operator with a per-step Dirichlet table (dns_conv_set_dbc_table) and
- * a row-partitioned stepper are refused.  Any nnz, any number of cells.
+ * an operator with a per-step Dirichlet table (dns_conv_set_dbc_table: use
+ * dns_imex_set_functionals_bc) and a row-partitioned stepper are refused.  Any nnz, any number of cells.
  * Works with and without observer feedback and the recorder. */
 int dns_imex_set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
                              const dns_csr *cm, const dns_csr *cp,
                              const double *c0, const double *scale,
                              const int32_t *cell_ptr, const int32_t *cell_idx,
                              const double *cell_w, double dt, int32_t nrows);
+/* The same with Dirichlet values g that change from step to step (controlled
+ * boundaries: a rotating body, a modulated inflow), ndbc of them in the order
+ * of the convection operator's dbcinds:
+ *     y_k = scale_k * ( ca_k . v + cm_k . (v - v_prev) / dt + cp_k . p
+ *                       + cab_k . g + cmb_k . (g - g_prev) / dt
+ *                       + sum_{c in cells_k} sum_{sl < 12} w_k[c][sl] N_loc(c; v, g)[sl]
+ *                       + c0_k )
+ * cab, cmb: nF x ndbc, the Dirichlet columns of phi^T A and phi^T M (host CSR,
+ * NULL: no such term); c0 holds constants that are no boundary terms.
+ * dbc_table: row-major (nrows + 1) x ndbc, row j the values of the state
+ * BEFORE the j-th step after this call, row nrows those of the state after
+ * the last one: log row r uses g = row r + 1, g_prev = row r.  It is a table
+ * of the functionals' own; the operator's table (dns_conv_set_dbc_table) keeps
+ * its meaning and length.  Further limits: ndbc >= 1, equal to the operator's
+ * where cells are listed -- when it is set and when a step runs.  With
+ * constant values the rows are those of dns_imex_set_functionals with
+ * c0 + cab . g for c0. */
+int dns_imex_set_functionals_bc(dns_imex *st, int32_t nF, const dns_csr *ca,
+                                const dns_csr *cm, const dns_csr *cp,
+                                const dns_csr *cab, const dns_csr *cmb,
+                                const double *c0, const double *scale,
+                                const int32_t *cell_ptr,
+                                const int32_t *cell_idx, const double *cell_w,
+                                double dt, int32_t nrows, int32_t ndbc,
+                                const double *dbc_table);
 /* rows [first, first + count) of the log: out (count x nF) */
 int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,
                              double *out);

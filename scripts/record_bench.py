@@ -20,6 +20,18 @@ One command per leg (profiles/r08_recorder/README.md):
                   evaluated on the host (`MomentumFunctionals.evaluate`) per
                   step: what scripts/schaefer_turek_unsteady.py does without
                   the device log
+  --leg moving_open    the cylinder rotates, `omega(t)` tabulated: rhs table
+                  and Dirichlet table of the convection operator as
+                  `cnab(resident=dict(bcs_time_only=True))` sets them, nothing
+                  else attached (no API newer than `set_dbc_table`, so the
+                  parent tree runs it too)
+  --leg moving_forces  the same with drag, lift, torque and dp of every step on
+                  the device (`set_functionals(..., dbc_table=)`), then ONE
+                  download of the rows
+  --leg moving_host    what there is without the moving-boundary functionals: a
+                  device snapshot of every step, ONE download, then
+                  `MomentumFunctionals.evaluate(..., dbc=, dbc_prev=)` per
+                  step on the host (profiles/r12_functionals_bc/README.md)
   --refine R      the same legs on the mesh refined R times (multigrid Schur
                   block, dt = 1/(512 2^R), start from rest, as refined_bench.py)
 
@@ -253,10 +265,118 @@ def leg_forces_stepwise(su, steps, spin):
     return out
 
 
+class _Rotation(object):
+    """the cylinder's dofs carry `omega(t) (-(y - yc), x - xc)`: the tables of
+    `rows` steps from t = 0 (right-hand sides as `cnab` forms them, Dirichlet
+    values of the operator's order with one row more: the values behind the
+    last step) and a convection operator of the leg's own to carry them"""
+
+    def __init__(self, su, stp, rows):
+        from dolfin_navier_scipy_amd import fem, convection
+        femp, dt = su.femp, getattr(su, 'dt', 1./512)
+        th, inv = femp['V'], np.asarray(femp['invinds'])
+        self.dbi = np.asarray(femp['dbcinds'], dtype=np.int64)
+        nodes = fem.cylinder_nodes(th)
+        pos = {int(d): k for k, d in enumerate(self.dbi)}
+        cyl = np.array([[pos[2*n], pos[2*n + 1]] for n in nodes]).reshape(-1)
+        xy = th.nodecoords[nodes]
+        shape = np.stack([-(xy[:, 1] - 0.2), xy[:, 0] - 0.2],
+                         axis=1).reshape(-1)
+        base = np.asarray(femp['dbcvals'], dtype=np.float64).reshape(-1)
+        times = dt*np.arange(rows + 1)
+        self.tab = np.tile(base, (rows + 1, 1))
+        self.tab[:, cyl] = np.outer(2.*np.sin(2*np.pi*times/0.25), shape)
+        st = th.stokes_mats(nu=femp['nu'])
+        aux = np.zeros((th.vdim, rows + 1))
+        aux[self.dbi[cyl], :] = self.tab[:, cyl].T
+        bfv = -(st['A'] @ aux)[inv, :].T                  # (rows + 1, NV)
+        mbc = (st['M'] @ aux)[inv, :].T
+        bfp = -(st['J'] @ aux).T
+        fv, fp = su.rhsd['fv'][:, 0], su.rhsd['fp'][:, 0]
+        gv = dt*fv[None, :] - (mbc[1:] - mbc[:-1]) + .5*dt*(bfv[1:] + bfv[:-1])
+        gp = fp[None, :] + bfp[1:]
+        self.cvop = convection.ConvectionP2.from_taylor_hood(
+            th, inv, self.dbi, base)
+        stp.set_convection(self.cvop, scale=-1.0)
+        stp.set_rhs_table(gv, gp)
+        self.cvop.set_dbc_table(self.tab[:rows])
+        self.nodes, self.rows = nodes, rows
+
+    def functionals(self, su):
+        from dolfin_navier_scipy_amd import fem
+        th, femp = su.femp['V'], su.femp
+        return fem.boundary_forces(th, femp, nodes=self.nodes) \
+            + fem.boundary_torque(th, femp, nodes=self.nodes) \
+            + fem.pressure_difference(th, (0.15, 0.2), (0.25, 0.2))
+
+    def close(self, stp):
+        stp.set_convection(None)
+        self.cvop.close()
+
+
+def _leg_moving(su, steps, spin, what):
+    stp, cf, opts, close = su.stepper()
+    rot = None
+    try:
+        dt = getattr(su, 'dt', 1./512)
+        rows = spin + 3*steps
+        rot = _Rotation(su, stp, rows)
+        fn = rot.functionals(su) if what != 'open' else None
+        if what == 'host':
+            stp.set_recorder(rows, snap_slots='all')
+        if what == 'forces':
+            stp.set_functionals(fn, rows, dt, dbc_table=rot.tab)
+        stp.run(spin, cf, opts)
+        secs, its, n = _timed_window(stp, cf, opts, steps)
+        out = _record(stp, steps, secs, its)
+        out['windows'] = n
+        spin += (n - 1)*steps
+        if what == 'forces':
+            t0 = time.perf_counter()
+            got = stp.get_functionals(spin, steps)
+            dl = time.perf_counter() - t0
+            out.update(download_seconds=dl,
+                       steps_per_s_with_download=steps/(secs + dl),
+                       names=fn.names, row_last=got[-1].tolist(),
+                       body_cells=int(fn.cells[0].size))
+        if what == 'host':
+            t0 = time.perf_counter()
+            v, p = stp.record_snapshots(spin - 1, steps + 1)
+            dl = time.perf_counter() - t0
+            got = np.empty((steps, fn.nF))
+            for k in range(steps):
+                r = spin + k
+                got[k] = fn.evaluate(v[k + 1], v[k], p[k + 1], dt,
+                                     dbc=rot.tab[r + 1], dbc_prev=rot.tab[r])
+            ev = time.perf_counter() - t0 - dl
+            out.update(download_seconds=dl, evaluate_seconds=ev,
+                       steps_per_s_with_download=steps/(secs + dl + ev),
+                       names=fn.names, row_last=got[-1].tolist())
+    finally:
+        if rot is not None:
+            rot.close(stp)
+        close()
+    return out
+
+
+def leg_moving_open(su, steps, spin):
+    return _leg_moving(su, steps, spin, 'open')
+
+
+def leg_moving_forces(su, steps, spin):
+    return _leg_moving(su, steps, spin, 'forces')
+
+
+def leg_moving_host(su, steps, spin):
+    return _leg_moving(su, steps, spin, 'host')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--leg', choices=('stepwise', 'open', 'snap', 'outputs',
-                                      'forces', 'forces_stepwise'),
+                                      'forces', 'forces_stepwise',
+                                      'moving_open', 'moving_forces',
+                                      'moving_host'),
                     required=True)
     ap.add_argument('--with-outputs', action='store_true',
                     help="leg forces: the recorder's y log on as well")
@@ -275,13 +395,16 @@ def main():
     else:
         import feedback_bench as fbb
         su = fbb.Setup()
-    fn = dict(stepwise=leg_stepwise, open=leg_open, snap=leg_snap,
+    fn = dict(moving_open=leg_moving_open, moving_forces=leg_moving_forces,
+              moving_host=leg_moving_host,
+              stepwise=leg_stepwise, open=leg_open, snap=leg_snap,
               outputs=leg_outputs, forces_stepwise=leg_forces_stepwise,
               forces=(leg_forces_outputs if args.with_outputs
                       else leg_forces))[args.leg]
     reps = [fn(su, args.steps, args.spin) for _ in range(args.repeats)]
     key = 'steps_per_s_with_download' \
-        if args.leg in ('snap', 'outputs', 'forces') \
+        if args.leg in ('snap', 'outputs', 'forces', 'moving_forces',
+                        'moving_host') \
         else 'steps_per_s'
     rates = [r['steps_per_s'] for r in reps]
     out = dict(leg=args.leg, label=args.label, steps=args.steps,
