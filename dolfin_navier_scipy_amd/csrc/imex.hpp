@@ -7,6 +7,7 @@
 #include "record.hpp"
 #include "ring.hpp"
 #include "solver.hpp"
+#include "stats.hpp"
 #include "trap.hpp"
 #include "step_kernels.hpp"
 #include <memory>
@@ -184,7 +185,26 @@ struct dns_imex : dns::Ring {
     std::unique_ptr<Functionals> fn;
     int fn_launch(hipStream_t s);  // k_functional_step for the state as it stands
     uint64_t fn_key() const;
-    // What the three have in common (imex_attach_capi.inc): which of them
+    // flow statistics (stats.hpp): k_stats_step runs in front of every step
+    // (behind the other three) and once behind the last step of a call; it
+    // ADDS row `counter - 1` to running sums, so -- unlike the rows of the
+    // other three -- a row must not be seen twice: the workgroups' marks
+    // (the head of `acc`) drop the second launch for a row, rewind_tables()
+    // zeroes them with the counter, and a batch checkpoints `acc` as a whole
+    // (`ck_st`: `ck` can be full without it).  Present = on.
+    struct Statistics {
+        dns::StLayout lay;
+        int rows = 0;              // steps the bin table covers
+        std::vector<int> pi, pj;   // (the same pairs set again keep the sums)
+        dns::DevBuf<int> bin;
+        dns::DevBuf<int2> pairs;
+        dns::DevBuf<double> acc;
+    };
+    std::unique_ptr<Statistics> stat;
+    dns::Checkpoint ck_st;
+    int st_launch(hipStream_t s);  // k_stats_step for the state as it stands
+    uint64_t st_key() const;
+    // What the four have in common (imex_attach_capi.inc): which of them
     // run in front of a step and which behind the last step of a call, what
     // they add to the key of a captured step, the refusals a step makes on
     // their behalf, and what they mean for the step counter.

@@ -1,6 +1,7 @@
 // The attachments of the resident IMEX loop -- observer feedback
 // (feedback.hpp), trajectory recorder (record.hpp), force functionals
-// (functional.hpp): one node each in front of every step -- and their extern
+// (functional.hpp), flow statistics (stats.hpp): one node each in front of
+// every step -- and their extern
 // "C" entry points (included by dns_amd.hip behind imex_capi.inc).
 
 // "feedback on", its shape, its coefficients and every buffer k_lti_step is
@@ -104,14 +105,36 @@ int dns_imex::fb_launch(hipStream_t s) {
     return DNS_OK;
 }
 
-// ---- what the three have in common ------------------------------------------
+// "statistics on", their shape and grid, every buffer k_stats_step is handed
+// and the pressure scale of the state it is about to add
+uint64_t dns_imex::st_key() const {
+    const Statistics &t = *stat;
+    return mix64(0x57a7, {kw(t.rows), kw(t.lay.nbins), kw(t.lay.npairs),
+                          kw(t.lay.G), kw(last_pscale), kw(t.bin.p),
+                          kw(t.pairs.p), kw(t.acc.p), kw(stepctr.p)});
+}
+
+int dns_imex::st_launch(hipStream_t s) {
+    const Statistics &t = *stat;
+    const dns::StArgs a{stepctr.p, t.rows, xs[cur].p, sys->nv, sys->n,
+                        (int)sys->ld, last_pscale, t.bin.p, t.lay.nbins,
+                        t.lay.npairs, t.pairs.p, t.acc.p, t.lay.G,
+                        t.lay.head(), t.lay.npx()};
+    hipLaunchKernelGGL(dns::k_stats_step, t.lay.G, dns::kBlock, 0, s, a);
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+// ---- what the four have in common -------------------------------------------
 
 // In front of every step, in this order: k_lti_step leaves the right-hand
-// side the front kernels read, the other two write the row of the step before.
+// side the front kernels read, the other three write down / add the row of
+// the step before.
 int dns_imex::launch_front_nodes(hipStream_t s) {
     if (fb.on) DNS_TRY(fb_launch(s));
     if (rec) DNS_TRY(rec_launch(s));
     if (fn) DNS_TRY(fn_launch(s));
+    if (stat) DNS_TRY(st_launch(s));
     return DNS_OK;
 }
 
@@ -119,6 +142,7 @@ int dns_imex::launch_front_nodes(hipStream_t s) {
 int dns_imex::launch_closing_nodes(hipStream_t s) {
     if (rec) DNS_TRY(rec_launch(s));
     if (fn) DNS_TRY(fn_launch(s));
+    if (stat) DNS_TRY(st_launch(s));
     return DNS_OK;
 }
 
@@ -126,11 +150,13 @@ uint64_t dns_imex::attachments_key(uint64_t k) const {
     if (fb.on) k = mix64(k, {fb_key()});
     if (rec) k = mix64(k, {rec_key()});
     if (fn) k = mix64(k, {fn_key()});
+    if (stat) k = mix64(k, {st_key()});
     return k;
 }
 
 bool dns_imex::tables() const {
-    return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on || rec || fn;
+    return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on || rec ||
+           fn || stat;
 }
 
 int dns_imex::rows_left() const {
@@ -139,14 +165,20 @@ int dns_imex::rows_left() const {
     if (fb.on) lim = std::min(lim, fb.rows);
     if (rec) lim = std::min(lim, rec->rows);
     if (fn) lim = std::min(lim, fn->rows);
+    if (stat) lim = std::min(lim, stat->rows);
     if (conv && conv->dbc_rows > 0) lim = std::min(lim, conv->dbc_rows);
     return lim - tab_pos;
 }
 
 // New tables: the step counter, which selects the row of every table, the log
 // rows and the slot of the observer state (`tab_pos & 1`, slot 0 from here
-// on), goes back to 0 -- here and nowhere else; complete on return.
+// on), goes back to 0 -- here and nowhere else; complete on return.  The marks
+// of the statistics count rows since the rewind: they go back with it (the
+// sums stay).
 int dns_imex::rewind_tables() {
+    if (stat)
+        DNS_HIP(hipMemsetAsync(stat->acc.p, 0, stat->lay.G * sizeof(double),
+                               sys->stream));
     if (fb.on && (tab_pos & 1)) {
         const size_t n = (size_t)fb.stride();
         DNS_HIP(hipMemcpyAsync(fb.state.p, fb.state.p + n, n * sizeof(double),
@@ -161,7 +193,7 @@ int dns_imex::rewind_tables() {
     return DNS_OK;
 }
 
-// None of the three runs on a row-partitioned / distributed stepper: refused
+// None of the four runs on a row-partitioned / distributed stepper: refused
 // when it is set and, should the stepper be partitioned later, by the step.
 int dns_imex::refuse_partitioned(const char *noun, const char *reason) const {
     if (!(r1_rows || part.on || sys->dist())) return DNS_OK;
@@ -176,11 +208,15 @@ static const char *const kRecPartitioned =
     "the outputs y = C v would need an all-reduce, the snapshots a gather "
     "(multi-rank recording is not supported)";
 static const char *const kFnPartitioned = "the sums would need an all-reduce";
+static const char *const kStPartitioned =
+    "the sums are local to a rank, the getter would need a gather (multi-rank "
+    "statistics are not supported)";
 
 // what a step refuses on their behalf
 int dns_imex::check_attachments() const {
     if (fb.on) DNS_TRY(refuse_partitioned("observer feedback", kFbPartitioned));
     if (rec) DNS_TRY(refuse_partitioned("recorder", kRecPartitioned));
+    if (stat) DNS_TRY(refuse_partitioned("statistics", kStPartitioned));
     if (!fn) return DNS_OK;
     DNS_TRY(refuse_partitioned("functionals", kFnPartitioned));
     if (fn->ncl > 0 && !conv)
@@ -733,6 +769,103 @@ int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,
 int dns_imex_clear_functionals(dns_imex *st) try {
     DNS_TRY(quiesce(st));
     st->fn.reset();
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// ---- flow statistics (stats.hpp) -------------------------------------------
+
+int dns_imex_set_stats(dns_imex *st, int32_t nrows, const int32_t *bin,
+                       int32_t nbins, int32_t npairs, const int32_t *pair_i,
+                       const int32_t *pair_j, int32_t reset) try {
+    if (!st || !bin) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_saddle *h = st->sys;
+    DNS_TRY(st->refuse_partitioned("statistics", kStPartitioned));
+    if (nbins < 1 || nbins > dns::kStMaxBins)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "statistics: nbins = %d outside 1..%d", (int)nbins,
+                         dns::kStMaxBins);
+    if (nrows < 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "statistics: nrows = %d < 1",
+                         (int)nrows);
+    if (npairs < 0 || (npairs > 0 && (!pair_i || !pair_j)))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "statistics: npairs = %d without pair_i / pair_j",
+                         (int)npairs);
+    dns::StLayout lay;
+    lay.G = dns::stats_grid((int)h->ld, npairs);
+    lay.nbins = nbins;
+    lay.ld = (int)h->ld;
+    lay.npairs = npairs;
+    // (the checkpoint of a batch counts in int)
+    if (lay.total() >= ((size_t)1 << 31))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "statistics: an accumulator of %zu entries (%d bins "
+                         "x (2 x %d + %d)), the limit is 2^31 - 1",
+                         lay.total(), (int)nbins, lay.ld, lay.npx());
+    for (int r = 0; r < nrows; ++r)
+        if (bin[r] < -1 || bin[r] >= nbins)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "statistics: bin[%d] = %d outside -1..%d", r,
+                             (int)bin[r], (int)nbins - 1);
+    for (int q = 0; q < npairs; ++q)
+        if (pair_i[q] < 0 || pair_i[q] >= h->n || pair_j[q] < 0 ||
+            pair_j[q] >= h->n)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "statistics: pair %d = (%d, %d) outside 0..%d "
+                             "(NV + NP - 1)", q, (int)pair_i[q],
+                             (int)pair_j[q], h->n - 1);
+    DNS_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still add to it
+    // In place (keep_or_alloc; everything was checked above: a failed
+    // allocation leaves the stepper without statistics).
+    std::unique_ptr<dns_imex::Statistics> t = std::move(st->stat);
+    if (!t) t.reset(new (std::nothrow) dns_imex::Statistics());
+    if (!t) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    const bool keep = !reset && t->acc.p && t->lay.nbins == nbins &&
+                      t->lay.ld == lay.ld && t->lay.npairs == npairs &&
+                      std::equal(t->pi.begin(), t->pi.end(), pair_i) &&
+                      std::equal(t->pj.begin(), t->pj.end(), pair_j);
+    if (!keep) {
+        DNS_TRY(keep_or_alloc(t->acc, t->acc, lay.total()));
+        DNS_TRY(t->acc.zero(s));
+        DNS_TRY(keep_or_alloc(t->pairs, t->pairs, (size_t)npairs));
+        std::vector<int2> pq((size_t)npairs);
+        for (int q = 0; q < npairs; ++q) pq[q] = make_int2(pair_i[q], pair_j[q]);
+        if (npairs > 0) DNS_TRY(t->pairs.upload(pq.data(), pq.size(), s));
+        t->pi.assign(pair_i, pair_i + npairs);
+        t->pj.assign(pair_j, pair_j + npairs);
+        t->lay = lay;
+    }
+    DNS_TRY(keep_or_alloc(t->bin, t->bin, (size_t)nrows));
+    DNS_TRY(t->bin.upload(bin, (size_t)nrows, s));
+    t->rows = nrows;
+    st->stat = std::move(t);
+    return st->rewind_tables();
+} DNS_CAPI_CATCH
+
+int dns_imex_get_stats(dns_imex *st, int32_t first_bin, int32_t count,
+                       double *counts, double *s1, double *s2,
+                       double *sx) try {
+    DNS_TRY(need(st, st && st->stat, "statistics are", "dns_imex_set_stats"));
+    const dns_imex::Statistics &t = *st->stat;
+    const dns::StLayout &l = t.lay;
+    const double *bins = t.acc.p + l.head();
+    const size_t n = (size_t)st->sys->n, bs = l.bin_stride();
+    DNS_TRY(download_log_rows(st, counts, t.acc.p + l.G, first_bin, count, 1,
+                              l.nbins, "bins", "statistics"));
+    DNS_TRY(download_log_rows(st, s1, bins, first_bin, count, n, l.nbins,
+                              "bins", "statistics", bs));
+    DNS_TRY(download_log_rows(st, s2, bins + l.ld, first_bin, count, n,
+                              l.nbins, "bins", "statistics", bs));
+    return download_log_rows(st, sx, bins + (size_t)2 * l.ld, first_bin,
+                             count, (size_t)l.npairs, l.nbins, "bins",
+                             "statistics", bs);
+} DNS_CAPI_CATCH
+
+int dns_imex_clear_stats(dns_imex *st) try {
+    DNS_TRY(quiesce(st));
+    st->stat.reset();
     return DNS_OK;
 } DNS_CAPI_CATCH
 

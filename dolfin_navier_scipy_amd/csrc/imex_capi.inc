@@ -387,7 +387,8 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
                              "dns_conv_set_dbc_table / "
                              "dns_imex_set_feedback_table / "
                              "dns_imex_set_recorder / "
-                             "dns_imex_set_functionals)", tab_pos);
+                             "dns_imex_set_functionals / dns_imex_set_stats)",
+                             tab_pos);
     }
     if (conv) conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
     const int next_nsol = std::min(nsol + 1, 5);
@@ -846,12 +847,20 @@ int ImexRun::run_batch() {
         DNS_TRY(ck.add(st->fb.state.p, (size_t)2 * st->fb.stride()));
         DNS_TRY(ck.add(st->fb.geff.p, h->nv));
     }
+    // flow statistics: the sums AND the workgroups' marks -- a restored batch
+    // adds its rows again, to the sums the batch started from (a checkpoint
+    // of their own: the list above can be full)
+    dns::Checkpoint &cks = st->ck_st;
+    cks.clear();
+    if (st->stat)
+        DNS_TRY(cks.add(st->stat->acc.p, st->stat->lay.total()));
     const dns_imex::HostState hs0 = st->host_state();
     // back to the checkpoint, then what derives from it: K x products of the
     // ring, device step counter, cell values (not in the ring), the six-node
     // warm start and cell values (the counter is back at the first step)
     auto restore = [&]() -> int {
         DNS_TRY(ck.restore(h->stream));
+        if (st->stat) DNS_TRY(cks.restore(h->stream));
         st->set_host_state(hs0);
         if (carrying) DNS_TRY(st->prime_carry(false));
         if (st->tables()) DNS_TRY(st->sync_counter());
@@ -878,6 +887,7 @@ int ImexRun::run_batch() {
         }
         DNS_TRY(ck.save(h->stream, h->ctl.p, over ? h->oversolve_frac : 0.0,
                         attempt == 0));
+        if (st->stat && attempt == 0) DNS_TRY(cks.save(h->stream));
         h->pipeline_c = c;
         for (int q = 0, g = 0; q < nb; q += g) {
             g = st->group_for(nb - q);

@@ -9,3 +9,4 @@ from .problem_setups import (get_sysmats, condense_sysmatsbybcs,
 from .functionals import (MomentumFunctionals, boundary_forces,
                           boundary_torque, pressure_difference,
                           cylinder_nodes)
+from .statistics import FlowStatistics, component_pairs

@@ -687,6 +687,79 @@ class ImexStepper(object):
             C.dptr(out.reshape(-1) if out.size else np.zeros(1))))
         return out
 
+    # ---- flow statistics (`dns_imex_set_stats`) ------------------------------
+    def set_statistics(self, bins, nbins=None, pairs=None, reset=False):
+        """the next `len(bins)` steps (`step` and `run` alike) add the state
+        `x = [v; p]` they leave to running sums on the device: the step `s`
+        from now goes into bin `bins[s]` (`-1`: skipped; `nbins`: at most 256,
+        default `max(bins) + 1`), `N += 1`, `S1 += x`, `S2 += x**2` and, for
+        the index pairs `pairs` (`(npairs, 2)` into `[0, NV + NP)`),
+        `SX += x[i]*x[j]` (`fem.FlowStatistics` makes means, variances and
+        covariances of them).  The sums go on across calls with the same
+        `nbins` and `pairs` unless `reset`: the slices of a time loop set
+        their bins and keep summing; collect with `statistics()`.  Resets the
+        step counter like `set_rhs_table` (call it after that one)."""
+        bins = np.asarray(bins)
+        if bins.ndim != 1 or bins.size < 1:
+            raise ValueError('`bins`: one entry per step, at least one')
+        if not np.issubdtype(bins.dtype, np.integer):
+            raise ValueError('`bins` must be integers')
+        if nbins is None:
+            nbins = max(int(bins.max()) + 1, 1)
+        nbins = int(nbins)
+        if not 1 <= nbins <= 256:
+            raise ValueError('`nbins` = {0} outside 1..256'.format(nbins))
+        if bins.min() < -1 or bins.max() >= nbins:
+            raise ValueError('`bins`: entries are bins below `nbins` = {0} '
+                             'or -1'.format(nbins))
+        bins = np.ascontiguousarray(bins, dtype=np.int32)
+        n = self.sys.NV + self.sys.NP
+        pr = np.zeros((0, 2), dtype=np.int32) if pairs is None else \
+            np.asarray(pairs)
+        if pr.size and not np.issubdtype(pr.dtype, np.integer):
+            raise ValueError('`pairs` must be integers')
+        if pr.size == 0:
+            pr = np.zeros((0, 2), dtype=np.int32)
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise ValueError('`pairs` must be npairs x 2, it is {0}'.format(
+                pr.shape))
+        if pr.size and (pr.min() < 0 or pr.max() >= n):
+            raise ValueError('`pairs`: indices into [0, NV + NP) = [0, {0})'
+                             .format(n))
+        pi = np.ascontiguousarray(pr[:, 0], dtype=np.int32)
+        pj = np.ascontiguousarray(pr[:, 1], dtype=np.int32)
+        npairs = int(pi.size)
+        C.check(self.lib.dns_imex_set_stats(
+            self._h, int(bins.size), bins.ctypes.data_as(C.c_int32_p), nbins,
+            npairs, pi.ctypes.data_as(C.c_int32_p) if npairs else None,
+            pj.ctypes.data_as(C.c_int32_p) if npairs else None,
+            int(bool(reset))))
+        self._st_shape = (nbins, npairs)
+
+    def clear_statistics(self):
+        C.check(self.lib.dns_imex_clear_stats(self._h))
+        self._st_shape = None
+
+    def statistics(self):
+        """the sums since they were last zeroed, a dict: `counts` `(nbins,)`
+        (integers), `s1_v`, `s2_v` `(nbins, NV)`, `s1_p`, `s2_p` `(nbins, NP)`
+        and `sx` `(nbins, npairs)`"""
+        shape = getattr(self, '_st_shape', None)
+        if shape is None:
+            raise ValueError('no statistics are set (`set_statistics`)')
+        nbins, npairs = shape
+        NV, NP = self.sys.NV, self.sys.NP
+        cnt = np.empty(nbins)
+        s1, s2 = np.empty((nbins, NV + NP)), np.empty((nbins, NV + NP))
+        sx = np.empty((nbins, npairs))
+        C.check(self.lib.dns_imex_get_stats(
+            self._h, 0, nbins, C.dptr(cnt), C.dptr(s1.reshape(-1)),
+            C.dptr(s2.reshape(-1)),
+            C.dptr(sx.reshape(-1)) if npairs else None))
+        return dict(counts=np.rint(cnt).astype(np.int64),
+                    s1_v=s1[:, :NV].copy(), s1_p=s1[:, NV:].copy(),
+                    s2_v=s2[:, :NV].copy(), s2_p=s2[:, NV:].copy(), sx=sx)
+
     def get_state(self):
         v = np.empty(self.sys.NV)
         p = np.empty(self.sys.NP)

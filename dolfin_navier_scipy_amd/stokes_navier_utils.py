@@ -357,7 +357,7 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
               vp_output=False, vp_out_fun=None, vp_output_dict=None,
               solver=None, device=0, bcs_time_only=False,
               applybcs_literal=True, record_on_device=False,
-              functionals=None, **kw):
+              functionals=None, statistics=None, **kw):
     """time-dependent Navier-Stokes on the device (reference snu:548-1600)
 
     Keyword names and meaning follow the reference.  `V`: object with the P2
@@ -412,11 +412,20 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     the Dirichlet values of the device convection operator; `ValueError`
     otherwise): the boundary terms follow the controlled values of every
     state, on the device with `bcs_time_only=True` (one `run` per time
-    slice), on the host otherwise.
+    slice), on the host otherwise.  `statistics` (explicit schemes): a
+    `fem.FlowStatistics` over the inner dofs and the pressure -- handed down
+    to the loop (`resident=dict(statistics=...)`), which adds the state after
+    the Heun start and after every AB2 / BDF2 step to its sums, on the device
+    where it runs resident (one download when the loop ends);
+    `time_int_utils.LAST_RUN['statistics']` and `['statistics_on']` hold the
+    sums and where they were formed.
     """
     if functionals is not None and not (treat_nonl_explicit
                                         and lin_vel_point is None):
         raise NotImplementedError('`functionals`: explicit schemes only')
+    if statistics is not None and not (treat_nonl_explicit
+                                       and lin_vel_point is None):
+        raise NotImplementedError('`statistics`: explicit schemes only')
     if dynamic_feedback and dyn_fb_disc == 'linear_implicit':
         raise NotImplementedError("`dyn_fb_disc='linear_implicit'` (the "
                                   'extended system of '
@@ -621,6 +630,8 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
             icd.setdefault('resident', {}).update(functionals=functionals)
             if not static_bcs:
                 icd['resident'].setdefault('static_dbcvals', list(dbcvals))
+        if statistics is not None:
+            icd.setdefault('resident', {}).update(statistics=statistics)
         v_end, p_end, ffflag = timintsc(trange=trange, inip=inip, scalep=-1.,
                                         g_tdp=rhsp, bcs_ini=inicdbcvals,
                                         check_ff_maxv=check_ff_maxv, **icd)

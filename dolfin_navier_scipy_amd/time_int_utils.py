@@ -50,12 +50,14 @@ LAST_RUN = {}
 
 
 def _record_run(name, system, stepper, feedback=None, fb_logs=None,
-                rec=None, flog=None):
+                rec=None, flog=None, slog=None):
     """`feedback`: 'resident' (observer on the device), 'host' (a
     `dynamic_rhs` called every step) or None (open loop); `fb_logs`: the
     `(y, u)` rows of the AB2 steps where the loop knows them; `rec`: the
     `_DeviceRecord` of a loop whose trajectory the device wrote down; `flog`:
-    the `_FunctionalLog` of a loop with `resident=dict(functionals=...)`"""
+    the `_FunctionalLog` of a loop with `resident=dict(functionals=...)`;
+    `slog`: the `_StatisticsSums` of one with `resident=dict(statistics=...)`
+    """
     LAST_RUN.clear()
     try:        # (runs in a `finally`: never in the way of the real error)
         ylog, ulog = fb_logs if fb_logs is not None else (None, None)
@@ -68,6 +70,9 @@ def _record_run(name, system, stepper, feedback=None, fb_logs=None,
             LAST_RUN.update(functionals=fy, functionals_t=ft,
                             functionals_on=flog.where,
                             functionals_names=flog.names)
+        if slog is not None:
+            LAST_RUN.update(statistics=slog.result(),
+                            statistics_on=slog.where)
         LAST_RUN.update(
             integrator=name, time_steps=stepper.total_steps,
             krylov_steps=stepper.total_iters,
@@ -370,6 +375,45 @@ def _functional_log(rsd, stepper, dt, moving, ndbc=0):
     return _FunctionalLog(stepper, fn, dt)
 
 
+class _StatisticsSums(object):
+    """`resident=dict(statistics=fs)` of `cnab` / `sbdftwo`, `fs` a
+    `fem.FlowStatistics`: arms the stepper's statistics per slice (or chunk)
+    next to the tables -- a bin table each, the sums go on -- and downloads
+    them ONCE, when the loop ends, into `fs`; where the loop takes one step at
+    a time the same states go through `fs.add` on the host.  The Heun start is
+    a host step on both paths (`start`): both count the same states"""
+
+    def __init__(self, stepper, fs):
+        self.stepper, self.fs = stepper, fs
+        self.where = None
+        self.armed = False
+
+    def start(self, v, p, time):
+        self.fs.add(v, p, time)
+
+    def arm(self, times):
+        self.stepper.set_statistics(self.fs.bins(times), nbins=self.fs.nbins,
+                                    pairs=self.fs.pairs, reset=False)
+        self.armed = True
+        self.where = 'device'
+
+    def collect(self, times):
+        pass
+
+    def host_row(self, v, p, time):
+        self.fs.add(v, p, time)
+        self.where = 'host'
+
+    def finish(self):
+        if self.armed:
+            self.fs.add_sums(self.stepper.statistics())
+            self.armed = False
+
+    def result(self):
+        return {k: (None if a is None else np.array(a))
+                for k, a in self.fs.sums().items()}
+
+
 # boundary values, the terms `applybcs` makes of them, the forcing at one time
 _Terms = collections.namedtuple('_Terms', 'bcs bfv mbc fv')
 
@@ -409,19 +453,24 @@ class _ResidentSlices(object):
         self.drec = _DeviceRecord(stepper, rsd, stepper.sys.NV,
                                   stepper.sys.NP) \
             if (self.on_device and rsd.get('record', False)) else None
-        self.flog = self.rfb = None
+        self.flog = self.rfb = self.slog = None
         self.attachments = []
 
     def attach(self, lti, c_n, c_c, drm, tstart):
-        """the functionals and, for a `LinearFeedback` that can run resident,
-        the observer (inside the loop's `try`: both may refuse)"""
+        """the functionals, the statistics and, for a `LinearFeedback` that
+        can run resident, the observer (inside the loop's `try`: they may
+        refuse)"""
         self.flog = _functional_log(
             self.rsd, self.stepper, self.dt, self.moving,
             len(self.statvals) + self.nbcs)
         if lti is not None and self.on_device:
             self.rfb = _ResidentFeedback(lti, self.stepper, drm, c_n, c_c,
                                          self.dt, tstart)
-        self.attachments = [a for a in (self.rfb, self.flog) if a is not None]
+        fs = self.rsd.get('statistics', None)
+        if fs is not None:
+            self.slog = _StatisticsSums(self.stepper, fs)
+        self.attachments = [a for a in (self.rfb, self.flog, self.slog)
+                            if a is not None]
 
     def run(self, ctrange):
         """the whole slice: tabulate what the callbacks return, upload,
@@ -654,6 +703,17 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                         (g - g_prev)/dt` go by the values of each state, on
                         the device with `bcs_time_only` (a table of their own
                         per slice), on the host otherwise
+      `statistics`      a `fem.FlowStatistics`: running sums (mean, second
+                        moments, products of listed pairs, by bins) of the
+                        state `[v; p]` after the Heun start and after every
+                        AB2 / BDF2 step, `trange[1:]`, added on the device
+                        where the loop runs resident
+                        (`ImexStepper.set_statistics`: a bin table per slice,
+                        ONE download when the loop ends), through `fs.add` on
+                        the host otherwise; the sums end up in the object
+                        itself (on top of what it held) and, as a dict, in
+                        `LAST_RUN['statistics']`; `['statistics_on']` says
+                        'device' or 'host'
     `LAST_RUN['record']` says 'device' or 'host', `LAST_RUN['run_calls']`
     counts the `stepper.run` calls of the loop.
     The per-step data the callbacks return (`f_tdp`, `g_tdp`, `applybcs`) are
@@ -713,6 +773,8 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
     statvals, moving = rs.statvals, rs.moving
     try:
         rs.attach(lti if fb_dev else None, .5, .5, drm, trange[1])
+        if rs.slog is not None:
+            rs.slog.start(v_n, p_n, trange[1])
         for kck, ctrange in enumerate(listofts):
             nrmvc = stepper.vnorm()
             if verbose:
@@ -750,12 +812,17 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                                      dbc_prev=statvals + list(bcs_c))
                 elif rs.flog is not None:
                     rs.flog.host_row(v_n, v_c, p_n, ctime)
+                if rs.slog is not None:
+                    rs.slog.host_row(v_n, p_n, ctime)
                 savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
         if rs.rfb is not None:
             rs.rfb.finish(drm)
+        if rs.slog is not None:
+            rs.slog.finish()
     finally:
         _record_run('cnab', system, stepper, *_feedback_record(
-            rs.rfb, lti, state_dependent), rec=rs.drec, flog=rs.flog)
+            rs.rfb, lti, state_dependent), rec=rs.drec, flog=rs.flog,
+                    slog=rs.slog)
         stepper.close()
         system.close()
     return v_n, p_n, ffflag
@@ -818,6 +885,8 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
     ffflag = 0
     try:
         rs.attach(lti if fb_dev else None, 2./3, 0., drm, trange[1])
+        if rs.slog is not None:
+            rs.slog.start(v_n, p_n, trange[1])
         for kck, ctrange in enumerate(listofts):
             nrmvc = np.linalg.norm(v_c)
             if nrmvc > check_ff_maxv or np.isnan(nrmvc):
@@ -854,12 +923,17 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
                                      dbc_prev=statvals + list(bcs_c))
                 elif rs.flog is not None:
                     rs.flog.host_row(v_n, v_c, p_n, ctime)
+                if rs.slog is not None:
+                    rs.slog.host_row(v_n, p_n, ctime)
                 savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
         if rs.rfb is not None:
             rs.rfb.finish(drm)
+        if rs.slog is not None:
+            rs.slog.finish()
     finally:
         _record_run('sbdftwo', system, stepper, *_feedback_record(
-            rs.rfb, lti, state_dependent), rec=rs.drec, flog=rs.flog)
+            rs.rfb, lti, state_dependent), rec=rs.drec, flog=rs.flog,
+                    slog=rs.slog)
         stepper.close()
         system.close()
     return v_n, p_n, ffflag

@@ -552,6 +552,32 @@ int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,
                              double *out);
 /* functionals off (the step is what it was before) */
 int dns_imex_clear_functionals(dns_imex *st);
+/* Flow statistics (time averages, variances, Reynolds stresses; phase
+ * averages and batch means by bins) as running sums on the device: the next
+ * nrows steps (dns_imex_step and dns_imex_run alike) add the state they leave,
+ * x_r = [v; pscale * p~] of row r -- what dns_imex_get_state returns after the
+ * (r+1)-th step after this call --, to the sums of bin b = bin[r] (-1: the
+ * step is skipped; nbins in 1..256):
+ *     N_b += 1,  S1_b[i] += x_r[i],  S2_b[i] += x_r[i]^2     (i < NV + NP),
+ *     SX_b[q] += x_r[pair_i[q]] * x_r[pair_j[q]]             (q < npairs)
+ * with index pairs into [0, NV + NP) (npairs 0: none).  One kernel per step,
+ * no atomics, the rows of a bin in step order: the same bits however the steps
+ * are split into calls; S1 is plain additions.  A row is added once, whoever
+ * launches for it a second time, and a batch dns_imex_run restores and repeats
+ * adds to the sums it started from.  The sums are kept across calls with the
+ * same nbins and pairs and reset == 0 (the slices of a time loop set a bin
+ * table each and go on summing), zeroed otherwise.  Every check comes first: a
+ * refused call leaves the statistics that were there.  Resets the step counter
+ * like dns_imex_set_rhs_table.  Not on a row-partitioned stepper. */
+int dns_imex_set_stats(dns_imex *st, int32_t nrows, const int32_t *bin,
+                       int32_t nbins, int32_t npairs, const int32_t *pair_i,
+                       const int32_t *pair_j, int32_t reset);
+/* bins [first_bin, first_bin + count): counts (count), s1 and s2 (count x
+ * (NV + NP), unpadded), sx (count x npairs); NULL outputs are skipped */
+int dns_imex_get_stats(dns_imex *st, int32_t first_bin, int32_t count,
+                       double *counts, double *s1, double *s2, double *sx);
+/* statistics off (the step is what it was before) */
+int dns_imex_clear_stats(dns_imex *st);
 /* ||v||_2 of the current velocity (blow-up guard, tiu:94-103) */
 int dns_imex_vnorm(dns_imex *st, double *out);
 

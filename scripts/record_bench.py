@@ -32,6 +32,13 @@ One command per leg (profiles/r08_recorder/README.md):
                   device snapshot of every step, ONE download, then
                   `MomentumFunctionals.evaluate(..., dbc=, dbc_prev=)` per
                   step on the host (profiles/r12_functionals_bc/README.md)
+  --leg stats     `run(steps)` with the flow statistics on the device (one bin,
+                  `fem.component_pairs` of the whole mesh:
+                  `ImexStepper.set_statistics`), then ONE download of the sums
+  --leg stats_by_record  what there is without them: a device snapshot of
+                  every step, ONE download, the same sums by NumPy
+  --leg stats_stepwise   `run(1)` + `get_state()` + `FlowStatistics.add` per
+                  step (profiles/r13_statistics/README.md)
   --refine R      the same legs on the mesh refined R times (multigrid Schur
                   block, dt = 1/(512 2^R), start from rest, as refined_bench.py)
 
@@ -371,12 +378,105 @@ def leg_moving_host(su, steps, spin):
     return _leg_moving(su, steps, spin, 'host')
 
 
+def _flow_statistics(su):
+    from dolfin_navier_scipy_amd import fem
+    return fem.FlowStatistics(pairs=fem.component_pairs(
+        su.femp['V'], su.femp['invinds']))
+
+
+def leg_stats(su, steps, spin):
+    stp, cf, opts, close = su.stepper()
+    try:
+        fs = _flow_statistics(su)
+        # (set before the spin-up, rows for up to three windows: as
+        # _leg_recorded; the spin-up and repeated windows go into no bin)
+        rows = spin + 3*steps
+        stp.set_statistics(-np.ones(rows, dtype=np.int32), nbins=1,
+                           pairs=fs.pairs)
+        stp.run(spin, cf, opts)
+        for n in range(1, 4):
+            bins = -np.ones(rows, dtype=np.int32)
+            bins[:steps] = 0
+            # (the same buffers: the graphs of the spin-up are replayed)
+            stp.set_statistics(bins, nbins=1, pairs=fs.pairs, reset=True)
+            secs, its, _ = stp.run(steps, cf, opts)
+            if stp.last_run['captures'] == 0:
+                break
+        out = _record(stp, steps, secs, its)
+        out['windows'] = n
+        t0 = time.perf_counter()
+        sums = stp.statistics()
+        dl = time.perf_counter() - t0
+        fs.add_sums(sums)
+        nbytes = sum(int(a.nbytes) for a in sums.values())
+        out.update(download_seconds=dl, download_bytes=nbytes,
+                   steps_per_s_with_download=steps/(secs + dl),
+                   counts=fs.counts.tolist(), npairs=int(fs.pairs.shape[0]),
+                   mean_v_max=float(np.abs(fs.mean()[0]).max()),
+                   cov_max=float(np.abs(fs.covariance()).max()))
+    finally:
+        close()
+    return out
+
+
+def leg_stats_by_record(su, steps, spin):
+    stp, cf, opts, close = su.stepper()
+    try:
+        fs = _flow_statistics(su)
+        stp.set_recorder(spin + 3*steps, snap_slots='all')
+        stp.run(spin, cf, opts)
+        secs, its, n = _timed_window(stp, cf, opts, steps)
+        out = _record(stp, steps, secs, its)
+        out['windows'] = n
+        spin += (n - 1)*steps
+        t0 = time.perf_counter()
+        v, p = stp.record_snapshots(spin, steps)
+        dl = time.perf_counter() - t0
+        x = np.hstack([v, p])
+        fs.add_sums(dict(
+            counts=[steps], s1_v=v.sum(axis=0)[None, :],
+            s1_p=p.sum(axis=0)[None, :], s2_v=(v*v).sum(axis=0)[None, :],
+            s2_p=(p*p).sum(axis=0)[None, :],
+            sx=(x[:, fs.pairs[:, 0]]*x[:, fs.pairs[:, 1]]).sum(axis=0)[None, :]))
+        ev = time.perf_counter() - t0 - dl
+        out.update(download_seconds=dl, evaluate_seconds=ev,
+                   download_bytes=int(v.nbytes + p.nbytes),
+                   steps_per_s_with_download=steps/(secs + dl + ev),
+                   counts=fs.counts.tolist(),
+                   mean_v_max=float(np.abs(fs.mean()[0]).max()),
+                   cov_max=float(np.abs(fs.covariance()).max()))
+    finally:
+        close()
+    return out
+
+
+def leg_stats_stepwise(su, steps, spin):
+    stp, cf, opts, close = su.stepper()
+    try:
+        fs = _flow_statistics(su)
+        stp.run(spin, cf, opts)
+        t0 = time.perf_counter()
+        for k in range(steps):
+            stp.run(1, cf, opts)
+            v, p = stp.get_state()
+            fs.add(v, p, float(k))
+        secs = time.perf_counter() - t0
+        out = dict(seconds=secs, steps_per_s=steps/secs, vnorm=stp.vnorm(),
+                   counts=fs.counts.tolist(),
+                   mean_v_max=float(np.abs(fs.mean()[0]).max()),
+                   cov_max=float(np.abs(fs.covariance()).max()))
+    finally:
+        close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--leg', choices=('stepwise', 'open', 'snap', 'outputs',
                                       'forces', 'forces_stepwise',
                                       'moving_open', 'moving_forces',
-                                      'moving_host'),
+                                      'moving_host', 'stats',
+                                      'stats_by_record', 'stats_stepwise'),
                     required=True)
     ap.add_argument('--with-outputs', action='store_true',
                     help="leg forces: the recorder's y log on as well")
@@ -396,7 +496,9 @@ def main():
         import feedback_bench as fbb
         su = fbb.Setup()
     fn = dict(moving_open=leg_moving_open, moving_forces=leg_moving_forces,
-              moving_host=leg_moving_host,
+              moving_host=leg_moving_host, stats=leg_stats,
+              stats_by_record=leg_stats_by_record,
+              stats_stepwise=leg_stats_stepwise,
               stepwise=leg_stepwise, open=leg_open, snap=leg_snap,
               outputs=leg_outputs, forces_stepwise=leg_forces_stepwise,
               forces=(leg_forces_outputs if args.with_outputs
@@ -404,7 +506,7 @@ def main():
     reps = [fn(su, args.steps, args.spin) for _ in range(args.repeats)]
     key = 'steps_per_s_with_download' \
         if args.leg in ('snap', 'outputs', 'forces', 'moving_forces',
-                        'moving_host') \
+                        'moving_host', 'stats', 'stats_by_record') \
         else 'steps_per_s'
     rates = [r['steps_per_s'] for r in reps]
     out = dict(leg=args.leg, label=args.label, steps=args.steps,
