@@ -49,38 +49,57 @@ SOLVER = dict(method='gmres', rtol=None, maxiter=400, restart=60,
 LAST_RUN = {}
 
 
-def _record_run(name, system, stepper, feedback=None, fb_logs=None,
-                rec=None, flog=None, slog=None):
-    """`feedback`: 'resident' (observer on the device), 'host' (a
-    `dynamic_rhs` called every step) or None (open loop); `fb_logs`: the
-    `(y, u)` rows of the AB2 steps where the loop knows them; `rec`: the
-    `_DeviceRecord` of a loop whose trajectory the device wrote down; `flog`:
-    the `_FunctionalLog` of a loop with `resident=dict(functionals=...)`;
-    `slog`: the `_StatisticsSums` of one with `resident=dict(statistics=...)`
-    """
+def _record_run(name, system, stepper, reports=()):
+    """`reports`: what rode along with the loop (`_Attachment`s, a
+    `_DeviceRecord` or None); the keys of their `report()` go on top of those
+    of an open loop whose trajectory the host collected"""
     LAST_RUN.clear()
     try:        # (runs in a `finally`: never in the way of the real error)
-        ylog, ulog = fb_logs if fb_logs is not None else (None, None)
-        rec_y, rec_t = rec.result() if rec is not None else (None, None)
-        LAST_RUN.update(record='device' if rec is not None else 'host',
-                        run_calls=getattr(stepper, 'run_calls', 0),
-                        record_y=rec_y, record_t=rec_t)
-        if flog is not None:
-            fy, ft = flog.result()
-            LAST_RUN.update(functionals=fy, functionals_t=ft,
-                            functionals_on=flog.where,
-                            functionals_names=flog.names)
-        if slog is not None:
-            LAST_RUN.update(statistics=slog.result(),
-                            statistics_on=slog.where)
         LAST_RUN.update(
+            record='host', run_calls=getattr(stepper, 'run_calls', 0),
+            record_y=None, record_t=None,
             integrator=name, time_steps=stepper.total_steps,
             krylov_steps=stepper.total_iters,
             schur_hierarchy=getattr(system, 'schur_hierarchy', None),
-            precond=system.precond_info(), feedback=feedback,
-            feedback_y=ylog, feedback_u=ulog)
+            precond=system.precond_info(), feedback=None,
+            feedback_y=None, feedback_u=None)
+        for rep in reports:
+            LAST_RUN.update({} if rep is None else rep.report())
     except Exception:
         pass
+
+
+class _Attachment(object):
+    """What rides along with the loop of `cnab` / `sbdftwo`.  The loop calls
+    every attachment at the same places and never names one; each overrides
+    what it needs"""
+
+    def start(self, v, p, time):
+        """the state after the Heun start"""
+
+    def arm(self, times, tables):
+        """behind `set_rhs_table`, for the steps towards `times` of a slice
+        (or chunk) that runs on the device; `tables`: what the slice
+        tabulated beside the right-hand sides (`_Tables`)"""
+
+    def collect(self, times):
+        """after these steps have run on the device"""
+
+    def host_row(self, step):
+        """after a step with a host round trip (`_Step`)"""
+
+    def finish(self, drm):
+        """behind the last slice; `drm`: the memory dict of `dynamic_rhs`"""
+
+    def report(self):
+        """the keys it contributes to `LAST_RUN`"""
+        return {}
+
+
+# `dbc*`: where the boundary moves (else None), the Dirichlet values -- of the
+# state before each step and behind the last (`arm`), of the two states
+_Tables = collections.namedtuple('_Tables', 'dbc')
+_Step = collections.namedtuple('_Step', 'v v_prev p time dbc dbc_prev')
 
 
 class LinearFeedback(object):
@@ -159,7 +178,7 @@ class LinearFeedback(object):
         return self._out(t, mode, y, chx, memory)
 
 
-class _ResidentFeedback(object):
+class _ResidentFeedback(_Attachment):
     """the device side of a `LinearFeedback` inside `cnab` / `sbdftwo`: takes
     the observer over from the Heun start, tabulates the drift per slice,
     collects the logs and hands the final state back to the memory dict"""
@@ -174,10 +193,9 @@ class _ResidentFeedback(object):
         stepper.set_feedback_state(drm['lasthx'], drm['lastrhs'],
                                    fb.hc @ drm['lasthx'])
 
-    def arm(self, ctrange):
-        """after `set_rhs_table`, for the steps towards `ctrange`: the drift
-        the step towards `ctrange[s]` sees is the one at the time before it
-        (tiu:187-188)"""
+    def arm(self, ctrange, tables):
+        """the drift the step towards `ctrange[s]` sees is the one at the
+        time before it (tiu:187-188)"""
         befores = [self.tlast] + list(ctrange[:-1])
         drift = None if self.fb._drift is None else \
             np.array([self.fb.drift(t)[:, 0] for t in befores])
@@ -189,31 +207,33 @@ class _ResidentFeedback(object):
         self.ylog.append(y)
         self.ulog.append(u)
 
-    def logs(self):
-        if not self.ylog:
-            return np.zeros((0, self.fb.Ny)), np.zeros((0, self.fb.Nu))
-        return np.vstack(self.ylog), np.vstack(self.ulog)
-
     def finish(self, drm):
         hx, flast, _ = self.stepper.feedback_state()
         drm.update(dict(lastt=self.tlast, lasthx=hx.reshape((-1, 1)),
                         lastrhs=flast.reshape((-1, 1)), lastdt=self.dt))
 
-
-def _feedback_record(rfb, lti, state_dependent):
-    """`feedback=` and `fb_logs=` of `_record_run`"""
-    if rfb is not None:
-        return 'resident', rfb.logs()
-    if lti is not None:
-        return 'host', _host_feedback_logs(lti)
-    return ('host' if state_dependent else None), None
+    def report(self):
+        y = np.vstack(self.ylog) if self.ylog else np.zeros((0, self.fb.Ny))
+        u = np.vstack(self.ulog) if self.ulog else np.zeros((0, self.fb.Nu))
+        return dict(feedback='resident', feedback_y=y, feedback_u=u)
 
 
-def _host_feedback_logs(fb):
-    rows = [h for h in fb.history if h[1] == 'abtwo']
-    if not rows:
-        return np.zeros((0, fb.Ny)), np.zeros((0, fb.Nu))
-    return np.array([h[2] for h in rows]), np.array([h[3] for h in rows])
+class _HostFeedback(_Attachment):
+    """a `dynamic_rhs` (or `f_tvdp`) the loop calls back every step: reports
+    only -- for a `LinearFeedback` `lti` the `(y, u)` rows of its AB2 steps"""
+
+    def __init__(self, lti):
+        self.lti = lti
+
+    def report(self):
+        fb = self.lti
+        if fb is None:
+            return dict(feedback='host')
+        rows = [h for h in fb.history if h[1] == 'abtwo']
+        y, u = ([h[k] for h in rows] for k in (2, 3))
+        return dict(feedback='host',
+                    feedback_y=np.array(y).reshape((-1, fb.Ny)),
+                    feedback_u=np.array(u).reshape((-1, fb.Nu)))
 
 
 RECORD_BYTES = 1 << 30      # default cap of a slice's snapshot buffer
@@ -312,27 +332,36 @@ class _DeviceRecord(object):
         y = np.vstack(self.ys) if self.ys else np.zeros((0, ny))
         return y, np.array(self.ts, dtype=np.float64)
 
+    def report(self):
+        rec_y, rec_t = self.result()
+        return dict(record='device', record_y=rec_y, record_t=rec_t)
 
-class _FunctionalLog(object):
+
+class _FunctionalLog(_Attachment):
     """`resident=dict(functionals=fn)` of `cnab` / `sbdftwo`: arms the
     stepper's functionals per slice (or chunk) next to the tables, collects
     the rows of the device's log and their times; where the loop takes one
     step at a time the same rows come from `fn.evaluate` on the host.  With
-    controlled (moving) Dirichlet values `arm` is handed their table rows --
-    one more than steps: the values of the state before each step and of the
-    state after the last --, `host_row` the values of the two states"""
+    controlled (moving) Dirichlet values `arm` takes their rows from `tables`
+    -- one more than steps --, `host_row` the values of the two states; the
+    loop has `ndbc` of them, static ones included, and the functionals'
+    boundary rows `cab`, `cmb` must be as wide, in that order"""
 
-    def __init__(self, stepper, fn, dt):
+    def __init__(self, stepper, fn, dt, ndbc=None):
+        if ndbc is not None and fn.inv is not None and fn.cab.shape[1] != ndbc:
+            raise ValueError(
+                '`functionals` with controlled (moving) Dirichlet values: '
+                'they were built for {0} Dirichlet dofs, the loop has {1} '
+                '(`static_dbcvals` then the controlled ones: build them with '
+                '`dbcinds` in that order)'.format(fn.cab.shape[1], ndbc))
         self.stepper, self.fn, self.dt = stepper, fn, dt
         self.ys, self.ts = [], []
         self.where = None
         self.names = None if fn is None else list(fn.names)
 
-    def arm(self, times, dbc_rows=None):
-        if dbc_rows is None:
-            self.stepper.set_functionals(self.fn, len(times), self.dt)
-            return
-        if len(dbc_rows) != len(times) + 1:
+    def arm(self, times, tables):
+        dbc_rows = tables.dbc
+        if dbc_rows is not None and len(dbc_rows) != len(times) + 1:
             raise ValueError('{0} steps need {1} rows of Dirichlet values, '
                              'got {2}'.format(len(times), len(times) + 1,
                                               len(dbc_rows)))
@@ -347,10 +376,10 @@ class _FunctionalLog(object):
         self.ys.append(np.asarray(rows, dtype=np.float64))
         self.ts.extend(times)
 
-    def host_row(self, v, v_prev, p, time, dbc=None, dbc_prev=None):
-        self.add(self.fn.evaluate(v, v_prev, p, self.dt, dbc=dbc,
-                                  dbc_prev=dbc_prev).reshape((1, -1)),
-                 [time])
+    def host_row(self, step):
+        self.add(self.fn.evaluate(step.v, step.v_prev, step.p, self.dt,
+                                  dbc=step.dbc, dbc_prev=step.dbc_prev
+                                  ).reshape((1, -1)), [step.time])
         self.where = 'host'
 
     def result(self):
@@ -358,24 +387,13 @@ class _FunctionalLog(object):
         y = np.vstack(self.ys) if self.ys else np.zeros((0, nf))
         return y, np.array(self.ts, dtype=np.float64)
 
-
-def _functional_log(rsd, stepper, dt, moving, ndbc=0):
-    """`ndbc`: static and controlled Dirichlet values of a loop with
-    controlled (`moving`) ones: the functionals' boundary rows `cab`, `cmb`
-    must be as wide, in that order"""
-    fn = rsd.get('functionals', None)
-    if fn is None:
-        return None
-    if moving and fn.inv is not None and fn.cab.shape[1] != ndbc:
-        raise ValueError(
-            '`functionals` with controlled (moving) Dirichlet values: they '
-            'were built for {0} Dirichlet dofs, the loop has {1} '
-            '(`static_dbcvals` then the controlled ones: build them with '
-            '`dbcinds` in that order)'.format(fn.cab.shape[1], ndbc))
-    return _FunctionalLog(stepper, fn, dt)
+    def report(self):
+        fy, ft = self.result()
+        return dict(functionals=fy, functionals_t=ft,
+                    functionals_on=self.where, functionals_names=self.names)
 
 
-class _StatisticsSums(object):
+class _StatisticsSums(_Attachment):
     """`resident=dict(statistics=fs)` of `cnab` / `sbdftwo`, `fs` a
     `fem.FlowStatistics`: arms the stepper's statistics per slice (or chunk)
     next to the tables -- a bin table each, the sums go on -- and downloads
@@ -391,53 +409,87 @@ class _StatisticsSums(object):
     def start(self, v, p, time):
         self.fs.add(v, p, time)
 
-    def arm(self, times):
+    def arm(self, times, tables):
         self.stepper.set_statistics(self.fs.bins(times), nbins=self.fs.nbins,
                                     pairs=self.fs.pairs, reset=False)
         self.armed = True
         self.where = 'device'
 
-    def collect(self, times):
-        pass
-
-    def host_row(self, v, p, time):
-        self.fs.add(v, p, time)
+    def host_row(self, step):
+        self.fs.add(step.v, step.p, step.time)
         self.where = 'host'
 
-    def finish(self):
+    def finish(self, drm):
         if self.armed:
             self.fs.add_sums(self.stepper.statistics())
             self.armed = False
 
-    def result(self):
-        return {k: (None if a is None else np.array(a))
+    def report(self):
+        sums = {k: (None if a is None else np.array(a))
                 for k, a in self.fs.sums().items()}
+        return dict(statistics=sums, statistics_on=self.where)
 
 
-# boundary values, the terms `applybcs` makes of them, the forcing at one time
-_Terms = collections.namedtuple('_Terms', 'bcs bfv mbc fv')
+# boundary values, the terms `applybcs` makes of them, the forcing and what
+# `dynamic_rhs` returned at one time; `dfv` is the float 0. where the loop runs
+# resident: there the actuation, if any, is added on the device
+_Terms = collections.namedtuple('_Terms', 'bcs bfv mbc fv dfv')
+
+# What tells the schemes apart, as data: the system is `M + theta*dt*A`;
+# `r1(M, A, dt)`; `coeffs(dt)`: `a_c, a_p, cn_c, cn_o` of `dns_imex_coeffs`;
+# `fb_weights`: `(c_n, c_c)` of a resident `LinearFeedback`; `row(dt, prev,
+# cur, nxt)`: the scheme's ONE formula of a step's `gvec` -- everything that is
+# not `R1 v` or convection -- from the `_Terms` at the two times before it and
+# at its own; `keep_prev`: the state before a slice's last step is a stop;
+# `state_v_p`: `set_state` gets the velocity before the Heun start;
+# `guard_prev`: the blow-up guard looks at the velocity BEFORE the last step
+# and logs nothing (reference quirk, tiu:311), else at `stepper.vnorm()`
+_Scheme = collections.namedtuple(
+    '_Scheme', 'name theta r1 coeffs fb_weights row keep_prev state_v_p '
+    'guard_prev')
+
+_CNAB = _Scheme(
+    name='cnab', theta=.5, r1=lambda M, A, dt: (M - .5*dt*A).tocsr(),
+    coeffs=lambda dt: dict(a_c=1., a_p=0., cn_c=1.5*dt, cn_o=-.5*dt),
+    fb_weights=(.5, .5),
+    row=lambda dt, p, c, n: (-(n.mbc - c.mbc)
+                             + .5*dt*(c.fv + n.fv + n.bfv + c.bfv
+                                      + n.dfv + c.dfv)),
+    keep_prev=False, state_v_p=False, guard_prev=False)
+
+_SBDF2 = _Scheme(
+    name='sbdftwo', theta=2./3, r1=lambda M, A, dt: M,
+    coeffs=lambda dt: dict(a_c=4./3, a_p=-1./3, cn_c=4./3*dt, cn_o=-2./3*dt),
+    fb_weights=(2./3, 0.),
+    row=lambda dt, p, c, n: (-(n.mbc - 4/3*c.mbc + 1/3*p.mbc)
+                             + 2/3*dt*n.bfv + 2/3*dt*(n.fv + n.dfv)),
+    keep_prev=True, state_v_p=True, guard_prev=True)
 
 
-class _ResidentSlices(object):
-    """What `cnab` and `sbdftwo` share where they run resident: how they read
-    `resident=`, and a time slice as tabulate / upload / replay / collect.
-    The scheme hands over what differs: `row(prev, cur, nxt)`, the `gvt` row
-    of a step from the `_Terms` at the two times before it and at its own,
-    and `keep_prev`, whether the state before a slice's last step is a stop"""
+class _ImexLoop(object):
+    """The AB2 / BDF2 steps of `cnab` and `sbdftwo` behind the Heun start: how
+    `resident=` is read, the terms of the last two times (`prev`, `cur`) and
+    the last two states, a time slice on the device as tabulate / upload /
+    replay / collect (`run_slice`), a step with a host round trip (`step`),
+    and the slices one after the other (`march`).  What differs between the
+    schemes is in `scheme`; what rides along is in `attachments`"""
 
-    def __init__(self, stepper, cf, opts, dt, resident, conv, bcs_ini,
-                 state_dependent, prev=None, cur=None, row=None,
-                 keep_prev=False, getbcs=None, applybcs=None, appndbcs=None,
-                 f_tdp=None, g_tdp=None, savevp=None):
-        self.stepper, self.cf, self.opts, self.dt = stepper, cf, opts, dt
-        self.conv, self.row, self.keep_prev = conv, row, keep_prev
-        self.prev, self.cur = prev, cur
+    def __init__(self, scheme, stepper, cf, opts, dt, resident, conv, bcs_ini,
+                 state_dependent, prev=None, cur=None, v_c=None, v_n=None,
+                 p_n=None, drm=None, getbcs=None, applybcs=None,
+                 appndbcs=None, f_tdp=None, g_tdp=None, f_vdp=None,
+                 dynamic_rhs=None, savevp=None):
+        self.scheme, self.stepper, self.cf = scheme, stepper, cf
+        self.opts = opts
+        self.dt, self.conv, self.state_dependent = dt, conv, state_dependent
+        # (`v_c`: the velocity before the last step, `v_n`, `p_n`: the state)
+        self.v_c, self.v_n, self.p_n, self.drm = v_c, v_n, p_n, drm
         self.getbcs, self.applybcs, self.appndbcs = getbcs, applybcs, appndbcs
-        self.f_tdp, self.g_tdp, self.savevp = f_tdp, g_tdp, savevp
+        self.f_tdp, self.g_tdp, self.f_vdp = f_tdp, g_tdp, f_vdp
+        self.dynamic_rhs, self.savevp = dynamic_rhs, savevp
         self.rsd = rsd = dict(resident or {})
         self.statvals = list(rsd.get('static_dbcvals', []) or [])
         self.moving = len(bcs_ini) > 0
-        self.nbcs = len(bcs_ini)
         if conv is not None:
             stepper.set_convection(conv, scale=-1.0)
             if self.moving or self.statvals:
@@ -446,6 +498,8 @@ class _ResidentSlices(object):
                           and not state_dependent
                           and (not self.moving
                                or rsd.get('bcs_time_only', False)))
+        self.prev = prev
+        self.cur = cur._replace(dfv=0.) if self.on_device else cur
         savetimes = rsd.get('savevp_times', None)
         self.savetimes = None if savetimes is None else set(savetimes)
         # `record=True`: the device writes the trajectory down (where the loop
@@ -453,61 +507,80 @@ class _ResidentSlices(object):
         self.drec = _DeviceRecord(stepper, rsd, stepper.sys.NV,
                                   stepper.sys.NP) \
             if (self.on_device and rsd.get('record', False)) else None
-        self.flog = self.rfb = self.slog = None
         self.attachments = []
 
-    def attach(self, lti, c_n, c_c, drm, tstart):
-        """the functionals, the statistics and, for a `LinearFeedback` that
-        can run resident, the observer (inside the loop's `try`: they may
-        refuse)"""
-        self.flog = _functional_log(
-            self.rsd, self.stepper, self.dt, self.moving,
-            len(self.statvals) + self.nbcs)
-        if lti is not None and self.on_device:
-            self.rfb = _ResidentFeedback(lti, self.stepper, drm, c_n, c_c,
-                                         self.dt, tstart)
+    def attach(self, lti, fb_dev, tstart):
+        """the functionals, the statistics and the feedback -- a
+        `LinearFeedback` `lti` that can run resident (`fb_dev`) as the
+        observer on the device -- in the order they are armed in (inside the
+        loop's `try`: they may refuse)"""
+        resident_fb = fb_dev and self.on_device
+        if not resident_fb and (lti is not None or self.state_dependent):
+            self.attachments.append(_HostFeedback(lti))
+        fn = self.rsd.get('functionals', None)
+        flog = None if fn is None else _FunctionalLog(
+            self.stepper, fn, self.dt,
+            ndbc=len(self._dbc(self.cur)) if self.moving else None)
+        if resident_fb:
+            self.attachments.append(_ResidentFeedback(
+                lti, self.stepper, self.drm, *self.scheme.fb_weights,
+                dt=self.dt, tstart=tstart))
         fs = self.rsd.get('statistics', None)
-        if fs is not None:
-            self.slog = _StatisticsSums(self.stepper, fs)
-        self.attachments = [a for a in (self.rfb, self.flog, self.slog)
-                            if a is not None]
+        self.attachments += [a for a in (
+            flog, None if fs is None else _StatisticsSums(self.stepper, fs))
+            if a is not None]
 
-    def run(self, ctrange):
-        """the whole slice: tabulate what the callbacks return, upload,
-        replay; the host sees the `stop_steps` only, `savevp` the save times.
-        Returns `{step of the slice: (v, p)}` of the stops"""
-        stepper, statvals, moving = self.stepper, self.statvals, self.moving
+    def _terms_at(self, ctime, v_c=None, p_c=None):
+        """the callbacks of the step towards `ctime` behind `f_vdp`, in the
+        reference's order (tiu:114-120, 330-336); with the state the step
+        starts from `dynamic_rhs` as well, without it (a slice is tabulated
+        ahead of its states) `getbcs` sees `None, None`.  Returns the `_Terms`
+        and the lower right-hand side"""
+        vfull = None if v_c is None else self.appndbcs(v_c, self.cur.bcs)
+        bcs_n = self.getbcs(ctime, vfull, p_c, mode='abtwo')
+        bfv_n, bfp_n, mbc_n = self.applybcs(bcs_n)
+        fv_n, fp_n = self.f_tdp(ctime), self.g_tdp(ctime)
+        dfv_n = 0.
+        if v_c is not None:
+            dfv_n, self.drm = self.dynamic_rhs(ctime, vc=v_c, memory=self.drm,
+                                               mode='abtwo')
+        return (_Terms(bcs_n, bfv_n, mbc_n, fv_n, dfv_n),
+                _col(fp_n + bfp_n, self.stepper.sys.NP))
+
+    def _dbc(self, terms):
+        return self.statvals + list(terms.bcs)
+
+    def run_slice(self, ctrange):
+        """the whole slice on the device: tabulate what the callbacks return,
+        upload, replay; the host sees the `stop_steps` only, `savevp` the save
+        times"""
+        stepper, moving = self.stepper, self.moving
         NV, NP = stepper.sys.NV, stepper.sys.NP
         ns = len(ctrange)
         gvt, gpt = np.empty((ns, NV)), np.empty((ns, NP))
-        dbt = np.empty((ns, len(statvals) + len(self.cur.bcs))) \
-            if moving else None
-        for s, ctime in enumerate(ctrange):
-            bcs_n = self.getbcs(ctime, None, None, mode='abtwo')
-            bfv_n, bfp_n, mbc_n = self.applybcs(bcs_n)
-            fv_n, fp_n = self.f_tdp(ctime), self.g_tdp(ctime)
-            nxt = _Terms(bcs_n, bfv_n, mbc_n, fv_n)
-            gvt[s] = _col(self.row(self.prev, self.cur, nxt), NV)[:, 0]
-            gpt[s] = _col(fp_n + bfp_n, NP)[:, 0]
-            if moving:       # N(v_c) sees the CURRENT boundary values
-                dbt[s] = statvals + list(self.cur.bcs)
-            self.prev, self.cur = self.cur, nxt
-        bcs_n = self.cur.bcs
-        span = [0, 0]
         # (the functionals see the values of the state a step LEAVES: one row
         # more, the values behind the slice's last step)
-        dbt_end = np.vstack([dbt, [statvals + list(bcs_n)]]) if moving \
-            else None
+        dbt = np.empty((ns + 1, len(self._dbc(self.cur)))) if moving else None
+        for s, ctime in enumerate(ctrange):
+            nxt, gp = self._terms_at(ctime)
+            gvt[s] = _col(self.scheme.row(self.dt, self.prev, self.cur, nxt),
+                          NV)[:, 0]
+            gpt[s] = gp[:, 0]
+            if moving:       # N(v_c) sees the CURRENT boundary values
+                dbt[s] = self._dbc(self.cur)
+            self.prev, self.cur = self.cur, nxt
+        bcs_n = self.cur.bcs
+        if moving:
+            dbt[ns] = self._dbc(self.cur)
+        span = [0, 0]
 
         def upload(a, b):
             stepper.set_rhs_table(gvt[a:b], gpt[a:b])
             if moving:
                 self.conv.set_dbc_table(dbt[a:b])
+            tables = _Tables(dbt[a:b + 1] if moving else None)
             for att in self.attachments:
-                if att is self.flog and moving:
-                    att.arm(ctrange[a:b], dbt_end[a:b + 1])
-                else:
-                    att.arm(ctrange[a:b])
+                att.arm(ctrange[a:b], tables)
             span[:] = [a, b]
 
         def after_chunk():
@@ -517,25 +590,81 @@ class _ResidentSlices(object):
             # the device writes the slice down; the host collects it
             states = self.drec.run_slice(
                 self.cf, self.opts, ctrange, self.savetimes, upload,
-                keep_prev=self.keep_prev, after_chunk=after_chunk)
+                keep_prev=self.scheme.keep_prev, after_chunk=after_chunk)
         else:
             upload(0, ns)
             states, done = {}, 0
-            for s in stop_steps(ctrange, self.savetimes, self.keep_prev):
+            for s in stop_steps(ctrange, self.savetimes,
+                                self.scheme.keep_prev):
                 stepper.run(s + 1 - done, self.cf, self.opts)
                 done = s + 1
                 states[s] = stepper.get_state()
             after_chunk()
         for s, ctime in enumerate(ctrange):
             if self.savetimes is None or ctime in self.savetimes:
-                bcs_at = dbt[s + 1][len(statvals):].tolist() \
+                bcs_at = dbt[s + 1][len(self.statvals):].tolist() \
                     if (moving and s + 1 < ns) else bcs_n
                 self.savevp(self.appndbcs(states[s][0], bcs_at),
                             states[s][1], time=ctime)
         if moving:
-            self.conv.set_dbcvals(statvals + list(bcs_n))
+            self.conv.set_dbcvals(self._dbc(self.cur))
         stepper.set_rhs(_col(0., NV), _col(0., NP))
-        return states
+        if self.scheme.keep_prev:
+            self.v_c = states[ns - 2][0] if ns > 1 else self.v_n
+        self.v_n, self.p_n = states[ns - 1]
+
+    def step(self, ctime):
+        """one step with a host round trip: each callback of the reference's
+        step, in its order (tiu:104-143, 320-353)"""
+        stepper, conv, cur = self.stepper, self.conv, self.cur
+        v_c, p_c = self.v_n, self.p_n
+        if conv is not None and (self.moving or self.statvals):
+            conv.set_dbcvals(self._dbc(cur))
+        nfc_new = None if conv is not None \
+            else self.f_vdp(self.appndbcs(v_c, cur.bcs))
+        nxt, gp = self._terms_at(ctime, v_c, p_c)
+        gvec = self.scheme.row(self.dt, self.prev, cur, nxt)
+        stepper.set_rhs(_col(gvec, stepper.sys.NV), gp)
+        stepper.step(self.cf, nfc_new=nfc_new, opts=self.opts)
+        v_n, p_n = stepper.get_state()
+        row = _Step(v_n, v_c, p_n, ctime,
+                    self._dbc(nxt) if self.moving else None,
+                    self._dbc(cur) if self.moving else None)
+        for att in self.attachments:
+            att.host_row(row)
+        self.savevp(self.appndbcs(v_n, nxt.bcs), p_n, time=ctime)
+        self.prev, self.cur = cur, nxt
+        self.v_c, self.v_n, self.p_n = v_c, v_n, p_n
+
+    def _blown_up(self, kck, ntimeslices, check_ff_maxv, verbose):
+        """the blow-up guard at a slice's start"""
+        quiet = self.scheme.guard_prev
+        nrmvc = np.linalg.norm(self.v_c) if quiet else self.stepper.vnorm()
+        if verbose and not quiet:
+            logging.info('time {0}/{1} -- |v| {2:.2e}'.format(
+                kck, ntimeslices, nrmvc))
+        blown = nrmvc > check_ff_maxv or np.isnan(nrmvc)
+        if blown and not quiet:
+            logging.warning('BREAK: |v| is `NaN` or |v| > threshhold')
+        return blown
+
+    def march(self, tstart, listofts, ntimeslices, check_ff_maxv, verbose):
+        """all slices; returns `ffflag`"""
+        ffflag = 0
+        for att in self.attachments:
+            att.start(self.v_n, self.p_n, tstart)
+        for kck, ctrange in enumerate(listofts):
+            if self._blown_up(kck, ntimeslices, check_ff_maxv, verbose):
+                ffflag = 1
+                break
+            if self.on_device and len(ctrange) > 0:
+                self.run_slice(ctrange)
+            else:
+                for ctime in ctrange:
+                    self.step(ctime)
+        for att in self.attachments:
+            att.finish(self.drm)
+        return ffflag
 
 
 def _checkuniformgrid(trange):
@@ -653,6 +782,64 @@ def _onestepheun(vc=None, pc=None, tc=None, tn=None, M=None, A=None, J=None,
             drm)
 
 
+def _imex_loop(scheme, trange, inivel, inip, bcs_ini, M, A, J, f_vdp, f_tdp,
+               g_tdp, scalep, getbcs, applybcs, appndbcs, savevp, dynamic_rhs,
+               dynamic_rhs_memory, check_ff_maxv, ntimeslices, verbose, solver,
+               device_convection, invinds, resident, f_tvdp=None):
+    """`cnab` / `sbdftwo` with their keywords (`scheme`: `_CNAB` / `_SBDF2`):
+    the Heun start on the host, the constant system and the stepper on the
+    device, then the slices of `_ImexLoop`"""
+    prm = _solver_settings(solver)
+    # a `LinearFeedback` is evaluated on the device with the step itself
+    lti = dynamic_rhs if isinstance(dynamic_rhs, LinearFeedback) else None
+    fb_dev = (lti is not None and f_tvdp is None
+              and device_convection is not None and resident is not None)
+    state_dependent = (dynamic_rhs is not None and not fb_dev) \
+        or f_tvdp is not None
+    dt, listofts = _inittimegrid(trange, ntimeslices=ntimeslices)
+    NP, NV = J.shape
+    if device_convection is not None and f_vdp is None:
+        f_vdp = device_convection.host_callback(invinds)   # Heun start only
+    dynamic_rhs, f_vdp = _wrap_callbacks(NV, dynamic_rhs, f_tvdp, f_vdp)
+    dfv_c, drm = dynamic_rhs(trange[0], vc=inivel, memory=dynamic_rhs_memory,
+                             mode='init')
+    savevp(appndbcs(inivel, bcs_ini), inip, time=trange[0])
+    (v_n, p_n, bcs_n, bfv_n, mbc_c, mbc_n, fv_n, nfc_c, nfc_n, dfv_n,
+     drm) = _onestepheun(vc=inivel, pc=inip, tc=trange[0], tn=trange[1],
+                         M=M, A=A, J=J, scalep=scalep, dfv_c=dfv_c,
+                         dynamic_rhs=dynamic_rhs, drm=drm, bcs_c=bcs_ini,
+                         applybcs=applybcs, appndbcs=appndbcs, getbcs=getbcs,
+                         f_tdp=f_tdp, f_vdp=f_vdp, g_tdp=g_tdp)
+    savevp(appndbcs(v_n, bcs_n), p_n, time=trange[1])
+
+    # the constant system of the loop, factor-once in the reference (tiu:89-91)
+    M, A = sps.csr_matrix(M), sps.csr_matrix(A)
+    system, opts = _device_system((M + scheme.theta*dt*A).tocsr(), J, prm)
+    stepper = ImexStepper(system, scheme.r1(M, A, dt))
+    cf = ImexStepper.coeffs(pscale=scalep/dt, extrapolate=prm['extrapolate'],
+                            carry_residual=prm['carry_residual'],
+                            **scheme.coeffs(dt))
+    stepper.set_state(v_n, v_p=inivel if scheme.state_v_p else None,
+                      ptilde_c=p_n*dt/scalep, nfc_c=nfc_c)
+    loop = _ImexLoop(
+        scheme, stepper, cf, opts, dt, resident, device_convection, bcs_ini,
+        state_dependent, prev=_Terms(None, None, mbc_c, None, None),
+        cur=_Terms(bcs_n, bfv_n, mbc_n, fv_n, dfv_n), v_c=inivel, v_n=v_n,
+        p_n=p_n, drm=drm, getbcs=getbcs, applybcs=applybcs,
+        appndbcs=appndbcs, f_tdp=f_tdp, g_tdp=g_tdp, f_vdp=f_vdp,
+        dynamic_rhs=dynamic_rhs, savevp=savevp)
+    try:
+        loop.attach(lti, fb_dev, trange[1])
+        ffflag = loop.march(trange[1], listofts, ntimeslices, check_ff_maxv,
+                            verbose)
+    finally:
+        _record_run(scheme.name, system, stepper,
+                    [loop.drec] + loop.attachments)
+        stepper.close()
+        system.close()
+    return loop.v_n, loop.p_n, ffflag
+
+
 def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
          M=None, A=None, J=None, f_vdp=None, f_tdp=None, g_tdp=None,
          f_tvdp=None, scalep=-1., getbcs=None, applybcs=None, appndbcs=None,
@@ -729,103 +916,7 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
     `['feedback_u']` hold the outputs and inputs of the AB2 steps.
     Returns `v_n, p_n, ffflag` like the reference.
     """
-    prm = _solver_settings(solver)
-    # a `LinearFeedback` is evaluated on the device with the step itself
-    lti = dynamic_rhs if isinstance(dynamic_rhs, LinearFeedback) else None
-    fb_dev = (lti is not None and f_tvdp is None
-              and device_convection is not None and resident is not None)
-    state_dependent = (dynamic_rhs is not None and not fb_dev) \
-        or f_tvdp is not None
-    dt, listofts = _inittimegrid(trange, ntimeslices=ntimeslices)
-    NP, NV = J.shape
-    ffflag = 0
-    if device_convection is not None and f_vdp is None:
-        f_vdp = device_convection.host_callback(invinds)   # Heun start only
-    dynamic_rhs, f_vdp = _wrap_callbacks(NV, dynamic_rhs, f_tvdp, f_vdp)
-    dfv_c, drm = dynamic_rhs(trange[0], vc=inivel, memory=dynamic_rhs_memory,
-                             mode='init')
-    savevp(appndbcs(inivel, bcs_ini), inip, time=trange[0])
-    (v_n, p_n, bcs_n, bfv_n, mbc_c, mbc_n, fv_n, nfc_c, nfc_n, dfv_n,
-     drm) = _onestepheun(vc=inivel, pc=inip, tc=trange[0], tn=trange[1],
-                         M=M, A=A, J=J, scalep=scalep, dfv_c=dfv_c,
-                         dynamic_rhs=dynamic_rhs, drm=drm, bcs_c=bcs_ini,
-                         applybcs=applybcs, appndbcs=appndbcs, getbcs=getbcs,
-                         f_tdp=f_tdp, f_vdp=f_vdp, g_tdp=g_tdp)
-    savevp(appndbcs(v_n, bcs_n), p_n, time=trange[1])
-
-    # the constant system of the loop, factor-once in the reference (tiu:89-91)
-    M, A = sps.csr_matrix(M), sps.csr_matrix(A)
-    system, opts = _device_system((M + .5*dt*A).tocsr(), J, prm)
-    stepper = ImexStepper(system, (M - .5*dt*A).tocsr())
-    cf = ImexStepper.coeffs(a_c=1., a_p=0., cn_c=1.5*dt, cn_o=-.5*dt,
-                            pscale=scalep/dt, extrapolate=prm['extrapolate'],
-                            carry_residual=prm['carry_residual'])
-    stepper.set_state(v_n, ptilde_c=p_n*dt/scalep, nfc_c=nfc_c)
-    # (a row: everything that is not `M v - dt/2 A v` or convection)
-    rs = _ResidentSlices(
-        stepper, cf, opts, dt, resident, device_convection, bcs_ini,
-        state_dependent, prev=_Terms(None, None, mbc_c, None),
-        cur=_Terms(bcs_n, bfv_n, mbc_n, fv_n),
-        row=lambda p, c, n: (-(n.mbc - c.mbc)
-                             + .5*dt*(c.fv + n.fv + n.bfv + c.bfv)),
-        getbcs=getbcs, applybcs=applybcs, appndbcs=appndbcs, f_tdp=f_tdp,
-        g_tdp=g_tdp, savevp=savevp)
-    statvals, moving = rs.statvals, rs.moving
-    try:
-        rs.attach(lti if fb_dev else None, .5, .5, drm, trange[1])
-        if rs.slog is not None:
-            rs.slog.start(v_n, p_n, trange[1])
-        for kck, ctrange in enumerate(listofts):
-            nrmvc = stepper.vnorm()
-            if verbose:
-                logging.info('time {0}/{1} -- |v| {2:.2e}'.format(
-                    kck, ntimeslices, nrmvc))
-            if nrmvc > check_ff_maxv or np.isnan(nrmvc):
-                logging.warning('BREAK: |v| is `NaN` or |v| > threshhold')
-                ffflag = 1
-                break
-            if rs.on_device and len(ctrange) > 0:
-                v_n, p_n = rs.run(ctrange)[len(ctrange) - 1]
-                continue
-            for ctime in ctrange:
-                v_c, p_c = v_n, p_n
-                bcs_c, bfv_c, mbc_c = bcs_n, bfv_n, mbc_n
-                fv_c, dfv_c = fv_n, dfv_n
-                if device_convection is not None and (moving or statvals):
-                    device_convection.set_dbcvals(statvals + list(bcs_c))
-                nfc_new = None if device_convection is not None \
-                    else f_vdp(appndbcs(v_c, bcs_c))
-                bcs_n = getbcs(ctime, appndbcs(v_c, bcs_c), p_c, mode='abtwo')
-                bfv_n, bfp_n, mbc_n = applybcs(bcs_n)
-                fv_n, fp_n = f_tdp(ctime), g_tdp(ctime)
-                dfv_n, drm = dynamic_rhs(ctime, vc=v_c, memory=drm,
-                                         mode='abtwo')
-                # everything that is not `M v - dt/2 A v` or convection
-                gvec = -(mbc_n - mbc_c) \
-                    + .5*dt*(fv_c + fv_n + bfv_n + bfv_c + dfv_n + dfv_c)
-                stepper.set_rhs(_col(gvec, NV), _col(fp_n + bfp_n, NP))
-                stepper.step(cf, nfc_new=nfc_new, opts=opts)
-                v_n, p_n = stepper.get_state()
-                if rs.flog is not None and moving:
-                    rs.flog.host_row(v_n, v_c, p_n, ctime,
-                                     dbc=statvals + list(bcs_n),
-                                     dbc_prev=statvals + list(bcs_c))
-                elif rs.flog is not None:
-                    rs.flog.host_row(v_n, v_c, p_n, ctime)
-                if rs.slog is not None:
-                    rs.slog.host_row(v_n, p_n, ctime)
-                savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
-        if rs.rfb is not None:
-            rs.rfb.finish(drm)
-        if rs.slog is not None:
-            rs.slog.finish()
-    finally:
-        _record_run('cnab', system, stepper, *_feedback_record(
-            rs.rfb, lti, state_dependent), rec=rs.drec, flog=rs.flog,
-                    slog=rs.slog)
-        stepper.close()
-        system.close()
-    return v_n, p_n, ffflag
+    return _imex_loop(_CNAB, **locals())
 
 
 def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
@@ -842,101 +933,9 @@ def sbdftwo(trange=None, inivel=None, inip=None, bcs_ini=[],
     the device operator, and whole time slices without a host round trip per
     step when the callbacks depend on the time only (rhs / boundary-value
     tables)."""
-    prm = _solver_settings(solver)
-    lti = dynamic_rhs if isinstance(dynamic_rhs, LinearFeedback) else None
-    fb_dev = (lti is not None and device_convection is not None
-              and resident is not None)
-    state_dependent = dynamic_rhs is not None and not fb_dev
-    dt, listofts = _inittimegrid(trange, ntimeslices=ntimeslices)
-    NP, NV = J.shape
-    if device_convection is not None and f_vdp is None:
-        f_vdp = device_convection.host_callback(invinds)   # Heun start only
-    dynamic_rhs, f_vdp = _wrap_callbacks(NV, dynamic_rhs, None, f_vdp)
-    dfv_c, drm = dynamic_rhs(trange[0], vc=inivel, memory=dynamic_rhs_memory,
-                             mode='init')
-    savevp(appndbcs(inivel, bcs_ini), inip, time=trange[0])
-    v_c = inivel
-    (v_n, p_n, bcs_n, bfv_n, mbc_c, mbc_n, fv_n, nfc_c, nfc_n, dfv_n,
-     drm) = _onestepheun(vc=v_c, pc=inip, tc=trange[0], tn=trange[1],
-                         M=M, A=A, J=J, scalep=scalep, dfv_c=dfv_c,
-                         dynamic_rhs=dynamic_rhs, drm=drm, bcs_c=bcs_ini,
-                         applybcs=applybcs, appndbcs=appndbcs, getbcs=getbcs,
-                         f_tdp=f_tdp, f_vdp=f_vdp, g_tdp=g_tdp)
-    savevp(appndbcs(v_n, bcs_n), p_n, time=trange[1])
-
-    M, A = sps.csr_matrix(M), sps.csr_matrix(A)
-    system, opts = _device_system((M + 2./3*dt*A).tocsr(), J, prm)
-    stepper = ImexStepper(system, M)
-    cf = ImexStepper.coeffs(a_c=4./3, a_p=-1./3, cn_c=4./3*dt, cn_o=-2./3*dt,
-                            pscale=scalep/dt, extrapolate=prm['extrapolate'],
-                            carry_residual=prm['carry_residual'])
-    stepper.set_state(v_n, v_p=v_c, ptilde_c=p_n*dt/scalep, nfc_c=nfc_c)
-    # (kept too: the velocity BEFORE a slice's last step, for the blow-up guard
-    # of the next slice, tiu:317,322)
-    rs = _ResidentSlices(
-        stepper, cf, opts, dt, resident, device_convection, bcs_ini,
-        state_dependent, prev=_Terms(None, None, mbc_c, None),
-        cur=_Terms(bcs_n, bfv_n, mbc_n, fv_n), keep_prev=True,
-        row=lambda p, c, n: (-(n.mbc - 4/3*c.mbc + 1/3*p.mbc)
-                             + 2/3*dt*n.bfv + 2/3*dt*n.fv),
-        getbcs=getbcs, applybcs=applybcs, appndbcs=appndbcs, f_tdp=f_tdp,
-        g_tdp=g_tdp, savevp=savevp)
-    statvals, moving = rs.statvals, rs.moving
-    ffflag = 0
-    try:
-        rs.attach(lti if fb_dev else None, 2./3, 0., drm, trange[1])
-        if rs.slog is not None:
-            rs.slog.start(v_n, p_n, trange[1])
-        for kck, ctrange in enumerate(listofts):
-            nrmvc = np.linalg.norm(v_c)
-            if nrmvc > check_ff_maxv or np.isnan(nrmvc):
-                ffflag = 1
-                break
-            if rs.on_device and len(ctrange) > 0:
-                ns = len(ctrange)
-                states = rs.run(ctrange)
-                v_c = states[ns - 2][0] if ns > 1 else v_n
-                v_n, p_n = states[ns - 1]
-                continue
-            for ctime in ctrange:
-                v_p, mbc_p = v_c, mbc_c
-                v_c, p_c = v_n, p_n
-                bcs_c, mbc_c = bcs_n, mbc_n
-                dfv_c = dfv_n
-                if device_convection is not None and (moving or statvals):
-                    device_convection.set_dbcvals(statvals + list(bcs_c))
-                nfc_new = None if device_convection is not None \
-                    else f_vdp(appndbcs(v_c, bcs_c))
-                bcs_n = getbcs(ctime, appndbcs(v_c, bcs_c), p_c, mode='abtwo')
-                bfv_n, bfp_n, mbc_n = applybcs(bcs_n)
-                fv_n, fp_n = f_tdp(ctime), g_tdp(ctime)
-                dfv_n, drm = dynamic_rhs(ctime, vc=v_c, memory=drm,
-                                         mode='abtwo')
-                gvec = -(mbc_n - 4/3*mbc_c + 1/3*mbc_p) + 2/3*dt*bfv_n \
-                    + 2/3*dt*(fv_n + dfv_n)
-                stepper.set_rhs(_col(gvec, NV), _col(fp_n + bfp_n, NP))
-                stepper.step(cf, nfc_new=nfc_new, opts=opts)
-                v_n, p_n = stepper.get_state()
-                if rs.flog is not None and moving:
-                    rs.flog.host_row(v_n, v_c, p_n, ctime,
-                                     dbc=statvals + list(bcs_n),
-                                     dbc_prev=statvals + list(bcs_c))
-                elif rs.flog is not None:
-                    rs.flog.host_row(v_n, v_c, p_n, ctime)
-                if rs.slog is not None:
-                    rs.slog.host_row(v_n, p_n, ctime)
-                savevp(appndbcs(v_n, bcs_n), p_n, time=ctime)
-        if rs.rfb is not None:
-            rs.rfb.finish(drm)
-        if rs.slog is not None:
-            rs.slog.finish()
-    finally:
-        _record_run('sbdftwo', system, stepper, *_feedback_record(
-            rs.rfb, lti, state_dependent), rec=rs.drec, flog=rs.flog,
-                    slog=rs.slog)
-        stepper.close()
-        system.close()
-    return v_n, p_n, ffflag
+    kw = locals()
+    del kw['check_ff']          # (unused, as in the reference)
+    return _imex_loop(_SBDF2, **kw)
 
 
 def semi_implicit_euler(iniv=None, jmat=None, mmat=None, amat=None, rhsv=None,

@@ -1,6 +1,6 @@
 """Host side of the force functionals with time-varying Dirichlet values
 (`fem.functionals`: `cab`, `cmb`, `evaluate(..., dbc=, dbc_prev=)`,
-`boundary_torque`) and the table rows `_ResidentSlices.run` hands the
+`boundary_torque`) and the table rows `_ImexLoop.run_slice` hands the
 functionals' log.
 
 Shapes: `scenarios.toy_problem()` (NV = 1286, NP = 207, 348 cells, 240
@@ -292,27 +292,27 @@ def test_table_rows_for_slices_and_chunks_that_do_not_divide(record):
     def bcs(t):            # two controlled values, functions of the time
         return [float(t), float(-2*t)]
     stepper, conv = _StubStepper(), _StubConv()
-    cur = tiu._Terms(bcs(trange[1]), 0., 0., 0.)
+    cur = tiu._Terms(bcs(trange[1]), 0., 0., 0., 0.)
     # (chunks: at most two snapshots each, so the slices of 4 steps, which
     # keep their last two, split unevenly)
     rsd = dict(bcs_time_only=True, static_dbcvals=stat, functionals=_StubFn(),
                record=record, record_bytes=2*8*64, savevp_times=())
-    rs = tiu._ResidentSlices(
-        stepper, None, None, dt, rsd, conv, bcs(trange[0]), False,
-        prev=tiu._Terms(None, None, 0., None), cur=cur,
-        row=lambda p, c, n: 0., keep_prev=True,
+    # (SBDF2 keeps the state before a slice's last step; its row is 0. here)
+    rs = tiu._ImexLoop(
+        tiu._SBDF2, stepper, None, None, dt, rsd, conv, bcs(trange[0]), False,
+        prev=tiu._Terms(None, None, 0., None, None), cur=cur,
         getbcs=lambda t, v, p, mode=None: bcs(t),
         applybcs=lambda b: (0., 0., 0.), appndbcs=lambda v, b: v,
         f_tdp=lambda t: 0., g_tdp=lambda t: 0.,
         savevp=lambda v, p, time=None: None)
     assert rs.on_device and (rs.drec is not None) == record
-    rs.attach(None, .5, .5, {}, trange[1])
+    rs.attach(None, False, trange[1])
     tprev = trange[1]
     for ctrange in slices:
         if not len(ctrange):
             continue
         stepper.armed, conv.tables = [], []
-        rs.run(ctrange)
+        rs.run_slice(ctrange)
         times = [tprev] + list(ctrange)      # the states before / after
         want = np.array([stat + bcs(t) for t in times])
         assert sum(n for n, _ in stepper.armed) == len(ctrange)
@@ -332,8 +332,8 @@ def test_table_rows_for_slices_and_chunks_that_do_not_divide(record):
     # a functional built for another number of Dirichlet dofs is refused
     bad = dict(rsd, functionals=type('F', (_StubFn,),
                                      dict(cab=sps.csr_matrix((1, 4))))())
-    rs2 = tiu._ResidentSlices(
-        stepper, None, None, dt, bad, conv, bcs(0.), False,
-        prev=tiu._Terms(None, None, 0., None), cur=cur)
+    rs2 = tiu._ImexLoop(
+        tiu._SBDF2, stepper, None, None, dt, bad, conv, bcs(0.), False,
+        prev=tiu._Terms(None, None, 0., None, None), cur=cur)
     with pytest.raises(ValueError):
-        rs2.attach(None, .5, .5, {}, trange[1])
+        rs2.attach(None, False, trange[1])
