@@ -1,5 +1,6 @@
 // Cycle length and batch length of the pipelined batches of dns_imex_run
 // (imex_capi.inc): host arithmetic only, no HIP (tests/host_sanitize.cpp).
+// (The sweeps' counterpart, constants of its own: newton_picard._CyclePolicy)
 #pragma once
 #include <algorithm>
 

@@ -15,6 +15,7 @@ matrix sums and one saddle-point solve per time step:
 
 Host code only drives the loop (`TrapezoidalStepper.sweep`, `newton_picard`).
 """
+import collections
 import ctypes as ct
 import os
 import sys
@@ -64,6 +65,151 @@ def values_in_pattern(mat, pattern):
     return out
 
 
+def _lowrank(feedback, trange, k):
+    """the low-rank terms of step `k` as `TrapezoidalStepper.step` takes
+    them"""
+    if feedback is None:
+        return None
+    umat_c, vmat_c = feedback(trange[k-1])
+    umat_n, vmat_n = feedback(trange[k])
+    if umat_c is not umat_n and not np.array_equal(umat_c, umat_n):
+        raise NotImplementedError('`umat` must not depend on the time '
+                                  '(one input matrix, snu:1476-1478)')
+    return umat_n, vmat_c, vmat_n
+
+
+# what the steps of one sweep share: its arguments and what it collects
+_Sweep = collections.namedtuple(
+    '_Sweep', 'trange lin_which newton opts extrapolate feedback record '
+    'vdict pdict tot')
+
+
+class _CyclePolicy(object):
+    """The cycle length -- Krylov columns per solve -- of the pipelined batches
+    of one sweep; arithmetic on the counters of `poll()`, nothing else.
+
+    `over` (oversolve, `set_oversolve`): every solve runs the `cycle` columns
+    of the replayed graph.  The cycle grows when a batch ended close to the
+    tolerance, shrinks to what was run when every solve reached the floor
+    earlier, and is TRIED one column shorter (on a short batch) when every
+    solve stood a decade below the tolerance in front of its last column.
+    Without it a solve stops at the tolerance and the cycle is the longest
+    solve of the last batch plus a slack column.
+
+    The same idea as the oversolve branch of `dns::BatchPolicy`
+    (`csrc/batch_policy.hpp`, the batches of `dns_imex_run`), NOT the same
+    code: `hold` is its `lower_hold` (batches until a shorter cycle may be
+    tried), `backoff` its `lower_backoff` (the hold behind a trial that
+    failed), `lowered` its `lowered_last` (the batch just run was a trial).
+    What differs: the constants -- the back-off is x 4 up to 4096 here, x 2 up
+    to 1024 there; 0.9 / 0.25 / 0.5 are fixed here, `raise` / `lower` are
+    parameters there; the hold behind a fallback is `max(backoff, 4)` here.
+    `learning` exists only here: a stepper that has no HINT -- the cycle the
+    last sweep of this kind (Picard / Newton) ended with -- runs short batches
+    and lowers the cycle more readily until a batch keeps it.  There is no
+    `spiked`: a batch that fails is replayed step by step and always raises
+    the cycle.  The two are not to be merged or their constants aligned
+    without a measurement: they decide which graphs a run replays."""
+
+    def __init__(self, over):
+        self.over = bool(over)
+        self.cycle = None                     # (no pipelined batch yet)
+        self.hold, self.backoff = 0, 2
+        self.lowered = self.learning = False
+
+    def after_startup(self, worst, hint=None):
+        """`worst`: the most Krylov steps a synchronous start-up step took"""
+        self.cycle = max(1, worst) if self.over else max(2, worst + 1)
+        if self.over and hint is not None:
+            # what the last sweep of this kind settled at (sweeps repeat
+            # themselves: Picard, then Newton after Newton over the same
+            # range); the first steps only bound it from above (+ 1: a sweep
+            # STARTS in a transient -- from the initial state, with an empty
+            # warm-start history -- that the end of the last sweep did not
+            # see; a first batch that fails is repeated step by step)
+            self.cycle = min(self.cycle, hint + 1)
+        self.learning = self.over and hint is None
+
+    def short_batch(self):
+        """a trial batch -- and the first batches of a stepper that does not
+        know its cycle length yet -- are short (`min(batch, 16)` steps)"""
+        return self.lowered or self.learning
+
+    def after_batch(self, maxit, maxneed, maxrel, maxprev):
+        """a batch in which no solve failed"""
+        was = self.cycle
+        if not self.over:
+            self.cycle = max(2, maxit + 1)
+            return
+        if maxrel > 0.9:
+            self.cycle = was + 1
+            if self.lowered:
+                self.backoff = min(4096, 4*self.backoff)
+            self.hold = self.backoff
+        elif maxit < was:
+            self.cycle = max(1, maxit)
+        elif was > 1 and self.hold == 0 and (
+                0. < maxprev < 0.25
+                or (self.learning and maxneed < was and maxprev < 0.5)):
+            self.cycle = was - 1
+        self.lowered = self.cycle < was and maxit >= was
+        self.hold = max(0, self.hold - 1)
+        self.learning = self.learning and self.cycle != was
+
+    def after_fallback(self, worst):
+        """a batch with a failed solve, repeated with synchronous steps of at
+        most `worst` Krylov steps"""
+        if self.over:
+            self.cycle = max(self.cycle + 1, worst)
+            if self.lowered:
+                self.backoff = min(4096, 4*self.backoff)
+            self.hold, self.lowered = max(self.backoff, 4), False
+        else:
+            self.cycle = max(2, worst + 1)
+
+    def hint(self):
+        """what the next sweep of this kind starts from"""
+        return self.cycle
+
+
+class _RefreshPolicy(object):
+    """When `sweep` rebuilds the preconditioner (`refresh_precond`): when the
+    Krylov steps per time step of a batch exceed `bound` AND have risen by a
+    fifth over `level`, what this preconditioner gave in the first batch
+    behind its set-up (a first batch above the bound gets one rebuild straight
+    away: a set-up made for another state) -- the system matrix follows the
+    flow every step, the preconditioner follows it when it pays.  One per
+    stepper: `level` and `tried` carry over from sweep to sweep.  `bound`
+    `None` / 0: never."""
+
+    def __init__(self, bound):
+        self.bound, self.level, self.tried = bound, None, False
+
+    def rebuild(self, per_step, more):
+        """a batch took `per_step` Krylov steps per time step; `more`: steps
+        follow.  True: rebuild now (the caller does, and counts it)"""
+        if not self.bound or not more:
+            return False
+        if self.level is None:
+            # the first batch behind a set-up: what THIS preconditioner
+            # gives at its best.  Above the bound, one rebuild about the
+            # current operator is tried (a set-up made for another state)
+            self.level = per_step
+            if per_step > self.bound and not self.tried:
+                self.tried = True
+                self.level = None
+                return True
+            return False
+        # later: rebuild when the count is above the bound AND has risen by a
+        # fifth over that level -- a bound that no rebuild reaches (tight
+        # tolerance) must not rebuild batch after batch
+        if per_step > self.bound and per_step > 1.2*self.level:
+            self.level = None
+            self.tried = True
+            return True
+        return False
+
+
 class TrapezoidalStepper(object):
     """`M, A, J` condensed (inner dofs), `conv` a `ConvectionP2` of the same
     space; `dt` is the step size the preconditioner is set up for (other
@@ -91,10 +237,11 @@ class TrapezoidalStepper(object):
         stopping at it (`set_oversolve`; 0: stop at the tolerance, with a
         slack column per cycle as until round 4)"""
         self.lib = C.load_library()
-        self.refresh_iters = refresh_iters
+        self._refresh = _RefreshPolicy(refresh_iters)
         self.batch = int(batch)
         self.refreshes = 0
-        self._level, self._tried = None, False    # (state of the policy)
+        self._cycle_hint = {}      # newton -> cycle the last such sweep left
+        self._exports = []
         self.conv = conv
         self.M, self.A, self.J = (sps.csr_matrix(M), sps.csr_matrix(A),
                                   sps.csr_matrix(J))
@@ -192,7 +339,7 @@ class TrapezoidalStepper(object):
         out = np.empty((count, self.NV))
         C.check(self.lib.dns_trap_traj_export_async(self._h, which, slot0,
                                                     count, C.dptr(out)))
-        self._exports = getattr(self, '_exports', []) + [out]   # keep alive
+        self._exports.append(out)                     # keep alive
         return out
 
     def export_wait(self):
@@ -308,10 +455,51 @@ class TrapezoidalStepper(object):
         on the device -- `M + dt/2 (A + N(v_lin))` of the step that ran last.
         The reference factorises the current operator in every step
         (snu:1484-1512) and therefore never solves with a stale one; here the
-        polynomial and the Schur block are rebuilt when the policy of `sweep`
-        asks for it (0.07 s at N=2, the price of a few hundred time steps)"""
+        polynomial and the Schur block are rebuilt when `_RefreshPolicy` tells
+        `sweep` to (0.07 s at N=2, the price of a few hundred time steps)"""
         self.system.setup_precond(**self._pkw)
         self.refreshes += 1
+
+    def _one(self, sw, k):
+        st = self.step(sw.trange[k] - sw.trange[k-1], sw.lin_which, k, k,
+                       sw.newton, opts=sw.opts, extrapolate=sw.extrapolate,
+                       feedback=_lowrank(sw.feedback, sw.trange, k))
+        if sw.record:
+            sw.vdict[sw.trange[k]], sw.pdict[sw.trange[k]] = self.state()
+        return st
+
+    def _sync_steps(self, sw, k0, k1):
+        """steps `k0 .. k1 - 1` of the sweep, every one run to convergence:
+        their Krylov steps and the most one of them took"""
+        its, worst = 0, 0
+        for k in range(k0, k1):
+            st = self._one(sw, k)
+            its += st['iters']
+            worst = max(worst, st['iters'])
+            sw.tot['device_seconds'] += st['device_seconds']
+        return its, worst
+
+    def _pipelined_batch(self, sw, cycle, k, kend):
+        """steps `k .. kend - 1` enqueued behind a checkpoint with solves of
+        `cycle` columns, and the counters the device kept of them"""
+        self.checkpoint()
+        self.set_pipeline(cycle)
+        try:
+            if sw.record:
+                for kk in range(k, kend):
+                    self._one(sw, kk)
+            else:
+                # (uniform grid, no low-rank terms: the loop is the library's)
+                self.run(sw.trange[k] - sw.trange[k-1], sw.lin_which, k,
+                         kend - k, sw.newton, opts=sw.opts,
+                         extrapolate=sw.extrapolate)
+            acc = self.poll()
+        finally:
+            self.set_pipeline(0)
+        if os.environ.get('DNS_DEBUG'):
+            print('[sweep] steps {0}..{1} cycle {2}: {3}'.format(
+                k, kend, cycle, acc), file=sys.stderr)
+        return acc
 
     def sweep(self, trange, iniv, lin_which, picard, opts=None, extrapolate=4,
               record=True, pipeline=True, batch=None, feedback=None):
@@ -323,15 +511,10 @@ class TrapezoidalStepper(object):
         Uniform time grids run PIPELINED in batches of `batch` steps
         (`self.batch`, 64): nobody waits for a step, the device counts Krylov
         steps and failures, the host looks once per batch.  A batch in which a
-        step did not converge within the agreed cycle length is repeated from
-        its checkpoint with synchronous steps.  REFRESH POLICY
-        (`refresh_iters`, constructor): when the Krylov steps per time step of
-        a batch exceed the bound AND have risen by a fifth over what this
-        preconditioner gave in the first batch behind its set-up, it is rebuilt
-        about the current operator before the next batch (a first batch above
-        the bound gets one rebuild straight away: a set-up made for another
-        state) -- the system matrix follows the flow every step, the
-        preconditioner follows it when it pays.
+        step did not converge within the agreed cycle length (`_CyclePolicy`)
+        is repeated from its checkpoint with synchronous steps.  Between two
+        batches the preconditioner is rebuilt about the current operator when
+        `_RefreshPolicy` (`refresh_iters`, constructor) asks for it.
 
         `feedback`: callable `t -> (umat (NV, r), vmat (r, NV))`, the low-rank
         terms of the closed loop per time instance (snu:1367-1384, 1461-1483;
@@ -350,166 +533,56 @@ class TrapezoidalStepper(object):
         nt = trange.size
         self.start(iniv, newton)
         self.write_linpoint(1 - lin_which, 0, iniv)
-        vdict, pdict = {}, {}
-        if record:
-            vdict[trange[0]] = np.asarray(iniv, dtype=float).reshape((-1, 1))
         tot = dict(iters=0, device_seconds=0., refreshes=0, replayed_batches=0,
                    batches=[])
-
-        def lowrank(k):
-            if feedback is None:
-                return None
-            umat_c, vmat_c = feedback(trange[k-1])
-            umat_n, vmat_n = feedback(trange[k])
-            if umat_c is not umat_n and not np.array_equal(umat_c, umat_n):
-                raise NotImplementedError('`umat` must not depend on the time '
-                                          '(one input matrix, snu:1476-1478)')
-            return umat_n, vmat_c, vmat_n
-
-        def one(k):
-            st = self.step(trange[k] - trange[k-1], lin_which, k, k, newton,
-                           opts=opts, extrapolate=extrapolate,
-                           feedback=lowrank(k))
-            if record:
-                vdict[trange[k]], pdict[trange[k]] = self.state()
-            return st
-
-        def sync_steps(k0, k1):
-            its, worst = 0, 0
-            for k in range(k0, k1):
-                st = one(k)
-                its += st['iters']
-                worst = max(worst, st['iters'])
-                tot['device_seconds'] += st['device_seconds']
-            return its, worst
-
-        def policy(per_step, k):
-            bound = self.refresh_iters
-            tot['batches'].append(per_step)
-            if not bound or k >= nt:
-                return
-            if self._level is None:
-                # the first batch behind a set-up: what THIS preconditioner
-                # gives at its best.  Above the bound, one rebuild about the
-                # current operator is tried (a set-up made for another state)
-                self._level = per_step
-                if per_step > bound and not self._tried:
-                    self._tried = True
-                    self._level = None
-                    self.refresh_precond()
-                    tot['refreshes'] += 1
-                return
-            # later: rebuild when the count is above the bound AND has risen by
-            # a fifth over that level -- a bound that no rebuild reaches (tight
-            # tolerance) must not rebuild batch after batch
-            if per_step > bound and per_step > 1.2*self._level:
-                self._level = None
-                self._tried = True
-                self.refresh_precond()
-                tot['refreshes'] += 1
-
+        sw = _Sweep(trange, lin_which, newton, opts, extrapolate, feedback,
+                    record, {}, {}, tot)
+        if record:
+            sw.vdict[trange[0]] = np.asarray(iniv, dtype=float).reshape(
+                (-1, 1))
         pipelined = pipeline and uniform and feedback is None
+        policy = _CyclePolicy(pipelined and self._over)
         # (synchronous until the warm start has its full order -- five
         # solutions for the quartic one: the steps before need more Krylov
         # steps than the run will, and a first batch sized by them fails)
         k = min(nt, 7) if pipelined else 1
-        over = pipelined and getattr(self, '_over', False)
-        hints = self.__dict__.setdefault('_cycle_hint', {})
-        learning = False
         if pipelined:
-            its, worst = sync_steps(1, k)
+            its, worst = self._sync_steps(sw, 1, k)
             tot['iters'] += its
-            cycle = max(1, worst) if over else max(2, worst + 1)
-            if over and newton in hints:
-                # what the last sweep of this kind settled at (sweeps repeat
-                # themselves: Picard, then Newton after Newton over the same
-                # range); the first steps above only bound it from above
-                # (+ 1: a sweep STARTS in a transient -- from the initial state,
-                # with an empty warm-start history -- that the end of the last
-                # sweep did not see; a first batch that fails is repeated
-                # step by step)
-                cycle = min(cycle, hints[newton] + 1)
-            learning = over and newton not in hints
-        hold, backoff, lowered = 0, 2, False
+            policy.after_startup(worst, self._cycle_hint.get(newton))
         while k < nt:
-            kend = min(nt, k + batch)
-            if lowered or learning:
-                # a trial batch -- and the first batches of a stepper that
-                # does not know its cycle length yet -- are short
-                kend = min(nt, k + min(batch, 16))
+            kend = min(nt, k + (min(batch, 16) if policy.short_batch()
+                                else batch))
             if not pipelined:
-                its, _ = sync_steps(k, kend)
+                acc, (its, _) = None, self._sync_steps(sw, k, kend)
             else:
-                self.checkpoint()
-                self.set_pipeline(cycle)
-                try:
-                    if record:
-                        for kk in range(k, kend):
-                            one(kk)
-                    else:
-                        # (uniform grid, no low-rank terms: the loop is the
-                        # library's)
-                        self.run(trange[k] - trange[k-1], lin_which, k,
-                                 kend - k, newton, opts=opts,
-                                 extrapolate=extrapolate)
-                    acc = self.poll()
-                finally:
-                    self.set_pipeline(0)
-                if os.environ.get('DNS_DEBUG'):
-                    print('[sweep] steps {0}..{1} cycle {2}: {3}'.format(
-                        k, kend, cycle, acc), file=sys.stderr)
-                if acc['fails'] == 0 and not over:
-                    its, cycle = acc['iters'], max(2, acc['maxit'] + 1)
-                elif acc['fails'] == 0:
-                    # oversolve (as csrc/batch_policy.hpp): every solve
-                    # ran the `cycle` columns of the replayed graph.  The
-                    # cycle grows when the batch ended close to the tolerance,
-                    # shrinks to what was run when every solve reached the
-                    # floor earlier, and is TRIED one column shorter (on a
-                    # short batch) when every solve stood a decade below the
-                    # tolerance in front of its last column
+                acc = self._pipelined_batch(sw, policy.cycle, k, kend)
+                if acc['fails'] == 0:
                     its = acc['iters']
-                    was = cycle
-                    if acc['maxrel'] > 0.9:
-                        cycle = was + 1
-                        if lowered:
-                            backoff = min(4096, 4*backoff)
-                        hold = backoff
-                    elif acc['maxit'] < was:
-                        cycle = max(1, acc['maxit'])
-                    elif was > 1 and hold == 0 and (
-                            0. < acc['maxprev'] < 0.25
-                            or (learning and acc['maxneed'] < was
-                                and acc['maxprev'] < 0.5)):
-                        cycle = was - 1
-                    lowered = cycle < was and acc['maxit'] >= was
-                    hold = max(0, hold - 1)
-                    learning = learning and cycle != was
+                    policy.after_batch(acc['maxit'], acc['maxneed'],
+                                       acc['maxrel'], acc['maxprev'])
                 else:
                     # a step of this batch was not through after `cycle` Krylov
                     # steps: the batch again, every step run to convergence
                     self.restore(newton)
-                    its, worst = sync_steps(k, kend)
-                    if over:
-                        cycle = max(cycle + 1, worst)
-                        if lowered:
-                            backoff = min(4096, 4*backoff)
-                        hold, lowered = max(backoff, 4), False
-                    else:
-                        cycle = max(2, worst + 1)
+                    its, worst = self._sync_steps(sw, k, kend)
+                    policy.after_fallback(worst)
                     tot['replayed_batches'] += 1
             tot['iters'] += its
             # (oversolve: what the refresh policy goes by is the columns a
             # solve NEEDED, not the columns the cycle ran)
             per = its/float(kend - k)
-            if over and pipelined and acc['fails'] == 0:
+            if policy.over and acc['fails'] == 0:
                 per = min(per, acc['sumneed']/float(max(1, acc['solves'])))
-            policy(per, kend)
+            tot['batches'].append(per)
+            if self._refresh.rebuild(per, kend < nt):
+                self.refresh_precond()
+                tot['refreshes'] += 1
             k = kend
-        if over and nt > 2*batch:
-            hints[newton] = cycle      # (a real sweep, not a warm-up pass)
-        tot['cycle'] = cycle if pipelined else None
-        return vdict, pdict, self.update_norm(), tot
+        if policy.over and nt > 2*batch:    # (a real sweep, no warm-up pass)
+            self._cycle_hint[newton] = policy.hint()
+        tot['cycle'] = policy.cycle
+        return sw.vdict, sw.pdict, self.update_norm(), tot
 
 
 def time_sections(trange, nsects=1, addfullsweep=False):
