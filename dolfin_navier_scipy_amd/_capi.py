@@ -213,6 +213,17 @@ SIGNATURES = {
     'dns_imex_get_stats': (ct.c_int, [_VP, ct.c_int32, ct.c_int32, c_double_p,
                                       c_double_p, c_double_p, c_double_p]),
     'dns_imex_clear_stats': (ct.c_int, [_VP]),
+    'dns_imex_set_quadratics': (ct.c_int, [_VP, ct.c_int32,
+                                           ct.POINTER(dns_csr), ct.c_int32,
+                                           c_int32_p, c_int32_p, c_int32_p,
+                                           ct.POINTER(dns_csr),
+                                           ct.POINTER(dns_csr), c_double_p,
+                                           c_double_p, ct.c_double, ct.c_int32,
+                                           ct.c_int32]),
+    'dns_imex_get_quadratics': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
+                                           c_double_p]),
+    'dns_imex_quadratics_grid': (ct.c_int, [_VP, c_int32_p]),
+    'dns_imex_clear_quadratics': (ct.c_int, [_VP]),
     'dns_imex_run_info': (ct.c_int, [_VP, c_int32_p, c_int32_p, c_int32_p,
                                      c_int32_p]),
     'dns_imex_step_counters': (ct.c_int, [_VP, ct.POINTER(ct.c_int64)]),

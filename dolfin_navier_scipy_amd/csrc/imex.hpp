@@ -4,6 +4,7 @@
 #include "convection.hpp"
 #include "feedback.hpp"
 #include "functional.hpp"
+#include "quadratic.hpp"
 #include "record.hpp"
 #include "ring.hpp"
 #include "solver.hpp"
@@ -204,7 +205,34 @@ struct dns_imex : dns::Ring {
     dns::Checkpoint ck_st;
     int st_launch(hipStream_t s);  // k_stats_step for the state as it stands
     uint64_t st_key() const;
-    // What the four have in common (imex_attach_capi.inc): which of them
+    // quadratic functionals (quadratic.hpp): k_quadratic_step runs in front of
+    // every step (the last of the front nodes) and once behind the last step
+    // of a call; it writes row `counter - 1` of the log, so a restored batch
+    // overwrites its own rows and the log needs no checkpoint.  The matrices
+    // stay on the device across calls that hand over the same ones (`Qh`:
+    // what the device holds).  Present = on.
+    struct Quadratics {
+        int nM = 0, nQ = 0, G = 1, rows = 0;
+        double dt = 1.0;
+        int mat[dns::kQdMaxForms] = {}, lop[dns::kQdMaxForms] = {},
+            rop[dns::kQdMaxForms] = {};
+        int need[dns::kQdMaxMats] = {};
+        long long nzbase[dns::kQdMaxMats] = {};
+        struct HostMat {
+            std::vector<int> rp, ci;
+            std::vector<double> va;
+        };
+        std::vector<HostMat> Qh;
+        dns::DevBuf<int> rp, ci;   // the nM matrices, one behind the other
+        dns::DevBuf<double> va;
+        dns::DevBuf<int> lrp, lci; // the 2 nQ sparse rows (k, qa / qw)
+        dns::DevBuf<double> lva, scale, c0;
+        dns::DevBuf<double> log;   // rows x G x nQ
+    };
+    std::unique_ptr<Quadratics> qd;
+    int qd_launch(hipStream_t s);  // k_quadratic_step for the state as it stands
+    uint64_t qd_key() const;
+    // What the five have in common (imex_attach_capi.inc): which of them
     // run in front of a step and which behind the last step of a call, what
     // they add to the key of a captured step, the refusals a step makes on
     // their behalf, and what they mean for the step counter.

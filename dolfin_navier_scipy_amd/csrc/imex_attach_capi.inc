@@ -1,7 +1,7 @@
 // The attachments of the resident IMEX loop -- observer feedback
 // (feedback.hpp), trajectory recorder (record.hpp), force functionals
-// (functional.hpp), flow statistics (stats.hpp): one node each in front of
-// every step -- and their extern
+// (functional.hpp), flow statistics (stats.hpp), quadratic functionals
+// (quadratic.hpp): one node each in front of every step -- and their extern
 // "C" entry points (included by dns_amd.hip behind imex_capi.inc).
 
 // "feedback on", its shape, its coefficients and every buffer k_lti_step is
@@ -125,16 +125,66 @@ int dns_imex::st_launch(hipStream_t s) {
     return DNS_OK;
 }
 
-// ---- what the four have in common -------------------------------------------
+// "quadratics on", their shape, forms and grid and every buffer
+// k_quadratic_step is handed (the ring vectors come with the step key)
+uint64_t dns_imex::qd_key() const {
+    const Quadratics &q = *qd;
+    uint64_t k = mix64(0x9d, {kw(q.nM), kw(q.nQ), kw(q.G), kw(q.rows),
+                              kw(q.dt), kw(q.rp.p), kw(q.ci.p), kw(q.va.p),
+                              kw(q.lrp.p), kw(q.lci.p), kw(q.lva.p),
+                              kw(q.scale.p), kw(q.c0.p), kw(q.log.p),
+                              kw(stepctr.p)});
+    for (int m = 0; m < q.nM; ++m)
+        k = mix64(k, {kw(q.nzbase[m]), kw(q.need[m])});
+    for (int f = 0; f < q.nQ; ++f)
+        k = mix64(k, {kw(q.mat[f]), kw(q.lop[f]), kw(q.rop[f])});
+    return k;
+}
+
+int dns_imex::qd_launch(hipStream_t s) {
+    const Quadratics &q = *qd;
+    dns::QdArgs a{};
+    a.stepctr = stepctr.p;
+    a.nrows = q.rows;
+    a.x = xs[cur].p;
+    a.xp = xs[prev].p;
+    a.nv = sys->nv;
+    a.dt = q.dt;
+    a.nM = q.nM;
+    a.nQ = q.nQ;
+    a.G = q.G;
+    a.rp = q.rp.p;
+    a.ci = q.ci.p;
+    a.va = q.va.p;
+    for (int m = 0; m < dns::kQdMaxMats; ++m) {
+        a.nzbase[m] = q.nzbase[m];
+        a.need |= (unsigned)q.need[m] << (2 * m);
+    }
+    for (int f = 0; f < q.nQ; ++f)
+        a.forms |= dns::quadratic_form_bits(q.mat[f], q.lop[f], q.rop[f])
+                   << (4 * f);
+    a.lrp = q.lrp.p;
+    a.lci = q.lci.p;
+    a.lva = q.lva.p;
+    a.scale = q.scale.p;
+    a.c0 = q.c0.p;
+    a.log = q.log.p;
+    hipLaunchKernelGGL(dns::k_quadratic_step, q.G, dns::kBlock, 0, s, a);
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+// ---- what the five have in common -------------------------------------------
 
 // In front of every step, in this order: k_lti_step leaves the right-hand
-// side the front kernels read, the other three write down / add the row of
+// side the front kernels read, the other four write down / add the row of
 // the step before.
 int dns_imex::launch_front_nodes(hipStream_t s) {
     if (fb.on) DNS_TRY(fb_launch(s));
     if (rec) DNS_TRY(rec_launch(s));
     if (fn) DNS_TRY(fn_launch(s));
     if (stat) DNS_TRY(st_launch(s));
+    if (qd) DNS_TRY(qd_launch(s));
     return DNS_OK;
 }
 
@@ -143,6 +193,7 @@ int dns_imex::launch_closing_nodes(hipStream_t s) {
     if (rec) DNS_TRY(rec_launch(s));
     if (fn) DNS_TRY(fn_launch(s));
     if (stat) DNS_TRY(st_launch(s));
+    if (qd) DNS_TRY(qd_launch(s));
     return DNS_OK;
 }
 
@@ -151,12 +202,13 @@ uint64_t dns_imex::attachments_key(uint64_t k) const {
     if (rec) k = mix64(k, {rec_key()});
     if (fn) k = mix64(k, {fn_key()});
     if (stat) k = mix64(k, {st_key()});
+    if (qd) k = mix64(k, {qd_key()});
     return k;
 }
 
 bool dns_imex::tables() const {
     return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on || rec ||
-           fn || stat;
+           fn || stat || qd;
 }
 
 int dns_imex::rows_left() const {
@@ -166,6 +218,7 @@ int dns_imex::rows_left() const {
     if (rec) lim = std::min(lim, rec->rows);
     if (fn) lim = std::min(lim, fn->rows);
     if (stat) lim = std::min(lim, stat->rows);
+    if (qd) lim = std::min(lim, qd->rows);
     if (conv && conv->dbc_rows > 0) lim = std::min(lim, conv->dbc_rows);
     return lim - tab_pos;
 }
@@ -193,7 +246,7 @@ int dns_imex::rewind_tables() {
     return DNS_OK;
 }
 
-// None of the four runs on a row-partitioned / distributed stepper: refused
+// None of the five runs on a row-partitioned / distributed stepper: refused
 // when it is set and, should the stepper be partitioned later, by the step.
 int dns_imex::refuse_partitioned(const char *noun, const char *reason) const {
     if (!(r1_rows || part.on || sys->dist())) return DNS_OK;
@@ -211,12 +264,22 @@ static const char *const kFnPartitioned = "the sums would need an all-reduce";
 static const char *const kStPartitioned =
     "the sums are local to a rank, the getter would need a gather (multi-rank "
     "statistics are not supported)";
+static const char *const kQdPartitioned = "the sums would need an all-reduce";
+static const char *const kQdMovingBc =
+    "quadratics with a per-step Dirichlet table on the convection operator "
+    "(dns_conv_set_dbc_table): moving boundary values are not part of the "
+    "constants";
 
 // what a step refuses on their behalf
 int dns_imex::check_attachments() const {
     if (fb.on) DNS_TRY(refuse_partitioned("observer feedback", kFbPartitioned));
     if (rec) DNS_TRY(refuse_partitioned("recorder", kRecPartitioned));
     if (stat) DNS_TRY(refuse_partitioned("statistics", kStPartitioned));
+    if (qd) {
+        DNS_TRY(refuse_partitioned("quadratics", kQdPartitioned));
+        if (conv && conv->dbc_rows > 0)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT, "%s", kQdMovingBc);
+    }
     if (!fn) return DNS_OK;
     DNS_TRY(refuse_partitioned("functionals", kFnPartitioned));
     if (fn->ncl > 0 && !conv)
@@ -866,6 +929,205 @@ int dns_imex_get_stats(dns_imex *st, int32_t first_bin, int32_t count,
 int dns_imex_clear_stats(dns_imex *st) try {
     DNS_TRY(quiesce(st));
     st->stat.reset();
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// ---- quadratic functionals (quadratic.hpp) ---------------------------------
+
+int dns_imex_set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
+                            int32_t nQ, const int32_t *mat, const int32_t *lop,
+                            const int32_t *rop, const dns_csr *qa,
+                            const dns_csr *qw, const double *c0,
+                            const double *scale, double dt, int32_t nrows,
+                            int32_t max_grid) try {
+    if (!st || !mats || !mat || !lop || !rop)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_saddle *h = st->sys;
+    DNS_TRY(st->refuse_partitioned("quadratics", kQdPartitioned));
+    if (st->conv && st->conv->dbc_rows > 0)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "%s", kQdMovingBc);
+    if (nM < 1 || nM > dns::kQdMaxMats)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "quadratics: nM = %d outside 1..%d", (int)nM,
+                         dns::kQdMaxMats);
+    if (nQ < 1 || nQ > dns::kQdMaxForms)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "quadratics: nQ = %d outside 1..%d", (int)nQ,
+                         dns::kQdMaxForms);
+    if (nrows < 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "quadratics: nrows = %d < 1",
+                         (int)nrows);
+    if (max_grid < 0)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "quadratics: max_grid = %d < 0",
+                         (int)max_grid);
+    if (!(dt > 0.0))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "quadratics: dt must be "
+                         "positive");
+    const int nv = h->nv;
+    for (int m = 0; m < nM; ++m) {
+        // (check_csr: every column index inside [0, ncols))
+        DNS_TRY(dns::check_csr(&mats[m], "quadratics: a matrix"));
+        if (mats[m].nrows != nv || mats[m].ncols != nv)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "quadratics: matrix %d must be NV x NV (%d), it "
+                             "is %d x %d", m, nv, (int)mats[m].nrows,
+                             (int)mats[m].ncols);
+    }
+    const dns_csr *lin[2] = {qa, qw};
+    const char *lname[2] = {"qa", "qw"};
+    for (int t = 0; t < 2; ++t) {
+        if (!lin[t]) continue;
+        DNS_TRY(dns::check_csr(lin[t], lname[t]));
+        if (lin[t]->nrows != nQ || lin[t]->ncols != nv)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "quadratics: %s must be nQ x NV (%d x %d), it is "
+                             "%d x %d", lname[t], (int)nQ, nv,
+                             (int)lin[t]->nrows, (int)lin[t]->ncols);
+    }
+    for (int k = 0; k < nQ; ++k) {
+        if (mat[k] < 0 || mat[k] >= nM)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "quadratics: mat[%d] = %d outside 0..%d", k,
+                             (int)mat[k], (int)nM - 1);
+        if (lop[k] < 0 || lop[k] > 1 || rop[k] < 0 || rop[k] > 1)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "quadratics: operands (%d, %d) of form %d are "
+                             "not 0 (v) or 1 (v - v_prev)", (int)lop[k],
+                             (int)rop[k], k);
+    }
+    const int G = dns::quadratic_grid(nM, nv, max_grid);
+    if ((size_t)nrows * G * nQ >= ((size_t)1 << 31))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "quadratics: a log of %zu entries (%d rows x %d "
+                         "workgroups x %d forms), the limit is 2^31 - 1: cap "
+                         "the grid (max_grid) or take shorter slices",
+                         (size_t)nrows * G * nQ, (int)nrows, G, (int)nQ);
+    // the same matrices as the device holds: as many, and each equal entry by
+    // entry (row pointers, columns and the bytes of the values)
+    dns_imex::Quadratics none;
+    const dns_imex::Quadratics &old = st->qd ? *st->qd : none;
+    bool same = old.rp.p && (int)old.Qh.size() == nM;
+    for (int m = 0; same && m < nM; ++m) {
+        const auto &o = old.Qh[m];
+        const dns_csr &c = mats[m];
+        same = o.rp.size() == (size_t)nv + 1 && (int64_t)o.ci.size() == c.nnz &&
+               std::equal(o.rp.begin(), o.rp.end(), c.rowptr) &&
+               std::equal(o.ci.begin(), o.ci.end(), c.colidx) &&
+               (c.nnz == 0 ||
+                memcmp(o.va.data(), c.vals, (size_t)c.nnz * sizeof(double)) == 0);
+    }
+    // the 2 nQ sparse rows (k, qa / qw) in one CSR; a null term is an empty row
+    std::vector<int> lrp((size_t)2 * nQ + 1, 0), lci;
+    std::vector<double> lva;
+    for (int k = 0; k < nQ; ++k)
+        for (int t = 0; t < 2; ++t) {
+            if (lin[t])
+                for (int64_t z = lin[t]->rowptr[k]; z < lin[t]->rowptr[k + 1];
+                     ++z) {
+                    lci.push_back(lin[t]->colidx[z]);
+                    lva.push_back(lin[t]->vals[z]);
+                }
+            lrp[(size_t)2 * k + t + 1] = (int)lci.size();
+        }
+    std::vector<double> sc(nQ, 1.0), cc(nQ, 0.0);
+    if (scale) sc.assign(scale, scale + nQ);
+    if (c0) cc.assign(c0, c0 + nQ);
+    DNS_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
+    // In place (keep_or_alloc; everything was checked above: a failed
+    // allocation leaves the stepper without quadratics).
+    std::unique_ptr<dns_imex::Quadratics> q = std::move(st->qd);
+    if (!q) q.reset(new (std::nothrow) dns_imex::Quadratics());
+    if (!q) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    auto put = [&](auto &buf, const auto &host) -> int {
+        DNS_TRY(keep_or_alloc(buf, buf, host.size()));
+        if (!host.empty()) DNS_TRY(buf.upload(host.data(), host.size(), s));
+        return DNS_OK;
+    };
+    if (!same) {
+        size_t total = 0;
+        for (int m = 0; m < nM; ++m) total += (size_t)mats[m].nnz;
+        q->Qh.clear();                  // (until the device holds the new ones)
+        DNS_TRY(keep_or_alloc(q->rp, q->rp, (size_t)nM * (nv + 1)));
+        DNS_TRY(keep_or_alloc(q->ci, q->ci, total));
+        DNS_TRY(keep_or_alloc(q->va, q->va, total));
+        std::vector<dns_imex::Quadratics::HostMat> held((size_t)nM);
+        size_t base = 0;
+        for (int m = 0; m < nM; ++m) {
+            const dns_csr &c = mats[m];
+            const size_t nz = (size_t)c.nnz;
+            auto &o = held[m];
+            o.rp.assign(c.rowptr, c.rowptr + nv + 1);
+            o.ci.assign(c.colidx, c.colidx + nz);
+            o.va.assign(c.vals, c.vals + nz);
+            DNS_TRY(dns::upload_to(q->rp.p + (size_t)m * (nv + 1), c.rowptr,
+                                   (size_t)nv + 1, s));
+            if (nz > 0) {
+                DNS_TRY(dns::upload_to(q->ci.p + base, c.colidx, nz, s));
+                DNS_TRY(dns::upload_to(q->va.p + base, c.vals, nz, s));
+            }
+            q->nzbase[m] = (long long)base;
+            base += nz;
+        }
+        for (int m = nM; m < dns::kQdMaxMats; ++m) q->nzbase[m] = 0;
+        q->Qh = std::move(held);
+    }
+    DNS_TRY(put(q->lrp, lrp));
+    DNS_TRY(put(q->lci, lci));
+    DNS_TRY(put(q->lva, lva));
+    DNS_TRY(put(q->scale, sc));
+    DNS_TRY(put(q->c0, cc));
+    DNS_TRY(keep_or_alloc(q->log, q->log, (size_t)nrows * G * nQ));
+    DNS_TRY(q->log.zero(s));
+    for (int m = 0; m < dns::kQdMaxMats; ++m) q->need[m] = 0;
+    for (int k = 0; k < dns::kQdMaxForms; ++k) {
+        q->mat[k] = k < nQ ? mat[k] : 0;
+        q->lop[k] = k < nQ ? lop[k] : 0;
+        q->rop[k] = k < nQ ? rop[k] : 0;
+        if (k < nQ) q->need[mat[k]] |= rop[k] ? 2 : 1;
+    }
+    q->nM = nM;
+    q->nQ = nQ;
+    q->G = G;
+    q->rows = nrows;
+    q->dt = dt;
+    st->qd = std::move(q);
+    return st->rewind_tables();
+} DNS_CAPI_CATCH
+
+int dns_imex_get_quadratics(dns_imex *st, int32_t first, int32_t count,
+                            double *out) try {
+    DNS_TRY(need(st, st && st->qd, "quadratics are",
+                 "dns_imex_set_quadratics"));
+    const dns_imex::Quadratics &q = *st->qd;
+    if (!out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    const size_t per = (size_t)q.G * q.nQ;
+    std::vector<double> part((size_t)std::min(std::max(count, 0), q.rows) * per);
+    DNS_TRY(download_log_rows(st, part.data(), q.log.p, first, count, per,
+                              q.rows, "quadratic rows", "log"));
+    // the workgroups' shares, in index order
+    for (int r = 0; r < count; ++r)
+        for (int k = 0; k < q.nQ; ++k) {
+            double y = 0.0;
+            for (int g = 0; g < q.G; ++g)
+                y += part[(size_t)r * per + (size_t)g * q.nQ + k];
+            out[(size_t)r * q.nQ + k] = y;
+        }
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_imex_quadratics_grid(dns_imex *st, int32_t *grid) try {
+    DNS_TRY(need(st, st && st->qd, "quadratics are",
+                 "dns_imex_set_quadratics"));
+    if (!grid) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    *grid = st->qd->G;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_imex_clear_quadratics(dns_imex *st) try {
+    DNS_TRY(quiesce(st));
+    st->qd.reset();
     return DNS_OK;
 } DNS_CAPI_CATCH
 

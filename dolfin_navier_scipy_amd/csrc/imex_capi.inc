@@ -387,7 +387,8 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
                              "dns_conv_set_dbc_table / "
                              "dns_imex_set_feedback_table / "
                              "dns_imex_set_recorder / "
-                             "dns_imex_set_functionals / dns_imex_set_stats)",
+                             "dns_imex_set_functionals / dns_imex_set_stats / "
+                             "dns_imex_set_quadratics)",
                              tab_pos);
     }
     if (conv) conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
@@ -1188,7 +1189,8 @@ int dns_imex_step(dns_imex *st, const double *nfc_new,
         return dns::fail(DNS_ERR_NOT_READY,
                          "the per-step tables are used up after %d steps: "
                          "upload the next ones (dns_imex_set_rhs_table / ... / "
-                         "dns_imex_set_functionals)", st->tab_pos);
+                         "dns_imex_set_functionals / dns_imex_set_quadratics)",
+                         st->tab_pos);
     if (nfc_new) {
         std::swap(st->nc, st->no);
         DNS_TRY(st->nfc[st->nc].upload(nfc_new, (size_t)h->nv, h->stream));
@@ -1225,7 +1227,7 @@ int dns_imex_run(dns_imex *st, int32_t nsteps, const dns_imex_coeffs *cf,
         return dns::fail(DNS_ERR_NOT_READY,
                          "%d steps asked for, the per-step tables hold %d more "
                          "(dns_imex_set_rhs_table / ... / "
-                         "dns_imex_set_functionals)",
+                         "dns_imex_set_functionals / dns_imex_set_quadratics)",
                          (int)nsteps, st->rows_left());
     // the run's settings of the system, undone on every exit (the status of
     // the oversolve reset is ignored: the first error is the one reported)

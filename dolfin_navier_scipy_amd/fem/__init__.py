@@ -10,3 +10,5 @@ from .functionals import (MomentumFunctionals, boundary_forces,
                           boundary_torque, pressure_difference,
                           cylinder_nodes)
 from .statistics import FlowStatistics, component_pairs
+from .quadratics import (QuadraticFunctionals, kinetic_energy, dissipation,
+                         kinetic_energy_rate, rate_norm, energy_budget)

@@ -760,6 +760,79 @@ class ImexStepper(object):
                     s1_v=s1[:, :NV].copy(), s1_p=s1[:, NV:].copy(),
                     s2_v=s2[:, :NV].copy(), s2_p=s2[:, NV:].copy(), sx=sx)
 
+    # ---- quadratic functionals (`dns_imex_set_quadratics`) ------------------
+    def set_quadratics(self, qf, nrows, dt, max_grid=None):
+        """the next `nrows` steps (`step` and `run` alike) evaluate the
+        quadratic forms `qf` (`fem.QuadraticFunctionals`: kinetic energy,
+        dissipation rate, `u^T M du/dt`, the M-norm of `du/dt`, ...; at most 8
+        forms over at most 4 matrices) of the state they leave, on the device,
+        into a log of `nrows` rows; `dt`: the time step of the difference
+        `w = v - v_prev`.  Row `s` is `qf.evaluate` of what `get_state` would
+        have returned after the `(s+1)`-th step from now and the state before
+        it.  Resets the step counter like `set_rhs_table` (call it after that
+        one, and collect with `get_quadratics` before the next tables).  The
+        log takes `nrows x G x nQ` doubles, `G` the workgroups of the kernel
+        (at most 256): `max_grid` caps it lower.  Matrices the device holds
+        already are not uploaded again."""
+        nrows = int(nrows)
+        if nrows < 1:
+            raise ValueError('`nrows` must be positive')
+        args = qf.device_args()
+        NV = self.sys.NV
+        nQ = int(args['scale'].size)
+        mats = args['mats']
+        for m, mat in enumerate(mats):
+            if mat.shape != (NV, NV):
+                raise ValueError('matrix {0} must be NV x NV (NV = {1}), it '
+                                 'is {2}'.format(m, NV, mat.shape))
+        views = [C.CsrView(mat) for mat in mats]
+        structs = (C.dns_csr*len(views))(*[v.struct for v in views])
+        lin = []
+        for name in ('qa', 'qw'):
+            mat = args[name]
+            if mat is None or mat.nnz == 0:
+                lin.append(None)
+                continue
+            if mat.shape != (nQ, NV):
+                raise ValueError('{0} must be nQ x NV = {1} x {2}, it is '
+                                 '{3}'.format(name, nQ, NV, mat.shape))
+            lin.append(C.CsrView(mat))
+        forms = [np.ascontiguousarray(args[k], dtype=np.int32)
+                 for k in ('mat', 'lop', 'rop')]
+        c0, scale = C.as_f64(args['c0'], nQ), C.as_f64(args['scale'], nQ)
+        C.check(self.lib.dns_imex_set_quadratics(
+            self._h, len(views), structs, nQ,
+            *[f.ctypes.data_as(C.c_int32_p) for f in forms],
+            *[None if v is None else v.byref() for v in lin],
+            C.dptr(c0), C.dptr(scale), float(dt), nrows,
+            0 if max_grid is None else int(max_grid)))
+        self._qd_shape = (nrows, nQ)
+
+    def clear_quadratics(self):
+        C.check(self.lib.dns_imex_clear_quadratics(self._h))
+        self._qd_shape = None
+
+    def quadratics_grid(self):
+        """`G`, the workgroups of the kernel: the log on the device holds
+        `nrows x G x nQ` doubles"""
+        g = ct.c_int32(0)
+        C.check(self.lib.dns_imex_quadratics_grid(self._h, ct.byref(g)))
+        return g.value
+
+    def get_quadratics(self, first=0, count=None):
+        """rows `first .. first + count` of the quadratics' log (default: of
+        all steps taken since `set_quadratics`), `(count, nQ)`"""
+        shape = getattr(self, '_qd_shape', None)
+        if shape is None:
+            raise ValueError('no quadratics are set (`set_quadratics`)')
+        if count is None:
+            count = self.table_position()[0] - first
+        out = np.empty((int(count), shape[1]))
+        C.check(self.lib.dns_imex_get_quadratics(
+            self._h, int(first), int(count),
+            C.dptr(out.reshape(-1) if out.size else np.zeros(1))))
+        return out
+
     def get_state(self):
         v = np.empty(self.sys.NV)
         p = np.empty(self.sys.NP)

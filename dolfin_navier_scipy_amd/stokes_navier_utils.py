@@ -357,7 +357,7 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
               vp_output=False, vp_out_fun=None, vp_output_dict=None,
               solver=None, device=0, bcs_time_only=False,
               applybcs_literal=True, record_on_device=False,
-              functionals=None, statistics=None, **kw):
+              functionals=None, statistics=None, quadratics=None, **kw):
     """time-dependent Navier-Stokes on the device (reference snu:548-1600)
 
     Keyword names and meaning follow the reference.  `V`: object with the P2
@@ -418,7 +418,15 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     the Heun start and after every AB2 / BDF2 step to its sums, on the device
     where it runs resident (one download when the loop ends);
     `time_int_utils.LAST_RUN['statistics']` and `['statistics_on']` hold the
-    sums and where they were formed.
+    sums and where they were formed.  `quadratics` (explicit schemes): a
+    `fem.QuadraticFunctionals` of the condensed problem (the energy budget:
+    kinetic energy, dissipation rate, `u^T M du/dt`, the M-norm of `du/dt`)
+    -- handed down to the loop (`resident=dict(quadratics=...)`), which
+    evaluates it after every AB2 / BDF2 step, on the device where it runs
+    resident; `time_int_utils.LAST_RUN['quadratics']`, `['quadratics_t']`,
+    `['quadratics_on']`, `['quadratics_names']` hold the rows, their times,
+    where they came from and the forms' names.  Constant Dirichlet values
+    only (`ValueError` with controlled boundaries).
     """
     if functionals is not None and not (treat_nonl_explicit
                                         and lin_vel_point is None):
@@ -426,6 +434,9 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     if statistics is not None and not (treat_nonl_explicit
                                        and lin_vel_point is None):
         raise NotImplementedError('`statistics`: explicit schemes only')
+    if quadratics is not None and not (treat_nonl_explicit
+                                       and lin_vel_point is None):
+        raise NotImplementedError('`quadratics`: explicit schemes only')
     if dynamic_feedback and dyn_fb_disc == 'linear_implicit':
         raise NotImplementedError("`dyn_fb_disc='linear_implicit'` (the "
                                   'extended system of '
@@ -632,6 +643,8 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
                 icd['resident'].setdefault('static_dbcvals', list(dbcvals))
         if statistics is not None:
             icd.setdefault('resident', {}).update(statistics=statistics)
+        if quadratics is not None:
+            icd.setdefault('resident', {}).update(quadratics=quadratics)
         v_end, p_end, ffflag = timintsc(trange=trange, inip=inip, scalep=-1.,
                                         g_tdp=rhsp, bcs_ini=inicdbcvals,
                                         check_ff_maxv=check_ff_maxv, **icd)

@@ -393,6 +393,49 @@ class _FunctionalLog(_Attachment):
                     functionals_on=self.where, functionals_names=self.names)
 
 
+class _QuadraticLog(_Attachment):
+    """`resident=dict(quadratics=qf)` of `cnab` / `sbdftwo`, `qf` a
+    `fem.QuadraticFunctionals` (the energy budget): arms the stepper's
+    quadratics per slice (or chunk) next to the tables -- the matrices stay on
+    the device from slice to slice --, collects the rows of the device's log
+    and their times; where the loop takes one step at a time the same rows
+    come from `qf.evaluate` on the host.  The forms carry CONSTANT Dirichlet
+    values: a loop with moving ones is refused"""
+
+    def __init__(self, stepper, qf, dt, max_grid=None):
+        self.stepper, self.qf, self.dt = stepper, qf, dt
+        self.max_grid = max_grid
+        self.ys, self.ts = [], []
+        self.where = None
+        self.names = list(qf.names)
+
+    def arm(self, times, tables):
+        self.stepper.set_quadratics(self.qf, len(times), self.dt,
+                                    max_grid=self.max_grid)
+
+    def collect(self, times):
+        self.add(self.stepper.get_quadratics(0, len(times)), times)
+        self.where = 'device'
+
+    def add(self, rows, times):
+        self.ys.append(np.asarray(rows, dtype=np.float64))
+        self.ts.extend(times)
+
+    def host_row(self, step):
+        self.add(self.qf.evaluate(step.v, step.v_prev, self.dt
+                                  ).reshape((1, -1)), [step.time])
+        self.where = 'host'
+
+    def result(self):
+        y = np.vstack(self.ys) if self.ys else np.zeros((0, self.qf.nQ))
+        return y, np.array(self.ts, dtype=np.float64)
+
+    def report(self):
+        qy, qt = self.result()
+        return dict(quadratics=qy, quadratics_t=qt,
+                    quadratics_on=self.where, quadratics_names=self.names)
+
+
 class _StatisticsSums(_Attachment):
     """`resident=dict(statistics=fs)` of `cnab` / `sbdftwo`, `fs` a
     `fem.FlowStatistics`: arms the stepper's statistics per slice (or chunk)
@@ -510,7 +553,7 @@ class _ImexLoop(object):
         self.attachments = []
 
     def attach(self, lti, fb_dev, tstart):
-        """the functionals, the statistics and the feedback -- a
+        """the functionals, the statistics, the quadratics and the feedback -- a
         `LinearFeedback` `lti` that can run resident (`fb_dev`) as the
         observer on the device -- in the order they are armed in (inside the
         loop's `try`: they may refuse)"""
@@ -526,8 +569,16 @@ class _ImexLoop(object):
                 lti, self.stepper, self.drm, *self.scheme.fb_weights,
                 dt=self.dt, tstart=tstart))
         fs = self.rsd.get('statistics', None)
+        qf = self.rsd.get('quadratics', None)
+        if qf is not None and self.moving:
+            raise ValueError(
+                '`quadratics` with moving Dirichlet values: the forms carry '
+                'the boundary values as constants')
         self.attachments += [a for a in (
-            flog, None if fs is None else _StatisticsSums(self.stepper, fs))
+            flog, None if fs is None else _StatisticsSums(self.stepper, fs),
+            None if qf is None else _QuadraticLog(
+                self.stepper, qf, self.dt,
+                max_grid=self.rsd.get('quadratics_max_grid', None)))
             if a is not None]
 
     def _terms_at(self, ctime, v_c=None, p_c=None):
@@ -901,6 +952,20 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                         itself (on top of what it held) and, as a dict, in
                         `LAST_RUN['statistics']`; `['statistics_on']` says
                         'device' or 'host'
+      `quadratics`      a `fem.QuadraticFunctionals` (the energy budget:
+                        kinetic energy, dissipation rate, `u^T M du/dt`, the
+                        M-norm of `du/dt`; any forms `a^T Q b` over sparse
+                        matrices): evaluated on the device after every step
+                        of a slice (`ImexStepper.set_quadratics`; the
+                        matrices are uploaded once), rows and times as for
+                        `functionals`: `LAST_RUN['quadratics']` is `nsteps x
+                        nQ`, `['quadratics_t']` its times, `['quadratics_on']`
+                        'device' or 'host' (`qf.evaluate` per step),
+                        `['quadratics_names']` the forms' names.  Constant
+                        Dirichlet values only: `ValueError` with `bcs_ini` not
+                        empty.  `quadratics_max_grid` caps the workgroups of
+                        the kernel and with them the log (`nsteps x G x nQ`
+                        doubles per slice)
     `LAST_RUN['record']` says 'device' or 'host', `LAST_RUN['run_calls']`
     counts the `stepper.run` calls of the loop.
     The per-step data the callbacks return (`f_tdp`, `g_tdp`, `applybcs`) are

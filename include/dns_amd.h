@@ -578,6 +578,57 @@ int dns_imex_get_stats(dns_imex *st, int32_t first_bin, int32_t count,
                        double *counts, double *s1, double *s2, double *sx);
 /* statistics off (the step is what it was before) */
 int dns_imex_clear_stats(dns_imex *st);
+/* Quadratic functionals of the velocity (the energy budget: kinetic energy
+ * 1/2 u^T M u, dissipation rate u^T A u, the rate u^T M du/dt, the M-norm of
+ * du/dt) in a log on the device: while dns_imex_step / dns_imex_run step (and
+ * replay their graphs), one more kernel per step evaluates nQ forms over nM
+ * sparse matrices Q_0 .. Q_{nM-1} of the state the step has left.  With v =
+ * current velocity, w = v - v_prev (the one before) and the operands a_0 = v,
+ * a_1 = w:
+ *     y_k = scale_k * ( dt^-(l_k + r_k) * a_{l_k}^T Q_{m_k} a_{r_k}
+ *                       + qa_k . v + (qw_k . w) / dt + c0_k )
+ * mats: nM host CSR matrices, each NV x NV, general (not assumed symmetric);
+ * mat / lop / rop: nQ entries each, m_k in [0, nM), l_k and r_k 0 or 1; qa,
+ * qw: nQ x NV (host CSR, NULL: no such term); c0 / scale: nQ values (NULL: 0 /
+ * 1).  The sparse rows and c0 carry constant Dirichlet values g: for u = E v +
+ * g, u^T Q u = v^T Q_ii v + (g^T (Q_bi + Q_ib^T)) v + g^T Q_bb g.  Forms that
+ * share a matrix share one pass over it.
+ * Row r of the log belongs to the (r+1)-th step after this call, which resets
+ * the step counter like dns_imex_set_rhs_table (call it after that one);
+ * stepping past the last row fails with DNS_ERR_NOT_READY.  The log is nrows x
+ * G x nQ doubles, G the workgroups of the kernel (one per 16 rows of the
+ * matrices, at most 256; max_grid > 0 caps it lower, 0: the default) -- the
+ * getter sums G in index order, nothing is added atomically: the same bits
+ * launched or replayed.  A batch dns_imex_run restores and repeats overwrites
+ * its own rows.  Calling it again re-arms it: buffers that are large enough
+ * are kept, and the same matrices are neither uploaded again nor change what a
+ * captured step graph is keyed by -- "the same" means as many matrices as the
+ * device holds, each equal to the one held entry by entry (row pointers,
+ * columns and the bytes of the values; the library keeps a host copy to
+ * compare with: 12 bytes per non-zero and 4 per row of host memory for as
+ * long as the forms are set, and one pass over it per call).  Every check
+ * comes first: a call refused for its arguments or for the stepper's state
+ * leaves the forms that were there; a failed allocation or upload behind the
+ * checks (DNS_ERR_HIP) leaves the stepper without quadratics.
+ * Limits (DNS_ERR_BAD_ARGUMENT beyond them): 1 <= nM <= 4, 1 <= nQ <= 8,
+ * nrows >= 1, a log below 2^31 entries; column indices inside [0, NV); any
+ * number of non-zeros.  A row-partitioned stepper and a convection operator
+ * with a per-step Dirichlet table (dns_conv_set_dbc_table: moving boundary
+ * values are not part of the constants) are refused, here and by the step.
+ * Works with and without the other attachments. */
+int dns_imex_set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
+                            int32_t nQ, const int32_t *mat, const int32_t *lop,
+                            const int32_t *rop, const dns_csr *qa,
+                            const dns_csr *qw, const double *c0,
+                            const double *scale, double dt, int32_t nrows,
+                            int32_t max_grid);
+/* rows [first, first + count) of the log: out (count x nQ) */
+int dns_imex_get_quadratics(dns_imex *st, int32_t first, int32_t count,
+                            double *out);
+/* G: the workgroups the log is laid out for (nrows x G x nQ doubles) */
+int dns_imex_quadratics_grid(dns_imex *st, int32_t *grid);
+/* quadratics off (the step is what it was before) */
+int dns_imex_clear_quadratics(dns_imex *st);
 /* ||v||_2 of the current velocity (blow-up guard, tiu:94-103) */
 int dns_imex_vnorm(dns_imex *st, double *out);
 

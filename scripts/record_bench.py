@@ -39,6 +39,14 @@ One command per leg (profiles/r08_recorder/README.md):
                   every step, ONE download, the same sums by NumPy
   --leg stats_stepwise   `run(1)` + `get_state()` + `FlowStatistics.add` per
                   step (profiles/r13_statistics/README.md)
+  --leg quad      `run(steps)` with the energy budget of every step on the device
+                  (kinetic energy, dissipation rate, its rate and the M-norm of
+                  dv/dt: `fem.energy_budget`, `ImexStepper.set_quadratics`),
+                  then ONE download of the rows
+  --leg quad_by_record  what there is without it: a device snapshot of every
+                  step, ONE download, `QuadraticFunctionals.evaluate` per step
+  --leg quad_stepwise   `run(1)` + `get_state()` + `evaluate` per step
+                  (profiles/r14_quadratics/README.md)
   --refine R      the same legs on the mesh refined R times (multigrid Schur
                   block, dt = 1/(512 2^R), start from rest, as refined_bench.py)
 
@@ -470,13 +478,101 @@ def leg_stats_stepwise(su, steps, spin):
     return out
 
 
+def leg_quad(su, steps, spin):
+    from dolfin_navier_scipy_amd import fem
+    stp, cf, opts, close = su.stepper()
+    try:
+        qf = fem.energy_budget(su.femp['V'], su.femp)
+        dt = getattr(su, 'dt', 1./512)
+        # (set before the spin-up, rows for up to three windows: as
+        # _leg_recorded)
+        stp.set_quadratics(qf, spin + 3*steps, dt)
+        stp.run(spin, cf, opts)
+        secs, its, n = _timed_window(stp, cf, opts, steps)
+        out = _record(stp, steps, secs, its)
+        out['windows'] = n
+        spin += (n - 1)*steps
+        t0 = time.perf_counter()
+        rows = stp.get_quadratics(spin, steps)
+        dl = time.perf_counter() - t0
+        # (what crosses the bus: every workgroup's share of every row, the
+        # getter sums them.  What the kernel must read per step: the matrices
+        # -- 12 bytes per non-zero, 4 per row -- and the two velocities)
+        NV = qf.NV
+        grid = stp.quadratics_grid()
+        nnz = sum(int(m.nnz) for m in qf.mats)
+        out.update(download_seconds=dl,
+                   download_bytes=int(steps*grid*qf.nQ*8),
+                   steps_per_s_with_download=steps/(secs + dl),
+                   rows_bytes=int(rows.nbytes), workgroups=grid,
+                   kernel_bytes_per_step=int(12*nnz + 4*qf.nM*(NV + 1)
+                                             + 16*NV),
+                   nnz=nnz, names=qf.names, row_last=rows[-1].tolist())
+    finally:
+        close()
+    return out
+
+
+def leg_quad_by_record(su, steps, spin):
+    from dolfin_navier_scipy_amd import fem
+    stp, cf, opts, close = su.stepper()
+    try:
+        qf = fem.energy_budget(su.femp['V'], su.femp)
+        dt = getattr(su, 'dt', 1./512)
+        stp.set_recorder(spin + 3*steps, snap_slots='all')
+        stp.run(spin, cf, opts)
+        secs, its, n = _timed_window(stp, cf, opts, steps)
+        out = _record(stp, steps, secs, its)
+        out['windows'] = n
+        spin += (n - 1)*steps
+        t0 = time.perf_counter()
+        # (one snapshot more: the state before the first step of the window)
+        v, p = stp.record_snapshots(spin - 1, steps + 1)
+        dl = time.perf_counter() - t0
+        rows = np.array([qf.evaluate(v[k + 1], v[k], dt)
+                         for k in range(steps)])
+        ev = time.perf_counter() - t0 - dl
+        out.update(download_seconds=dl, evaluate_seconds=ev,
+                   download_bytes=int(v.nbytes + p.nbytes),
+                   steps_per_s_with_download=steps/(secs + dl + ev),
+                   names=qf.names, row_last=rows[-1].tolist())
+    finally:
+        close()
+    return out
+
+
+def leg_quad_stepwise(su, steps, spin):
+    from dolfin_navier_scipy_amd import fem
+    stp, cf, opts, close = su.stepper()
+    try:
+        qf = fem.energy_budget(su.femp['V'], su.femp)
+        dt = getattr(su, 'dt', 1./512)
+        stp.run(spin, cf, opts)
+        vprev = stp.get_state()[0][:, 0]
+        rows = np.empty((steps, qf.nQ))
+        t0 = time.perf_counter()
+        for k in range(steps):
+            stp.run(1, cf, opts)
+            v, p = stp.get_state()
+            rows[k] = qf.evaluate(v[:, 0], vprev, dt)
+            vprev = v[:, 0]
+        secs = time.perf_counter() - t0
+        out = dict(seconds=secs, steps_per_s=steps/secs, vnorm=stp.vnorm(),
+                   names=qf.names, row_last=rows[-1].tolist())
+    finally:
+        close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--leg', choices=('stepwise', 'open', 'snap', 'outputs',
                                       'forces', 'forces_stepwise',
                                       'moving_open', 'moving_forces',
                                       'moving_host', 'stats',
-                                      'stats_by_record', 'stats_stepwise'),
+                                      'stats_by_record', 'stats_stepwise',
+                                      'quad', 'quad_by_record',
+                                      'quad_stepwise'),
                     required=True)
     ap.add_argument('--with-outputs', action='store_true',
                     help="leg forces: the recorder's y log on as well")
@@ -498,7 +594,9 @@ def main():
     fn = dict(moving_open=leg_moving_open, moving_forces=leg_moving_forces,
               moving_host=leg_moving_host, stats=leg_stats,
               stats_by_record=leg_stats_by_record,
-              stats_stepwise=leg_stats_stepwise,
+              stats_stepwise=leg_stats_stepwise, quad=leg_quad,
+              quad_by_record=leg_quad_by_record,
+              quad_stepwise=leg_quad_stepwise,
               stepwise=leg_stepwise, open=leg_open, snap=leg_snap,
               outputs=leg_outputs, forces_stepwise=leg_forces_stepwise,
               forces=(leg_forces_outputs if args.with_outputs
@@ -506,7 +604,8 @@ def main():
     reps = [fn(su, args.steps, args.spin) for _ in range(args.repeats)]
     key = 'steps_per_s_with_download' \
         if args.leg in ('snap', 'outputs', 'forces', 'moving_forces',
-                        'moving_host', 'stats', 'stats_by_record') \
+                        'moving_host', 'stats', 'stats_by_record', 'quad',
+                        'quad_by_record') \
         else 'steps_per_s'
     rates = [r['steps_per_s'] for r in reps]
     out = dict(leg=args.leg, label=args.label, steps=args.steps,
