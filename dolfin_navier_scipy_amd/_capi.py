@@ -83,6 +83,24 @@ class dns_imex_coeffs(ct.Structure):
                 ('carry_residual', ct.c_int32)]
 
 
+class dns_spmv_epi(ct.Structure):
+    _fields_ = [('kernel', ct.c_int32), ('nv', ct.c_int32),
+                ('fp32_vals', ct.c_int32), ('mode', ct.c_int32),
+                ('alpha', ct.c_double), ('beta', ct.c_double),
+                ('omega', ct.c_double), ('b', c_double_p), ('x2', c_double_p),
+                ('dinv', c_double_p), ('xin', c_double_p), ('V', c_double_p),
+                ('ld', ct.c_int64), ('ny', ct.c_int64),
+                ('part_len', ct.c_int64), ('part_bb_len', ct.c_int64),
+                ('nsplit', ct.c_int32), ('nvec', ct.c_int32),
+                ('with_ww', ct.c_int32), ('with_bb', ct.c_int32),
+                ('map_on', ct.c_int32), ('row0', ct.c_int32),
+                ('len1', ct.c_int32), ('row2', ct.c_int32),
+                ('len2', ct.c_int32), ('nvl', ct.c_int32), ('v0', ct.c_int32),
+                ('p0', ct.c_int32), ('grid_cap', ct.c_int32),
+                ('use_guard', ct.c_int32), ('guard', ct.c_int32),
+                ('pad', ct.c_int32)]
+
+
 # every symbol include/dns_amd.h declares: name -> (restype, argtypes)
 _VP = ct.c_void_p
 ALLREDUCE_CB = ct.CFUNCTYPE(ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_int32)
@@ -249,6 +267,10 @@ SIGNATURES = {
                                  c_double_p, c_double_p, ct.c_int32,
                                  ct.c_int32, c_double_p,
                                  ct.POINTER(ct.c_int64)]),
+    'dns_spmv_epilogue': (ct.c_int, [ct.c_int, ct.POINTER(dns_csr),
+                                     ct.POINTER(dns_spmv_epi), c_double_p,
+                                     c_double_p, c_double_p, c_double_p,
+                                     c_int32_p, c_int32_p]),
     'dns_spmv_bench': (ct.c_int, [ct.c_int, ct.POINTER(dns_csr), ct.c_int32,
                                   ct.c_int32, ct.c_int32, c_double_p,
                                   c_double_p]),

@@ -3074,6 +3074,184 @@ int dns_spmv_pair(int device, const dns_csr *k, int32_t nv, const double *x,
     return DNS_OK;
 } DNS_CAPI_CATCH
 
+// ONE launch of k_spmv_stream16x / k_spmv_pair16x with the caller's epilogue
+// (tests: every StreamEpi option in isolation).  y, part and part_bb go up with
+// the caller's contents and come back, so untouched entries can be told apart
+int dns_spmv_epilogue(int device, const dns_csr *a, const dns_spmv_epi *e,
+                      const double *x, double *y, double *part,
+                      double *part_bb, int32_t *nparts, int32_t *nblocks) try {
+    DNS_TRY(check_csr(a, "A"));
+    if (!e || !x || !y || !nparts || !nblocks)
+        return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    const bool pair = e->kernel == DNS_EPI_PAIR;
+    const bool split = e->x2 != nullptr;
+    const int64_t ny = e->ny;
+    if (e->kernel != DNS_EPI_STREAM && !pair)
+        return fail(DNS_ERR_BAD_ARGUMENT, "unknown kernel %d", e->kernel);
+    if (e->mode < DNS_EPI_PLAIN || e->mode > DNS_EPI_ADD_CB)
+        return fail(DNS_ERR_BAD_ARGUMENT, "unknown mode %d", e->mode);
+    if (a->nrows < 1 || a->ncols < 1 || ny < 1 || ny > INT32_MAX)
+        return fail(DNS_ERR_BAD_ARGUMENT, "empty matrix or result");
+    if (e->grid_cap < 1 || e->grid_cap > 65535)
+        return fail(DNS_ERR_BAD_ARGUMENT, "grid_cap outside [1, 65535]");
+    if (e->nvec < 0)     // (too many: the launchers refuse)
+        return fail(DNS_ERR_BAD_ARGUMENT, "negative nvec");
+    if (!part && (e->nvec > 0 || e->with_ww || e->with_bb))
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "dots without a partials array are not computed");
+    if (part && e->nvec > 0 && (!e->V || e->ld < ny))
+        return fail(DNS_ERR_BAD_ARGUMENT, "V missing or ld < ny");
+    if (e->with_bb && (!part_bb || !e->b))
+        return fail(DNS_ERR_BAD_ARGUMENT, "<b, b> needs b and part_bb");
+    if (e->mode == DNS_EPI_PLAIN) {
+        if (e->dinv || e->xin)
+            return fail(DNS_ERR_BAD_ARGUMENT, "plain mode reads no dinv / xin");
+        if (!e->b && e->beta != 0.0)
+            return fail(DNS_ERR_BAD_ARGUMENT, "beta without b is ignored");
+    } else {
+        if (pair)
+            return fail(DNS_ERR_BAD_ARGUMENT,
+                        "the pair kernel has no sweep / add_cb epilogue");
+        if (!e->dinv || !e->b)
+            return fail(DNS_ERR_BAD_ARGUMENT, "sweep / add_cb need dinv and b");
+        if (e->beta != 0.0)
+            return fail(DNS_ERR_BAD_ARGUMENT, "sweep / add_cb ignore beta");
+        if (e->mode == DNS_EPI_ADD_CB && e->xin)
+            return fail(DNS_ERR_BAD_ARGUMENT, "add_cb reads no xin");
+    }
+    if (split && (e->nsplit < 1 || e->nsplit >= a->ncols))
+        return fail(DNS_ERR_BAD_ARGUMENT, "nsplit outside (0, ncols)");
+    if (pair) {
+        if (split || e->fp32_vals || e->map_on)
+            return fail(DNS_ERR_BAD_ARGUMENT,
+                        "the pair kernel takes no x2, fp32 values or RowMap");
+        if (ny != a->ncols)
+            return fail(DNS_ERR_BAD_ARGUMENT, "pair: ny must be the columns");
+        if (e->nvl >= 0) {
+            const int64_t npl = (int64_t)a->nrows - e->nvl;
+            if (e->v0 < 0 || e->p0 < 0 || npl < 0 ||
+                (int64_t)e->v0 + e->nvl > e->nv ||
+                (int64_t)e->p0 + npl > (int64_t)a->ncols - e->nv)
+                return fail(DNS_ERR_BAD_ARGUMENT, "pair: row block outside K");
+        } else if (a->nrows != a->ncols) {
+            return fail(DNS_ERR_BAD_ARGUMENT, "K must be square");
+        }
+    } else if (e->map_on) {
+        if (e->row0 < 0 || e->len1 < 0 || e->row2 < 0 || e->len2 < 0 ||
+            (int64_t)e->len1 + e->len2 != a->nrows ||
+            (int64_t)e->row0 + e->len1 > ny || (int64_t)e->row2 + e->len2 > ny)
+            return fail(DNS_ERR_BAD_ARGUMENT, "RowMap outside [0, ny)");
+    } else if (ny != a->nrows) {
+        return fail(DNS_ERR_BAD_ARGUMENT, "ny must be the rows (no RowMap)");
+    }
+    DNS_HIP(hipSetDevice(device));
+    ScopedStream ss;
+    DNS_HIP(hipStreamCreate(&ss.s));
+    CsrDev A;
+    PairDev Ap;
+    DevBuf<float> v32;
+    int nb;
+    if (pair) {
+        HostPair P;
+        const HostCsr kh = host_copy(a);
+        const char *why = "";
+        if (!host_pair_from_k(kh, e->nv, P, &why, e->nvl >= 0 ? e->nvl : -1,
+                              e->nvl >= 0 ? e->v0 : 0, e->nvl >= 0 ? e->p0 : 0))
+            return fail(DNS_ERR_BAD_ARGUMENT, "no pair format: %s", why);
+        DNS_TRY(Ap.upload(P, ss.s));
+        nb = Ap.nblocks;
+    } else {
+        DNS_TRY(A.upload(a, ss.s));
+        nb = A.nrowblocks_t[1];
+        if (e->fp32_vals) {
+            std::vector<float> h((size_t)a->nnz + 2, 0.0f);
+            for (int64_t k = 0; k < a->nnz; ++k) h[k] = (float)a->vals[k];
+            DNS_TRY(v32.alloc(h.size()));
+            DNS_TRY(v32.upload(h.data(), h.size(), ss.s));
+        }
+    }
+    const int grid = nb > 0 ? std::max(1, std::min(nb, (int)e->grid_cap)) : 0;
+    const int nrow_p = e->nvec + 1;
+    if (part && e->part_len < (int64_t)nrow_p * grid)
+        return fail(DNS_ERR_BAD_ARGUMENT, "part holds fewer than %d x %d",
+                    nrow_p, grid);
+    if (e->with_bb && e->part_bb_len < grid)
+        return fail(DNS_ERR_BAD_ARGUMENT, "part_bb holds fewer than %d", grid);
+    // every vector has its full length on the device (NaN where the caller
+    // supplies nothing): a kernel that ignores an option reads NaN, not
+    // another allocation
+    const double qnan = __builtin_nan("");
+    auto up = [&](DevBuf<double> &d, const double *h, size_t have,
+                  size_t len) -> int {
+        std::vector<double> tmp(len, qnan);
+        if (h) std::copy(h, h + have, tmp.begin());
+        DNS_TRY(d.alloc(len));
+        return d.upload(tmp.data(), len, ss.s);
+    };
+    const size_t nc = (size_t)a->ncols;
+    const size_t nx = split ? (size_t)e->nsplit : nc;
+    DevBuf<double> dx, dx2, dy, db, ddinv, dxin, dV, dpart, dbb;
+    DevBuf<int> dguard;
+    DNS_TRY(up(dx, x, nx, nc));
+    if (split) DNS_TRY(up(dx2, e->x2, nc - nx, nc));
+    DNS_TRY(up(dy, y, (size_t)ny, (size_t)ny));
+    if (e->b) DNS_TRY(up(db, e->b, (size_t)ny, (size_t)ny));
+    if (e->dinv) DNS_TRY(up(ddinv, e->dinv, (size_t)ny, (size_t)ny));
+    if (e->xin) DNS_TRY(up(dxin, e->xin, (size_t)ny, (size_t)ny));
+    if (part && e->nvec > 0)
+        DNS_TRY(up(dV, e->V, (size_t)e->ld * e->nvec, (size_t)e->ld * e->nvec));
+    if (part)
+        DNS_TRY(up(dpart, part, (size_t)e->part_len,
+                   std::max<size_t>(1, (size_t)e->part_len)));
+    if (e->with_bb)
+        DNS_TRY(up(dbb, part_bb, (size_t)e->part_bb_len,
+                   std::max<size_t>(1, (size_t)e->part_bb_len)));
+    if (e->use_guard) {
+        const int gv = e->guard;
+        DNS_TRY(dguard.alloc(1));
+        DNS_TRY(dguard.upload(&gv, 1, ss.s));
+    }
+    StreamEpi ep = stream_epi_plain(e->alpha, e->beta, e->b ? db.p : nullptr);
+    ep.x2 = split ? dx2.p : nullptr;
+    ep.nsplit = split ? e->nsplit : 0;
+    if (e->mode != DNS_EPI_PLAIN) {
+        ep.dinv = ddinv.p;
+        ep.xin = e->xin ? dxin.p : nullptr;
+        ep.omega = e->omega;
+        ep.add_cb = e->mode == DNS_EPI_ADD_CB;
+    }
+    if (part) {
+        ep.V = dV.p;
+        ep.ld = (size_t)e->ld;
+        ep.nvec = e->nvec;
+        ep.with_ww = e->with_ww != 0;
+        ep.part = dpart.p;
+        ep.nparts = grid;
+        ep.part_bb = e->with_bb ? dbb.p : nullptr;
+    }
+    if (!pair && e->map_on) {
+        ep.map_on = 1;
+        ep.rm = RowMap{e->row0, e->len1, e->row2, e->len2};
+    }
+    if (pair)
+        DNS_TRY(launch_pair16x(Ap, dx.p, dy.p, ep, ss.s, dguard.p,
+                               e->grid_cap));
+    else if (e->fp32_vals)
+        DNS_TRY(launch_stream16x<float>(A, v32.p, dx.p, dy.p, ep, ss.s,
+                                        dguard.p, e->grid_cap));
+    else
+        DNS_TRY(launch_stream16x<double>(A, A.vals.p, dx.p, dy.p, ep, ss.s,
+                                         dguard.p, e->grid_cap));
+    DNS_TRY(dy.download(y, (size_t)ny, ss.s));
+    if (part) DNS_TRY(dpart.download(part, (size_t)e->part_len, ss.s));
+    if (e->with_bb)
+        DNS_TRY(dbb.download(part_bb, (size_t)e->part_bb_len, ss.s));
+    DNS_HIP(hipStreamSynchronize(ss.s));
+    *nparts = grid;
+    *nblocks = nb;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
 int dns_hbm_probe(int device, int64_t bytes, int32_t kind, int32_t reps,
                   double *gbytes_per_s) try {
     if (!gbytes_per_s || reps < 1 || bytes < 4096 || kind < 0 || kind > 8)

@@ -390,6 +390,10 @@ inline int launch_pair16x(const PairDev &A, const double *x, double *y,
                           int grid_cap = 65535, int diag = 0) {
     if (!A.ready) return fail(DNS_ERR_NOT_READY, "no pair format");
     if (A.nblocks == 0) return DNS_OK;
+    if (ep.part && ep.nvec > kStreamDots)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "fused dots: %d vectors, at most %d per launch", ep.nvec,
+                    kStreamDots);
     PairArgs a;
     a.rpA = A.rpA.p; a.rpB = A.rpB.p; a.rpC = A.rpC.p;
     a.rowblocks = A.rowblocks.p; a.base = A.base.p;

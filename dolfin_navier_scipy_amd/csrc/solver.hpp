@@ -291,6 +291,10 @@ inline int launch_stream16x(const CsrDev &A, const VT *vals, const double *x,
     if (A.nrows == 0) return DNS_OK;
     if (!A.c16.p)
         return fail(DNS_ERR_NOT_READY, "matrix has no 16-bit column table");
+    if (ep.part && ep.nvec > kStreamDots)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "fused dots: %d vectors, at most %d per launch", ep.nvec,
+                    kStreamDots);
     const double avg = A.nrows > 0 ? (double)A.nnz / A.nrows : 1.0;
     const int nb = A.nrowblocks_t[1];
     const int grid = std::max(1, std::min(nb, grid_cap));

@@ -7,7 +7,7 @@ import scipy.sparse as sps
 from . import _capi as C
 
 __all__ = ['streaming_precond_defaults', 'choose_schur', 'SaddleSystem', 'ImexStepper', 'spmv', 'dot', 'axpy', 'gemv',
-           'dense_inverse', 'spmv_bench', 'spmv_pair', 'solve_opts', 'precond_opts']
+           'dense_inverse', 'spmv_bench', 'spmv_pair', 'spmv_epilogue', 'solve_opts', 'precond_opts']
 
 _METHODS = {'gmres': C.DNS_METHOD_GMRES, 'bicgstab': C.DNS_METHOD_BICGSTAB}
 _SCHUR = {'dense': C.DNS_SCHUR_DENSE, 'jacobi': C.DNS_SCHUR_JACOBI, 'mg': 2}
@@ -925,6 +925,72 @@ def spmv_pair(K, nv, x, reps=0, warmup=1, device=0):
     if reps > 0:
         return out, secs.value, fb.value
     return out
+
+
+def spmv_epilogue(A, x, y0, kernel='stream', nv=0, fp32_vals=False,
+                  alpha=1., beta=0., b=None, x2=None, nsplit=0, mode='plain',
+                  dinv=None, xin=None, omega=1., V=None, nvec=0, ld=None,
+                  with_ww=False, with_bb=False, part=None, part_bb=None,
+                  rowmap=None, pair_block=None, grid_cap=65535, guard=None,
+                  device=0):
+    """ONE launch of the streaming kernel with epilogues (`kernel='stream'`)
+    or of the pair kernel (`'pair'`, `nv` velocity dofs) through
+    `dns_spmv_epilogue` -- tests of the epilogues in isolation.
+
+    `y0`: initial contents of `y` (global length); `part` / `part_bb`: the
+    caller's pre-filled partials arrays (`part` turns the fused dots on), both
+    returned as the device left them.  `V`: `nvec` rows of `ld` entries;
+    `rowmap = (row0, len1, row2, len2)`; `pair_block = (nvl, v0, p0)`;
+    `guard`: value of a device flag (None: no flag).  Returns
+    `dict(y, part, part_bb, nparts, nblocks)`."""
+    lib = C.load_library()
+    view = C.CsrView(A)
+    f64 = lambda v: None if v is None else C.as_f64(v)
+    split = x2 is not None
+    x = C.as_f64(x, size=int(nsplit) if split else view.shape[1])
+    x2 = None if not split else C.as_f64(x2, size=view.shape[1] - int(nsplit))
+    y = C.as_f64(y0).copy()
+    ny = y.size
+    b, dinv, xin = f64(b), f64(dinv), f64(xin)
+    for v in (b, dinv, xin):
+        if v is not None and v.size != ny:
+            raise ValueError('b, dinv and xin hold one entry per row of y')
+    e = C.dns_spmv_epi()
+    e.kernel = {'stream': 0, 'pair': 1}[kernel]
+    e.nv = int(nv)
+    e.fp32_vals = int(bool(fp32_vals))
+    e.mode = {'plain': 0, 'sweep': 1, 'add_cb': 2}[mode]
+    e.alpha, e.beta, e.omega = float(alpha), float(beta), float(omega)
+    e.b, e.x2, e.dinv, e.xin = C.dptr(b), C.dptr(x2), C.dptr(dinv), C.dptr(xin)
+    e.nsplit = int(nsplit)
+    e.nvec = int(nvec)
+    e.ld = ny if ld is None else int(ld)
+    if V is not None:
+        V = C.as_f64(V)
+        if V.size != e.ld * e.nvec:
+            raise ValueError('V holds nvec rows of ld entries')
+    e.V = C.dptr(V)
+    e.ny = ny
+    e.with_ww, e.with_bb = int(bool(with_ww)), int(bool(with_bb))
+    part = None if part is None else C.as_f64(part).copy()
+    part_bb = None if part_bb is None else C.as_f64(part_bb).copy()
+    e.part_len = 0 if part is None else part.size
+    e.part_bb_len = 0 if part_bb is None else part_bb.size
+    if rowmap is not None:
+        e.map_on = 1
+        e.row0, e.len1, e.row2, e.len2 = [int(v) for v in rowmap]
+    e.nvl = -1
+    if pair_block is not None:
+        e.nvl, e.v0, e.p0 = [int(v) for v in pair_block]
+    e.grid_cap = int(grid_cap)
+    e.use_guard = int(guard is not None)
+    e.guard = int(guard or 0)
+    nparts, nblocks = ct.c_int32(0), ct.c_int32(0)
+    C.check(lib.dns_spmv_epilogue(device, view.byref(), ct.byref(e), C.dptr(x),
+                                  C.dptr(y), C.dptr(part), C.dptr(part_bb),
+                                  ct.byref(nparts), ct.byref(nblocks)))
+    return dict(y=y, part=part, part_bb=part_bb, nparts=nparts.value,
+                nblocks=nblocks.value)
 
 
 def dot(x, y, device=0):

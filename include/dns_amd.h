@@ -701,6 +701,53 @@ int dns_spmv_pair(int device, const dns_csr *k, int32_t nv, const double *x,
                   double *y, int32_t reps, int32_t warmup, double *avg_seconds,
                   int64_t *format_bytes);
 
+/* ONE launch of the streaming kernel with epilogues (k_spmv_stream16x) or of
+ * the pair kernel (k_spmv_pair16x) with the epilogue described here -- what the
+ * solver's large applies run, reachable in isolation (tests).  Vectors b, dinv,
+ * xin and the rows of V are indexed by GLOBAL row and hold `ny` entries (V: `ld
+ * >= ny` apart).  Any combination the chosen kernel does not implement is
+ * refused with DNS_ERR_BAD_ARGUMENT. */
+#define DNS_EPI_STREAM  0
+#define DNS_EPI_PAIR    1
+#define DNS_EPI_PLAIN   0   /* y = alpha A x + beta b                         */
+#define DNS_EPI_SWEEP   1   /* y = alpha (xin + omega dinv .* (b - A x))       */
+#define DNS_EPI_ADD_CB  2   /* y = alpha A x + omega dinv .* b                 */
+typedef struct dns_spmv_epi {
+    int32_t kernel;          /* DNS_EPI_STREAM / DNS_EPI_PAIR                  */
+    int32_t nv;              /* pair: GLOBAL number of velocity dofs           */
+    int32_t fp32_vals;       /* stream: values rounded to float on the device  */
+    int32_t mode;            /* DNS_EPI_PLAIN / _SWEEP / _ADD_CB               */
+    double alpha, beta, omega;
+    const double *b;         /* may be NULL (plain)                            */
+    const double *x2;        /* != NULL: x holds the columns < nsplit, x2 the  */
+    const double *dinv;      /*          other ncols - nsplit                  */
+    const double *xin;       /* sweep; NULL = 0                                */
+    const double *V;         /* fused dots: nvec vectors, ld apart             */
+    int64_t ld;
+    int64_t ny;              /* entries of y (global length)                   */
+    int64_t part_len;        /* doubles the caller's `part` / `part_bb` hold   */
+    int64_t part_bb_len;
+    int32_t nsplit;
+    int32_t nvec, with_ww, with_bb;
+    int32_t map_on;          /* stream: RowMap{row0, len1, row2, len2}         */
+    int32_t row0, len1, row2, len2;
+    int32_t nvl, v0, p0;     /* pair: nvl >= 0 = row block of nvl velocity rows
+                              * from even global row v0, pressure rows from p0 */
+    int32_t grid_cap;        /* at most this many workgroups (= partials)      */
+    int32_t use_guard, guard;/* use_guard: launch with a device flag = guard   */
+    int32_t pad;
+} dns_spmv_epi;
+/* `a`: the matrix (stream: its rows are the RowMap's; pair: K or a row block of
+ * K with global columns).  y (ny entries), part and part_bb are uploaded with
+ * the caller's contents, so what the launch did not write comes back as it
+ * was.  part != NULL turns the fused dots on: row i < nvec of the
+ * (nvec + 1) x *nparts table holds the partials of <V_i, y>, row nvec those of
+ * <y, y> (with_ww); part_bb[*nparts] those of <b, b> (with_bb).  *nparts = the
+ * grid that was launched, *nblocks = the row blocks of the format. */
+int dns_spmv_epilogue(int device, const dns_csr *a, const dns_spmv_epi *e,
+                      const double *x, double *y, double *part,
+                      double *part_bb, int32_t *nparts, int32_t *nblocks);
+
 /* Multigrid Schur block for pressure spaces too large for the dense inverse
  * (refined meshes).  `prol[l]` (CSR, n_l x n_{l+1}, l = 0 .. nprol-1) are the
  * prolongations of a nested hierarchy of pressure spaces, finest first (n_0 =

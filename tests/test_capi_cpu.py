@@ -51,6 +51,7 @@ def test_struct_layout_matches_header(capi):
     assert ct.sizeof(capi.dns_solve_opts) == 40
     assert ct.sizeof(capi.dns_solve_stats) == 48
     assert ct.sizeof(capi.dns_imex_coeffs) == 48
+    assert ct.sizeof(capi.dns_spmv_epi) == 176
 
 
 def test_null_and_bad_arguments_fail_cleanly(capi):
@@ -71,6 +72,32 @@ def test_null_and_bad_arguments_fail_cleanly(capi):
     y = np.zeros(4)
     st = lib.dns_spmv(0, view.byref(), capi.dptr(x), capi.dptr(y), 1.0, 0.0, 0)
     assert st == capi.DNS_ERR_BAD_ARGUMENT
+    # the epilogue entry: null arguments, a malformed matrix, and combinations
+    # the chosen kernel does not implement
+    assert lib.dns_spmv_epilogue(0, None, None, None, None, None, None, None,
+                                 None) == capi.DNS_ERR_BAD_ARGUMENT
+    good = capi.CsrView(A)
+    npb, nbl = ct.c_int32(0), ct.c_int32(0)
+
+    def epi(v=good, **kw):
+        e = capi.dns_spmv_epi(ny=4, grid_cap=8, nvl=-1, alpha=1.0)
+        for k, val in kw.items():
+            setattr(e, k, val)
+        return lib.dns_spmv_epilogue(0, v.byref(), ct.byref(e), capi.dptr(x),
+                                     capi.dptr(y), None, None, ct.byref(npb),
+                                     ct.byref(nbl))
+    d = capi.dptr(np.ones(4))
+    for bad in (dict(v=view), dict(kernel=2), dict(mode=3), dict(grid_cap=0),
+                dict(ny=5), dict(nvec=1), dict(with_bb=1), dict(beta=1.0),
+                dict(mode=1), dict(mode=1, dinv=d, b=d, beta=1.0),
+                dict(mode=2, dinv=d, b=d, xin=d), dict(x2=d, nsplit=4),
+                dict(map_on=1, row0=2, len1=4),
+                dict(kernel=1, nv=2, mode=1, dinv=d, b=d),
+                dict(kernel=1, nv=2, x2=d, nsplit=2),
+                dict(kernel=1, nv=2, fp32_vals=1),
+                dict(kernel=1, nv=2, map_on=1, len1=4),
+                dict(kernel=1, nv=2, nvl=2, v0=2, p0=0)):
+        assert epi(**bad) == capi.DNS_ERR_BAD_ARGUMENT, bad
 
 
 def test_no_device_is_loud(capi):
