@@ -242,6 +242,21 @@ SIGNATURES = {
                                            c_double_p]),
     'dns_imex_quadratics_grid': (ct.c_int, [_VP, c_int32_p]),
     'dns_imex_clear_quadratics': (ct.c_int, [_VP]),
+    'dns_imex_set_ensemble': (ct.c_int, [_VP, ct.c_int32, c_int32_p,
+                                         ct.c_int32, ct.c_int32]),
+    'dns_imex_get_ensemble': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
+                                         c_double_p]),
+    'dns_imex_ensemble_gram': (ct.c_int, [_VP, ct.POINTER(dns_csr),
+                                          ct.c_int32, c_double_p]),
+    'dns_imex_ensemble_combine': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
+                                             c_double_p, c_double_p]),
+    'dns_imex_clear_ensemble': (ct.c_int, [_VP]),
+    'dns_ensemble_gram': (ct.c_int, [ct.c_int, ct.c_int32, ct.c_int32,
+                                     ct.c_int32, c_double_p,
+                                     ct.POINTER(dns_csr), c_double_p]),
+    'dns_ensemble_combine': (ct.c_int, [ct.c_int, ct.c_int32, ct.c_int32,
+                                        ct.c_int32, c_double_p, ct.c_int32,
+                                        c_double_p, c_double_p]),
     'dns_imex_run_info': (ct.c_int, [_VP, c_int32_p, c_int32_p, c_int32_p,
                                      c_int32_p]),
     'dns_imex_step_counters': (ct.c_int, [_VP, ct.POINTER(ct.c_int64)]),

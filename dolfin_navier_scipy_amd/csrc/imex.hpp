@@ -2,6 +2,7 @@
 #pragma once
 #include "batch_policy.hpp"
 #include "convection.hpp"
+#include "ensemble.hpp"
 #include "feedback.hpp"
 #include "functional.hpp"
 #include "quadratic.hpp"
@@ -232,7 +233,28 @@ struct dns_imex : dns::Ring {
     std::unique_ptr<Quadratics> qd;
     int qd_launch(hipStream_t s);  // k_quadratic_step for the state as it stands
     uint64_t qd_key() const;
-    // What the five have in common (imex_attach_capi.inc): which of them
+    // snapshot ensemble (ensemble.hpp): k_ensemble_step runs in front of every
+    // step (the last of the front nodes) and once behind the last step of a
+    // call; it copies v into slot `slot[counter - 1]` of E, which the stepper
+    // owns ACROSS the slices of a time loop (they re-arm the slot table only).
+    // A row copied twice or by a restored batch has the same bits: no marks,
+    // no checkpoint.  The Gram matrix and the linear combinations run behind
+    // the loop as plain launches (`W`: the weights as uploaded last, `Wh`
+    // what they are; `y`, `part`, `gm`, `cf`, `out`: their scratch).
+    // Present = on.
+    struct Ensemble {
+        int rows = 0, nslots = 0;
+        size_t ldv = 0;
+        dns::DevBuf<int> slot;
+        dns::DevBuf<double> E;
+        std::unique_ptr<dns::EnsWeights> W;
+        dns::HostCsr Wh;
+        dns::DevBuf<double> y, part, gm, cf, out;
+    };
+    std::unique_ptr<Ensemble> ens;
+    int ens_launch(hipStream_t s); // k_ensemble_step for the state as it stands
+    uint64_t ens_key() const;
+    // What the six have in common (imex_attach_capi.inc): which of them
     // run in front of a step and which behind the last step of a call, what
     // they add to the key of a captured step, the refusals a step makes on
     // their behalf, and what they mean for the step counter.

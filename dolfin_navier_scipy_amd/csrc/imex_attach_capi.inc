@@ -1,8 +1,9 @@
 // The attachments of the resident IMEX loop -- observer feedback
 // (feedback.hpp), trajectory recorder (record.hpp), force functionals
 // (functional.hpp), flow statistics (stats.hpp), quadratic functionals
-// (quadratic.hpp): one node each in front of every step -- and their extern
-// "C" entry points (included by dns_amd.hip behind imex_capi.inc).
+// (quadratic.hpp), snapshot ensemble (ensemble.hpp): one node each in front of
+// every step -- and their extern "C" entry points (included by dns_amd.hip
+// behind imex_capi.inc).
 
 // "feedback on", its shape, its coefficients and every buffer k_lti_step is
 // handed: a graph captured for another set must not be replayed
@@ -174,10 +175,28 @@ int dns_imex::qd_launch(hipStream_t s) {
     return DNS_OK;
 }
 
-// ---- what the five have in common -------------------------------------------
+// "ensemble on", its shape and every buffer k_ensemble_step is handed (E is
+// kept from slice to slice, and with it the key)
+uint64_t dns_imex::ens_key() const {
+    const Ensemble &e = *ens;
+    return mix64(0xe5b, {kw(e.rows), kw(e.nslots), kw((long long)e.ldv),
+                         kw(e.slot.p), kw(e.E.p), kw(stepctr.p)});
+}
+
+int dns_imex::ens_launch(hipStream_t s) {
+    const Ensemble &e = *ens;
+    const dns::EnsStepArgs a{stepctr.p, e.rows, xs[cur].p, sys->nv, e.slot.p,
+                             e.E.p, e.nslots, e.ldv};
+    hipLaunchKernelGGL(dns::k_ensemble_step, dns::ensemble_step_grid(sys->nv),
+                       dns::kBlock, 0, s, a);
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+// ---- what the six have in common --------------------------------------------
 
 // In front of every step, in this order: k_lti_step leaves the right-hand
-// side the front kernels read, the other four write down / add the row of
+// side the front kernels read, the other five write down / add the row of
 // the step before.
 int dns_imex::launch_front_nodes(hipStream_t s) {
     if (fb.on) DNS_TRY(fb_launch(s));
@@ -185,6 +204,7 @@ int dns_imex::launch_front_nodes(hipStream_t s) {
     if (fn) DNS_TRY(fn_launch(s));
     if (stat) DNS_TRY(st_launch(s));
     if (qd) DNS_TRY(qd_launch(s));
+    if (ens) DNS_TRY(ens_launch(s));
     return DNS_OK;
 }
 
@@ -194,6 +214,7 @@ int dns_imex::launch_closing_nodes(hipStream_t s) {
     if (fn) DNS_TRY(fn_launch(s));
     if (stat) DNS_TRY(st_launch(s));
     if (qd) DNS_TRY(qd_launch(s));
+    if (ens) DNS_TRY(ens_launch(s));
     return DNS_OK;
 }
 
@@ -203,12 +224,13 @@ uint64_t dns_imex::attachments_key(uint64_t k) const {
     if (fn) k = mix64(k, {fn_key()});
     if (stat) k = mix64(k, {st_key()});
     if (qd) k = mix64(k, {qd_key()});
+    if (ens) k = mix64(k, {ens_key()});
     return k;
 }
 
 bool dns_imex::tables() const {
     return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on || rec ||
-           fn || stat || qd;
+           fn || stat || qd || ens;
 }
 
 int dns_imex::rows_left() const {
@@ -219,6 +241,7 @@ int dns_imex::rows_left() const {
     if (fn) lim = std::min(lim, fn->rows);
     if (stat) lim = std::min(lim, stat->rows);
     if (qd) lim = std::min(lim, qd->rows);
+    if (ens) lim = std::min(lim, ens->rows);
     if (conv && conv->dbc_rows > 0) lim = std::min(lim, conv->dbc_rows);
     return lim - tab_pos;
 }
@@ -246,7 +269,7 @@ int dns_imex::rewind_tables() {
     return DNS_OK;
 }
 
-// None of the five runs on a row-partitioned / distributed stepper: refused
+// None of the six runs on a row-partitioned / distributed stepper: refused
 // when it is set and, should the stepper be partitioned later, by the step.
 int dns_imex::refuse_partitioned(const char *noun, const char *reason) const {
     if (!(r1_rows || part.on || sys->dist())) return DNS_OK;
@@ -265,6 +288,9 @@ static const char *const kStPartitioned =
     "the sums are local to a rank, the getter would need a gather (multi-rank "
     "statistics are not supported)";
 static const char *const kQdPartitioned = "the sums would need an all-reduce";
+static const char *const kEnsPartitioned =
+    "the slots would hold a rank's rows only, the Gram matrix would need an "
+    "all-reduce (multi-rank ensembles are not supported)";
 static const char *const kQdMovingBc =
     "quadratics with a per-step Dirichlet table on the convection operator "
     "(dns_conv_set_dbc_table): moving boundary values are not part of the "
@@ -275,6 +301,7 @@ int dns_imex::check_attachments() const {
     if (fb.on) DNS_TRY(refuse_partitioned("observer feedback", kFbPartitioned));
     if (rec) DNS_TRY(refuse_partitioned("recorder", kRecPartitioned));
     if (stat) DNS_TRY(refuse_partitioned("statistics", kStPartitioned));
+    if (ens) DNS_TRY(refuse_partitioned("ensemble", kEnsPartitioned));
     if (qd) {
         DNS_TRY(refuse_partitioned("quadratics", kQdPartitioned));
         if (conv && conv->dbc_rows > 0)
@@ -1128,6 +1155,181 @@ int dns_imex_quadratics_grid(dns_imex *st, int32_t *grid) try {
 int dns_imex_clear_quadratics(dns_imex *st) try {
     DNS_TRY(quiesce(st));
     st->qd.reset();
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// ---- snapshot ensemble (ensemble.hpp) --------------------------------------
+
+int dns_imex_set_ensemble(dns_imex *st, int32_t nrows, const int32_t *slot,
+                          int32_t nslots, int32_t reset) try {
+    if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_saddle *h = st->sys;
+    DNS_TRY(st->refuse_partitioned("ensemble", kEnsPartitioned));
+    DNS_TRY(dns::check_slot_table(nrows, slot, nslots));
+    const size_t ldv = dns::ens_ldv(h->nv);
+    DNS_TRY(dns::check_ensemble_shape(nslots, h->nv, ldv));
+    DNS_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
+    // Built aside where it is not kept: a refusal (a failed allocation) leaves
+    // the ensemble that was there.
+    dns_imex::Ensemble none;
+    dns_imex::Ensemble &old = st->ens ? *st->ens : none;
+    const bool keep = !reset && old.E.p && old.nslots == nslots &&
+                      old.ldv == ldv;
+    dns::DevBuf<double> E;
+    dns::DevBuf<int> tab;
+    if (!keep) DNS_TRY(E.alloc((size_t)nslots * ldv));
+    DNS_TRY(keep_or_alloc(tab, old.slot, (size_t)nrows));
+    // (nothing is refused from here on)
+    if (!st->ens) {
+        st->ens.reset(new (std::nothrow) dns_imex::Ensemble());
+        if (!st->ens) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    }
+    dns_imex::Ensemble &e = *st->ens;
+    if (!keep) {
+        std::swap(e.E.p, E.p);
+        std::swap(e.E.n, E.n);
+        DNS_TRY(e.E.zero(s));
+    }
+    if (tab.p) {
+        std::swap(e.slot.p, tab.p);
+        std::swap(e.slot.n, tab.n);
+    }
+    DNS_TRY(e.slot.upload(slot, (size_t)nrows, s));
+    e.rows = nrows;
+    e.nslots = nslots;
+    e.ldv = ldv;
+    return st->rewind_tables();
+} DNS_CAPI_CATCH
+
+static int ens_need(dns_imex *st) {
+    return need(st, st && st->ens, "ensemble is", "dns_imex_set_ensemble");
+}
+
+int dns_imex_get_ensemble(dns_imex *st, int32_t first_slot, int32_t count,
+                          double *v) try {
+    DNS_TRY(ens_need(st));
+    const dns_imex::Ensemble &e = *st->ens;
+    return download_log_rows(st, v, e.E.p, first_slot, count,
+                             (size_t)st->sys->nv, e.nslots, "slots",
+                             "ensemble", e.ldv);
+} DNS_CAPI_CATCH
+
+int dns_imex_ensemble_gram(dns_imex *st, const dns_csr *w, int32_t m,
+                           double *g) try {
+    DNS_TRY(ens_need(st));
+    dns_imex::Ensemble &e = *st->ens;
+    const int nv = st->sys->nv;
+    if (!g) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (m < 1 || m > e.nslots)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "ensemble: m = %d outside 1..%d (nslots)", (int)m,
+                         e.nslots);
+    DNS_TRY(dns::check_ensemble_weights(w, nv));
+    hipStream_t s = st->sys->stream;
+    if (w) {
+        // the same weights as the device holds are not uploaded again
+        const dns::HostCsr &o = e.Wh;
+        const bool same =
+            e.W && o.nrows == w->nrows && o.nnz() == w->nnz &&
+            std::equal(o.rowptr.begin(), o.rowptr.end(), w->rowptr) &&
+            std::equal(o.colidx.begin(), o.colidx.end(), w->colidx) &&
+            (w->nnz == 0 || memcmp(o.vals.data(), w->vals,
+                                   (size_t)w->nnz * sizeof(double)) == 0);
+        if (!same) {
+            DNS_HIP(hipStreamSynchronize(s));
+            auto W = std::make_unique<dns::EnsWeights>();
+            DNS_TRY(W->upload(w, s));
+            e.W = std::move(W);
+            e.Wh = dns::host_copy(w);
+        }
+    }
+    if (e.gm.n < (size_t)m * m) DNS_TRY(e.gm.alloc((size_t)m * m));
+    DNS_TRY(dns::launch_ensemble_gram(e.E.p, m, nv, e.ldv,
+                                      w ? e.W.get() : nullptr, e.y, e.part,
+                                      e.gm.p, s));
+    DNS_TRY(e.gm.download(g, (size_t)m * m, s));
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_imex_ensemble_combine(dns_imex *st, int32_t m, int32_t r,
+                              const double *coef, double *out) try {
+    DNS_TRY(ens_need(st));
+    dns_imex::Ensemble &e = *st->ens;
+    const int nv = st->sys->nv;
+    if (!coef || !out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (m < 1 || m > e.nslots || r < 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "ensemble: m = %d outside 1..%d (nslots) or r = %d < "
+                         "1", (int)m, e.nslots, (int)r);
+    hipStream_t s = st->sys->stream;
+    const std::vector<double> packed = dns::ens_pack_coef(coef, r, m);
+    if (e.cf.n < packed.size()) DNS_TRY(e.cf.alloc(packed.size()));
+    if (e.out.n < (size_t)r * e.ldv) DNS_TRY(e.out.alloc((size_t)r * e.ldv));
+    DNS_TRY(e.cf.upload(packed.data(), packed.size(), s));
+    DNS_TRY(dns::launch_ensemble_combine(e.E.p, m, nv, e.ldv, e.cf.p, r,
+                                         e.out.p, e.ldv, s));
+    DNS_TRY(dns::download_rows(out, (const double *)e.out.p, (size_t)r,
+                               (size_t)nv, e.ldv, s));
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_imex_clear_ensemble(dns_imex *st) try {
+    DNS_TRY(quiesce(st));
+    st->ens.reset();
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// ---- the two dense operations alone (host pointers; tests) ------------------
+
+int dns_ensemble_gram(int device, int32_t m, int32_t nv, int32_t ld,
+                      const double *e, const dns_csr *w, double *g) try {
+    if (!e || !g) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(dns::check_ensemble_shape(m, nv, ld < 0 ? 0 : (size_t)ld));
+    DNS_TRY(dns::check_ensemble_weights(w, nv));
+    DNS_HIP(hipSetDevice(device));
+    ScopedStream ss;
+    DNS_HIP(hipStreamCreate(&ss.s));
+    dns::DevBuf<double> E, y, part, G;
+    dns::EnsWeights W;
+    DNS_TRY(E.alloc((size_t)m * ld));
+    DNS_TRY(G.alloc((size_t)m * m));
+    DNS_TRY(E.upload(e, (size_t)m * ld, ss.s));
+    if (w) DNS_TRY(W.upload(w, ss.s));
+    DNS_TRY(dns::launch_ensemble_gram(E.p, m, nv, (size_t)ld,
+                                      w ? &W : nullptr, y, part, G.p, ss.s));
+    DNS_TRY(G.download(g, (size_t)m * m, ss.s));
+    DNS_HIP(hipStreamSynchronize(ss.s));
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_ensemble_combine(int device, int32_t m, int32_t nv, int32_t ld,
+                         const double *e, int32_t r, const double *coef,
+                         double *out) try {
+    if (!e || !coef || !out)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(dns::check_ensemble_shape(m, nv, ld < 0 ? 0 : (size_t)ld));
+    if (r < 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "ensemble: r = %d < 1", (int)r);
+    DNS_HIP(hipSetDevice(device));
+    ScopedStream ss;
+    DNS_HIP(hipStreamCreate(&ss.s));
+    dns::DevBuf<double> E, C, O;
+    const size_t ldo = ((size_t)nv + 1) & ~(size_t)1;
+    DNS_TRY(E.alloc((size_t)m * ld));
+    const std::vector<double> packed = dns::ens_pack_coef(coef, r, m);
+    DNS_TRY(C.alloc(packed.size()));
+    DNS_TRY(O.alloc((size_t)r * ldo));
+    DNS_TRY(E.upload(e, (size_t)m * ld, ss.s));
+    DNS_TRY(C.upload(packed.data(), packed.size(), ss.s));
+    DNS_TRY(dns::launch_ensemble_combine(E.p, m, nv, (size_t)ld, C.p, r, O.p,
+                                         ldo, ss.s));
+    DNS_TRY(dns::download_rows(out, (const double *)O.p, (size_t)r, (size_t)nv,
+                               ldo, ss.s));
+    DNS_HIP(hipStreamSynchronize(ss.s));
     return DNS_OK;
 } DNS_CAPI_CATCH
 

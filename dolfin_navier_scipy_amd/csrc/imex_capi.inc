@@ -388,7 +388,8 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
                              "dns_imex_set_feedback_table / "
                              "dns_imex_set_recorder / "
                              "dns_imex_set_functionals / dns_imex_set_stats / "
-                             "dns_imex_set_quadratics)",
+                             "dns_imex_set_quadratics / "
+                             "dns_imex_set_ensemble)",
                              tab_pos);
     }
     if (conv) conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;

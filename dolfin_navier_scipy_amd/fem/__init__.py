@@ -12,3 +12,4 @@ from .functionals import (MomentumFunctionals, boundary_forces,
 from .statistics import FlowStatistics, component_pairs
 from .quadratics import (QuadraticFunctionals, kinetic_energy, dissipation,
                          kinetic_energy_rate, rate_norm, energy_budget)
+from .pod import SnapshotPOD

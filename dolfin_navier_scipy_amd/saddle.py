@@ -7,7 +7,8 @@ import scipy.sparse as sps
 from . import _capi as C
 
 __all__ = ['streaming_precond_defaults', 'choose_schur', 'SaddleSystem', 'ImexStepper', 'spmv', 'dot', 'axpy', 'gemv',
-           'dense_inverse', 'spmv_bench', 'spmv_pair', 'spmv_epilogue', 'solve_opts', 'precond_opts']
+           'dense_inverse', 'spmv_bench', 'spmv_pair', 'spmv_epilogue', 'solve_opts', 'precond_opts',
+           'ensemble_gram', 'ensemble_combine']
 
 _METHODS = {'gmres': C.DNS_METHOD_GMRES, 'bicgstab': C.DNS_METHOD_BICGSTAB}
 _SCHUR = {'dense': C.DNS_SCHUR_DENSE, 'jacobi': C.DNS_SCHUR_JACOBI, 'mg': 2}
@@ -833,6 +834,77 @@ class ImexStepper(object):
             C.dptr(out.reshape(-1) if out.size else np.zeros(1))))
         return out
 
+    # ---- snapshot ensemble (`dns_imex_set_ensemble`) -------------------------
+    def set_ensemble(self, slots, nslots=None, reset=False):
+        """the next `len(slots)` steps (`step` and `run` alike) copy the
+        velocity they leave into slot `slots[s]` of an ensemble of `nslots`
+        snapshots on the device (`-1`: the step is not kept; default `nslots`:
+        `max(slots) + 1`) -- the snapshots of a POD (`fem.SnapshotPOD`).  The
+        ensemble is kept across calls with the same `nslots` unless `reset`:
+        the slices of a time loop set their slot tables and go on filling;
+        `ensemble_gram` and `ensemble_combine` work on it behind the loop.
+        Resets the step counter like `set_rhs_table` (call it after that
+        one)."""
+        slots = np.asarray(slots)
+        if slots.ndim != 1 or slots.size < 1:
+            raise ValueError('`slots`: one entry per step, at least one')
+        if not np.issubdtype(slots.dtype, np.integer):
+            raise ValueError('`slots` must be integers')
+        if nslots is None:
+            nslots = max(int(slots.max()) + 1, 1)
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        C.check(self.lib.dns_imex_set_ensemble(
+            self._h, int(slots.size), slots.ctypes.data_as(C.c_int32_p),
+            int(nslots), int(bool(reset))))
+        self._ens_slots = int(nslots)
+
+    def clear_ensemble(self):
+        C.check(self.lib.dns_imex_clear_ensemble(self._h))
+        self._ens_slots = None
+
+    def _ens_m(self, m):
+        nslots = getattr(self, '_ens_slots', None)
+        if nslots is None:
+            raise ValueError('no ensemble is set (`set_ensemble`)')
+        return nslots if m is None else int(m)
+
+    def ensemble(self, first=0, count=None):
+        """slots `first .. first + count` of the ensemble (default: all),
+        `(count, NV)`"""
+        count = self._ens_m(None) - first if count is None else int(count)
+        out = np.empty((count, self.sys.NV))
+        C.check(self.lib.dns_imex_get_ensemble(
+            self._h, int(first), count,
+            C.dptr(out.reshape(-1) if out.size else np.zeros(1))))
+        return out
+
+    def ensemble_gram(self, W=None, m=None):
+        """`G = E W E^T` of the first `m` slots (default: all), `(m, m)`,
+        exactly symmetric; `W`: symmetric NV x NV (None: the identity).  Runs
+        on the device (fp64 matrix cores), `m^2` doubles come back."""
+        m = self._ens_m(m)
+        view = None if W is None else C.CsrView(W)
+        out = np.empty((m, m))
+        C.check(self.lib.dns_imex_ensemble_gram(
+            self._h, None if view is None else view.byref(), m,
+            C.dptr(out.reshape(-1))))
+        return out
+
+    def ensemble_combine(self, coef, m=None):
+        """`coef @ E` for the first `m` slots: `coef` `(r, m)`, returns `(r,
+        NV)` -- per entry `acc = fma(coef[q, s], E[s, k], acc)`, `s`
+        ascending"""
+        coef = np.ascontiguousarray(np.atleast_2d(coef), dtype=np.float64)
+        m = self._ens_m(coef.shape[1] if m is None else m)
+        if coef.shape[1] != m or coef.shape[0] < 1:
+            raise ValueError('`coef` must be r x m = r x {0}, it is {1}'
+                             .format(m, coef.shape))
+        out = np.empty((coef.shape[0], self.sys.NV))
+        C.check(self.lib.dns_imex_ensemble_combine(
+            self._h, m, coef.shape[0], C.dptr(coef.reshape(-1)),
+            C.dptr(out.reshape(-1))))
+        return out
+
     def get_state(self):
         v = np.empty(self.sys.NV)
         p = np.empty(self.sys.NP)
@@ -908,6 +980,39 @@ def spmv(A, x, y=None, alpha=1., beta=0., variant='vector', device=0):
     C.check(lib.dns_spmv(device, view.byref(), C.dptr(x), C.dptr(out),
                          float(alpha), float(beta),
                          _VARIANTS.get(variant, variant)))
+    return out
+
+
+def ensemble_gram(E, W=None, nv=None, device=0):
+    """`G = E[:, :nv] W E[:, :nv]^T` through `dns_ensemble_gram` (the kernels
+    of `ImexStepper.ensemble_gram` alone): `E` is `m x ld`, `ld` even, its
+    columns from `nv` on are never read"""
+    lib = C.load_library()
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    m, ld = E.shape
+    nv = ld if nv is None else int(nv)
+    view = None if W is None else C.CsrView(W)
+    out = np.empty((m, m))
+    C.check(lib.dns_ensemble_gram(device, m, nv, ld, C.dptr(E.reshape(-1)),
+                                  None if view is None else view.byref(),
+                                  C.dptr(out.reshape(-1))))
+    return out
+
+
+def ensemble_combine(E, coef, nv=None, device=0):
+    """`coef @ E[:, :nv]` through `dns_ensemble_combine`: `coef` is `r x m`"""
+    lib = C.load_library()
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    coef = np.ascontiguousarray(np.atleast_2d(coef), dtype=np.float64)
+    m, ld = E.shape
+    nv = ld if nv is None else int(nv)
+    if coef.shape[1] != m:
+        raise ValueError('`coef` must be r x {0}, it is {1}'.format(
+            m, coef.shape))
+    out = np.empty((coef.shape[0], nv))
+    C.check(lib.dns_ensemble_combine(device, m, nv, ld, C.dptr(E.reshape(-1)),
+                                     coef.shape[0], C.dptr(coef.reshape(-1)),
+                                     C.dptr(out.reshape(-1))))
     return out
 
 

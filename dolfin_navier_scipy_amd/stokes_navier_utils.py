@@ -357,7 +357,8 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
               vp_output=False, vp_out_fun=None, vp_output_dict=None,
               solver=None, device=0, bcs_time_only=False,
               applybcs_literal=True, record_on_device=False,
-              functionals=None, statistics=None, quadratics=None, **kw):
+              functionals=None, statistics=None, quadratics=None, pod=None,
+              **kw):
     """time-dependent Navier-Stokes on the device (reference snu:548-1600)
 
     Keyword names and meaning follow the reference.  `V`: object with the P2
@@ -426,7 +427,12 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     resident; `time_int_utils.LAST_RUN['quadratics']`, `['quadratics_t']`,
     `['quadratics_on']`, `['quadratics_names']` hold the rows, their times,
     where they came from and the forms' names.  Constant Dirichlet values
-    only (`ValueError` with controlled boundaries).
+    only (`ValueError` with controlled boundaries).  `pod` (explicit
+    schemes): a `fem.SnapshotPOD` of the condensed problem -- handed down to
+    the loop (`resident=dict(pod=...)`), which keeps the snapshots on the
+    device where it runs resident and forms Gram matrix and modes there;
+    `time_int_utils.LAST_RUN['pod']` and `['pod_on']` hold the result and
+    where it was formed.  The POD covers the inner velocity dofs.
     """
     if functionals is not None and not (treat_nonl_explicit
                                         and lin_vel_point is None):
@@ -437,6 +443,9 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     if quadratics is not None and not (treat_nonl_explicit
                                        and lin_vel_point is None):
         raise NotImplementedError('`quadratics`: explicit schemes only')
+    if pod is not None and not (treat_nonl_explicit
+                                and lin_vel_point is None):
+        raise NotImplementedError('`pod`: explicit schemes only')
     if dynamic_feedback and dyn_fb_disc == 'linear_implicit':
         raise NotImplementedError("`dyn_fb_disc='linear_implicit'` (the "
                                   'extended system of '
@@ -645,6 +654,8 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
             icd.setdefault('resident', {}).update(statistics=statistics)
         if quadratics is not None:
             icd.setdefault('resident', {}).update(quadratics=quadratics)
+        if pod is not None:
+            icd.setdefault('resident', {}).update(pod=pod)
         v_end, p_end, ffflag = timintsc(trange=trange, inip=inip, scalep=-1.,
                                         g_tdp=rhsp, bcs_ini=inicdbcvals,
                                         check_ff_maxv=check_ff_maxv, **icd)

@@ -436,6 +436,85 @@ class _QuadraticLog(_Attachment):
                     quadratics_on=self.where, quadratics_names=self.names)
 
 
+class _PodEnsemble(_Attachment):
+    """`resident=dict(pod=pod)` of `cnab` / `sbdftwo`, `pod` a
+    `fem.SnapshotPOD`: plans the kept steps of the whole loop once, arms the
+    stepper's snapshot ensemble per slice (or chunk) next to the tables -- a
+    slot table each, the ensemble stays and fills up --, and when the loop ends
+    forms the Gram matrix on the device, decomposes it on the host (`m x m`)
+    and has the device combine the modes and the mean flow: `m^2` and `(r + 1)
+    NV` doubles come back, the snapshots never do.  Where the loop takes one
+    step at a time the kept states are stored on the host and go through
+    `pod.evaluate`.  The snapshots are the inner velocity dofs: controlled
+    Dirichlet values are not in them"""
+
+    def __init__(self, stepper, pod, trange, keep_snapshots=False):
+        NV = stepper.sys.NV
+        if pod.NV != NV:
+            raise ValueError('`pod`: its weight matrix is {0} x {0}, the loop '
+                             'has NV = {1}'.format(pod.NV, NV))
+        self.stepper, self.pod = stepper, pod
+        kept, _ = pod.plan(trange)
+        self.times = np.array([float(trange[k]) for k in kept])
+        self.m = len(kept)
+        self.where, self.armed = None, False
+        self.keep_snapshots = keep_snapshots
+        self.host = {}
+        self.filled = 0             # kept steps that have run
+        self.res = None
+
+    def arm(self, times, tables):
+        self.stepper.set_ensemble(self.pod.slots_for(times), nslots=self.m,
+                                  reset=not self.armed)
+        self.armed = True
+
+    def collect(self, times):
+        self.filled += int(np.sum(self.pod.slots_for(times) >= 0))
+
+    def host_row(self, step):
+        slot = int(self.pod.slots_for([step.time])[0])
+        if slot >= 0:
+            self.host[slot] = np.array(step.v, dtype=np.float64).reshape(-1)
+            self.filled += 1
+
+    def finish(self, drm):
+        pod, stepper = self.pod, self.stepper
+        if self.filled < self.m:
+            # the loop broke off (blow-up guard): slots are unfilled or hold
+            # what blew up -- no decomposition, the caller gets its `ffflag`
+            self.res = None
+            self.where = self.where or ('device' if self.armed else 'host')
+            if self.armed:
+                stepper.clear_ensemble()
+                self.armed = False
+            return
+        if self.armed and not self.host:
+            gram = stepper.ensemble_gram(pod.W)
+            dec = pod.decompose(gram)
+            modes, mean = pod.split(dec, stepper.ensemble_combine(dec['coef']))
+            self.res = dict(gram=gram, sigma=dec['sigma'], modes=modes,
+                            mean=mean, coeffs=dec['coeffs'], coef=dec['coef'])
+            if self.keep_snapshots:
+                self.res['snapshots'] = stepper.ensemble()
+            self.where = 'device'
+        else:
+            S = stepper.ensemble() if self.armed else \
+                np.zeros((self.m, pod.NV))
+            for slot, v in self.host.items():
+                S[slot] = v
+            self.res = pod.evaluate(S)
+            if self.keep_snapshots:
+                self.res['snapshots'] = S
+            self.where = 'host'
+        self.res['times'] = self.times
+        if self.armed:
+            stepper.clear_ensemble()
+            self.armed = False
+
+    def report(self):
+        return dict(pod=self.res, pod_on=self.where)
+
+
 class _StatisticsSums(_Attachment):
     """`resident=dict(statistics=fs)` of `cnab` / `sbdftwo`, `fs` a
     `fem.FlowStatistics`: arms the stepper's statistics per slice (or chunk)
@@ -552,8 +631,9 @@ class _ImexLoop(object):
             if (self.on_device and rsd.get('record', False)) else None
         self.attachments = []
 
-    def attach(self, lti, fb_dev, tstart):
-        """the functionals, the statistics, the quadratics and the feedback -- a
+    def attach(self, lti, fb_dev, tstart, trange=None):
+        """the functionals, the statistics, the quadratics, the POD ensemble
+        (it plans over the loop's `trange`) and the feedback -- a
         `LinearFeedback` `lti` that can run resident (`fb_dev`) as the
         observer on the device -- in the order they are armed in (inside the
         loop's `try`: they may refuse)"""
@@ -570,6 +650,7 @@ class _ImexLoop(object):
                 dt=self.dt, tstart=tstart))
         fs = self.rsd.get('statistics', None)
         qf = self.rsd.get('quadratics', None)
+        pod = self.rsd.get('pod', None)
         if qf is not None and self.moving:
             raise ValueError(
                 '`quadratics` with moving Dirichlet values: the forms carry '
@@ -578,7 +659,10 @@ class _ImexLoop(object):
             flog, None if fs is None else _StatisticsSums(self.stepper, fs),
             None if qf is None else _QuadraticLog(
                 self.stepper, qf, self.dt,
-                max_grid=self.rsd.get('quadratics_max_grid', None)))
+                max_grid=self.rsd.get('quadratics_max_grid', None)),
+            None if pod is None else _PodEnsemble(
+                self.stepper, pod, trange,
+                keep_snapshots=self.rsd.get('pod_snapshots', False)))
             if a is not None]
 
     def _terms_at(self, ctime, v_c=None, p_c=None):
@@ -880,7 +964,7 @@ def _imex_loop(scheme, trange, inivel, inip, bcs_ini, M, A, J, f_vdp, f_tdp,
         appndbcs=appndbcs, f_tdp=f_tdp, g_tdp=g_tdp, f_vdp=f_vdp,
         dynamic_rhs=dynamic_rhs, savevp=savevp)
     try:
-        loop.attach(lti, fb_dev, trange[1])
+        loop.attach(lti, fb_dev, trange[1], trange=trange)
         ffflag = loop.march(trange[1], listofts, ntimeslices, check_ff_maxv,
                             verbose)
     finally:
@@ -966,6 +1050,28 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                         empty.  `quadratics_max_grid` caps the workgroups of
                         the kernel and with them the log (`nsteps x G x nQ`
                         doubles per slice)
+      `pod`             a `fem.SnapshotPOD` (weight matrix, which times are
+                        kept, truncation): the velocities of the kept AB2 /
+                        BDF2 steps (`trange[2:]`; the Heun start is not a
+                        snapshot) are copied into an ensemble on the device
+                        that lasts over the slices
+                        (`ImexStepper.set_ensemble`: one copy node per step);
+                        when the loop ends the Gram matrix `S W S^T` is formed
+                        on the device (fp64 matrix cores), decomposed on the
+                        host (`m x m`) and the modes and the mean flow are
+                        combined on the device: `m^2 + (r + 1) NV` doubles
+                        come back.  `LAST_RUN['pod']` is a dict `gram`,
+                        `sigma`, `modes` (r x NV), `mean`, `coeffs` (r x m),
+                        `coef`, `times`; `['pod_on']` says 'device' or 'host'
+                        (`pod.evaluate` of the states stored per step); a
+                        loop that breaks off on the blow-up guard leaves
+                        `['pod']` None.  The
+                        snapshots are the inner dofs `v`: with controlled
+                        Dirichlet values the boundary values are not part of
+                        the POD.  `ValueError` when the ensemble would exceed
+                        `pod.max_bytes`.  `pod_snapshots=True` downloads the
+                        snapshots as well (`['pod']['snapshots']`, m x NV:
+                        diagnostics)
     `LAST_RUN['record']` says 'device' or 'host', `LAST_RUN['run_calls']`
     counts the `stepper.run` calls of the loop.
     The per-step data the callbacks return (`f_tdp`, `g_tdp`, `applybcs`) are

@@ -629,6 +629,39 @@ int dns_imex_get_quadratics(dns_imex *st, int32_t first, int32_t count,
 int dns_imex_quadratics_grid(dns_imex *st, int32_t *grid);
 /* quadratics off (the step is what it was before) */
 int dns_imex_clear_quadratics(dns_imex *st);
+/* Snapshot ensemble for a proper orthogonal decomposition (method of
+ * snapshots) on the device: the stepper owns a buffer E of nslots slots, NV
+ * doubles each (ldv = NV rounded up to 64 apart; velocities only), and the next
+ * nrows steps (dns_imex_step and dns_imex_run alike) copy the velocity they
+ * leave, v_r of row r -- what dns_imex_get_state returns after the (r+1)-th
+ * step after this call, bit for bit --, into slot slot[r] (-1: the step is not
+ * kept; slots in [0, nslots)).  One kernel per step; a row copied twice, or by
+ * a batch dns_imex_run restores and repeats, has the same bits.  E is kept
+ * across calls with the same nslots and reset == 0 (the slices of a time loop
+ * set a slot table each and go on filling), reallocated and zeroed otherwise.
+ * Every check comes first: a refused call leaves the ensemble that was there.
+ * Resets the step counter like dns_imex_set_rhs_table.  Not on a
+ * row-partitioned stepper.  Works with and without the other attachments. */
+int dns_imex_set_ensemble(dns_imex *st, int32_t nrows, const int32_t *slot,
+                          int32_t nslots, int32_t reset);
+/* slots [first_slot, first_slot + count): v (count x NV, unpadded) */
+int dns_imex_get_ensemble(dns_imex *st, int32_t first_slot, int32_t count,
+                          double *v);
+/* g (m x m, host) = E W E^T of the first m slots; w: symmetric NV x NV host
+ * CSR (the mass matrix; the same matrix handed over again is not uploaded
+ * again), NULL: the identity.  Plain launches behind the loop: Y = E W for 16
+ * snapshots at a time, 16 x 16 tiles on the fp64 matrix cores over chunks of
+ * 1024 entries, their partials added in chunk order.  No atomics: the same
+ * bits in every run, on every device; g is exactly symmetric.  Extra device
+ * memory: 16 x ldv + ceil(m / 16) x ceil(NV / 1024) x 256 doubles. */
+int dns_imex_ensemble_gram(dns_imex *st, const dns_csr *w, int32_t m,
+                           double *g);
+/* out (r x NV, host) = coef (r x m, host) times the first m slots; per entry
+ * acc = fma(coef[q, s], E[s, k], acc) for s = 0 .. m - 1: a fixed order */
+int dns_imex_ensemble_combine(dns_imex *st, int32_t m, int32_t r,
+                              const double *coef, double *out);
+/* ensemble off and freed (the step is what it was before) */
+int dns_imex_clear_ensemble(dns_imex *st);
 /* ||v||_2 of the current velocity (blow-up guard, tiu:94-103) */
 int dns_imex_vnorm(dns_imex *st, double *out);
 
@@ -682,6 +715,16 @@ int dns_gemv(int device, int32_t n, const double *a_rowmajor, const double *x,
              double *y, double alpha);
 /* dense in-place inverse by the device Gauss-Jordan used for the Schur block */
 int dns_dense_inverse(int device, int32_t n, double *a_rowmajor);
+
+/* the two dense operations of dns_imex_ensemble_gram / _combine alone, through
+ * the same launchers: e is m x ld on the host (ld even, >= nv; entries at and
+ * behind nv of a row are never read), w NV x NV or NULL, g m x m, coef r x m,
+ * out r x nv */
+int dns_ensemble_gram(int device, int32_t m, int32_t nv, int32_t ld,
+                      const double *e, const dns_csr *w, double *g);
+int dns_ensemble_combine(int device, int32_t m, int32_t nv, int32_t ld,
+                         const double *e, int32_t r, const double *coef,
+                         double *out);
 
 /* repeat y = A x `reps` times on resident data; reports the average kernel
  * time (HIP events on the launch stream) -- the roofline measurement */
