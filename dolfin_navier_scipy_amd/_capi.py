@@ -101,6 +101,14 @@ class dns_spmv_epi(ct.Structure):
                 ('pad', ct.c_int32)]
 
 
+class dns_trap_probe(ct.Structure):
+    _fields_ = [(k, c_double_p) for k in
+                ('nvals', 'fvals', 'kfvals', 'rhsbc', 'fvn', 'b', 'x0', 'r',
+                 'partR', 'partB')] + \
+               [('parts_cap', ct.c_int32), ('nparts', ct.c_int32),
+                ('fused', ct.c_int32), ('pad', ct.c_int32)]
+
+
 # every symbol include/dns_amd.h declares: name -> (restype, argtypes)
 _VP = ct.c_void_p
 ALLREDUCE_CB = ct.CFUNCTYPE(ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_int32)
@@ -329,6 +337,9 @@ SIGNATURES = {
                                  ct.POINTER(ct.c_int32)]),
     'dns_trap_checkpoint': (ct.c_int, [_VP]),
     'dns_trap_restore': (ct.c_int, [_VP, ct.c_int32]),
+    'dns_trap_assembly_probe': (ct.c_int, [_VP, ct.c_double, ct.c_int32,
+                                           ct.c_int32, ct.c_int32, c_double_p,
+                                           ct.POINTER(dns_trap_probe)]),
     'dns_hbm_probe': (ct.c_int, [ct.c_int, ct.c_int64, ct.c_int32, ct.c_int32,
                                  c_double_p]),
     'dns_imex_set_rhs_table': (ct.c_int, [_VP, ct.c_int32, c_double_p,

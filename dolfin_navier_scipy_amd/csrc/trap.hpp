@@ -222,6 +222,17 @@ struct dns_trap : dns::Ring {
     } part;
     int ensure_partition();
     int gather_slot(int which, int slot);  // collective: whole slot everywhere
+    // what the front part of a step (everything it enqueues before its
+    // solve) leaves for the rest of it
+    struct Front {
+        double *x;               // work buffer: the warm start
+        const double *vlin;
+        bool pon, fuse_r;
+        int rv0, rv1, ex, gb_rows;
+    };
+    int enqueue_front(double dt, int lin_which, int lin_slot, int newton,
+                      int extrapolate_x0, const dns_solve_opts &o,
+                      const Feedback *fb, bool x_given, Front *out);
     int step_impl(double dt, int lin_which, int lin_slot, int out_slot,
                   int newton, int extrapolate_x0, const dns_solve_opts *opts,
                   dns_solve_stats *stats, const Feedback *fb);

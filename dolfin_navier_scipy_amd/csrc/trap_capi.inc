@@ -422,27 +422,17 @@ int dns_trap::export_fence(int which) {
     return DNS_OK;
 }
 
-int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
-                        int newton, int extrapolate_x0,
-                        const dns_solve_opts *opts, dns_solve_stats *stats,
-                        const Feedback *fb) {
+// The front part of a step: everything it enqueues before its solve -- the
+// warm start, the element launch (k_conv_step_cells) and the gather launch
+// (k_conv_mat_bc_gather: N, F into the system, the right-hand side and, fused,
+// the start residual with its norms).  `x_given`: the work buffer holds the
+// warm start already (dns_trap_assembly_probe: the caller's).
+int dns_trap::enqueue_front(double dt, int lin_which, int lin_slot, int newton,
+                            int extrapolate_x0, const dns_solve_opts &o,
+                            const Feedback *fb, bool x_given, Front *out) {
     dns_trap *t = this;
-    if (!(dt > 0.0) || lin_which < 0 || lin_which > 1 || lin_slot < 0 ||
-        lin_slot >= t->nslots || out_slot >= t->nslots)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     dns_saddle *h = t->sys;
     dns_conv *cv = t->conv;
-    if (!h->precond_ready)
-        return dns::fail(DNS_ERR_NOT_READY, "preconditioner not set up");
-    DNS_HIP(hipSetDevice(h->device));
-    dns_solve_opts o;
-    if (opts)
-        o = *opts;
-    else
-        dns_default_solve_opts(&o);
-    dns_solve_stats local;
-    dns_solve_stats *st = stats ? stats : &local;
-    memset(st, 0, sizeof(*st));
     hipStream_t s = h->stream;
     const int nv = h->nv, np = h->np, n = h->n;
     const int nw = newton ? 1 : 0;
@@ -476,7 +466,7 @@ int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
                          t->pre_sig == dns::extrap_sig(t->nsol, extrapolate_x0) &&
                          same_dt && std::fabs(dt - t->pre_dt) <= 1e-12 * dt;
     t->pre_ok = false;
-    if (!use_pre) {
+    if (!use_pre && !x_given) {
         // (else the tail of the step before has left the warm start in `x`)
         double e[5];
         const int order = same_dt ? dns::extrap_coeffs(t->nsol, ex, e) : 0;
@@ -548,6 +538,42 @@ int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
         kdirect ? h->K.vals.p : (double *)nullptr, nw != 0,
         pon ? &rr : (const dns_conv::RowRange *)nullptr, &trhs));
     DNS_TRY(h->device_values_changed(kdirect, pon));
+    *out = Front{x, vlin, pon, fuse_r, rv0, rv1, ex, gb_rows};
+    return DNS_OK;
+}
+
+int dns_trap::step_impl(double dt, int lin_which, int lin_slot, int out_slot,
+                        int newton, int extrapolate_x0,
+                        const dns_solve_opts *opts, dns_solve_stats *stats,
+                        const Feedback *fb) {
+    dns_trap *t = this;
+    if (!(dt > 0.0) || lin_which < 0 || lin_which > 1 || lin_slot < 0 ||
+        lin_slot >= t->nslots || out_slot >= t->nslots)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
+    dns_saddle *h = t->sys;
+    if (!h->precond_ready)
+        return dns::fail(DNS_ERR_NOT_READY, "preconditioner not set up");
+    DNS_HIP(hipSetDevice(h->device));
+    dns_solve_opts o;
+    if (opts)
+        o = *opts;
+    else
+        dns_default_solve_opts(&o);
+    dns_solve_stats local;
+    dns_solve_stats *st = stats ? stats : &local;
+    memset(st, 0, sizeof(*st));
+    hipStream_t s = h->stream;
+    const int nv = h->nv, np = h->np, n = h->n;
+    const double hdt = 0.5 * dt;
+    // warm start, element launch, gather launch: N_n, F into the system, the
+    // right-hand side and -- fused -- the start residual
+    Front fr;
+    DNS_TRY(t->enqueue_front(dt, lin_which, lin_slot, newton, extrapolate_x0, o,
+                             fb, false, &fr));
+    double *x = fr.x;
+    const double *vlin = fr.vlin;
+    const bool pon = fr.pon, fuse_r = fr.fuse_r;
+    const int rv0 = fr.rv0, rv1 = fr.rv1, ex = fr.ex, gb_rows = fr.gb_rows;
     if (t->have_mbc_tab) {
         // rhs += mbcs_n - mbcs_c (snu:1044-1045)
         hipLaunchKernelGGL(dns::k_axpby, dns::grid_for_elems(nv), dns::kBlock,
@@ -880,6 +906,71 @@ int dns_trap_update_norm(dns_trap *t, double *out) try {
         DNS_TRY(h->allreduce_host(&v, 1));
         *out = v;
     }
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// TEST ONLY: the front part of a step (dns_trap::enqueue_front, the member
+// function step_impl calls) and a copy out of what it has left
+int dns_trap_assembly_probe(dns_trap *t, double dt, int32_t lin_which,
+                            int32_t lin_slot, int32_t newton,
+                            const double *x0_in, dns_trap_probe *out) try {
+    if (!t || !out || !(dt > 0.0) || lin_which < 0 || lin_which > 1 ||
+        lin_slot < 0 || lin_slot >= t->nslots || out->parts_cap < 0)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
+    dns_saddle *h = t->sys;
+    if (h->dist() || h->dist_sliced || h->rank_local)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "the assembly probe takes an un-partitioned handle");
+    if (t->pipeline_c > 0 || t->pend.on || t->upd_slot > 0)
+        return dns::fail(DNS_ERR_NOT_READY,
+                         "the assembly probe: a pipelined batch or an "
+                         "update-norm job is pending");
+    DNS_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t nv = (size_t)h->nv, n = (size_t)h->n, nnz = (size_t)h->F.nnz;
+    dns_solve_opts o;
+    dns_default_solve_opts(&o);
+    if (x0_in) DNS_TRY(dns::upload_to(t->xs[t->work].p, x0_in, n, s));
+    dns_trap::Front fr;
+    DNS_TRY(t->enqueue_front(dt, lin_which, lin_slot, newton, 4, o, nullptr,
+                             x0_in != nullptr, &fr));
+    DNS_HIP(hipStreamSynchronize(s));
+    out->fused = fr.fuse_r ? 1 : 0;
+    out->nparts = fr.fuse_r ? fr.gb_rows : 0;
+    if (out->nvals) DNS_TRY(t->nn_vals.download(out->nvals, nnz, s));
+    if (out->fvals) DNS_TRY(dns::download_from(out->fvals, h->F.vals.p, nnz, s));
+    if (out->kfvals) {
+        if (!t->kpos.p)
+            return dns::fail(DNS_ERR_NOT_READY, "no positions of F in K");
+        std::vector<int> kp(nnz);
+        std::vector<double> kv((size_t)h->K.nnz);
+        DNS_TRY(t->kpos.download(kp.data(), nnz, s));
+        DNS_TRY(dns::download_from(kv.data(), h->K.vals.p, kv.size(), s));
+        DNS_HIP(hipStreamSynchronize(s));
+        for (size_t z = 0; z < nnz; ++z) {
+            if (kp[z] < 0 || (size_t)kp[z] >= kv.size())
+                return dns::fail(DNS_ERR_HOST, "position %d outside K", kp[z]);
+            out->kfvals[z] = kv[(size_t)kp[z]];
+        }
+    }
+    if (out->rhsbc) DNS_TRY(t->rhsbc.download(out->rhsbc, nv, s));
+    if (out->fvn) DNS_TRY(t->fvn_n.download(out->fvn, nv, s));
+    if (out->b) DNS_TRY(t->b.download(out->b, n, s));
+    if (out->x0) DNS_TRY(dns::download_from(out->x0, fr.x, n, s));
+    if (fr.fuse_r) {
+        if (fr.gb_rows > out->parts_cap && (out->partR || out->partB))
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "%d partials, room for %d", fr.gb_rows,
+                             out->parts_cap);
+        if (out->r) DNS_TRY(dns::download_from(out->r, h->r.p, n, s));
+        if (out->partR)
+            DNS_TRY(dns::download_from(out->partR, h->partR.p,
+                                       (size_t)fr.gb_rows, s));
+        if (out->partB)
+            DNS_TRY(dns::download_from(out->partB, h->partB.p,
+                                       (size_t)fr.gb_rows, s));
+    }
+    DNS_HIP(hipStreamSynchronize(s));
     return DNS_OK;
 } DNS_CAPI_CATCH
 

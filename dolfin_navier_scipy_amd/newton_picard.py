@@ -235,7 +235,9 @@ class TrapezoidalStepper(object):
         kept).  `oversolve`: the solves of a pipelined batch run the columns
         of their cycle down to this fraction of the tolerance instead of
         stopping at it (`set_oversolve`; 0: stop at the tolerance, with a
-        slack column per cycle as until round 4)"""
+        slack column per cycle as until round 4).  `precond=False`: no
+        preconditioner is set up -- `assembly_probe` works, `step` refuses
+        (tests of the assembly with matrices no set-up would accept)"""
         self.lib = C.load_library()
         self._refresh = _RefreshPolicy(refresh_iters)
         self.batch = int(batch)
@@ -261,6 +263,11 @@ class TrapezoidalStepper(object):
         self.system = SaddleSystem(F0, self.J, JT=JT, device=device)
         if comm is not None:
             self.system.set_comm(comm)
+        if precond is False:
+            # (no preconditioner: `assembly_probe` only, `step` refuses)
+            self._pkw = None
+            self._finish_create(conv, nslots, oversolve)
+            return
         pkw = dict(cheb_degree=6, schur='auto', fhat='auto', fp32_store=True,
                    drop_tol=3e-3)
         if comm is not None:
@@ -272,6 +279,9 @@ class TrapezoidalStepper(object):
                                                           None))
         self._pkw = dict(pkw)
         self.system.setup_precond(**pkw)
+        self._finish_create(conv, nslots, oversolve)
+
+    def _finish_create(self, conv, nslots, oversolve):
         conv.bind_pattern(self.pattern)
         self.nslots = int(nslots)
         self._h = ct.c_void_p()
@@ -399,6 +409,34 @@ class TrapezoidalStepper(object):
             raise C.NotConverged(st.status, 'time step solve failed: '
                                  '{0}'.format(self.last_stats))
         return self.last_stats
+
+    def assembly_probe(self, dt, lin_which, lin_slot, newton, x0=None):
+        """TEST ONLY (`dns_trap_assembly_probe`): the launches a `step`
+        enqueues before its solve, then what they have left, as a dict --
+        `nvals`, `fvals`, `kfvals` (F as it sits in K), `rhsbc`, `fvn`, `b`,
+        `x0` (the warm start used; `x0 (NV + NP)` given: that one), `fused`
+        and, fused, `r`, `partR`, `partB` (one entry per workgroup of the row
+        part).  `start` again before the stepper steps."""
+        n, nnz = self.NV + self.NP, self.mvals.size
+        cap = 2048 + 256
+        res = dict(nvals=np.empty(nnz), fvals=np.empty(nnz),
+                   kfvals=np.empty(nnz), rhsbc=np.empty(self.NV),
+                   fvn=np.empty(self.NV), b=np.empty(n), x0=np.empty(n),
+                   r=np.full(n, np.nan), partR=np.full(cap, np.nan),
+                   partB=np.full(cap, np.nan))
+        pr = C.dns_trap_probe(parts_cap=cap)
+        for k, arr in res.items():
+            setattr(pr, k, C.dptr(arr))
+        xin = None if x0 is None else C.as_f64(x0, n)
+        C.check(self.lib.dns_trap_assembly_probe(
+            self._h, float(dt), int(lin_which), int(lin_slot),
+            int(bool(newton)), C.dptr(xin), ct.byref(pr)))
+        res['fused'] = bool(pr.fused)
+        res['partR'] = res['partR'][:pr.nparts]
+        res['partB'] = res['partB'][:pr.nparts]
+        if not pr.fused:
+            res['r'] = None
+        return res
 
     def run(self, dt, lin_which, slot0, count, newton, opts=None,
             extrapolate=4):

@@ -977,6 +977,31 @@ int dns_trap_poll_ext(dns_trap *t, int32_t *out6, double *out2);
 int dns_trap_checkpoint(dns_trap *t);
 int dns_trap_restore(dns_trap *t, int32_t newton);
 
+/* TEST ONLY.  The launches a `dns_trap_step` (default options) enqueues BEFORE
+ * its solve -- warm start, element launch, gather launch, by the same member
+ * function the step calls -- then a synchronise and a copy out: the assembly
+ * pair of a trapezoidal step reachable in isolation.  Every pointer of `out`
+ * may be NULL.  x0_in != NULL: these NV + NP values are the warm start instead
+ * of the extrapolated one.  Needs no preconditioner.  DNS_ERR_NOT_READY with a
+ * pipelined batch or a pending update-norm job, DNS_ERR_BAD_ARGUMENT on a
+ * row-partitioned handle.  The system matrix is re-valued and no solution
+ * follows: call dns_trap_start before the stepper steps again. */
+typedef struct dns_trap_probe {
+    double *nvals, *fvals;   /* N(v_lin), F = M + dt/2 (A + N): nnz of pattern */
+    double *kfvals;          /* the values of F as they sit in K (nnz)         */
+    double *rhsbc, *fvn;     /* NV each                                        */
+    double *b, *x0;          /* NV + NP each: right-hand side, warm start used */
+    double *r;               /* NV + NP, written if *fused                     */
+    double *partR, *partB;   /* parts_cap each: raw partials, if *fused        */
+    int32_t parts_cap;
+    int32_t nparts;          /* out: partials the launch wrote (0: not fused)  */
+    int32_t fused;           /* out: the start residual came from the gather   */
+    int32_t pad;
+} dns_trap_probe;
+int dns_trap_assembly_probe(dns_trap *t, double dt, int32_t lin_which,
+                            int32_t lin_slot, int32_t newton,
+                            const double *x0_in, dns_trap_probe *out);
+
 /* ---- resident helpers of the caller side of the path -----------------------
  * A CSR matrix kept in HBM for repeated products with host vectors: what the
  * closures of `solve_nse` do per step with SciPy -- `applybcs` (snu:1111-1115:

@@ -100,6 +100,18 @@ def test_null_and_bad_arguments_fail_cleanly(capi):
         assert epi(**bad) == capi.DNS_ERR_BAD_ARGUMENT, bad
 
 
+def test_assembly_probe_checks_its_arguments_on_the_host(capi):
+    import ctypes as ct
+    lib = capi.load_library()
+    pr = capi.dns_trap_probe()
+    assert ct.sizeof(pr) == 96
+    assert lib.dns_trap_assembly_probe(None, 1e-3, 0, 0, 0, None,
+                                       ct.byref(pr)) \
+        == capi.DNS_ERR_BAD_ARGUMENT
+    assert lib.dns_trap_assembly_probe(None, 1e-3, 0, 0, 0, None, None) \
+        == capi.DNS_ERR_BAD_ARGUMENT
+
+
 def test_no_device_is_loud(capi):
     """without a GPU the product path must raise, never fall back"""
     if capi.device_count() > 0:
