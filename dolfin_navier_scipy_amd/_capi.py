@@ -265,6 +265,13 @@ SIGNATURES = {
     'dns_ensemble_combine': (ct.c_int, [ct.c_int, ct.c_int32, ct.c_int32,
                                         ct.c_int32, c_double_p, ct.c_int32,
                                         c_double_p, c_double_p]),
+    'dns_ensemble_project': (ct.c_int, [ct.c_int, ct.c_int32, ct.c_int32,
+                                        ct.c_int32, ct.c_int32, c_double_p,
+                                        c_double_p, ct.POINTER(dns_csr),
+                                        c_double_p]),
+    'dns_conv_project_tensor': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
+                                           ct.c_int32, c_double_p, c_double_p,
+                                           c_double_p]),
     'dns_imex_run_info': (ct.c_int, [_VP, c_int32_p, c_int32_p, c_int32_p,
                                      c_int32_p]),
     'dns_imex_step_counters': (ct.c_int, [_VP, ct.POINTER(ct.c_int64)]),

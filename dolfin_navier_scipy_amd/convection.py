@@ -13,9 +13,41 @@ from . import _capi as C
 
 __all__ = ['ConvectionP2']
 
+ROM_MAX_BASIS = 33          # kRomMaxBasis of csrc/galerkin_host.hpp
+
 
 def _i32(arr):
     return np.ascontiguousarray(arr, dtype=np.int32)
+
+
+def check_basis(nv, ndbc, basis, dbc_rows=None, ntest=None):
+    """the shapes `project_tensor` takes, refused by name on the host:
+    returns `(basis (nb, ld) padded to an even `ld`, dbc_rows (nb, ndbc) or
+    None, ntest)`"""
+    B = np.asarray(basis, dtype=np.float64)
+    if B.ndim != 2 or B.shape[1] < nv or B.shape[1] > nv + 64 \
+            or (B.shape[1] != nv and B.shape[1] % 2):
+        raise ValueError(
+            '`basis` must be nb x {0} (the inner dofs; or padded to an '
+            'even width), it is {1}'.format(nv, B.shape))
+    nb = B.shape[0]
+    if not 1 <= nb <= ROM_MAX_BASIS:
+        raise ValueError(
+            '`basis` has nb = {0} rows, the tensor kernel takes 1..{1} '
+            '(32 modes and a mean flow)'.format(nb, ROM_MAX_BASIS))
+    nt = nb if ntest is None else int(ntest)
+    if not 1 <= nt <= nb:
+        raise ValueError('`ntest` = {0} outside 1..nb = {1}'.format(nt, nb))
+    D = None
+    if dbc_rows is not None:
+        D = np.ascontiguousarray(dbc_rows, dtype=np.float64)
+        if D.shape != (nb, ndbc):
+            raise ValueError(
+                '`dbc_rows` must be nb x ndbc = {0} x {1}, it is {2}'
+                .format(nb, ndbc, D.shape))
+    if B.shape[1] % 2:
+        B = np.hstack([B, np.zeros((nb, 1))])
+    return np.ascontiguousarray(B), D, nt
 
 
 class ConvectionP2(object):
@@ -29,10 +61,17 @@ class ConvectionP2(object):
         ar = C.as_f64(area)
         self.ncells = ar.size
         self._cell_vdofs = cv.reshape((-1, 12))
+        # (the element data stays here as well: `fem.GalerkinROM`'s host model
+        # works from the same object)
+        self.glam, self.area = gl.reshape((-1, 3, 2)), ar
+        self._dbcinds = None
+        self.dbc_table_rows = 0     # > 0: a time-varying Dirichlet table is set
         self._vdim = int(vdim)
         inv, dbi = _i32(invinds), _i32(dbcinds)
         self._invinds = inv
         dbv = C.as_f64(dbcvals, size=dbi.size)
+        self._dbcinds = dbi
+        self.dbcvals = np.array(dbv)    # the constant set (None: a table)
         self.ndbc = int(dbi.size)
         self.nv = inv.size
         self._h = ct.c_void_p()
@@ -52,6 +91,8 @@ class ConvectionP2(object):
         """one constant set of Dirichlet values (drops a value table)"""
         dbv = C.as_f64(dbcvals, size=self.ndbc)
         C.check(self.lib.dns_conv_set_dbcvals(self._h, C.dptr(dbv)))
+        self.dbc_table_rows = 0
+        self.dbcvals = np.array(dbv)
 
     def set_dbc_table(self, table):
         """`(nrows, ndbc)` Dirichlet values per step (IMEX stepper: row s for
@@ -63,6 +104,8 @@ class ConvectionP2(object):
         flat = C.as_f64(tab) if tab.size else np.zeros(1)
         C.check(self.lib.dns_conv_set_dbc_table(self._h, int(nrows),
                                                 C.dptr(flat)))
+        self.dbc_table_rows = int(nrows)
+        self.dbcvals = None
 
     def set_dbc_row(self, row):
         C.check(self.lib.dns_conv_set_dbc_row(self._h, int(row)))
@@ -73,6 +116,26 @@ class ConvectionP2(object):
         C.check(self.lib.dns_conv_apply(self._h, C.dptr(v), float(scale),
                                         C.dptr(out)))
         return out.reshape((-1, 1))
+
+    # -- the convection tensor of a Galerkin projection ----------------------
+    def check_basis(self, basis, dbc_rows=None, ntest=None):
+        return check_basis(self.nv, self.ndbc, basis, dbc_rows, ntest)
+
+    def project_tensor(self, basis, dbc_rows=None, ntest=None):
+        """`T[i, j, k] = int phi_i . (u_j . grad) u_k` (`ntest x nb x nb`; `j`
+        convects, `k` is convected) on the device, `dns_conv_project_tensor`:
+        `u_b` is row `b` of `basis` on the inner dofs and row `b` of `dbc_rows`
+        (None: zeros) on the Dirichlet dofs, the test functions `phi_i` are the
+        rows `i < ntest` on the inner dofs and vanish on the Dirichlet dofs.
+        The operator's own Dirichlet values play no part"""
+        B, D, nt = self.check_basis(basis, dbc_rows, ntest)
+        nb, ld = B.shape
+        out = np.empty((nt, nb, nb))
+        C.check(self.lib.dns_conv_project_tensor(
+            self._h, nb, nt, ld, C.dptr(B.reshape(-1)),
+            None if (D is None or D.size == 0) else C.dptr(D.reshape(-1)),
+            C.dptr(out.reshape(-1))))
+        return out
 
     # -- linearised convection matrices (Newton/Picard sweeps) ---------------
     def connectivity(self):

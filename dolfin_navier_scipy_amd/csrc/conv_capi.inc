@@ -194,6 +194,31 @@ int dns_conv_apply(dns_conv *cv, const double *v_inner, double scale,
     return DNS_OK;
 } DNS_CAPI_CATCH
 
+int dns_conv_project_tensor(dns_conv *cv, int32_t nb, int32_t nt, int32_t ld,
+                            const double *basis, const double *dbc_rows,
+                            double *out) try {
+    if (!cv || !basis || !out)
+        return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    const int nlive = dns::rom_live_cells(cv->cmap_host.data(), cv->ncells);
+    DNS_TRY(dns::check_rom_shape(nb, nt, cv->nv_inner, ld, nlive));
+    DNS_HIP(hipSetDevice(cv->device));
+    const bool with_d = dbc_rows && cv->ndbc > 0;
+    DevBuf<double> B, D, part, T;
+    DNS_TRY(B.alloc((size_t)nb * ld));
+    DNS_TRY(T.alloc((size_t)nt * nb * nb));
+    DNS_TRY(B.upload(basis, (size_t)nb * ld, nullptr));
+    if (with_d) {
+        DNS_TRY(D.alloc((size_t)nb * cv->ndbc));
+        DNS_TRY(D.upload(dbc_rows, (size_t)nb * cv->ndbc, nullptr));
+    }
+    DNS_TRY(dns::launch_rom_tensor(*cv, nlive, B.p, (size_t)ld,
+                                   with_d ? D.p : nullptr, nb, nt, part, T.p,
+                                   nullptr));
+    DNS_TRY(T.download(out, (size_t)nt * nb * nb, nullptr));
+    DNS_HIP(hipDeviceSynchronize());
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
 int dns_conv_bind_pattern(dns_conv *cv, const dns_csr *pat) try {
     if (!cv || !pat || !pat->rowptr || !pat->colidx)
         return fail(DNS_ERR_BAD_ARGUMENT, "null argument");

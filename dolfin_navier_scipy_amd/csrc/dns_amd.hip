@@ -3324,4 +3324,5 @@ dns::RowMap dns_saddle::dist_rowmap() const { return dd->kmap; }
 #include "imex_attach_capi.inc"
 #include "trap_capi.inc"
 #include "ops_capi.inc"
+#include "galerkin.hpp"
 #include "conv_capi.inc"

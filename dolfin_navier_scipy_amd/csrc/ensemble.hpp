@@ -17,6 +17,10 @@
 //   k_ens_spmm         Y = E[16 jb .. 16 jb + 15, :] W   (skipped for W = I)
 //   k_ens_gram         partial tiles (ib <= jb, jb) per chunk of kEnsChunk k
 //   k_ens_gram_reduce  sums the partials in chunk order, writes G and mirrors
+// P = X W Y^T for two row sets (launch_ensemble_project: the reduced operators
+// of a Galerkin projection) runs the same three kernels, k_ens_gram and
+// k_ens_gram_reduce in their non-mirroring form <false>: every tile (ib, jb),
+// every entry written once.
 // No atomics; the chunk length is a constant, so the bits are the same in
 // every run and on every grid.  Extra memory beside E: Y, 16 x ldv doubles,
 // and the partial tiles of one block column, ceil(m / 16) x ceil(NV / 1024) x
@@ -75,15 +79,16 @@ struct EnsSpmmArgs {
     int ns;                             // snapshots of the block, 1..16
     int nv;
     size_t ld, ldy;
-    const int *rp, *ci;                 // W (nv x nv, symmetric)
+    const int *rp, *ci;                 // W (nv x nv, any)
     const double *va;
     double *Y;                          // 16 x ldy
 };
 
 // One wave per row r of W, the waves of the grid stride over the rows, lanes
 // stride over the row's entries; (column, value) is loaded once and used for
-// every snapshot of the block; wave_sum: a fixed order.  W symmetric:
-// Y[s, r] = sum_c W[r, c] E[s, c] = (E W)[s, r].
+// every snapshot of the block; wave_sum: a fixed order.  For any W
+// Y[s, r] = sum_c W[r, c] E[s, c] = (W e_s)[r], so that the tiles behind it
+// hold x_i . (W e_j); for a symmetric W that is (E W)[s, r] as well.
 __global__ void __launch_bounds__(kBlock) k_ens_spmm(EnsSpmmArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int wpg = kBlock / kWave;
@@ -119,6 +124,9 @@ struct EnsGramArgs {
     int m, nv, jb, nchunks;
     size_t ld, ldb;
     double *part;                       // (jb + 1) x nchunks x 256
+    int mj = 0;                         // <false>: rows of the other set (the
+                                        // block column's side), part is
+                                        // ens_blocks(m) x nchunks x 256
 };
 
 // entries k, k + 1 of a row (k even), nothing at or behind `kend`, nothing of
@@ -143,16 +151,20 @@ __device__ __forceinline__ double2 ens_pair(const double *__restrict__ p, int k,
 // k0 + 2 kq, k0 + 2 kq + 1 of its row with one 16-byte load and feeds the two
 // to two MFMAs (a permutation of k, the same for A and B).  Result register g
 // of lane l is row (l >> 4) + 4 g, column l & 15 (NOT the f32 map).
+// SYM: G = E W E^T, the tiles ib <= jb only (the reduction mirrors); !SYM:
+// every block row ib of E against the block column jb of another row set of
+// `mj` rows.
+template <bool SYM>
 __global__ void __launch_bounds__(kBlock) k_ens_gram(EnsGramArgs a) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int ib = blockIdx.y * (kBlock / kWave) + wave;
-    if (ib > a.jb) return;                      // (a whole wave)
+    if (SYM ? ib > a.jb : ib >= ens_blocks(a.m)) return;    // (a whole wave)
     const int chunk = blockIdx.x;
     const int kbeg = chunk * kEnsChunk;
     const int kend = min(a.nv, kbeg + kEnsChunk);
     const int row = lane & 15, kq = lane >> 4;
     const int i = ib * kEnsTile + row, j = a.jb * kEnsTile + row;
-    const bool iok = i < a.m, jok = j < a.m;
+    const bool iok = i < a.m, jok = j < (SYM ? a.m : a.mj);
     const double *__restrict__ pa = a.E + (size_t)(iok ? i : 0) * a.ld;
     const double *__restrict__ pb = a.B + (size_t)(jok ? row : 0) * a.ldb;
     ens_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
@@ -182,10 +194,12 @@ __global__ void __launch_bounds__(kBlock) k_ens_gram(EnsGramArgs a) {
 
 // Workgroup ib, thread e: entry e of tile (ib, jb), its partials added in
 // chunk order; of a diagonal tile the upper triangle only; written to G[i, j]
-// and G[j, i]: G is exactly symmetric.
+// and G[j, i]: G is exactly symmetric.  !SYM: every entry of the tile, to
+// G[i, j] of the m x mj result alone.
+template <bool SYM>
 __global__ void __launch_bounds__(kBlock)
 k_ens_gram_reduce(const double *__restrict__ part, int nchunks, int jb, int m,
-                  double *__restrict__ G) {
+                  double *__restrict__ G, int mj) {
     const int ib = blockIdx.x, e = threadIdx.x;
     const double *__restrict__ p =
         part + (size_t)ib * nchunks * (kEnsTile * kEnsTile) + e;
@@ -193,9 +207,13 @@ k_ens_gram_reduce(const double *__restrict__ part, int nchunks, int jb, int m,
     for (int c = 0; c < nchunks; ++c) s += p[(size_t)c * (kEnsTile * kEnsTile)];
     const int i = ib * kEnsTile + ens_tile_row(e);
     const int j = jb * kEnsTile + ens_tile_col(e);
-    if (i < m && j < m && j >= i) {
-        G[(size_t)i * m + j] = s;
-        G[(size_t)j * m + i] = s;
+    if (SYM) {
+        if (i < m && j < m && j >= i) {
+            G[(size_t)i * m + j] = s;
+            G[(size_t)j * m + i] = s;
+        }
+    } else if (i < m && j < mj) {
+        G[(size_t)i * mj + j] = s;
     }
 }
 
@@ -311,10 +329,47 @@ inline int launch_ensemble_gram(const double *E, int m, int nv, size_t ld,
         }
         const EnsGramArgs ga{E, W ? y.p : Ej, m, nv, jb, nch, ld,
                              W ? ldy : ld, part.p};
-        hipLaunchKernelGGL(k_ens_gram, dim3(nch, (jb + wpg) / wpg), kBlock, 0,
-                           s, ga);
-        hipLaunchKernelGGL(k_ens_gram_reduce, jb + 1, kBlock, 0, s, part.p,
-                           nch, jb, m, G);
+        hipLaunchKernelGGL(k_ens_gram<true>, dim3(nch, (jb + wpg) / wpg),
+                           kBlock, 0, s, ga);
+        hipLaunchKernelGGL(k_ens_gram_reduce<true>, jb + 1, kBlock, 0, s,
+                           part.p, nch, jb, m, G, m);
+    }
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
+// P (device, mx x my) = X W Y^T, P[i, j] = x_i . (W y_j), for the mx rows at X
+// (ldx apart) and the my rows at Y (ldy apart); W null: I.  The chunks and the
+// order of their sums are those of the Gram matrix: with X = Y and a
+// symmetric W the tiles ib <= jb hold its bits.  `y` and `part` are scratch
+// the caller keeps (grown here).  Enqueued on `s`.
+inline int launch_ensemble_project(const double *X, int mx, size_t ldx,
+                                   const double *Y, int my, size_t ldy, int nv,
+                                   const EnsWeights *W, DevBuf<double> &y,
+                                   DevBuf<double> &part, double *P,
+                                   hipStream_t s) {
+    DNS_TRY(check_ensemble_shape(mx, nv, ldx));
+    DNS_TRY(check_ensemble_shape(my, nv, ldy));
+    const int nbx = ens_blocks(mx), nby = ens_blocks(my), nch = ens_chunks(nv);
+    const size_t ldw = ens_ldv(nv);
+    if (W && y.n < (size_t)kEnsTile * ldw) DNS_TRY(y.alloc((size_t)kEnsTile * ldw));
+    if (part.n < ens_partials(mx, nv)) DNS_TRY(part.alloc(ens_partials(mx, nv)));
+    const int wpg = kBlock / kWave;
+    for (int jb = 0; jb < nby; ++jb) {
+        const double *Yj = Y + (size_t)jb * kEnsTile * ldy;
+        if (W) {
+            const EnsSpmmArgs sa{Yj, std::min(kEnsTile, my - jb * kEnsTile), nv,
+                                 ldy, ldw, W->rp.p, W->ci.p, W->va.p, y.p};
+            hipLaunchKernelGGL(k_ens_spmm,
+                               std::max(1, std::min((nv + wpg - 1) / wpg, 4096)),
+                               kBlock, 0, s, sa);
+        }
+        const EnsGramArgs ga{X, W ? y.p : Yj, mx, nv, jb, nch, ldx,
+                             W ? ldw : ldy, part.p, my};
+        hipLaunchKernelGGL(k_ens_gram<false>, dim3(nch, (nbx + wpg - 1) / wpg),
+                           kBlock, 0, s, ga);
+        hipLaunchKernelGGL(k_ens_gram_reduce<false>, nbx, kBlock, 0, s, part.p,
+                           nch, jb, mx, P, my);
     }
     DNS_HIP(hipGetLastError());
     return DNS_OK;

@@ -1306,6 +1306,35 @@ int dns_ensemble_gram(int device, int32_t m, int32_t nv, int32_t ld,
     return DNS_OK;
 } DNS_CAPI_CATCH
 
+int dns_ensemble_project(int device, int32_t mx, int32_t my, int32_t nv,
+                         int32_t ld, const double *x, const double *y,
+                         const dns_csr *w, double *p) try {
+    if (!x || !p) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(dns::check_ensemble_shape(mx, nv, ld < 0 ? 0 : (size_t)ld));
+    DNS_TRY(dns::check_ensemble_shape(y ? my : mx, nv, (size_t)ld));
+    DNS_TRY(dns::check_ensemble_weights(w, nv));
+    if (!y) my = mx;
+    DNS_HIP(hipSetDevice(device));
+    ScopedStream ss;
+    DNS_HIP(hipStreamCreate(&ss.s));
+    dns::DevBuf<double> X, Y, scratch, part, P;
+    dns::EnsWeights W;
+    DNS_TRY(X.alloc((size_t)mx * ld));
+    DNS_TRY(P.alloc((size_t)mx * my));
+    DNS_TRY(X.upload(x, (size_t)mx * ld, ss.s));
+    if (y) {
+        DNS_TRY(Y.alloc((size_t)my * ld));
+        DNS_TRY(Y.upload(y, (size_t)my * ld, ss.s));
+    }
+    if (w) DNS_TRY(W.upload(w, ss.s));
+    DNS_TRY(dns::launch_ensemble_project(X.p, mx, (size_t)ld, y ? Y.p : X.p, my,
+                                         (size_t)ld, nv, w ? &W : nullptr,
+                                         scratch, part, P.p, ss.s));
+    DNS_TRY(P.download(p, (size_t)mx * my, ss.s));
+    DNS_HIP(hipStreamSynchronize(ss.s));
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
 int dns_ensemble_combine(int device, int32_t m, int32_t nv, int32_t ld,
                          const double *e, int32_t r, const double *coef,
                          double *out) try {

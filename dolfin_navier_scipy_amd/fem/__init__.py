@@ -13,3 +13,4 @@ from .statistics import FlowStatistics, component_pairs
 from .quadratics import (QuadraticFunctionals, kinetic_energy, dissipation,
                          kinetic_energy_rate, rate_norm, energy_budget)
 from .pod import SnapshotPOD
+from .rom import GalerkinROM

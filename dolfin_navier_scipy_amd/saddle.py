@@ -8,7 +8,7 @@ from . import _capi as C
 
 __all__ = ['streaming_precond_defaults', 'choose_schur', 'SaddleSystem', 'ImexStepper', 'spmv', 'dot', 'axpy', 'gemv',
            'dense_inverse', 'spmv_bench', 'spmv_pair', 'spmv_epilogue', 'solve_opts', 'precond_opts',
-           'ensemble_gram', 'ensemble_combine']
+           'ensemble_gram', 'ensemble_combine', 'ensemble_project']
 
 _METHODS = {'gmres': C.DNS_METHOD_GMRES, 'bicgstab': C.DNS_METHOD_BICGSTAB}
 _SCHUR = {'dense': C.DNS_SCHUR_DENSE, 'jacobi': C.DNS_SCHUR_JACOBI, 'mg': 2}
@@ -996,6 +996,29 @@ def ensemble_gram(E, W=None, nv=None, device=0):
     C.check(lib.dns_ensemble_gram(device, m, nv, ld, C.dptr(E.reshape(-1)),
                                   None if view is None else view.byref(),
                                   C.dptr(out.reshape(-1))))
+    return out
+
+
+def ensemble_project(X, Y=None, W=None, nv=None, device=0):
+    """`P = X[:, :nv] W Y[:, :nv]^T`, `P[i, j] = x_i . (W y_j)`, through
+    `dns_ensemble_project`: `X` is `mx x ld`, `Y` `my x ld` (`None`: `Y = X`),
+    `ld` even, `W` any `nv x nv` matrix or `None` for the identity"""
+    lib = C.load_library()
+    X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.float64)
+    mx, ld = X.shape
+    if Y is not None:
+        Y = np.ascontiguousarray(np.atleast_2d(Y), dtype=np.float64)
+        if Y.shape[1] != ld:
+            raise ValueError('`Y` must have the {0} columns of `X`, it is '
+                             '{1}'.format(ld, Y.shape))
+    my = mx if Y is None else Y.shape[0]
+    nv = ld if nv is None else int(nv)
+    view = None if W is None else C.CsrView(W)
+    out = np.empty((mx, my))
+    C.check(lib.dns_ensemble_project(
+        device, mx, my, nv, ld, C.dptr(X.reshape(-1)),
+        None if Y is None else C.dptr(Y.reshape(-1)),
+        None if view is None else view.byref(), C.dptr(out.reshape(-1))))
     return out
 
 

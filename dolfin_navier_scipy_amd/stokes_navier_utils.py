@@ -358,6 +358,7 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
               solver=None, device=0, bcs_time_only=False,
               applybcs_literal=True, record_on_device=False,
               functionals=None, statistics=None, quadratics=None, pod=None,
+              rom=None,
               **kw):
     """time-dependent Navier-Stokes on the device (reference snu:548-1600)
 
@@ -432,7 +433,11 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     the loop (`resident=dict(pod=...)`), which keeps the snapshots on the
     device where it runs resident and forms Gram matrix and modes there;
     `time_int_utils.LAST_RUN['pod']` and `['pod_on']` hold the result and
-    where it was formed.  The POD covers the inner velocity dofs.
+    where it was formed.  The POD covers the inner velocity dofs.  `rom`
+    (with `pod`, explicit schemes): a `fem.GalerkinROM` -- handed down beside
+    it (`resident=dict(rom=...)`): the Galerkin projection of the system onto
+    the modes, reduced matrices and the cubic convection tensor, formed where
+    the POD was; `LAST_RUN['rom']`, `['rom_on']`.  `ValueError` without `pod`.
     """
     if functionals is not None and not (treat_nonl_explicit
                                         and lin_vel_point is None):
@@ -443,6 +448,12 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     if quadratics is not None and not (treat_nonl_explicit
                                        and lin_vel_point is None):
         raise NotImplementedError('`quadratics`: explicit schemes only')
+    if rom is not None and pod is None:
+        raise ValueError('`rom` without `pod`: the reduced operators are '
+                         'projections onto the POD\'s modes')
+    if rom is not None and not (treat_nonl_explicit
+                                and lin_vel_point is None):
+        raise NotImplementedError('`rom`: explicit schemes only')
     if pod is not None and not (treat_nonl_explicit
                                 and lin_vel_point is None):
         raise NotImplementedError('`pod`: explicit schemes only')
@@ -656,6 +667,8 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
             icd.setdefault('resident', {}).update(quadratics=quadratics)
         if pod is not None:
             icd.setdefault('resident', {}).update(pod=pod)
+        if rom is not None:
+            icd.setdefault('resident', {}).update(rom=rom)
         v_end, p_end, ffflag = timintsc(trange=trange, inip=inip, scalep=-1.,
                                         g_tdp=rhsp, bcs_ini=inicdbcvals,
                                         check_ff_maxv=check_ff_maxv, **icd)

@@ -446,9 +446,13 @@ class _PodEnsemble(_Attachment):
     NV` doubles come back, the snapshots never do.  Where the loop takes one
     step at a time the kept states are stored on the host and go through
     `pod.evaluate`.  The snapshots are the inner velocity dofs: controlled
-    Dirichlet values are not in them"""
+    Dirichlet values are not in them.  With `rom` (a `fem.GalerkinROM`) the
+    modes and the mean flow go on into `rom.project` with the loop's convection
+    operator `conv` -- on the device where the POD was formed there, through
+    the host model otherwise"""
 
-    def __init__(self, stepper, pod, trange, keep_snapshots=False):
+    def __init__(self, stepper, pod, trange, keep_snapshots=False, rom=None,
+                 conv=None):
         NV = stepper.sys.NV
         if pod.NV != NV:
             raise ValueError('`pod`: its weight matrix is {0} x {0}, the loop '
@@ -462,6 +466,7 @@ class _PodEnsemble(_Attachment):
         self.host = {}
         self.filled = 0             # kept steps that have run
         self.res = None
+        self.rom, self.conv, self.rom_res = rom, conv, None
 
     def arm(self, times, tables):
         self.stepper.set_ensemble(self.pod.slots_for(times), nslots=self.m,
@@ -510,9 +515,18 @@ class _PodEnsemble(_Attachment):
         if self.armed:
             stepper.clear_ensemble()
             self.armed = False
+        if self.rom is not None:
+            if self.rom.M is None:
+                self.rom.M = pod.W
+            self.rom_res = self.rom.project(
+                self.res['modes'], self.res['mean'], self.conv,
+                self.conv.dbcvals, device=self.where == 'device')
 
     def report(self):
-        return dict(pod=self.res, pod_on=self.where)
+        out = dict(pod=self.res, pod_on=self.where)
+        if self.rom is not None:
+            out.update(rom=self.rom_res, rom_on=self.where)
+        return out
 
 
 class _StatisticsSums(_Attachment):
@@ -655,6 +669,20 @@ class _ImexLoop(object):
             raise ValueError(
                 '`quadratics` with moving Dirichlet values: the forms carry '
                 'the boundary values as constants')
+        rom = self.rsd.get('rom', None)
+        if rom is not None:
+            if pod is None:
+                raise ValueError('`rom` without `pod`: the reduced operators '
+                                 'are projections onto the POD\'s modes')
+            if self.conv is None:
+                raise ValueError(
+                    '`rom` needs the loop\'s device convection operator '
+                    '(`device_convection`) for the tensor: a host `f_vdp` '
+                    'has no element data')
+            if self.moving:
+                raise ValueError(
+                    '`rom` with moving Dirichlet values: constant boundary '
+                    'values only, the mean flow carries them')
         self.attachments += [a for a in (
             flog, None if fs is None else _StatisticsSums(self.stepper, fs),
             None if qf is None else _QuadraticLog(
@@ -662,7 +690,8 @@ class _ImexLoop(object):
                 max_grid=self.rsd.get('quadratics_max_grid', None)),
             None if pod is None else _PodEnsemble(
                 self.stepper, pod, trange,
-                keep_snapshots=self.rsd.get('pod_snapshots', False)))
+                keep_snapshots=self.rsd.get('pod_snapshots', False),
+                rom=rom, conv=self.conv))
             if a is not None]
 
     def _terms_at(self, ctime, v_c=None, p_c=None):
@@ -1072,6 +1101,21 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                         `pod.max_bytes`.  `pod_snapshots=True` downloads the
                         snapshots as well (`['pod']['snapshots']`, m x NV:
                         diagnostics)
+      `rom`             with `pod`: a `fem.GalerkinROM` (the condensed `A`,
+                        `fv`; `M` defaults to the POD's weight matrix).  When
+                        the modes exist they are projected with the loop's
+                        convection operator (`rom.project`): the reduced mass
+                        and stiffness matrices and the constant term through
+                        `X W Y^T` on the fp64 matrix cores, the cubic
+                        convection tensor `int phi_i . (u_j . grad) u_k`
+                        through `ConvectionP2.project_tensor` -- on the device
+                        where the POD was formed there, by the fp64 host model
+                        otherwise.  `LAST_RUN['rom']` is the dict `Mr`, `Ar`,
+                        `b0`, `c`, `L`, `H` (`div` with `J`), None where the
+                        loop broke off; `['rom_on']` says 'device' or 'host'.
+                        Constant Dirichlet values only; `ValueError` without
+                        `pod`, without `device_convection`, or with `bcs_ini`
+                        not empty
     `LAST_RUN['record']` says 'device' or 'host', `LAST_RUN['run_calls']`
     counts the `stepper.run` calls of the loop.
     The per-step data the callbacks return (`f_tdp`, `g_tdp`, `applybcs`) are

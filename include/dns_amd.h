@@ -698,6 +698,20 @@ int dns_conv_set_dbc_row(dns_conv *cv, int32_t row);
 /* out = scale * N(u)u restricted to the inner dofs (host in/out; parity) */
 int dns_conv_apply(dns_conv *cv, const double *v_inner, double scale,
                    double *out);
+/* the cubic convection tensor of a Galerkin projection (reduced-order models),
+ *   out[i, j, k] = sum_cells sum_q w_q |cell| phi_i(x_q) . (u_j . grad) u_k (x_q),
+ * nt x nb x nb, row-major, j the convecting and k the convected field, by the
+ * 7-point rule of dns_conv_apply.  basis is nb x ld on the host (ld even, >=
+ * the inner dofs; row b holds u_b on the inner dofs), dbc_rows nb x ndbc the
+ * Dirichlet values row b carries (NULL: zeros); the test functions phi_i are
+ * the rows i < nt on the inner dofs and zero on the Dirichlet dofs.  1 <= nt
+ * <= nb <= 33 (32 modes and a mean flow).  Fixed chunks of 512 cells, fp64
+ * matrix cores, partial tiles added in chunk order: no atomics, the same bits
+ * in every run.  The operator's own Dirichlet values and tables play no part
+ * and stay as they are */
+int dns_conv_project_tensor(dns_conv *cv, int32_t nb, int32_t nt, int32_t ld,
+                            const double *basis, const double *dbc_rows,
+                            double *out);
 /* let the stepper evaluate nfc_c = scale * N(v_c)v_c itself every step
  * (scale = -1: "goes to the rhs", stokes_navier_utils.py:1128-1140); NULL
  * detaches.  dns_imex_step then takes nfc_new = NULL and dns_imex_run
@@ -725,6 +739,17 @@ int dns_ensemble_gram(int device, int32_t m, int32_t nv, int32_t ld,
 int dns_ensemble_combine(int device, int32_t m, int32_t nv, int32_t ld,
                          const double *e, int32_t r, const double *coef,
                          double *out);
+/* p (mx x my, row-major) = X W Y^T, p[i, j] = x_i . (W y_j): the reduced
+ * operators of a Galerkin projection.  x is mx x ld and y my x ld on the host
+ * (ld even, >= nv, as above); y NULL: Y = X (my is ignored); w any NV x NV
+ * matrix -- it need not be symmetric -- or NULL for the identity.  The kernels
+ * are those of dns_ensemble_gram in their non-mirroring form: the same chunks
+ * of 1024 entries summed in chunk order, no atomics, the same bits in every
+ * run; with Y = X and a symmetric w the tiles on and above the block diagonal
+ * hold dns_ensemble_gram's bits */
+int dns_ensemble_project(int device, int32_t mx, int32_t my, int32_t nv,
+                         int32_t ld, const double *x, const double *y,
+                         const dns_csr *w, double *p);
 
 /* repeat y = A x `reps` times on resident data; reports the average kernel
  * time (HIP events on the launch stream) -- the roofline measurement */
