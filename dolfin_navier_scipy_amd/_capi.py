@@ -206,6 +206,19 @@ SIGNATURES = {
     'dns_imex_get_feedback_log': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
                                              c_double_p, c_double_p]),
     'dns_imex_clear_feedback': (ct.c_int, [_VP]),
+    'dns_imex_set_feedback_boundary': (ct.c_int, [_VP, ct.POINTER(dns_csr),
+                                                  c_double_p, ct.c_int32,
+                                                  ct.POINTER(dns_csr),
+                                                  ct.POINTER(dns_csr),
+                                                  ct.POINTER(dns_csr),
+                                                  c_double_p, c_double_p]),
+    'dns_imex_set_feedback_state_bc': (ct.c_int, [_VP, c_double_p, c_double_p,
+                                                  c_double_p, c_double_p]),
+    'dns_imex_get_feedback_state_bc': (ct.c_int, [_VP, c_double_p, c_double_p,
+                                                  c_double_p, c_double_p]),
+    'dns_imex_get_feedback_bcs': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
+                                             c_double_p]),
+    'dns_imex_get_feedback_rhs': (ct.c_int, [_VP, c_double_p, c_double_p]),
     'dns_imex_set_recorder': (ct.c_int, [_VP, ct.POINTER(dns_csr), ct.c_int32,
                                          c_int32_p, ct.c_int32]),
     'dns_imex_get_record_outputs': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,

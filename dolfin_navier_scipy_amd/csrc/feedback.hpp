@@ -168,6 +168,230 @@ __global__ void __launch_bounds__(kBlock) k_lti_step(LtiArgs a) {
     }
 }
 
+// ---- boundary actuation -----------------------------------------------------
+// The observer's output drives the controlled Dirichlet values (the reference's
+// `diricontfuncs` read the state): behind the same y, f, hx_n, u_n
+//   b(s + 1) = base + S u_n                        (S: nc x Nu CSR)
+// goes into the controlled columns of row s + 1 of the convection operator's
+// Dirichlet table -- the front convection of this step reads row s, the tail's
+// convection of the new state row s + 1, both later in the stream -- and what
+// the boundary terms of the right-hand sides have that is linear in u is added
+// to the rows the host tabulated with u = 0:
+//   geff  = g(s) + sum_{j = n, c, p} (wm_j Bm + wa_j Ba) u_j
+//                + dt (c_n B u_n + c_c B u_c)      (B optional)
+//   gpeff = gp(s) + Bj u_n
+// (Ba, Bm: NV x Nu, Bj: NP x Nu: `applybcs` of the unit controls; u_p, the
+// output two times back, is SBDF2's.)  The state slot holds hx, f_last, u_c,
+// u_p: 2 hN + 2 Nu entries.
+struct LtiBcArgs {
+    LtiArgs l;                          // brp null: no B; geff null: no
+                                        // right-hand-side terms at all
+    int np, nc;
+    const int *srp, *sci;
+    const double *sva, *base;
+    double *dbc;                        // the table's controlled columns, row 0
+    int dbc_stride, dbc_rows;
+    const int *arp, *aci;               // Ba, Bm, Bj (all null: literal zero)
+    const double *ava;
+    const int *mrp, *mci;
+    const double *mva;
+    const int *jrp, *jci;
+    const double *jva;
+    double wm_n, wm_c, wm_p, wa_n, wa_c, wa_p;
+    TabRef gp;
+    double *gpeff;
+};
+
+// entry k of a state slot to its place in LDS
+__device__ __forceinline__ void lti_bc_put(int k, double v, int hN, int Nu,
+                                           double *shx, double *sfl,
+                                           double *suc, double *sup) {
+    if (k < hN) shx[k] = v;
+    else if (k < 2 * hN) sfl[k - hN] = v;
+    else if (k < 2 * hN + Nu) suc[k - 2 * hN] = v;
+    else if (k < 2 * hN + 2 * Nu) sup[k - 2 * hN - Nu] = v;
+}
+
+// sum_k A[r, k] u[k] over the entries [k0, k1) of a row, in storage order
+__device__ __forceinline__ double lti_row_dot(const int *__restrict__ ci,
+                                              const double *__restrict__ va,
+                                              int k0, int k1, const double *u) {
+    double acc = 0.0;
+    for (int k = k0; k < k1; ++k) acc = fma(va[k], u[ci[k]], acc);
+    return acc;
+}
+
+// k_lti_step's observer step word for word (the same summation orders, every
+// workgroup redundantly, workgroup 0 writes state and logs), then each
+// workgroup writes its entries of the Dirichlet row and its rows of geff and
+// gpeff.  As there, what does not depend on y is asked for before the first
+// barrier: both state slots, the staged matrices, the first row pointers and
+// the first entries of g and gp of every thread.
+template <bool STAGE>
+__global__ void __launch_bounds__(kBlock) k_lti_bc_step(LtiBcArgs b) {
+    const LtiArgs &a = b.l;
+    __shared__ double sy[kFbMaxOut], shx[kFbMaxState], sfl[kFbMaxState],
+        sf[kFbMaxState], shn[kFbMaxState], sun[kFbMaxIn], suc[kFbMaxIn],
+        sup[kFbMaxIn], spart[kBlock], smat[STAGE ? kFbStage : 1];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int hN = a.hN, Ny = a.Ny, Nu = a.Nu;
+    const int stride = 2 * hN + 2 * Nu;         // <= 2 kBlock
+    // ---- loads that depend on nothing ----
+    int step = *a.stepctr;
+    double st0 = 0.0, st1 = 0.0, st0b = 0.0, st1b = 0.0;
+    if (tid < stride) {
+        st0 = a.state[tid];
+        st1 = a.state[stride + tid];
+    }
+    if (tid + kBlock < stride) {
+        st0b = a.state[tid + kBlock];
+        st1b = a.state[stride + tid + kBlock];
+    }
+    const int r_first = blockIdx.x * kBlock + tid;
+    const bool rhs_v = a.geff != nullptr, rhs_p = b.gpeff != nullptr;
+    const bool has_b = a.brp != nullptr, has_m = b.mrp != nullptr;
+    int bk0 = 0, bk1 = 0, mk0 = 0, mk1 = 0, ak0 = 0, ak1 = 0, jk0 = 0, jk1 = 0;
+    if (rhs_v && r_first < a.nv) {
+        if (has_b) {
+            bk0 = a.brp[r_first];
+            bk1 = a.brp[r_first + 1];
+        }
+        if (has_m) {
+            mk0 = b.mrp[r_first];
+            mk1 = b.mrp[r_first + 1];
+            ak0 = b.arp[r_first];
+            ak1 = b.arp[r_first + 1];
+        }
+    }
+    if (rhs_p && r_first < b.np) {
+        jk0 = b.jrp[r_first];
+        jk1 = b.jrp[r_first + 1];
+    }
+    int sk0 = 0, sk1 = 0;
+    if (r_first < b.nc) {
+        sk0 = b.srp[r_first];
+        sk1 = b.srp[r_first + 1];
+    }
+    const double *__restrict__ mhaT = a.haT, *__restrict__ mhbT = a.hbT,
+                               *__restrict__ mhc = a.hc;
+    if (STAGE) {
+        const int n1 = hN * hN, n2 = n1 + hN * Ny, n3 = n2 + Nu * hN;
+        for (int k = tid; k < n3; k += kBlock)
+            smat[k] = k < n1 ? a.haT[k] : k < n2 ? a.hbT[k - n1] : a.hc[k - n2];
+        mhaT = smat;
+        mhbT = smat + n1;
+        mhc = smat + n2;
+    }
+    step = step < 0 ? 0 : step;
+    const int row = step >= a.rows ? a.rows - 1 : step;
+    const int par = step & 1;
+    double *__restrict__ nw = a.state + (size_t)(1 - par) * stride;
+    // ---- loads that depend on the counter only ----
+    const double *__restrict__ g = rhs_v ? tab_row(a.g) : nullptr;
+    const double *__restrict__ gp = rhs_p ? tab_row(b.gp) : nullptr;
+    const double g_first = rhs_v && r_first < a.nv ? g[r_first] : 0.0;
+    const double gp_first = rhs_p && r_first < b.np ? gp[r_first] : 0.0;
+    double dr = 0.0;
+    if (a.drift && tid < hN) dr = a.drift[(size_t)row * hN + tid];
+    lti_bc_put(tid, par ? st1 : st0, hN, Nu, shx, sfl, suc, sup);
+    lti_bc_put(tid + kBlock, par ? st1b : st0b, hN, Nu, shx, sfl, suc, sup);
+    // y = C v_c: one wave per sensor row, lanes stride over its entries
+    for (int r = wave; r < Ny; r += kBlock / kWave) {
+        double acc = 0.0;
+        for (int k = a.crp[r] + lane; k < a.crp[r + 1]; k += kWave)
+            acc = fma(a.cva[k], a.v[a.cci[k]], acc);
+        acc = wave_sum(acc);
+        if (lane == 0) sy[r] = acc;
+    }
+    __syncthreads();
+    // f = ha hx + hb y + drift: two threads per row of ha
+    {
+        const int i = tid & (kFbMaxState - 1), half = tid / kFbMaxState;
+        const int jm = hN / 2;
+        const int j0 = half ? jm : 0, j1 = half ? hN : jm;
+        double acc = 0.0;
+        if (i < hN)
+            for (int j = j0; j < j1; ++j)
+                acc = fma(mhaT[(size_t)j * hN + i], shx[j], acc);
+        spart[tid] = acc;
+    }
+    __syncthreads();
+    if (tid < hN) {
+        double f = spart[tid] + spart[tid + kFbMaxState];
+        for (int k = 0; k < Ny; ++k)
+            f = fma(mhbT[(size_t)k * hN + tid], sy[k], f);
+        if (a.drift) f += dr;
+        sf[tid] = f;
+        shn[tid] = shx[tid] + 1.5 * a.dt * f - 0.5 * a.dt * sfl[tid];
+    }
+    __syncthreads();
+    // u_n = hc hx_n: one wave per input
+    for (int m = wave; m < Nu; m += kBlock / kWave) {
+        double acc = 0.0;
+        for (int i = lane; i < hN; i += kWave)
+            acc = fma(mhc[(size_t)m * hN + i], shn[i], acc);
+        acc = wave_sum(acc);
+        if (lane == 0) sun[m] = acc;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0) {
+        if (tid < hN) {
+            nw[tid] = shn[tid];
+            nw[hN + tid] = sf[tid];
+        }
+        if (tid < Nu) {
+            nw[2 * hN + tid] = sun[tid];
+            nw[2 * hN + Nu + tid] = suc[tid];
+            a.ulog[(size_t)row * Nu + tid] = sun[tid];
+        }
+        if (tid < Ny) a.ylog[(size_t)row * Ny + tid] = sy[tid];
+    }
+    // the Dirichlet values of the state this step leaves: row step + 1
+    if (step + 1 < b.dbc_rows) {
+        double *__restrict__ drow = b.dbc + (size_t)(step + 1) * b.dbc_stride;
+        for (int i = r_first; i < b.nc; i += gridDim.x * kBlock) {
+            const bool first = i == r_first;
+            const int k0 = first ? sk0 : b.srp[i], k1 = first ? sk1 : b.srp[i + 1];
+            drow[i] = b.base[i] + lti_row_dot(b.sci, b.sva, k0, k1, sun);
+        }
+    }
+    // geff: rows without entries copy g
+    if (rhs_v)
+        for (int r = r_first; r < a.nv; r += gridDim.x * kBlock) {
+            const bool first = r == r_first;
+            double add = 0.0;
+            if (has_m) {
+                const int m0 = first ? mk0 : b.mrp[r];
+                const int m1 = first ? mk1 : b.mrp[r + 1];
+                const int a0 = first ? ak0 : b.arp[r];
+                const int a1 = first ? ak1 : b.arp[r + 1];
+                const double mn = lti_row_dot(b.mci, b.mva, m0, m1, sun);
+                const double mc = lti_row_dot(b.mci, b.mva, m0, m1, suc);
+                const double mp = lti_row_dot(b.mci, b.mva, m0, m1, sup);
+                const double an = lti_row_dot(b.aci, b.ava, a0, a1, sun);
+                const double ac = lti_row_dot(b.aci, b.ava, a0, a1, suc);
+                const double ap = lti_row_dot(b.aci, b.ava, a0, a1, sup);
+                add = b.wm_n * mn + b.wm_c * mc + b.wm_p * mp + b.wa_n * an +
+                      b.wa_c * ac + b.wa_p * ap;
+            }
+            if (has_b) {
+                const int k0 = first ? bk0 : a.brp[r];
+                const int k1 = first ? bk1 : a.brp[r + 1];
+                const double sn = lti_row_dot(a.bci, a.bva, k0, k1, sun);
+                const double sc = lti_row_dot(a.bci, a.bva, k0, k1, suc);
+                add += a.dt * (a.c_n * sn + a.c_c * sc);
+            }
+            a.geff[r] = (first ? g_first : g[r]) + add;
+        }
+    if (rhs_p)
+        for (int r = r_first; r < b.np; r += gridDim.x * kBlock) {
+            const bool first = r == r_first;
+            const int k0 = first ? jk0 : b.jrp[r], k1 = first ? jk1 : b.jrp[r + 1];
+            b.gpeff[r] = (first ? gp_first : gp[r]) +
+                         lti_row_dot(b.jci, b.jva, k0, k1, sun);
+        }
+}
+
 // (ha, hb, hc fit the LDS stage?)
 inline bool lti_staged(int hN, int Ny, int Nu) {
     return hN * hN + hN * Ny + Nu * hN <= kFbStage;

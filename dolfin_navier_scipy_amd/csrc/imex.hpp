@@ -138,9 +138,25 @@ struct dns_imex : dns::Ring {
         double dt = 0.0, c_n = 0.0, c_c = 0.0;
         dns::CsrDev C, B;
         dns::DevBuf<double> haT, hbT, hc, drift, state, ylog, ulog, geff;
-        int stride() const { return 2 * hN + Nu; }
+        // boundary actuation (dns_imex_set_feedback_boundary): k_lti_bc_step
+        // in the place of k_lti_step.  It also writes the controlled columns
+        // [col0, col0 + nc) of row `counter + 1` of the convection operator's
+        // Dirichlet table, and the slot keeps u_p behind u_c.  `bc_rhs`: the
+        // boundary terms Ba, Bm, Bj were given; `has_b`: B has entries
+        bool bc = false, bc_rhs = false, has_b = true;
+        int nc = 0, col0 = 0;
+        dns::CsrDev S, Ba, Bm, Bj;
+        dns::DevBuf<double> base;
+        // (behind geff in ONE buffer of NV + NP: one entry of a checkpoint)
+        double *gpeff = nullptr;
+        double wm[3] = {0, 0, 0}, wa[3] = {0, 0, 0};
+        int stride() const { return 2 * hN + Nu + (bc ? Nu : 0); }
+        // does the step read geff / gpeff?
+        bool rhs_v() const { return !bc || bc_rhs || has_b; }
+        bool rhs_p() const { return bc && bc_rhs; }
     } fb;
-    int fb_launch(hipStream_t s);  // k_lti_step for the step about to run
+    int fb_launch(hipStream_t s);  // k_lti_step / k_lti_bc_step for the step
+                                   // about to run
     uint64_t fb_key() const;
     // trajectory recorder (record.hpp): k_record_step runs in front of every
     // step (behind k_lti_step) and once behind the last step of a call; it
@@ -274,13 +290,18 @@ struct dns_imex : dns::Ring {
     }
     // (with feedback: what k_lti_step has made of g_src() for this step)
     dns::TabRef g_ref() const {
-        if (fb.on) return {fb.geff.p, nullptr, 0, 1};
+        if (fb.on && fb.rhs_v()) return {fb.geff.p, nullptr, 0, 1};
         return g_src();
     }
-    dns::TabRef gp_ref() const {
+    dns::TabRef gp_src() const {
         if (tab_rows > 0 && tab_p)
             return {gptab.p, stepctr.p, std::max(1, sys->np), tab_rows};
         return {gp.p, nullptr, 0, 1};
+    }
+    // (with boundary feedback and its terms: what k_lti_bc_step has made of it)
+    dns::TabRef gp_ref() const {
+        if (fb.on && fb.rhs_p()) return {fb.gpeff, nullptr, 0, 1};
+        return gp_src();
     }
     int sync_counter();            // device counter <- tab_pos
     double last_pscale = 1.0;

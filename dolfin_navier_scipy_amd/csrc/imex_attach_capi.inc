@@ -8,11 +8,22 @@
 // "feedback on", its shape, its coefficients and every buffer k_lti_step is
 // handed: a graph captured for another set must not be replayed
 uint64_t dns_imex::fb_key() const {
-    return mix64(0xfb, {kw(fb.hN), kw(fb.Ny), kw(fb.Nu), kw(fb.rows),
-                        kw(fb.has_drift), kw(fb.dt), kw(fb.c_n), kw(fb.c_c),
-                        kw(fb.C.vals.p), kw(fb.B.vals.p), kw(fb.haT.p),
-                        kw(fb.drift.p), kw(fb.state.p), kw(fb.ylog.p),
-                        kw(fb.ulog.p), kw(fb.geff.p), kw(g.p)});
+    uint64_t k = mix64(0xfb, {kw(fb.hN), kw(fb.Ny), kw(fb.Nu), kw(fb.rows),
+                              kw(fb.has_drift), kw(fb.dt), kw(fb.c_n),
+                              kw(fb.c_c), kw(fb.C.vals.p), kw(fb.B.vals.p),
+                              kw(fb.haT.p), kw(fb.drift.p), kw(fb.state.p),
+                              kw(fb.ylog.p), kw(fb.ulog.p), kw(fb.geff.p),
+                              kw(g.p)});
+    if (!fb.bc) return k;
+    // the boundary mode: its shape, weights and every further buffer
+    // k_lti_bc_step is handed (the table itself is part of config_key)
+    k = mix64(k, {kw(0xbc), kw(fb.nc), kw(fb.col0), kw(fb.bc_rhs),
+                  kw(fb.has_b), kw(fb.S.vals.p), kw(fb.base.p),
+                  kw(fb.Ba.vals.p), kw(fb.Bm.vals.p), kw(fb.Bj.vals.p),
+                  kw(fb.gpeff), kw(gp.p)});
+    return mix64(k, {kw(fb.wm[0]), kw(fb.wm[1]), kw(fb.wm[2]), kw(fb.wa[0]),
+                     kw(fb.wa[1]), kw(fb.wa[2]),
+                     kw(conv ? conv->ndbc : 0)});
 }
 
 // "recorder on", its shape, every buffer k_record_step is handed and the
@@ -96,6 +107,49 @@ int dns_imex::fb_launch(hipStream_t s) {
                          fb.has_drift ? fb.drift.p : (const double *)nullptr,
                          fb.state.p, fb.ylog.p, fb.ulog.p, fb.dt, fb.c_n,
                          fb.c_c, g_src(), xs[cur].p, fb.geff.p};
+    if (fb.bc) {
+        // (check_attachments has seen to the convection operator and its table)
+        dns::LtiBcArgs b{};
+        b.l = a;
+        if (!fb.has_b) b.l.brp = nullptr;
+        if (!fb.rhs_v()) b.l.geff = nullptr;
+        b.np = sys->np;
+        b.nc = fb.nc;
+        b.srp = fb.S.rowptr.p;
+        b.sci = fb.S.colidx.p;
+        b.sva = fb.S.vals.p;
+        b.base = fb.base.p;
+        b.dbc = conv->dbc_tab.p + fb.col0;
+        b.dbc_stride = std::max(1, conv->ndbc);
+        b.dbc_rows = conv->dbc_rows;
+        if (fb.bc_rhs) {
+            b.arp = fb.Ba.rowptr.p;
+            b.aci = fb.Ba.colidx.p;
+            b.ava = fb.Ba.vals.p;
+            b.mrp = fb.Bm.rowptr.p;
+            b.mci = fb.Bm.colidx.p;
+            b.mva = fb.Bm.vals.p;
+            b.jrp = fb.Bj.rowptr.p;
+            b.jci = fb.Bj.colidx.p;
+            b.jva = fb.Bj.vals.p;
+            b.gpeff = fb.gpeff;
+        }
+        b.wm_n = fb.wm[0];
+        b.wm_c = fb.wm[1];
+        b.wm_p = fb.wm[2];
+        b.wa_n = fb.wa[0];
+        b.wa_c = fb.wa[1];
+        b.wa_p = fb.wa[2];
+        b.gp = gp_src();
+        if (dns::lti_staged(fb.hN, fb.Ny, fb.Nu))
+            hipLaunchKernelGGL(dns::k_lti_bc_step<true>, dns::lti_grid(sys->nv),
+                               dns::kBlock, 0, s, b);
+        else
+            hipLaunchKernelGGL(dns::k_lti_bc_step<false>,
+                               dns::lti_grid(sys->nv), dns::kBlock, 0, s, b);
+        DNS_HIP(hipGetLastError());
+        return DNS_OK;
+    }
     if (dns::lti_staged(fb.hN, fb.Ny, fb.Nu))
         hipLaunchKernelGGL(dns::k_lti_step<true>, dns::lti_grid(sys->nv),
                            dns::kBlock, 0, s, a);
@@ -299,6 +353,30 @@ static const char *const kQdMovingBc =
 // what a step refuses on their behalf
 int dns_imex::check_attachments() const {
     if (fb.on) DNS_TRY(refuse_partitioned("observer feedback", kFbPartitioned));
+    if (fb.on && fb.bc) {
+        // k_lti_bc_step writes row `counter + 1` of the operator's table
+        if (!conv)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "boundary feedback needs the device convection "
+                             "operator whose Dirichlet table it writes "
+                             "(dns_imex_set_convection)");
+        if (fb.col0 + fb.nc > conv->ndbc)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "boundary feedback: the controlled columns "
+                             "[%d, %d) do not fit the %d Dirichlet values of "
+                             "the convection operator", fb.col0,
+                             fb.col0 + fb.nc, conv->ndbc);
+        if (conv->dbc_rows < fb.rows + 1)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "boundary feedback: the Dirichlet table has %d "
+                             "rows, %d steps need %d (dns_conv_set_dbc_table; "
+                             "row 0: the values of the current state)",
+                             conv->dbc_rows, fb.rows, fb.rows + 1);
+        if (fn || qd)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "boundary feedback with functionals / quadratics: "
+                             "their Dirichlet values are host-made copies");
+    }
     if (rec) DNS_TRY(refuse_partitioned("recorder", kRecPartitioned));
     if (stat) DNS_TRY(refuse_partitioned("statistics", kStPartitioned));
     if (ens) DNS_TRY(refuse_partitioned("ensemble", kEnsPartitioned));
@@ -584,6 +662,9 @@ int dns_imex_set_feedback(dns_imex *st, const dns_csr *cmat, const dns_csr *bmat
     DNS_HIP(hipStreamSynchronize(h->stream));   // replays may still read it
     dns_imex::Feedback &f = st->fb;
     f.on = false;
+    f.bc = f.bc_rhs = false;       // (dns_imex_set_feedback_boundary follows)
+    f.has_b = true;
+    f.gpeff = nullptr;
     hipStream_t s = h->stream;
     DNS_TRY(f.C.upload(cmat, s));
     DNS_TRY(f.B.upload(bmat, s));
@@ -685,7 +766,166 @@ int dns_imex_get_feedback_log(dns_imex *st, int32_t first, int32_t count,
 int dns_imex_clear_feedback(dns_imex *st) try {
     DNS_TRY(quiesce(st));
     st->fb.on = false;
+    st->fb.bc = st->fb.bc_rhs = false;
+    st->fb.gpeff = nullptr;
     st->fb.rows = 0;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// ---- boundary feedback (k_lti_bc_step) -------------------------------------
+
+static int fbc_need(dns_imex *st) {
+    return need(st, st && st->fb.on && st->fb.bc, "boundary feedback is",
+                "dns_imex_set_feedback_boundary");
+}
+
+int dns_imex_set_feedback_boundary(dns_imex *st, const dns_csr *smat,
+                                   const double *base, int32_t col0,
+                                   const dns_csr *ba, const dns_csr *bm,
+                                   const dns_csr *bj, const double *wm,
+                                   const double *wa) try {
+    if (!st || !smat || !wm || !wa)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    // every check first: a refusal leaves the feedback as dns_imex_set_feedback
+    // left it
+    DNS_TRY(st->refuse_partitioned("boundary feedback", kFbPartitioned));
+    DNS_TRY(fb_need(st));
+    dns_saddle *h = st->sys;
+    dns_imex::Feedback &f = st->fb;
+    if (!st->conv)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "boundary feedback needs a device convection operator: "
+                         "it writes that operator's Dirichlet table "
+                         "(dns_imex_set_convection)");
+    DNS_TRY(dns::check_csr(smat, "S"));
+    const int nc = smat->nrows;
+    if (nc < 1 || smat->ncols != f.Nu)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "boundary feedback: S must be nc x Nu (%d columns), "
+                         "it is %d x %d", f.Nu, (int)smat->nrows,
+                         (int)smat->ncols);
+    if (col0 < 0 || col0 + nc > st->conv->ndbc)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "boundary feedback: the controlled columns [%d, %d) "
+                         "do not fit the %d Dirichlet values of the convection "
+                         "operator", (int)col0, (int)col0 + nc,
+                         st->conv->ndbc);
+    const bool rhs = ba || bm || bj;
+    if (rhs && !(ba && bm && bj))
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "boundary feedback: Ba, Bm and Bj come together (or "
+                         "all NULL: no boundary terms)");
+    if (rhs) {
+        const dns_csr *mats[3] = {ba, bm, bj};
+        const char *names[3] = {"Ba", "Bm", "Bj"};
+        for (int t = 0; t < 3; ++t) {
+            DNS_TRY(dns::check_csr(mats[t], names[t]));
+            const int want = t == 2 ? h->np : h->nv;
+            if (mats[t]->nrows != want || mats[t]->ncols != f.Nu)
+                return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                                 "boundary feedback: %s must be %d x %d, it is "
+                                 "%d x %d", names[t], want, f.Nu,
+                                 (int)mats[t]->nrows, (int)mats[t]->ncols);
+        }
+    }
+    DNS_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still read it
+    f.on = false;
+    DNS_TRY(f.S.upload(smat, s));
+    std::vector<double> b0((size_t)nc, 0.0);
+    if (base) b0.assign(base, base + nc);
+    DNS_TRY(f.base.alloc((size_t)nc));
+    DNS_TRY(f.base.upload(b0.data(), (size_t)nc, s));
+    if (rhs) {
+        DNS_TRY(f.Ba.upload(ba, s));
+        DNS_TRY(f.Bm.upload(bm, s));
+        DNS_TRY(f.Bj.upload(bj, s));
+    }
+    // geff and gpeff in one buffer; the slots get room for u_p
+    const size_t ng = (size_t)h->nv + (size_t)std::max(1, h->np);
+    if (f.geff.n < ng) DNS_TRY(f.geff.alloc(ng));
+    DNS_TRY(f.geff.zero(s));
+    f.bc = true;
+    f.bc_rhs = rhs;
+    f.has_b = f.B.nnz > 0;
+    f.gpeff = rhs ? f.geff.p + h->nv : nullptr;
+    f.nc = nc;
+    f.col0 = col0;
+    for (int j = 0; j < 3; ++j) {
+        f.wm[j] = wm[j];
+        f.wa[j] = wa[j];
+    }
+    DNS_TRY(f.state.alloc((size_t)2 * f.stride()));
+    DNS_TRY(f.state.zero(s));
+    f.rows = 0;                                 // the table follows
+    f.has_drift = false;
+    DNS_HIP(hipStreamSynchronize(s));
+    f.on = true;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_imex_set_feedback_state_bc(dns_imex *st, const double *hx,
+                                   const double *f_last, const double *u_c,
+                                   const double *u_p) try {
+    DNS_TRY(fbc_need(st));
+    if (!hx || !f_last || !u_c || !u_p)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    dns_imex::Feedback &f = st->fb;
+    hipStream_t s = st->sys->stream;
+    DNS_HIP(hipStreamSynchronize(s));
+    double *slot = f.state.p + (size_t)(st->tab_pos & 1) * f.stride();
+    DNS_TRY(dns::upload_to(slot, hx, (size_t)f.hN, s));
+    DNS_TRY(dns::upload_to(slot + f.hN, f_last, (size_t)f.hN, s));
+    DNS_TRY(dns::upload_to(slot + 2 * f.hN, u_c, (size_t)f.Nu, s));
+    DNS_TRY(dns::upload_to(slot + 2 * f.hN + f.Nu, u_p, (size_t)f.Nu, s));
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_imex_get_feedback_state_bc(dns_imex *st, double *hx, double *f_last,
+                                   double *u_c, double *u_p) try {
+    DNS_TRY(fbc_need(st));
+    const dns_imex::Feedback &f = st->fb;
+    hipStream_t s = st->sys->stream;
+    const double *slot = f.state.p + (size_t)(st->tab_pos & 1) * f.stride();
+    if (hx) DNS_TRY(dns::download_from(hx, slot, (size_t)f.hN, s));
+    if (f_last)
+        DNS_TRY(dns::download_from(f_last, slot + f.hN, (size_t)f.hN, s));
+    if (u_c) DNS_TRY(dns::download_from(u_c, slot + 2 * f.hN, (size_t)f.Nu, s));
+    if (u_p)
+        DNS_TRY(dns::download_from(u_p, slot + 2 * f.hN + f.Nu, (size_t)f.Nu,
+                                   s));
+    DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_imex_get_feedback_bcs(dns_imex *st, int32_t first, int32_t count,
+                              double *bcs) try {
+    DNS_TRY(fbc_need(st));
+    const dns_imex::Feedback &f = st->fb;
+    const dns_conv *cv = st->conv;
+    if (!bcs) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (!cv || cv->dbc_rows < 1 || f.col0 + f.nc > cv->ndbc)
+        return dns::fail(DNS_ERR_NOT_READY,
+                         "boundary feedback: no Dirichlet table of that width "
+                         "on the convection operator (dns_conv_set_dbc_table)");
+    return download_log_rows(st, bcs, cv->dbc_tab.p + f.col0, first, count,
+                             (size_t)f.nc, cv->dbc_rows, "table rows",
+                             "Dirichlet table", (size_t)std::max(1, cv->ndbc));
+} DNS_CAPI_CATCH
+
+int dns_imex_get_feedback_rhs(dns_imex *st, double *geff, double *gpeff) try {
+    DNS_TRY(fbc_need(st));
+    const dns_imex::Feedback &f = st->fb;
+    const dns_saddle *h = st->sys;
+    if ((geff && !f.rhs_v()) || (gpeff && !f.rhs_p()))
+        return dns::fail(DNS_ERR_NOT_READY,
+                         "boundary feedback without terms of the right-hand "
+                         "side: the step reads the tabulated rows");
+    hipStream_t s = h->stream;
+    if (geff) DNS_TRY(dns::download_from(geff, f.geff.p, (size_t)h->nv, s));
+    if (gpeff) DNS_TRY(dns::download_from(gpeff, f.gpeff, (size_t)h->np, s));
+    DNS_HIP(hipStreamSynchronize(s));
     return DNS_OK;
 } DNS_CAPI_CATCH
 

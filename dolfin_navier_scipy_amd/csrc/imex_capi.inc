@@ -847,7 +847,9 @@ int ImexRun::run_batch() {
     // counter; the log rows of a discarded batch are overwritten)
     if (st->fb.on) {
         DNS_TRY(ck.add(st->fb.state.p, (size_t)2 * st->fb.stride()));
-        DNS_TRY(ck.add(st->fb.geff.p, h->nv));
+        // (boundary feedback: gpeff lies behind geff)
+        DNS_TRY(ck.add(st->fb.geff.p,
+                       (size_t)h->nv + (st->fb.gpeff ? (size_t)h->np : 0)));
     }
     // flow statistics: the sums AND the workgroups' marks -- a restored batch
     // adds its rows again, to the sums the batch started from (a checkpoint
@@ -1192,6 +1194,7 @@ int dns_imex_step(dns_imex *st, const double *nfc_new,
                          "upload the next ones (dns_imex_set_rhs_table / ... / "
                          "dns_imex_set_functionals / dns_imex_set_quadratics)",
                          st->tab_pos);
+    DNS_TRY(st->check_attachments());
     if (nfc_new) {
         std::swap(st->nc, st->no);
         DNS_TRY(st->nfc[st->nc].upload(nfc_new, (size_t)h->nv, h->stream));
@@ -1230,6 +1233,9 @@ int dns_imex_run(dns_imex *st, int32_t nsteps, const dns_imex_coeffs *cf,
                          "(dns_imex_set_rhs_table / ... / "
                          "dns_imex_set_functionals / dns_imex_set_quadratics)",
                          (int)nsteps, st->rows_left());
+    // (what a step would refuse on behalf of its attachments, before anything
+    // is touched or captured)
+    DNS_TRY(st->check_attachments());
     // the run's settings of the system, undone on every exit (the status of
     // the oversolve reset is ignored: the first error is the one reported)
     bool over = false;

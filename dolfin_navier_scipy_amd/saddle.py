@@ -527,6 +527,73 @@ class ImexStepper(object):
             C.dptr(u.reshape(-1))))
         return y, u
 
+    # ---- boundary feedback (`dns_imex_set_feedback_boundary`) ---------------
+    def set_feedback_boundary(self, s_mat, base=None, col0=0, Ba=None,
+                              Bm=None, Bj=None, wm=(0., 0., 0.),
+                              wa=(0., 0., 0.)):
+        """behind `set_feedback` (whose `b_mat` may be empty): the observer's
+        output drives the controlled Dirichlet values, `b = base + s_mat u`
+        (`s_mat`: `nc x Nu`), written by the device into the columns `col0 ..
+        col0 + nc` of the NEXT row of the Dirichlet table of the attached
+        convection operator (`ConvectionP2.set_dbc_table`, one row more than
+        steps: row 0 holds the values of the current state).  `Ba`, `Bm` (`NV
+        x Nu`), `Bj` (`NP x Nu`): what `applybcs` makes of the unit controls
+        (all None: the literal zero); `wm`, `wa`: the scheme's weights of
+        `Bm u_j`, `Ba u_j` for `j = n, c, p` (`include/dns_amd.h`).  State
+        and table follow: `set_feedback_state(.., u_p=)`,
+        `set_feedback_table`."""
+        _, _, Nu = self._fb_shape
+        sview = C.CsrView(s_mat)
+        if sview.shape[1] != Nu:
+            raise ValueError('s_mat must be nc x Nu')
+        nc = sview.shape[0]
+        mats = (Ba, Bm, Bj)
+        if any(m is None for m in mats) and not all(m is None for m in mats):
+            raise ValueError('Ba, Bm and Bj come together')
+        views = [None if m is None else C.CsrView(m) for m in mats]
+        base = None if base is None else C.as_f64(base, nc)
+        wm, wa = C.as_f64(wm, 3), C.as_f64(wa, 3)
+        C.check(self.lib.dns_imex_set_feedback_boundary(
+            self._h, sview.byref(), C.dptr(base), int(col0),
+            *[None if v is None else v.byref() for v in views],
+            C.dptr(wm), C.dptr(wa)))
+        self._fb_nc = nc
+
+    def set_feedback_state_bc(self, hx, f_last, u_c, u_p):
+        hN, _, Nu = self._fb_shape
+        args = [C.as_f64(hx, hN), C.as_f64(f_last, hN), C.as_f64(u_c, Nu),
+                C.as_f64(u_p, Nu)]
+        C.check(self.lib.dns_imex_set_feedback_state_bc(
+            self._h, *[C.dptr(a) for a in args]))
+
+    def feedback_state_bc(self):
+        """`(hx, f_last, u_c, u_p)` of the current time"""
+        hN, _, Nu = self._fb_shape
+        out = np.empty(hN), np.empty(hN), np.empty(Nu), np.empty(Nu)
+        C.check(self.lib.dns_imex_get_feedback_state_bc(
+            self._h, *[C.dptr(a) for a in out]))
+        return out
+
+    def feedback_bcs(self, first=0, count=None):
+        """rows `first .. first + count` of the controlled columns of the
+        Dirichlet table as the device filled them (`count x nc`; default: row
+        0 up to the row of the current state).  Row `s + 1` holds the values
+        of the state step `s` left"""
+        if count is None:
+            count = self.table_position()[0] + 1 - first
+        out = np.empty((int(count), self._fb_nc))
+        C.check(self.lib.dns_imex_get_feedback_bcs(
+            self._h, int(first), int(count), C.dptr(out.reshape(-1))))
+        return out
+
+    def feedback_rhs(self, velocity=True, pressure=True):
+        """`(geff, gpeff)` the last step read (None where not asked for)"""
+        geff = np.empty(self.sys.NV) if velocity else None
+        gpeff = np.empty(self.sys.NP) if pressure else None
+        C.check(self.lib.dns_imex_get_feedback_rhs(self._h, C.dptr(geff),
+                                                   C.dptr(gpeff)))
+        return geff, gpeff
+
     # ---- trajectory recorder (`dns_imex_set_recorder`) ----------------------
     def set_recorder(self, nrows, cv_mat=None, snap_slots=None):
         """the next `nrows` steps (`step` and `run` alike) write themselves

@@ -414,7 +414,14 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     the Dirichlet values of the device convection operator; `ValueError`
     otherwise): the boundary terms follow the controlled values of every
     state, on the device with `bcs_time_only=True` (one `run` per time
-    slice), on the host otherwise.  `statistics` (explicit schemes): a
+    slice), on the host otherwise.  `diricontfuncs` may be a
+    `time_int_utils.BoundaryFeedback` (or its `controls()`): an observer whose
+    outputs are the gains of the controlled boundaries, `b = gain_k *
+    diricontbcvals[k]`; the explicit schemes then run resident without
+    `bcs_time_only` (`LAST_RUN['feedback'] == 'resident-boundary'`), any other
+    state-dependent function keeps the per-step path; `functionals`,
+    `quadratics`, `rom` beside it are a `ValueError`.
+    `statistics` (explicit schemes): a
     `fem.FlowStatistics` over the inner dofs and the pressure -- handed down
     to the loop (`resident=dict(statistics=...)`), which adds the state after
     the Heun start and after every AB2 / BDF2 step to its sums, on the device
@@ -496,6 +503,37 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     Afull, Mfull, Jfull = rs['A'], rs['M'], rs['J']
     NP = cj.shape[0]
     vdim = cnv if V is None else V.vdim
+    # a `BoundaryFeedback` (or its `controls()`) as the control functions: one
+    # observer behind all of them, which the explicit loops can run resident
+    bfb = diricontfuncs if isinstance(diricontfuncs, tiu.BoundaryFeedback) \
+        else None
+    if bfb is None and diricontfuncs:
+        owners = set(id(getattr(f, 'boundary_feedback', None))
+                     for f in diricontfuncs)
+        first = getattr(diricontfuncs[0], 'boundary_feedback', None)
+        if first is not None and len(owners) == 1 \
+                and len(diricontfuncs) == first.Nu:
+            bfb = first
+    if bfb is not None:
+        if diricontbcvals is None or len(diricontbcvals) != bfb.Nu:
+            raise ValueError('a `BoundaryFeedback` with {0} inputs needs as '
+                             'many controlled boundaries (`diricontbcvals`)'
+                             .format(bfb.Nu))
+        if bfb.s_mat is None:
+            # `b = gain_k * shape_k` per boundary: one column each
+            offs = np.cumsum([0] + [len(sv) for sv in diricontbcvals])
+            smat = sps.lil_matrix((offs[-1], bfb.Nu))
+            for k, shape in enumerate(diricontbcvals):
+                smat[offs[k]:offs[k + 1], k] = np.asarray(
+                    shape, dtype=np.float64).reshape((-1, 1))
+            bfb.bind_boundary(smat.tocsr())
+        bfb.bind_inner(dbcnt)       # (refuses a sensor on a controlled dof)
+        if diricontfuncs is bfb:
+            diricontfuncs = bfb.controls()
+        if diricontfuncmems is None:
+            diricontfuncmems = [None]*bfb.Nu
+        if iniv is not None:        # (else the Stokes start asks the controls)
+            bfb.observe(trange[0], mode='init')
     cdict = dict(A=Afull, J=Jfull, loccntbcinds=loccnt, invinds_loc=locinv,
                  diricontbcvals=diricontbcvals, diricontfuncs=diricontfuncs,
                  diricontfuncmems=diricontfuncmems)
@@ -611,6 +649,9 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
                                       diricontfuncs=diricontfuncs,
                                       diricontfuncmems=diricontfuncmems,
                                       mode=mode)
+        if bfb is not None:
+            # (the loops recognise the observer behind the closure)
+            getbcs.boundary_feedback = bfb
         timintsc = {'cnab': tiu.cnab, 'sbdf2': tiu.sbdftwo}[time_int_scheme]
         icd = dict(f_tdp=rhsv, inivel=iniv, verbose=verbose, M=cmmat,
                    A=camat, J=cj, f_vdp=f_vdp, getbcs=getbcs,
@@ -631,7 +672,8 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
                       and not (vp_output or return_vp_dict
                                or return_dictofvelstrs)
                       and cv_mat.shape[1] == cnv)
-        if cvop is not None and (static_bcs or bcs_time_only):
+        if cvop is not None and (static_bcs or bcs_time_only
+                                 or bfb is not None):
             # the loop may evaluate N(v)v itself and, the callbacks being
             # functions of the time only, run whole time slices resident
             # (CNAB and SBDF2 alike)
@@ -774,7 +816,6 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
         feedback = None
         if closed_loop:
             # snu:1367-1384, 1461-1483
-            import scipy.sparse as sps
             bdense = np.asarray(b_mat.todense()) if sps.issparse(b_mat) \
                 else np.asarray(b_mat, dtype=np.float64)
 

@@ -13,6 +13,8 @@ Krylov iteration of `csrc/` (instead of `spsla.factorized`, tiu:89-91,134).
  * `_inittimegrid`       (tiu:480-489)
  * `LinearFeedback`      (tiu:148-196 composed as in snu:1243-1247) observer
                          feedback as a `dynamic_rhs` the loops can run resident
+ * `BoundaryFeedback`    the same observer driving the controlled Dirichlet
+                         values (`getbcs` / `diricontfuncs`), resident as well
 
 Per step the host still evaluates the reference's callbacks (`f_vdp`, `getbcs`,
 `applybcs`, `f_tdp`, `g_tdp`, `dynamic_rhs`, `savevp`) because they are the
@@ -30,7 +32,7 @@ from . import lin_alg_utils as lau
 from .saddle import SaddleSystem, ImexStepper, solve_opts, choose_schur
 
 __all__ = ['cnab', 'sbdftwo', 'semi_implicit_euler', 'SOLVER',
-           'LinearFeedback']
+           'LinearFeedback', 'BoundaryFeedback']
 
 # solver settings of the time loops; `rtol` is relative to ||rhs||.  `None`:
 # `lin_alg_utils.default_rtol` of the system at hand -- 1e-12, and 1e-13 where
@@ -234,6 +236,256 @@ class _HostFeedback(_Attachment):
         return dict(feedback='host',
                     feedback_y=np.array(y).reshape((-1, fb.Ny)),
                     feedback_u=np.array(u).reshape((-1, fb.Nu)))
+
+
+class BoundaryFeedback(object):
+    """Output feedback through a linear observer whose output drives the
+    controlled Dirichlet values (rotating cylinders, a modulated inflow)
+
+        y = cv_mat v_inner,   hx' = ha hx + hb y + drift(t),   u = hc hx,
+        b(t) = base + s_mat u(t)
+
+    `b`: the `nc` values of the controlled dofs in the order `getbcs` returns
+    them, `s_mat`: `nc x Nu`, `base`: `nc` values (default 0).  The
+    discretisation, the modes (`init`, `heunpred`, `heuncorr`, `abtwo`) and
+    the keys of `memory` are `LinearFeedback`'s.  `cv_mat` is given over the
+    FULL velocity dofs together with `invinds`; an entry in a Dirichlet column
+    is refused: sensors live in the flow.
+
+    Two faces of one object:
+     * a `getbcs` of `cnab` / `sbdftwo`: `fb(time, vvec, pvec, mode=)` returns
+       the list `b`; `vvec` is the full vector.  `bcs_ini` is what
+       `fb(trange[0], mode='init')` returns.  With `device_convection` and
+       `resident=` the AB2 / BDF2 steps are not called back: the device
+       advances the observer and writes the values into the convection
+       operator's Dirichlet table (`ImexStepper.set_feedback_boundary`)
+     * `diricontfuncs` of `solve_nse`: `fb.controls()` returns `Nu` callables
+       `func(time, vel=, p=, mode=, memory=)` that share the observer -- the
+       first call for a `(time, mode)` advances it, the others read it; or
+       the instance itself, `diricontfuncs=fb` (`s_mat` may be None then:
+       `solve_nse` builds it from `diricontbcvals`, one column per boundary)
+
+    `memory` is the object's own (`getbcs` has none to pass); `calls` counts
+    the calls by mode; `history` lists `(t, mode, y, u)` of every observer
+    step that was made on the host."""
+
+    def __init__(self, cv_mat, s_mat, ha, hb, hc, inihx, invinds=None,
+                 base=None, drift=None):
+        self.ha = np.array(ha, dtype=np.float64)
+        hN = self.ha.shape[0]
+        self.hb = np.array(hb, dtype=np.float64).reshape((hN, -1))
+        self.hc = np.array(hc, dtype=np.float64).reshape((-1, hN))
+        self.inihx = np.array(inihx, dtype=np.float64).reshape((hN, 1))
+        self.hN, self.Ny, self.Nu = hN, self.hb.shape[1], self.hc.shape[0]
+        self.cv_mat = sps.csr_matrix(cv_mat)
+        if self.cv_mat.shape[0] != self.Ny:
+            raise ValueError('cv_mat has {0} rows, hb takes {1} outputs'
+                             .format(self.cv_mat.shape[0], self.Ny))
+        self.s_mat = self.base = self.invinds = self.cv_inner = None
+        self._base = base
+        if invinds is not None:
+            self.bind_inner(invinds)
+        if s_mat is not None:
+            self.bind_boundary(s_mat)
+        self._drift = drift
+        self.memory = {}
+        self.calls = dict(init=0, heunpred=0, heuncorr=0, abtwo=0)
+        self.history = []
+        self._seen = None           # `((time, mode), u)` of the last step
+
+    def bind_inner(self, invinds):
+        """the inner dofs of the full vector `cv_mat` is given over"""
+        inv = np.asarray(invinds, dtype=np.int64).reshape(-1)
+        outside = np.ones(self.cv_mat.shape[1], dtype=bool)
+        outside[inv] = False
+        cols = self.cv_mat.tocoo().col
+        if np.any(outside[cols]):
+            raise ValueError(
+                'cv_mat has an entry in a Dirichlet column (dof {0}): sensors '
+                'live in the flow'.format(int(cols[outside[cols]][0])))
+        self.invinds = inv
+        self.cv_inner = self.cv_mat[:, inv].tocsr()
+        self.cv_inner.sort_indices()
+
+    def bind_boundary(self, s_mat):
+        s_mat = sps.csr_matrix(s_mat)
+        if s_mat.shape[1] != self.Nu:
+            raise ValueError('s_mat has {0} columns, hc gives {1} inputs'
+                             .format(s_mat.shape[1], self.Nu))
+        s_mat.sort_indices()
+        nc = s_mat.shape[0]
+        base = np.zeros(nc) if self._base is None else \
+            np.array(self._base, dtype=np.float64).reshape(-1)
+        if base.size != nc:
+            raise ValueError('base has {0} entries, s_mat {1} rows'
+                             .format(base.size, nc))
+        self.s_mat, self.base = s_mat, base
+
+    def drift(self, t):
+        if self._drift is None:
+            return np.zeros((self.hN, 1))
+        return np.asarray(self._drift(t), dtype=np.float64).reshape(
+            (self.hN, 1))
+
+    def values(self, u):
+        """`b = base + s_mat u`"""
+        return self.base + self.s_mat @ np.asarray(u).reshape(-1)
+
+    def observe(self, t, vvec=None, mode='abtwo'):
+        """one observer step (`LinearFeedback.__call__` without `b_mat`);
+        `vvec`: the full velocity vector.  Returns `u` (Nu)"""
+        mode = 'init' if mode == 'stokes' else \
+            'abtwo' if mode is None else mode
+        if mode not in self.calls:
+            raise ValueError('unknown mode {0}'.format(mode))
+        self.calls[mode] += 1
+        ha, hb, inihx, memory = self.ha, self.hb, self.inihx, self.memory
+        if mode == 'init':
+            memory.clear()
+            memory.update(dict(lastt=t, lasthx=inihx))
+            y, chx = None, inihx
+        else:
+            if self.cv_inner is None:
+                raise ValueError('no inner dofs given (`invinds`)')
+            vin = np.asarray(vvec, dtype=np.float64).reshape(-1)[self.invinds]
+            y = self.cv_inner @ vin.reshape((-1, 1))
+            curdt = t - memory['lastt']
+            if mode == 'heunpred':
+                currhs = ha @ inihx + hb @ y + self.drift(memory['lastt'])
+                chx = inihx + curdt*currhs
+                memory.update(dict(lastrhs=currhs, hphx=chx))
+            elif mode == 'heuncorr':
+                currhs = ha @ memory['hphx'] + hb @ y + self.drift(t)
+                chx = inihx + .5*curdt*(currhs + memory['lastrhs'])
+                memory.update(dict(lastt=t, lasthx=chx, lastdt=curdt))
+            else:
+                currhs = ha @ memory['lasthx'] + hb @ y \
+                    + self.drift(memory['lastt'])
+                chx = memory['lasthx'] + 1.5*curdt*currhs \
+                    - .5*memory['lastdt']*memory['lastrhs']
+                memory.update(dict(lastt=t, lasthx=chx, lastrhs=currhs,
+                                   lastdt=curdt))
+        u = (self.hc @ chx).reshape(-1)
+        self.history.append((t, mode, None if y is None else y.reshape(-1),
+                             u))
+        return u
+
+    def __call__(self, time, vvec=None, pvec=None, mode='abtwo'):
+        return self.values(self.observe(time, vvec, mode)).tolist()
+
+    def controls(self):
+        """`Nu` control functions of one observer for `diricontfuncs`"""
+        def control(k):
+            def func(time, vel=None, p=None, mode=None, memory=None):
+                key = (time, mode)
+                if self._seen is None or self._seen[0] != key:
+                    self._seen = (key, self.observe(time, vel, mode))
+                return float(self._seen[1][k]), memory
+            func.boundary_feedback = self
+            return func
+        return [control(k) for k in range(self.Nu)]
+
+    def boundary_terms(self, applybcs, NV, NP):
+        """`(Ba, Bm, Bj)`: `bfv`, `mbc` (NV x Nu) and `bfp` (NP x Nu) of the
+        unit controls `s_mat e_k` -- `applybcs` is linear --, or None where it
+        returns zero for all of them (the literal closure)"""
+        cols = []
+        for k in range(self.Nu):
+            e = np.zeros(self.Nu)
+            e[k] = 1.
+            bfv, bfp, mbc = applybcs((self.s_mat @ e).tolist())
+            cols.append((_col(bfv, NV), _col(mbc, NV), _col(bfp, NP)))
+        if not any(np.any(c) for col in cols for c in col):
+            return None
+        return tuple(sps.csr_matrix(np.hstack([col[q] for col in cols]))
+                     for q in range(3))
+
+
+def _boundary_feedback_of(getbcs):
+    """the `BoundaryFeedback` behind a `getbcs`, if any: the instance itself
+    or a closure that carries it (`solve_nse`)"""
+    if isinstance(getbcs, BoundaryFeedback):
+        return getbcs
+    fb = getattr(getbcs, 'boundary_feedback', None)
+    return fb if isinstance(fb, BoundaryFeedback) else None
+
+
+class _ResidentBoundaryFeedback(_Attachment):
+    """the device side of a `BoundaryFeedback` inside `cnab` / `sbdftwo`:
+    takes the observer over from the Heun start, leaves the loop the terms of
+    `u = 0` to tabulate, arms drift rows and logs per slice, collects `y`,
+    `u` and the boundary values the device wrote and hands the final state
+    back to the object's memory"""
+
+    def __init__(self, fb, loop, tstart):
+        stepper = loop.stepper
+        NV, NP = stepper.sys.NV, stepper.sys.NP
+        self.fb, self.stepper, self.dt = fb, stepper, loop.dt
+        self.tlast = tstart
+        self.ylog, self.ulog, self.blog = [], [], []
+        self.slice_bcs = []
+        mem = fb.memory
+        u_c = (fb.hc @ mem['lasthx']).reshape(-1)
+        u_p = (fb.hc @ fb.inihx).reshape(-1)
+        # (what the device continues must be what the host started)
+        for name, got, u in (('bcs_ini', loop.bcs_ini, u_p),
+                             ('the Heun start', loop.cur.bcs, u_c)):
+            want = fb.values(u)
+            if len(got) != want.size or not np.allclose(
+                    np.asarray(got, dtype=np.float64), want, rtol=1e-12,
+                    atol=1e-14):
+                raise ValueError(
+                    'boundary feedback: the boundary values of {0} are not '
+                    '`base + s_mat u` of the observer (`bcs_ini` must be '
+                    '`fb(trange[0], mode=\'init\')`)'.format(name))
+        terms = fb.boundary_terms(loop.applybcs, NV, NP)
+        Ba, Bm, Bj = (None, None, None) if terms is None else terms
+        wm, wa = loop.scheme.bc_weights(loop.dt)
+        stepper.set_feedback(fb.cv_inner, sps.csr_matrix((NV, fb.Nu)), fb.ha,
+                             fb.hb, fb.hc, c_n=0., c_c=0., dt=loop.dt)
+        stepper.set_feedback_boundary(fb.s_mat, fb.base,
+                                      col0=len(loop.statvals), Ba=Ba, Bm=Bm,
+                                      Bj=Bj, wm=wm, wa=wa)
+        # corrector state, the PREDICTOR's right-hand side (tiu:171-174)
+        stepper.set_feedback_state_bc(mem['lasthx'], mem['lastrhs'], u_c, u_p)
+        # the values of the current state (row 0 of the next table); the loop
+        # tabulates with `u = 0`
+        self.current = np.array(loop.cur.bcs, dtype=np.float64)
+        self.base_bcs = fb.base.tolist()
+        bfv0, _, mbc0 = loop.applybcs(self.base_bcs)
+        loop.prev = loop.prev._replace(mbc=mbc0)
+        loop.cur = loop.cur._replace(bcs=self.base_bcs, bfv=bfv0, mbc=mbc0)
+
+    def arm(self, ctrange, tables):
+        befores = [self.tlast] + list(ctrange[:-1])
+        drift = None if self.fb._drift is None else \
+            np.array([self.fb.drift(t)[:, 0] for t in befores])
+        self.stepper.set_feedback_table(len(ctrange), drift)
+        self.tlast = ctrange[-1]
+
+    def collect(self, ctrange):
+        y, u = self.stepper.feedback_log()
+        rows = self.stepper.feedback_bcs(0, len(ctrange) + 1)
+        self.ylog.append(y)
+        self.ulog.append(u)
+        self.blog.append(rows[1:])
+        self.slice_bcs.extend(rows[1:])
+        self.current = rows[-1].copy()
+
+    def finish(self, drm):
+        hx, flast, _, _ = self.stepper.feedback_state_bc()
+        self.fb.memory.update(dict(
+            lastt=self.tlast, lasthx=hx.reshape((-1, 1)),
+            lastrhs=flast.reshape((-1, 1)), lastdt=self.dt))
+
+    def report(self):
+        fb = self.fb
+        y = np.vstack(self.ylog) if self.ylog else np.zeros((0, fb.Ny))
+        u = np.vstack(self.ulog) if self.ulog else np.zeros((0, fb.Nu))
+        b = np.vstack(self.blog) if self.blog else \
+            np.zeros((0, fb.base.size))
+        return dict(feedback='resident-boundary', feedback_y=y, feedback_u=u,
+                    feedback_bcs=b)
 
 
 RECORD_BYTES = 1 << 30      # default cap of a slice's snapshot buffer
@@ -580,14 +832,18 @@ _Terms = collections.namedtuple('_Terms', 'bcs bfv mbc fv dfv')
 # `state_v_p`: `set_state` gets the velocity before the Heun start;
 # `guard_prev`: the blow-up guard looks at the velocity BEFORE the last step
 # and logs nothing (reference quirk, tiu:311), else at `stepper.vnorm()`
+# `bc_weights(dt)`: `(wm, wa)`, what `row` multiplies `mbc` and `bfv` of the
+# times `n, c, p` with -- a resident `BoundaryFeedback` adds `(wm_j Bm + wa_j
+# Ba) u_j` on the device
 _Scheme = collections.namedtuple(
     '_Scheme', 'name theta r1 coeffs fb_weights row keep_prev state_v_p '
-    'guard_prev')
+    'guard_prev bc_weights')
 
 _CNAB = _Scheme(
     name='cnab', theta=.5, r1=lambda M, A, dt: (M - .5*dt*A).tocsr(),
     coeffs=lambda dt: dict(a_c=1., a_p=0., cn_c=1.5*dt, cn_o=-.5*dt),
     fb_weights=(.5, .5),
+    bc_weights=lambda dt: ((-1., 1., 0.), (.5*dt, .5*dt, 0.)),
     row=lambda dt, p, c, n: (-(n.mbc - c.mbc)
                              + .5*dt*(c.fv + n.fv + n.bfv + c.bfv
                                       + n.dfv + c.dfv)),
@@ -597,6 +853,7 @@ _SBDF2 = _Scheme(
     name='sbdftwo', theta=2./3, r1=lambda M, A, dt: M,
     coeffs=lambda dt: dict(a_c=4./3, a_p=-1./3, cn_c=4./3*dt, cn_o=-2./3*dt),
     fb_weights=(2./3, 0.),
+    bc_weights=lambda dt: ((-1., 4/3, -1/3), (2/3*dt, 0., 0.)),
     row=lambda dt, p, c, n: (-(n.mbc - 4/3*c.mbc + 1/3*p.mbc)
                              + 2/3*dt*n.bfv + 2/3*dt*(n.fv + n.dfv)),
     keep_prev=True, state_v_p=True, guard_prev=True)
@@ -614,7 +871,14 @@ class _ImexLoop(object):
                  state_dependent, prev=None, cur=None, v_c=None, v_n=None,
                  p_n=None, drm=None, getbcs=None, applybcs=None,
                  appndbcs=None, f_tdp=None, g_tdp=None, f_vdp=None,
-                 dynamic_rhs=None, savevp=None):
+                 dynamic_rhs=None, savevp=None, bfb=None):
+        # (`bfb`: the `BoundaryFeedback` behind `getbcs` where the loop can
+        # run it resident -- the only state-dependent `getbcs` that may)
+        self.bfb, self.bfb_att, self.bcs_ini = bfb, None, bcs_ini
+        if bfb is not None and (conv is None or resident is None
+                                or state_dependent):
+            raise ValueError('a resident `BoundaryFeedback` needs '
+                             '`device_convection` and `resident=`')
         self.scheme, self.stepper, self.cf = scheme, stepper, cf
         self.opts = opts
         self.dt, self.conv, self.state_dependent = dt, conv, state_dependent
@@ -632,7 +896,7 @@ class _ImexLoop(object):
                 conv.set_dbcvals(self.statvals + list(cur.bcs))
         self.on_device = (conv is not None and resident is not None
                           and not state_dependent
-                          and (not self.moving
+                          and (not self.moving or bfb is not None
                                or rsd.get('bcs_time_only', False)))
         self.prev = prev
         self.cur = cur._replace(dfv=0.) if self.on_device else cur
@@ -654,6 +918,21 @@ class _ImexLoop(object):
         resident_fb = fb_dev and self.on_device
         if not resident_fb and (lti is not None or self.state_dependent):
             self.attachments.append(_HostFeedback(lti))
+        host_bfb = _boundary_feedback_of(self.getbcs)
+        if self.bfb is None and host_bfb is not None and lti is None \
+                and not self.state_dependent:
+            # called back every step: its `(y, u)` rows for the report
+            self.attachments.append(_HostFeedback(host_bfb))
+        if self.bfb is not None:
+            # (their Dirichlet tables are host-made copies of the values)
+            for key in ('functionals', 'quadratics', 'rom'):
+                if self.rsd.get(key, None) is not None:
+                    raise ValueError(
+                        '`{0}` together with a resident `BoundaryFeedback`: '
+                        'the boundary values exist on the device only, the '
+                        '{0} read host-made tables'.format(key))
+            self.bfb_att = _ResidentBoundaryFeedback(self.bfb, self, tstart)
+            self.attachments.append(self.bfb_att)
         fn = self.rsd.get('functionals', None)
         flog = None if fn is None else _FunctionalLog(
             self.stepper, fn, self.dt,
@@ -701,7 +980,10 @@ class _ImexLoop(object):
         ahead of its states) `getbcs` sees `None, None`.  Returns the `_Terms`
         and the lower right-hand side"""
         vfull = None if v_c is None else self.appndbcs(v_c, self.cur.bcs)
-        bcs_n = self.getbcs(ctime, vfull, p_c, mode='abtwo')
+        # (a resident `BoundaryFeedback` is not called: the slice is tabulated
+        # for `u = 0`, the device adds what is linear in `u`)
+        bcs_n = self.bfb_att.base_bcs if self.bfb_att is not None else \
+            self.getbcs(ctime, vfull, p_c, mode='abtwo')
         bfv_n, bfp_n, mbc_n = self.applybcs(bcs_n)
         fv_n, fp_n = self.f_tdp(ctime), self.g_tdp(ctime)
         dfv_n = 0.
@@ -737,10 +1019,19 @@ class _ImexLoop(object):
         if moving:
             dbt[ns] = self._dbc(self.cur)
         span = [0, 0]
+        bfa, nstat = self.bfb_att, len(self.statvals)
+        if bfa is not None:
+            bfa.slice_bcs = []
 
         def upload(a, b):
             stepper.set_rhs_table(gvt[a:b], gpt[a:b])
-            if moving:
+            if bfa is not None:
+                # one row more: the device writes row `s + 1` in step `s`;
+                # row 0 holds the values of the state the chunk starts from
+                tab = dbt[a:b + 1].copy()
+                tab[0, nstat:] = bfa.current
+                self.conv.set_dbc_table(tab)
+            elif moving:
                 self.conv.set_dbc_table(dbt[a:b])
             tables = _Tables(dbt[a:b + 1] if moving else None)
             for att in self.attachments:
@@ -764,9 +1055,13 @@ class _ImexLoop(object):
                 done = s + 1
                 states[s] = stepper.get_state()
             after_chunk()
+        if bfa is not None:
+            # the values every state carries are the device's
+            self.cur = self.cur._replace(bcs=bfa.current.tolist())
         for s, ctime in enumerate(ctrange):
             if self.savetimes is None or ctime in self.savetimes:
-                bcs_at = dbt[s + 1][len(self.statvals):].tolist() \
+                bcs_at = bfa.slice_bcs[s].tolist() if bfa is not None \
+                    else dbt[s + 1][len(self.statvals):].tolist() \
                     if (moving and s + 1 < ns) else bcs_n
                 self.savevp(self.appndbcs(states[s][0], bcs_at),
                             states[s][1], time=ctime)
@@ -960,6 +1255,13 @@ def _imex_loop(scheme, trange, inivel, inip, bcs_ini, M, A, J, f_vdp, f_tdp,
               and device_convection is not None and resident is not None)
     state_dependent = (dynamic_rhs is not None and not fb_dev) \
         or f_tvdp is not None
+    # a `BoundaryFeedback` behind `getbcs` runs on the device as well (beside
+    # an open loop: the step has ONE observer node)
+    bfb = _boundary_feedback_of(getbcs)
+    if not (bfb is not None and dynamic_rhs is None and f_tvdp is None
+            and device_convection is not None and resident is not None
+            and len(bcs_ini) > 0):
+        bfb = None
     dt, listofts = _inittimegrid(trange, ntimeslices=ntimeslices)
     NP, NV = J.shape
     if device_convection is not None and f_vdp is None:
@@ -991,7 +1293,7 @@ def _imex_loop(scheme, trange, inivel, inip, bcs_ini, M, A, J, f_vdp, f_tdp,
         cur=_Terms(bcs_n, bfv_n, mbc_n, fv_n, dfv_n), v_c=inivel, v_n=v_n,
         p_n=p_n, drm=drm, getbcs=getbcs, applybcs=applybcs,
         appndbcs=appndbcs, f_tdp=f_tdp, g_tdp=g_tdp, f_vdp=f_vdp,
-        dynamic_rhs=dynamic_rhs, savevp=savevp)
+        dynamic_rhs=dynamic_rhs, savevp=savevp, bfb=bfb)
     try:
         loop.attach(lti, fb_dev, trange[1], trange=trange)
         ffflag = loop.march(trange[1], listofts, ntimeslices, check_ff_maxv,
@@ -1129,6 +1431,14 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
     the loop the final observer state is written back into the memory dict;
     `LAST_RUN['feedback']` says 'resident' then and `LAST_RUN['feedback_y']`,
     `['feedback_u']` hold the outputs and inputs of the AB2 steps.
+    A `getbcs` that reads the state keeps the per-step path as well -- except
+    a `BoundaryFeedback` (without `dynamic_rhs` / `f_tvdp`, with `bcs_ini`
+    from its `init` call): the device advances its observer and writes the
+    controlled values into the convection operator's Dirichlet table, the
+    slices are tabulated for `u = 0`; `LAST_RUN['feedback']` says
+    'resident-boundary' and `['feedback_bcs']` holds the values of every
+    step.  `functionals`, `quadratics` and `rom` beside it are a
+    `ValueError` (their Dirichlet tables are host-made copies).
     Returns `v_n, p_n, ffflag` like the reference.
     """
     return _imex_loop(_CNAB, **locals())

@@ -463,6 +463,48 @@ int dns_imex_get_feedback_log(dns_imex *st, int32_t first, int32_t count,
                               double *y, double *u);
 /* back to open-loop steps */
 int dns_imex_clear_feedback(dns_imex *st);
+/* ---- boundary feedback: the observer drives controlled Dirichlet values ----
+ * Behind dns_imex_set_feedback (whose `bmat` may be empty: no actuation
+ * through the right-hand side): the same observer step, and
+ *     b(s+1) = base + S u_n                  S: nc x Nu CSR, base: nc (NULL: 0)
+ * written into the columns [col0, col0 + nc) of row s + 1 of the Dirichlet
+ * table of the attached convection operator (dns_conv_set_dbc_table, which
+ * needs nsteps + 1 rows: row 0 holds the values of the current state, the
+ * other columns and rows are the host's).  The front convection of step s
+ * reads row s, the convection of the new state row s + 1.
+ * `ba`, `bm` (NV x Nu), `bj` (NP x Nu): what `applybcs` makes of the unit
+ * controls S e_k (-A_bc, M_bc, -J_bc columns); all NULL: no boundary terms.
+ * With them the rows the host tabulated for u = 0 get what is linear in u:
+ *     geff  = g(s) + sum_{j = n, c, p} (wm[j] Bm + wa[j] Ba) u_j
+ *                  + dt (c_n B u_n + c_c B u_c)
+ *     gpeff = gp(s) + Bj u_n
+ * `wm`, `wa`: three weights each for u_n, u_c, u_p (CNAB: wm = (-1, 1, 0),
+ * wa = dt/2 (1, 1, 0); SBDF2: wm = (-1, 4/3, -1/3), wa = (2/3 dt, 0, 0)).
+ * Limits as dns_imex_set_feedback; refused (DNS_ERR_BAD_ARGUMENT) on a
+ * row-partitioned stepper, without a device convection operator, and for
+ * widths that do not fit; a step refuses a table with fewer than nsteps + 1
+ * rows, and functionals / quadratics beside it.  After this call the observer
+ * state is zero and no table is set. */
+int dns_imex_set_feedback_boundary(dns_imex *st, const dns_csr *smat,
+                                   const double *base, int32_t col0,
+                                   const dns_csr *ba, const dns_csr *bm,
+                                   const dns_csr *bj, const double *wm,
+                                   const double *wa);
+/* the observer state with u_p (Nu), the input one time before u_c */
+int dns_imex_set_feedback_state_bc(dns_imex *st, const double *hx,
+                                   const double *f_last, const double *u_c,
+                                   const double *u_p);
+/* the same, read back (any pointer may be NULL) */
+int dns_imex_get_feedback_state_bc(dns_imex *st, double *hx, double *f_last,
+                                   double *u_c, double *u_p);
+/* rows [first, first + count) of the controlled columns of the Dirichlet
+ * table as they stand on the device (count x nc): row s + 1 is what step s
+ * wrote */
+int dns_imex_get_feedback_bcs(dns_imex *st, int32_t first, int32_t count,
+                              double *bcs);
+/* the right-hand sides the last step read: geff (NV), gpeff (NP); either may
+ * be NULL; DNS_ERR_NOT_READY for one the step does not form */
+int dns_imex_get_feedback_rhs(dns_imex *st, double *geff, double *gpeff);
 /* ---- trajectory recorder of the explicit loops ----------------------------
  * While dns_imex_step / dns_imex_run step (and replay their graphs), one more
  * kernel per step writes down the trajectory on the device:
