@@ -129,32 +129,38 @@ struct dns_imex : dns::Ring {
     // the front kernels then read through g_ref().  The state slot that holds
     // the current hx / f_last / u_c is `tab_pos & 1`: the step counter selects
     // the slot, the drift row and the log row alike, so a restored batch
-    // (HostState::tab_pos, sync_counter) replays all three.
+    // (HostState::tab_pos, sync_counter) replays all three.  Present = on.
     struct Feedback {
-        bool on = false;
         int hN = 0, Ny = 0, Nu = 0;
         int rows = 0;              // drift rows = log capacity (0: no table yet)
         bool has_drift = false;
         double dt = 0.0, c_n = 0.0, c_c = 0.0;
         dns::CsrDev C, B;
+        // (geff: NV entries, in the boundary mode NV + NP -- gpeff lies behind
+        // it in ONE buffer: one entry of a checkpoint)
         dns::DevBuf<double> haT, hbT, hc, drift, state, ylog, ulog, geff;
         // boundary actuation (dns_imex_set_feedback_boundary): k_lti_bc_step
         // in the place of k_lti_step.  It also writes the controlled columns
         // [col0, col0 + nc) of row `counter + 1` of the convection operator's
-        // Dirichlet table, and the slot keeps u_p behind u_c.  `bc_rhs`: the
-        // boundary terms Ba, Bm, Bj were given; `has_b`: B has entries
-        bool bc = false, bc_rhs = false, has_b = true;
-        int nc = 0, col0 = 0;
-        dns::CsrDev S, Ba, Bm, Bj;
-        dns::DevBuf<double> base;
-        // (behind geff in ONE buffer of NV + NP: one entry of a checkpoint)
-        double *gpeff = nullptr;
-        double wm[3] = {0, 0, 0}, wa[3] = {0, 0, 0};
+        // Dirichlet table, and the slot keeps u_p behind u_c.  `rhs`: the
+        // boundary terms Ba, Bm, Bj were given (else they stay empty, their
+        // pointers null).  Present = boundary mode.
+        struct Boundary {
+            bool rhs = false;
+            int nc = 0, col0 = 0;
+            dns::CsrDev S, Ba, Bm, Bj;
+            dns::DevBuf<double> base;
+            double wm[3] = {0, 0, 0}, wa[3] = {0, 0, 0};
+        };
+        std::unique_ptr<Boundary> bc;
+        bool has_b() const { return B.nnz > 0; }
         int stride() const { return 2 * hN + Nu + (bc ? Nu : 0); }
         // does the step read geff / gpeff?
-        bool rhs_v() const { return !bc || bc_rhs || has_b; }
-        bool rhs_p() const { return bc && bc_rhs; }
-    } fb;
+        bool rhs_v() const { return !bc || bc->rhs || has_b(); }
+        bool rhs_p() const { return bc && bc->rhs; }
+        double *gpeff(int nv) const { return rhs_p() ? geff.p + nv : nullptr; }
+    };
+    std::unique_ptr<Feedback> fb;
     int fb_launch(hipStream_t s);  // k_lti_step / k_lti_bc_step for the step
                                    // about to run
     uint64_t fb_key() const;
@@ -290,7 +296,7 @@ struct dns_imex : dns::Ring {
     }
     // (with feedback: what k_lti_step has made of g_src() for this step)
     dns::TabRef g_ref() const {
-        if (fb.on && fb.rhs_v()) return {fb.geff.p, nullptr, 0, 1};
+        if (fb && fb->rhs_v()) return {fb->geff.p, nullptr, 0, 1};
         return g_src();
     }
     dns::TabRef gp_src() const {
@@ -300,7 +306,7 @@ struct dns_imex : dns::Ring {
     }
     // (with boundary feedback and its terms: what k_lti_bc_step has made of it)
     dns::TabRef gp_ref() const {
-        if (fb.on && fb.rhs_p()) return {fb.gpeff, nullptr, 0, 1};
+        if (fb && fb->rhs_p()) return {fb->gpeff(sys->nv), nullptr, 0, 1};
         return gp_src();
     }
     int sync_counter();            // device counter <- tab_pos

@@ -8,22 +8,22 @@
 // "feedback on", its shape, its coefficients and every buffer k_lti_step is
 // handed: a graph captured for another set must not be replayed
 uint64_t dns_imex::fb_key() const {
-    uint64_t k = mix64(0xfb, {kw(fb.hN), kw(fb.Ny), kw(fb.Nu), kw(fb.rows),
-                              kw(fb.has_drift), kw(fb.dt), kw(fb.c_n),
-                              kw(fb.c_c), kw(fb.C.vals.p), kw(fb.B.vals.p),
-                              kw(fb.haT.p), kw(fb.drift.p), kw(fb.state.p),
-                              kw(fb.ylog.p), kw(fb.ulog.p), kw(fb.geff.p),
-                              kw(g.p)});
-    if (!fb.bc) return k;
+    const Feedback &f = *fb;
+    uint64_t k = mix64(0xfb, {kw(f.hN), kw(f.Ny), kw(f.Nu), kw(f.rows),
+                              kw(f.has_drift), kw(f.dt), kw(f.c_n), kw(f.c_c),
+                              kw(f.C.vals.p), kw(f.B.vals.p), kw(f.haT.p),
+                              kw(f.drift.p), kw(f.state.p), kw(f.ylog.p),
+                              kw(f.ulog.p), kw(f.geff.p), kw(g.p)});
+    if (!f.bc) return k;
     // the boundary mode: its shape, weights and every further buffer
     // k_lti_bc_step is handed (the table itself is part of config_key)
-    k = mix64(k, {kw(0xbc), kw(fb.nc), kw(fb.col0), kw(fb.bc_rhs),
-                  kw(fb.has_b), kw(fb.S.vals.p), kw(fb.base.p),
-                  kw(fb.Ba.vals.p), kw(fb.Bm.vals.p), kw(fb.Bj.vals.p),
-                  kw(fb.gpeff), kw(gp.p)});
-    return mix64(k, {kw(fb.wm[0]), kw(fb.wm[1]), kw(fb.wm[2]), kw(fb.wa[0]),
-                     kw(fb.wa[1]), kw(fb.wa[2]),
-                     kw(conv ? conv->ndbc : 0)});
+    const Feedback::Boundary &b = *f.bc;
+    k = mix64(k, {kw(0xbc), kw(b.nc), kw(b.col0), kw(b.rhs), kw(f.has_b()),
+                  kw(b.S.vals.p), kw(b.base.p), kw(b.Ba.vals.p),
+                  kw(b.Bm.vals.p), kw(b.Bj.vals.p), kw(f.gpeff(sys->nv)),
+                  kw(gp.p)});
+    return mix64(k, {kw(b.wm[0]), kw(b.wm[1]), kw(b.wm[2]), kw(b.wa[0]),
+                     kw(b.wa[1]), kw(b.wa[2]), kw(conv ? conv->ndbc : 0)});
 }
 
 // "recorder on", its shape, every buffer k_record_step is handed and the
@@ -96,68 +96,46 @@ int dns_imex::fn_launch(hipStream_t s) {
     return DNS_OK;
 }
 
-int dns_imex::fb_launch(hipStream_t s) {
-    if (fb.rows < 1)
-        return dns::fail(DNS_ERR_NOT_READY, "observer feedback without a "
-                         "table (dns_imex_set_feedback_table)");
-    const dns::LtiArgs a{stepctr.p, fb.rows, fb.hN, fb.Ny, fb.Nu, sys->nv,
-                         fb.C.rowptr.p, fb.C.colidx.p, fb.C.vals.p,
-                         fb.B.rowptr.p, fb.B.colidx.p, fb.B.vals.p,
-                         fb.haT.p, fb.hbT.p, fb.hc.p,
-                         fb.has_drift ? fb.drift.p : (const double *)nullptr,
-                         fb.state.p, fb.ylog.p, fb.ulog.p, fb.dt, fb.c_n,
-                         fb.c_c, g_src(), xs[cur].p, fb.geff.p};
-    if (fb.bc) {
-        // (check_attachments has seen to the convection operator and its table)
-        dns::LtiBcArgs b{};
-        b.l = a;
-        if (!fb.has_b) b.l.brp = nullptr;
-        if (!fb.rhs_v()) b.l.geff = nullptr;
-        b.np = sys->np;
-        b.nc = fb.nc;
-        b.srp = fb.S.rowptr.p;
-        b.sci = fb.S.colidx.p;
-        b.sva = fb.S.vals.p;
-        b.base = fb.base.p;
-        b.dbc = conv->dbc_tab.p + fb.col0;
-        b.dbc_stride = std::max(1, conv->ndbc);
-        b.dbc_rows = conv->dbc_rows;
-        if (fb.bc_rhs) {
-            b.arp = fb.Ba.rowptr.p;
-            b.aci = fb.Ba.colidx.p;
-            b.ava = fb.Ba.vals.p;
-            b.mrp = fb.Bm.rowptr.p;
-            b.mci = fb.Bm.colidx.p;
-            b.mva = fb.Bm.vals.p;
-            b.jrp = fb.Bj.rowptr.p;
-            b.jci = fb.Bj.colidx.p;
-            b.jva = fb.Bj.vals.p;
-            b.gpeff = fb.gpeff;
-        }
-        b.wm_n = fb.wm[0];
-        b.wm_c = fb.wm[1];
-        b.wm_p = fb.wm[2];
-        b.wa_n = fb.wa[0];
-        b.wa_c = fb.wa[1];
-        b.wa_p = fb.wa[2];
-        b.gp = gp_src();
-        if (dns::lti_staged(fb.hN, fb.Ny, fb.Nu))
-            hipLaunchKernelGGL(dns::k_lti_bc_step<true>, dns::lti_grid(sys->nv),
-                               dns::kBlock, 0, s, b);
-        else
-            hipLaunchKernelGGL(dns::k_lti_bc_step<false>,
-                               dns::lti_grid(sys->nv), dns::kBlock, 0, s, b);
-        DNS_HIP(hipGetLastError());
-        return DNS_OK;
-    }
-    if (dns::lti_staged(fb.hN, fb.Ny, fb.Nu))
-        hipLaunchKernelGGL(dns::k_lti_step<true>, dns::lti_grid(sys->nv),
-                           dns::kBlock, 0, s, a);
-    else
-        hipLaunchKernelGGL(dns::k_lti_step<false>, dns::lti_grid(sys->nv),
-                           dns::kBlock, 0, s, a);
+// k_lti_step<STAGE> / k_lti_bc_step<STAGE> by the size of ha, hb, hc
+template <typename Args>
+static int lti_launch(void (*staged)(Args), void (*inplace)(Args),
+                      const Args &a, const dns::LtiArgs &l, hipStream_t s) {
+    hipLaunchKernelGGL(dns::lti_staged(l.hN, l.Ny, l.Nu) ? staged : inplace,
+                       dns::lti_grid(l.nv), dns::kBlock, 0, s, a);
     DNS_HIP(hipGetLastError());
     return DNS_OK;
+}
+
+int dns_imex::fb_launch(hipStream_t s) {
+    const Feedback &f = *fb;
+    if (f.rows < 1)
+        return dns::fail(DNS_ERR_NOT_READY, "observer feedback without a "
+                         "table (dns_imex_set_feedback_table)");
+    const dns::LtiArgs a{stepctr.p, f.rows, f.hN, f.Ny, f.Nu, sys->nv,
+                         f.C.rowptr.p, f.C.colidx.p, f.C.vals.p,
+                         f.B.rowptr.p, f.B.colidx.p, f.B.vals.p,
+                         f.haT.p, f.hbT.p, f.hc.p,
+                         f.has_drift ? f.drift.p : (const double *)nullptr,
+                         f.state.p, f.ylog.p, f.ulog.p, f.dt, f.c_n,
+                         f.c_c, g_src(), xs[cur].p, f.geff.p};
+    if (!f.bc)
+        return lti_launch(dns::k_lti_step<true>, dns::k_lti_step<false>, a, a,
+                          s);
+    // (check_attachments has seen to the convection operator and its table;
+    // Ba, Bm, Bj and gpeff are null without the boundary terms)
+    const Feedback::Boundary &c = *f.bc;
+    dns::LtiArgs l = a;
+    if (!f.has_b()) l.brp = nullptr;
+    if (!f.rhs_v()) l.geff = nullptr;
+    const dns::LtiBcArgs b{
+        l, sys->np, c.nc, c.S.rowptr.p, c.S.colidx.p, c.S.vals.p, c.base.p,
+        conv->dbc_tab.p + c.col0, std::max(1, conv->ndbc), conv->dbc_rows,
+        c.Ba.rowptr.p, c.Ba.colidx.p, c.Ba.vals.p, c.Bm.rowptr.p,
+        c.Bm.colidx.p, c.Bm.vals.p, c.Bj.rowptr.p, c.Bj.colidx.p, c.Bj.vals.p,
+        c.wm[0], c.wm[1], c.wm[2], c.wa[0], c.wa[1], c.wa[2], gp_src(),
+        f.gpeff(sys->nv)};
+    return lti_launch(dns::k_lti_bc_step<true>, dns::k_lti_bc_step<false>, b,
+                      b.l, s);
 }
 
 // "statistics on", their shape and grid, every buffer k_stats_step is handed
@@ -253,7 +231,7 @@ int dns_imex::ens_launch(hipStream_t s) {
 // side the front kernels read, the other five write down / add the row of
 // the step before.
 int dns_imex::launch_front_nodes(hipStream_t s) {
-    if (fb.on) DNS_TRY(fb_launch(s));
+    if (fb) DNS_TRY(fb_launch(s));
     if (rec) DNS_TRY(rec_launch(s));
     if (fn) DNS_TRY(fn_launch(s));
     if (stat) DNS_TRY(st_launch(s));
@@ -273,7 +251,7 @@ int dns_imex::launch_closing_nodes(hipStream_t s) {
 }
 
 uint64_t dns_imex::attachments_key(uint64_t k) const {
-    if (fb.on) k = mix64(k, {fb_key()});
+    if (fb) k = mix64(k, {fb_key()});
     if (rec) k = mix64(k, {rec_key()});
     if (fn) k = mix64(k, {fn_key()});
     if (stat) k = mix64(k, {st_key()});
@@ -283,14 +261,14 @@ uint64_t dns_imex::attachments_key(uint64_t k) const {
 }
 
 bool dns_imex::tables() const {
-    return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb.on || rec ||
+    return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb || rec ||
            fn || stat || qd || ens;
 }
 
 int dns_imex::rows_left() const {
     int lim = 1 << 30;
     if (tab_rows > 0) lim = std::min(lim, tab_rows);
-    if (fb.on) lim = std::min(lim, fb.rows);
+    if (fb) lim = std::min(lim, fb->rows);
     if (rec) lim = std::min(lim, rec->rows);
     if (fn) lim = std::min(lim, fn->rows);
     if (stat) lim = std::min(lim, stat->rows);
@@ -309,9 +287,9 @@ int dns_imex::rewind_tables() {
     if (stat)
         DNS_HIP(hipMemsetAsync(stat->acc.p, 0, stat->lay.G * sizeof(double),
                                sys->stream));
-    if (fb.on && (tab_pos & 1)) {
-        const size_t n = (size_t)fb.stride();
-        DNS_HIP(hipMemcpyAsync(fb.state.p, fb.state.p + n, n * sizeof(double),
+    if (fb && (tab_pos & 1)) {
+        const size_t n = (size_t)fb->stride();
+        DNS_HIP(hipMemcpyAsync(fb->state.p, fb->state.p + n, n * sizeof(double),
                                hipMemcpyDeviceToDevice, sys->stream));
     }
     tab_pos = 0;
@@ -352,26 +330,27 @@ static const char *const kQdMovingBc =
 
 // what a step refuses on their behalf
 int dns_imex::check_attachments() const {
-    if (fb.on) DNS_TRY(refuse_partitioned("observer feedback", kFbPartitioned));
-    if (fb.on && fb.bc) {
+    if (fb) DNS_TRY(refuse_partitioned("observer feedback", kFbPartitioned));
+    if (fb && fb->bc) {
+        const Feedback::Boundary &b = *fb->bc;
         // k_lti_bc_step writes row `counter + 1` of the operator's table
         if (!conv)
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
                              "boundary feedback needs the device convection "
                              "operator whose Dirichlet table it writes "
                              "(dns_imex_set_convection)");
-        if (fb.col0 + fb.nc > conv->ndbc)
+        if (b.col0 + b.nc > conv->ndbc)
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
                              "boundary feedback: the controlled columns "
                              "[%d, %d) do not fit the %d Dirichlet values of "
-                             "the convection operator", fb.col0,
-                             fb.col0 + fb.nc, conv->ndbc);
-        if (conv->dbc_rows < fb.rows + 1)
+                             "the convection operator", b.col0,
+                             b.col0 + b.nc, conv->ndbc);
+        if (conv->dbc_rows < fb->rows + 1)
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
                              "boundary feedback: the Dirichlet table has %d "
                              "rows, %d steps need %d (dns_conv_set_dbc_table; "
                              "row 0: the values of the current state)",
-                             conv->dbc_rows, fb.rows, fb.rows + 1);
+                             conv->dbc_rows, fb->rows, fb->rows + 1);
         if (fn || qd)
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
                              "boundary feedback with functionals / quadratics: "
@@ -624,6 +603,29 @@ static int set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
     return st->rewind_tables();
 }
 
+// The state slot of the current parity -- hx, f_last, u_c and (boundary mode)
+// u_p -- from the host (`P` const double *) or to it (double *); a null
+// pointer leaves its part out; complete on return.
+template <typename P>
+static int fb_state_copy(dns_imex *st, P hx, P f_last, P u_c, P u_p) {
+    constexpr bool up = std::is_const<std::remove_pointer_t<P>>::value;
+    const dns_imex::Feedback &f = *st->fb;
+    hipStream_t s = st->sys->stream;
+    if (up) DNS_HIP(hipStreamSynchronize(s));
+    double *slot = f.state.p + (size_t)(st->tab_pos & 1) * f.stride();
+    const P host[4] = {hx, f_last, u_c, u_p};
+    const int len[4] = {f.hN, f.hN, f.Nu, f.Nu};
+    for (int q = 0; q < 4; slot += len[q++]) {
+        if (!host[q]) continue;
+        if constexpr (up)
+            DNS_TRY(dns::upload_to(slot, host[q], (size_t)len[q], s));
+        else
+            DNS_TRY(dns::download_from(host[q], slot, (size_t)len[q], s));
+    }
+    if (!up) DNS_HIP(hipStreamSynchronize(s));
+    return DNS_OK;
+}
+
 extern "C" {
 
 // ---- observer feedback (feedback.hpp) --------------------------------------
@@ -659,13 +661,15 @@ int dns_imex_set_feedback(dns_imex *st, const dns_csr *cmat, const dns_csr *bmat
     if (!(dt > 0.0))
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "observer feedback: dt <= 0");
     DNS_HIP(hipSetDevice(h->device));
-    DNS_HIP(hipStreamSynchronize(h->stream));   // replays may still read it
-    dns_imex::Feedback &f = st->fb;
-    f.on = false;
-    f.bc = f.bc_rhs = false;       // (dns_imex_set_feedback_boundary follows)
-    f.has_b = true;
-    f.gpeff = nullptr;
     hipStream_t s = h->stream;
+    DNS_HIP(hipStreamSynchronize(s));           // replays may still read it
+    // A fresh one (the plain mode: dns_imex_set_feedback_boundary follows),
+    // moved in once nothing can fail any more; a `geff` that is large enough
+    // is taken over from the one that was there.
+    std::unique_ptr<dns_imex::Feedback> fp(new (std::nothrow)
+                                               dns_imex::Feedback());
+    if (!fp) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    dns_imex::Feedback &f = *fp;
     DNS_TRY(f.C.upload(cmat, s));
     DNS_TRY(f.B.upload(bmat, s));
     const size_t n = (size_t)hN;
@@ -683,22 +687,22 @@ int dns_imex_set_feedback(dns_imex *st, const dns_csr *cmat, const dns_csr *bmat
     f.hN = hN;
     f.Ny = Ny;
     f.Nu = Nu;
-    DNS_TRY(f.state.alloc((size_t)2 * f.stride()));
-    DNS_TRY(f.state.zero(s));
-    if (f.geff.n < (size_t)h->nv) DNS_TRY(f.geff.alloc((size_t)h->nv));
-    DNS_TRY(f.geff.zero(s));
-    f.rows = 0;
-    f.has_drift = false;
     f.dt = dt;
     f.c_n = c_n;
     f.c_c = c_c;
+    DNS_TRY(f.state.alloc((size_t)2 * f.stride()));
+    DNS_TRY(f.state.zero(s));
+    dns::DevBuf<double> &old = st->fb ? st->fb->geff : f.geff;
+    DNS_TRY(keep_or_alloc(f.geff, old, (size_t)h->nv));
+    DNS_TRY((f.geff.p ? f.geff : old).zero(s));
     DNS_HIP(hipStreamSynchronize(s));
-    f.on = true;
+    adopt(f.geff, old);
+    st->fb = std::move(fp);
     return DNS_OK;
 } DNS_CAPI_CATCH
 
 static int fb_need(dns_imex *st) {
-    return need(st, st && st->fb.on, "observer feedback is",
+    return need(st, st && st->fb, "observer feedback is",
                 "dns_imex_set_feedback");
 }
 
@@ -707,35 +711,20 @@ int dns_imex_set_feedback_state(dns_imex *st, const double *hx,
     DNS_TRY(fb_need(st));
     if (!hx || !f_last || !u_c)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
-    dns_imex::Feedback &f = st->fb;
-    hipStream_t s = st->sys->stream;
-    DNS_HIP(hipStreamSynchronize(s));
-    double *slot = f.state.p + (size_t)(st->tab_pos & 1) * f.stride();
-    DNS_TRY(dns::upload_to(slot, hx, (size_t)f.hN, s));
-    DNS_TRY(dns::upload_to(slot + f.hN, f_last, (size_t)f.hN, s));
-    DNS_TRY(dns::upload_to(slot + 2 * f.hN, u_c, (size_t)f.Nu, s));
-    return DNS_OK;
+    return fb_state_copy(st, hx, f_last, u_c, (const double *)nullptr);
 } DNS_CAPI_CATCH
 
 int dns_imex_get_feedback_state(dns_imex *st, double *hx, double *f_last,
                                 double *u_c) try {
     DNS_TRY(fb_need(st));
-    const dns_imex::Feedback &f = st->fb;
-    hipStream_t s = st->sys->stream;
-    const double *slot = f.state.p + (size_t)(st->tab_pos & 1) * f.stride();
-    if (hx) DNS_TRY(dns::download_from(hx, slot, (size_t)f.hN, s));
-    if (f_last)
-        DNS_TRY(dns::download_from(f_last, slot + f.hN, (size_t)f.hN, s));
-    if (u_c) DNS_TRY(dns::download_from(u_c, slot + 2 * f.hN, (size_t)f.Nu, s));
-    DNS_HIP(hipStreamSynchronize(s));
-    return DNS_OK;
+    return fb_state_copy(st, hx, f_last, u_c, (double *)nullptr);
 } DNS_CAPI_CATCH
 
 int dns_imex_set_feedback_table(dns_imex *st, int32_t nsteps,
                                 const double *drift) try {
     DNS_TRY(fb_need(st));
     if (nsteps < 1) return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
-    dns_imex::Feedback &f = st->fb;
+    dns_imex::Feedback &f = *st->fb;
     dns_saddle *h = st->sys;
     hipStream_t s = h->stream;
     DNS_HIP(hipStreamSynchronize(s));           // replays may still read it
@@ -756,7 +745,7 @@ int dns_imex_set_feedback_table(dns_imex *st, int32_t nsteps,
 int dns_imex_get_feedback_log(dns_imex *st, int32_t first, int32_t count,
                               double *y, double *u) try {
     DNS_TRY(fb_need(st));
-    const dns_imex::Feedback &f = st->fb;
+    const dns_imex::Feedback &f = *st->fb;
     DNS_TRY(download_log_rows(st, y, f.ylog.p, first, count, (size_t)f.Ny,
                               f.rows, "log rows", "table"));
     return download_log_rows(st, u, f.ulog.p, first, count, (size_t)f.Nu,
@@ -765,17 +754,14 @@ int dns_imex_get_feedback_log(dns_imex *st, int32_t first, int32_t count,
 
 int dns_imex_clear_feedback(dns_imex *st) try {
     DNS_TRY(quiesce(st));
-    st->fb.on = false;
-    st->fb.bc = st->fb.bc_rhs = false;
-    st->fb.gpeff = nullptr;
-    st->fb.rows = 0;
+    st->fb.reset();
     return DNS_OK;
 } DNS_CAPI_CATCH
 
 // ---- boundary feedback (k_lti_bc_step) -------------------------------------
 
 static int fbc_need(dns_imex *st) {
-    return need(st, st && st->fb.on && st->fb.bc, "boundary feedback is",
+    return need(st, st && st->fb && st->fb->bc, "boundary feedback is",
                 "dns_imex_set_feedback_boundary");
 }
 
@@ -786,12 +772,12 @@ int dns_imex_set_feedback_boundary(dns_imex *st, const dns_csr *smat,
                                    const double *wa) try {
     if (!st || !smat || !wm || !wa)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
-    // every check first: a refusal leaves the feedback as dns_imex_set_feedback
+    // a refusal, or a failure, leaves the feedback as dns_imex_set_feedback
     // left it
     DNS_TRY(st->refuse_partitioned("boundary feedback", kFbPartitioned));
     DNS_TRY(fb_need(st));
     dns_saddle *h = st->sys;
-    dns_imex::Feedback &f = st->fb;
+    dns_imex::Feedback &f = *st->fb;
     if (!st->conv)
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "boundary feedback needs a device convection operator: "
@@ -831,37 +817,42 @@ int dns_imex_set_feedback_boundary(dns_imex *st, const dns_csr *smat,
     DNS_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     DNS_HIP(hipStreamSynchronize(s));           // replays may still read it
-    f.on = false;
-    DNS_TRY(f.S.upload(smat, s));
+    std::unique_ptr<dns_imex::Feedback::Boundary> b(
+        new (std::nothrow) dns_imex::Feedback::Boundary());
+    if (!b) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
+    DNS_TRY(b->S.upload(smat, s));
     std::vector<double> b0((size_t)nc, 0.0);
     if (base) b0.assign(base, base + nc);
-    DNS_TRY(f.base.alloc((size_t)nc));
-    DNS_TRY(f.base.upload(b0.data(), (size_t)nc, s));
+    DNS_TRY(b->base.alloc((size_t)nc));
+    DNS_TRY(b->base.upload(b0.data(), (size_t)nc, s));
     if (rhs) {
-        DNS_TRY(f.Ba.upload(ba, s));
-        DNS_TRY(f.Bm.upload(bm, s));
-        DNS_TRY(f.Bj.upload(bj, s));
+        DNS_TRY(b->Ba.upload(ba, s));
+        DNS_TRY(b->Bm.upload(bm, s));
+        DNS_TRY(b->Bj.upload(bj, s));
     }
-    // geff and gpeff in one buffer; the slots get room for u_p
-    const size_t ng = (size_t)h->nv + (size_t)std::max(1, h->np);
-    if (f.geff.n < ng) DNS_TRY(f.geff.alloc(ng));
-    DNS_TRY(f.geff.zero(s));
-    f.bc = true;
-    f.bc_rhs = rhs;
-    f.has_b = f.B.nnz > 0;
-    f.gpeff = rhs ? f.geff.p + h->nv : nullptr;
-    f.nc = nc;
-    f.col0 = col0;
+    b->rhs = rhs;
+    b->nc = nc;
+    b->col0 = col0;
     for (int j = 0; j < 3; ++j) {
-        f.wm[j] = wm[j];
-        f.wa[j] = wa[j];
+        b->wm[j] = wm[j];
+        b->wa[j] = wa[j];
     }
-    DNS_TRY(f.state.alloc((size_t)2 * f.stride()));
-    DNS_TRY(f.state.zero(s));
+    // geff and gpeff in one buffer; the slots get room for u_p: fresh
+    // buffers, which take the others' place once nothing can fail any more
+    dns::DevBuf<double> geff, state;
+    DNS_TRY(keep_or_alloc(geff, f.geff,
+                          (size_t)h->nv + (size_t)std::max(1, h->np)));
+    DNS_TRY((geff.p ? geff : f.geff).zero(s));
+    DNS_TRY(state.alloc((size_t)4 * (f.hN + f.Nu)));
+    DNS_TRY(state.zero(s));
+    DNS_HIP(hipStreamSynchronize(s));
+    if (geff.p) f.geff.release();               // (else: kept)
+    adopt(f.geff, geff);
+    f.state.release();
+    adopt(f.state, state);
+    f.bc = std::move(b);
     f.rows = 0;                                 // the table follows
     f.has_drift = false;
-    DNS_HIP(hipStreamSynchronize(s));
-    f.on = true;
     return DNS_OK;
 } DNS_CAPI_CATCH
 
@@ -871,52 +862,33 @@ int dns_imex_set_feedback_state_bc(dns_imex *st, const double *hx,
     DNS_TRY(fbc_need(st));
     if (!hx || !f_last || !u_c || !u_p)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
-    dns_imex::Feedback &f = st->fb;
-    hipStream_t s = st->sys->stream;
-    DNS_HIP(hipStreamSynchronize(s));
-    double *slot = f.state.p + (size_t)(st->tab_pos & 1) * f.stride();
-    DNS_TRY(dns::upload_to(slot, hx, (size_t)f.hN, s));
-    DNS_TRY(dns::upload_to(slot + f.hN, f_last, (size_t)f.hN, s));
-    DNS_TRY(dns::upload_to(slot + 2 * f.hN, u_c, (size_t)f.Nu, s));
-    DNS_TRY(dns::upload_to(slot + 2 * f.hN + f.Nu, u_p, (size_t)f.Nu, s));
-    return DNS_OK;
+    return fb_state_copy(st, hx, f_last, u_c, u_p);
 } DNS_CAPI_CATCH
 
 int dns_imex_get_feedback_state_bc(dns_imex *st, double *hx, double *f_last,
                                    double *u_c, double *u_p) try {
     DNS_TRY(fbc_need(st));
-    const dns_imex::Feedback &f = st->fb;
-    hipStream_t s = st->sys->stream;
-    const double *slot = f.state.p + (size_t)(st->tab_pos & 1) * f.stride();
-    if (hx) DNS_TRY(dns::download_from(hx, slot, (size_t)f.hN, s));
-    if (f_last)
-        DNS_TRY(dns::download_from(f_last, slot + f.hN, (size_t)f.hN, s));
-    if (u_c) DNS_TRY(dns::download_from(u_c, slot + 2 * f.hN, (size_t)f.Nu, s));
-    if (u_p)
-        DNS_TRY(dns::download_from(u_p, slot + 2 * f.hN + f.Nu, (size_t)f.Nu,
-                                   s));
-    DNS_HIP(hipStreamSynchronize(s));
-    return DNS_OK;
+    return fb_state_copy(st, hx, f_last, u_c, u_p);
 } DNS_CAPI_CATCH
 
 int dns_imex_get_feedback_bcs(dns_imex *st, int32_t first, int32_t count,
                               double *bcs) try {
     DNS_TRY(fbc_need(st));
-    const dns_imex::Feedback &f = st->fb;
+    const dns_imex::Feedback::Boundary &b = *st->fb->bc;
     const dns_conv *cv = st->conv;
     if (!bcs) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
-    if (!cv || cv->dbc_rows < 1 || f.col0 + f.nc > cv->ndbc)
+    if (!cv || cv->dbc_rows < 1 || b.col0 + b.nc > cv->ndbc)
         return dns::fail(DNS_ERR_NOT_READY,
                          "boundary feedback: no Dirichlet table of that width "
                          "on the convection operator (dns_conv_set_dbc_table)");
-    return download_log_rows(st, bcs, cv->dbc_tab.p + f.col0, first, count,
-                             (size_t)f.nc, cv->dbc_rows, "table rows",
+    return download_log_rows(st, bcs, cv->dbc_tab.p + b.col0, first, count,
+                             (size_t)b.nc, cv->dbc_rows, "table rows",
                              "Dirichlet table", (size_t)std::max(1, cv->ndbc));
 } DNS_CAPI_CATCH
 
 int dns_imex_get_feedback_rhs(dns_imex *st, double *geff, double *gpeff) try {
     DNS_TRY(fbc_need(st));
-    const dns_imex::Feedback &f = st->fb;
+    const dns_imex::Feedback &f = *st->fb;
     const dns_saddle *h = st->sys;
     if ((geff && !f.rhs_v()) || (gpeff && !f.rhs_p()))
         return dns::fail(DNS_ERR_NOT_READY,
@@ -924,7 +896,8 @@ int dns_imex_get_feedback_rhs(dns_imex *st, double *geff, double *gpeff) try {
                          "side: the step reads the tabulated rows");
     hipStream_t s = h->stream;
     if (geff) DNS_TRY(dns::download_from(geff, f.geff.p, (size_t)h->nv, s));
-    if (gpeff) DNS_TRY(dns::download_from(gpeff, f.gpeff, (size_t)h->np, s));
+    if (gpeff)
+        DNS_TRY(dns::download_from(gpeff, f.gpeff(h->nv), (size_t)h->np, s));
     DNS_HIP(hipStreamSynchronize(s));
     return DNS_OK;
 } DNS_CAPI_CATCH

@@ -845,11 +845,11 @@ int ImexRun::run_batch() {
     // observer feedback: both slots of the state and the right-hand side it
     // left (the slot, the drift row and the log row come back with the step
     // counter; the log rows of a discarded batch are overwritten)
-    if (st->fb.on) {
-        DNS_TRY(ck.add(st->fb.state.p, (size_t)2 * st->fb.stride()));
+    if (st->fb) {
+        DNS_TRY(ck.add(st->fb->state.p, (size_t)2 * st->fb->stride()));
         // (boundary feedback: gpeff lies behind geff)
-        DNS_TRY(ck.add(st->fb.geff.p,
-                       (size_t)h->nv + (st->fb.gpeff ? (size_t)h->np : 0)));
+        DNS_TRY(ck.add(st->fb->geff.p,
+                       (size_t)h->nv + (st->fb->rhs_p() ? (size_t)h->np : 0)));
     }
     // flow statistics: the sums AND the workgroups' marks -- a restored batch
     // adds its rows again, to the sums the batch started from (a checkpoint

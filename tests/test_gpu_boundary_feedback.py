@@ -246,6 +246,69 @@ def test_bc_kernel_against_its_definition(gtiu, toy_prob, hN, Nu, weights,
         lp.close()
 
 
+@pytest.mark.parametrize('hN,Nu', [(1, 2), (13, 2), (128, 2)])
+def test_bc_observer_step_has_the_plain_kernels_bits(gtiu, toy_prob, hN, Nu):
+    """`k_lti_bc_step` and `k_lti_step` share one observer step: two steppers
+    on one system, the same state, tables, sensors, observer and drift; the
+    boundary mode literal, without `B`, with an `S` of zeros (every Dirichlet
+    row it writes is `base`), the plain mode with an empty `B` and the same
+    constant Dirichlet table.  Four steps, one `run(1)` each: `y`, `u`, `hx`,
+    `f_last`, `u_c` are the same bits, `u_p` is the `u_c` of the step before.
+    (hN = 1: one half of `ha hx` is empty; 13: odd, staged in LDS; 128: read
+    in place, the slots 258 and 260 entries long)
+
+    The velocities of the two loops are NOT bit equal throughout -- measured
+    on the MI355X, before the two kernels shared their code as after: equal
+    after the steps 0, 1, 2, different after step 3 in all three cases (why
+    is not established: the one loop's steps read `g` from the table row, the
+    other's the same values from `geff`).  So the observer quantities of the
+    first step are
+    always compared (`v` is the same by construction), those of a later step
+    only while the `v` it read was bit equal; nothing is compared within a
+    tolerance."""
+    from dolfin_navier_scipy_amd import saddle
+    bc = ToyBcLoop(toy_prob, hN=hN, Nu=Nu, literal=True, nst=4, setup=False)
+    bc.S = sps.csr_matrix((np.zeros(bc.S.nnz), bc.S.indices, bc.S.indptr),
+                          shape=bc.S.shape)
+    M, A = (toy_prob['smc'][k] for k in 'MA')
+    stp = saddle.ImexStepper(bc.system, (M - .5*bc.dt*A).tocsr())
+    cvop, _ = bs.toy_cvop(toy_prob)
+    try:
+        obs = bc.obs
+        assert bc.B.nnz == 0 and bc.terms is None and obs['hb'].shape[1] == 3
+        stp.set_state(bc.stp.get_state()[0])
+        stp.set_convection(cvop, scale=-1.0)
+        bc.arm()
+        stp.set_feedback(bc.C, sps.csr_matrix((bc.NV, Nu)), obs['ha'],
+                         obs['hb'], obs['hc'], c_n=.5, c_c=.5, dt=bc.dt)
+        stp.set_feedback_state(bc.hx, bc.fl, bc.uc)
+        stp.set_rhs_table(bc.gtab, bc.gptab)
+        assert np.array_equal(bc.tab[0], bc.tab[1])
+        cvop.set_dbc_table(bc.tab)
+        stp.set_feedback_table(bc.nst, bc.drift)
+        uc, same_v = bc.uc, True
+        for k in range(bc.nst):
+            bc.run(1)
+            stp.run(1, bc.cf, bc.opts)
+            ghx, gfl, guc, gup = bc.stp.feedback_state_bc()
+            assert np.array_equal(gup, uc), k
+            uc = guc
+            assert np.array_equal(bc.stp.feedback_bcs(k + 1, 1)[0], bc.base)
+            if not same_v:
+                continue
+            for a, b in zip(bc.stp.feedback_log(k, 1), stp.feedback_log(k, 1)):
+                assert np.array_equal(a, b), k
+            for a, b in zip((ghx, gfl, guc), stp.feedback_state()):
+                assert np.array_equal(a, b), k
+            same_v = np.array_equal(bc.stp.get_state()[0], stp.get_state()[0])
+            print(hN, 'step', k, 'observer bit equal; v after it:', same_v)
+        assert np.abs(uc).max() > 0
+    finally:
+        stp.close()
+        cvop.close()
+        bc.close()
+
+
 # ---- 2. zero gain ---------------------------------------------------------------
 
 @pytest.mark.parametrize('scheme,literal', [('cnab', False), ('sbdf2', False),
@@ -563,6 +626,56 @@ def test_limits_and_refusals_are_loud(gtiu, toy_prob):
     finally:
         lp.close()
         ref.close()
+
+
+def test_a_refused_boundary_leaves_the_plain_feedback_working(gtiu, toy_prob):
+    """`dns_imex_set_feedback_boundary` refuses an `S` of the wrong width and
+    `Ba` without `Bm` (both past the wrapper's own checks): the feedback stays
+    as `set_feedback` left it -- the state that was set, and a step that runs"""
+    from dolfin_navier_scipy_amd import _capi
+    lp = ToyBcLoop(toy_prob, Nu=2, nst=2, with_b=True, setup=False)
+    try:
+        stp, obs = lp.stp, lp.obs
+        stp.set_feedback(lp.C, lp.B, obs['ha'], obs['hb'], obs['hc'], c_n=.5,
+                         c_c=.5, dt=lp.dt)
+        stp.set_feedback_state(lp.hx, lp.fl, lp.uc)
+        shape, col0 = stp._fb_shape, len(lp.statvals)
+        stp._fb_shape = shape[:2] + (3,)            # (the wrapper lets it by)
+        with pytest.raises(_capi.DnsError) as exc:
+            stp.set_feedback_boundary(bs.shape_matrix(lp.base, 3), lp.base,
+                                      col0=col0)
+        stp._fb_shape = shape
+        assert exc.value.status == _capi.DNS_ERR_BAD_ARGUMENT
+        assert 'S must be nc x Nu' in str(exc.value)
+        Ba = lp.terms[0]
+        sview, aview = _capi.CsrView(lp.S), _capi.CsrView(Ba)
+        w = _capi.as_f64((0., 0., 0.), 3)
+        with pytest.raises(_capi.DnsError) as exc:
+            _capi.check(stp.lib.dns_imex_set_feedback_boundary(
+                stp._h, sview.byref(), _capi.dptr(lp.base), col0,
+                aview.byref(), None, None, _capi.dptr(w), _capi.dptr(w)))
+        assert exc.value.status == _capi.DNS_ERR_BAD_ARGUMENT
+        assert 'come together' in str(exc.value)
+        # still the plain feedback: no boundary mode, the state as it was set
+        with pytest.raises(_capi.DnsError) as exc:
+            stp.feedback_state_bc()
+        assert exc.value.status == _capi.DNS_ERR_NOT_READY
+        want = (lp.hx, lp.fl, lp.uc)
+        assert all(np.array_equal(a, b)
+                   for a, b in zip(stp.feedback_state(), want))
+        stp.set_rhs_table(lp.gtab, lp.gptab)
+        stp.set_feedback_table(lp.nst, lp.drift)
+        assert all(np.array_equal(a, b)
+                   for a, b in zip(stp.feedback_state(), want))
+        lp.run(1)
+        assert stp.table_position()[0] == 1
+        y, u = stp.feedback_log(0, 1)
+        v = lp.stp.get_state()[0]
+        assert np.all(np.isfinite(y)) and np.all(np.isfinite(u))
+        assert np.all(np.isfinite(v))
+        assert np.array_equal(stp.feedback_state()[2], u[0])
+    finally:
+        lp.close()
 
 
 def test_a_row_partitioned_stepper_is_refused(gtiu, toy_prob):
