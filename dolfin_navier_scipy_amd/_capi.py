@@ -109,6 +109,17 @@ class dns_trap_probe(ct.Structure):
                 ('fused', ct.c_int32), ('pad', ct.c_int32)]
 
 
+class dns_imex_probe(ct.Structure):
+    _fields_ = [(k, c_double_p) for k in
+                ('ring', 'nfc_in', 'g_in', 'gp_in', 'b_prev', 'kxs_in',
+                 'rcarry_in', 'rc6_in', 'x0_other', 'x0', 'b', 'nfc_out',
+                 'kx', 'r', 'partR', 'partB', 'kxs_cur', 'rcarry_out')] + \
+               [(k, ct.c_int32) for k in
+                ('parts_cap', 'nsol', 'tab_row', 'has_carry', 'has_six',
+                 'form', 'mode', 'use_pre', 'carry', 'k_lpr', 'r1_lpr',
+                 'nparts', 'r1_pair', 'pad')]
+
+
 # every symbol include/dns_amd.h declares: name -> (restype, argtypes)
 _VP = ct.c_void_p
 ALLREDUCE_CB = ct.CFUNCTYPE(ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_int32)
@@ -193,6 +204,10 @@ SIGNATURES = {
                                 ct.POINTER(ct.c_int64)]),
     'dns_imex_get_state': (ct.c_int, [_VP, c_double_p, c_double_p]),
     'dns_imex_vnorm': (ct.c_int, [_VP, c_double_p]),
+    'dns_imex_front_probe': (ct.c_int, [_VP, ct.POINTER(dns_imex_coeffs),
+                                        ct.POINTER(dns_solve_opts),
+                                        ct.c_int32, c_double_p,
+                                        ct.POINTER(dns_imex_probe)]),
     'dns_imex_set_feedback': (ct.c_int, [_VP, ct.POINTER(dns_csr),
                                          ct.POINTER(dns_csr), c_double_p,
                                          c_double_p, c_double_p, ct.c_int32,

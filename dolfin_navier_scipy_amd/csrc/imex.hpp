@@ -391,4 +391,15 @@ struct dns_imex : dns::Ring {
     dns::StepHooks hooks(const dns_imex_coeffs *cf, const StepPlan &pl);
     int step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
                     dns_solve_stats *st, bool with_true_residual);
+    // what dns_imex_step does before step_device: its refusals, the upload of
+    // the caller's convection vector, the products of a carry step
+    int step_refusals(const double *nfc_new) const;
+    int step_preamble(const double *nfc_new, const dns_imex_coeffs *cf,
+                      const dns_solve_opts &o);
+    void turn_convection();
+    // dns_imex_front_probe (TEST ONLY) has run a front without its solve: the
+    // convection slot and the carry buffers are those of a step that never
+    // finished.  dns_imex_set_state starts over.
+    bool probed = false;
+    int refuse_probed() const;
 };

@@ -256,8 +256,9 @@ int dns_imex::front_rows(const dns_imex_coeffs *cf, const StepPlan &pl) {
                            rv1 - rv0, h->np, R1.rowptr.p, R1.colidx.p,
                            R1.vals.p, xs[cur].p,
                            (nsol >= 2) ? xs[prev].p : xs[cur].p, cf->a_c,
-                           cf->a_p, nfc[nc].p, nfc[no].p, cf->cn_c, cf->cn_o,
-                           g_ref(), gp_ref(), b.p, rv0, h->nv, rp0, rp1));
+                           (nsol >= 2) ? cf->a_p : 0.0, nfc[nc].p, nfc[no].p,
+                           cf->cn_c, cf->cn_o, g_ref(), gp_ref(), b.p, rv0,
+                           h->nv, rp0, rp1));
     return warm_start(cf, pl);
 }
 
@@ -359,13 +360,20 @@ dns::StepHooks dns_imex::hooks(const dns_imex_coeffs *cf, const StepPlan &pl) {
     return hk;
 }
 
+// device convection: the old nfc_c becomes nfc_o, the new one is evaluated
+// from the current velocity inside the step's graph, with the Dirichlet row
+// the device counter selects (step_device; dns_imex_front_probe)
+void dns_imex::turn_convection() {
+    if (!conv) return;
+    std::swap(nc, no);
+    conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
+}
+
 int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
                           dns_solve_stats *st, bool with_true_residual) {
     dns_saddle *h = sys;
     double *x = xs[work].p;
-    // device convection: the old nfc_c becomes nfc_o, the new one is
-    // evaluated from the current velocity inside the step's graph
-    if (conv) std::swap(nc, no);
+    turn_convection();
     if (!h->precond_ready)
         return dns::fail(DNS_ERR_NOT_READY, "preconditioner not set up");
     // (a step that has to cut the stepper's row blocks first neither trusts
@@ -392,7 +400,6 @@ int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
                              "dns_imex_set_ensemble)",
                              tab_pos);
     }
-    if (conv) conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
     const int next_nsol = std::min(nsol + 1, 5);
     if (o->method == DNS_METHOD_GMRES) {
         const dns::StepHooks hk = hooks(cf, pl);
@@ -1000,6 +1007,45 @@ int ImexRun::finish_run(double *device_seconds, int64_t *total_iters) {
     return DNS_OK;
 }
 
+int dns_imex::refuse_probed() const {
+    if (!probed) return DNS_OK;
+    return dns::fail(DNS_ERR_NOT_READY,
+                     "dns_imex_front_probe has run the front of a step without "
+                     "its solve: dns_imex_set_state before the stepper steps "
+                     "again");
+}
+
+// what dns_imex_step refuses before anything is touched
+int dns_imex::step_refusals(const double *nfc_new) const {
+    if (nfc_new && conv)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "a device convection operator is attached: the "
+                         "convection vector must not be supplied by the host");
+    // (refused before the convection history is touched: the stepper stays
+    // as it was)
+    if (tables() && rows_left() < 1)
+        return dns::fail(DNS_ERR_NOT_READY,
+                         "the per-step tables are used up after %d steps: "
+                         "upload the next ones (dns_imex_set_rhs_table / ... / "
+                         "dns_imex_set_functionals / dns_imex_set_quadratics)",
+                         tab_pos);
+    return check_attachments();
+}
+
+int dns_imex::step_preamble(const double *nfc_new, const dns_imex_coeffs *cf,
+                            const dns_solve_opts &o) {
+    dns_saddle *h = sys;
+    DNS_TRY(step_refusals(nfc_new));
+    if (nfc_new) {
+        std::swap(nc, no);
+        DNS_TRY(nfc[nc].upload(nfc_new, (size_t)h->nv, h->stream));
+    }
+    if (cf->carry_residual && !carry_ok && pre_ok && nsol >= 5 &&
+        o.method == DNS_METHOD_GMRES)
+        DNS_TRY(prime_carry(true));
+    return DNS_OK;
+}
+
 extern "C" {
 
 // both creates: `r1` is all of R1, or with `by_rows` this rank's rows of it
@@ -1107,6 +1153,7 @@ int dns_imex_set_state(dns_imex *st, const double *v_c, const double *v_p,
     st->carry_ok = false;
     st->six_ok = false;
     st->dcells_ok = false;
+    st->probed = false;
     st->part.state_full = true;
     if (v_p) {
         DNS_TRY(st->xs[1].upload(v_p, (size_t)h->nv, s));
@@ -1182,26 +1229,8 @@ int dns_imex_step(dns_imex *st, const double *nfc_new,
     dns_solve_stats local;
     dns_solve_stats *sp = stats ? stats : &local;
     memset(sp, 0, sizeof(*sp));
-    if (nfc_new && st->conv)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "a device convection operator is attached: the "
-                         "convection vector must not be supplied by the host");
-    // (refused before the convection history is touched: the stepper stays
-    // as it was)
-    if (st->tables() && st->rows_left() < 1)
-        return dns::fail(DNS_ERR_NOT_READY,
-                         "the per-step tables are used up after %d steps: "
-                         "upload the next ones (dns_imex_set_rhs_table / ... / "
-                         "dns_imex_set_functionals / dns_imex_set_quadratics)",
-                         st->tab_pos);
-    DNS_TRY(st->check_attachments());
-    if (nfc_new) {
-        std::swap(st->nc, st->no);
-        DNS_TRY(st->nfc[st->nc].upload(nfc_new, (size_t)h->nv, h->stream));
-    }
-    if (cf->carry_residual && !st->carry_ok && st->pre_ok && st->nsol >= 5 &&
-        o.method == DNS_METHOD_GMRES)
-        DNS_TRY(st->prime_carry(true));
+    DNS_TRY(st->refuse_probed());
+    DNS_TRY(st->step_preamble(nfc_new, cf, o));
     // nobody reads the history per time step (scripts/extrap_probe.py does)
     h->want_history = st->env_step_history;
     const int src = st->step_device(cf, &o, sp, true);
@@ -1227,6 +1256,7 @@ int dns_imex_run(dns_imex *st, int32_t nsteps, const dns_imex_coeffs *cf,
     dns_solve_stats local;
     ImexRun r{st, h, cf, nsteps, last_stats ? last_stats : &local, o, o};
     memset(r.sp, 0, sizeof(*r.sp));
+    DNS_TRY(st->refuse_probed());
     if (st->tables() && st->rows_left() < nsteps)
         return dns::fail(DNS_ERR_NOT_READY,
                          "%d steps asked for, the per-step tables hold %d more "
@@ -1321,6 +1351,141 @@ int dns_imex_vnorm(dns_imex *st, double *out) try {
     DNS_TRY(st->gather_state());
     DNS_TRY(h->dot_host(h->nv, st->xs[st->cur].p, st->xs[st->cur].p, &s2));
     *out = std::sqrt(s2);
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// TEST ONLY: the front of a step -- what dns_imex_step does before
+// step_device (step_preamble), then the member function prologue() would pick
+// for the plan (front_six / front_fused / front_rows / front_stream), without
+// the attachments' nodes and without a solve -- with a copy out of what the
+// front reads before it runs and of what it has left.  The stepper is consumed.
+int dns_imex_front_probe(dns_imex *st, const dns_imex_coeffs *cf,
+                         const dns_solve_opts *opts, int32_t cycle_len,
+                         const double *nfc_new, dns_imex_probe *out) try {
+    if (!st || !cf || !out || cycle_len < 0 || out->parts_cap < 0)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
+    dns_saddle *h = st->sys;
+    // (a communicator attached: partitioned at the next set-up at the latest)
+    if (h->comm || h->dist() || h->dist_sliced || h->rank_local || st->part.on)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "the front probe takes an un-partitioned handle");
+    if (st->fb || st->rec || st->fn || st->stat || st->qd || st->ens)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "the front probe takes a stepper without attachments "
+                         "(feedback, recorder, functionals, statistics, "
+                         "quadratics, ensemble)");
+    if (h->pipeline_c > 0 || st->preparing)
+        return dns::fail(DNS_ERR_NOT_READY,
+                         "the front probe: a pipelined batch is pending");
+    DNS_TRY(st->refuse_probed());
+    if (!h->precond_ready)
+        return dns::fail(DNS_ERR_NOT_READY, "preconditioner not set up");
+    DNS_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    dns_solve_opts o;
+    if (opts)
+        o = *opts;
+    else
+        dns_default_solve_opts(&o);
+    // (the refusals of the step itself; from the first touch on the stepper
+    // counts as consumed, whatever fails behind)
+    DNS_TRY(st->step_refusals(nfc_new));
+    st->probed = true;
+    DNS_TRY(st->step_preamble(nfc_new, cf, o));
+    // (from here on as step_device: the turn of a device convection, the plan)
+    st->turn_convection();
+    const StepPlan pl = st->plan(cf, &o, cycle_len);
+    const bool six = pl.form == StepPlan::Six;
+    const size_t n = (size_t)h->n, nv = (size_t)h->nv, np = (size_t)h->np;
+    const int par = st->work & 1;
+    // ---- what the front will read
+    out->nsol = st->nsol;
+    out->has_carry = pl.carry ? 1 : 0;
+    out->has_six = six ? 1 : 0;
+    int ctr = 0;
+    if (st->tables()) DNS_TRY(st->stepctr.download(&ctr, 1, s));
+    DNS_HIP(hipStreamSynchronize(s));
+    out->tab_row = ctr;
+    auto row_of = [&](const dns::TabRef &t) {
+        if (!t.ctr) return t.base;
+        const int r = ctr < 0 ? 0 : (ctr >= t.rows ? t.rows - 1 : ctr);
+        return t.base + (size_t)r * t.stride;
+    };
+    const int ring[5] = {st->cur, st->prev, st->pprev, st->p3, st->p4};
+    if (out->ring)
+        for (int q = 0; q < 5; ++q)
+            DNS_TRY(st->xs[ring[q]].download(out->ring + q * n, n, s));
+    if (out->nfc_in) {
+        DNS_TRY(st->nfc[st->nc].download(out->nfc_in, nv, s));
+        DNS_TRY(st->nfc[st->no].download(out->nfc_in + nv, nv, s));
+    }
+    if (out->g_in)
+        DNS_TRY(dns::download_from(out->g_in, row_of(st->g_ref()), nv, s));
+    if (out->gp_in && np)
+        DNS_TRY(dns::download_from(out->gp_in, row_of(st->gp_ref()), np, s));
+    if (out->b_prev) DNS_TRY(st->b.download(out->b_prev, n, s));
+    if (pl.carry) {
+        if (out->kxs_in)
+            for (int q = 1; q < 5; ++q)
+                DNS_TRY(st->kxs[ring[q]].download(out->kxs_in + (q - 1) * n, n,
+                                                  s));
+        if (out->rcarry_in) DNS_TRY(st->rcarry.download(out->rcarry_in, nv, s));
+    }
+    if (six) {
+        if (out->rc6_in) {
+            DNS_TRY(st->rc6[par].download(out->rc6_in, nv, s));
+            DNS_TRY(st->rc6[1 - par].download(out->rc6_in + nv, nv, s));
+        }
+        if (out->x0_other)
+            DNS_TRY(st->x0buf[1 - par].download(out->x0_other, n, s));
+    }
+    DNS_HIP(hipStreamSynchronize(s));
+    // ---- the front, by its form (prologue() without launch_front_nodes)
+    switch (pl.form) {
+        case StepPlan::Six: DNS_TRY(st->front_six(cf, pl)); break;
+        case StepPlan::Fused: DNS_TRY(st->front_fused(cf, pl)); break;
+        case StepPlan::StreamRhs: DNS_TRY(st->front_stream(cf, pl)); break;
+        case StepPlan::Plain: DNS_TRY(st->front_rows(cf, pl)); break;
+        default:
+            return dns::fail(DNS_ERR_HOST, "front probe: a partitioned plan on "
+                             "an un-partitioned handle");
+    }
+    DNS_HIP(hipStreamSynchronize(s));
+    // ---- what it has left
+    out->form = (int32_t)pl.form;
+    out->mode = pl.mode;
+    out->use_pre = pl.use_pre ? 1 : 0;
+    out->carry = pl.carry ? 1 : 0;
+    out->k_lpr = h->K.lpr;
+    out->r1_lpr = st->R1.lpr;
+    out->r1_pair = st->R1p.ready ? 1 : 0;
+    out->pad = 0;
+    const bool fused = pl.form == StepPlan::Fused;
+    out->nparts = fused ? st->front_nparts(pl) : 0;
+    if (out->x0)
+        DNS_TRY((six ? st->x0buf[par] : st->xs[st->work]).download(out->x0, n,
+                                                                   s));
+    if (out->b) DNS_TRY(st->b.download(out->b, n, s));
+    if (out->nfc_out) DNS_TRY(st->nfc[st->nc].download(out->nfc_out, nv, s));
+    if (six && out->kx) DNS_TRY(st->kx6.download(out->kx, n, s));
+    if (fused) {
+        if (out->nparts > out->parts_cap && (out->partR || out->partB))
+            return dns::fail(DNS_ERR_BAD_ARGUMENT, "%d partials, room for %d",
+                             out->nparts, out->parts_cap);
+        if (out->r) DNS_TRY(dns::download_from(out->r, h->r.p, n, s));
+        if (out->partR)
+            DNS_TRY(dns::download_from(out->partR, h->partR.p,
+                                       (size_t)out->nparts, s));
+        if (out->partB)
+            DNS_TRY(dns::download_from(out->partB, h->partB.p,
+                                       (size_t)out->nparts, s));
+    }
+    if (pl.mode == 2) {
+        if (out->kxs_cur) DNS_TRY(st->kxs[st->cur].download(out->kxs_cur, n, s));
+        if (out->rcarry_out)
+            DNS_TRY(st->rcarry.download(out->rcarry_out, nv, s));
+    }
+    DNS_HIP(hipStreamSynchronize(s));
     return DNS_OK;
 } DNS_CAPI_CATCH
 

@@ -424,6 +424,51 @@ int dns_imex_step_counters(dns_imex *st, int64_t *out3);
 int dns_imex_run_cycles(dns_imex *st, int64_t *out2);
 /* v (NV) and p = pscale*p~ (NP) of the current state */
 int dns_imex_get_state(dns_imex *st, double *v, double *p);
+
+/* TEST ONLY.  The front of ONE step on one GPU: what `dns_imex_step` does
+ * before its solve (the upload of `nfc_new` with its swap, the K x products of
+ * a carry step), then the plan for `cycle_len` (0: a synchronous solve; > 0:
+ * the cycle length of a pipelined batch) and the launches that plan puts in
+ * front of the first Krylov cycle -- by the member functions the step itself
+ * calls, without the nodes of the attachments and without a solve -- then a
+ * synchronise.  `out` receives what the front READS, copied before it runs,
+ * and what it has LEFT.  Every pointer of `out` may be NULL (n = NV + NP).
+ * DNS_ERR_BAD_ARGUMENT on a row-partitioned handle or with an attachment
+ * (feedback, recorder, functionals, statistics, quadratics, ensemble);
+ * DNS_ERR_NOT_READY with a pipelined batch pending; nothing is touched then.
+ * The stepper is CONSUMED: the convection slot, the carry buffers and the
+ * work vector are those of a step that never finished.  dns_imex_step,
+ * dns_imex_run and a second probe answer DNS_ERR_NOT_READY until
+ * dns_imex_set_state starts over. */
+typedef struct dns_imex_probe {
+    /* --- read by the front */
+    double *ring;          /* 5 n: cur, prev, pprev, p3, p4, raw [v; p~]       */
+    double *nfc_in;        /* 2 NV: nfc_c, nfc_o as the front finds them       */
+    double *g_in, *gp_in;  /* NV, NP: the rows of g / gp the counter selects   */
+    double *b_prev;        /* n: the right-hand side of the step before        */
+    double *kxs_in;        /* 4 n: K x of prev .. p4      (has_carry)          */
+    double *rcarry_in;     /* NV: the carried residual    (has_carry)          */
+    double *rc6_in;        /* 2 NV: current, previous     (has_six)            */
+    double *x0_other;      /* n: the warm start before    (has_six)            */
+    /* --- left by the front */
+    double *x0, *b;        /* n each                                           */
+    double *nfc_out;       /* NV: nfc_c (written with a device convection)     */
+    double *kx;            /* n: K x0                     (six-node form)      */
+    double *r;             /* n: b - K x0                 (nparts > 0)         */
+    double *partR, *partB; /* parts_cap each: raw partials (nparts > 0)        */
+    double *kxs_cur;       /* n: K x_c                    (mode 2)             */
+    double *rcarry_out;    /* NV: b_prev - K x_c          (mode 2)             */
+    int32_t parts_cap;     /* in                                               */
+    int32_t nsol, tab_row, has_carry, has_six;
+    /* the plan: StepPlan::Form (0 Plain, 1 Six, 2 Fused, 5 StreamRhs), the
+     * MODE of k_step_front, "the tail before left the warm start", "residual
+     * carried"; the lanes-per-row instantiations of K and R1; the partials;
+     * "R1 is held in the pair format" (the streamed product then takes it) */
+    int32_t form, mode, use_pre, carry, k_lpr, r1_lpr, nparts, r1_pair, pad;
+} dns_imex_probe;
+int dns_imex_front_probe(dns_imex *st, const dns_imex_coeffs *cf,
+                         const dns_solve_opts *opts, int32_t cycle_len,
+                         const double *nfc_new, dns_imex_probe *out);
 /* ---- observer feedback of the explicit loops ------------------------------
  * The reference's `dynamic_rhs` of a closed loop with a linear observer
  * (`get_heunab_lti`, tiu:148-196, composed as in snu:1243-1247), resident:

@@ -112,6 +112,18 @@ def test_assembly_probe_checks_its_arguments_on_the_host(capi):
         == capi.DNS_ERR_BAD_ARGUMENT
 
 
+def test_front_probe_checks_its_arguments_on_the_host(capi):
+    import ctypes as ct
+    lib = capi.load_library()
+    pr = capi.dns_imex_probe()
+    assert ct.sizeof(pr) == 200
+    cf = capi.dns_imex_coeffs(a_c=1.)
+    assert lib.dns_imex_front_probe(None, ct.byref(cf), None, 0, None,
+                                    ct.byref(pr)) == capi.DNS_ERR_BAD_ARGUMENT
+    assert lib.dns_imex_front_probe(None, None, None, 0, None, None) \
+        == capi.DNS_ERR_BAD_ARGUMENT
+
+
 def test_no_device_is_loud(capi):
     """without a GPU the product path must raise, never fall back"""
     if capi.device_count() > 0:
