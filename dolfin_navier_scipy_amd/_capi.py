@@ -101,6 +101,16 @@ class dns_spmv_epi(ct.Structure):
                 ('pad', ct.c_int32)]
 
 
+class dns_row_probe(ct.Structure):
+    _fields_ = [('kernel', ct.c_int32), ('lpr', ct.c_int32),
+                ('fp32_vals', ct.c_int32), ('nsplit', ct.c_int32),
+                ('a2', ct.POINTER(dns_csr)), ('a3', ct.POINTER(dns_csr)),
+                ('x2', c_double_p), ('x3', c_double_p), ('x4', c_double_p),
+                ('a_c', ct.c_double), ('a_p', ct.c_double),
+                ('y2', c_double_p), ('y3', c_double_p),
+                ('nparts', ct.c_int32), ('pad', ct.c_int32)]
+
+
 class dns_trap_probe(ct.Structure):
     _fields_ = [(k, c_double_p) for k in
                 ('nvals', 'fvals', 'kfvals', 'rhsbc', 'fvn', 'b', 'x0', 'r',
@@ -329,6 +339,9 @@ SIGNATURES = {
                                      ct.POINTER(dns_spmv_epi), c_double_p,
                                      c_double_p, c_double_p, c_double_p,
                                      c_int32_p, c_int32_p]),
+    'dns_row_kernel_probe': (ct.c_int, [ct.c_int, ct.POINTER(dns_csr),
+                                        ct.POINTER(dns_row_probe), c_double_p,
+                                        c_double_p]),
     'dns_spmv_bench': (ct.c_int, [ct.c_int, ct.POINTER(dns_csr), ct.c_int32,
                                   ct.c_int32, ct.c_int32, c_double_p,
                                   c_double_p]),

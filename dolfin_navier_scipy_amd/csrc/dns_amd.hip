@@ -1646,7 +1646,26 @@ int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
         else
             hipLaunchKernelGGL(k_arn_head_lazy<1>, gridA, kBlock, 0, stream, np,
                                (const void *)sinv.p, tau.p, zp, 0, ctr0);
-        DNS_TRY(apply_fhat_part(r.p, zp, Z.p, zero_ptr(), nullptr));
+        if (fhat_explicit && !streams(Gc) && !dist()) {
+            // (the rows of k_spmv_split in three load levels: no guard, no
+            // column selector, same bits)
+            const int g = grid_for_rows(nv, Gc.lpr);
+            if (fp32_store) {
+                DNS_LPR_SWITCH(
+                    Gc.lpr,
+                    hipLaunchKernelGGL((k_spmv_gc_lazy<L, float>), g, kBlock, 0,
+                                       stream, nv, Gc.rowptr.p, Gc.colidx.p,
+                                       gc32.p, r.p, zp, Z.p));
+            } else {
+                DNS_LPR_SWITCH(
+                    Gc.lpr,
+                    hipLaunchKernelGGL((k_spmv_gc_lazy<L, double>), g, kBlock,
+                                       0, stream, nv, Gc.rowptr.p, Gc.colidx.p,
+                                       Gc.vals.p, r.p, zp, Z.p));
+            }
+        } else {
+            DNS_TRY(apply_fhat_part(r.p, zp, Z.p, zero_ptr(), nullptr));
+        }
         // K z with <r, w>, <w, w> folded to at most kBlock partials of each
         // (kLazyRows consecutive rows per sub-wave and pass)
         const int rows_wg = kLazyRows * (kLazyBlock / K.lpr);
@@ -3249,6 +3268,183 @@ int dns_spmv_epilogue(int device, const dns_csr *a, const dns_spmv_epi *e,
     DNS_HIP(hipStreamSynchronize(ss.s));
     *nparts = grid;
     *nblocks = nb;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// TEST ONLY: ONE launch of a row kernel of the lazy six-node step on the
+// caller's operators (dns_amd.h: DNS_ROWK_*), with the grids the step uses
+int dns_row_kernel_probe(int device, const dns_csr *a, dns_row_probe *p,
+                         const double *x, double *y) try {
+    if (!p || !x || !y) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    const int kern = p->kernel;
+    if (kern < DNS_ROWK_GC || kern > DNS_ROWK_HEAD)
+        return fail(DNS_ERR_BAD_ARGUMENT, "unknown kernel %d", kern);
+    const bool head = kern == DNS_ROWK_HEAD;
+    if (!head) DNS_TRY(check_csr(a, "A"));
+    if (!head && (a->nrows < 1 || a->ncols < 1))
+        return fail(DNS_ERR_BAD_ARGUMENT, "empty matrix");
+    const int lpr = p->lpr;
+    if (kern != DNS_ROWK_TAU && !head &&
+        (lpr < 2 || lpr > 64 || (lpr & (lpr - 1))))
+        return fail(DNS_ERR_BAD_ARGUMENT, "lpr must be a power of two in [2, 64]");
+    if (kern == DNS_ROWK_GC &&
+        (p->nsplit != a->nrows || a->ncols < a->nrows || !p->x2))
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "Gc: nv x (nv + np), nsplit = nv, x2 = the pressure part");
+    if (kern == DNS_ROWK_TAU && !p->x2)
+        return fail(DNS_ERR_BAD_ARGUMENT, "tau: x = b, x2 = kx");
+    if (kern == DNS_ROWK_STEP) {
+        if (a->nrows != a->ncols)
+            return fail(DNS_ERR_BAD_ARGUMENT, "step: K must be square");
+        DNS_TRY(check_csr(p->a2, "R1"));
+        DNS_TRY(check_csr(p->a3, "cell list"));
+        if (p->a2->nrows != p->a2->ncols || p->a2->nrows < 1 ||
+            p->a2->nrows > a->nrows || p->a3->nrows != p->a2->nrows ||
+            p->a3->ncols < 1)
+            return fail(DNS_ERR_BAD_ARGUMENT,
+                        "step: R1 nv x nv, cell list nv x ncell, nv <= n");
+        if (!p->x2 || !p->x3 || !p->x4 || !p->y2 || !p->y3)
+            return fail(DNS_ERR_BAD_ARGUMENT,
+                        "step: x2 = v_c, x3 = v_p, x4 = cell values, y2 = b, "
+                        "y3 = nfc");
+    }
+    if (kern == DNS_ROWK_RW &&
+        (a->nrows != a->ncols || !p->x2 || !p->y2))
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "rw: K square, x2 = r, y2 = 2 * kBlock partials");
+    if (head && (p->nsplit < 1 || !p->x2))
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "head: nsplit = np, x2 = the np x np rows");
+    DNS_HIP(hipSetDevice(device));
+    ScopedStream ss;
+    DNS_HIP(hipStreamCreate(&ss.s));
+    auto up = [&](DevBuf<double> &d, const double *h, size_t len) -> int {
+        DNS_TRY(d.alloc(len));
+        return len ? d.upload(h, len, ss.s) : DNS_OK;
+    };
+    p->nparts = 0;
+    if (head) {
+        // the padded fp32 rows of the dense inverse, as the set-up lays them
+        // out: sld a multiple of four, zeros behind the row
+        const int np = p->nsplit, sld = (np + 3) & ~3;
+        std::vector<float> h((size_t)np * sld, 0.0f);
+        for (int i = 0; i < np; ++i)
+            for (int j = 0; j < np; ++j)
+                h[(size_t)i * sld + j] = (float)p->x2[(size_t)i * np + j];
+        DevBuf<float> s32;
+        DevBuf<double> dtau, dzp;
+        DNS_TRY(s32.alloc(h.size()));
+        DNS_TRY(s32.upload(h.data(), h.size(), ss.s));
+        DNS_TRY(up(dtau, x, (size_t)np));
+        DNS_TRY(dzp.alloc((size_t)np));
+        const int grid = std::max(1, std::min((np + 3) / 4, 2048));
+        hipLaunchKernelGGL(k_arn_head_lazy<2>, grid, kBlock, 0, ss.s, np,
+                           (const void *)s32.p, dtau.p, dzp.p, sld,
+                           (int *)nullptr);
+        DNS_HIP(hipGetLastError());
+        DNS_TRY(dzp.download(y, (size_t)np, ss.s));
+        DNS_HIP(hipStreamSynchronize(ss.s));
+        return DNS_OK;
+    }
+    CsrDev A;
+    DNS_TRY(A.upload(a, ss.s));
+    const int nr = a->nrows, nc = a->ncols;
+    if (kern == DNS_ROWK_GC) {
+        const int nv = nr;
+        DevBuf<double> drv, dzp, dzv;
+        DevBuf<float> v32;
+        DNS_TRY(up(drv, x, (size_t)nv));
+        DNS_TRY(up(dzp, p->x2, (size_t)(nc - nv)));
+        DNS_TRY(dzv.alloc((size_t)nv));
+        if (p->fp32_vals) {
+            std::vector<float> h((size_t)a->nnz + 1, 0.0f);
+            for (int64_t k = 0; k < a->nnz; ++k) h[k] = (float)a->vals[k];
+            DNS_TRY(v32.alloc(h.size()));
+            DNS_TRY(v32.upload(h.data(), h.size(), ss.s));
+        }
+        const int g = grid_for_rows(nv, lpr);
+        if (p->fp32_vals) {
+            DNS_LPR_SWITCH(lpr, hipLaunchKernelGGL(
+                                    (k_spmv_gc_lazy<L, float>), g, kBlock, 0,
+                                    ss.s, nv, A.rowptr.p, A.colidx.p, v32.p,
+                                    drv.p, dzp.p, dzv.p));
+        } else {
+            DNS_LPR_SWITCH(lpr, hipLaunchKernelGGL(
+                                    (k_spmv_gc_lazy<L, double>), g, kBlock, 0,
+                                    ss.s, nv, A.rowptr.p, A.colidx.p, A.vals.p,
+                                    drv.p, dzp.p, dzv.p));
+        }
+        DNS_HIP(hipGetLastError());
+        DNS_TRY(dzv.download(y, (size_t)nv, ss.s));
+    } else if (kern == DNS_ROWK_TAU) {
+        const int np = nr, nv = nc, n = nv + np;
+        DevBuf<double> db, dkx, dtau, dr, dpr, dpb;
+        DNS_TRY(up(db, x, (size_t)n));
+        DNS_TRY(up(dkx, p->x2, (size_t)n));
+        DNS_TRY(dtau.alloc((size_t)np));
+        DNS_TRY(dr.alloc((size_t)n));
+        const int gd = grid_for_elems(n);
+        DNS_TRY(dpr.alloc((size_t)gd));
+        DNS_TRY(dpb.alloc((size_t)gd));
+        const int gt = std::max(1, std::min((np + 1) / 2, 4096));
+        hipLaunchKernelGGL(k_tau_first, gt + gd, kBlock, 0, ss.s, gt, n, np, nv,
+                           A.rowptr.p, A.colidx.p, A.vals.p, db.p, dkx.p,
+                           dtau.p, dr.p, dpr.p, dpb.p);
+        DNS_HIP(hipGetLastError());
+        DNS_TRY(dtau.download(y, (size_t)np, ss.s));
+        if (p->y2) DNS_TRY(dr.download(p->y2, (size_t)n, ss.s));
+    } else if (kern == DNS_ROWK_STEP) {
+        const int n = nr, nv = p->a2->nrows, ncell = p->a3->ncols;
+        CsrDev R1, G;
+        DNS_TRY(R1.upload(p->a2, ss.s));
+        DNS_TRY(G.upload(p->a3, ss.s));
+        DevBuf<double> dx0, dxc, dxp, dcv, dzero, dnfc, db, dkx;
+        DNS_TRY(up(dx0, x, (size_t)n));
+        DNS_TRY(up(dxc, p->x2, (size_t)n));
+        DNS_TRY(up(dxp, p->x3, (size_t)n));
+        DNS_TRY(up(dcv, p->x4, (size_t)ncell));
+        // (g, g_p and the old convection term: zeros, with factors 0)
+        DNS_TRY(dzero.alloc((size_t)n));
+        DNS_TRY(dzero.zero(ss.s));
+        DNS_TRY(dnfc.alloc((size_t)nv));
+        DNS_TRY(db.alloc((size_t)n));
+        DNS_TRY(dkx.alloc((size_t)n));
+        const TabRef gt{dzero.p, nullptr, 0, 1}, gpt{dzero.p, nullptr, 0, 1};
+        const int gk = std::max(1, std::min(grid_for_rows(n, lpr), 2048));
+        const int gb = grid_for_rows(n, lpr);
+        DNS_LPR_SWITCH(
+            lpr, hipLaunchKernelGGL(
+                     (k_step_one2<L>), gk + gb, kBlock, 0, ss.s, gk, n, nv,
+                     A.rowptr.p, A.colidx.p, A.vals.p, R1.rowptr.p, R1.colidx.p,
+                     R1.vals.p, dx0.p, dxc.p, dxp.p, p->a_c, p->a_p, dnfc.p,
+                     dzero.p, 0.0, 0.0, gt, gpt, G.rowptr.p, G.colidx.p, dcv.p,
+                     1.0, (const double *)nullptr, (const double *)nullptr,
+                     db.p, dkx.p));
+        DNS_HIP(hipGetLastError());
+        DNS_TRY(dkx.download(y, (size_t)n, ss.s));
+        DNS_TRY(db.download(p->y2, (size_t)n, ss.s));
+        DNS_TRY(dnfc.download(p->y3, (size_t)nv, ss.s));
+    } else {
+        const int n = nr;
+        DevBuf<double> dz, dr, dw, dpart;
+        DNS_TRY(up(dz, x, (size_t)n));
+        DNS_TRY(up(dr, p->x2, (size_t)n));
+        DNS_TRY(dw.alloc((size_t)n));
+        const int rows_wg = kLazyRows * (kLazyBlock / lpr);
+        const int gl = std::max(1, std::min((n + rows_wg - 1) / rows_wg,
+                                            kBlock));
+        DNS_TRY(dpart.alloc((size_t)2 * gl));
+        DNS_LPR_SWITCH(
+            lpr, hipLaunchKernelGGL((k_spmv_rw<L, kLazyRows, kLazyBlock>), gl,
+                                    kLazyBlock, 0, ss.s, n, A.rowptr.p,
+                                    A.colidx.p, A.vals.p, dz.p, dw.p, dr.p,
+                                    dpart.p));
+        DNS_HIP(hipGetLastError());
+        DNS_TRY(dw.download(y, (size_t)n, ss.s));
+        DNS_TRY(dpart.download(p->y2, (size_t)2 * gl, ss.s));
+        p->nparts = gl;
+    }
+    DNS_HIP(hipStreamSynchronize(ss.s));
     return DNS_OK;
 } DNS_CAPI_CATCH
 

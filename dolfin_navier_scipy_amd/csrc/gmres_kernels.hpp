@@ -22,6 +22,7 @@
 // (fixed order, no atomics); workgroup 0 alone writes the control block.
 #pragma once
 #include "kernels.hpp"
+#include "row_loads.hpp"
 
 namespace dns {
 
@@ -278,6 +279,33 @@ k_arn_head_lazy(int np, const void *__restrict__ sinv,
     if (stepctr && blockIdx.x == 0 && threadIdx.x == 0) *stepctr += 1;
 }
 
+// zv = Gc [r_v; zp] of the lazy one-column cycle (k_spmv_split reads a guard
+// and a column selector, the lazy cycle has neither): the row pointers, then
+// the (col, val) loads of four chunks, then their four gathers -- three load
+// levels for a row of up to 4 LPR entries (row_loads.hpp; the loop form never
+// entered its unrolled part on an average row of Gc and went on entry by
+// entry).  Same accumulators, same order, same bits as k_spmv_split.
+template <int LPR, typename VT>
+__global__ void __launch_bounds__(kBlock)
+k_spmv_gc_lazy(int nv, const int *__restrict__ rowptr,
+               const int *__restrict__ colidx, const VT *__restrict__ vals,
+               const double *__restrict__ rv, const double *__restrict__ zp,
+               double *__restrict__ zv) {
+    const int sub = (blockIdx.x * kBlock + threadIdx.x) / LPR;
+    const int sublane = threadIdx.x % LPR;
+    const int nsub = gridDim.x * (kBlock / LPR);
+    for (int row = sub; row < nv; row += nsub) {
+        const int k0 = rowptr[row], k1 = rowptr[row + 1];
+        double s = 0.0;
+        if (k0 < k1)
+            s = row_dot_flat<LPR, 4, VT>(RowQuads{}, colidx, vals,
+                                         GatherSplit{rv, zp, nv}, k0, k1,
+                                         sublane);
+        s = subwave_sum<LPR>(s);
+        if (sublane == 0) zv[row] = s;
+    }
+}
+
 // w = K z of the lazy one-column cycle with the partials of <r, w> and <w, w>
 //   part[wg] = <r, w>,  part[nparts + wg] = <w, w>      (nparts = gridDim.x)
 // folded to at most kBlock workgroups, so that a thread of the tail needs ONE
@@ -301,32 +329,65 @@ k_spmv_rw(int nrows, const int *__restrict__ rowptr,
     const int nsub = gridDim.x * (BS / LPR);
     double awr = 0.0, aww = 0.0;
     for (int base = sub * R; base < nrows; base += nsub * R) {
+        // level 1: pointers and r of the R rows, from rows clamped into the
+        // matrix; level 2: two chunks of each row from indices clamped into
+        // the row; level 3: the gathers -- every level one basic block, the
+        // values selected afterwards (row_loads.hpp).  A pass with a row that
+        // is empty or past the end (nothing to clamp into) takes the
+        // predicated loop form.
         int k0[R], k1[R];
         double rv[R];
+        bool flat = base + R <= nrows;
 #pragma unroll
         for (int q = 0; q < R; ++q) {
             const bool on = base + q < nrows;
-            k0[q] = on ? rowptr[base + q] : 0;
-            k1[q] = on ? rowptr[base + q + 1] : 0;
-            rv[q] = on ? r[base + q] : 0.0;
-        }
-        int c0[R], c1[R];
-        double v0[R], v1[R];
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            const int k = k0[q] + sublane;
-            const bool on0 = k < k1[q], on1 = k + LPR < k1[q];
-            c0[q] = on0 ? colidx[k] : -1;
-            v0[q] = on0 ? vals[k] : 0.0;
-            c1[q] = on1 ? colidx[k + LPR] : -1;
-            v1[q] = on1 ? vals[k + LPR] : 0.0;
+            const int rq = min(base + q, nrows - 1);
+            const int p0 = rowptr[rq], p1 = rowptr[rq + 1];
+            const double rr = r[rq];
+            k0[q] = on ? p0 : 0;
+            k1[q] = on ? p1 : 0;
+            rv[q] = on ? rr : 0.0;
+            flat = flat && p0 < p1;
         }
         double s[R];
+        if (flat) {
+            int c[R][2];
+            double v[R][2], zz[R][2];
 #pragma unroll
-        for (int q = 0; q < R; ++q) {
-            const double z0 = c0[q] >= 0 ? z[c0[q]] : 0.0;
-            const double z1 = c1[q] >= 0 ? z[c1[q]] : 0.0;
-            s[q] = fma(v1[q], z1, v0[q] * z0);
+            for (int q = 0; q < R; ++q)
+                row_chunks_load<LPR, 2, double>(colidx, vals, k0[q] + sublane,
+                                                k1[q], c[q], v[q]);
+#pragma unroll
+            for (int q = 0; q < R; ++q)
+                row_gather<2>(c[q], GatherVec{z}, zz[q]);
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const int k = k0[q] + sublane;
+                const bool on0 = k < k1[q], on1 = k + LPR < k1[q];
+                // (the loop form's zeros for a chunk the lane does not have:
+                // its bits, the sign of a zero included)
+                const double v0 = on0 ? v[q][0] : 0.0, z0 = on0 ? zz[q][0] : 0.0;
+                const double v1 = on1 ? v[q][1] : 0.0, z1 = on1 ? zz[q][1] : 0.0;
+                s[q] = fma(v1, z1, v0 * z0);
+            }
+        } else {
+            int c0[R], c1[R];
+            double v0[R], v1[R];
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const int k = k0[q] + sublane;
+                const bool on0 = k < k1[q], on1 = k + LPR < k1[q];
+                c0[q] = on0 ? colidx[k] : -1;
+                v0[q] = on0 ? vals[k] : 0.0;
+                c1[q] = on1 ? colidx[k + LPR] : -1;
+                v1[q] = on1 ? vals[k + LPR] : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const double z0 = c0[q] >= 0 ? z[c0[q]] : 0.0;
+                const double z1 = c1[q] >= 0 ? z[c1[q]] : 0.0;
+                s[q] = fma(v1[q], z1, v0[q] * z0);
+            }
         }
 #pragma unroll
         for (int q = 0; q < R; ++q) {

@@ -406,8 +406,14 @@ k_step_one2(int gk, int n, int nv, const int *__restrict__ k_rowptr,
         const int sub = (blockIdx.x * kBlock + threadIdx.x) / LPR;
         const int nsub = gk * (kBlock / LPR);
         for (int row = sub; row < n; row += nsub) {
-            const double s = csr_row_dot<LPR>(k_rowptr, k_colidx, k_vals, x0,
-                                              row, sublane);
+            // (csr_row_dot's sums in three load levels: row_loads.hpp)
+            const int k0 = k_rowptr[row], k1 = k_rowptr[row + 1];
+            double s = 0.0;
+            if (k0 < k1)
+                s = row_dot_flat<LPR, 2, double>(RowPairs{}, k_colidx, k_vals,
+                                                 GatherVec{x0}, k0, k1,
+                                                 sublane);
+            s = subwave_sum<LPR>(s);
             if (sublane == 0) kx[row] = s;
         }
         return;
@@ -504,28 +510,23 @@ k_tau_first(int gt, int n, int np, int nv, const int *__restrict__ rowptr,
     const int pair = threadIdx.x >> 7, l128 = threadIdx.x & 127;
     for (int base = blockIdx.x * 2; base < np; base += gt * 2) {
         const int row = base + pair;
-        double s0 = 0.0, s1 = 0.0;
-        if (row < np) {
-            const int k1 = rowptr[row + 1];
-            int k = rowptr[row] + l128;
-            for (; k + 128 < k1; k += 256) {
-                const int c0 = colidx[k], c1 = colidx[k + 128];
-                const double v0 = vals[k], v1 = vals[k + 128];
-                s0 = fma(v0, b[c0] - kx[c0], s0);
-                s1 = fma(v1, b[c1] - kx[c1], s1);
-            }
-            if (k < k1) {
-                const int c0 = colidx[k];
-                s0 = fma(vals[k], b[c0] - kx[c0], s0);
-            }
-        }
-        const double s = wave_sum(s0 + s1);
+        // level 1: the row's pointers WITH its own entries of b and kx (they
+        // used to be asked for behind the two barriers); levels 2 and 3: four
+        // chunks of 128 and their gathers (row_loads.hpp; an average row has
+        // 270 entries, the fourth chunk repeats the row's last entry)
+        const int rowc = min(row, np - 1);
+        const int k0 = rowptr[rowc], k1 = rowptr[rowc + 1];
+        const double bp = b[nv + rowc], kp = kx[nv + rowc];
+        double sl = 0.0;
+        if (row < np && k0 < k1)
+            sl = row_dot_flat<128, 4, double>(RowPairs{}, colidx, vals,
+                                              GatherDiff{b, kx}, k0, k1, l128);
+        const double s = wave_sum(sl);
         __syncthreads();
         if (lane == 0) half[wave] = s;
         __syncthreads();
         if (l128 == 0 && row < np)
-            tau[row] = (b[nv + row] - kx[nv + row]) -
-                       (half[2 * pair] + half[2 * pair + 1]);
+            tau[row] = (bp - kp) - (half[2 * pair] + half[2 * pair + 1]);
     }
 }
 

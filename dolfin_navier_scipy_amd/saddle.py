@@ -1236,6 +1236,82 @@ def spmv_epilogue(A, x, y0, kernel='stream', nv=0, fp32_vals=False,
                 nblocks=nblocks.value)
 
 
+def row_kernel_probe(kernel, A=None, x=None, lpr=32, fp32_vals=False, x2=None,
+                     R1=None, cells=None, v_p=None, cellvals=None, a_c=1.,
+                     a_p=0., device=0):
+    """TEST ONLY (`dns_row_kernel_probe`): ONE launch of a row kernel of the
+    lazy six-node step on the caller's operators.
+
+    `'gc'`: `A` nv x (nv + np), `x` = r_v, `x2` = z_p -> `dict(y)`;
+    `'tau'`: `A` np x nv, `x` = b, `x2` = kx -> `dict(y, r)`;
+    `'step'`: `A` = K, `R1`, `cells` (nv x ncell pattern), `x` = x0, `x2` = v_c,
+    `v_p`, `cellvals` -> `dict(kx, b, nfc)`;
+    `'rw'`: `A` = K, `x` = z, `x2` = r -> `dict(y, wr, ww)` (partials);
+    `'head'`: `x2` = the dense np x np rows, `x` = tau -> `dict(y)`."""
+    lib = C.load_library()
+    code = {'gc': 0, 'tau': 1, 'step': 2, 'rw': 3, 'head': 4}[kernel]
+    p = C.dns_row_probe()
+    p.kernel, p.lpr, p.fp32_vals = code, int(lpr), int(bool(fp32_vals))
+    p.a_c, p.a_p = float(a_c), float(a_p)
+    keep = []
+    if kernel == 'head':
+        S = np.ascontiguousarray(x2, dtype=np.float64)
+        npr = S.shape[0]
+        if S.shape != (npr, npr):
+            raise ValueError('head: a square dense matrix')
+        x = C.as_f64(x, size=npr)
+        p.nsplit = npr
+        p.x2 = C.dptr(S)
+        y = np.empty(npr)
+        C.check(lib.dns_row_kernel_probe(device, None, ct.byref(p), C.dptr(x),
+                                         C.dptr(y)))
+        return dict(y=y)
+    view = C.CsrView(A)
+    nr, nc = view.shape
+    out = {}
+    if kernel == 'gc':
+        x = C.as_f64(x, size=nr)
+        x2 = C.as_f64(x2, size=nc - nr)
+        p.nsplit = nr
+        y = np.empty(nr)
+    elif kernel == 'tau':
+        x = C.as_f64(x, size=nr + nc)
+        x2 = C.as_f64(x2, size=nr + nc)
+        y = np.empty(nr)
+        out['r'] = np.empty(nr + nc)
+        p.y2 = C.dptr(out['r'])
+    elif kernel == 'step':
+        v2, v3 = C.CsrView(R1), C.CsrView(cells)
+        keep += [v2, v3]
+        nv = v2.shape[0]
+        x = C.as_f64(x, size=nr)
+        x2 = C.as_f64(x2, size=nr)
+        v_p = C.as_f64(v_p, size=nr)
+        cellvals = C.as_f64(cellvals, size=v3.shape[1])
+        p.a2, p.a3 = ct.pointer(v2.struct), ct.pointer(v3.struct)
+        p.x3, p.x4 = C.dptr(v_p), C.dptr(cellvals)
+        y = np.empty(nr)
+        out['b'], out['nfc'] = np.empty(nr), np.empty(nv)
+        p.y2, p.y3 = C.dptr(out['b']), C.dptr(out['nfc'])
+    else:
+        x = C.as_f64(x, size=nr)
+        x2 = C.as_f64(x2, size=nr)
+        y = np.empty(nr)
+        parts = np.zeros(512)
+        p.y2 = C.dptr(parts)
+    p.x2 = C.dptr(x2)
+    C.check(lib.dns_row_kernel_probe(device, view.byref(), ct.byref(p),
+                                     C.dptr(x), C.dptr(y)))
+    if kernel == 'step':
+        out['kx'] = y
+        return out
+    out['y'] = y
+    if kernel == 'rw':
+        out['wr'] = parts[:p.nparts].copy()
+        out['ww'] = parts[p.nparts:2*p.nparts].copy()
+    return out
+
+
 def dot(x, y, device=0):
     x, y = C.as_f64(x), C.as_f64(y)
     out = ct.c_double(0.)

@@ -903,6 +903,41 @@ int dns_spmv_epilogue(int device, const dns_csr *a, const dns_spmv_epi *e,
                       const double *x, double *y, double *part,
                       double *part_bb, int32_t *nparts, int32_t *nblocks);
 
+/* TEST ONLY: ONE launch of a row kernel of the lazy six-node step on the
+ * caller's operators, with the grid the step gives it (tests of the kernels in
+ * isolation: row lengths at the edges of their load chunks).
+ *   GC    a: nv x (nv + np), nsplit = nv; x = r_v (nv), x2 = z_p (np);
+ *         y = a [x; x2] (nv).  fp32_vals: values rounded to float
+ *   TAU   a: np x nv; x = b, x2 = kx (nv + np each); y (np) =
+ *         (b - kx)[nv + i] - (a (b - kx)[:nv])[i]; y2 (optional) = b - kx
+ *   STEP  a = K (n x n), a2 = R1 (nv x nv), a3 = the cell list (nv x ncell, its
+ *         values are not read); x = x0, x2 = v_c, x3 = v_p (n each), x4 = cell
+ *         values (ncell); y = K x0 (n), y2 = b (n): b_v = R1 (a_c v_c + a_p v_p)
+ *         + 0 * (...), b_p = 0; y3 (nv) = sum of the listed cell values
+ *   RW    a = K (n x n); x = z, x2 = r; y = w = K z, y2 = [<r, w> | <w, w>]
+ *         partials, nparts of each (room for 2 x 256)
+ *   HEAD  a unused; nsplit = np, x2 = np x np rows (row-major, rounded to
+ *         float), x = tau; y = -x2 tau (k_arn_head_lazy, fp32 rows)          */
+#define DNS_ROWK_GC    0
+#define DNS_ROWK_TAU   1
+#define DNS_ROWK_STEP  2
+#define DNS_ROWK_RW    3
+#define DNS_ROWK_HEAD  4
+typedef struct dns_row_probe {
+    int32_t kernel;          /* DNS_ROWK_*                                     */
+    int32_t lpr;             /* lanes per row (GC, STEP, RW)                   */
+    int32_t fp32_vals;       /* GC                                             */
+    int32_t nsplit;          /* GC: nv; HEAD: np                               */
+    const dns_csr *a2, *a3;
+    const double *x2, *x3, *x4;
+    double a_c, a_p;         /* STEP                                           */
+    double *y2, *y3;
+    int32_t nparts;          /* out (RW)                                       */
+    int32_t pad;
+} dns_row_probe;
+int dns_row_kernel_probe(int device, const dns_csr *a, dns_row_probe *p,
+                         const double *x, double *y);
+
 /* Multigrid Schur block for pressure spaces too large for the dense inverse
  * (refined meshes).  `prol[l]` (CSR, n_l x n_{l+1}, l = 0 .. nprol-1) are the
  * prolongations of a nested hierarchy of pressure spaces, finest first (n_0 =
