@@ -268,6 +268,16 @@ SIGNATURES = {
                                                c_double_p, ct.c_double,
                                                ct.c_int32, ct.c_int32,
                                                c_double_p]),
+    'dns_imex_set_functionals_live': (ct.c_int, [_VP, ct.c_int32,
+                                                 ct.POINTER(dns_csr),
+                                                 ct.POINTER(dns_csr),
+                                                 ct.POINTER(dns_csr),
+                                                 ct.POINTER(dns_csr),
+                                                 ct.POINTER(dns_csr),
+                                                 c_double_p, c_double_p,
+                                                 c_int32_p, c_int32_p,
+                                                 c_double_p, ct.c_double,
+                                                 ct.c_int32, ct.c_int32]),
     'dns_imex_get_functionals': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
                                             c_double_p]),
     'dns_imex_clear_functionals': (ct.c_int, [_VP]),
@@ -284,6 +294,23 @@ SIGNATURES = {
                                            ct.POINTER(dns_csr), c_double_p,
                                            c_double_p, ct.c_double, ct.c_int32,
                                            ct.c_int32]),
+    'dns_imex_set_quadratics_bc': (ct.c_int, [_VP, ct.c_int32,
+                                              ct.POINTER(dns_csr), ct.c_int32,
+                                              c_int32_p, c_int32_p, c_int32_p,
+                                              ct.POINTER(dns_csr),
+                                              ct.POINTER(dns_csr), c_double_p,
+                                              c_double_p, ct.c_double,
+                                              ct.c_int32, ct.c_int32,
+                                              ct.c_int32, c_double_p]),
+    'dns_imex_set_quadratics_live': (ct.c_int, [_VP, ct.c_int32,
+                                                ct.POINTER(dns_csr),
+                                                ct.c_int32, c_int32_p,
+                                                c_int32_p, c_int32_p,
+                                                ct.POINTER(dns_csr),
+                                                ct.POINTER(dns_csr),
+                                                c_double_p, c_double_p,
+                                                ct.c_double, ct.c_int32,
+                                                ct.c_int32, ct.c_int32]),
     'dns_imex_get_quadratics': (ct.c_int, [_VP, ct.c_int32, ct.c_int32,
                                            c_double_p]),
     'dns_imex_quadratics_grid': (ct.c_int, [_VP, c_int32_p]),

@@ -200,6 +200,9 @@ struct dns_imex : dns::Ring {
         int ndbc = 0;
         dns::DevBuf<double> gtab;
         bool moving() const { return ndbc > 0; }
+        // dns_imex_set_functionals_live: no table of their own, the rows are
+        // those of the attached convection operator's table (bc_table())
+        bool live = false;
         // the convection operator whose cell order `cidx` refers to (a step
         // with another one attached is refused)
         const dns_conv *conv = nullptr;
@@ -251,8 +254,31 @@ struct dns_imex : dns::Ring {
         dns::DevBuf<int> lrp, lci; // the 2 nQ sparse rows (k, qa / qw)
         dns::DevBuf<double> lva, scale, c0;
         dns::DevBuf<double> log;   // rows x G x nQ
+        // moving Dirichlet values (dns_imex_set_quadratics_bc / _live):
+        // matrices and sparse rows are nv + ndbc wide; the table of their own,
+        // (rows + 1) x ndbc, or (`live`) the convection operator's; ndbc = 0:
+        // constant values
+        int ndbc = 0;
+        dns::DevBuf<double> gtab;
+        bool live = false;
+        bool moving() const { return ndbc > 0; }
     };
     std::unique_ptr<Quadratics> qd;
+    // Where an attachment with moving Dirichlet values reads them: its own
+    // table (`own`, `rows` + 1 rows of `ndbc`) or, `live`, the table of the
+    // attached convection operator (check_attachments has seen to its width
+    // and length) -- pointer, row stride, rows.
+    struct BcTable {
+        const double *p;
+        int stride, rows;
+    };
+    BcTable bc_table(bool live, const dns::DevBuf<double> &own, int ndbc,
+                     int rows) const {
+        if (live && conv)
+            return {conv->dbc_tab.p, std::max(1, conv->ndbc), conv->dbc_rows};
+        return {own.p, ndbc, rows + 1};
+    }
+    int check_live(const char *noun, int ndbc, int rows) const;
     int qd_launch(hipStream_t s);  // k_quadratic_step for the state as it stands
     uint64_t qd_key() const;
     // snapshot ensemble (ensemble.hpp): k_ensemble_step runs in front of every

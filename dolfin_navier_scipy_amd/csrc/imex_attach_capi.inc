@@ -52,14 +52,19 @@ int dns_imex::rec_launch(hipStream_t s) {
 }
 
 // "functionals on", their shape and instance (constant or moving Dirichlet
-// values: the table and its width), every buffer k_functional_step is handed
-// (the ring vectors come with the step key) and the pressure scale
+// values: the table in use -- their own or the operator's --, its stride and
+// rows), every buffer k_functional_step is handed (the ring vectors come with
+// the step key) and the pressure scale
 uint64_t dns_imex::fn_key() const {
     const Functionals &f = *fn;
     uint64_t k = mix64(0xf6, {kw(f.nF), kw(f.G), kw(f.rows), kw(f.ncl),
                               kw(f.dt), kw(last_pscale), kw(f.rp.p),
                               kw(f.ci.p), kw(f.va.p), kw(f.cptr.p)});
-    if (f.moving()) k = mix64(k, {kw(0xbc), kw(f.ndbc), kw(f.gtab.p)});
+    if (f.moving()) {
+        const BcTable t = bc_table(f.live, f.gtab, f.ndbc, f.rows);
+        k = mix64(k, {kw(0xbc), kw(f.ndbc), kw(f.live), kw(t.p), kw(t.stride),
+                      kw(t.rows)});
+    }
     return mix64(k,
                  {kw(f.cidx.p), kw(f.cw.p), kw(f.scale.p), kw(f.c0.p),
                   kw(f.log.p), kw(stepctr.p), kw(conv ? conv->ncells : 0),
@@ -84,7 +89,9 @@ int dns_imex::fn_launch(hipStream_t s) {
     if (f.moving()) {
         dns::FnBcArgs b;
         static_cast<dns::FnArgs &>(b) = a;
-        b.gtab = f.gtab.p;
+        // (a live table is as wide as the functionals' own -- its stride is
+        // ndbc -- and has more than `rows` rows: check_attachments)
+        b.gtab = bc_table(f.live, f.gtab, f.ndbc, f.rows).p;
         b.ndbc = f.ndbc;
         hipLaunchKernelGGL(dns::k_functional_step<dns::FnBcArgs>, f.G,
                            dns::kBlock, 0, s, b);
@@ -158,8 +165,9 @@ int dns_imex::st_launch(hipStream_t s) {
     return DNS_OK;
 }
 
-// "quadratics on", their shape, forms and grid and every buffer
-// k_quadratic_step is handed (the ring vectors come with the step key)
+// "quadratics on", their shape, forms and grid, every buffer
+// k_quadratic_step is handed (the ring vectors come with the step key) and,
+// with moving Dirichlet values, the table in use, its stride and rows
 uint64_t dns_imex::qd_key() const {
     const Quadratics &q = *qd;
     uint64_t k = mix64(0x9d, {kw(q.nM), kw(q.nQ), kw(q.G), kw(q.rows),
@@ -171,6 +179,11 @@ uint64_t dns_imex::qd_key() const {
         k = mix64(k, {kw(q.nzbase[m]), kw(q.need[m])});
     for (int f = 0; f < q.nQ; ++f)
         k = mix64(k, {kw(q.mat[f]), kw(q.lop[f]), kw(q.rop[f])});
+    if (q.moving()) {
+        const BcTable t = bc_table(q.live, q.gtab, q.ndbc, q.rows);
+        k = mix64(k, {kw(0xbc), kw(q.ndbc), kw(q.live), kw(t.p), kw(t.stride),
+                      kw(t.rows)});
+    }
     return k;
 }
 
@@ -202,7 +215,19 @@ int dns_imex::qd_launch(hipStream_t s) {
     a.scale = q.scale.p;
     a.c0 = q.c0.p;
     a.log = q.log.p;
-    hipLaunchKernelGGL(dns::k_quadratic_step, q.G, dns::kBlock, 0, s, a);
+    if (q.moving()) {
+        const BcTable t = bc_table(q.live, q.gtab, q.ndbc, q.rows);
+        dns::QdBcArgs b;
+        static_cast<dns::QdArgs &>(b) = a;
+        b.gtab = t.p;
+        b.ndbc = q.ndbc;                // (== t.stride: check_attachments)
+        b.trows = t.rows;
+        hipLaunchKernelGGL(dns::k_quadratic_step<dns::QdBcArgs>, q.G,
+                           dns::kBlock, 0, s, b);
+    } else {
+        hipLaunchKernelGGL(dns::k_quadratic_step<dns::QdArgs>, q.G,
+                           dns::kBlock, 0, s, a);
+    }
     DNS_HIP(hipGetLastError());
     return DNS_OK;
 }
@@ -230,6 +255,14 @@ int dns_imex::ens_launch(hipStream_t s) {
 // In front of every step, in this order: k_lti_step leaves the right-hand
 // side the front kernels read, the other five write down / add the row of
 // the step before.
+//
+// Functionals and quadratics that read the operator's LIVE Dirichlet table
+// (boundary feedback) depend on this order: k_lti_bc_step, the FIRST front
+// node of step s, writes row s + 1; row j thus holds the values of the state
+// before step j -- the row convention of the attachments' own tables -- and
+// rows s and s - 1, which the two nodes of step s read behind it on the same
+// stream, were complete a step earlier (row 0 was uploaded).  The closing
+// launch reads row `rows`, which the last step's observer node wrote.
 int dns_imex::launch_front_nodes(hipStream_t s) {
     if (fb) DNS_TRY(fb_launch(s));
     if (rec) DNS_TRY(rec_launch(s));
@@ -328,6 +361,28 @@ static const char *const kQdMovingBc =
     "(dns_conv_set_dbc_table): moving boundary values are not part of the "
     "constants";
 
+// What reading the operator's live Dirichlet table takes: the operator, its
+// width and `rows` + 1 rows (the setters and the step ask alike).
+int dns_imex::check_live(const char *noun, int ndbc, int rows) const {
+    if (!conv)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "%s on the operator's Dirichlet table: no device "
+                         "convection operator is attached "
+                         "(dns_imex_set_convection)", noun);
+    if (conv->ndbc != ndbc)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "%s on the operator's Dirichlet table: ndbc = %d, "
+                         "the convection operator has %d Dirichlet values",
+                         noun, ndbc, conv->ndbc);
+    if (conv->dbc_rows < rows + 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "%s on the operator's Dirichlet table: it has %d "
+                         "rows, %d steps need %d (dns_conv_set_dbc_table; row "
+                         "0: the values of the current state)", noun,
+                         conv->dbc_rows, rows, rows + 1);
+    return DNS_OK;
+}
+
 // what a step refuses on their behalf
 int dns_imex::check_attachments() const {
     if (fb) DNS_TRY(refuse_partitioned("observer feedback", kFbPartitioned));
@@ -351,18 +406,32 @@ int dns_imex::check_attachments() const {
                              "rows, %d steps need %d (dns_conv_set_dbc_table; "
                              "row 0: the values of the current state)",
                              conv->dbc_rows, fb->rows, fb->rows + 1);
-        if (fn || qd)
+        // (the device makes the values: a host-made copy cannot hold them)
+        if ((fn && !fn->live) || (qd && !qd->live))
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "boundary feedback with functionals / quadratics: "
-                             "their Dirichlet values are host-made copies");
+                             "boundary feedback with %s that do not read the "
+                             "operator's live Dirichlet table: their Dirichlet "
+                             "values are host-made copies (%s)",
+                             fn && !fn->live ? "functionals" : "quadratics",
+                             fn && !fn->live ? "dns_imex_set_functionals_live"
+                                             : "dns_imex_set_quadratics_live");
     }
     if (rec) DNS_TRY(refuse_partitioned("recorder", kRecPartitioned));
     if (stat) DNS_TRY(refuse_partitioned("statistics", kStPartitioned));
     if (ens) DNS_TRY(refuse_partitioned("ensemble", kEnsPartitioned));
     if (qd) {
         DNS_TRY(refuse_partitioned("quadratics", kQdPartitioned));
-        if (conv && conv->dbc_rows > 0)
+        if (!qd->moving() && conv && conv->dbc_rows > 0)
             return dns::fail(DNS_ERR_BAD_ARGUMENT, "%s", kQdMovingBc);
+        // (the columns behind nv are positions in the operator's values)
+        if (qd->moving() && conv && conv->ndbc != qd->ndbc)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "quadratics with moving Dirichlet values were set "
+                             "for %d values, the convection operator attached "
+                             "now has %d: set them again "
+                             "(dns_imex_set_quadratics_bc)", qd->ndbc,
+                             conv->ndbc);
+        if (qd->live) DNS_TRY(check_live("quadratics", qd->ndbc, qd->rows));
     }
     if (!fn) return DNS_OK;
     DNS_TRY(refuse_partitioned("functionals", kFnPartitioned));
@@ -391,6 +460,7 @@ int dns_imex::check_attachments() const {
                          "now has %d: set them again "
                          "(dns_imex_set_functionals_bc)", fn->ndbc,
                          conv->ndbc);
+    if (fn->live) DNS_TRY(check_live("functionals", fn->ndbc, fn->rows));
     return DNS_OK;
 }
 
@@ -453,9 +523,10 @@ static int quiesce(dns_imex *st) {
 }
 
 // What dns_imex_set_functionals (`moving` false: constant Dirichlet values,
-// three sparse rows per functional) and dns_imex_set_functionals_bc (`moving`:
-// five rows and a table of the values, (nrows + 1) x ndbc) share: every check
-// first -- a refusal leaves the functionals that were there --, then the
+// three sparse rows per functional), dns_imex_set_functionals_bc (`moving`:
+// five rows and a table of the values, (nrows + 1) x ndbc) and
+// dns_imex_set_functionals_live (`moving` and `live`: no table, the attached
+// convection operator's is read) share: every check first -- a refusal leaves the functionals that were there --, then the
 // upload.  Called inside the exports' exception barrier.
 static int set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
                            const dns_csr *cm, const dns_csr *cp,
@@ -464,7 +535,7 @@ static int set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
                            const int32_t *cell_ptr, const int32_t *cell_idx,
                            const double *cell_w, double dt, int32_t nrows,
                            int32_t ndbc, const double *dbc_table,
-                           bool moving) {
+                           bool moving, bool live = false) {
     if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
     DNS_TRY(st->refuse_partitioned("functionals", kFnPartitioned));
@@ -482,9 +553,10 @@ static int set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "functionals: ndbc = %d < 1 (constant Dirichlet "
                          "values: dns_imex_set_functionals)", (int)ndbc);
-    if (moving && !dbc_table)
+    if (moving && !live && !dbc_table)
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "functionals: no table of the Dirichlet values");
+    if (live) DNS_TRY(st->check_live("functionals", ndbc, nrows));
     const int nterms = moving ? 5 : 3;
     const dns_csr *terms[5] = {ca, cm, cp, cab, cmb};
     const char *names[5] = {"ca", "cm", "cp", "cab", "cmb"};
@@ -585,12 +657,13 @@ static int set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
     }
     DNS_TRY(keep_or_alloc(f->log, f->log, (size_t)nrows * G * nF));
     DNS_TRY(f->log.zero(s));
-    if (moving) {
+    if (moving && !live) {
         const size_t ng = ((size_t)nrows + 1) * ndbc;
         DNS_TRY(keep_or_alloc(f->gtab, f->gtab, ng));
         DNS_TRY(f->gtab.upload(dbc_table, ng, s));
     }
     f->ndbc = moving ? ndbc : 0;
+    f->live = live;
     f->nF = nF;
     f->G = G;
     f->rows = nrows;
@@ -1048,6 +1121,19 @@ int dns_imex_set_functionals_bc(dns_imex *st, int32_t nF, const dns_csr *ca,
                            cell_idx, cell_w, dt, nrows, ndbc, dbc_table, true);
 } DNS_CAPI_CATCH
 
+int dns_imex_set_functionals_live(dns_imex *st, int32_t nF, const dns_csr *ca,
+                                  const dns_csr *cm, const dns_csr *cp,
+                                  const dns_csr *cab, const dns_csr *cmb,
+                                  const double *c0, const double *scale,
+                                  const int32_t *cell_ptr,
+                                  const int32_t *cell_idx,
+                                  const double *cell_w, double dt,
+                                  int32_t nrows, int32_t ndbc) try {
+    return set_functionals(st, nF, ca, cm, cp, cab, cmb, c0, scale, cell_ptr,
+                           cell_idx, cell_w, dt, nrows, ndbc, nullptr, true,
+                           true);
+} DNS_CAPI_CATCH
+
 int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,
                              double *out) try {
     DNS_TRY(need(st, st && st->fn, "functionals are",
@@ -1174,18 +1260,32 @@ int dns_imex_clear_stats(dns_imex *st) try {
 
 // ---- quadratic functionals (quadratic.hpp) ---------------------------------
 
-int dns_imex_set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
-                            int32_t nQ, const int32_t *mat, const int32_t *lop,
-                            const int32_t *rop, const dns_csr *qa,
-                            const dns_csr *qw, const double *c0,
-                            const double *scale, double dt, int32_t nrows,
-                            int32_t max_grid) try {
+// What dns_imex_set_quadratics (`moving` false: constant Dirichlet values,
+// NV x NV matrices), dns_imex_set_quadratics_bc (`moving`: matrices and rows
+// NV + ndbc wide and a table of the values, (nrows + 1) x ndbc) and
+// dns_imex_set_quadratics_live (`moving` and `live`: no table, the attached
+// convection operator's is read) share.  Called inside the exports' exception
+// barrier.
+static int set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
+                          int32_t nQ, const int32_t *mat, const int32_t *lop,
+                          const int32_t *rop, const dns_csr *qa,
+                          const dns_csr *qw, const double *c0,
+                          const double *scale, double dt, int32_t nrows,
+                          int32_t max_grid, int32_t ndbc,
+                          const double *dbc_table, bool moving, bool live) {
     if (!st || !mats || !mat || !lop || !rop)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
     DNS_TRY(st->refuse_partitioned("quadratics", kQdPartitioned));
-    if (st->conv && st->conv->dbc_rows > 0)
+    if (!moving && st->conv && st->conv->dbc_rows > 0)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "%s", kQdMovingBc);
+    if (moving && ndbc < 1)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "quadratics: ndbc = %d < 1 (constant Dirichlet "
+                         "values: dns_imex_set_quadratics)", (int)ndbc);
+    if (moving && !live && !dbc_table)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "quadratics: no table of the Dirichlet values");
     if (nM < 1 || nM > dns::kQdMaxMats)
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "quadratics: nM = %d outside 1..%d", (int)nM,
@@ -1203,15 +1303,24 @@ int dns_imex_set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
     if (!(dt > 0.0))
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "quadratics: dt must be "
                          "positive");
-    const int nv = h->nv;
+    if (live) DNS_TRY(st->check_live("quadratics", ndbc, nrows));
+    // (the columns behind NV are positions in the operator's values)
+    if (moving && st->conv && st->conv->ndbc != ndbc)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "quadratics: ndbc = %d, the convection operator "
+                         "attached has %d Dirichlet values", (int)ndbc,
+                         st->conv->ndbc);
+    // (`nv`: the width of every matrix and row, NV + ndbc with moving values)
+    const int nv = h->nv + (moving ? ndbc : 0);
     for (int m = 0; m < nM; ++m) {
         // (check_csr: every column index inside [0, ncols))
         DNS_TRY(dns::check_csr(&mats[m], "quadratics: a matrix"));
         if (mats[m].nrows != nv || mats[m].ncols != nv)
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "quadratics: matrix %d must be NV x NV (%d), it "
-                             "is %d x %d", m, nv, (int)mats[m].nrows,
-                             (int)mats[m].ncols);
+                             "quadratics: matrix %d must be %s (%d), it "
+                             "is %d x %d", m,
+                             moving ? "(NV + ndbc) x (NV + ndbc)" : "NV x NV",
+                             nv, (int)mats[m].nrows, (int)mats[m].ncols);
     }
     const dns_csr *lin[2] = {qa, qw};
     const char *lname[2] = {"qa", "qw"};
@@ -1220,8 +1329,9 @@ int dns_imex_set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
         DNS_TRY(dns::check_csr(lin[t], lname[t]));
         if (lin[t]->nrows != nQ || lin[t]->ncols != nv)
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "quadratics: %s must be nQ x NV (%d x %d), it is "
-                             "%d x %d", lname[t], (int)nQ, nv,
+                             "quadratics: %s must be nQ x %s (%d x %d), it is "
+                             "%d x %d", lname[t],
+                             moving ? "(NV + ndbc)" : "NV", (int)nQ, nv,
                              (int)lin[t]->nrows, (int)lin[t]->ncols);
     }
     for (int k = 0; k < nQ; ++k) {
@@ -1320,6 +1430,13 @@ int dns_imex_set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
     DNS_TRY(put(q->c0, cc));
     DNS_TRY(keep_or_alloc(q->log, q->log, (size_t)nrows * G * nQ));
     DNS_TRY(q->log.zero(s));
+    if (moving && !live) {
+        const size_t ng = ((size_t)nrows + 1) * ndbc;
+        DNS_TRY(keep_or_alloc(q->gtab, q->gtab, ng));
+        DNS_TRY(q->gtab.upload(dbc_table, ng, s));
+    }
+    q->ndbc = moving ? ndbc : 0;
+    q->live = live;
     for (int m = 0; m < dns::kQdMaxMats; ++m) q->need[m] = 0;
     for (int k = 0; k < dns::kQdMaxForms; ++k) {
         q->mat[k] = k < nQ ? mat[k] : 0;
@@ -1334,6 +1451,38 @@ int dns_imex_set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
     q->dt = dt;
     st->qd = std::move(q);
     return st->rewind_tables();
+}
+
+int dns_imex_set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
+                            int32_t nQ, const int32_t *mat, const int32_t *lop,
+                            const int32_t *rop, const dns_csr *qa,
+                            const dns_csr *qw, const double *c0,
+                            const double *scale, double dt, int32_t nrows,
+                            int32_t max_grid) try {
+    return set_quadratics(st, nM, mats, nQ, mat, lop, rop, qa, qw, c0, scale,
+                          dt, nrows, max_grid, 0, nullptr, false, false);
+} DNS_CAPI_CATCH
+
+int dns_imex_set_quadratics_bc(dns_imex *st, int32_t nM, const dns_csr *mats,
+                               int32_t nQ, const int32_t *mat,
+                               const int32_t *lop, const int32_t *rop,
+                               const dns_csr *qa, const dns_csr *qw,
+                               const double *c0, const double *scale,
+                               double dt, int32_t nrows, int32_t max_grid,
+                               int32_t ndbc, const double *dbc_table) try {
+    return set_quadratics(st, nM, mats, nQ, mat, lop, rop, qa, qw, c0, scale,
+                          dt, nrows, max_grid, ndbc, dbc_table, true, false);
+} DNS_CAPI_CATCH
+
+int dns_imex_set_quadratics_live(dns_imex *st, int32_t nM, const dns_csr *mats,
+                                 int32_t nQ, const int32_t *mat,
+                                 const int32_t *lop, const int32_t *rop,
+                                 const dns_csr *qa, const dns_csr *qw,
+                                 const double *c0, const double *scale,
+                                 double dt, int32_t nrows, int32_t max_grid,
+                                 int32_t ndbc) try {
+    return set_quadratics(st, nM, mats, nQ, mat, lop, rop, qa, qw, c0, scale,
+                          dt, nrows, max_grid, ndbc, nullptr, true, true);
 } DNS_CAPI_CATCH
 
 int dns_imex_get_quadratics(dns_imex *st, int32_t first, int32_t count,

@@ -13,10 +13,20 @@
 // over it: per matrix the products s0 = Q v and / or s1 = Q w are formed, as
 // some form on it needs them.
 //
+// Moving Dirichlet values (QdBcArgs): the forms stand on the full space,
+// n = nv + ndbc rows and columns per matrix in the order [inner dofs;
+// Dirichlet dofs], the operands are a_0 = u = [v; g] and a_1 = d = [v - v_prev;
+// g - g_prev] with g, g_prev rows `counter`, `counter - 1` of a table of the
+// Dirichlet values (row j: the values of the state before step j, the row
+// convention of FnBcArgs) -- the stepper's own copy or the convection
+// operator's live table, which k_lti_bc_step writes.
+//
 // No workgroup waits for another and nothing is added atomically: workgroup g
 // writes its share of y_k to log[row][g][k] in a fixed order, the getter sums
 // g in index order -- the same bits in every run, launched or replayed.
 #pragma once
+#include <type_traits>
+
 #include "kernels.hpp"
 
 namespace dns {
@@ -53,17 +63,31 @@ struct QdArgs {
     double *log;                        // nrows x G x nQ
 };
 
+// Moving Dirichlet values: `gtab` holds `trows` rows of `ndbc` values each
+// (one behind the other); in the prologue of step s (counter s) the state is
+// the one before step s: its values are row s, those of the state before it row
+// s - 1; the closing launch reads row nrows (trows >= nrows + 1).  Matrices and
+// sparse rows are nv + ndbc wide, the row pointers nM x (nv + ndbc + 1).  The
+// kernel is instantiated per argument type, so the instance for constant
+// values takes QdArgs as it stands.
+struct QdBcArgs : QdArgs {
+    const double *gtab;
+    int ndbc;
+    int trows;
+};
+
 // passes over one matrix: kQdRows rows each, so that a pass never holds rows
 // of two matrices (what it forms is uniform over the workgroup)
 inline unsigned quadratic_form_bits(int mat, int lop, int rop) {
     return (unsigned)mat | (unsigned)lop << 2 | (unsigned)rop << 3;
 }
 
-inline int quadratic_passes(int nv) { return (nv + kQdRows - 1) / kQdRows; }
+// (`n`: the rows of a matrix, nv or nv + ndbc)
+inline int quadratic_passes(int n) { return (n + kQdRows - 1) / kQdRows; }
 
 // enough workgroups for one pass each, capped (`max_grid` > 0: lower)
-inline int quadratic_grid(int nM, int nv, int max_grid) {
-    int g = std::min(nM * quadratic_passes(nv), kQdMaxGrid);
+inline int quadratic_grid(int nM, int n, int max_grid) {
+    int g = std::min(nM * quadratic_passes(n), kQdMaxGrid);
     if (max_grid > 0) g = std::min(g, max_grid);
     return std::max(1, g);
 }
@@ -79,11 +103,23 @@ inline int quadratic_grid(int nM, int nv, int max_grid) {
 // order.  Sparse rows: one wave per row, the waves of the whole grid stride
 // over the 2 nQ rows, wave_sum (k_functional_step's).
 //
-// NOTHING the kernel loads depends on the counter: it is asked for first and
-// looked at last, where it gives the row to store to (or none: the launch in
-// front of the first step after the forms were set, whose sums are dropped).
+// Constant Dirichlet values (ARGS = QdArgs): NOTHING the kernel loads depends
+// on the counter: it is asked for first and looked at last, where it gives the
+// row to store to (or none: the launch in front of the first step after the
+// forms were set, whose sums are dropped).  Moving ones (QdBcArgs): the counter
+// selects the two table rows, clamped to [0, trows - 1] (the launch in front of
+// the first step takes row 0 twice and drops its sums): every address is valid
+// whatever the counter says.  Only the gathers from the table wait for it: a
+// column c goes to x / xp with the index c < nv ? c : 0 -- a load that does not
+// know the counter, issued as in the constant instance -- and, right behind
+// it and without a branch, to the table with the index c < nv ? 0 : c - nv;
+// the value is selected once both are there, so no column pays a second,
+// dependent round trip.  The row pointers, the matrix stream and the inner
+// left operands do not depend on the counter either.
 // The divisions by dt happen once per form, on the workgroup's share.
-__global__ void __launch_bounds__(kBlock) k_quadratic_step(QdArgs a) {
+template <typename ARGS>
+__global__ void __launch_bounds__(kBlock) k_quadratic_step(ARGS a) {
+    constexpr bool kBc = std::is_same<ARGS, QdBcArgs>::value;
     constexpr int kWaves = kBlock / kWave;
     __shared__ double rowsum[2 * kQdMaxForms];
     __shared__ double red[kQdMaxMats * 4 * kWaves];
@@ -92,13 +128,23 @@ __global__ void __launch_bounds__(kBlock) k_quadratic_step(QdArgs a) {
     const int step = *a.stepctr;
     const int grp = tid / kQdLanes, sub = tid % kQdLanes;
     const int nv = a.nv;
+    // (n: rows and columns of a matrix)
+    int n = nv;
+    const double *gc = nullptr, *gp = nullptr;
+    if constexpr (kBc) {
+        n = nv + a.ndbc;
+        const int r1 = min(max(step, 0), a.trows - 1);
+        const int r0 = min(max(step - 1, 0), a.trows - 1);
+        gc = a.gtab + (size_t)r1 * a.ndbc;
+        gp = a.gtab + (size_t)r0 * a.ndbc;
+    }
     double sc = 0.0, c0 = 0.0;
     if (tid < a.nQ) {
         sc = a.scale[tid];
         c0 = a.c0[tid];
     }
     // ---- matrices ----
-    const int ppm = (nv + kQdRows - 1) / kQdRows;
+    const int ppm = (n + kQdRows - 1) / kQdRows;
     for (int m = 0; m < a.nM; ++m) {
         long long base = a.nzbase[0];
 #pragma unroll
@@ -106,7 +152,7 @@ __global__ void __launch_bounds__(kBlock) k_quadratic_step(QdArgs a) {
             base = m == q ? a.nzbase[q] : base;
         const int *__restrict__ ci = a.ci + base;
         const double *__restrict__ va = a.va + base;
-        const int *__restrict__ rpm = a.rp + (size_t)m * (nv + 1);
+        const int *__restrict__ rpm = a.rp + (size_t)m * (n + 1);
         const unsigned need = a.need >> (2 * m);
         const bool n0 = need & 1, n1 = need & 2;
         // (pass j of matrix m is pass m * ppm + j of the grid's stride)
@@ -114,10 +160,22 @@ __global__ void __launch_bounds__(kBlock) k_quadratic_step(QdArgs a) {
         double avv = 0.0, avw = 0.0, awv = 0.0, aww = 0.0;
         for (int pass = first; pass < ppm; pass += G) {
             const int i = pass * kQdRows + grp;
-            const bool live = i < nv;
+            const bool live = i < n;
             int k0 = 0, k1 = 0;
             double vi = 0.0, vpi = 0.0;
-            if (live) {
+            if constexpr (kBc) {
+                if (live) {
+                    k0 = rpm[i];
+                    k1 = rpm[i + 1];
+                    if (i < nv) {
+                        vi = a.x[i];
+                        vpi = a.xp[i];
+                    } else {
+                        vi = gc[i - nv];
+                        vpi = gp[i - nv];
+                    }
+                }
+            } else if (live) {
                 k0 = rpm[i];
                 k1 = rpm[i + 1];
                 vi = a.x[i];
@@ -133,10 +191,39 @@ __global__ void __launch_bounds__(kBlock) k_quadratic_step(QdArgs a) {
                     c[j] = kk < k1 ? ci[kk] : 0;
                     q[j] = kk < k1 ? va[kk] : 0.0;
                 }
+                if constexpr (kBc) {
+                    // inner part first (an index of its own for the boundary
+                    // columns: no load of x / xp knows the table rows)
+                    // (the table's values land in registers of their own:
+                    // their loads go out behind the inner ones without
+                    // waiting for them)
+                    double xq[kQdUnroll], gv[kQdUnroll], gq[kQdUnroll];
 #pragma unroll
-                for (int j = 0; j < kQdUnroll; ++j) {
-                    xv[j] = a.x[c[j]];
-                    xw[j] = n1 ? xv[j] - a.xp[c[j]] : 0.0;
+                    for (int j = 0; j < kQdUnroll; ++j) {
+                        const int cx = c[j] < nv ? c[j] : 0;
+                        xv[j] = a.x[cx];
+                        xq[j] = n1 ? a.xp[cx] : 0.0;
+                    }
+#pragma unroll
+                    for (int j = 0; j < kQdUnroll; ++j) {
+                        // (no branch: an inner column reads entry 0, one
+                        // line for all of them)
+                        const int cg = c[j] < nv ? 0 : c[j] - nv;
+                        gv[j] = gc[cg];
+                        gq[j] = n1 ? gp[cg] : 0.0;
+                    }
+#pragma unroll
+                    for (int j = 0; j < kQdUnroll; ++j) {
+                        const bool in = c[j] < nv;
+                        xv[j] = in ? xv[j] : gv[j];
+                        xw[j] = n1 ? xv[j] - (in ? xq[j] : gq[j]) : 0.0;
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < kQdUnroll; ++j) {
+                        xv[j] = a.x[c[j]];
+                        xw[j] = n1 ? xv[j] - a.xp[c[j]] : 0.0;
+                    }
                 }
 #pragma unroll
                 for (int j = 0; j < kQdUnroll; ++j) {
@@ -183,9 +270,22 @@ __global__ void __launch_bounds__(kBlock) k_quadratic_step(QdArgs a) {
                 c[j] = kk < k1 ? a.lci[kk] : 0;
                 q[j] = kk < k1 ? a.lva[kk] : 0.0;
             }
+            if constexpr (kBc) {
 #pragma unroll
-            for (int j = 0; j < kQdUnroll; ++j)
-                xv[j] = diff ? a.x[c[j]] - a.xp[c[j]] : a.x[c[j]];
+                for (int j = 0; j < kQdUnroll; ++j) {
+                    // (as in the matrix part: x / xp with an index that does
+                    // not know the table, the table's entry beside it)
+                    const bool in = c[j] < nv;
+                    const int cx = in ? c[j] : 0, cg = in ? 0 : c[j] - nv;
+                    const double xi = diff ? a.x[cx] - a.xp[cx] : a.x[cx];
+                    const double gi = diff ? gc[cg] - gp[cg] : gc[cg];
+                    xv[j] = in ? xi : gi;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < kQdUnroll; ++j)
+                    xv[j] = diff ? a.x[c[j]] - a.xp[c[j]] : a.x[c[j]];
+            }
 #pragma unroll
             for (int j = 0; j < kQdUnroll; ++j)
                 s = k + j * kWave < k1 ? fma(q[j], xv[j], s) : s;

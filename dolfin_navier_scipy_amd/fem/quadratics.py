@@ -23,6 +23,16 @@ space
 and the difference of two states has no boundary part.  Forms that share a
 matrix (the same object) share it on the device: `1/2 v^T M v`, `v^T M w` and
 `w^T M w` read `M` once per step.
+
+Moving Dirichlet values (`ndbc > 0`): the forms stand on the full space.  Every
+matrix is `(NV + ndbc) x (NV + ndbc)` in the order `[inner dofs; Dirichlet
+dofs]` -- the Dirichlet dofs in the loop's order, `static_dbcvals` then the
+controlled ones, the convention of `MomentumFunctionals.cab` --, the rows
+`qa`, `qw` are `nQ x (NV + ndbc)`, and the operands are `a_0 = u = [v; g]`,
+`a_1 = d = [v - v_prev; g - g_prev]` with the Dirichlet values `g`, `g_prev` of
+the two states: nothing of `g` is folded into constants (the builders'
+`moving=True`; `ImexStepper.set_quadratics(..., dbc_table=)`,
+`dns_imex_set_quadratics_bc`).
 """
 import weakref
 
@@ -50,26 +60,31 @@ class QuadraticFunctionals(object):
     is the same object in both is kept once), `scaled(factors)` multiplies the
     scales.  The device takes at most 8 forms over at most 4 matrices."""
 
-    def __init__(self, NV):
+    def __init__(self, NV, ndbc=0):
         self.NV = int(NV)
+        self.ndbc = int(ndbc)
+        if self.ndbc < 0:
+            raise ValueError('`ndbc` must not be negative')
         self.mats = []
         self.mat = np.zeros(0, dtype=np.int32)
         self.lop = np.zeros(0, dtype=np.int32)
         self.rop = np.zeros(0, dtype=np.int32)
-        self.qa = sps.csr_matrix((0, self.NV))
-        self.qw = sps.csr_matrix((0, self.NV))
+        self.qa = sps.csr_matrix((0, self.N))
+        self.qw = sps.csr_matrix((0, self.N))
         self.c0, self.scale = np.zeros(0), np.zeros(0)
         self.names = []
 
     @classmethod
     def from_matrices(cls, NV, mats, forms, qa=None, qw=None, c0=None,
-                      scale=None, names=None):
+                      scale=None, names=None, ndbc=0):
         """`mats`: the matrices (`NV x NV`), `forms`: a list of `(mat, lop,
         rop)` -- index into `mats`, left and right operand (0: `v`, 1:
         `v - v_prev`); `qa`, `qw`: `nQ x NV` sparse rows (None: no such
-        term), `c0`, `scale`: `nQ` values (None: 0 / 1)"""
-        new = cls(NV)
-        NV = new.NV
+        term), `c0`, `scale`: `nQ` values (None: 0 / 1).  With `ndbc > 0`
+        (moving Dirichlet values) matrices and rows are `NV + ndbc` wide,
+        `[inner dofs; Dirichlet dofs]`"""
+        new = cls(NV, ndbc)
+        NV = new.N      # (the width of every matrix and row)
         mats = list(mats)
         forms = [tuple(int(i) for i in f) for f in forms]
         nQ = len(forms)
@@ -103,6 +118,11 @@ class QuadraticFunctionals(object):
         return new
 
     @property
+    def N(self):
+        """the width of the matrices and rows: `NV + ndbc`"""
+        return self.NV + self.ndbc
+
+    @property
     def nQ(self):
         return self.scale.size
 
@@ -113,6 +133,11 @@ class QuadraticFunctionals(object):
     def __add__(self, other):
         if other.NV != self.NV:
             raise ValueError('quadratics of different problems')
+        if other.ndbc != self.ndbc:
+            raise ValueError(
+                'quadratics of different `ndbc` ({0} and {1}): forms with '
+                'constant and with moving Dirichlet values do not '
+                'stack'.format(self.ndbc, other.ndbc))
         mats = list(self.mats)
         where = []
         for m in other.mats:
@@ -122,7 +147,7 @@ class QuadraticFunctionals(object):
             else:
                 where.append(len(mats))
                 mats.append(m)
-        new = QuadraticFunctionals(self.NV)
+        new = QuadraticFunctionals(self.NV, self.ndbc)
         new.mats = mats
         new.mat = np.concatenate(
             [self.mat, np.array(where, dtype=np.int32)[other.mat]]
@@ -139,7 +164,7 @@ class QuadraticFunctionals(object):
     def scaled(self, factors):
         """a copy whose scales are multiplied by `factors` (a number or one
         per form); the matrices are shared"""
-        new = QuadraticFunctionals(self.NV)
+        new = QuadraticFunctionals(self.NV, self.ndbc)
         new.mats = self.mats
         new.mat, new.lop, new.rop = self.mat, self.lop, self.rop
         new.qa, new.qw, new.c0 = self.qa, self.qw, self.c0
@@ -154,7 +179,15 @@ class QuadraticFunctionals(object):
         """`dict(mats, mat, lop, rop, qa, qw, c0, scale)` in the layout of
         `dns_imex_set_quadratics`: the list of CSR matrices, three int32
         arrays of `nQ` entries, the sparse rows `nQ x NV` and two float64
-        arrays of `nQ` entries"""
+        arrays of `nQ` entries.  With moving Dirichlet values also `ndbc`
+        (> 0), the number of Dirichlet dofs behind the inner ones: matrices
+        and rows are `NV + ndbc` wide (`dns_imex_set_quadratics_bc`)"""
+        args = self._device_args()
+        if self.ndbc > 0:
+            args['ndbc'] = self.ndbc
+        return args
+
+    def _device_args(self):
         return dict(mats=list(self.mats),
                     mat=np.ascontiguousarray(self.mat, dtype=np.int32),
                     lop=np.ascontiguousarray(self.lop, dtype=np.int32),
@@ -164,8 +197,12 @@ class QuadraticFunctionals(object):
                     scale=np.ascontiguousarray(self.scale, dtype=np.float64))
 
     # -- the NumPy statement ----------------------------------------------
-    def evaluate(self, v, v_prev, dt, return_scale=False):
-        """`y (nQ,)` for inner velocities `v`, `v_prev`; with `return_scale`
+    def evaluate(self, v, v_prev, dt, return_scale=False, dbc=None,
+                 dbc_prev=None):
+        """`y (nQ,)` for inner velocities `v`, `v_prev` (`ndbc > 0`: and the
+        Dirichlet values `dbc`, `dbc_prev` of the two states, which the
+        operands go on with -- the boundary products count in `T_k`, `n_k`
+        like any other); with `return_scale`
         also `T_k`, the sum of the absolute values of every product of form
         k as it enters `y_k` (the matrix entries `|a_i Q_ij b_j|`, the rows'
         `|qa_j v_j|`, `|qw_j w_j|` and `|c0_k|`, with the powers of `dt` and
@@ -175,6 +212,19 @@ class QuadraticFunctionals(object):
         NV = self.NV
         v = np.asarray(v, dtype=np.float64).reshape(-1)[:NV]
         w = v - np.asarray(v_prev, dtype=np.float64).reshape(-1)[:NV]
+        if self.ndbc > 0:
+            if dbc is None or dbc_prev is None:
+                raise ValueError(
+                    'quadratics with moving Dirichlet values (ndbc = {0}) '
+                    'need `dbc` and `dbc_prev`'.format(self.ndbc))
+            g, gp = (np.asarray(x, dtype=np.float64).reshape(-1)
+                     for x in (dbc, dbc_prev))
+            if g.size != self.ndbc or gp.size != self.ndbc:
+                raise ValueError(
+                    '`dbc`, `dbc_prev`: {0} and {1} values, the forms were '
+                    'built for {2}'.format(g.size, gp.size, self.ndbc))
+            v, w = np.concatenate([v, g]), np.concatenate([w, g - gp])
+            NV = self.N
         ops = (v, w)
         prod = {}
         y = np.zeros(self.nQ)
@@ -249,45 +299,89 @@ def _problem_mats(th, femp):
     return cache[key]
 
 
+def _full_mats(th, femp):
+    """`M` and `A` of a problem on `[inner dofs; Dirichlet dofs]`, the
+    Dirichlet dofs in the order of `femp['dbcinds']`: `Q[perm][:, perm]` with
+    `perm = invinds ++ dbcinds`, built once per space, viscosity and index
+    sets (the moving builders share them: the same objects stack to ONE matrix
+    each)"""
+    inv = np.asarray(femp['invinds'], dtype=np.int64)
+    dbi = np.asarray(femp['dbcinds'], dtype=np.int64)
+    key = ('full', float(femp['nu']), inv.tobytes(), dbi.tobytes())
+    cache = _blocks.setdefault(th, {})
+    if key not in cache:
+        stms = th.stokes_mats(nu=femp['nu'])
+        perm = np.concatenate([inv, dbi])
+
+        def full(Q):
+            Q = sps.csr_matrix(sps.csr_matrix(Q)[perm, :][:, perm])
+            Q.sum_duplicates()
+            Q.sort_indices()
+            return Q
+        cache[key] = dict(M=full(stms['M']), A=full(stms['A']), NV=inv.size,
+                          ndbc=dbi.size)
+    return cache[key]
+
+
+def _moving(th, femp, which, form, name, scale=None):
+    blk = _full_mats(th, femp)
+    return QuadraticFunctionals.from_matrices(
+        blk['NV'], [blk[which]], [form], scale=scale, names=[name],
+        ndbc=blk['ndbc'])
+
+
 def _row(vec):
     return sps.csr_matrix(np.asarray(vec, dtype=np.float64).reshape((1, -1)))
 
 
-def kinetic_energy(th, femp, name='ekin'):
-    """`1/2 u^T M u` of the full velocity `u` (Dirichlet values included)"""
+def kinetic_energy(th, femp, name='ekin', moving=False):
+    """`1/2 u^T M u` of the full velocity `u` (Dirichlet values included);
+    `moving`: on the full space, the Dirichlet values come with the state"""
+    if moving:
+        return _moving(th, femp, 'M', (0, 0, 0), name, scale=[.5])
     Mii, left, right, const = _problem_mats(th, femp)['M']
     return QuadraticFunctionals.from_matrices(
         Mii.shape[0], [Mii], [(0, 0, 0)], qa=_row(left + right), c0=[const],
         scale=[.5], names=[name])
 
 
-def dissipation(th, femp, name='dissipation'):
+def dissipation(th, femp, name='dissipation', moving=False):
     """`u^T A u`: `nu/2 int |grad u + grad u^T|^2` with the symmetric-gradient
-    `A` of `TaylorHood.stokes_mats`"""
+    `A` of `TaylorHood.stokes_mats`; `moving`: on the full space"""
+    if moving:
+        return _moving(th, femp, 'A', (0, 0, 0), name)
     Aii, left, right, const = _problem_mats(th, femp)['A']
     return QuadraticFunctionals.from_matrices(
         Aii.shape[0], [Aii], [(0, 0, 0)], qa=_row(left + right), c0=[const],
         names=[name])
 
 
-def kinetic_energy_rate(th, femp, name='ekin_rate'):
-    """`u^T M (u - u_prev)/dt`; the boundary values do not move, so `u -
-    u_prev` lives on the inner dofs: `(v^T M_ii w + g^T M_bi w)/dt`"""
+def kinetic_energy_rate(th, femp, name='ekin_rate', moving=False):
+    """`u^T M (u - u_prev)/dt`; where the boundary values do not move `u -
+    u_prev` lives on the inner dofs: `(v^T M_ii w + g^T M_bi w)/dt`; `moving`:
+    on the full space, `u - u_prev` includes `g - g_prev`"""
+    if moving:
+        return _moving(th, femp, 'M', (0, 0, 1), name)
     Mii, left, _, _ = _problem_mats(th, femp)['M']
     return QuadraticFunctionals.from_matrices(
         Mii.shape[0], [Mii], [(0, 0, 1)], qw=_row(left), names=[name])
 
 
-def rate_norm(th, femp, name='rate_norm'):
+def rate_norm(th, femp, name='rate_norm', moving=False):
     """`d^T M d` with `d = (u - u_prev)/dt`: the squared M-norm of the
-    discrete time derivative"""
+    discrete time derivative; `moving`: `d` includes `(g - g_prev)/dt`"""
+    if moving:
+        return _moving(th, femp, 'M', (0, 1, 1), name)
     Mii = _problem_mats(th, femp)['M'][0]
     return QuadraticFunctionals.from_matrices(
         Mii.shape[0], [Mii], [(0, 1, 1)], names=[name])
 
 
-def energy_budget(th, femp):
+def energy_budget(th, femp, moving=False):
     """the four together: `ekin`, `dissipation`, `ekin_rate`, `rate_norm`
-    over two matrices"""
-    return kinetic_energy(th, femp) + dissipation(th, femp) \
-        + kinetic_energy_rate(th, femp) + rate_norm(th, femp)
+    over two matrices; `moving`: with moving Dirichlet values (`ndbc =
+    len(femp['dbcinds'])`)"""
+    return kinetic_energy(th, femp, moving=moving) \
+        + dissipation(th, femp, moving=moving) \
+        + kinetic_energy_rate(th, femp, moving=moving) \
+        + rate_norm(th, femp, moving=moving)

@@ -743,15 +743,28 @@ class ImexStepper(object):
         the last one; row `s` of the log is then `fn.evaluate(..., dbc=
         dbc_table[s + 1], dbc_prev=dbc_table[s])`
         (`dns_imex_set_functionals_bc`).  The table is the functionals' own:
-        the operator's (`set_dbc_table`) keeps its meaning and length."""
+        the operator's (`set_dbc_table`) keeps its meaning and length.
+
+        `dbc_table='operator'`: no table of their own -- the values are read
+        from the table of the attached convection operator (`conv.
+        set_dbc_table`, at least `nrows + 1` rows of the functionals' width,
+        the same row convention), which a resident `BoundaryFeedback` writes
+        step by step (`dns_imex_set_functionals_live`)."""
         nrows = int(nrows)
         if nrows < 1:
             raise ValueError('`nrows` must be positive')
+        live = isinstance(dbc_table, str)
+        if live and dbc_table != 'operator':
+            raise ValueError('`dbc_table`: a table or the string '
+                             '\'operator\', not {0!r}'.format(dbc_table))
         moving = dbc_table is not None
         args = fn.device_args(moving=True) if moving else fn.device_args()
         nF = int(args['scale'].size)
         terms = [('ca', self.sys.NV), ('cm', self.sys.NV), ('cp', self.sys.NP)]
-        if moving:
+        if live:
+            ndbc = int(args['cab'].shape[1])
+            terms += [('cab', ndbc), ('cmb', ndbc)]
+        elif moving:
             tab = np.ascontiguousarray(dbc_table, dtype=np.float64)
             if tab.ndim != 2 or tab.shape[0] != nrows + 1:
                 raise ValueError('`dbc_table` must have nrows + 1 = {0} rows, '
@@ -777,7 +790,10 @@ class ImexStepper(object):
         refs = [None if v is None else v.byref() for v in views]
         tail = (C.dptr(c0), C.dptr(scale), cptr.ctypes.data_as(C.c_int32_p),
                 cidx.ctypes.data_as(C.c_int32_p), C.dptr(cw), float(dt), nrows)
-        if moving:
+        if live:
+            C.check(self.lib.dns_imex_set_functionals_live(
+                self._h, nF, *refs, *tail, ndbc))
+        elif moving:
             C.check(self.lib.dns_imex_set_functionals_bc(
                 self._h, nF, *refs, *tail, ndbc, C.dptr(tab.reshape(-1))))
         else:
@@ -877,7 +893,7 @@ class ImexStepper(object):
                     s2_v=s2[:, :NV].copy(), s2_p=s2[:, NV:].copy(), sx=sx)
 
     # ---- quadratic functionals (`dns_imex_set_quadratics`) ------------------
-    def set_quadratics(self, qf, nrows, dt, max_grid=None):
+    def set_quadratics(self, qf, nrows, dt, max_grid=None, dbc_table=None):
         """the next `nrows` steps (`step` and `run` alike) evaluate the
         quadratic forms `qf` (`fem.QuadraticFunctionals`: kinetic energy,
         dissipation rate, `u^T M du/dt`, the M-norm of `du/dt`, ...; at most 8
@@ -889,12 +905,42 @@ class ImexStepper(object):
         one, and collect with `get_quadratics` before the next tables).  The
         log takes `nrows x G x nQ` doubles, `G` the workgroups of the kernel
         (at most 256): `max_grid` caps it lower.  Matrices the device holds
-        already are not uploaded again."""
+        already are not uploaded again.
+
+        Forms with moving Dirichlet values (`qf.ndbc > 0`: the builders'
+        `moving=True`) need `dbc_table` (`(nrows + 1, ndbc)`): row `j` holds
+        the values of the state BEFORE the `j`-th step from now, row `nrows`
+        those of the state after the last one; row `s` of the log is then
+        `qf.evaluate(..., dbc=dbc_table[s + 1], dbc_prev=dbc_table[s])`
+        (`dns_imex_set_quadratics_bc`; the table is the quadratics' own).
+        `dbc_table='operator'`: the values are read from the table of the
+        attached convection operator instead, which a resident
+        `BoundaryFeedback` writes step by step
+        (`dns_imex_set_quadratics_live`)."""
         nrows = int(nrows)
         if nrows < 1:
             raise ValueError('`nrows` must be positive')
+        live = isinstance(dbc_table, str)
+        if live and dbc_table != 'operator':
+            raise ValueError('`dbc_table`: a table or the string '
+                             '\'operator\', not {0!r}'.format(dbc_table))
         args = qf.device_args()
-        NV = self.sys.NV
+        ndbc = int(args.get('ndbc', 0))
+        if ndbc > 0 and dbc_table is None:
+            raise ValueError(
+                'quadratics with moving Dirichlet values (ndbc = {0}) need '
+                '`dbc_table`: the rows of values or \'operator\''.format(ndbc))
+        if ndbc == 0 and dbc_table is not None:
+            raise ValueError(
+                '`dbc_table` with quadratics that carry constant Dirichlet '
+                'values (ndbc = 0): build them with `moving=True`')
+        if ndbc > 0 and not live:
+            tab = np.ascontiguousarray(dbc_table, dtype=np.float64)
+            if tab.ndim != 2 or tab.shape != (nrows + 1, ndbc):
+                raise ValueError(
+                    '`dbc_table` must be (nrows + 1) x ndbc = {0} x {1}, it '
+                    'is {2}'.format(nrows + 1, ndbc, tab.shape))
+        NV = self.sys.NV + ndbc
         nQ = int(args['scale'].size)
         mats = args['mats']
         for m, mat in enumerate(mats):
@@ -916,12 +962,18 @@ class ImexStepper(object):
         forms = [np.ascontiguousarray(args[k], dtype=np.int32)
                  for k in ('mat', 'lop', 'rop')]
         c0, scale = C.as_f64(args['c0'], nQ), C.as_f64(args['scale'], nQ)
-        C.check(self.lib.dns_imex_set_quadratics(
-            self._h, len(views), structs, nQ,
-            *[f.ctypes.data_as(C.c_int32_p) for f in forms],
-            *[None if v is None else v.byref() for v in lin],
-            C.dptr(c0), C.dptr(scale), float(dt), nrows,
-            0 if max_grid is None else int(max_grid)))
+        head = (self._h, len(views), structs, nQ,
+                *[f.ctypes.data_as(C.c_int32_p) for f in forms],
+                *[None if v is None else v.byref() for v in lin],
+                C.dptr(c0), C.dptr(scale), float(dt), nrows,
+                0 if max_grid is None else int(max_grid))
+        if live:
+            C.check(self.lib.dns_imex_set_quadratics_live(*head, ndbc))
+        elif ndbc > 0:
+            C.check(self.lib.dns_imex_set_quadratics_bc(
+                *head, ndbc, C.dptr(tab.reshape(-1))))
+        else:
+            C.check(self.lib.dns_imex_set_quadratics(*head))
         self._qd_shape = (nrows, nQ)
 
     def clear_quadratics(self):

@@ -419,8 +419,11 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     outputs are the gains of the controlled boundaries, `b = gain_k *
     diricontbcvals[k]`; the explicit schemes then run resident without
     `bcs_time_only` (`LAST_RUN['feedback'] == 'resident-boundary'`), any other
-    state-dependent function keeps the per-step path; `functionals`,
-    `quadratics`, `rom` beside it are a `ValueError`.
+    state-dependent function keeps the per-step path; `functionals` and
+    `quadratics` beside it stay on the device -- they read the Dirichlet
+    values the observer writes there -- and must be built for the controlled
+    boundary (`functionals` as above, `quadratics` with `moving=True`;
+    `ValueError` otherwise); `rom` beside it is a `ValueError`.
     `statistics` (explicit schemes): a
     `fem.FlowStatistics` over the inner dofs and the pressure -- handed down
     to the loop (`resident=dict(statistics=...)`), which adds the state after
@@ -434,8 +437,13 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
     evaluates it after every AB2 / BDF2 step, on the device where it runs
     resident; `time_int_utils.LAST_RUN['quadratics']`, `['quadratics_t']`,
     `['quadratics_on']`, `['quadratics_names']` hold the rows, their times,
-    where they came from and the forms' names.  Constant Dirichlet values
-    only (`ValueError` with controlled boundaries).  `pod` (explicit
+    where they came from and the forms' names.  With controlled boundaries
+    the forms stand on the full space (the builders' `moving=True`, with
+    `invinds` and `dbcinds` as for `functionals`): they follow the
+    controlled values of every state, on the device with
+    `bcs_time_only=True` or a `BoundaryFeedback`, on the host otherwise;
+    forms that carry constant Dirichlet values are a `ValueError` there.
+    `pod` (explicit
     schemes): a `fem.SnapshotPOD` of the condensed problem -- handed down to
     the loop (`resident=dict(pod=...)`), which keeps the snapshots on the
     device where it runs resident and forms Gram matrix and modes there;
@@ -707,6 +715,8 @@ def solve_nse(A=None, M=None, J=None, JT=None, fv=None, fp=None, fvtd=None,
             icd.setdefault('resident', {}).update(statistics=statistics)
         if quadratics is not None:
             icd.setdefault('resident', {}).update(quadratics=quadratics)
+            if not static_bcs:      # (the order of the forms' Dirichlet dofs)
+                icd['resident'].setdefault('static_dbcvals', list(dbcvals))
         if pod is not None:
             icd.setdefault('resident', {}).update(pod=pod)
         if rom is not None:

@@ -597,9 +597,11 @@ class _FunctionalLog(_Attachment):
     controlled (moving) Dirichlet values `arm` takes their rows from `tables`
     -- one more than steps --, `host_row` the values of the two states; the
     loop has `ndbc` of them, static ones included, and the functionals'
-    boundary rows `cab`, `cmb` must be as wide, in that order"""
+    boundary rows `cab`, `cmb` must be as wide, in that order.  `live`
+    (beside a resident `BoundaryFeedback`): the device makes the values, so
+    `arm` points the functionals at the operator's table instead"""
 
-    def __init__(self, stepper, fn, dt, ndbc=None):
+    def __init__(self, stepper, fn, dt, ndbc=None, live=False):
         if ndbc is not None and fn.inv is not None and fn.cab.shape[1] != ndbc:
             raise ValueError(
                 '`functionals` with controlled (moving) Dirichlet values: '
@@ -607,11 +609,16 @@ class _FunctionalLog(_Attachment):
                 '(`static_dbcvals` then the controlled ones: build them with '
                 '`dbcinds` in that order)'.format(fn.cab.shape[1], ndbc))
         self.stepper, self.fn, self.dt = stepper, fn, dt
+        self.live = live
         self.ys, self.ts = [], []
         self.where = None
         self.names = None if fn is None else list(fn.names)
 
     def arm(self, times, tables):
+        if self.live:
+            self.stepper.set_functionals(self.fn, len(times), self.dt,
+                                         dbc_table='operator')
+            return
         dbc_rows = tables.dbc
         if dbc_rows is not None and len(dbc_rows) != len(times) + 1:
             raise ValueError('{0} steps need {1} rows of Dirichlet values, '
@@ -651,19 +658,50 @@ class _QuadraticLog(_Attachment):
     quadratics per slice (or chunk) next to the tables -- the matrices stay on
     the device from slice to slice --, collects the rows of the device's log
     and their times; where the loop takes one step at a time the same rows
-    come from `qf.evaluate` on the host.  The forms carry CONSTANT Dirichlet
-    values: a loop with moving ones is refused"""
+    come from `qf.evaluate` on the host.  Forms that carry CONSTANT Dirichlet
+    values (`qf.ndbc == 0`) are for loops without moving ones (`ndbc` None).
+    With controlled (moving) Dirichlet values `arm` takes their rows from
+    `tables` -- one more than steps --, `host_row` the values of the two
+    states; the loop has `ndbc` of them, static ones included, and the forms
+    must stand on `NV + ndbc` dofs, the Dirichlet dofs in that order.  `live`
+    (beside a resident `BoundaryFeedback`): `arm` points the forms at the
+    operator's table, which the device writes"""
 
-    def __init__(self, stepper, qf, dt, max_grid=None):
+    def __init__(self, stepper, qf, dt, max_grid=None, ndbc=None,
+                 live=False):
+        if ndbc is not None and qf.ndbc == 0:
+            raise ValueError(
+                '`quadratics` with moving Dirichlet values: the forms carry '
+                'the boundary values as constants (build them with '
+                '`moving=True`)')
+        if (ndbc or 0) != qf.ndbc:
+            raise ValueError(
+                '`quadratics` with controlled (moving) Dirichlet values: '
+                'they were built for {0} Dirichlet dofs, the loop has {1} '
+                '(`static_dbcvals` then the controlled ones: build them with '
+                '`dbcinds` in that order)'.format(qf.ndbc, ndbc or 0))
         self.stepper, self.qf, self.dt = stepper, qf, dt
+        self.live = live
         self.max_grid = max_grid
         self.ys, self.ts = [], []
         self.where = None
         self.names = list(qf.names)
 
     def arm(self, times, tables):
+        if self.qf.ndbc == 0:
+            self.stepper.set_quadratics(self.qf, len(times), self.dt,
+                                        max_grid=self.max_grid)
+            return
+        dbc_rows = 'operator' if self.live else tables.dbc
+        if not self.live and (dbc_rows is None
+                              or len(dbc_rows) != len(times) + 1):
+            raise ValueError('{0} steps need {1} rows of Dirichlet values, '
+                             'got {2}'.format(
+                                 len(times), len(times) + 1,
+                                 None if dbc_rows is None else len(dbc_rows)))
         self.stepper.set_quadratics(self.qf, len(times), self.dt,
-                                    max_grid=self.max_grid)
+                                    max_grid=self.max_grid,
+                                    dbc_table=dbc_rows)
 
     def collect(self, times):
         self.add(self.stepper.get_quadratics(0, len(times)), times)
@@ -674,7 +712,8 @@ class _QuadraticLog(_Attachment):
         self.ts.extend(times)
 
     def host_row(self, step):
-        self.add(self.qf.evaluate(step.v, step.v_prev, self.dt
+        self.add(self.qf.evaluate(step.v, step.v_prev, self.dt,
+                                  dbc=step.dbc, dbc_prev=step.dbc_prev
                                   ).reshape((1, -1)), [step.time])
         self.where = 'host'
 
@@ -923,31 +962,49 @@ class _ImexLoop(object):
                 and not self.state_dependent:
             # called back every step: its `(y, u)` rows for the report
             self.attachments.append(_HostFeedback(host_bfb))
-        if self.bfb is not None:
-            # (their Dirichlet tables are host-made copies of the values)
-            for key in ('functionals', 'quadratics', 'rom'):
-                if self.rsd.get(key, None) is not None:
+        ndbc = len(self._dbc(self.cur)) if self.moving else None
+        fn = self.rsd.get('functionals', None)
+        qf = self.rsd.get('quadratics', None)
+        live = self.bfb is not None
+        if live:
+            # The boundary values exist on the device only: functionals and
+            # quadratics read the operator's table, which the observer kernel
+            # writes; nothing host-made can stand in for it.
+            if self.rsd.get('rom', None) is not None:
+                raise ValueError(
+                    '`rom` together with a resident `BoundaryFeedback`: '
+                    'constant boundary values only, the mean flow carries '
+                    'them')
+            for key, att, wide in (
+                    ('functionals', fn, lambda a: a.inv is not None
+                     and a.cab.shape[1]),
+                    ('quadratics', qf, lambda a: a.ndbc)):
+                if att is None:
+                    continue
+                try:
+                    have = wide(att)
+                except AttributeError:
+                    have = None
+                if have != ndbc:
                     raise ValueError(
                         '`{0}` together with a resident `BoundaryFeedback`: '
-                        'the boundary values exist on the device only, the '
-                        '{0} read host-made tables'.format(key))
+                        'the boundary values exist on the device only, so '
+                        'the {0} must be built for the loop\'s {1} moving '
+                        'Dirichlet values (`static_dbcvals` then the '
+                        'controlled ones{2})'.format(
+                            key, ndbc,
+                            '; `moving=True`' if key == 'quadratics'
+                            else '; `dbcinds` in that order'))
             self.bfb_att = _ResidentBoundaryFeedback(self.bfb, self, tstart)
             self.attachments.append(self.bfb_att)
-        fn = self.rsd.get('functionals', None)
         flog = None if fn is None else _FunctionalLog(
-            self.stepper, fn, self.dt,
-            ndbc=len(self._dbc(self.cur)) if self.moving else None)
+            self.stepper, fn, self.dt, ndbc=ndbc, live=live)
         if resident_fb:
             self.attachments.append(_ResidentFeedback(
                 lti, self.stepper, self.drm, *self.scheme.fb_weights,
                 dt=self.dt, tstart=tstart))
         fs = self.rsd.get('statistics', None)
-        qf = self.rsd.get('quadratics', None)
         pod = self.rsd.get('pod', None)
-        if qf is not None and self.moving:
-            raise ValueError(
-                '`quadratics` with moving Dirichlet values: the forms carry '
-                'the boundary values as constants')
         rom = self.rsd.get('rom', None)
         if rom is not None:
             if pod is None:
@@ -966,7 +1023,8 @@ class _ImexLoop(object):
             flog, None if fs is None else _StatisticsSums(self.stepper, fs),
             None if qf is None else _QuadraticLog(
                 self.stepper, qf, self.dt,
-                max_grid=self.rsd.get('quadratics_max_grid', None)),
+                max_grid=self.rsd.get('quadratics_max_grid', None),
+                ndbc=ndbc, live=live),
             None if pod is None else _PodEnsemble(
                 self.stepper, pod, trange,
                 keep_snapshots=self.rsd.get('pod_snapshots', False),
@@ -1376,9 +1434,17 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
                         `functionals`: `LAST_RUN['quadratics']` is `nsteps x
                         nQ`, `['quadratics_t']` its times, `['quadratics_on']`
                         'device' or 'host' (`qf.evaluate` per step),
-                        `['quadratics_names']` the forms' names.  Constant
-                        Dirichlet values only: `ValueError` with `bcs_ini` not
-                        empty.  `quadratics_max_grid` caps the workgroups of
+                        `['quadratics_names']` the forms' names.  With
+                        controlled Dirichlet values (`bcs_ini` not empty) the
+                        forms must stand on the full space (the builders'
+                        `moving=True` with `dbcinds` = the static dofs then
+                        the controlled ones, `qf.ndbc` = their number): the
+                        operands `[v; g]`, `[v - v_prev; g - g_prev]` go by
+                        the values of each state, on the device with
+                        `bcs_time_only` (a table of their own per slice), on
+                        the host otherwise; forms that carry the boundary
+                        values as constants (`qf.ndbc == 0`) are a
+                        `ValueError` there.  `quadratics_max_grid` caps the workgroups of
                         the kernel and with them the log (`nsteps x G x nQ`
                         doubles per slice)
       `pod`             a `fem.SnapshotPOD` (weight matrix, which times are
@@ -1437,8 +1503,11 @@ def cnab(trange=None, inivel=None, inip=None, bcs_ini=[],
     controlled values into the convection operator's Dirichlet table, the
     slices are tabulated for `u = 0`; `LAST_RUN['feedback']` says
     'resident-boundary' and `['feedback_bcs']` holds the values of every
-    step.  `functionals`, `quadratics` and `rom` beside it are a
-    `ValueError` (their Dirichlet tables are host-made copies).
+    step.  `functionals` and `quadratics` beside it run on the device too:
+    they read the operator's table, where the observer kernel writes the
+    values (no host-made copy could hold them), and must be built for the
+    loop's moving Dirichlet values (`ValueError` otherwise); `rom` beside it
+    is a `ValueError`.
     Returns `v_n, p_n, ffflag` like the reference.
     """
     return _imex_loop(_CNAB, **locals())

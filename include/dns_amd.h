@@ -634,6 +634,24 @@ int dns_imex_set_functionals_bc(dns_imex *st, int32_t nF, const dns_csr *ca,
                                 const int32_t *cell_idx, const double *cell_w,
                                 double dt, int32_t nrows, int32_t ndbc,
                                 const double *dbc_table);
+/* dns_imex_set_functionals_bc without a table of their own: the Dirichlet
+ * values are read from the table of the attached convection operator
+ * (dns_conv_set_dbc_table) -- row j of it holds the values of the state before
+ * the j-th step, the same convention -- which is what boundary feedback
+ * (dns_imex_set_feedback_boundary) writes step by step: the functionals then
+ * follow the values the observer makes on the device.  Needs, when it is set
+ * and when a step runs (DNS_ERR_BAD_ARGUMENT otherwise, the message names what
+ * is missing): an attached convection operator, its ndbc equal to `ndbc`, and
+ * at least nrows + 1 rows in its table.  Beside boundary feedback only
+ * functionals set this way are accepted. */
+int dns_imex_set_functionals_live(dns_imex *st, int32_t nF, const dns_csr *ca,
+                                  const dns_csr *cm, const dns_csr *cp,
+                                  const dns_csr *cab, const dns_csr *cmb,
+                                  const double *c0, const double *scale,
+                                  const int32_t *cell_ptr,
+                                  const int32_t *cell_idx,
+                                  const double *cell_w, double dt,
+                                  int32_t nrows, int32_t ndbc);
 /* rows [first, first + count) of the log: out (count x nF) */
 int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,
                              double *out);
@@ -709,6 +727,37 @@ int dns_imex_set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
                             const dns_csr *qw, const double *c0,
                             const double *scale, double dt, int32_t nrows,
                             int32_t max_grid);
+/* The same on the full space, with Dirichlet values g that change from step to
+ * step, ndbc of them in the order of the convection operator's dbcinds: every
+ * matrix is (NV + ndbc) x (NV + ndbc) in the order [inner dofs; Dirichlet
+ * dofs], qa and qw are nQ x (NV + ndbc), and the operands are a_0 = u = [v; g]
+ * and a_1 = d = [v - v_prev; g - g_prev]:
+ *     y_k = scale_k * ( dt^-(l_k + r_k) * a_{l_k}^T Q_{m_k} a_{r_k}
+ *                       + qa_k . u + (qw_k . d) / dt + c0_k )
+ * Nothing of g is folded into qa, qw or c0.  dbc_table: row-major (nrows + 1) x
+ * ndbc, row j the values of the state BEFORE the j-th step after this call,
+ * row nrows those of the state after the last one: log row r uses g = row
+ * r + 1, g_prev = row r (the convention of dns_imex_set_functionals_bc; a table
+ * of the quadratics' own).  Further limits: ndbc >= 1, equal to the ndbc of an
+ * attached convection operator -- when it is set and when a step runs.  The
+ * same matrices are kept on the device as with dns_imex_set_quadratics. */
+int dns_imex_set_quadratics_bc(dns_imex *st, int32_t nM, const dns_csr *mats,
+                               int32_t nQ, const int32_t *mat,
+                               const int32_t *lop, const int32_t *rop,
+                               const dns_csr *qa, const dns_csr *qw,
+                               const double *c0, const double *scale,
+                               double dt, int32_t nrows, int32_t max_grid,
+                               int32_t ndbc, const double *dbc_table);
+/* dns_imex_set_quadratics_bc without a table of their own: the values are read
+ * from the table of the attached convection operator, as with
+ * dns_imex_set_functionals_live, with the same three requirements. */
+int dns_imex_set_quadratics_live(dns_imex *st, int32_t nM, const dns_csr *mats,
+                                 int32_t nQ, const int32_t *mat,
+                                 const int32_t *lop, const int32_t *rop,
+                                 const dns_csr *qa, const dns_csr *qw,
+                                 const double *c0, const double *scale,
+                                 double dt, int32_t nrows, int32_t max_grid,
+                                 int32_t ndbc);
 /* rows [first, first + count) of the log: out (count x nQ) */
 int dns_imex_get_quadratics(dns_imex *st, int32_t first, int32_t count,
                             double *out);

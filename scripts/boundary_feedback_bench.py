@@ -15,6 +15,13 @@ process each:
                   every step is a host round trip -- the only route before
   --leg open      `bcs_time_only`: a prescribed rotation, tabulated ahead
 
+`--attach budget` (profiles/r18_closed_loop_budget/README.md) adds drag, lift
+and torque of the cylinder (`functionals`) and the energy budget with moving
+Dirichlet values (`quadratics`, `energy_budget(moving=True)`) to any leg: on
+the device beside the resident feedback (they read the operator's Dirichlet
+table) and in the `open` leg (tables of their own), through `evaluate` on the
+host in the `host` leg.
+
 Timing: the host clock between two `savevp` calls of ONE `cnab` run over
 `warmup + steps` loop steps, cut into slices of `warmup` steps: the call behind
 the first slice and the call behind the last one (a resident slice hands the
@@ -93,7 +100,19 @@ class Setup(object):
         full[self.cntinds, 0] = bcs
         return full
 
-    def run(self, leg, warmup, steps):
+    def attachments(self):
+        """drag, lift, torque of the cylinder and the moving energy budget,
+        built for the loop's Dirichlet dofs (static, then the cylinder's)"""
+        from dolfin_navier_scipy_amd import fem
+        femp = dict(invinds=self.inv, nu=self.femp['nu'],
+                    dbcinds=np.concatenate([self.statinds, self.cntinds]),
+                    dbcvals=np.concatenate([self.statvals, 0.*self.shape]))
+        fn = fem.boundary_forces(self.th, femp) \
+            + fem.boundary_torque(self.th, femp)
+        return dict(functionals=fn,
+                    quadratics=fem.energy_budget(self.th, femp, moving=True))
+
+    def run(self, leg, warmup, steps, attach='none'):
         """one `cnab` call; the host seconds of the `steps` loop steps behind
         the first `warmup`"""
         from dolfin_navier_scipy_amd import time_int_utils as tiu
@@ -110,6 +129,9 @@ class Setup(object):
         marks = {float(trange[warmup + 1]): None, float(trange[-1]): None}
         resident = dict(static_dbcvals=self.statvals.tolist(),
                         savevp_times=list(marks))
+
+        if attach == 'budget':
+            resident.update(self.attachments())
 
         def savevp(vvec, pvec, time=None):
             if time in marks:
@@ -158,8 +180,15 @@ class Setup(object):
         last = tiu.LAST_RUN
         u = last.get('feedback_u')
         t_a, t_b = (marks[k] for k in sorted(marks))
+        rows = {k: (None if last.get(k) is None
+                    else np.asarray(last[k])[-1].tolist())
+                for k in ('functionals', 'quadratics')}
         return dict(seconds=t_b - t_a, steps_per_s=steps/(t_b - t_a),
                     ffflag=int(ff), feedback=last['feedback'],
+                    functionals_on=last.get('functionals_on'),
+                    quadratics_on=last.get('quadratics_on'),
+                    functionals_last=rows['functionals'],
+                    quadratics_last=rows['quadratics'],
                     run_calls=last['run_calls'],
                     krylov_steps=int(last['krylov_steps']),
                     vnorm=float(np.linalg.norm(v)),
@@ -171,6 +200,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--leg', choices=('resident', 'host', 'open'),
                     required=True)
+    ap.add_argument('--attach', choices=('none', 'budget'), default='none')
     ap.add_argument('--steps', type=int, default=400)
     ap.add_argument('--warmup', type=int, default=40)
     ap.add_argument('--repeats', type=int, default=3)
@@ -183,9 +213,9 @@ def main():
     su = Setup(refine=args.refine)
     reps = []
     for _ in range(args.repeats):
-        reps.append(su.run(args.leg, args.warmup, args.steps))
+        reps.append(su.run(args.leg, args.warmup, args.steps, args.attach))
     rates = [r['steps_per_s'] for r in reps]
-    out = dict(leg=args.leg, steps=args.steps, warmup=args.warmup,
+    out = dict(leg=args.leg, attach=args.attach, steps=args.steps, warmup=args.warmup,
                refine=args.refine, device=_capi.device_name(0),
                unknowns=int(sum(su.J.shape)), steps_per_s=rates,
                best=max(rates), worst=min(rates), repeats=reps)
