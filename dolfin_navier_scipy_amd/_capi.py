@@ -127,7 +127,11 @@ class dns_imex_probe(ct.Structure):
                [(k, ct.c_int32) for k in
                 ('parts_cap', 'nsol', 'tab_row', 'has_carry', 'has_six',
                  'form', 'mode', 'use_pre', 'carry', 'k_lpr', 'r1_lpr',
-                 'nparts', 'r1_pair', 'pad')]
+                 'nparts', 'r1_pair', 'pad')] + \
+               [('r_in', c_double_p), ('x0copy', c_double_p),
+                ('rowmap', ct.c_int32*4)] + \
+               [(k, ct.c_int32) for k in
+                ('dcarry', 'dtail', 'have_cells', 'nsel')]
 
 
 # every symbol include/dns_amd.h declares: name -> (restype, argtypes)

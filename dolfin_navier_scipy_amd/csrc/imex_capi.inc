@@ -1355,20 +1355,19 @@ int dns_imex_vnorm(dns_imex *st, double *out) try {
 } DNS_CAPI_CATCH
 
 // TEST ONLY: the front of a step -- what dns_imex_step does before
-// step_device (step_preamble), then the member function prologue() would pick
-// for the plan (front_six / front_fused / front_rows / front_stream), without
-// the attachments' nodes and without a solve -- with a copy out of what the
-// front reads before it runs and of what it has left.  The stepper is consumed.
+// step_device (step_preamble), then what step_device does before its solve
+// (the stepper's row blocks, the turn of a device convection, the plan), then
+// the member function prologue() would pick for the plan (front_six /
+// front_fused / front_dist / front_rows / front_stream), without the
+// attachments' nodes and without a solve -- with a copy out of what the front
+// reads before it runs and of what it has left.  The stepper is consumed.  On a
+// row-partitioned handle the call is COLLECTIVE (gather_state may all-gather).
 int dns_imex_front_probe(dns_imex *st, const dns_imex_coeffs *cf,
                          const dns_solve_opts *opts, int32_t cycle_len,
                          const double *nfc_new, dns_imex_probe *out) try {
     if (!st || !cf || !out || cycle_len < 0 || out->parts_cap < 0)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     dns_saddle *h = st->sys;
-    // (a communicator attached: partitioned at the next set-up at the latest)
-    if (h->comm || h->dist() || h->dist_sliced || h->rank_local || st->part.on)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "the front probe takes an un-partitioned handle");
     if (st->fb || st->rec || st->fn || st->stat || st->qd || st->ens)
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "the front probe takes a stepper without attachments "
@@ -1392,10 +1391,16 @@ int dns_imex_front_probe(dns_imex *st, const dns_imex_coeffs *cf,
     DNS_TRY(st->step_refusals(nfc_new));
     st->probed = true;
     DNS_TRY(st->step_preamble(nfc_new, cf, o));
-    // (from here on as step_device: the turn of a device convection, the plan)
+    // (from here on as step_device: the stepper's own row blocks -- a step
+    // that has to cut them first trusts no tail's warm start --, the turn of a
+    // device convection, the plan)
+    const bool cut = h->dist() && !st->part.on;
+    DNS_TRY(st->ensure_partition());
     st->turn_convection();
-    const StepPlan pl = st->plan(cf, &o, cycle_len);
+    StepPlan pl = st->plan(cf, &o, cycle_len);
+    if (cut) pl.can_pre = pl.use_pre = false;
     const bool six = pl.form == StepPlan::Six;
+    const bool dfront = pl.form == StepPlan::DistFront;
     const size_t n = (size_t)h->n, nv = (size_t)h->nv, np = (size_t)h->np;
     const int par = st->work & 1;
     // ---- what the front will read
@@ -1424,6 +1429,7 @@ int dns_imex_front_probe(dns_imex *st, const dns_imex_coeffs *cf,
     if (out->gp_in && np)
         DNS_TRY(dns::download_from(out->gp_in, row_of(st->gp_ref()), np, s));
     if (out->b_prev) DNS_TRY(st->b.download(out->b_prev, n, s));
+    if (out->r_in) DNS_TRY(dns::download_from(out->r_in, h->r.p, n, s));
     if (pl.carry) {
         if (out->kxs_in)
             for (int q = 1; q < 5; ++q)
@@ -1431,24 +1437,28 @@ int dns_imex_front_probe(dns_imex *st, const dns_imex_coeffs *cf,
                                                   s));
         if (out->rcarry_in) DNS_TRY(st->rcarry.download(out->rcarry_in, nv, s));
     }
-    if (six) {
+    if (six || pl.dcarry) {
         if (out->rc6_in) {
             DNS_TRY(st->rc6[par].download(out->rc6_in, nv, s));
             DNS_TRY(st->rc6[1 - par].download(out->rc6_in + nv, nv, s));
         }
+        // (row-partitioned: the solve before has overwritten its warm start in
+        // place; what is left of it is the copy its front made for a lazy
+        // tail with cells, x0c -- stale unless that step's plan had dtail)
         if (out->x0_other)
-            DNS_TRY(st->x0buf[1 - par].download(out->x0_other, n, s));
+            DNS_TRY((six ? st->x0buf[1 - par] : st->x0c)
+                        .download(out->x0_other, n, s));
     }
     DNS_HIP(hipStreamSynchronize(s));
     // ---- the front, by its form (prologue() without launch_front_nodes)
     switch (pl.form) {
         case StepPlan::Six: DNS_TRY(st->front_six(cf, pl)); break;
         case StepPlan::Fused: DNS_TRY(st->front_fused(cf, pl)); break;
-        case StepPlan::StreamRhs: DNS_TRY(st->front_stream(cf, pl)); break;
-        case StepPlan::Plain: DNS_TRY(st->front_rows(cf, pl)); break;
-        default:
-            return dns::fail(DNS_ERR_HOST, "front probe: a partitioned plan on "
-                             "an un-partitioned handle");
+        case StepPlan::DistFront: DNS_TRY(st->front_dist(cf, pl)); break;
+        case StepPlan::StreamRhs:
+        case StepPlan::StreamRows: DNS_TRY(st->front_stream(cf, pl)); break;
+        case StepPlan::Plain:
+        case StepPlan::Rows: DNS_TRY(st->front_rows(cf, pl)); break;
     }
     DNS_HIP(hipStreamSynchronize(s));
     // ---- what it has left
@@ -1460,15 +1470,26 @@ int dns_imex_front_probe(dns_imex *st, const dns_imex_coeffs *cf,
     out->r1_lpr = st->R1.lpr;
     out->r1_pair = st->R1p.ready ? 1 : 0;
     out->pad = 0;
+    const dns::RowMap rm = (h->dist() && h->dist_sliced && h->dd)
+                               ? h->dist_rowmap() : dns::RowMap{0, 0, 0, 0};
+    out->rowmap[0] = rm.row0;
+    out->rowmap[1] = rm.len1;
+    out->rowmap[2] = rm.row2;
+    out->rowmap[3] = rm.len2;
+    out->dcarry = pl.dcarry ? 1 : 0;
+    out->dtail = pl.dtail ? 1 : 0;
+    out->have_cells = pl.have_cells ? 1 : 0;
+    out->nsel = st->part.on ? st->part.nsel : 0;
     const bool fused = pl.form == StepPlan::Fused;
-    out->nparts = fused ? st->front_nparts(pl) : 0;
+    out->nparts = (fused || dfront) ? st->front_nparts(pl) : 0;
     if (out->x0)
         DNS_TRY((six ? st->x0buf[par] : st->xs[st->work]).download(out->x0, n,
                                                                    s));
     if (out->b) DNS_TRY(st->b.download(out->b, n, s));
     if (out->nfc_out) DNS_TRY(st->nfc[st->nc].download(out->nfc_out, nv, s));
     if (six && out->kx) DNS_TRY(st->kx6.download(out->kx, n, s));
-    if (fused) {
+    if (pl.dtail && out->x0copy) DNS_TRY(st->x0c.download(out->x0copy, n, s));
+    if (fused || dfront) {
         if (out->nparts > out->parts_cap && (out->partR || out->partB))
             return dns::fail(DNS_ERR_BAD_ARGUMENT, "%d partials, room for %d",
                              out->nparts, out->parts_cap);

@@ -452,20 +452,25 @@ class ImexStepper(object):
             C.check(status)
         return secs.value, its.value, self.last_stats
 
-    PROBE_FORMS = {0: 'Plain', 1: 'Six', 2: 'Fused', 5: 'StreamRhs'}
+    PROBE_FORMS = {0: 'Plain', 1: 'Six', 2: 'Fused', 3: 'DistFront',
+                   4: 'Rows', 5: 'StreamRhs', 6: 'StreamRows'}
 
     def front_probe(self, cf, opts=None, cycle_len=0, nfc_new=None):
         """TEST ONLY (`dns_imex_front_probe`): the front of one step without
         its solve, as a dict -- what the front reads (`nsol`, `ring` `(5, n)`
-        in ring order, `nfc_in` `(2, NV)`, `g_in`, `gp_in`, `b_prev`,
+        in ring order, `nfc_in` `(2, NV)`, `g_in`, `gp_in`, `b_prev`, `r_in`,
         `tab_row`; for a carry plan `kxs_in` `(4, n)`, `rcarry_in`; for a
-        six-node plan `rc6_in` `(2, NV)`, `x0_other`) and what it has left
-        (`x0`, `b`, `nfc_out`; `kx` six-node; `r`, `partR`, `partB` where the
-        front forms them; `kxs_cur`, `rcarry_out` in mode 2), with the plan
-        (`form` by name, `mode`, `use_pre`, `carry`) and `k_lpr`, `r1_lpr`,
-        `r1_pair` (R1 is held in the pair format).
-        What a plan does not have is None.  The stepper is consumed:
-        `set_state` before it steps again."""
+        six-node plan or a partitioned one with `dcarry` `rc6_in` `(2, NV)`,
+        `x0_other`) and what it has left (`x0`, `b`, `nfc_out`; `kx`
+        six-node; `r`, `partR`, `partB` where the front forms them;
+        `kxs_cur`, `rcarry_out` in mode 2; `x0copy` with `dtail`), with the
+        plan (`form` by name, `mode`, `use_pre`, `carry`, `dcarry`, `dtail`,
+        `have_cells`), `rowmap` (`row0, len1, row2, len2` of this rank's rows,
+        zeros when un-partitioned), `nsel` and `k_lpr`, `r1_lpr`, `r1_pair`
+        (R1 is held in the pair format).
+        What a plan does not have is None.  On a row-partitioned system every
+        rank calls it together.  The stepper is consumed: `set_state` before
+        it steps again."""
         NV, NP = self.sys.NV, self.sys.NP
         n, cap = NV + NP, 4096
         o = solve_opts() if opts is None else opts
@@ -475,7 +480,7 @@ class ImexStepper(object):
                    rcarry_in=nan(NV), rc6_in=nan(2, NV), x0_other=nan(n),
                    x0=nan(n), b=nan(n), nfc_out=nan(NV), kx=nan(n), r=nan(n),
                    partR=nan(cap), partB=nan(cap), kxs_cur=nan(n),
-                   rcarry_out=nan(NV))
+                   rcarry_out=nan(NV), r_in=nan(n), x0copy=nan(n))
         pr = C.dns_imex_probe(parts_cap=cap)
         for k, arr in res.items():
             setattr(pr, k, C.dptr(arr.reshape(-1)))
@@ -483,21 +488,28 @@ class ImexStepper(object):
         C.check(self.lib.dns_imex_front_probe(
             self._h, ct.byref(cf), ct.byref(o), int(cycle_len), C.dptr(nf),
             ct.byref(pr)))
-        for k in ('nsol', 'tab_row', 'mode', 'k_lpr', 'r1_lpr', 'nparts'):
+        for k in ('nsol', 'tab_row', 'mode', 'k_lpr', 'r1_lpr', 'nparts',
+                  'nsel'):
             res[k] = int(getattr(pr, k))
         res['form'] = self.PROBE_FORMS[int(pr.form)]
-        res['use_pre'], res['carry'] = bool(pr.use_pre), bool(pr.carry)
-        res['r1_pair'] = bool(pr.r1_pair)
+        for k in ('use_pre', 'carry', 'r1_pair', 'dcarry', 'dtail',
+                  'have_cells'):
+            res[k] = bool(getattr(pr, k))
+        res['rowmap'] = tuple(int(v) for v in pr.rowmap)
         res['partR'] = res['partR'][:pr.nparts]
         res['partB'] = res['partB'][:pr.nparts]
         if not pr.has_carry:
             res['kxs_in'] = res['rcarry_in'] = None
         if not pr.has_six:
-            res['rc6_in'] = res['x0_other'] = res['kx'] = None
+            res['kx'] = None
+        if not (pr.has_six or pr.dcarry):
+            res['rc6_in'] = res['x0_other'] = None
         if pr.nparts == 0:
             res['r'] = res['partR'] = res['partB'] = None
         if pr.mode != 2:
             res['kxs_cur'] = res['rcarry_out'] = None
+        if not pr.dtail:
+            res['x0copy'] = None
         return res
 
     def step_counters(self):

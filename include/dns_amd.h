@@ -425,17 +425,22 @@ int dns_imex_run_cycles(dns_imex *st, int64_t *out2);
 /* v (NV) and p = pscale*p~ (NP) of the current state */
 int dns_imex_get_state(dns_imex *st, double *v, double *p);
 
-/* TEST ONLY.  The front of ONE step on one GPU: what `dns_imex_step` does
- * before its solve (the upload of `nfc_new` with its swap, the K x products of
- * a carry step), then the plan for `cycle_len` (0: a synchronous solve; > 0:
- * the cycle length of a pipelined batch) and the launches that plan puts in
- * front of the first Krylov cycle -- by the member functions the step itself
- * calls, without the nodes of the attachments and without a solve -- then a
- * synchronise.  `out` receives what the front READS, copied before it runs,
- * and what it has LEFT.  Every pointer of `out` may be NULL (n = NV + NP).
- * DNS_ERR_BAD_ARGUMENT on a row-partitioned handle or with an attachment
- * (feedback, recorder, functionals, statistics, quadratics, ensemble);
- * DNS_ERR_NOT_READY with a pipelined batch pending; nothing is touched then.
+/* TEST ONLY.  The front of ONE step: what `dns_imex_step` does before its
+ * solve (the upload of `nfc_new` with its swap, the K x products of a carry
+ * step; on a row-partitioned handle the stepper's own row blocks and halo
+ * plan), then the plan for `cycle_len` (0: a synchronous solve; > 0: the cycle
+ * length of a pipelined batch) and the launches that plan puts in front of the
+ * first Krylov cycle -- by the member functions the step itself calls, without
+ * the nodes of the attachments and without a solve -- then a synchronise.
+ * `out` receives what the front READS, copied before it runs, and what it has
+ * LEFT.  Every pointer of `out` may be NULL (n = NV + NP).  On a
+ * row-partitioned handle the call is COLLECTIVE: every rank calls it, in the
+ * same order with the same arguments (the current solution may be
+ * all-gathered before the row blocks are cut); every vector is copied out in
+ * full, valid on the rank's own rows and their halo.
+ * DNS_ERR_BAD_ARGUMENT with an attachment (feedback, recorder, functionals,
+ * statistics, quadratics, ensemble); DNS_ERR_NOT_READY with a pipelined batch
+ * pending; nothing is touched then.
  * The stepper is CONSUMED: the convection slot, the carry buffers and the
  * work vector are those of a step that never finished.  dns_imex_step,
  * dns_imex_run and a second probe answer DNS_ERR_NOT_READY until
@@ -448,8 +453,10 @@ typedef struct dns_imex_probe {
     double *b_prev;        /* n: the right-hand side of the step before        */
     double *kxs_in;        /* 4 n: K x of prev .. p4      (has_carry)          */
     double *rcarry_in;     /* NV: the carried residual    (has_carry)          */
-    double *rc6_in;        /* 2 NV: current, previous     (has_six)            */
-    double *x0_other;      /* n: the warm start before    (has_six)            */
+    double *rc6_in;        /* 2 NV: current, previous     (has_six or dcarry)  */
+    double *x0_other;      /* n: the warm start before    (has_six; dcarry:
+                            * the copy the front before made, stale unless
+                            * that step's plan had dtail)                      */
     /* --- left by the front */
     double *x0, *b;        /* n each                                           */
     double *nfc_out;       /* NV: nfc_c (written with a device convection)     */
@@ -460,11 +467,23 @@ typedef struct dns_imex_probe {
     double *rcarry_out;    /* NV: b_prev - K x_c          (mode 2)             */
     int32_t parts_cap;     /* in                                               */
     int32_t nsol, tab_row, has_carry, has_six;
-    /* the plan: StepPlan::Form (0 Plain, 1 Six, 2 Fused, 5 StreamRhs), the
-     * MODE of k_step_front, "the tail before left the warm start", "residual
-     * carried"; the lanes-per-row instantiations of K and R1; the partials;
-     * "R1 is held in the pair format" (the streamed product then takes it) */
+    /* the plan: StepPlan::Form (0 Plain, 1 Six, 2 Fused, 3 DistFront, 4 Rows,
+     * 5 StreamRhs, 6 StreamRows), the MODE of k_step_front, "the tail before
+     * left the warm start", "residual carried"; the lanes-per-row
+     * instantiations of K and R1; the partials; "R1 is held in the pair
+     * format" (the streamed product then takes it) */
     int32_t form, mode, use_pre, carry, k_lpr, r1_lpr, nparts, r1_pair, pad;
+    /* --- appended for the row-partitioned forms */
+    double *r_in;          /* n: the solver's residual vector as the front
+                            * finds it (read by no front: what it must leave
+                            * untouched outside the own rows)                  */
+    double *x0copy;        /* n: the copy of x0 left by the front (dtail)      */
+    /* row0, len1, row2, len2 of this rank's rows of K (all zero when the
+     * handle is not partitioned); the plan's "residuals of the one-step
+     * solves carried", "lazy tail with the convection cells", "the tail
+     * before left the cells"; the number of cells this rank evaluates */
+    int32_t rowmap[4];
+    int32_t dcarry, dtail, have_cells, nsel;
 } dns_imex_probe;
 int dns_imex_front_probe(dns_imex *st, const dns_imex_coeffs *cf,
                          const dns_solve_opts *opts, int32_t cycle_len,

@@ -55,6 +55,19 @@ largest |mutant - model| / tolerance (all >= 100):
     carry dropped 4.8e4 (a previous solve converged to 1e-10)
     x0 of the step before 1.7e15
 
+By rows (`footprint`, `front_model_rows`: the row-partitioned forms DistFront,
+Rows, StreamRows; tests/test_gpu_zz_dist_front.py): the same formulas on a
+rank's own rows of the row-sliced K / R1, from the ring as that rank holds it,
+every entry outside the rank's footprint (own rows, columns of its rows of K
+and R1, dofs of the convection cells that touch an own row) set to NaN first.
+On the CPU, 2 and 3 ranks, CNAB and SBDF2, in the order of `k_dist_front`
+(32 lanes, fused): x0 0.154  b 0.073  kx 0.164  r 0.127, with the carried
+residuals b 0.145  r 0.163 (all <= 0.25).  Mutations, smallest miss /
+tolerance: row2 off by one 5.8e15, len1 one short 8.5e12, one halo entry of
+the previous ring slot x0 4.1e14 (r 1.3e11 where K's own rows hold a non-zero
+there), rcc <-> rcp 1.3e5, carry dropped 9.3e4, a_p at nsol = 1 9.1e12, a cell
+never evaluated nfc_c 1.9e12 (b 9.2e9).
+
 Measured on an MI355X (tests/test_gpu_imex_front.py prints them with
 `pytest -s`), largest error / tolerance over all of its cases:
     x0 0.136  b 0.252  kx (Six) 0.032  r0 0.139  sum partR 0.016
@@ -200,6 +213,131 @@ def front_model(K, R1, ring, e, a_c, a_p, cn_c, cn_o, nfc, g, gp, carry=None):
     b, ba = np.concatenate([bv, gp]), np.concatenate([bva, np.abs(gp)])
     out.update(x0=(x0, x0a), b=(b, ba), kx=(kx, kxa), r=(b - kx, ba + kxa))
     return out
+
+
+# ---- the front by rows (row-partitioned forms) -------------------------------
+
+def own_rows(st_v, st_p, rank, nv):
+    """this rank's global rows of K: its velocity rows, then its pressure
+    rows (`RowMap {st_v[r], len1, nv + st_p[r], len2}`)"""
+    return np.r_[np.arange(st_v[rank], st_v[rank + 1]),
+                 nv + np.arange(st_p[rank], st_p[rank + 1])]
+
+
+def selected_cells(conv_space, st_v, rank):
+    """the cells with a test function on one of the rank's velocity rows
+    (`conv_space.code (nc, 12)`: inner row of the slot, negative: Dirichlet)"""
+    code = conv_space.code
+    return np.flatnonzero(((code >= st_v[rank])
+                           & (code < st_v[rank + 1])).any(axis=1))
+
+
+def footprint(K, R1, st_v, st_p, rank, conv_space=None):
+    """the sorted global entries of a solution vector rank `rank` may read:
+    its own velocity and pressure rows, the columns of those rows of K, the
+    columns of its own rows of R1 and, with a convection, every dof of every
+    cell that has a test function on an own row"""
+    K, R1 = sps.csr_matrix(K), sps.csr_matrix(R1)
+    nv = R1.shape[0]
+    own = own_rows(st_v, st_p, rank, nv)
+    mark = np.zeros(K.shape[0], dtype=bool)
+    mark[own] = True
+    mark[K[own].indices] = True
+    mark[R1[st_v[rank]:st_v[rank + 1]].indices] = True
+    if conv_space is not None:
+        d = conv_space.code[selected_cells(conv_space, st_v, rank)]
+        mark[d[d >= 0]] = True
+    return np.flatnonzero(mark)
+
+
+def _only(x, keep):
+    """`x` in long double, NaN wherever the last index is not in `keep`"""
+    x = _ld(x)
+    y = np.full(x.shape, np.nan, dtype=LD)
+    y[..., keep] = x[..., keep]
+    return y
+
+
+def front_model_rows(K, R1, st_v, st_p, rank, ring, e, a_c, a_p, cn_c, cn_o,
+                     nfc, g, gp, carry=None, conv_space=None):
+    """`front_model` on the own rows of the row-sliced K / R1, from the ring
+    AS THAT RANK DOWNLOADED IT: every entry outside the footprint (and of
+    `nfc`, `g`, `gp`, `carry['rc']` outside the own rows) is overwritten with
+    NaN before use, so nothing else is read.  Returns `(value, moduli)` for
+    `x0` on the footprint, `b`, `kx`, `r` on the own rows (velocity rows, then
+    pressure rows) and, with `carry = dict(rc=(2, nv))` (the carried residuals
+    of the current and the previous solve), the term `a_c rcc + a_p rcp` on the
+    own velocity rows as `carry`; `own`, `fp`: the index sets"""
+    K, R1 = sps.csr_matrix(K), sps.csr_matrix(R1)
+    n, nv = K.shape[0], R1.shape[0]
+    ov = np.arange(st_v[rank], st_v[rank + 1])
+    op = np.arange(st_p[rank], st_p[rank + 1])
+    own = own_rows(st_v, st_p, rank, nv)
+    fp = footprint(K, R1, st_v, st_p, rank, conv_space)
+    ring = _only(ring, fp)
+    nfc, g, gp = _only(nfc, ov), _only(g, ov), _only(gp, op)
+    Kr, Rr = K[own], R1[ov]
+    e = [LD(float(x)) for x in e]
+    a_c, a_p, cn_c, cn_o = (LD(float(x)) for x in (a_c, a_p, cn_c, cn_o))
+    x0 = np.zeros(n, dtype=LD)
+    x0a = np.zeros(n, dtype=LD)
+    for i in range(5):
+        if e[i] != 0:
+            x0 = x0 + e[i]*ring[i]
+            x0a = x0a + abs(e[i])*np.abs(ring[i])
+    w = a_c*ring[0, :nv]
+    wa = abs(a_c)*np.abs(ring[0, :nv])
+    if a_p != 0:
+        w = w + a_p*ring[1, :nv]
+        wa = wa + abs(a_p)*np.abs(ring[1, :nv])
+    bv = spmv(Rr, w) + cn_c*nfc[0, ov] + cn_o*nfc[1, ov] + g[ov]
+    bva = (spmv(np.abs(Rr), wa) + abs(cn_c)*np.abs(nfc[0, ov])
+           + abs(cn_o)*np.abs(nfc[1, ov]) + np.abs(g[ov]))
+    out = dict(own=own, fp=fp)
+    if carry is not None:
+        rc = _only(carry['rc'], ov)
+        t, ta = a_c*rc[0, ov], abs(a_c)*np.abs(rc[0, ov])
+        if a_p != 0:
+            t, ta = t + a_p*rc[1, ov], ta + abs(a_p)*np.abs(rc[1, ov])
+        out['carry'] = (t, ta)
+        bv, bva = bv + t, bva + ta
+    b, ba = np.concatenate([bv, gp[op]]), np.concatenate([bva, np.abs(gp[op])])
+    kx, kxa = spmv(Kr, x0), spmv(np.abs(Kr), x0a)
+    out.update(x0=(x0[fp], x0a[fp]), b=(b, ba), kx=(kx, kxa),
+               r=(b - kx, ba + kxa))
+    return out
+
+
+def dist_front_eval64(K, R1, st_v, st_p, rank, ring, e, a_c, a_p, cn_c, cn_o,
+                      nfc, g, gp, carry=None, lanes=32, fused=True):
+    """`x0` (all entries), `b`, `kx`, `r` (own rows) in fp64 in the order of
+    `k_dist_front`: the row sums over sub-waves of `lanes`, `s + cn_c nc +
+    cn_o nfc_o + g`, the two `fma` of the carry, `bv - sk`"""
+    f8 = lambda x: np.asarray(x, dtype=np.float64)
+    K, R1 = sps.csr_matrix(K), sps.csr_matrix(R1)
+    n, nv = K.shape[0], R1.shape[0]
+    ov = np.arange(st_v[rank], st_v[rank + 1])
+    op = np.arange(st_p[rank], st_p[rank + 1])
+    own = own_rows(st_v, st_p, rank, nv)
+    ring, nfc, g, gp = f8(ring), f8(nfc), f8(g), f8(gp)
+    x0 = e[0]*ring[0]
+    for i in range(1, 5):
+        if e[i] != 0:
+            x0 = _fma(np.full(n, float(e[i])), ring[i], x0, fused)
+    if a_p != 0:
+        w = _fma(np.full(nv, float(a_c)), ring[0, :nv], a_p*ring[1, :nv], fused)
+    else:
+        w = a_c*ring[0, :nv]
+    sk = spmv64(K[own], x0, lanes, fused)
+    bv = spmv64(R1[ov], w, lanes, fused) + cn_c*nfc[0, ov] + cn_o*nfc[1, ov] \
+        + g[ov]
+    if carry is not None:
+        rc = f8(carry['rc'])
+        bv = _fma(np.full(ov.size, float(a_c)), rc[0, ov], bv, fused)
+        if a_p != 0:
+            bv = _fma(np.full(ov.size, float(a_p)), rc[1, ov], bv, fused)
+    b = np.concatenate([bv, gp[op]])
+    return dict(x0=x0, b=b, kx=sk, r=b - sk)
 
 
 def sumsq(v):

@@ -116,7 +116,13 @@ def test_front_probe_checks_its_arguments_on_the_host(capi):
     import ctypes as ct
     lib = capi.load_library()
     pr = capi.dns_imex_probe()
-    assert ct.sizeof(pr) == 200
+    # (18 pointers, 14 words; appended: 2 pointers, rowmap[4], 4 words -- the
+    # offsets from before keep their place)
+    assert ct.sizeof(pr) == 248
+    assert type(pr).parts_cap.offset == 144 and type(pr).pad.offset == 196
+    assert type(pr).r_in.offset == 200 and type(pr).x0copy.offset == 208
+    assert type(pr).rowmap.offset == 216 and type(pr).dcarry.offset == 232
+    assert type(pr).nsel.offset == 244
     cf = capi.dns_imex_coeffs(a_c=1.)
     assert lib.dns_imex_front_probe(None, ct.byref(cf), None, 0, None,
                                     ct.byref(pr)) == capi.DNS_ERR_BAD_ARGUMENT

@@ -38,9 +38,10 @@ everywhere, R1.lpr = 32 for CNAB and 16 for SBDF2, on the toy and on the wake):
 The wake runs the same lanes-per-row instantiations as the toy (32 / 32).
 
 Not reachable from one process and therefore not exercised: the refusal of a
-pending pipelined batch (`dns_imex_run` leaves none behind).  The refusal of a
-row-partitioned handle is exercised through a communicator attached to the
-system.  Of the six attachments the force functionals are not attached here
+pending pipelined batch (`dns_imex_run` leaves none behind).  A row-partitioned
+handle is probed too (a communicator attached to the system: form DistFront);
+its forms are held entry by entry in `test_gpu_zz_dist_front.py`.  Of the six
+attachments the force functionals are not attached here
 (they need a problem's test vectors); the other five are, one by one.
 """
 import contextlib
@@ -486,9 +487,14 @@ def test_probe_refusals_and_consumed_stepper(toy):
         _capi.check(stp.lib.dns_comm_create_callbacks(0, 1, 0, ar, ag, None,
                                                       ct.byref(h)))
         stp.sys.set_comm(Comm(h, 0, 1, keep=(ar, ag)))
-        with pytest.raises(_capi.DnsError, match='un-partitioned') as ei:
-            stp.front_probe(cf, _opts())
-        assert ei.value.status == _capi.DNS_ERR_BAD_ARGUMENT
+        # (attaching has dropped the preconditioner: set up by rows, the probe
+        # then runs the partitioned front; tests/test_gpu_zz_dist_front.py)
+        stp.sys.setup_precond(cheb_degree=4, schur='dense', fhat='explicit',
+                              factorization='full')
+        out = stp.front_probe(cf, _opts(), nfc_new=inp['nfc_new'][0])
+        assert out['form'] == 'DistFront'
+        assert out['rowmap'] == (0, nv, nv, toy['np'])
+        _start(stp, inp, 1)
         stp.sys.set_comm(None)
         stp.lib.dns_comm_destroy(h)
         # (detaching has dropped the preconditioner)
