@@ -36,6 +36,11 @@ class NotConverged(DnsError):
     pass
 
 
+class LinearisedRefusal(DnsError, ValueError):
+    """what a linearised convection operator (`ConvectionP2.set_base_flow`)
+    is refused for, with the library's message"""
+
+
 class Breakdown(DnsError):
     pass
 
@@ -352,6 +357,12 @@ SIGNATURES = {
     'dns_conv_destroy': (None, [_VP]),
     'dns_conv_set_dbcvals': (ct.c_int, [_VP, c_double_p]),
     'dns_conv_apply': (ct.c_int, [_VP, c_double_p, ct.c_double, c_double_p]),
+    'dns_conv_set_base_flow': (ct.c_int, [_VP, c_double_p, c_double_p,
+                                          ct.c_int32]),
+    'dns_conv_clear_base_flow': (ct.c_int, [_VP]),
+    'dns_conv_get_mode': (ct.c_int, [_VP, c_int32_p]),
+    'dns_conv_cells_probe': (ct.c_int, [_VP, c_double_p, c_int32_p, ct.c_int32,
+                                        ct.c_double, c_double_p, c_int32_p]),
     'dns_imex_set_convection': (ct.c_int, [_VP, _VP, ct.c_double]),
     'dns_spmv': (ct.c_int, [ct.c_int, ct.POINTER(dns_csr), c_double_p,
                             c_double_p, ct.c_double, ct.c_double, ct.c_int32]),
@@ -494,6 +505,9 @@ def check(status):
         raise NotConverged(status, msg)
     if status == DNS_BREAKDOWN:
         raise Breakdown(status, msg)
+    if status == DNS_ERR_BAD_ARGUMENT and msg.startswith('linearised '
+                                                         'convection'):
+        raise LinearisedRefusal(status, msg)
     raise DnsError(status, msg)
 
 

@@ -110,7 +110,58 @@ class ConvectionP2(object):
     def set_dbc_row(self, row):
         C.check(self.lib.dns_conv_set_dbc_row(self._h, int(row)))
 
+    # -- linearised / adjoint convection about a base flow --------------------
+    def set_base_flow(self, base, adjoint=False):
+        """From here on the operator evaluates, for the perturbation `w` it
+        is handed (`apply`, an attached `cnab` / `sbdftwo` loop),
+        `L(V)w = N(V)w + N(w)V` -- or with `adjoint` the transpose
+        `(N1(V) + N2(V))_II^T w` -- instead of `N(w)w`.  `base`: the full
+        velocity vector `V` (`vdim` entries) or the pair `(v_inner, dbcvals)`.
+        The perturbation's own Dirichlet values stay the operator's; the
+        adjoint takes zero values and no table (`ValueError` otherwise)"""
+        if isinstance(base, (tuple, list)) and len(base) == 2:
+            vin = C.as_f64(base[0], size=self.nv)
+            dbv = C.as_f64(base[1], size=self.ndbc)
+        else:
+            full = C.as_f64(base, size=self._vdim)
+            vin = np.ascontiguousarray(full[self._invinds])
+            dbv = np.ascontiguousarray(full[self._dbcinds])
+        if dbv.size == 0:
+            dbv = np.zeros(1)
+        C.check(self.lib.dns_conv_set_base_flow(
+            self._h, C.dptr(vin), C.dptr(dbv), int(bool(adjoint))))
+
+    def clear_base_flow(self):
+        """back to `N(v)v`"""
+        C.check(self.lib.dns_conv_clear_base_flow(self._h))
+
+    @property
+    def linearised(self):
+        """False, 'forward' or 'adjoint'"""
+        mode = ct.c_int32(0)
+        C.check(self.lib.dns_conv_get_mode(self._h, ct.byref(mode)))
+        return {0: False, 1: 'forward', 2: 'adjoint'}[mode.value]
+
+    def cell_values(self, v_inner, sel=None, fill=0.0):
+        """TEST ONLY: `(cells (12, ncells), pos)` -- what the element launch
+        leaves for `v_inner` in the current mode, in the operator's internal
+        cell order, and the caller's cell -> internal cell.  `sel`: internal
+        cells to evaluate, every other entry is `fill`"""
+        v = C.as_f64(v_inner, size=self.nv)
+        out = np.empty((12, self.ncells))
+        pos = np.empty(self.ncells, dtype=np.int32)
+        s = None if sel is None else _i32(sel)
+        C.check(self.lib.dns_conv_cells_probe(
+            self._h, C.dptr(v),
+            None if s is None or s.size == 0
+            else s.ctypes.data_as(C.c_int32_p),
+            -1 if s is None else int(s.size), float(fill),
+            C.dptr(out.reshape(-1)), pos.ctypes.data_as(C.c_int32_p)))
+        return out, pos
+
     def apply(self, v_inner, scale=1.0):
+        """`scale*N(v)v` on the inner dofs -- with a base flow set,
+        `scale*L(V)v` or its transpose"""
         v = C.as_f64(v_inner, size=self.nv)
         out = np.empty(self.nv)
         C.check(self.lib.dns_conv_apply(self._h, C.dptr(v), float(scale),
@@ -193,7 +244,8 @@ class ConvectionP2(object):
 
     def host_callback(self, invinds, scale=-1.0):
         """an `f_vdp(vfull)` callable (reference tiu:113) backed by this
-        operator: the inner part of `vfull` in, `scale*N(v)v` out"""
+        operator: the inner part of `vfull` in, `scale*N(v)v` out (with a
+        base flow set: what `apply` gives then)"""
         inv = np.asarray(invinds)
 
         def f_vdp(vfull):

@@ -115,6 +115,7 @@ int dns_conv_create_p2(int device, int32_t ncells, const int32_t *cell_vdofs,
     cv->ncells = ncells;
     cv->nv_inner = nv_inner;
     cv->ndbc = ndbc;
+    cv->dbc_host.assign(dbcvals, dbcvals + ndbc);
     DNS_TRY(cv->cellmap.alloc(cmap.size()));
     DNS_TRY(cv->gptr.alloc(cnt.size()));
     DNS_TRY(cv->gidx.alloc(gidx.size()));
@@ -144,10 +145,13 @@ void dns_conv_destroy(dns_conv *cv) {
 
 int dns_conv_set_dbcvals(dns_conv *cv, const double *dbcvals) try {
     if (!cv || !dbcvals) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (cv->lin_mode == dns::kConvAdjoint)
+        DNS_TRY(dns::check_adjoint_dbc(dbcvals, cv->ndbc, 0));
     DNS_HIP(hipSetDevice(cv->device));
     if (cv->ndbc > 0)
         DNS_TRY(dns::upload_to(cv->dbcvals.p, dbcvals, (size_t)cv->ndbc,
                                nullptr));
+    cv->dbc_host.assign(dbcvals, dbcvals + cv->ndbc);
     cv->dbc_rows = 0;                  // one constant value set from here on
     cv->dbc_gen++;
     cv->dbc_ctr = nullptr;
@@ -158,6 +162,8 @@ int dns_conv_set_dbc_table(dns_conv *cv, int32_t nrows,
                            const double *vals) try {
     if (!cv || nrows < 1 || !vals)
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
+    if (cv->lin_mode == dns::kConvAdjoint)
+        DNS_TRY(dns::check_adjoint_dbc(nullptr, 0, nrows));
     DNS_HIP(hipSetDevice(cv->device));
     DNS_HIP(hipDeviceSynchronize());           // replays may still read it
     const size_t nd = (size_t)std::max(1, cv->ndbc);
@@ -176,6 +182,76 @@ int dns_conv_set_dbc_row(dns_conv *cv, int32_t row) try {
         return fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     cv->dbc_row = row;
     cv->dbc_gen++;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_conv_set_base_flow(dns_conv *cv, const double *v_inner,
+                           const double *dbcvals, int32_t adjoint) try {
+    if (!cv) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (adjoint)
+        DNS_TRY(dns::check_adjoint_dbc(cv->dbc_host.data(), cv->ndbc,
+                                       cv->dbc_rows));
+    std::vector<double> vb;
+    DNS_TRY(dns::expand_base_flow(cv->cmap_host.data(), cv->ncells,
+                                  cv->nv_inner, cv->ndbc, v_inner, dbcvals,
+                                  vb));
+    DNS_HIP(hipSetDevice(cv->device));
+    DNS_HIP(hipDeviceSynchronize());           // replays may still read it
+    if (cv->vbase.n < vb.size()) DNS_TRY(cv->vbase.alloc(vb.size()));
+    DNS_TRY(cv->vbase.upload(vb.data(), vb.size(), nullptr));
+    DNS_HIP(hipDeviceSynchronize());
+    cv->lin_mode = adjoint ? dns::kConvAdjoint : dns::kConvForward;
+    cv->dbc_gen++;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_conv_clear_base_flow(dns_conv *cv) try {
+    if (!cv) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_HIP(hipSetDevice(cv->device));
+    DNS_HIP(hipDeviceSynchronize());           // replays may still read it
+    cv->vbase.release();
+    cv->lin_mode = dns::kConvNonlinear;
+    cv->dbc_gen++;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_conv_get_mode(const dns_conv *cv, int32_t *mode) try {
+    if (!cv || !mode) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    *mode = cv->lin_mode;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// TEST ONLY: the cell values [12][ncells] (internal cell order) the element
+// launch leaves for `v_inner`, all cells or -- nsel >= 0 -- the cells sel[0 ..
+// nsel) of the internal order over a background of `fill`; with `cell_pos` the
+// caller's cell -> internal cell
+int dns_conv_cells_probe(dns_conv *cv, const double *v_inner,
+                         const int32_t *sel, int32_t nsel, double fill,
+                         double *cells_out, int32_t *cell_pos) try {
+    if (!cv || !v_inner || !cells_out || (nsel > 0 && !sel))
+        return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    for (int k = 0; k < nsel; ++k)
+        if (sel[k] < 0 || sel[k] >= cv->ncells)
+            return fail(DNS_ERR_BAD_ARGUMENT, "cell %d outside 0..%d", sel[k],
+                        cv->ncells - 1);
+    DNS_HIP(hipSetDevice(cv->device));
+    const size_t nc12 = (size_t)12 * cv->ncells;
+    DevBuf<double> dv;
+    DevBuf<int> dsel;
+    DNS_TRY(dv.alloc((size_t)std::max(1, cv->nv_inner)));
+    DNS_TRY(dv.upload(v_inner, (size_t)cv->nv_inner, nullptr));
+    std::vector<double> bg(nc12, fill);
+    DNS_TRY(cv->cellvals.upload(bg.data(), nc12, nullptr));
+    if (nsel >= 0) {
+        DNS_TRY(dsel.alloc((size_t)std::max(1, nsel)));
+        if (nsel > 0) DNS_TRY(dsel.upload(sel, (size_t)nsel, nullptr));
+    }
+    DNS_TRY(cv->enqueue_cells(dv.p, nullptr, nsel >= 0 ? dsel.p : nullptr,
+                              std::max(0, nsel)));
+    DNS_TRY(cv->cellvals.download(cells_out, nc12, nullptr));
+    DNS_HIP(hipDeviceSynchronize());
+    if (cell_pos)
+        for (int c = 0; c < cv->ncells; ++c) cell_pos[c] = cv->cpos_host[c];
     return DNS_OK;
 } DNS_CAPI_CATCH
 
@@ -199,6 +275,7 @@ int dns_conv_project_tensor(dns_conv *cv, int32_t nb, int32_t nt, int32_t ld,
                             double *out) try {
     if (!cv || !basis || !out)
         return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(cv->refuse_linearised("dns_conv_project_tensor"));
     const int nlive = dns::rom_live_cells(cv->cmap_host.data(), cv->ncells);
     DNS_TRY(dns::check_rom_shape(nb, nt, cv->nv_inner, ld, nlive));
     DNS_HIP(hipSetDevice(cv->device));
@@ -304,6 +381,7 @@ int dns_conv_assemble(dns_conv *cv, const double *u_inner, int32_t newton,
                       double *nvals, double *rhsbc, double *rhscon) try {
     if (!cv || !u_inner || !nvals)
         return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(cv->refuse_linearised("dns_conv_assemble"));
     if (!cv->mat) return fail(DNS_ERR_NOT_READY, "no pattern bound");
     DNS_HIP(hipSetDevice(cv->device));
     const size_t nv = (size_t)cv->nv_inner;
@@ -335,6 +413,7 @@ int dns_conv_assemble2(dns_conv *cv, const double *u_inner,
                        double *rhscon) try {
     if (!cv || !u_inner || !nvals || !dbcvals_lin)
         return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(cv->refuse_linearised("dns_conv_assemble2"));
     if (!cv->mat) return fail(DNS_ERR_NOT_READY, "no pattern bound");
     DNS_HIP(hipSetDevice(cv->device));
     const size_t nv = (size_t)cv->nv_inner;
@@ -393,6 +472,9 @@ int dns_imex_set_convection(dns_imex *st, dns_conv *cv, double scale) try {
         return fail(DNS_ERR_BAD_ARGUMENT,
                     "convection operator has %d inner dofs, system has %d",
                     cv->nv_inner, st->sys->nv);
+    if (cv && cv->linearised())
+        DNS_TRY(st->refuse_partitioned(
+            "linearised convection operator", kLinPartitioned));
     st->sys->drop_graphs();
     st->conv = cv;
     st->conv_scale = scale;

@@ -14,6 +14,7 @@
 //                  inverted index (dof -> list of (local slot, cell)) and
 //                  applies the sign/scale of the caller (`-1`: goes to the rhs)
 #pragma once
+#include "conv_host.hpp"
 #include "kernels.hpp"
 
 namespace dns {
@@ -280,6 +281,252 @@ k_conv_cells_lane(int ncells, const int *__restrict__ cellmap,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Linearised convection about a resident base flow V (dns_conv_set_base_flow):
+//   forward  L(V) w      [(a,i)] = int phi_a ((w . grad) V_i + (V . grad) w_i)
+//   adjoint  L(V)^T_cell w [(a,i)] = int (phi_a sum_k w_k d_i V_k
+//                                          + w_i (V . grad phi_a))
+// in the cell-value layout of N(u)u: k_conv_gather, k_step_back, k_imex_bvec
+// take them as they take those.  w comes from the state vector / the Dirichlet
+// values like u above, V from `vbase [12][ncells]` (internal cell order, the
+// Dirichlet values of V expanded on the host: no map in the way).
+//
+// One quadrature point, forward: cv_i = w_q |T| (grad V_i . w + grad w_i . V)
+// -- a chain of four (one product, three fma) where conv_point has two.
+__device__ __forceinline__ void
+conv_lin_point(int q, const double (&gl)[3][2], const double (&wl)[6][2],
+               const double (&Vl)[6][2], double wq, double (&ph)[6],
+               double &cv0, double &cv1) {
+#pragma clang fp contract(off)
+    double wx[2] = {0.0, 0.0}, Vx[2] = {0.0, 0.0};
+    double gw[2][2] = {{0.0, 0.0}, {0.0, 0.0}};   // gw[i][d] = d_d w_i
+    double gV[2][2] = {{0.0, 0.0}, {0.0, 0.0}};   // gV[i][d] = d_d V_i
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        ph[a] = c_conv.phi[q][a];
+        const double d0 = c_conv.dphi[q][a][0], d1 = c_conv.dphi[q][a][1],
+                     d2 = c_conv.dphi[q][a][2];
+        const double gx =
+            fma(d2, gl[2][0], fma(d1, gl[1][0], __dmul_rn(d0, gl[0][0])));
+        const double gy =
+            fma(d2, gl[2][1], fma(d1, gl[1][1], __dmul_rn(d0, gl[0][1])));
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            wx[i] = fma(ph[a], wl[a][i], wx[i]);
+            Vx[i] = fma(ph[a], Vl[a][i], Vx[i]);
+            gw[i][0] = fma(gx, wl[a][i], gw[i][0]);
+            gw[i][1] = fma(gy, wl[a][i], gw[i][1]);
+            gV[i][0] = fma(gx, Vl[a][i], gV[i][0]);
+            gV[i][1] = fma(gy, Vl[a][i], gV[i][1]);
+        }
+    }
+    cv0 = __dmul_rn(wq, fma(gw[0][1], Vx[1],
+                            fma(gw[0][0], Vx[0],
+                                fma(gV[0][1], wx[1],
+                                    __dmul_rn(gV[0][0], wx[0])))));
+    cv1 = __dmul_rn(wq, fma(gw[1][1], Vx[1],
+                            fma(gw[1][0], Vx[0],
+                                fma(gV[1][1], wx[1],
+                                    __dmul_rn(gV[1][0], wx[0])))));
+}
+
+// One quadrature point, adjoint: the value of slot (a, i) at the point is
+//   phi_a cs_i + da_a cw_i,   cs_i = w_q |T| sum_k w_k d_i V_k,
+//   cw_i = w_q |T| w_i,       da_a = V . grad phi_a
+// -- the second weighting is grad phi_a, not phi_a: conv_adj_value below is
+// the reduction step's own product.
+__device__ __forceinline__ void
+conv_adj_point(int q, const double (&gl)[3][2], const double (&wl)[6][2],
+               const double (&Vl)[6][2], double wq, double (&ph)[6],
+               double (&da)[6], double &cs0, double &cs1, double &cw0,
+               double &cw1) {
+#pragma clang fp contract(off)
+    double wx[2] = {0.0, 0.0}, Vx[2] = {0.0, 0.0};
+    double gV[2][2] = {{0.0, 0.0}, {0.0, 0.0}};   // gV[k][d] = d_d V_k
+    double gp[6][2];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        ph[a] = c_conv.phi[q][a];
+        const double d0 = c_conv.dphi[q][a][0], d1 = c_conv.dphi[q][a][1],
+                     d2 = c_conv.dphi[q][a][2];
+        gp[a][0] =
+            fma(d2, gl[2][0], fma(d1, gl[1][0], __dmul_rn(d0, gl[0][0])));
+        gp[a][1] =
+            fma(d2, gl[2][1], fma(d1, gl[1][1], __dmul_rn(d0, gl[0][1])));
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            wx[i] = fma(ph[a], wl[a][i], wx[i]);
+            Vx[i] = fma(ph[a], Vl[a][i], Vx[i]);
+            gV[i][0] = fma(gp[a][0], Vl[a][i], gV[i][0]);
+            gV[i][1] = fma(gp[a][1], Vl[a][i], gV[i][1]);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+        da[a] = fma(Vx[1], gp[a][1], __dmul_rn(Vx[0], gp[a][0]));
+    cs0 = __dmul_rn(wq, fma(wx[1], gV[1][0], __dmul_rn(wx[0], gV[0][0])));
+    cs1 = __dmul_rn(wq, fma(wx[1], gV[1][1], __dmul_rn(wx[0], gV[0][1])));
+    cw0 = __dmul_rn(wq, wx[0]);
+    cw1 = __dmul_rn(wq, wx[1]);
+}
+
+// the twelve slot values of one quadrature point, either mode: what the sums
+// over the points (shuffle tree / register tree) add up
+template <bool ADJ>
+__device__ __forceinline__ void
+conv_lin_values(int q, const double (&gl)[3][2], const double (&wl)[6][2],
+                const double (&Vl)[6][2], double wq, double (&pv)[12]) {
+#pragma clang fp contract(off)
+    double ph[6];
+    if constexpr (ADJ) {
+        double da[6], cs0, cs1, cw0, cw1;
+        conv_adj_point(q, gl, wl, Vl, wq, ph, da, cs0, cs1, cw0, cw1);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+            pv[2 * a] = fma(da[a], cw0, __dmul_rn(ph[a], cs0));
+            pv[2 * a + 1] = fma(da[a], cw1, __dmul_rn(ph[a], cs1));
+        }
+    } else {
+        double cv0, cv1;
+        conv_lin_point(q, gl, wl, Vl, wq, ph, cv0, cv1);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+            pv[2 * a] = __dmul_rn(ph[a], cv0);
+            pv[2 * a + 1] = __dmul_rn(ph[a], cv1);
+        }
+    }
+}
+
+// Eight lanes per cell, the sibling of conv_cells_block_to: lane q fetches dof
+// slots q and q + 8 of w (map entry, then the value) and of V (straight from
+// vbase: issued beside the map loads, not behind them) and gradient entry q.
+template <bool ADJ, typename VAL, typename SINK>
+__device__ __forceinline__ void
+conv_lin_cells_block_to(int bid, int ncells,
+                        const int *__restrict__ cellmap,      // [12][ncells]
+                        const double *__restrict__ glam,      // [6][ncells]
+                        const double *__restrict__ area,
+                        const double *__restrict__ vbase,     // [12][ncells]
+                        const VAL vsrc, TabRef dbctab, const SINK sink,
+                        const int *__restrict__ sel = nullptr, int nsel = 0) {
+#pragma clang fp contract(off)
+    const double *__restrict__ dbcvals = tab_row(dbctab);
+    const int t = bid * kBlock + threadIdx.x;
+    const int slot = t >> 3;
+    const int q = t & 7;
+    const bool live = sel ? slot < nsel : slot < ncells;
+    const int c = (sel && live) ? sel[slot] : slot;
+    const int cc = live ? c : 0;
+    const int qq = (q < 7) ? q : 0;
+    const int lane0 = (threadIdx.x & 63) & ~7;
+    const int m_a = cellmap[(size_t)q * ncells + cc];
+    const int m_b = (q < 4) ? cellmap[(size_t)(q + 8) * ncells + cc] : -1;
+    const double V_a = vbase[(size_t)q * ncells + cc];
+    const double V_b = (q < 4) ? vbase[(size_t)(q + 8) * ncells + cc] : 0.0;
+    const double gl_q = (q < 6) ? glam[(size_t)q * ncells + cc] : 0.0;
+    const double u_a = (m_a >= 0) ? vsrc.at(m_a) : dbcvals[-m_a - 1];
+    const double u_b = (q < 4) ? ((m_b >= 0) ? vsrc.at(m_b) : dbcvals[-m_b - 1])
+                               : 0.0;
+    double wl[6][2], Vl[6][2];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        wl[k >> 1][k & 1] = __shfl(u_a, lane0 + k, 64);
+        Vl[k >> 1][k & 1] = __shfl(V_a, lane0 + k, 64);
+    }
+#pragma unroll
+    for (int k = 8; k < 12; ++k) {
+        wl[k >> 1][k & 1] = __shfl(u_b, lane0 + k - 8, 64);
+        Vl[k >> 1][k & 1] = __shfl(V_b, lane0 + k - 8, 64);
+    }
+    double gl[3][2];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) gl[k >> 1][k & 1] = __shfl(gl_q, lane0 + k, 64);
+    const double wq =
+        (q < 7 && live) ? __dmul_rn(c_conv.qw[qq], area[cc]) : 0.0;
+    double pv[12];
+    conv_lin_values<ADJ>(qq, gl, wl, Vl, wq, pv);
+    double mine = 0.0, mine8 = 0.0;
+#pragma unroll
+    for (int sl = 0; sl < 12; ++sl) {
+        double v = pv[sl];
+        v += __shfl_xor(v, 1);
+        v += __shfl_xor(v, 2);
+        v += __shfl_xor(v, 4);
+        if (sl < 8) {
+            if (q == sl) mine = v;
+        } else {
+            if (q == sl - 8) mine8 = v;
+        }
+    }
+    sink(live, slot, c, q, mine, mine8);
+}
+
+template <bool ADJ>
+__global__ void __launch_bounds__(kBlock)
+k_conv_lin_cells(int ncells, const int *__restrict__ cellmap,
+                 const double *__restrict__ glam,
+                 const double *__restrict__ area,
+                 const double *__restrict__ vbase,
+                 const double *__restrict__ w_inner, TabRef dbctab,
+                 double *__restrict__ cellvals, const int *__restrict__ sel,
+                 int nsel) {
+    conv_lin_cells_block_to<ADJ>(blockIdx.x, ncells, cellmap, glam, area, vbase,
+                                 ConvFromVec{w_inner}, dbctab,
+                                 ConvStoreCells{cellvals, ncells}, sel, nsel);
+}
+
+// one lane per cell (lane_min cells and more): the sums over the points follow
+// the tree of the shuffles above, as in k_conv_cells_lane -- the same bits
+template <bool ADJ>
+__global__ void __launch_bounds__(kBlock)
+k_conv_lin_cells_lane(int ncells, const int *__restrict__ cellmap,
+                      const double *__restrict__ glam,
+                      const double *__restrict__ area,
+                      const double *__restrict__ vbase,
+                      const double *__restrict__ w_inner, TabRef dbctab,
+                      double *__restrict__ cellvals,
+                      const int *__restrict__ sel, int nsel) {
+#pragma clang fp contract(off)
+    const double *__restrict__ dbcvals = tab_row(dbctab);
+    const int slot = blockIdx.x * kBlock + threadIdx.x;
+    const bool live = sel ? slot < nsel : slot < ncells;
+    if (!live) return;
+    const int c = sel ? sel[slot] : slot;
+    int m[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) m[k] = cellmap[(size_t)k * ncells + c];
+    double Vl[6][2];
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+        Vl[k >> 1][k & 1] = vbase[(size_t)k * ncells + c];
+    double gl[3][2];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) gl[k >> 1][k & 1] = glam[(size_t)k * ncells + c];
+    const double ar = area[c];
+    double wl[6][2];
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+        wl[k >> 1][k & 1] = (m[k] >= 0) ? w_inner[m[k]] : dbcvals[-m[k] - 1];
+    double part[12][4];                 // tree of the sums over the points
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        double pv[12];
+        conv_lin_values<ADJ>(q, gl, wl, Vl, __dmul_rn(c_conv.qw[q], ar), pv);
+#pragma unroll
+        for (int sl = 0; sl < 12; ++sl) {
+            if (q & 1) part[sl][q >> 1] += pv[sl];
+            else part[sl][q >> 1] = pv[sl];
+        }
+    }
+#pragma unroll
+    for (int sl = 0; sl < 12; ++sl) {
+        part[sl][3] += 0.0;             // v_6 + v_7, v_7 = 0
+        const double s = (part[sl][0] + part[sl][1]) +
+                         (part[sl][2] + part[sl][3]);
+        cellvals[(size_t)sl * ncells + c] = s;
+    }
+}
+
 __global__ void __launch_bounds__(kBlock)
 k_conv_gather(int row0, int row1, const int *__restrict__ gptr,
               const int *__restrict__ gidx,
@@ -396,6 +643,26 @@ struct dns_conv {
         return {dbc_tab.p + (size_t)r * std::max(1, ndbc), nullptr, 0, 1};
     }
     int lane_min = dns::kConvLaneMin;      // DNS_CONV_LANE_MIN (read at create)
+    // Linearised about a base flow V (dns_conv_set_base_flow): the element
+    // launches evaluate L(V) w (DNS_CONV_FORWARD) or the cell transposes
+    // L(V)^T_cell w_cell (DNS_CONV_ADJOINT) instead of N(w) w, into the same
+    // cell values.  `vbase`: V at the twelve slots of every cell.
+    int lin_mode = 0;
+    dns::DevBuf<double> vbase;             // [12][ncells], internal cell order
+    std::vector<double> dbc_host;          // the constant Dirichlet set (the
+                                           // adjoint wants it zero)
+    bool linearised() const { return lin_mode != 0; }
+    // what the entry points that form N(u)u, N1, N2 themselves say to one
+    int refuse_linearised(const char *who) const {
+        if (!lin_mode) return DNS_OK;
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "linearised convection operator (%s mode, "
+                         "dns_conv_set_base_flow) in %s: it evaluates the "
+                         "nonlinear forms; dns_conv_clear_base_flow first",
+                         lin_mode == 2 ? "adjoint" : "forward", who);
+    }
+    int enqueue_lin_cells(const double *w_dev, hipStream_t s, const int *sel,
+                          int nsel);
     dns::DevBuf<double> cellvals_c;        // cell values of a second velocity
     dns::DevBuf<double> cellvals_x0;       // ... of N(v_lin) x0 (trapezoidal
                                            // stepper: residual in the gather)
@@ -438,6 +705,7 @@ struct dns_conv {
                       const int *sel = nullptr, int nsel = 0) {
         const int live = sel ? nsel : ncells;
         if (live <= 0) return DNS_OK;
+        if (lin_mode) return enqueue_lin_cells(v_dev, s, sel, nsel);
         if (live >= lane_min) {
             // streaming regime: one lane per cell (same values, bit for bit)
             hipLaunchKernelGGL(dns::k_conv_cells_lane,
@@ -974,6 +1242,33 @@ struct dns_conv_mat {
 };
 
 inline dns_conv::~dns_conv() { delete mat; }
+
+// the element launch of a linearised operator: mode x regime, four kernels
+inline int dns_conv::enqueue_lin_cells(const double *w_dev, hipStream_t s,
+                                       const int *sel, int nsel) {
+    const int live = sel ? nsel : ncells;
+    if (live <= 0) return DNS_OK;
+    if (vbase.n < (size_t)12 * ncells)
+        return dns::fail(DNS_ERR_NOT_READY,
+                         "linearised convection operator without a base flow");
+    const bool adj = lin_mode == 2;
+#define DNS_LIN_LAUNCH(KERNEL, GRID)                                          \
+    hipLaunchKernelGGL(KERNEL, GRID, dns::kBlock, 0, s, ncells, cellmap.p,    \
+                       glam.p, area.p, vbase.p, w_dev, dbc_ref(), cellvals.p, \
+                       sel, nsel)
+    if (live >= lane_min) {
+        const int g = (live + dns::kBlock - 1) / dns::kBlock;
+        if (adj) DNS_LIN_LAUNCH(dns::k_conv_lin_cells_lane<true>, g);
+        else DNS_LIN_LAUNCH(dns::k_conv_lin_cells_lane<false>, g);
+    } else {
+        const int g = (8 * live + dns::kBlock - 1) / dns::kBlock;
+        if (adj) DNS_LIN_LAUNCH(dns::k_conv_lin_cells<true>, g);
+        else DNS_LIN_LAUNCH(dns::k_conv_lin_cells<false>, g);
+    }
+#undef DNS_LIN_LAUNCH
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
 
 inline int dns_conv::enqueue_mat_cells(const double *v_dev, int newton,
                                        hipStream_t s, const int *sel,

@@ -356,6 +356,8 @@ static const char *const kQdPartitioned = "the sums would need an all-reduce";
 static const char *const kEnsPartitioned =
     "the slots would hold a rank's rows only, the Gram matrix would need an "
     "all-reduce (multi-rank ensembles are not supported)";
+static const char *const kLinPartitioned =
+    "the tails of the partitioned step evaluate N(v)v";
 static const char *const kQdMovingBc =
     "quadratics with a per-step Dirichlet table on the convection operator "
     "(dns_conv_set_dbc_table): moving boundary values are not part of the "
@@ -385,6 +387,19 @@ int dns_imex::check_live(const char *noun, int ndbc, int rows) const {
 
 // what a step refuses on their behalf
 int dns_imex::check_attachments() const {
+    if (conv && conv->linearised()) {
+        DNS_TRY(refuse_partitioned("linearised convection operator",
+                                   kLinPartitioned));
+        if (fn && fn->ncl > 0)
+            return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                             "linearised convection operator with functionals "
+                             "with cells: their kernel evaluates N(v)v on the "
+                             "listed cells (dns_imex_set_functionals without "
+                             "cells, or dns_conv_clear_base_flow)");
+        if (conv->lin_mode == dns::kConvAdjoint)
+            DNS_TRY(dns::check_adjoint_dbc(conv->dbc_host.data(), conv->ndbc,
+                                           conv->dbc_rows));
+    }
     if (fb) DNS_TRY(refuse_partitioned("observer feedback", kFbPartitioned));
     if (fb && fb->bc) {
         const Feedback::Boundary &b = *fb->bc;

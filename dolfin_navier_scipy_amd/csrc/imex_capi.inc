@@ -13,6 +13,11 @@ uint64_t dns_imex::config_key(const dns_imex_coeffs *cf) const {
                  kw((cf->carry_residual != 0) + 2 * carry_ok + 4 * six_ok +
                     8 * dcells_ok)});
     if (conv) k = mix64(k, {kw(conv->dbc_rows), kw(conv->dbc_tab.p)});
+    // (a linearised operator: mode and base flow; whatever sets, changes or
+    // clears them bumps dbc_gen)
+    if (conv && conv->linearised())
+        k = mix64(k, {kw(conv->lin_mode), kw(conv->vbase.p),
+                      kw(conv->dbc_gen)});
     return attachments_key(k);
 }
 
@@ -40,8 +45,9 @@ int dns_imex::build_r1_pair(const dns::HostCsr &rows, int v0) {
 
 // what the six-node step asks of the system, whatever the solve
 bool dns_imex::six_capable() const {
-    return env_six && !sys->dist() && !sys->streams(sys->K) &&
-           !sys->streams(R1) && sys->have_jg &&
+    // (its tail evaluates N(v)v of the new velocity: not a linearised operator)
+    return env_six && !(conv && conv->linearised()) && !sys->dist() &&
+           !sys->streams(sys->K) && !sys->streams(R1) && sys->have_jg &&
            sys->popts.schur == DNS_SCHUR_DENSE;
 }
 
@@ -158,8 +164,13 @@ int dns_imex::front_fused(const dns_imex_coeffs *cf, const StepPlan &pl) {
     double *x = xs[work].p;
     double e[5];
     dns::extrap_coeffs(nsol, cf->extrapolate_x0, e);
+    // a linearised operator launches its own element kernel in front; the
+    // front kernel then runs as it does without an operator (one launch more)
+    const bool lin = conv && conv->linearised();
+    if (lin) DNS_TRY(conv->enqueue_cells(xs[cur].p, s));
+    const dns_conv *fc = lin ? nullptr : conv;
     const int nconv =
-        conv ? (8 * conv->ncells + dns::kBlock - 1) / dns::kBlock : 0;
+        fc ? (8 * fc->ncells + dns::kBlock - 1) / dns::kBlock : 0;
     const dns::CarryRef cr =
         pl.carry ? dns::CarryRef{kxs[cur].p,  kxs[prev].p, kxs[pprev].p,
                                  kxs[p3].p,   kxs[p4].p,   rcarry.p}
@@ -170,12 +181,12 @@ int dns_imex::front_fused(const dns_imex_coeffs *cf, const StepPlan &pl) {
         h->K.lpr,                                                              \
         hipLaunchKernelGGL(                                                    \
             (dns::k_step_front<L, MODE>), nconv + h->gridS, dns::kBlock, 0, s, \
-            nconv, conv ? conv->ncells : 0,                                    \
-            conv ? conv->cellmap.p : (const int *)nullptr,                     \
-            conv ? conv->glam.p : (const double *)nullptr,                     \
-            conv ? conv->area.p : (const double *)nullptr,                     \
-            conv ? conv->dbc_ref() : dns::TabRef{nullptr, nullptr, 0, 1},      \
-            conv ? conv->cellvals.p : (double *)nullptr, n, nv,                \
+            nconv, fc ? fc->ncells : 0,                                        \
+            fc ? fc->cellmap.p : (const int *)nullptr,                         \
+            fc ? fc->glam.p : (const double *)nullptr,                         \
+            fc ? fc->area.p : (const double *)nullptr,                         \
+            fc ? fc->dbc_ref() : dns::TabRef{nullptr, nullptr, 0, 1},          \
+            fc ? fc->cellvals.p : (double *)nullptr, n, nv,                    \
             h->K.rowptr.p, h->K.colidx.p, h->K.vals.p, R1.rowptr.p,            \
             R1.colidx.p, R1.vals.p, xs[cur].p, xs[prev].p, xs[pprev].p,        \
             xs[p3].p, xs[p4].p, e[0], e[1], e[2], e[3], e[4], cf->a_c,         \

@@ -122,6 +122,7 @@ int dns_trap_create(dns_saddle *sys, dns_conv *conv, const double *m_vals,
     if (!sys || !conv || !m_vals || !a_vals || !out || nslots < 1)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     *out = nullptr;
+    DNS_TRY(conv->refuse_linearised("the trapezoidal stepper"));
     DNS_HIP(hipSetDevice(sys->device));
     // row-partitioned handle: the assembly is REPLICATED (every rank forms all
     // of N(v_lin), F and the right-hand side: element work, a few SpMVs), the
@@ -437,6 +438,7 @@ int dns_trap::enqueue_front(double dt, int lin_which, int lin_slot, int newton,
     const int nv = h->nv, np = h->np, n = h->n;
     const int nw = newton ? 1 : 0;
     const double hdt = 0.5 * dt;
+    DNS_TRY(cv->refuse_linearised("the trapezoidal stepper"));
     DNS_TRY(h->ensure_F_device());      // (a re-set-up slices the handle again)
     const double *vlin = t->traj[lin_which].p + (size_t)lin_slot * nv;
     // boundary values of the new time instance (controlled boundaries)

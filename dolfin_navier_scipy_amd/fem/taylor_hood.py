@@ -216,6 +216,16 @@ class TaylorHood(object):
                             keep_pattern=keep_pattern)
         return N1, N2, self.convection_vec(u0vec)
 
+    def linearised_convection_vec(self, V, w, adjoint=False):
+        """`L(V)w = N(V)w + N(w)V = (N1(V) + N2(V)) w` on the full space, or
+        with `adjoint` `(N1(V) + N2(V))^T w`, as `(vdim, 1)`: the NumPy
+        statement of the device's linearised operator
+        (`convection.ConvectionP2.set_base_flow`)"""
+        N1, N2, _ = self.convection_mats(np.asarray(V).reshape((-1, 1)))
+        L = (N1 + N2).tocsr()
+        wv = np.asarray(w, dtype=np.float64).reshape((-1, 1))
+        return (L.T if adjoint else L).dot(wv).reshape((-1, 1))
+
     # -- boundary forms (Robin-penalised control boundaries, outflow) ------
     def boundary_edges(self):
         """ids (into `self.edges`) of the boundary edges and their midpoints"""

@@ -1019,6 +1019,11 @@ class _ImexLoop(object):
                 raise ValueError(
                     '`rom` with moving Dirichlet values: constant boundary '
                     'values only, the mean flow carries them')
+            if getattr(self.conv, 'linearised', False):
+                raise ValueError(
+                    'linearised convection operator (`set_base_flow`) with '
+                    '`rom`: the tensor is the projection of the nonlinear '
+                    'form N(u)u (`clear_base_flow` first)')
         self.attachments += [a for a in (
             flog, None if fs is None else _StatisticsSums(self.stepper, fs),
             None if qf is None else _QuadraticLog(

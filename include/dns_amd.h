@@ -853,6 +853,33 @@ int dns_conv_set_dbc_row(dns_conv *cv, int32_t row);
 /* out = scale * N(u)u restricted to the inner dofs (host in/out; parity) */
 int dns_conv_apply(dns_conv *cv, const double *v_inner, double scale,
                    double *out);
+/* Linearised convection about a base flow V = [v_inner; dbcvals] (host
+ * pointers, expanded into the cells and uploaded once).  From here on every
+ * element launch of the operator -- dns_conv_apply, an attached CNAB / SBDF2
+ * stepper -- evaluates, for the perturbation w it is handed,
+ *   adjoint == 0:  L(V) w = int phi . ((w . grad) V + (V . grad) w)
+ *   adjoint != 0:  the sum of the cell transposes (N1(V) + N2(V))^T_cell w_cell
+ * instead of N(w)w, in the same cell-value layout.  The perturbation's own
+ * Dirichlet values stay the operator's (dns_conv_set_dbcvals / _set_dbc_table);
+ * the adjoint takes zero values and no table (then the sum is (L_II)^T w_I) and
+ * refuses anything else.  A linearised operator is refused by
+ * dns_conv_assemble*, dns_conv_project_tensor, the trapezoidal stepper, a
+ * row-partitioned IMEX stepper and functionals with cells.  The base flow is
+ * constant in time; the adjoint is the continuous one, stepped like any run */
+#define DNS_CONV_NONLINEAR 0
+#define DNS_CONV_FORWARD 1
+#define DNS_CONV_ADJOINT 2
+int dns_conv_set_base_flow(dns_conv *cv, const double *v_inner,
+                           const double *dbcvals, int32_t adjoint);
+int dns_conv_clear_base_flow(dns_conv *cv);
+int dns_conv_get_mode(const dns_conv *cv, int32_t *mode);
+/* TEST ONLY: the cell values [12][ncells] (the operator's internal cell order)
+ * the element launch leaves for v_inner in the current mode; nsel >= 0: only
+ * the internal cells sel[0..nsel) are evaluated, every other entry is `fill`.
+ * cell_pos (ncells, or NULL): the caller's cell -> internal cell */
+int dns_conv_cells_probe(dns_conv *cv, const double *v_inner,
+                         const int32_t *sel, int32_t nsel, double fill,
+                         double *cells_out, int32_t *cell_pos);
 /* the cubic convection tensor of a Galerkin projection (reduced-order models),
  *   out[i, j, k] = sum_cells sum_q w_q |cell| phi_i(x_q) . (u_j . grad) u_k (x_q),
  * nt x nb x nb, row-major, j the convecting and k the convected field, by the
