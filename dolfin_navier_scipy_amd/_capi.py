@@ -361,6 +361,15 @@ SIGNATURES = {
                                           ct.c_int32]),
     'dns_conv_clear_base_flow': (ct.c_int, [_VP]),
     'dns_conv_get_mode': (ct.c_int, [_VP, c_int32_p]),
+    'dns_conv_set_base_trajectory': (ct.c_int, [_VP, ct.c_int32, c_double_p,
+                                                ct.c_int32, ct.c_int32,
+                                                c_double_p, ct.c_int32]),
+    'dns_conv_set_base_rows': (ct.c_int, [_VP, ct.c_int32, c_int32_p]),
+    'dns_conv_set_base_row': (ct.c_int, [_VP, ct.c_int32]),
+    'dns_conv_get_base_info': (ct.c_int, [_VP, c_int32_p, c_int32_p]),
+    'dns_imex_ensemble_to_base': (ct.c_int, [_VP, ct.c_int32, ct.c_int32, _VP,
+                                             ct.c_int32, c_double_p,
+                                             ct.c_int32]),
     'dns_conv_cells_probe': (ct.c_int, [_VP, c_double_p, c_int32_p, ct.c_int32,
                                         ct.c_double, c_double_p, c_int32_p]),
     'dns_imex_set_convection': (ct.c_int, [_VP, _VP, ct.c_double]),

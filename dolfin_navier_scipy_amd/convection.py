@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _capi as C
 
-__all__ = ['ConvectionP2']
+__all__ = ['ConvectionP2', 'BaseTrajectory']
 
 ROM_MAX_BASIS = 33          # kRomMaxBasis of csrc/galerkin_host.hpp
 
@@ -50,6 +50,97 @@ def check_basis(nv, ndbc, basis, dbc_rows=None, ntest=None):
     return np.ascontiguousarray(B), D, nt
 
 
+# what `time_int_utils._checkuniformgrid` takes for "the same time":
+# `np.allclose(., 0)`, its absolute tolerance
+TIME_ATOL = 1e-8
+
+
+class BaseTrajectory(object):
+    """A time-varying base flow for `ConvectionP2.set_base_flow`: `m` stored
+    flows and their times, held piecewise constant (zero-order hold, no
+    interpolation).
+
+    `times`: `m` ascending stored times.  `v_rows`: `(m, nv)` inner values or
+    `(m, vdim)` full velocity vectors (`None`: the rows are on the device
+    already, `ImexStepper.ensemble_to_base`).  `dbcvals`: the base flow's
+    Dirichlet values, `(ndbc,)` for every row or `(m, ndbc)` (`None` with full
+    vectors: taken from them).  `time_map`: loop time -> stored time, the
+    identity by default; `lambda t: T - t` makes an adjoint run walk a stored
+    forward run backwards."""
+
+    def __init__(self, times, v_rows, dbcvals=None, time_map=None):
+        t = np.array(times, dtype=np.float64).reshape(-1)
+        if t.size < 1 or not np.all(np.isfinite(t)) \
+                or np.any(np.diff(t) <= TIME_ATOL):
+            raise ValueError('`times` must be ascending stored times, at '
+                             'least one: {0}'.format(t.tolist()[:8]))
+        self.times, self.time_map = t, time_map
+        self.v_rows = None if v_rows is None else \
+            np.asarray(v_rows, dtype=np.float64)
+        if self.v_rows is not None and (
+                self.v_rows.ndim != 2 or self.v_rows.shape[0] != t.size):
+            raise ValueError('`v_rows` must be {0} rows, one per stored time: '
+                             '{1}'.format(t.size, self.v_rows.shape))
+        self.dbcvals = None if dbcvals is None else \
+            np.asarray(dbcvals, dtype=np.float64)
+        # one stored flow holds for good; else a row holds for one interval
+        self.hold = np.inf if t.size == 1 else t[-1] - t[-2]
+
+    @property
+    def nrows(self):
+        return self.times.size
+
+    def row_at(self, time):
+        return int(self.rows_at([time])[0])
+
+    def rows_at(self, ts):
+        """for each loop time the index of the last stored time `<=
+        time_map(t)` (within `TIME_ATOL`).  `ValueError`, by the time, before
+        the first stored time and more than one storage interval behind the
+        last"""
+        rows = np.empty(len(ts), dtype=np.int32)
+        for k, t in enumerate(ts):
+            tm = float(t) if self.time_map is None \
+                else float(self.time_map(float(t)))
+            r = int(np.searchsorted(self.times, tm + TIME_ATOL,
+                                    side='right')) - 1
+            what = 'time {0!r}'.format(float(t)) + (
+                '' if self.time_map is None
+                else ' (stored time {0!r})'.format(tm))
+            if r < 0 or not np.isfinite(tm):
+                raise ValueError(
+                    'base trajectory: {0} lies before the first stored time '
+                    '{1!r}'.format(what, float(self.times[0])))
+            if tm - self.times[-1] > self.hold + TIME_ATOL:
+                raise ValueError(
+                    'base trajectory: {0} lies more than one storage interval '
+                    '({1!r}) behind the last stored time {2!r}'.format(
+                        what, float(self.hold), float(self.times[-1])))
+            rows[k] = r
+        return rows
+
+    def resolve_dbcvals(self, ndbc, full=None, dbcinds=None):
+        """the Dirichlet values as the library takes them: `(sets, flat)`"""
+        D = self.dbcvals
+        if D is None and ndbc == 0:
+            D = np.zeros((1, 0))
+        if D is None:
+            if full is None:
+                raise ValueError('base trajectory: `dbcvals`, the base '
+                                 'flow\'s Dirichlet values, are needed')
+            D = full[:, dbcinds]
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        if D.ndim <= 1 or (D.ndim == 2 and D.shape[0] == 1
+                           and self.nrows != 1):
+            D = D.reshape((1, -1))
+        if D.shape not in ((1, ndbc), (self.nrows, ndbc)):
+            raise ValueError(
+                'base trajectory: `dbcvals` must be ({0},) or ({1}, {0}), it '
+                'is {2}'.format(ndbc, self.nrows, D.shape))
+        flat = D.reshape(-1) if D.size else np.zeros(1)
+        return D.shape[0], np.ascontiguousarray(flat)
+
+
 class ConvectionP2(object):
     def __init__(self, cell_vdofs, glam, area, vdim, invinds, dbcinds,
                  dbcvals, device=0):
@@ -66,6 +157,7 @@ class ConvectionP2(object):
         self.glam, self.area = gl.reshape((-1, 3, 2)), ar
         self._dbcinds = None
         self.dbc_table_rows = 0     # > 0: a time-varying Dirichlet table is set
+        self.base_trajectory = None     # the `BaseTrajectory` that is set
         self._vdim = int(vdim)
         inv, dbi = _i32(invinds), _i32(dbcinds)
         self._invinds = inv
@@ -118,7 +210,14 @@ class ConvectionP2(object):
         `(N1(V) + N2(V))_II^T w` -- instead of `N(w)w`.  `base`: the full
         velocity vector `V` (`vdim` entries) or the pair `(v_inner, dbcvals)`.
         The perturbation's own Dirichlet values stay the operator's; the
-        adjoint takes zero values and no table (`ValueError` otherwise)"""
+        adjoint takes zero values and no table (`ValueError` otherwise).
+
+        `base` may be a `BaseTrajectory`: a time-varying base flow, uploaded
+        once.  `set_base_rows` then names the row of every step of an attached
+        loop, `set_base_row` the row for `apply`; `cnab` / `sbdftwo` arm both
+        from the trajectory's times"""
+        if isinstance(base, BaseTrajectory):
+            return self._set_base_trajectory(base, adjoint)
         if isinstance(base, (tuple, list)) and len(base) == 2:
             vin = C.as_f64(base[0], size=self.nv)
             dbv = C.as_f64(base[1], size=self.ndbc)
@@ -130,10 +229,57 @@ class ConvectionP2(object):
             dbv = np.zeros(1)
         C.check(self.lib.dns_conv_set_base_flow(
             self._h, C.dptr(vin), C.dptr(dbv), int(bool(adjoint))))
+        self.base_trajectory = None
+
+    def _set_base_trajectory(self, traj, adjoint):
+        R = traj.v_rows
+        if R is None or R.shape[1] not in (self.nv, self._vdim):
+            raise ValueError(
+                'base trajectory: `v_rows` must be ({0}, {1}) inner values or '
+                '({0}, {2}) full vectors, it is {3}'.format(
+                    traj.nrows, self.nv, self._vdim,
+                    None if R is None else R.shape))
+        full = R if (R.shape[1] == self._vdim and self._vdim != self.nv) \
+            else None
+        sets, dflat = traj.resolve_dbcvals(self.ndbc, full, self._dbcinds)
+        rows = np.ascontiguousarray(R if full is None
+                                    else full[:, self._invinds])
+        C.check(self.lib.dns_conv_set_base_trajectory(
+            self._h, traj.nrows,
+            C.dptr(rows.reshape(-1) if rows.size else np.zeros(1)),
+            int(rows.shape[1]), int(sets), C.dptr(dflat), int(bool(adjoint))))
+        self.base_trajectory = traj
+
+    def set_base_rows(self, rows):
+        """the per-step index table of a base trajectory: the `s`-th step of
+        the chunk an attached stepper runs next evaluates about row
+        `rows[min(s, len(rows) - 1)]` (descending: a reversed adjoint run;
+        repeats: a trajectory stored every k-th step)"""
+        r = _i32(np.asarray(rows).reshape(-1))
+        C.check(self.lib.dns_conv_set_base_rows(
+            self._h, int(r.size), r.ctypes.data_as(C.c_int32_p)))
+
+    def set_base_row(self, row):
+        """the row of the base trajectory `apply`, `cell_values` and
+        `host_callback` evaluate about (takes the index table off)"""
+        C.check(self.lib.dns_conv_set_base_row(self._h, int(row)))
+
+    @property
+    def base_trajectory_rows(self):
+        """rows of the base trajectory on the device; 0: a constant base flow
+        or none"""
+        return self._base_info()[0]
+
+    def _base_info(self):
+        nrows, nbrow = ct.c_int32(0), ct.c_int32(0)
+        C.check(self.lib.dns_conv_get_base_info(self._h, ct.byref(nrows),
+                                                ct.byref(nbrow)))
+        return nrows.value, nbrow.value
 
     def clear_base_flow(self):
         """back to `N(v)v`"""
         C.check(self.lib.dns_conv_clear_base_flow(self._h))
+        self.base_trajectory = None
 
     @property
     def linearised(self):

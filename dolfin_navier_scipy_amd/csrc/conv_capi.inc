@@ -200,6 +200,7 @@ int dns_conv_set_base_flow(dns_conv *cv, const double *v_inner,
     if (cv->vbase.n < vb.size()) DNS_TRY(cv->vbase.alloc(vb.size()));
     DNS_TRY(cv->vbase.upload(vb.data(), vb.size(), nullptr));
     DNS_HIP(hipDeviceSynchronize());
+    cv->release_base_trajectory();             // a constant base from here on
     cv->lin_mode = adjoint ? dns::kConvAdjoint : dns::kConvForward;
     cv->dbc_gen++;
     return DNS_OK;
@@ -210,8 +211,77 @@ int dns_conv_clear_base_flow(dns_conv *cv) try {
     DNS_HIP(hipSetDevice(cv->device));
     DNS_HIP(hipDeviceSynchronize());           // replays may still read it
     cv->vbase.release();
+    cv->release_base_trajectory();
     cv->lin_mode = dns::kConvNonlinear;
     cv->dbc_gen++;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// A time-varying base flow: `nrows` rows of inner velocities (`ld_host` apart)
+// and the base flow's Dirichlet values, one set or one per row.  One staged
+// upload of the packed rows; row 0 and no index table until one is set.
+int dns_conv_set_base_trajectory(dns_conv *cv, int32_t nrows,
+                                 const double *v_rows, int32_t ld_host,
+                                 int32_t dbc_nrows, const double *dbc_vals,
+                                 int32_t adjoint) try {
+    if (!cv) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(dns::check_base_trajectory(nrows, cv->nv_inner, v_rows, ld_host,
+                                       dbc_nrows, cv->ndbc, dbc_vals));
+    if (adjoint)
+        DNS_TRY(dns::check_adjoint_dbc(cv->dbc_host.data(), cv->ndbc,
+                                       cv->dbc_rows));
+    std::vector<double> rows;
+    DNS_TRY(dns::pack_base_trajectory(nrows, cv->nv_inner, v_rows, ld_host,
+                                      rows));
+    DNS_HIP(hipSetDevice(cv->device));
+    DNS_HIP(hipDeviceSynchronize());           // replays may still read it
+    DevBuf<double> T;
+    DNS_TRY(T.alloc(rows.size()));
+    DNS_TRY(T.upload(rows.data(), rows.size(), nullptr));
+    return cv->adopt_base_trajectory(T, nrows, dbc_nrows, dbc_vals,
+                                     adjoint != 0, nullptr);
+} DNS_CAPI_CATCH
+
+// The per-step index table: step s of the chunk an attached stepper runs next
+// (its counter) evaluates about row rows[min(s, n - 1)]
+int dns_conv_set_base_rows(dns_conv *cv, int32_t n, const int32_t *rows) try {
+    if (!cv) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(dns::check_base_rows(n, rows, cv->bt_rows));
+    DNS_HIP(hipSetDevice(cv->device));
+    DNS_HIP(hipDeviceSynchronize());           // replays may still read it
+    if (cv->brow.n < (size_t)n) {
+        DevBuf<int> tab;
+        DNS_TRY(tab.alloc((size_t)n));
+        std::swap(cv->brow.p, tab.p);
+        std::swap(cv->brow.n, tab.n);
+    }
+    cv->nbrow = 0;                             // (until the table is there)
+    cv->bt_ctr = nullptr;
+    cv->dbc_gen++;
+    DNS_TRY(cv->brow.upload(rows, (size_t)n, nullptr));
+    cv->nbrow = n;
+    cv->bt_row = rows[0];
+    cv->brow_gen++;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// The row for dns_conv_apply and the probes outside a stepper -- and, since it
+// takes the index table off, for the steps of an attached one
+int dns_conv_set_base_row(dns_conv *cv, int32_t row) try {
+    if (!cv) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(dns::check_base_row(row, cv->bt_rows));
+    cv->bt_row = row;
+    cv->nbrow = 0;
+    cv->bt_ctr = nullptr;
+    cv->dbc_gen++;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_conv_get_base_info(const dns_conv *cv, int32_t *nrows,
+                           int32_t *nbrow) try {
+    if (!cv) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    if (nrows) *nrows = cv->bt_rows;
+    if (nbrow) *nbrow = cv->nbrow;
     return DNS_OK;
 } DNS_CAPI_CATCH
 
@@ -246,6 +316,7 @@ int dns_conv_cells_probe(dns_conv *cv, const double *v_inner,
         DNS_TRY(dsel.alloc((size_t)std::max(1, nsel)));
         if (nsel > 0) DNS_TRY(dsel.upload(sel, (size_t)nsel, nullptr));
     }
+    cv->bt_ctr = nullptr;      // (outside a stepper: the row the host names)
     DNS_TRY(cv->enqueue_cells(dv.p, nullptr, nsel >= 0 ? dsel.p : nullptr,
                               std::max(0, nsel)));
     DNS_TRY(cv->cellvals.download(cells_out, nc12, nullptr));
@@ -264,6 +335,7 @@ int dns_conv_apply(dns_conv *cv, const double *v_inner, double scale,
     DNS_TRY(dv.alloc((size_t)cv->nv_inner));
     DNS_TRY(dout.alloc((size_t)cv->nv_inner));
     DNS_TRY(dv.upload(v_inner, (size_t)cv->nv_inner, nullptr));
+    cv->bt_ctr = nullptr;      // (outside a stepper: the row the host names)
     DNS_TRY(cv->enqueue(dv.p, scale, dout.p, nullptr));
     DNS_TRY(dout.download(outv, (size_t)cv->nv_inner, nullptr));
     DNS_HIP(hipDeviceSynchronize());

@@ -1,9 +1,13 @@
 // Host side of the linearised convection operator (convection.hpp,
 // conv_capi.inc): the expansion of a base flow into the twelve slots of every
-// cell and what the adjoint mode asks of the Dirichlet values.  No HIP in
-// here: tests/conv_lin_host_sanitize.cpp exercises it on the host alone.
+// cell, the layout and the index table of a base trajectory and what the
+// adjoint mode asks of the Dirichlet values.  No HIP in here:
+// tests/conv_lin_host_sanitize.cpp and tests/conv_traj_host_sanitize.cpp
+// exercise it on the host alone.
 #pragma once
+#include <algorithm>
 #include <cstddef>
+#include <cstdint>
 #include <vector>
 
 #include "status.hpp"
@@ -44,6 +48,102 @@ inline int expand_base_flow(const int *cmap, int ncells, int nv, int ndbc,
                 vbase[e] = dbcvals[d];
             }
         }
+    return DNS_OK;
+}
+
+// ---- base trajectory (dns_conv_set_base_trajectory) -------------------------
+// `nrows` rows of inner velocities, row r at `r * ldv` (ldv: nv rounded up to
+// 64, the slot layout of the snapshot ensemble: a slot copies row for row), the
+// base flow's Dirichlet values as one set or one per row, and an index table
+// `brow` that names the row of every step of an armed chunk (zero-order hold:
+// descending for a reversed run, repeated entries for a subsampled trajectory).
+constexpr size_t base_traj_ldv(int nv) {
+    return ((size_t)nv + 63) & ~(size_t)63;
+}
+constexpr size_t base_traj_offset(int row, size_t ldv) {
+    return (size_t)row * ldv;
+}
+// entries between two sets of Dirichlet values: 0 for one set (every row
+// reads set 0), max(1, ndbc) for a set per row
+constexpr int base_traj_dbc_stride(int dbc_nrows, int ndbc) {
+    return dbc_nrows > 1 ? (ndbc > 1 ? ndbc : 1) : 0;
+}
+
+inline int check_base_trajectory(int nrows, int nv, const double *v_rows,
+                                 long ld_host, int dbc_nrows, int ndbc,
+                                 const double *dbc_vals) {
+    if (nrows < 1)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: base trajectory of %d rows", nrows);
+    if (nv < 0 || ndbc < 0 || (nv > 0 && !v_rows) || (ndbc > 0 && !dbc_vals))
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: base trajectory needs the inner "
+                    "values (%d per row) and the Dirichlet values (%d)", nv,
+                    ndbc);
+    if (ld_host < (long)nv)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: base trajectory rows %ld apart, "
+                    "%d inner values each", ld_host, nv);
+    if (dbc_nrows != 1 && dbc_nrows != nrows)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: base trajectory of %d rows with "
+                    "%d sets of Dirichlet values (one set, or one per row)",
+                    nrows, dbc_nrows);
+    return DNS_OK;
+}
+
+// the rows as the device holds them: nrows x ldv, zeros behind nv
+inline int pack_base_trajectory(int nrows, int nv, const double *v_rows,
+                                long ld_host, std::vector<double> &out) {
+    DNS_TRY(check_base_trajectory(nrows, nv, v_rows, ld_host, 1, 0, nullptr));
+    const size_t ldv = base_traj_ldv(nv);
+    out.assign((size_t)nrows * std::max<size_t>(ldv, 1), 0.0);
+    for (int r = 0; r < nrows; ++r)
+        for (int i = 0; i < nv; ++i)
+            out[base_traj_offset(r, ldv) + (size_t)i] =
+                v_rows[(size_t)r * (size_t)ld_host + (size_t)i];
+    return DNS_OK;
+}
+
+// the per-step index table: every entry a row of the trajectory, refused by
+// name before anything is uploaded
+inline int check_base_rows(int n, const int32_t *rows, int nrows) {
+    if (nrows < 1)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: base rows without a base "
+                    "trajectory (dns_conv_set_base_trajectory)");
+    if (n < 1 || !rows)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: base rows: a table of %d entries",
+                    n);
+    for (int s = 0; s < n; ++s)
+        if (rows[s] < 0 || rows[s] >= nrows)
+            return fail(DNS_ERR_BAD_ARGUMENT,
+                        "linearised convection: base rows: entry %d is %d, "
+                        "outside 0..%d (the rows of the base trajectory)", s,
+                        (int)rows[s], nrows - 1);
+    return DNS_OK;
+}
+
+inline int check_base_row(int row, int nrows) {
+    if (nrows < 1)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: base row without a base "
+                    "trajectory (dns_conv_set_base_trajectory)");
+    if (row < 0 || row >= nrows)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: base row %d outside 0..%d (the "
+                    "rows of the base trajectory)", row, nrows - 1);
+    return DNS_OK;
+}
+
+// slots [first, first + count) of an ensemble of `nslots` slots
+inline int check_base_slots(int first, int count, int nslots) {
+    if (first < 0 || count < 1 || first > nslots - count)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: base trajectory from the "
+                    "ensemble: slots %d .. %ld outside 0..%d", first,
+                    (long)first + count - 1, nslots - 1);
     return DNS_OK;
 }
 

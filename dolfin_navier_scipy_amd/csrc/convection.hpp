@@ -397,20 +397,62 @@ conv_lin_values(int q, const double (&gl)[3][2], const double (&wl)[6][2],
     }
 }
 
+// Where the element kernels take the base flow V from.
+//   BaseCells : `vbase [12][ncells]`, a constant base flow expanded on the
+//               host (dns_conv_set_base_flow): no map in the way.
+//   BaseTraj  : row r of a resident trajectory of inner velocities (`V`, rows
+//               `ldv` apart: the slot layout of the snapshot ensemble) and of
+//               the base flow's Dirichlet values (`Vd`, one set -- `dstride`
+//               0 -- or one per row), gathered through `cellmap` as w is.
+//               r = brow[clamp(*ctr, 0, nbrow - 1)] with the device step
+//               counter of the stepper the operator is attached to, or the
+//               row the host names (`ctr` null).  Zero-order hold: nothing is
+//               rounded, the values are those of BaseCells about that row.
+struct BaseCells {
+    static constexpr bool kTrajectory = false;
+    const double *vbase;
+};
+struct BaseTraj {
+    static constexpr bool kTrajectory = true;
+    const double *V, *Vd;
+    const int *ctr, *brow;
+    int nbrow, row, nrows, dstride;
+    size_t ldv;
+};
+// The counter and the table entry depend on nothing a thread computes: asked
+// for beside the map loads, so that the gathers of V wait for one round trip
+// more than those of w.  (`r` is the same in every thread.)
+__device__ __forceinline__ int base_traj_row(const BaseTraj &b) {
+    int r = b.row;
+    if (b.ctr) {
+        int i = *b.ctr;
+        i = i < 0 ? 0 : (i >= b.nbrow ? b.nbrow - 1 : i);
+        r = b.brow[i];
+    }
+    return r < 0 ? 0 : (r >= b.nrows ? b.nrows - 1 : r);
+}
+__device__ __forceinline__ double base_traj_at(const BaseTraj &b, int r, int m) {
+    return (m >= 0) ? b.V[(size_t)r * b.ldv + m]
+                    : b.Vd[(size_t)r * b.dstride + (-m - 1)];
+}
+
 // Eight lanes per cell, the sibling of conv_cells_block_to: lane q fetches dof
-// slots q and q + 8 of w (map entry, then the value) and of V (straight from
-// vbase: issued beside the map loads, not behind them) and gradient entry q.
-template <bool ADJ, typename VAL, typename SINK>
+// slots q and q + 8 of w (map entry, then the value) and of V (BaseCells:
+// straight from vbase, issued beside the map loads, not behind them;
+// BaseTraj: behind the map entry and the row) and gradient entry q.
+template <bool ADJ, typename BASE, typename VAL, typename SINK>
 __device__ __forceinline__ void
 conv_lin_cells_block_to(int bid, int ncells,
                         const int *__restrict__ cellmap,      // [12][ncells]
                         const double *__restrict__ glam,      // [6][ncells]
                         const double *__restrict__ area,
-                        const double *__restrict__ vbase,     // [12][ncells]
+                        const BASE base,
                         const VAL vsrc, TabRef dbctab, const SINK sink,
                         const int *__restrict__ sel = nullptr, int nsel = 0) {
 #pragma clang fp contract(off)
     const double *__restrict__ dbcvals = tab_row(dbctab);
+    int brow = 0;
+    if constexpr (BASE::kTrajectory) brow = base_traj_row(base);
     const int t = bid * kBlock + threadIdx.x;
     const int slot = t >> 3;
     const int q = t & 7;
@@ -421,8 +463,15 @@ conv_lin_cells_block_to(int bid, int ncells,
     const int lane0 = (threadIdx.x & 63) & ~7;
     const int m_a = cellmap[(size_t)q * ncells + cc];
     const int m_b = (q < 4) ? cellmap[(size_t)(q + 8) * ncells + cc] : -1;
-    const double V_a = vbase[(size_t)q * ncells + cc];
-    const double V_b = (q < 4) ? vbase[(size_t)(q + 8) * ncells + cc] : 0.0;
+    double V_a, V_b;
+    if constexpr (BASE::kTrajectory) {
+        V_a = base_traj_at(base, brow, m_a);
+        V_b = (q < 4) ? base_traj_at(base, brow, m_b) : 0.0;
+    } else {
+        const double *__restrict__ vbase = base.vbase;        // [12][ncells]
+        V_a = vbase[(size_t)q * ncells + cc];
+        V_b = (q < 4) ? vbase[(size_t)(q + 8) * ncells + cc] : 0.0;
+    }
     const double gl_q = (q < 6) ? glam[(size_t)q * ncells + cc] : 0.0;
     const double u_a = (m_a >= 0) ? vsrc.at(m_a) : dbcvals[-m_a - 1];
     const double u_b = (q < 4) ? ((m_b >= 0) ? vsrc.at(m_b) : dbcvals[-m_b - 1])
@@ -461,33 +510,33 @@ conv_lin_cells_block_to(int bid, int ncells,
     sink(live, slot, c, q, mine, mine8);
 }
 
-template <bool ADJ>
+template <bool ADJ, typename BASE = BaseCells>
 __global__ void __launch_bounds__(kBlock)
 k_conv_lin_cells(int ncells, const int *__restrict__ cellmap,
                  const double *__restrict__ glam,
-                 const double *__restrict__ area,
-                 const double *__restrict__ vbase,
+                 const double *__restrict__ area, const BASE base,
                  const double *__restrict__ w_inner, TabRef dbctab,
                  double *__restrict__ cellvals, const int *__restrict__ sel,
                  int nsel) {
-    conv_lin_cells_block_to<ADJ>(blockIdx.x, ncells, cellmap, glam, area, vbase,
+    conv_lin_cells_block_to<ADJ>(blockIdx.x, ncells, cellmap, glam, area, base,
                                  ConvFromVec{w_inner}, dbctab,
                                  ConvStoreCells{cellvals, ncells}, sel, nsel);
 }
 
 // one lane per cell (lane_min cells and more): the sums over the points follow
 // the tree of the shuffles above, as in k_conv_cells_lane -- the same bits
-template <bool ADJ>
+template <bool ADJ, typename BASE = BaseCells>
 __global__ void __launch_bounds__(kBlock)
 k_conv_lin_cells_lane(int ncells, const int *__restrict__ cellmap,
                       const double *__restrict__ glam,
-                      const double *__restrict__ area,
-                      const double *__restrict__ vbase,
+                      const double *__restrict__ area, const BASE base,
                       const double *__restrict__ w_inner, TabRef dbctab,
                       double *__restrict__ cellvals,
                       const int *__restrict__ sel, int nsel) {
 #pragma clang fp contract(off)
     const double *__restrict__ dbcvals = tab_row(dbctab);
+    int brow = 0;
+    if constexpr (BASE::kTrajectory) brow = base_traj_row(base);
     const int slot = blockIdx.x * kBlock + threadIdx.x;
     const bool live = sel ? slot < nsel : slot < ncells;
     if (!live) return;
@@ -496,9 +545,16 @@ k_conv_lin_cells_lane(int ncells, const int *__restrict__ cellmap,
 #pragma unroll
     for (int k = 0; k < 12; ++k) m[k] = cellmap[(size_t)k * ncells + c];
     double Vl[6][2];
+    if constexpr (BASE::kTrajectory) {
 #pragma unroll
-    for (int k = 0; k < 12; ++k)
-        Vl[k >> 1][k & 1] = vbase[(size_t)k * ncells + c];
+        for (int k = 0; k < 12; ++k)
+            Vl[k >> 1][k & 1] = base_traj_at(base, brow, m[k]);
+    } else {
+        const double *__restrict__ vbase = base.vbase;        // [12][ncells]
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+            Vl[k >> 1][k & 1] = vbase[(size_t)k * ncells + c];
+    }
     double gl[3][2];
 #pragma unroll
     for (int k = 0; k < 6; ++k) gl[k >> 1][k & 1] = glam[(size_t)k * ncells + c];
@@ -651,6 +707,68 @@ struct dns_conv {
     dns::DevBuf<double> vbase;             // [12][ncells], internal cell order
     std::vector<double> dbc_host;          // the constant Dirichlet set (the
                                            // adjoint wants it zero)
+    // ... or about a time-varying one (dns_conv_set_base_trajectory,
+    // dns_imex_ensemble_to_base): `bt_rows` rows of inner velocities in
+    // `btraj`, `ldv` apart, the base flow's Dirichlet values in `btraj_dbc`
+    // (one set or `bt_rows`), and the per-step index table `brow` of `nbrow`
+    // entries, read through the device step counter of the stepper the
+    // operator is attached to (`bt_ctr`, as `dbc_ctr`); without a table, or
+    // outside a stepper, row `bt_row` (dns_conv_set_base_row).  bt_rows == 0:
+    // a constant base flow (`vbase`) or none.
+    dns::DevBuf<double> btraj, btraj_dbc;
+    dns::DevBuf<int> brow;
+    int bt_rows = 0, bt_dbc_rows = 0, nbrow = 0, bt_row = 0;
+    const int *bt_ctr = nullptr;
+    uint64_t brow_gen = 0;    // bumped by every new index table: the attached
+                              // stepper counts its steps from 0 again
+    dns::BaseTraj base_traj() const {
+        const bool tab = nbrow > 0 && bt_ctr;
+        return {btraj.p, btraj_dbc.p, tab ? bt_ctr : nullptr, brow.p, nbrow,
+                bt_row, bt_rows, dns::base_traj_dbc_stride(bt_dbc_rows, ndbc),
+                dns::base_traj_ldv(nv_inner)};
+    }
+    void release_base_trajectory() {
+        btraj.release();
+        btraj_dbc.release();
+        brow.release();
+        bt_rows = bt_dbc_rows = nbrow = bt_row = 0;
+        bt_ctr = nullptr;
+    }
+    // The rows `T` (nrows x ldv, on the device by the time `s` has run) take
+    // the place of whatever base flow there was; the base flow's Dirichlet
+    // values come from the host.  Whatever can fail comes before the first
+    // change: a refusal leaves the operator as it was.  The caller has checked
+    // the shapes (check_base_trajectory) and quiesced the device.
+    int adopt_base_trajectory(dns::DevBuf<double> &T, int nrows, int dbc_nrows,
+                              const double *dbc_vals, bool adjoint,
+                              hipStream_t s) {
+        if (adjoint)
+            DNS_TRY(dns::check_adjoint_dbc(dbc_host.data(), ndbc, dbc_rows));
+        const size_t nd = (size_t)std::max(1, ndbc);
+        dns::DevBuf<double> D;
+        DNS_TRY(D.alloc(nd * dbc_nrows));
+        DNS_TRY(D.zero(s));
+        if (ndbc > 0)
+            DNS_TRY(D.upload(dbc_vals, (size_t)ndbc * dbc_nrows, s));
+        DNS_HIP(hipStreamSynchronize(s));
+        // (nothing is refused from here on)
+        release_base_trajectory();
+        vbase.release();
+        std::swap(btraj.p, T.p);
+        std::swap(btraj.n, T.n);
+        std::swap(btraj_dbc.p, D.p);
+        std::swap(btraj_dbc.n, D.n);
+        bt_rows = nrows;
+        bt_dbc_rows = dbc_nrows;
+        lin_mode = adjoint ? dns::kConvAdjoint : dns::kConvForward;
+        dbc_gen++;
+        return DNS_OK;
+    }
+    // the stepper the operator is attached to hands it its step counter
+    void attach_counter(const int *ctr) {
+        dbc_ctr = dbc_rows > 0 ? ctr : nullptr;
+        bt_ctr = nbrow > 0 ? ctr : nullptr;
+    }
     bool linearised() const { return lin_mode != 0; }
     // what the entry points that form N(u)u, N1, N2 themselves say to one
     int refuse_linearised(const char *who) const {
@@ -1243,27 +1361,51 @@ struct dns_conv_mat {
 
 inline dns_conv::~dns_conv() { delete mat; }
 
-// the element launch of a linearised operator: mode x regime, four kernels
+// the element launch of a linearised operator: mode x regime, four kernels,
+// each with the constant base flow or a row of the base trajectory behind it
 inline int dns_conv::enqueue_lin_cells(const double *w_dev, hipStream_t s,
                                        const int *sel, int nsel) {
     const int live = sel ? nsel : ncells;
     if (live <= 0) return DNS_OK;
-    if (vbase.n < (size_t)12 * ncells)
+    const bool traj = bt_rows > 0;
+    if (traj ? btraj.n < dns::base_traj_offset(bt_rows,
+                                               dns::base_traj_ldv(nv_inner))
+             : vbase.n < (size_t)12 * ncells)
         return dns::fail(DNS_ERR_NOT_READY,
                          "linearised convection operator without a base flow");
     const bool adj = lin_mode == 2;
-#define DNS_LIN_LAUNCH(KERNEL, GRID)                                          \
+#define DNS_LIN_LAUNCH(KERNEL, GRID, BASE)                                    \
     hipLaunchKernelGGL(KERNEL, GRID, dns::kBlock, 0, s, ncells, cellmap.p,    \
-                       glam.p, area.p, vbase.p, w_dev, dbc_ref(), cellvals.p, \
+                       glam.p, area.p, BASE, w_dev, dbc_ref(), cellvals.p,    \
                        sel, nsel)
-    if (live >= lane_min) {
-        const int g = (live + dns::kBlock - 1) / dns::kBlock;
-        if (adj) DNS_LIN_LAUNCH(dns::k_conv_lin_cells_lane<true>, g);
-        else DNS_LIN_LAUNCH(dns::k_conv_lin_cells_lane<false>, g);
+    const int g1 = (live + dns::kBlock - 1) / dns::kBlock;
+    const int g8 = (8 * live + dns::kBlock - 1) / dns::kBlock;
+    if (traj) {
+        using dns::BaseTraj;
+        const BaseTraj bt = base_traj();
+        if (live >= lane_min) {
+            if (adj)
+                DNS_LIN_LAUNCH((dns::k_conv_lin_cells_lane<true, BaseTraj>), g1,
+                               bt);
+            else
+                DNS_LIN_LAUNCH((dns::k_conv_lin_cells_lane<false, BaseTraj>),
+                               g1, bt);
+        } else {
+            if (adj)
+                DNS_LIN_LAUNCH((dns::k_conv_lin_cells<true, BaseTraj>), g8, bt);
+            else
+                DNS_LIN_LAUNCH((dns::k_conv_lin_cells<false, BaseTraj>), g8,
+                               bt);
+        }
     } else {
-        const int g = (8 * live + dns::kBlock - 1) / dns::kBlock;
-        if (adj) DNS_LIN_LAUNCH(dns::k_conv_lin_cells<true>, g);
-        else DNS_LIN_LAUNCH(dns::k_conv_lin_cells<false>, g);
+        const dns::BaseCells bc{vbase.p};
+        if (live >= lane_min) {
+            if (adj) DNS_LIN_LAUNCH(dns::k_conv_lin_cells_lane<true>, g1, bc);
+            else DNS_LIN_LAUNCH(dns::k_conv_lin_cells_lane<false>, g1, bc);
+        } else {
+            if (adj) DNS_LIN_LAUNCH(dns::k_conv_lin_cells<true>, g8, bc);
+            else DNS_LIN_LAUNCH(dns::k_conv_lin_cells<false>, g8, bc);
+        }
     }
 #undef DNS_LIN_LAUNCH
     DNS_HIP(hipGetLastError());

@@ -315,6 +315,10 @@ struct dns_imex : dns::Ring {
     bool tables() const;
     int rows_left() const;
     int rewind_tables();           // new tables: the counter back to 0
+    // a new index table on the operator (dns_conv_set_base_rows) is a new
+    // table: seen by the next dns_imex_step / dns_imex_run
+    uint64_t brow_gen_seen = 0;
+    int adopt_base_rows();
     dns::TabRef g_src() const {
         if (tab_rows > 0 && tab_v)
             return {gtab.p, stepctr.p, sys->nv, tab_rows};

@@ -294,8 +294,8 @@ uint64_t dns_imex::attachments_key(uint64_t k) const {
 }
 
 bool dns_imex::tables() const {
-    return tab_rows > 0 || (conv && conv->dbc_rows > 0) || fb || rec ||
-           fn || stat || qd || ens;
+    return tab_rows > 0 || (conv && conv->dbc_rows > 0) ||
+           (conv && conv->nbrow > 0) || fb || rec || fn || stat || qd || ens;
 }
 
 int dns_imex::rows_left() const {
@@ -332,6 +332,16 @@ int dns_imex::rewind_tables() {
     DNS_TRY(sync_counter());
     DNS_HIP(hipStreamSynchronize(sys->stream));
     return DNS_OK;
+}
+
+// The per-step index table of a base trajectory lives on the operator, which
+// does not know its stepper: the step that follows a new one (a step or a run)
+// counts from 0 like after any table setter -- unless one of those has just
+// rewound the counter, as the slices of a time loop do.
+int dns_imex::adopt_base_rows() {
+    if (!conv || conv->brow_gen == brow_gen_seen) return DNS_OK;
+    brow_gen_seen = conv->brow_gen;
+    return tab_pos != 0 ? rewind_tables() : DNS_OK;
 }
 
 // None of the six runs on a row-partitioned / distributed stepper: refused
@@ -1658,6 +1668,49 @@ int dns_imex_clear_ensemble(dns_imex *st) try {
     DNS_TRY(quiesce(st));
     st->ens.reset();
     return DNS_OK;
+} DNS_CAPI_CATCH
+
+// Slots [first, first + count) of the ensemble become the base trajectory of
+// the linearised operator `cv`, device to device on the stepper's stream (the
+// slot layout is the trajectory's: one copy); only the base flow's Dirichlet
+// values cross the bus.  The forward run that filled the slots and the
+// linearised / adjoint run about them never meet on the host.
+int dns_imex_ensemble_to_base(dns_imex *st, int32_t first, int32_t count,
+                              dns_conv *cv, int32_t dbc_nrows,
+                              const double *dbc_vals, int32_t adjoint) try {
+    if (!st || !cv) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    static const char *const who =
+        "linearised convection: base trajectory from the ensemble";
+    if (!st->ens)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "%s: no ensemble is set (dns_imex_set_ensemble)", who);
+    const dns_imex::Ensemble &e = *st->ens;
+    dns_saddle *h = st->sys;
+    DNS_TRY(dns::check_base_slots(first, count, e.nslots));
+    if (cv->device != h->device)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "%s: the operator lives on device %d, the ensemble on "
+                         "device %d", who, cv->device, h->device);
+    if (cv->nv_inner != h->nv || dns::base_traj_ldv(cv->nv_inner) != e.ldv)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT,
+                         "%s: the operator has %d inner dofs, a slot holds %d",
+                         who, cv->nv_inner, h->nv);
+    // (the rows are on the device: only their number and the values are asked)
+    DNS_TRY(dns::check_base_trajectory(count, 0, nullptr, 0, dbc_nrows,
+                                       cv->ndbc, dbc_vals));
+    if (adjoint)
+        DNS_TRY(dns::check_adjoint_dbc(cv->dbc_host.data(), cv->ndbc,
+                                       cv->dbc_rows));
+    DNS_HIP(hipSetDevice(h->device));
+    DNS_HIP(hipDeviceSynchronize());           // replays may still read it
+    hipStream_t s = h->stream;
+    const size_t len = dns::base_traj_offset(count, e.ldv);
+    dns::DevBuf<double> T;
+    DNS_TRY(T.alloc(len));
+    DNS_HIP(hipMemcpyAsync(T.p, e.E.p + dns::base_traj_offset(first, e.ldv),
+                           len * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return cv->adopt_base_trajectory(T, count, dbc_nrows, dbc_vals,
+                                     adjoint != 0, s);
 } DNS_CAPI_CATCH
 
 // ---- the two dense operations alone (host pointers; tests) ------------------

@@ -18,6 +18,12 @@ uint64_t dns_imex::config_key(const dns_imex_coeffs *cf) const {
     if (conv && conv->linearised())
         k = mix64(k, {kw(conv->lin_mode), kw(conv->vbase.p),
                       kw(conv->dbc_gen)});
+    // (about a base trajectory: its buffers, its rows, the index table and the
+    // row the host names; they bump dbc_gen as well)
+    if (conv && conv->linearised() && conv->bt_rows > 0)
+        k = mix64(k, {kw(conv->btraj.p), kw(conv->btraj_dbc.p),
+                      kw(conv->bt_rows + 2 * (conv->bt_dbc_rows > 1)),
+                      kw(conv->brow.p), kw(conv->nbrow), kw(conv->bt_row)});
     return attachments_key(k);
 }
 
@@ -111,7 +117,7 @@ int dns_imex::prime_dcells(const dns_imex_coeffs *cf, const dns_solve_opts *o) {
     dcells_ok = false;
     // (asked before the batches set the cycle length: a one-step cycle?)
     if (!plan(cf, o, 1).dtail) return DNS_OK;
-    conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
+    conv->attach_counter(stepctr.p);
     DNS_TRY(conv->enqueue_cells(xs[cur].p, h->stream, part.conv_sel.p,
                                 part.nsel));
     dcells_ok = true;
@@ -377,7 +383,7 @@ dns::StepHooks dns_imex::hooks(const dns_imex_coeffs *cf, const StepPlan &pl) {
 void dns_imex::turn_convection() {
     if (!conv) return;
     std::swap(nc, no);
-    conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
+    conv->attach_counter(stepctr.p);
 }
 
 int dns_imex::step_device(const dns_imex_coeffs *cf, const dns_solve_opts *o,
@@ -502,7 +508,7 @@ int dns_imex::prime_six(const dns_imex_coeffs *cf, bool keep_r) {
     DNS_TRY(dns::enqueue_extrap(order, xs, *this, x0buf[work & 1].p, h->n,
                                 h->stream));
     if (conv) {
-        conv->dbc_ctr = conv->dbc_rows > 0 ? stepctr.p : nullptr;
+        conv->attach_counter(stepctr.p);
         DNS_TRY(conv->enqueue_cells(xs[cur].p, h->stream));
         six_conv_gen = conv->dbc_gen;
     }
@@ -1241,6 +1247,7 @@ int dns_imex_step(dns_imex *st, const double *nfc_new,
     dns_solve_stats *sp = stats ? stats : &local;
     memset(sp, 0, sizeof(*sp));
     DNS_TRY(st->refuse_probed());
+    DNS_TRY(st->adopt_base_rows());
     DNS_TRY(st->step_preamble(nfc_new, cf, o));
     // nobody reads the history per time step (scripts/extrap_probe.py does)
     h->want_history = st->env_step_history;
@@ -1268,6 +1275,7 @@ int dns_imex_run(dns_imex *st, int32_t nsteps, const dns_imex_coeffs *cf,
     ImexRun r{st, h, cf, nsteps, last_stats ? last_stats : &local, o, o};
     memset(r.sp, 0, sizeof(*r.sp));
     DNS_TRY(st->refuse_probed());
+    DNS_TRY(st->adopt_base_rows());
     if (st->tables() && st->rows_left() < nsteps)
         return dns::fail(DNS_ERR_NOT_READY,
                          "%d steps asked for, the per-step tables hold %d more "

@@ -1057,6 +1057,38 @@ class ImexStepper(object):
             C.dptr(out.reshape(-1) if out.size else np.zeros(1))))
         return out
 
+    def ensemble_to_base(self, conv, times=None, first=0, count=None,
+                         dbcvals=None, adjoint=False, time_map=None):
+        """slots `first .. first + count` of the ensemble (default: all from
+        `first` on) become the base trajectory of the linearised operator
+        `conv` (`ConvectionP2.set_base_flow` of a `BaseTrajectory`), device to
+        device: the forward run that filled the slots and the linearised or
+        adjoint run about them never meet on the host.  `dbcvals`: the base
+        flow's Dirichlet values, `(ndbc,)` or `(count, ndbc)` -- the only
+        thing that crosses the bus.  With `times` (one per slot, ascending;
+        `time_map` as in `BaseTrajectory`) the operator gets the trajectory's
+        clock as well, so that `cnab` / `sbdftwo` arm its rows; without, name
+        them with `conv.set_base_rows` / `set_base_row`.  Refused by name
+        (`ValueError`): no ensemble, slots out of range, another device,
+        another number of inner dofs"""
+        from .convection import BaseTrajectory
+        nslots = getattr(self, '_ens_slots', None)
+        if count is None:
+            count = (nslots if nslots is not None else 0) - int(first)
+        count = int(count)
+        traj = BaseTrajectory(np.arange(count) if times is None else times,
+                              None, dbcvals, time_map=time_map) \
+            if count >= 1 else None
+        if traj is not None and traj.nrows != count:
+            raise ValueError('base trajectory: {0} `times` for {1} slots'
+                             .format(traj.nrows, count))
+        sets, dflat = (1, np.zeros(1)) if traj is None else \
+            traj.resolve_dbcvals(conv.ndbc)
+        C.check(self.lib.dns_imex_ensemble_to_base(
+            self._h, int(first), count, conv._h, int(sets), C.dptr(dflat),
+            int(bool(adjoint))))
+        conv.base_trajectory = traj if times is not None else None
+
     def ensemble_gram(self, W=None, m=None):
         """`G = E W E^T` of the first `m` slots (default: all), `(m, m)`,
         exactly symmetric; `W`: symmetric NV x NV (None: the identity).  Runs

@@ -947,6 +947,11 @@ class _ImexLoop(object):
                                   stepper.sys.NP) \
             if (self.on_device and rsd.get('record', False)) else None
         self.attachments = []
+        # a linearised operator about a time-varying base flow
+        # (`convection.BaseTrajectory`): every evaluation names the row of the
+        # time of its operand; `t_n`: the time of the state `v_n` (`march`)
+        self.traj = getattr(conv, 'base_trajectory', None)
+        self.t_n = None
 
     def attach(self, lti, fb_dev, tstart, trange=None):
         """the functionals, the statistics, the quadratics, the POD ensemble
@@ -1082,6 +1087,9 @@ class _ImexLoop(object):
         if moving:
             dbt[ns] = self._dbc(self.cur)
         span = [0, 0]
+        # (`t_cur[s]`: the time of the state step `s` starts from -- the
+        # convention of `dbt[s]`)
+        t_cur = [self.t_n] + list(ctrange[:-1])
         bfa, nstat = self.bfb_att, len(self.statvals)
         if bfa is not None:
             bfa.slice_bcs = []
@@ -1096,6 +1104,8 @@ class _ImexLoop(object):
                 self.conv.set_dbc_table(tab)
             elif moving:
                 self.conv.set_dbc_table(dbt[a:b])
+            if self.traj is not None:
+                self.conv.set_base_rows(self.traj.rows_at(t_cur[a:b]))
             tables = _Tables(dbt[a:b + 1] if moving else None)
             for att in self.attachments:
                 att.arm(ctrange[a:b], tables)
@@ -1134,6 +1144,7 @@ class _ImexLoop(object):
         if self.scheme.keep_prev:
             self.v_c = states[ns - 2][0] if ns > 1 else self.v_n
         self.v_n, self.p_n = states[ns - 1]
+        self.t_n = ctrange[-1]
 
     def step(self, ctime):
         """one step with a host round trip: each callback of the reference's
@@ -1142,6 +1153,8 @@ class _ImexLoop(object):
         v_c, p_c = self.v_n, self.p_n
         if conv is not None and (self.moving or self.statvals):
             conv.set_dbcvals(self._dbc(cur))
+        if conv is not None and self.traj is not None:
+            conv.set_base_row(self.traj.row_at(self.t_n))
         nfc_new = None if conv is not None \
             else self.f_vdp(self.appndbcs(v_c, cur.bcs))
         nxt, gp = self._terms_at(ctime, v_c, p_c)
@@ -1157,6 +1170,7 @@ class _ImexLoop(object):
         self.savevp(self.appndbcs(v_n, nxt.bcs), p_n, time=ctime)
         self.prev, self.cur = cur, nxt
         self.v_c, self.v_n, self.p_n = v_c, v_n, p_n
+        self.t_n = ctime
 
     def _blown_up(self, kck, ntimeslices, check_ff_maxv, verbose):
         """the blow-up guard at a slice's start"""
@@ -1173,6 +1187,7 @@ class _ImexLoop(object):
     def march(self, tstart, listofts, ntimeslices, check_ff_maxv, verbose):
         """all slices; returns `ffflag`"""
         ffflag = 0
+        self.t_n = tstart
         for att in self.attachments:
             att.start(self.v_n, self.p_n, tstart)
         for kck, ctrange in enumerate(listofts):
@@ -1268,15 +1283,21 @@ def _onestepheun(vc=None, pc=None, tc=None, tn=None, M=None, A=None, J=None,
                  scalep=1., dfv_c=None, dynamic_rhs=None, drm={},
                  bcs_c=None, applybcs=None, appndbcs=None, getbcs=None,
                  f_tdp=None, f_vdp=None, g_tdp=None, krylov=None,
-                 krpslvprms={}):
+                 krpslvprms={}, base_row=None):
     """IMEX-Euler predictor / trapezoidal corrector (tiu:366-477); both
     saddle solves go through `lin_alg_utils.solve_sadpnt_smw` on the GPU.
-    The corrector keeps the reference's `amat=M` (tiu:466)."""
+    The corrector keeps the reference's `amat=M` (tiu:466).  `base_row(t)`: a
+    device convection about a base trajectory is told the time of the state
+    `f_vdp` is about to see"""
     NP, NV = J.shape
+    if base_row is None:
+        def base_row(time):
+            pass
     dt = tn - tc
     JT = sps.csr_matrix(J.T)
     bfv_c, _, mbc_c = applybcs(bcs_c)
     fv_c = f_tdp(tc)
+    base_row(tc)
     nfc_c = f_vdp(appndbcs(vc, bcs_c))
     tdfv_n, drm = dynamic_rhs(tn, vc=vc, memory=drm, mode='heunpred')
     tbcs = getbcs(tn, appndbcs(vc, bcs_c), pc, mode='heunpred')
@@ -1289,6 +1310,7 @@ def _onestepheun(vc=None, pc=None, tc=None, tn=None, M=None, A=None, J=None,
     tv_n = tvp_n[:NV, :]
     tp_n = 1./dt*scalep*tvp_n[NV:, :]
     dfv_n, drm = dynamic_rhs(tn, vc=tv_n, memory=drm, mode='heuncorr')
+    base_row(tn)
     tnfc_n = f_vdp(appndbcs(tv_n, tbcs))
     bcs_n = getbcs(tn, appndbcs(tv_n, tbcs), tp_n, mode='heuncorr')
     bfv_n, bfp_n, mbc_n = applybcs(bcs_n)
@@ -1299,6 +1321,7 @@ def _onestepheun(vc=None, pc=None, tc=None, tn=None, M=None, A=None, J=None,
                                 krpslvprms=krpslvprms)
     v_n = vp_n[:NV].reshape((NV, 1))
     p_n = 1./dt*scalep*vp_n[NV:].reshape((NP, 1))
+    base_row(tn)
     nfc_n = f_vdp(appndbcs(v_n, bcs_n))
     return (v_n, p_n, bcs_n, bfv_n, mbc_c, mbc_n, fv_n, nfc_c, nfc_n, dfv_n,
             drm)
@@ -1327,6 +1350,16 @@ def _imex_loop(scheme, trange, inivel, inip, bcs_ini, M, A, J, f_vdp, f_tdp,
         bfb = None
     dt, listofts = _inittimegrid(trange, ntimeslices=ntimeslices)
     NP, NV = J.shape
+    # a base trajectory on the operator must cover the time of every state
+    # convection is evaluated at (all but the last): refused by the time,
+    # before anything is armed
+    traj = getattr(device_convection, 'base_trajectory', None)
+    base_row = None
+    if traj is not None:
+        traj.rows_at(trange[:-1])
+
+        def base_row(time):
+            device_convection.set_base_row(traj.row_at(time))
     if device_convection is not None and f_vdp is None:
         f_vdp = device_convection.host_callback(invinds)   # Heun start only
     dynamic_rhs, f_vdp = _wrap_callbacks(NV, dynamic_rhs, f_tvdp, f_vdp)
@@ -1338,7 +1371,8 @@ def _imex_loop(scheme, trange, inivel, inip, bcs_ini, M, A, J, f_vdp, f_tdp,
                          M=M, A=A, J=J, scalep=scalep, dfv_c=dfv_c,
                          dynamic_rhs=dynamic_rhs, drm=drm, bcs_c=bcs_ini,
                          applybcs=applybcs, appndbcs=appndbcs, getbcs=getbcs,
-                         f_tdp=f_tdp, f_vdp=f_vdp, g_tdp=g_tdp)
+                         f_tdp=f_tdp, f_vdp=f_vdp, g_tdp=g_tdp,
+                         base_row=base_row)
     savevp(appndbcs(v_n, bcs_n), p_n, time=trange[1])
 
     # the constant system of the loop, factor-once in the reference (tiu:89-91)

@@ -864,8 +864,8 @@ int dns_conv_apply(dns_conv *cv, const double *v_inner, double scale,
  * the adjoint takes zero values and no table (then the sum is (L_II)^T w_I) and
  * refuses anything else.  A linearised operator is refused by
  * dns_conv_assemble*, dns_conv_project_tensor, the trapezoidal stepper, a
- * row-partitioned IMEX stepper and functionals with cells.  The base flow is
- * constant in time; the adjoint is the continuous one, stepped like any run */
+ * row-partitioned IMEX stepper and functionals with cells.  This base flow is
+ * constant in time (dns_conv_set_base_trajectory: one that is not); the adjoint is the continuous one, stepped like any run */
 #define DNS_CONV_NONLINEAR 0
 #define DNS_CONV_FORWARD 1
 #define DNS_CONV_ADJOINT 2
@@ -873,6 +873,46 @@ int dns_conv_set_base_flow(dns_conv *cv, const double *v_inner,
                            const double *dbcvals, int32_t adjoint);
 int dns_conv_clear_base_flow(dns_conv *cv);
 int dns_conv_get_mode(const dns_conv *cv, int32_t *mode);
+/* Linearised convection about a TIME-VARYING base flow: a trajectory of nrows
+ * base flows resident on the device -- the inner velocities (row r of v_rows,
+ * ld_host >= nv_inner doubles apart on the host; on the device ldv = nv_inner
+ * rounded up to 64 apart, the slot layout of the snapshot ensemble) and the
+ * base flow's Dirichlet values, dbc_nrows == 1: one set for every row, or
+ * dbc_nrows == nrows: row-major nrows x ndbc.  One upload; V is gathered
+ * through the cell map as the perturbation is.  Modes, the perturbation's own
+ * Dirichlet values and every refusal are those of dns_conv_set_base_flow.
+ * Which row an element launch evaluates about (zero-order hold, no
+ * interpolation):
+ *   dns_conv_set_base_rows  a per-step index table of n entries, each in
+ *                           0..nrows-1 (anything else is refused by name before
+ *                           anything is uploaded): the s-th step of the
+ *                           attached CNAB / SBDF2 stepper after the call (its
+ *                           step counter goes back to 0 as after any of its
+ *                           own table setters) evaluates about row
+ *                           rows[min(s, n - 1)].  Descending: an adjoint run
+ *                           backwards over a stored forward run; repeated
+ *                           entries: a trajectory stored every k-th step.
+ *                           Outside a stepper (dns_conv_apply) row rows[0]
+ *   dns_conv_set_base_row   one row the host names, for dns_conv_apply and for
+ *                           the steps alike; it takes the index table off
+ * Row 0 and no table until one of them is called.  dns_conv_set_base_flow and
+ * dns_conv_clear_base_flow release the trajectory; dns_conv_get_base_info:
+ * nrows (0: a constant base flow or none) and the length of the index table */
+int dns_conv_set_base_trajectory(dns_conv *cv, int32_t nrows,
+                                 const double *v_rows, int32_t ld_host,
+                                 int32_t dbc_nrows, const double *dbc_vals,
+                                 int32_t adjoint);
+int dns_conv_set_base_rows(dns_conv *cv, int32_t n, const int32_t *rows);
+int dns_conv_set_base_row(dns_conv *cv, int32_t row);
+int dns_conv_get_base_info(const dns_conv *cv, int32_t *nrows, int32_t *nbrow);
+/* ... adopted from the snapshot ensemble of a stepper (dns_imex_set_ensemble):
+ * slots first .. first + count - 1 become rows 0 .. count - 1, copied device to
+ * device on the stepper's stream; only dbc_vals (as above, dbc_nrows 1 or
+ * count) cross the bus.  Refused by name: no ensemble, slots out of range, the
+ * operator on another device, another number of inner dofs */
+int dns_imex_ensemble_to_base(dns_imex *st, int32_t first, int32_t count,
+                              dns_conv *cv, int32_t dbc_nrows,
+                              const double *dbc_vals, int32_t adjoint);
 /* TEST ONLY: the cell values [12][ncells] (the operator's internal cell order)
  * the element launch leaves for v_inner in the current mode; nsel >= 0: only
  * the internal cells sel[0..nsel) are evaluated, every other entry is `fill`.
