@@ -685,25 +685,118 @@ int dns_saddle::update_values_dist() {
     return DNS_OK;
 }
 
+// the plan of a row-partitioned cycle: this rank's row blocks, and every
+// reduction read as ONE all-reduced sum from `dsum`
+// (lazy: "norms" 1 and 0 -- the head copies r, scales nothing, stops never)
+CyclePlan dns_saddle::plan_cycle_dist(const dns_solve_opts *o, int first,
+                                      const dns::StepHooks &hk,
+                                      bool lazy) const {
+    using namespace dns;
+    const dns_dist_data *D = dd;
+    CyclePlan P;
+    P.v0 = D->v0, P.v1 = D->v1, P.p0 = D->p0, P.p1 = D->p1;
+    P.q1 = np;
+    P.map_on = 1;
+    P.kmap = D->kmap;
+    P.schur = schur_block();
+    if (D->schur_cols) {
+        // dense Schur inverse by columns: every rank forms its share of all NP
+        // rows from its own entries of tau; the shares are all-reduced behind
+        if (P.schur.kind == 1 || P.schur.kind == 2)
+            P.schur.stride = D->schur_ld;
+        P.schur.col0 = P.p0;
+        P.schur.ncols = P.p1 - P.p0;
+        P.schur.add_corr = comm->rank == 0 ? 1 : 0;
+    }
+    P.dense = popts.schur == DNS_SCHUR_DENSE;
+    P.mgs = popts.schur == DNS_SCHUR_MG;
+    // fused Gram-Schmidt (norm by Pythagoras: ONE all-reduce per step) unless
+    // the caller asks for the explicit form or a cycle of this solve has
+    // tripped the cancellation guard; the explicit form orthogonalises the
+    // own rows and takes the norm with a second all-reduce
+    P.fusedgs = o->reorth == 2;
+    // bandwidth regime: the row blocks go through the streaming kernels too
+    // (local CSR rows -> global rows through the RowMap of the epilogue)
+    P.stream_k = P.stream_dots = streams(K);
+    P.multidot_ww = 1;
+    P.first = first;
+    P.stepctr = first == 1 ? hk.stepctr : nullptr;
+    P.rtol = o->rtol;
+    P.atol = o->atol;
+    P.maxiter = o->maxiter;
+    P.gridA = head_grid();
+    const int nloc = (P.v1 - P.v0) + (P.p1 - P.p0);
+    P.gridKc = P.gridR =
+        std::max(1, std::min(grid_for_rows(nloc, K.lpr), 2048));
+    P.gridK = P.stream_k ? (Kp.ready ? pair_grid(Kp, sgrid)
+                                     : stream_grid(K, sgrid))
+                         : P.gridKc;
+    P.rr_part = lazy ? lazy_one.p : dsum.p;
+    P.bb_part = P.rr_part + 1;
+    P.rr_np = P.bb_np = 1;
+    P.hpart = dsum.p + 2;
+    P.hsummed = true;
+    P.npart = dsum.p + kMaxRestart + 4;
+    P.nnp = 1;
+    P.w = w.p;
+    P.ld = ld;
+    return P;
+}
+
+// zv (own rows) = Gc_loc [V_j,v ; zp]
+int dns_saddle::node_fhat_dist(const CyclePlan &P, int j) {
+    using namespace dns;
+    const double *vj = V.p + (size_t)j * ld;
+    double *zj = Z.p + (size_t)j * ld, *zp = zj + nv;
+    if (P.stream_k && streams(Gc)) {
+        StreamEpi ep = stream_epi_plain(1.0, 0.0, nullptr);
+        ep.x2 = zp;
+        ep.nsplit = nv;
+        ep.map_on = 1;
+        ep.rm = RowMap{P.v0, P.v1 - P.v0, 0, 0};
+        if (fp32_store)
+            return launch_stream16x<float>(Gc, gc32.p, vj, zj, ep, stream,
+                                           done_ptr());
+        return launch_stream16x<double>(Gc, Gc.vals.p, vj, zj, ep, stream,
+                                        done_ptr());
+    }
+    const int *g_rp = Gc.rowptr.p - P.v0;    // row pointers by GLOBAL row
+    const int g = grid_for_rows(P.v1 - P.v0, Gc.lpr);
+    if (fp32_store) {
+        DNS_LPR_SWITCH(
+            Gc.lpr,
+            hipLaunchKernelGGL((k_spmv_split<L, float>), g, kBlock, 0, stream,
+                               nv, g_rp, Gc.colidx.p, gc32.p, vj, (size_t)0,
+                               zero_ptr(), zp, zj, done_ptr(),
+                               (double *)nullptr, P.v0, P.v1));
+    } else {
+        DNS_LPR_SWITCH(
+            Gc.lpr,
+            hipLaunchKernelGGL((k_spmv_split<L, double>), g, kBlock, 0, stream,
+                               nv, g_rp, Gc.colidx.p, Gc.vals.p, vj, (size_t)0,
+                               zero_ptr(), zp, zj, done_ptr(),
+                               (double *)nullptr, P.v0, P.v1));
+    }
+    return DNS_OK;
+}
+
+// One restart cycle of the row-partitioned solve: the nodes of enqueue_cycle
+// on this rank's rows, with the halo exchanges, the gathers and the all-reduced
+// scalar sums between them
 int dns_saddle::enqueue_cycle_dist(const double *b, double *x, int c,
                                    const dns_solve_opts *o, int first,
                                    bool have_resid, const dns::StepHooks &hk) {
     using namespace dns;
     dns_dist_data *D = dd;
-    // fused Gram-Schmidt (norm by Pythagoras: ONE all-reduce per step) unless
-    // the caller asks for the explicit form or a cycle of this solve has
-    // tripped the cancellation guard; the explicit form orthogonalises the
-    // own rows and takes the norm with a second all-reduce
-    const bool fused = o->reorth == 2;
-    double *dnorm = dsum.p + kMaxRestart + 4;
-    const int v0 = D->v0, v1 = D->v1, p0 = D->p0, p1 = D->p1;
-    const int nloc = (v1 - v0) + (p1 - p0);
-    const int gK = std::max(1, std::min(grid_for_rows(nloc, K.lpr), 2048));
-    const bool dense = popts.schur == DNS_SCHUR_DENSE;
-    const bool mgs = popts.schur == DNS_SCHUR_MG;
-    const int gridA =
-        dense ? std::max(gridD, std::min((np + 3) / 4, 2048)) : gridD;
-    double *rrbb = dsum.p, *hsum = dsum.p + 2;
+    // one-step cycle (what a pipelined time step predicts once the warm start
+    // is good): the first vector stays un-normalised and the norms of r and b
+    // travel with the step's dots -- ONE all-reduce of scalars per time step
+    // instead of two (k_arn_tail_lazy1)
+    const bool lazy = dist_lazy1 && o->reorth == 2 && c == 1 && first == 1 &&
+                      o->atol < 1.0 && o->maxiter > 0;
+    const CyclePlan P = plan_cycle_dist(o, first, hk, lazy);
+    const bool fused = P.fusedgs, scols = D->schur_cols;
+    double *const hsum = P.hpart, *const dnorm = P.npart;
     // x is valid on the own entries AND on the halo the rows of K_loc
     // reference when a cycle starts: a caller's start vector is whole (solve,
     // trapezoidal stepper) or a combination of earlier solutions that are
@@ -715,67 +808,19 @@ int dns_saddle::enqueue_cycle_dist(const double *b, double *x, int c,
     // has a wider one (IMEX stepper: rows of R1 and convection cells as well),
     // so that the new iterate needs no exchange of its own behind the solve
     const dns_halo_plan *zplan = hk.z_plan ? hk.z_plan : &D->planK;
-    // bandwidth regime: the row blocks go through the streaming kernels too
-    // (local CSR rows -> global rows through the RowMap of the epilogue)
-    const bool big = streams(K);
     // (have_resid: the caller's prologue kernel has left r = b - K x and the
     // partials of both norms -- resid_nparts of them -- behind)
     const bool pre_r = have_resid && hk.resid_nparts > 0;
-    const int gS = big ? (Kp.ready ? pair_grid(Kp, sgrid)
-                                   : stream_grid(K, sgrid))
-                       : gK;
-    const int gR = pre_r ? hk.resid_nparts : gS;    // partials of ||r||, ||b||
-    if (pre_r) {
-    } else if (big) {
-        StreamEpi ep = stream_epi_plain(-1.0, 1.0, b);
-        ep.part = partR.p;
-        ep.nvec = 0;
-        ep.with_ww = 1;
-        ep.nparts = gS;
-        ep.part_bb = partB.p;
-        ep.map_on = 1;
-        ep.rm = D->kmap;
-        if (Kp.ready)
-            DNS_TRY(launch_pair16x(Kp, x, r.p, ep, stream, nullptr,
-                                   sgrid));
-        else
-            DNS_TRY(launch_stream16x<double>(K, K.vals.p, x, r.p, ep, stream,
-                                             nullptr, sgrid));
-    } else {
-        DNS_LPR_SWITCH(K.lpr,
-                       hipLaunchKernelGGL(k_resid_norm<L>, gK, kBlock, 0, stream,
-                                          n, K.rowptr.p, K.colidx.p, K.vals.p,
-                                          x, b, r.p, partR.p, partB.p,
-                                          D->kmap));
-    }
-    // one-step cycle (what a pipelined time step predicts once the warm start
-    // is good): the first vector stays un-normalised and the norms of r and b
-    // travel with the step's dots -- ONE all-reduce of scalars per time step
-    // instead of two (k_arn_tail_lazy1)
-    const bool lazy = dist_lazy1 && fused && c == 1 && first == 1 &&
-                      o->atol < 1.0 && o->maxiter > 0;
+    const int gR = pre_r ? hk.resid_nparts : P.gridK;   // partials of ||r||, ||b||
+    if (!pre_r) DNS_TRY(node_residual(P, b, x));
     if (lazy) {
-        if (!lazy_one.p) {
+        if (!lazy_one.p)
             return fail(DNS_ERR_NOT_READY, "lazy cycle without its constants");
-        }
     } else {
         hipLaunchKernelGGL(k_sum_partials2, 2, kBlock, 0, stream, partR.p,
-                           partB.p, gR, rrbb);
-        DNS_TRY(comm->allreduce(rrbb, 2, stream));
+                           partB.p, gR, P.rr_part);
+        DNS_TRY(comm->allreduce(P.rr_part, 2, stream));
     }
-    // (lazy: "norms" 1 and 0 -- the head copies r, scales nothing, stops never)
-    const double *rr_in = lazy ? lazy_one.p : rrbb;
-    const double *bb_in = lazy ? lazy_one.p + 1 : rrbb + 1;
-    // dense Schur inverse by columns: every rank forms its share of all NP
-    // rows from its own entries of tau; the shares are all-reduced behind
-    const bool scols = D->schur_cols;
-    const int sc0 = scols ? p0 : 0, scn = scols ? p1 - p0 : -1;
-    const int sstride = scols ? D->schur_ld : (fp32_store ? sld : 0);
-    const int q0 = 0, q1 = np;
-    const float *s32 = sinv32.p;
-    const double *s64 = sinv.p;
-    const int *g_rp = Gc.rowptr.p - v0;      // row pointers by GLOBAL row
-    const int *jg_rp = have_jg ? JG.rowptr.p - p0 : nullptr;
     for (int j = 0; j < c; ++j) {
         double *zj = Z.p + (size_t)j * ld;
         double *zp = zj + nv;
@@ -783,15 +828,9 @@ int dns_saddle::enqueue_cycle_dist(const double *b, double *x, int c,
         // velocity halo of the new (un-normalised) basis vector
         DNS_TRY(D->planU.exchange(comm, src, stream));
         const double *tin = nullptr;
-        if (have_jg && !mgs) {
-            DNS_LPR_SWITCH(
-                JG.lpr,
-                hipLaunchKernelGGL(
-                    k_tau_guard<L>,
-                    grid_for_rows(p1 - p0, JG.lpr == 64 ? 128 : JG.lpr), kBlock,
-                    0, stream, np, nv, jg_rp, JG.colidx.p, JG.vals.p, src,
-                    tau.p, hsum, 1, fused ? j : (j > 0 ? -1 : 0), ctl.p, p0,
-                    p1));
+        if (have_jg && !P.mgs) {
+            DNS_TRY(node_tau(src, hsum, 1, fused ? j : (j > 0 ? -1 : 0), P.p0,
+                             P.p1));
             // (column form of the dense inverse: own entries of tau suffice)
             if (!scols) DNS_TRY(comm->allgatherv(tau.p, st_p, stream));
             tin = tau.p;
@@ -799,162 +838,33 @@ int dns_saddle::enqueue_cycle_dist(const double *b, double *x, int c,
             // the Schur block reads the pressure part itself
             DNS_TRY(comm->allgatherv(src + nv, st_p, stream));
         }
-#define DNS_DIST_HEAD(SK, SINV)                                               \
-    do {                                                                      \
-        if (j == 0)                                                           \
-            hipLaunchKernelGGL(k_arn_head<SK>, gridA, kBlock, 0, stream, n,  \
-                               nv, np, 0, src, rr_in, 1, V.p, ld,             \
-                               (const void *)(SINV), zp, ctl.p, o->rtol,      \
-                               o->atol, bb_in, 1, o->maxiter, q0, q1,         \
-                               first, mgs ? nullptr : tin,                    \
-                               first == 1 ? hk.stepctr : nullptr,        \
-                               ((SK) == 2 || (SK) == 1) ? sstride : 0, sc0,   \
-                               scn);                                          \
-        else if (!fused)                                                      \
-            hipLaunchKernelGGL(k_arn_head<SK>, gridA, kBlock, 0, stream, n,  \
-                               nv, np, j, src, dnorm, 1, V.p, ld,             \
-                               (const void *)(SINV), zp, ctl.p, o->rtol,      \
-                               o->atol, rrbb + 1, 1, o->maxiter, q0, q1, 0,   \
-                               mgs ? nullptr : tin, (int *)nullptr,           \
-                               ((SK) == 2 || (SK) == 1) ? sstride : 0, sc0,   \
-                               scn);                                          \
-        else                                                                  \
-            hipLaunchKernelGGL(k_arn_head_f<SK>, gridA, kBlock, 0, stream,   \
-                               n, nv, np, j, w.p, hsum, 1, V.p, ld, Z.p,      \
-                               (const void *)(SINV), ctl.p, o->maxiter,       \
-                               mgs ? nullptr : tin, q0, q1,                   \
-                               ((SK) == 2 || (SK) == 1) ? sstride : 0, sc0,   \
-                               scn, (!scols || comm->rank == 0) ? 1 : 0);      \
-    } while (0)
-        if (mgs)
-            DNS_DIST_HEAD(3, nullptr);
-        else if (dense && fp32_store)
-            DNS_DIST_HEAD(2, s32);
-        else if (dense)
-            DNS_DIST_HEAD(1, s64);
-        else
-            DNS_DIST_HEAD(0, sinv.p);
-#undef DNS_DIST_HEAD
+        DNS_TRY(node_head(P, j, src, zp, tin));
         if (scols) DNS_TRY(comm->allreduce(zp, np, stream));
-        if (mgs) {
-            // replicated V-cycle on tau(V_j) / V_j,p
-            const double *sin = V.p + (size_t)j * ld + nv;
-            if (have_jg && streams(JG)) {
-                // tau of the NORMALISED vector, own rows, at the streaming rate
-                const double *vj = V.p + (size_t)j * ld;
-                StreamEpi ep = stream_epi_plain(-1.0, 1.0, vj + nv);
-                ep.map_on = 1;
-                ep.rm = RowMap{p0, p1 - p0, 0, 0};
-                if (JG.vals32.p)
-                    DNS_TRY(launch_stream16x<float>(JG, JG.vals32.p, vj, tau.p,
-                                                    ep, stream, done_ptr()));
-                else
-                    DNS_TRY(launch_stream16x<double>(JG, JG.vals.p, vj, tau.p,
-                                                     ep, stream, done_ptr()));
-                if (mg_nparts == 0)
-                    DNS_TRY(comm->allgatherv(tau.p, st_p, stream));
-                sin = tau.p;
-            } else if (have_jg) {
-                // tau of the NORMALISED vector: own rows, gathered
-                DNS_LPR_SWITCH(
-                    JG.lpr,
-                    hipLaunchKernelGGL(
-                        k_tau_guard<L>,
-                        grid_for_rows(p1 - p0, JG.lpr == 64 ? 128 : JG.lpr),
-                        kBlock, 0, stream, np, nv, jg_rp, JG.colidx.p,
-                        JG.vals.p, V.p + (size_t)j * ld, tau.p,
-                        (const double *)nullptr, 0, -1, ctl.p, p0, p1));
-                // (a partitioned cycle starts from the own rows of tau)
-                if (mg_nparts == 0)
-                    DNS_TRY(comm->allgatherv(tau.p, st_p, stream));
-                sin = tau.p;
-            }
-            if (mg_nparts > 0)
-                DNS_TRY(schur_mg_apply_dist(sin, zp, done_ptr()));
-            else
-                DNS_TRY(schur_mg_apply(sin, zp, nullptr, done_ptr()));
-        }
-        // zv (own rows) = Gc_loc [V_j,v ; zp]
-        if (big && streams(Gc)) {
-            StreamEpi ep = stream_epi_plain(1.0, 0.0, nullptr);
-            ep.x2 = zp;
-            ep.nsplit = nv;
-            ep.map_on = 1;
-            ep.rm = RowMap{v0, v1 - v0, 0, 0};
-            if (fp32_store)
-                DNS_TRY(launch_stream16x<float>(Gc, gc32.p,
-                                                V.p + (size_t)j * ld, zj, ep,
-                                                stream, done_ptr()));
-            else
-                DNS_TRY(launch_stream16x<double>(Gc, Gc.vals.p,
-                                                 V.p + (size_t)j * ld, zj, ep,
-                                                 stream, done_ptr()));
-        } else {
-            const int g = grid_for_rows(v1 - v0, Gc.lpr);
-            if (fp32_store) {
-                DNS_LPR_SWITCH(
-                    Gc.lpr,
-                    hipLaunchKernelGGL((k_spmv_split<L, float>), g, kBlock, 0,
-                                       stream, nv, g_rp, Gc.colidx.p, gc32.p,
-                                       V.p + (size_t)j * ld, (size_t)0,
-                                       zero_ptr(), zp, zj, done_ptr(),
-                                       (double *)nullptr, v0, v1));
-            } else {
-                DNS_LPR_SWITCH(
-                    Gc.lpr,
-                    hipLaunchKernelGGL((k_spmv_split<L, double>), g, kBlock, 0,
-                                       stream, nv, g_rp, Gc.colidx.p, Gc.vals.p,
-                                       V.p + (size_t)j * ld, (size_t)0,
-                                       zero_ptr(), zp, zj, done_ptr(),
-                                       (double *)nullptr, v0, v1));
-            }
-        }
+        // (replicated or partitioned V-cycle on tau(V_j) / V_j,p)
+        if (P.mgs) DNS_TRY(node_schur_mg(P, j));
+        DNS_TRY(node_fhat_dist(P, j));
         DNS_TRY(const_cast<dns_halo_plan *>(zplan)->exchange(comm, zj, stream));
         // w (own rows) = K_loc z and the step's dots over the own rows
-        const bool kdots = big && j + 1 <= kStreamDots;
-        if (kdots) {
-            StreamEpi ep = stream_epi_plain(1.0, 0.0, nullptr);
-            ep.V = V.p;
-            ep.ld = ld;
-            ep.nvec = j + 1;
-            ep.with_ww = 1;
-            ep.part = partA.p;
-            ep.nparts = gS;
-            ep.map_on = 1;
-            ep.rm = D->kmap;
-            if (Kp.ready)
-                DNS_TRY(launch_pair16x(Kp, zj, w.p, ep, stream, done_ptr(),
-                                       sgrid));
-            else
-                DNS_TRY(launch_stream16x<double>(K, K.vals.p, zj, w.p, ep,
-                                                 stream, done_ptr(),
-                                                 sgrid));
-        } else {
-            DNS_LPR_SWITCH(
-                K.lpr,
-                hipLaunchKernelGGL(k_spmv_multidot<L>, gK, kBlock, 0, stream, n,
-                                   K.rowptr.p, K.colidx.p, K.vals.p, zj, w.p,
-                                   V.p, ld, j, partA.p, gK, ctl.p, D->kmap, 1));
-        }
+        DNS_TRY(node_k_apply(P, j, zj));
         if (lazy) {
             hipLaunchKernelGGL(k_sum_lazy4, 1, kBlock, 0, stream, partA.p,
-                               kdots ? gS : gK, partR.p, partB.p, gR, hsum);
+                               P.kparts(j), partR.p, partB.p, gR, hsum);
             DNS_TRY(comm->allreduce(hsum, 4, stream));
-            continue;
+        } else {
+            hipLaunchKernelGGL(k_sum_partials_n, 1, kBlock, 0, stream, partA.p,
+                               P.kparts(j), j + 2, hsum);
+            DNS_TRY(comm->allreduce(hsum, fused ? j + 2 : j + 1, stream));
         }
-        hipLaunchKernelGGL(k_sum_partials_n, 1, kBlock, 0, stream, partA.p,
-                           kdots ? gS : gK, j + 2, hsum);
-        if (fused) {
-            DNS_TRY(comm->allreduce(hsum, j + 2, stream));
-            continue;
+        if (!fused) {
+            // explicit Gram-Schmidt on the own rows, norm by a second
+            // all-reduce
+            hipLaunchKernelGGL(k_orth<0>, gridD, kBlock, 0, stream, n, V.p, ld,
+                               w.p, hsum, 1, j, 0, partN.p, gridD, ctl.p,
+                               D->kmap);
+            hipLaunchKernelGGL(k_sum_partials, 1, kBlock, 0, stream, partN.p,
+                               gridD, dnorm);
+            DNS_TRY(comm->allreduce(dnorm, 1, stream));
         }
-        DNS_TRY(comm->allreduce(hsum, j + 1, stream));
-        // explicit Gram-Schmidt on the own rows, norm by a second all-reduce
-        hipLaunchKernelGGL(k_orth<0>, gridD, kBlock, 0, stream, n, V.p, ld, w.p,
-                           hsum, 1, j, 0, partN.p, gridD, ctl.p, D->kmap);
-        hipLaunchKernelGGL(k_sum_partials, 1, kBlock, 0, stream, partN.p,
-                           gridD, dnorm);
-        DNS_TRY(comm->allreduce(dnorm, 1, stream));
     }
     if (lazy) {
         const bool cells = hk.dist_tail.on && hk.dist_tail.cells.nblocks > 0;
@@ -966,15 +876,8 @@ int dns_saddle::enqueue_cycle_dist(const double *b, double *x, int c,
                            cells ? hk.dist_tail.x0copy : (const double *)nullptr,
                            cells ? hk.dist_tail.cells : TailCells{});
         if (cells) hk.dist_tail_ran = true;
-    } else if (fused) {
-        hipLaunchKernelGGL(k_arn_tail_acc, gridD, kBlock, 0, stream, c, n, hsum,
-                           1, ctl.p, histdev.p, (int)hist_cap, o->maxiter, Z.p,
-                           ld, x, hk.tail_extrap);
     } else {
-        hipLaunchKernelGGL(k_arn_tail, 1, kBlock, 0, stream, c, dnorm, 1, ctl.p,
-                           histdev.p, (int)hist_cap, o->maxiter, 0);
-        hipLaunchKernelGGL(k_basis_combine_acc, gridD, kBlock, 0, stream, n,
-                           Z.p, ld, ctl.p, x, hk.tail_extrap);
+        DNS_TRY(node_tail(P, c, x, hk));
     }
     // (residual carry-over: only the one-step cycle knows the true residual
     // behind it; a solve that ends with a general cycle carries none)

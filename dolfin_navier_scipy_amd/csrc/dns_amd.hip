@@ -502,13 +502,7 @@ int dns_saddle::apply_precond(const double *rvec, double *zout,
     if (have_jg) {
         // full block factorisation: tau = r_p - (J Fh^-1) r_v is what the
         // Schur block sees; its kernels read `rbase + nv`
-        DNS_LPR_SWITCH(
-            JG.lpr,
-            hipLaunchKernelGGL(k_tau_guard<L>,
-                               grid_for_rows(r1 - r0, JG.lpr == 64 ? 128 : JG.lpr),
-                               kBlock, 0, stream, np, nv, JG.rowptr.p,
-                               JG.colidx.p, JG.vals.p, rvec, tau.p,
-                               (const double *)nullptr, 0, 0, ctl.p, r0, r1));
+        DNS_TRY(node_tau(rvec, nullptr, 0, 0, r0, r1));
         rvec_schur = tau.p - nv;
     }
     if (popts.schur == DNS_SCHUR_MG) {
@@ -1396,10 +1390,7 @@ int dns_saddle::true_residual(const double *b, const double *x, double *out) {
     // (row-partitioned: this rank's rows, then the sum over the ranks; `x` is
     // whole on every rank after a solve)
     const RowMap rm = dist_sliced ? dist_rowmap() : RowMap{0, n, 0, 0};
-    DNS_LPR_SWITCH(K.lpr,
-                   hipLaunchKernelGGL(k_resid_norm<L>, gridS, kBlock, 0, stream,
-                                      n, K.rowptr.p, K.colidx.p, K.vals.p, x,
-                                      b, r.p, partR.p, (double *)nullptr, rm));
+    DNS_TRY(resid_norm_csr(gridS, x, b, nullptr, rm));
     hipLaunchKernelGGL(k_sum_partials, 1, kBlock, 0, stream, partR.p, gridS,
                        scal.p);
     DNS_HIP(hipGetLastError());
@@ -1549,338 +1540,107 @@ uint64_t dns::StepHooks::key(bool first) const {
     return k;
 }
 
+#include "cycle_nodes.inc"
+
+// Lazy one-column cycle of the six-node step (the time step's usual one): the
+// same six nodes and data flow, but the head is the dense Schur product alone,
+// Gc and K read r where the tau kernel left it, and the tail forms the step
+// from the four sums -- nothing is normalised, no guard is read
+int dns_saddle::enqueue_cycle_lazy6(const CyclePlan &P, const double *b,
+                                    const dns::StepHooks &hk) {
+    const StepHooks::Step6 &step6 = hk.step6;
+    DNS_TRY(node_tau_first(b, step6.kx));
+    double *zp = Z.p + nv;
+    if (fp32_store)
+        hipLaunchKernelGGL(k_arn_head_lazy<2>, P.gridA, kBlock, 0, stream, np,
+                           (const void *)sinv32.p, tau.p, zp, sld, P.stepctr);
+    else
+        hipLaunchKernelGGL(k_arn_head_lazy<1>, P.gridA, kBlock, 0, stream, np,
+                           (const void *)sinv.p, tau.p, zp, 0, P.stepctr);
+    if (fhat_explicit && !streams(Gc) && !dist()) {
+        // (the rows of k_spmv_split in three load levels: no guard, no
+        // column selector, same bits)
+        const int g = grid_for_rows(nv, Gc.lpr);
+        if (fp32_store) {
+            DNS_LPR_SWITCH(
+                Gc.lpr,
+                hipLaunchKernelGGL((k_spmv_gc_lazy<L, float>), g, kBlock, 0,
+                                   stream, nv, Gc.rowptr.p, Gc.colidx.p,
+                                   gc32.p, r.p, zp, Z.p));
+        } else {
+            DNS_LPR_SWITCH(
+                Gc.lpr,
+                hipLaunchKernelGGL((k_spmv_gc_lazy<L, double>), g, kBlock, 0,
+                                   stream, nv, Gc.rowptr.p, Gc.colidx.p,
+                                   Gc.vals.p, r.p, zp, Z.p));
+        }
+    } else {
+        DNS_TRY(apply_fhat_part(r.p, zp, Z.p, zero_ptr(), nullptr));
+    }
+    // K z with <r, w>, <w, w> folded to at most kBlock partials of each
+    // (kLazyRows consecutive rows per sub-wave and pass)
+    const int rows_wg = kLazyRows * (kLazyBlock / K.lpr);
+    const int gridL = std::max(1, std::min((n + rows_wg - 1) / rows_wg, kBlock));
+    DNS_LPR_SWITCH(
+        K.lpr,
+        hipLaunchKernelGGL((k_spmv_rw<L, kLazyRows, kLazyBlock>), gridL,
+                           kLazyBlock, 0, stream, n, K.rowptr.p, K.colidx.p,
+                           K.vals.p, Z.p, Wcols.p, r.p, partA.p));
+    hipLaunchKernelGGL(k_arn_tail6<true>, gridD + step6.cells.nblocks, kBlock,
+                       0, stream, 1, n, gridD, partA.p, gridL, ctl.p,
+                       histdev.p, (int)hist_cap, P.maxiter, Z.p, ld, P.t6,
+                       hk.tail_extrap, step6.cells,
+                       TailLazy{partR.p, partB.p, gridD, P.rtol, P.atol});
+    DNS_HIP(hipGetLastError());
+    return DNS_OK;
+}
+
 // One restart cycle of right-preconditioned GMRES with `c` Arnoldi steps:
-// residual, start, c x (precondition, K apply, Gram-Schmidt, close), then the
-// correction x += P^-1 (V y).  Kernels after convergence return at once
-// (ctl->done), so `c` may overshoot.  Nothing here synchronises or allocates.
+// residual, then per column tau, head (start / close + Schur block), Fh^-1,
+// K apply, Gram-Schmidt, then the tail with the correction x += P^-1 (V y).
+// Kernels after convergence return at once (ctl->done), so `c` may overshoot.
+// (one GPU; the row-partitioned solve has its own: enqueue_cycle_dist)
 int dns_saddle::enqueue_cycle(const double *b, double *x, int c,
                               const dns_solve_opts *o, int first,
                               bool have_resid, const dns::StepHooks &hk) {
     // (cycles per application of the multigrid block in THIS Krylov cycle:
     // part of what a captured graph of length c holds)
     mg_two_now = mg_two_for(c);
-    // `first`: 1 = the head kernel of this cycle resets the solve's counters,
-    // 2 = only its status (going on after a Gram-Schmidt fallback)
-    // (one GPU; the row-partitioned solve has its own: enqueue_cycle_dist)
-    // r = b - K x, ||r||^2, ||b||^2 (unless the caller's prologue kernel has
-    // produced r and the partials already)
-    int resid_np = gridS;
-    if (!have_resid && streams(K)) {
-        // bandwidth regime: r = b - K x at the streaming rate with the
-        // partials of both norms from the same launch
-        StreamEpi ep = stream_epi_plain(-1.0, 1.0, b);
-        ep.part = partR.p;
-        ep.nvec = 0;
-        ep.with_ww = 1;
-        resid_np = Kp.ready ? pair_grid(Kp, sgrid)
-                            : stream_grid(K, sgrid);
-        ep.nparts = resid_np;
-        ep.part_bb = partB.p;
-        if (Kp.ready)
-            DNS_TRY(launch_pair16x(Kp, x, r.p, ep, stream, nullptr,
-                                   sgrid));
-        else
-            DNS_TRY(launch_stream16x<double>(K, K.vals.p, x, r.p, ep, stream,
-                                             nullptr, sgrid));
-    } else if (!have_resid) {
-        DNS_LPR_SWITCH(
-            K.lpr, hipLaunchKernelGGL(k_resid_norm<L>, gridS, kBlock, 0, stream,
-                                      n, K.rowptr.p, K.colidx.p, K.vals.p, x, b,
-                                      r.p, partR.p, partB.p,
-                                      RowMap{0, n, 0, 0}));
-    }
-    // the consumers of a reduction read the per-workgroup partials
-    const double *rr_part = partR.p, *bb_part = partB.p;
-    const int rr_np = (have_resid && hk.resid_nparts > 0)
-                          ? hk.resid_nparts : resid_np;
-    const bool dense = popts.schur == DNS_SCHUR_DENSE;
-    const int q0 = 0, q1 = np;
-    // (dense Schur rows: one wave each, four per workgroup)
-    const int gridA =
-        dense ? std::max(gridD, std::min((q1 - q0 + 3) / 4, 2048)) : gridD;
-    // reorth == 2: Gram-Schmidt folded into the next head kernel
-    // bandwidth regime: K through the streaming kernel with the dots fused in
-    // (while they fit its accumulators)
-    const bool stream_k = streams(K);
-    const bool fusedgs = o->reorth == 2 && (fuse_dots || stream_k);
-    const int gridK = stream_k ? (Kp.ready ? pair_grid(Kp, sgrid)
-                                           : stream_grid(K, sgrid))
-                               : gridC;
-    // partials the consumers of step j's dots read: written by the kernel
-    // that applied K in step j
-    auto kparts = [&](int jj) {
-        return (stream_k && jj + 1 <= kStreamDots) ? gridK : gridC;
-    };
-    // six-node step: K z_j is kept per column (the tail forms the new
-    // residual r0 - sum y_j K z_j from them)
+    const CyclePlan P = plan_cycle(c, o, first, have_resid, hk);
     const StepHooks::Step6 &step6 = hk.step6;
-    // (the first head kernel of a solve bumps the stepper's step counter)
-    int *const ctr0 = first == 1 ? hk.stepctr : nullptr;
-    const bool s6 = step6.on && fusedgs && !stream_k && have_resid &&
-                    Wcols.n >= (size_t)c * ld;
-    Tail6 t6 = step6.t6;
-    t6.r0 = r.p;
-    t6.W = Wcols.p;
-    t6.nv = nv;
-    auto wcol = [&](int jj) -> double * {
-        return s6 ? Wcols.p + (size_t)jj * ld : w.p;
-    };
-    // six-node step: r = b - kx with its norms and tau(r) in ONE launch
-    auto tau_first = [&]() {
-        const int gt = std::max(1, std::min((np + 1) / 2, 4096));
-        hipLaunchKernelGGL(k_tau_first, gt + gridD, kBlock, 0, stream, gt, n,
-                           np, nv, JG.rowptr.p, JG.colidx.p, JG.vals.p, b,
-                           step6.kx, tau.p, r.p, partR.p, partB.p);
-    };
-    if (s6 && step6_lazy_for(c) && first == 1 && dense && step6.kx &&
-        have_jg) {
-        // lazy one-column cycle (the time step's usual one): the same six
-        // nodes and data flow, but the head is the dense Schur product alone,
-        // Gc and K read r where the tau kernel left it, and the tail forms the
-        // step from the four sums -- nothing is normalised, no guard is read
-        tau_first();
-        double *zp = Z.p + nv;
-        if (fp32_store)
-            hipLaunchKernelGGL(k_arn_head_lazy<2>, gridA, kBlock, 0, stream, np,
-                               (const void *)sinv32.p, tau.p, zp, sld, ctr0);
-        else
-            hipLaunchKernelGGL(k_arn_head_lazy<1>, gridA, kBlock, 0, stream, np,
-                               (const void *)sinv.p, tau.p, zp, 0, ctr0);
-        if (fhat_explicit && !streams(Gc) && !dist()) {
-            // (the rows of k_spmv_split in three load levels: no guard, no
-            // column selector, same bits)
-            const int g = grid_for_rows(nv, Gc.lpr);
-            if (fp32_store) {
-                DNS_LPR_SWITCH(
-                    Gc.lpr,
-                    hipLaunchKernelGGL((k_spmv_gc_lazy<L, float>), g, kBlock, 0,
-                                       stream, nv, Gc.rowptr.p, Gc.colidx.p,
-                                       gc32.p, r.p, zp, Z.p));
-            } else {
-                DNS_LPR_SWITCH(
-                    Gc.lpr,
-                    hipLaunchKernelGGL((k_spmv_gc_lazy<L, double>), g, kBlock,
-                                       0, stream, nv, Gc.rowptr.p, Gc.colidx.p,
-                                       Gc.vals.p, r.p, zp, Z.p));
-            }
-        } else {
-            DNS_TRY(apply_fhat_part(r.p, zp, Z.p, zero_ptr(), nullptr));
-        }
-        // K z with <r, w>, <w, w> folded to at most kBlock partials of each
-        // (kLazyRows consecutive rows per sub-wave and pass)
-        const int rows_wg = kLazyRows * (kLazyBlock / K.lpr);
-        const int gridL = std::max(1, std::min((n + rows_wg - 1) / rows_wg,
-                                               kBlock));
-        DNS_LPR_SWITCH(
-            K.lpr,
-            hipLaunchKernelGGL((k_spmv_rw<L, kLazyRows, kLazyBlock>), gridL,
-                               kLazyBlock, 0, stream, n, K.rowptr.p,
-                               K.colidx.p, K.vals.p, Z.p, Wcols.p, r.p,
-                               partA.p));
-        hipLaunchKernelGGL(k_arn_tail6<true>, gridD + step6.cells.nblocks,
-                           kBlock, 0, stream, 1, n, gridD, partA.p, gridL,
-                           ctl.p, histdev.p, (int)hist_cap, o->maxiter, Z.p,
-                           ld, t6, hk.tail_extrap, step6.cells,
-                           TailLazy{partR.p, partB.p, gridD, o->rtol,
-                                    o->atol});
-        DNS_HIP(hipGetLastError());
-        return DNS_OK;
-    }
+    if (P.s6 && step6_lazy_for(c) && first == 1 && P.dense && step6.kx &&
+        have_jg)
+        return enqueue_cycle_lazy6(P, b, hk);
+    if (!have_resid) DNS_TRY(node_residual(P, b, x));
     for (int j = 0; j < c; ++j) {
         // the preconditioned vectors are kept (Z_j) for the correction behind
         // the cycle
         double *zj = Z.p + (size_t)j * ld;
         double *zp = zj + nv;
-        const double *src = (j == 0) ? r.p : wcol(j - 1);
-        const double *spart = (j == 0) ? rr_part : partN.p;
-        const int snp = (j == 0) ? rr_np : gridD;
-        // full block factorisation: tau = src_p - (J Fh^-1) src_v feeds the
-        // Schur block instead of src_p (unguarded: 3 us when already done)
+        const double *src = (j == 0) ? r.p : P.wcol(j - 1);
         const double *tin = nullptr;
-        const bool mgs = popts.schur == DNS_SCHUR_MG;
-        if (s6 && j == 0 && step6.kx && have_jg && !mgs) {
-            // six-node step: r = b - kx is formed HERE (extra workgroups),
-            // the Schur rows gather b - kx themselves
-            tau_first();
-            tin = tau.p;
-        } else if (have_jg && !mgs) {
-            const int jt = (fusedgs && j > 0) ? j : 0;
-            DNS_LPR_SWITCH(
-                JG.lpr,
-                hipLaunchKernelGGL(k_tau_guard<L>,
-                                   grid_for_rows(q1 - q0, JG.lpr == 64 ? 128 : JG.lpr),
-                                   kBlock, 0,
-                                   stream, np, nv, JG.rowptr.p, JG.colidx.p,
-                                   JG.vals.p, src, tau.p, partA.p,
-                                   jt > 0 ? kparts(jt - 1) : gridC, jt, ctl.p,
-                                   q0, q1));
-            tin = tau.p;
-        }
-        if (fusedgs && j > 0 && mgs) {
-            hipLaunchKernelGGL(k_arn_head_f<3>, gridA, kBlock, 0, stream, n, nv,
-                               np, j, wcol(j - 1), partA.p, kparts(j - 1), V.p, ld, Z.p,
-                               (const void *)nullptr, ctl.p, o->maxiter,
-                               (const double *)nullptr);
-        } else if (!(fusedgs && j > 0) && mgs) {
-            hipLaunchKernelGGL(k_arn_head<3>, gridA, kBlock, 0, stream, n, nv,
-                               np, j, src, spart, snp, V.p, ld,
-                               (const void *)nullptr, zp, ctl.p, o->rtol,
-                               o->atol, bb_part, rr_np, o->maxiter, q0, q1,
-                               (j == 0) ? first : 0, (const double *)nullptr,
-                               j == 0 ? ctr0 : nullptr);
-        } else if (fusedgs && j > 0) {
-            if (dense && fp32_store)
-                hipLaunchKernelGGL(k_arn_head_f<2>, gridA, kBlock, 0, stream, n,
-                                   nv, np, j, wcol(j - 1), partA.p, kparts(j - 1), V.p,
-                                   ld,
-                                   Z.p, (const void *)sinv32.p, ctl.p,
-                                   o->maxiter, tin, 0, np, sld);
-            else if (dense)
-                hipLaunchKernelGGL(k_arn_head_f<1>, gridA, kBlock, 0, stream, n,
-                                   nv, np, j, wcol(j - 1), partA.p, kparts(j - 1), V.p,
-                                   ld,
-                                   Z.p, (const void *)sinv.p, ctl.p,
-                                   o->maxiter, tin);
-            else
-                hipLaunchKernelGGL(k_arn_head_f<0>, gridA, kBlock, 0, stream, n,
-                                   nv, np, j, wcol(j - 1), partA.p, kparts(j - 1), V.p,
-                                   ld,
-                                   Z.p, (const void *)sinv.p, ctl.p,
-                                   o->maxiter, tin);
-        } else if (dense && fp32_store)
-            hipLaunchKernelGGL(k_arn_head<2>, gridA, kBlock, 0, stream, n, nv,
-                               np, j, src, spart, snp, V.p, ld,
-                               (const void *)sinv32.p, zp, ctl.p, o->rtol,
-                               o->atol, bb_part, rr_np, o->maxiter, q0, q1,
-                               (j == 0) ? first : 0, tin,
-                               j == 0 ? ctr0 : nullptr,
-                               sld);
-        else if (dense)
-            hipLaunchKernelGGL(k_arn_head<1>, gridA, kBlock, 0, stream, n, nv,
-                               np, j, src, spart, snp, V.p, ld,
-                               (const void *)sinv.p, zp, ctl.p, o->rtol,
-                               o->atol, bb_part, rr_np, o->maxiter, q0, q1,
-                               (j == 0) ? first : 0, tin,
-                               j == 0 ? ctr0 : nullptr);
-        else
-            hipLaunchKernelGGL(k_arn_head<0>, gridA, kBlock, 0, stream, n, nv,
-                               np, j, src, spart, snp, V.p, ld,
-                               (const void *)sinv.p, zp, ctl.p, o->rtol,
-                               o->atol, bb_part, rr_np, o->maxiter, q0, q1,
-                               (j == 0) ? first : 0, tin,
-                               j == 0 ? ctr0 : nullptr);
-        if (mgs) {
-            // Schur block = V-cycle on V_j,p (or tau(V_j))
-            const double *sin = V.p + (size_t)j * ld + nv;
-            if (have_jg && streams(JG)) {
-                // tau = V_j,p - JG V_j,v through the streaming kernel
-                const double *vj = V.p + (size_t)j * ld;
-                if (JG.vals32.p)
-                    DNS_TRY(launch_stream16x<float>(
-                        JG, JG.vals32.p, vj, tau.p,
-                        stream_epi_plain(-1.0, 1.0, vj + nv), stream,
-                        done_ptr()));
-                else
-                    DNS_TRY(launch_spmv(JG, vj, tau.p, -1.0, 1.0, vj + nv,
-                                        DNS_SPMV_STREAM16, stream,
-                                        done_ptr()));
-                sin = tau.p;
-            } else if (have_jg) {
-                DNS_LPR_SWITCH(
-                    JG.lpr,
-                    hipLaunchKernelGGL(k_tau_guard<L>,
-                                       grid_for_rows(np, JG.lpr == 64 ? 128 : JG.lpr),
-                                       kBlock, 0,
-                                       stream, np, nv, JG.rowptr.p,
-                                       JG.colidx.p, JG.vals.p,
-                                       V.p + (size_t)j * ld, tau.p,
-                                       (const double *)nullptr, 0, -1, ctl.p,
-                                       0, np));
-                sin = tau.p;
+        if (have_jg && !P.mgs) {
+            if (P.s6 && j == 0 && step6.kx) {
+                // six-node step: r = b - kx is formed HERE (extra workgroups),
+                // the Schur rows gather b - kx themselves
+                DNS_TRY(node_tau_first(b, step6.kx));
+            } else {
+                // (unguarded: 3 us when already done)
+                const int jt = (P.fusedgs && j > 0) ? j : 0;
+                DNS_TRY(node_tau(src, P.hpart,
+                                 jt > 0 ? P.hparts(jt - 1) : gridC, jt, P.p0,
+                                 P.p1));
             }
-            DNS_TRY(schur_mg_apply(sin, zp, nullptr, done_ptr()));
+            tin = tau.p;
         }
+        DNS_TRY(node_head(P, j, src, zp, tin));
+        if (P.mgs) DNS_TRY(node_schur_mg(P, j));
         DNS_TRY(apply_fhat_part(V.p + (size_t)j * ld, zp, zj, done_ptr(),
                                 nullptr));
-        if (stream_k && fusedgs && j + 1 <= kStreamDots) {
-            StreamEpi ep = stream_epi_plain(1.0, 0.0, nullptr);
-            ep.V = V.p;
-            ep.ld = ld;
-            ep.nvec = j + 1;
-            ep.with_ww = 1;
-            ep.part = partA.p;
-            ep.nparts = gridK;
-            if (Kp.ready)
-                DNS_TRY(launch_pair16x(Kp, zj, w.p, ep, stream, done_ptr(),
-                                       sgrid));
-            else
-                DNS_TRY(launch_stream16x<double>(K, K.vals.p, zj, w.p, ep,
-                                                 stream, done_ptr(),
-                                                 sgrid));
-            continue;                    // no Gram-Schmidt kernel
-        } else if (fuse_dots || fusedgs) {
-            DNS_LPR_SWITCH(
-                K.lpr,
-                hipLaunchKernelGGL(k_spmv_multidot<L>, gridC, kBlock, 0,
-                                   stream, n, K.rowptr.p, K.colidx.p,
-                                   K.vals.p, zj, wcol(j), V.p, ld, j, partA.p,
-                                   gridC, ctl.p, RowMap{0, n, 0, 0},
-                                   fusedgs ? 1 : 0));
-            if (fusedgs) continue;       // no Gram-Schmidt kernel
-        } else {
-            if (K.c16.p) {
-                // bandwidth regime: the LDS-streaming kernel with 16-bit
-                // column offsets (the roofline kernel of bench.py)
-                DNS_TRY(launch_spmv(K, zj, w.p, 1.0, 0.0, nullptr,
-                                    DNS_SPMV_STREAM16, stream, done_ptr()));
-            } else {
-                DNS_LPR_SWITCH(
-                    K.lpr,
-                    hipLaunchKernelGGL(k_spmv_guard<L>,
-                                       grid_for_rows(n, K.lpr), kBlock, 0,
-                                       stream, n, K.rowptr.p, K.colidx.p,
-                                       K.vals.p, zj, w.p, ctl.p, 0, n));
-            }
-            hipLaunchKernelGGL(k_multidot, gridC, kBlock, 0, stream, n, V.p,
-                               ld, w.p, partA.p, gridC, j, ctl.p);
-        }
-        const double *hpart = partA.p;
-        const int hnp = gridC;
-        if (o->reorth == 1) {
-            hipLaunchKernelGGL(k_orth<1>, gridD, kBlock, 0, stream, n, V.p, ld,
-                               w.p, hpart, hnp, j, 0, partE.p, gridD, ctl.p);
-            hipLaunchKernelGGL(k_orth<0>, gridD, kBlock, 0, stream, n, V.p, ld,
-                               w.p, partE.p, gridD, j, 1, partN.p, gridD,
-                               ctl.p);
-        } else {
-            hipLaunchKernelGGL(k_orth<0>, gridD, kBlock, 0, stream, n, V.p, ld,
-                               w.p, hpart, hnp, j, 0, partN.p, gridD, ctl.p);
-        }
+        DNS_TRY(node_k_apply(P, j, zj));
+        if (!P.fusedgs) DNS_TRY(node_orth(P, j, o->reorth));
     }
-    if (s6) {
-        // six-node step: out-of-place tail + new residual + convection cells
-        hipLaunchKernelGGL(k_arn_tail6<false>, gridD + step6.cells.nblocks,
-                           kBlock, 0, stream, c, n, gridD, partA.p,
-                           kparts(c - 1), ctl.p, histdev.p, (int)hist_cap,
-                           o->maxiter, Z.p, ld, t6, hk.tail_extrap, step6.cells,
-                           TailLazy{});
-        DNS_HIP(hipGetLastError());
-        return DNS_OK;
-    }
-    if (fusedgs) {
-        // one GPU, fused Gram-Schmidt: tail and correction in ONE launch
-        hipLaunchKernelGGL(k_arn_tail_acc, gridD, kBlock, 0, stream, c, n,
-                           partA.p, kparts(c - 1), ctl.p, histdev.p,
-                           (int)hist_cap, o->maxiter, Z.p, ld, x, hk.tail_extrap);
-        DNS_HIP(hipGetLastError());
-        return DNS_OK;
-    }
-    hipLaunchKernelGGL(k_arn_tail, 1, kBlock, 0, stream, c, partN.p, gridD,
-                       ctl.p, histdev.p, (int)hist_cap, o->maxiter, 0);
-    hipLaunchKernelGGL(k_basis_combine_acc, gridD, kBlock, 0, stream, n, Z.p,
-                       ld, ctl.p, x, hk.tail_extrap);
-    DNS_HIP(hipGetLastError());
-    return DNS_OK;
+    return node_tail(P, c, x, hk);
 }
 
 int dns_saddle::ensure_solver_buffers(const dns_solve_opts *o) {
@@ -2014,11 +1774,7 @@ int dns_saddle::bicgstab(const double *b, double *x, const dns_solve_opts *o,
         drop_graphs();
         DNS_TRY(histdev.alloc(hcap));
     }
-    DNS_LPR_SWITCH(K.lpr,
-                   hipLaunchKernelGGL(k_resid_norm<L>, nred, kBlock, 0, stream,
-                                      n, K.rowptr.p, K.colidx.p, K.vals.p, x,
-                                      b, r.p, partR.p, partB.p,
-                                      RowMap{0, n, 0, 0}));
+    DNS_TRY(resid_norm_csr(nred, x, b, partB.p, RowMap{0, n, 0, 0}));
     spmv_count++;
     // <rhat, r> = <r, r> at the start: partR doubles as part_rr and part_nn
     hipLaunchKernelGGL(k_bicg_start, nred, kBlock, 0, stream, n, r.p,
@@ -2699,10 +2455,18 @@ int dns_saddle_probe(dns_saddle *h, int32_t which, int32_t chain,
     if (h->histdev.n < 1024) DNS_TRY(h->histdev.alloc(1024));
     h->hist_cap = h->histdev.n;
     hipStream_t s = h->stream;
-    const int j = 3, n = h->n, nv = h->nv, np = h->np;
-    const bool dense = h->popts.schur == DNS_SCHUR_DENSE;
-    const int gridA =
-        dense ? std::max(h->gridD, std::min((np + 3) / 4, 2048)) : h->gridD;
+    // the nodes of an explicit Gram-Schmidt cycle of the latency regime at
+    // column j = 3, on the scratch vectors z, w: the head cannot converge
+    // (tol = -1 in the header below) or run out of iterations
+    const int j = 3, n = h->n, nv = h->nv;
+    dns_solve_opts po;
+    memset(&po, 0, sizeof(po));
+    po.rtol = 1e-10;
+    po.maxiter = 1 << 30;
+    static const StepHooks none;
+    CyclePlan P = h->plan_cycle(8, &po, 0, false, none);
+    P.multidot = true;           // (K z + dots in one launch, whatever n)
+    P.bb_np = h->gridS;          // (partB as case 4 fills it)
     double *zp = h->z.p + nv;
     auto body = [&]() -> int {
         // which == 8: the four kernels of one Arnoldi step in sequence;
@@ -2721,66 +2485,22 @@ int dns_saddle_probe(dns_saddle *h, int32_t which, int32_t chain,
             for (int sub = 0; sub < nseq; ++sub)
             switch (seq[sub]) {
                 case 0:
-                    if (dense && h->fp32_store)
-                        hipLaunchKernelGGL(k_arn_head<2>, gridA, kBlock, 0, s, n,
-                                           nv, np, j, h->w.p, h->partN.p,
-                                           h->gridD, h->V.p, h->ld,
-                                           (const void *)h->sinv32.p, zp,
-                                           h->ctl.p, 1e-10, 0.0, h->partB.p,
-                                           h->gridS, 1 << 30, 0, np, 0,
-                                           (const double *)nullptr,
-                                           (int *)nullptr, h->sld);
-                    else if (dense)
-                        hipLaunchKernelGGL(k_arn_head<1>, gridA, kBlock, 0, s, n,
-                                           nv, np, j, h->w.p, h->partN.p,
-                                           h->gridD, h->V.p, h->ld,
-                                           (const void *)h->sinv.p, zp,
-                                           h->ctl.p, 1e-10, 0.0, h->partB.p,
-                                           h->gridS, 1 << 30, 0, np, 0, (const double *)nullptr);
-                    else if (h->popts.schur == DNS_SCHUR_JACOBI)
-                        // (sinv is the DIAGONAL here: np entries)
-                        hipLaunchKernelGGL(k_arn_head<0>, gridA, kBlock, 0, s, n,
-                                           nv, np, j, h->w.p, h->partN.p,
-                                           h->gridD, h->V.p, h->ld,
-                                           (const void *)h->sinv.p, zp,
-                                           h->ctl.p, 1e-10, 0.0, h->partB.p,
-                                           h->gridS, 1 << 30, 0, np, 0, (const double *)nullptr);
-                    else
-                        hipLaunchKernelGGL(k_arn_head<3>, gridA, kBlock, 0, s, n,
-                                           nv, np, j, h->w.p, h->partN.p,
-                                           h->gridD, h->V.p, h->ld,
-                                           (const void *)nullptr, zp,
-                                           h->ctl.p, 1e-10, 0.0, h->partB.p,
-                                           h->gridS, 1 << 30, 0, np, 0, (const double *)nullptr);
+                    DNS_TRY(h->node_head(P, j, h->w.p, zp, nullptr));
                     break;
                 case 1:
                     DNS_TRY(h->apply_fhat_part(h->V.p + (size_t)j * h->ld, zp,
                                                h->z.p, h->zero_ptr(), nullptr));
                     break;
                 case 2:
-                    DNS_LPR_SWITCH(
-                        h->K.lpr,
-                        hipLaunchKernelGGL(k_spmv_multidot<L>, h->gridC, kBlock,
-                                           0, s, n, h->K.rowptr.p,
-                                           h->K.colidx.p, h->K.vals.p, h->z.p,
-                                           h->w.p, h->V.p, h->ld, j,
-                                           h->partA.p, h->gridC, h->ctl.p,
-                                           RowMap{0, n, 0, 0}, 0));
+                    DNS_TRY(h->node_k_apply(P, j, h->z.p));
                     break;
                 case 3:
-                    hipLaunchKernelGGL(k_orth<0>, h->gridD, kBlock, 0, s, n,
-                                       h->V.p, h->ld, h->w.p, h->partA.p,
-                                       h->gridC, j, 0, h->partN.p, h->gridD,
-                                       h->ctl.p);
+                    DNS_TRY(h->node_orth(P, j, 0));
                     break;
                 case 4:
-                    DNS_LPR_SWITCH(
-                        h->K.lpr,
-                        hipLaunchKernelGGL(k_resid_norm<L>, h->gridS, kBlock, 0,
-                                           s, n, h->K.rowptr.p, h->K.colidx.p,
-                                           h->K.vals.p, h->xdev.p, h->bdev.p,
-                                           h->r.p, h->partR.p, h->partB.p,
-                                           RowMap{0, n, 0, 0}));
+                    // (the CSR form of node_residual, whatever the regime)
+                    DNS_TRY(h->resid_norm_csr(h->gridS, h->xdev.p, h->bdev.p,
+                                              h->partB.p, P.kmap));
                     break;
                 case 5:
                     hipLaunchKernelGGL(k_arn_tail, 1, kBlock, 0, s, 0,

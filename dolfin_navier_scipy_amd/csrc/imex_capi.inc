@@ -930,14 +930,8 @@ int ImexRun::run_batch() {
             // (the last rows: nobody runs a prologue behind it)
             DNS_TRY(st->launch_closing_nodes(h->stream));
             DNS_HIP(hipEventRecord(st->e1, h->stream));
-            DNS_LPR_SWITCH(
-                h->K.lpr,
-                hipLaunchKernelGGL(dns::k_resid_norm<L>, h->gridS, dns::kBlock,
-                                   0, h->stream, h->n, h->K.rowptr.p,
-                                   h->K.colidx.p, h->K.vals.p,
-                                   st->xs[st->cur].p, st->b.p, h->r.p,
-                                   h->partR.p, (double *)nullptr,
-                                   dns::RowMap{0, h->n, 0, 0}));
+            DNS_TRY(h->resid_norm_csr(h->gridS, st->xs[st->cur].p, st->b.p,
+                                      nullptr, dns::RowMap{0, h->n, 0, 0}));
             hipLaunchKernelGGL(dns::k_sum_partials, 1, dns::kBlock, 0,
                                h->stream, h->partR.p, h->gridS, h->scal.p);
             DNS_TRY(dns::d2h_pinned(h->scal_host.p, h->scal.p, 1, h->stream));

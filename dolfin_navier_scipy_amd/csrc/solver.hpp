@@ -397,6 +397,64 @@ struct StepHooks {
     uint64_t key(bool first) const;
 };
 
+// the Schur block as the head kernels take it
+struct SchurBlock {
+    int kind = 0;               // SK of k_arn_head / k_arn_head_f: 0 diagonal,
+                                // 1 / 2 dense fp64 / fp32, 3 multigrid (applied
+                                // behind the head: node_schur_mg)
+    const void *inv = nullptr;
+    int stride = 0;             // row stride of the dense inverse (0: np)
+    int col0 = 0, ncols = -1;   // the columns this rank holds (-1: all)
+    int add_corr = 1;           // this rank adds the Gram-Schmidt correction
+};
+
+// What the nodes of ONE Krylov cycle share (cycle_nodes.inc), computed once
+// per enqueue: plan_cycle on one GPU, plan_cycle_dist when row-partitioned.
+struct CyclePlan {
+    SchurBlock schur;
+    bool dense = false, mgs = false;
+    // reorth == 2: Gram-Schmidt folded into the next head kernel
+    bool fusedgs = false;
+    // bandwidth regime: K through the streaming / pair kernel, with the dots
+    // fused in (while they fit its accumulators: kStreamDots)
+    bool stream_k = false, stream_dots = false;
+    bool multidot = true;       // else: K z and k_multidot in two launches
+    int multidot_ww = 0;        // k_spmv_multidot adds the partials of <w, w>
+    int first = 0;              // 1: the head of column 0 resets the solve's
+                                // counters, 2: only its status
+    int *stepctr = nullptr;     // (that head bumps the stepper's step counter)
+    double rtol = 0, atol = 0;
+    int maxiter = 0;
+    int gridA = 0;              // head
+    int gridK = 0, gridKc = 0;  // K apply: streamed / by CSR rows
+    int gridR = 0;              // k_resid_norm
+    // the consumers of a reduction read per-workgroup partials (one GPU) or
+    // all-reduced sums (partitioned: one "partial" each, and the cycle sums
+    // into these buffers between the nodes)
+    double *rr_part = nullptr, *bb_part = nullptr;   // ||r||^2, ||b||^2
+    int rr_np = 0, bb_np = 0;
+    double *hpart = nullptr;           // dots of a step, <w, w> behind them
+    bool hsummed = false;
+    double *npart = nullptr;           // norm of the orthogonalised vector
+    int nnp = 0;
+    // partials of step j's dots: written by the kernel that applied K
+    int kparts(int j) const {
+        return (stream_dots && j + 1 <= kStreamDots) ? gridK : gridKc;
+    }
+    int hparts(int j) const { return hsummed ? 1 : kparts(j); }
+    // rows this rank computes: Schur, velocity, pressure; K's row block
+    int q0 = 0, q1 = 0, v0 = 0, v1 = 0, p0 = 0, p1 = 0;
+    int map_on = 0;
+    RowMap kmap = {0, 0, 0, 0};
+    // six-node step: K z_j is kept per column (the tail forms the new
+    // residual r0 - sum y_j K z_j from them)
+    bool s6 = false;
+    Tail6 t6 = {};
+    double *w = nullptr, *wcols = nullptr;
+    size_t ld = 0;
+    double *wcol(int j) const { return s6 ? wcols + (size_t)j * ld : w; }
+};
+
 }  // namespace dns
 
 // the opaque handle of the C-ABI
@@ -523,11 +581,12 @@ struct dns_saddle {
     bool dist_x0_exchange = false;
     // one-step cycles without the all-reduce of the residual norm
     // (k_arn_tail_lazy1); the constants 1, 0 the head reads as "norms"
+    // (plan_cycle_dist points rr_part / bb_part at them)
     bool dist_lazy1 = true;
-    // six-node step, one-column cycle: the head scales nothing and reduces
-    // nothing, the tail forms the step from <r, K z>, <K z, K z>, ||r||^2
-    // (k_arn_head_lazy, k_spmv_rw, k_arn_tail6<true>); longer cycles run the
-    // general nodes
+    // six-node step, one-column cycle (enqueue_cycle_lazy6): the head scales
+    // nothing and reduces nothing, the tail forms the step from <r, K z>,
+    // <K z, K z>, ||r||^2 (k_arn_head_lazy, k_spmv_rw, k_arn_tail6<true>);
+    // longer cycles run the general nodes
     bool step6_lazy = true;
     // (a six-node cycle of c columns is the lazy one; the tail reads one
     // partial of ||r||^2 per thread)
@@ -714,7 +773,8 @@ struct dns_saddle {
     // second column (one cycle each) is the cheaper way to the same
     // reduction -- with two cycles in every column a 200-step window that
     // starts in a two-column phase ran at 3360 steps/s instead of 4810 (refine
-    // 2).  enqueue_cycle sets `mg_two_now` for the kernels it enqueues.
+    // 2).  enqueue_cycle sets `mg_two_now` for the kernels its nodes enqueue
+    // (node_schur_mg -> schur_mg_apply); the partitioned cycle never does.
     bool mg_two_now = false;
     bool mg_two_for(int c) const {
         return mg_cycles_eff() >= 2 && (mg_cycles_knob == 2 || c <= 1);
@@ -755,6 +815,34 @@ struct dns_saddle {
     int enqueue_cycle(const double *b, double *x, int c,
                       const dns_solve_opts *o, int first, bool have_resid,
                       const dns::StepHooks &hk);
+    // ... its lazy one-column form (six-node step, step6_lazy_for)
+    int enqueue_cycle_lazy6(const dns::CyclePlan &P, const double *b,
+                            const dns::StepHooks &hk);
+    // the nodes of a cycle (cycle_nodes.inc): each only enqueues on `stream`.
+    // One launcher per node, shared by enqueue_cycle, enqueue_cycle_dist and
+    // dns_saddle_probe wherever the launches differ in nothing but values of
+    // the plan
+    int head_grid() const;
+    dns::SchurBlock schur_block() const;
+    dns::CyclePlan plan_cycle(int c, const dns_solve_opts *o, int first,
+                              bool have_resid, const dns::StepHooks &hk) const;
+    dns::CyclePlan plan_cycle_dist(const dns_solve_opts *o, int first,
+                                   const dns::StepHooks &hk, bool lazy) const;
+    int resid_norm_csr(int grid, const double *x, const double *b,
+                       double *part_bb, const dns::RowMap &rm);
+    int node_residual(const dns::CyclePlan &P, const double *b,
+                      const double *x);
+    int node_tau(const double *src, const double *part, int nparts, int jt,
+                 int p0, int p1);
+    int node_tau_first(const double *b, const double *kx);
+    int node_head(const dns::CyclePlan &P, int j, const double *src,
+                  double *zp, const double *tin);
+    int node_schur_mg(const dns::CyclePlan &P, int j);
+    int node_fhat_dist(const dns::CyclePlan &P, int j);
+    int node_k_apply(const dns::CyclePlan &P, int j, const double *zj);
+    int node_orth(const dns::CyclePlan &P, int j, int reorth);
+    int node_tail(const dns::CyclePlan &P, int c, double *x,
+                  const dns::StepHooks &hk);
     // run `body` eagerly or as a cached graph identified by `key`
     // launch == false: capture + instantiate only (set-up time), nothing runs
     template <typename Body>
