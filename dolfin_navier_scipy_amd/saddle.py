@@ -20,6 +20,11 @@ _FHAT = {'cheb': C.DNS_FHAT_CHEB, 'explicit': C.DNS_FHAT_EXPLICIT,
 
 def solve_opts(method='gmres', restart=60, maxiter=400, reorth=True,
                rtol=1e-10, atol=0., check_every=4, use_graph=False):
+    """`reorth`: True / 1 classical Gram-Schmidt twice, False / 0 once, 2 once
+    and fused into the head kernel.  On a row-partitioned handle (`set_comm`,
+    `from_rows`) `reorth = 1` is ONE pass as well: its explicit branch runs
+    `k_orth<0>` alone, a second pass would cost two more all-reduces per
+    column (pinned by `tests/test_gpu_zz_dist_krylov.py`)."""
     o = C.dns_solve_opts()
     C.load_library().dns_default_solve_opts(ct.byref(o))
     o.method = _METHODS[method.lower()] if isinstance(method, str) else method

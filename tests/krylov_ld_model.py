@@ -51,6 +51,8 @@ FACTOR = 32                             # ~ sqrt(1493), see the CPU test
 
 GMRES_MUTATIONS = ('drop_last_z', 'no_x0', 'givens_prev', 'backsub_T',
                    'no_fold_corr', 'hist_shift')
+# (of the one-step cycle of the row-partitioned solve, `k_arn_tail_lazy1`)
+LAZY_MUTATIONS = ('lazy_no_norm',)
 BICG_MUTATIONS = ('beta_plain', 'parity', 'omega_ss')
 
 
@@ -194,6 +196,8 @@ def gmres_cycles(prob, b, x0, cycles, reorth, noise=None, mut=None):
                 z = prob.apply(V[j])
             Z[j] = z = nz.precond(z, V[j])
             w = nz.mv(prob.mv(z), z)
+            if j == 0:
+                w0 = w
             Vj = V[:j + 1]
             h = nz.dots(Vj @ w, Vj, w)
             if reorth == 2:
@@ -245,6 +249,11 @@ def gmres_cycles(prob, b, x0, cycles, reorth, noise=None, mut=None):
             if mut == 'drop_last_z':
                 y[jc - 1] = 0
             xk = x + Z[:jc].T @ y
+            if mut == 'lazy_no_norm' and cyc == 0 and c == 1:
+                # the one-step cycle on the un-normalised `V_0 = r`:
+                # `x += (<w, r> / <w, w>) z`, here without the division
+                zr, wr = beta*Z[0], beta*w0
+                xk = x + (wr @ r)*zr
             xs.append(xk - xstart if mut == 'no_x0' else xk)
             res.append(norm_ld(b - prob.mv(xk)))
         x = xk
@@ -524,3 +533,68 @@ def stagnation_floor(prob, b):
         noisy = max(noisy, best(gmres_cycles(
             prob, b, None, (STAG_COLS,), 2, Noise(prob, seed, tols))[2]))
     return np.array([noisy, best(res), min(rounded), float(norm_ld(b))])
+
+
+# ---- the runs tests/test_gpu_zz_dist_krylov.py adds -------------------------------
+# (a second golden file; `FORMS` and `GOLDEN` above stay what they are)
+DIST_FORMS = {
+    # dense Schur, explicit degree 4, TRIANGULAR: no `J Fh^-1`, the Schur block
+    # of a row-partitioned head reads the pressure part itself
+    'D4t': pm.form_of(),
+}
+ALL_FORMS = dict(FORMS, **DIST_FORMS)
+# `cycle_first = 1`, `restart = 5`, `maxiter = 6`: the one-step cycle (lazy or
+# general: column 1 of GMRES either way), then `min(m, max(2 c, 8)) = 5`
+LAZY = (1, 5)
+LAZY_FORMS = ('D4', 'D4f', 'D4t', 'MG')
+GOLDEN_DIST = 'krylov_dist_tol.npz'
+
+
+def dist_runs(cases=CASES, lazy_cases=CASES, leg3=True):
+    """`(form, rhs, start, cycles, reorths)` of the second golden file: the
+    `LONG` and `RESTARTED` runs of `DIST_FORMS`, the `LAZY` runs (`reorth = 2`
+    alone: nothing else takes the one-step cycle) of `LAZY_FORMS`"""
+    for form in DIST_FORMS:
+        for rhs, start in cases:
+            for cycles in (LONG, RESTARTED) if leg3 else (LONG,):
+                yield form, rhs, start, cycles, REORTHS
+    for form in LAZY_FORMS:
+        for rhs, start in lazy_cases:
+            yield form, rhs, start, LAZY, (2,)
+
+
+def dist_clean_table(bench):
+    """`/h` and `/nx` of every run of `dist_runs()`"""
+    tab, probs = {}, {}
+    rhs_of, start_of = right_hand_sides(bench), starts(bench)
+    for form, rhs, start, cycles, reorths in dist_runs():
+        if form not in probs:
+            probs[form] = Problem(bench, ALL_FORMS[form])
+        for reorth in reorths:
+            out = gmres_cycles(probs[form], rhs_of[rhs], start_of[start],
+                               cycles, reorth)
+            key = gmres_key(form, rhs, start, reorth, cycles)
+            tab[key + '/nx'] = block_norms(out[0], bench.NV)
+            tab[key + '/h'] = np.asarray(out[1], dtype=np.float64)
+    return tab
+
+
+def dist_tolerance_table(bench, runs=None, log=None):
+    """every tolerance `tests/golden/krylov_dist_tol.npz` holds, by the recipe
+    of `tolerance_table` (`tolerances()`)"""
+    tab, probs = {}, {}
+    rhs_of, start_of = right_hand_sides(bench), starts(bench)
+    for form, rhs, start, cycles, reorths in (dist_runs() if runs is None
+                                              else runs):
+        if form not in probs:
+            probs[form] = Problem(bench, ALL_FORMS[form])
+        prob, tols = probs[form], []
+        for reorth in reorths:
+            def run(nz):
+                return gmres_cycles(prob, rhs_of[rhs], start_of[start], cycles,
+                                    reorth, nz)
+            key = gmres_key(form, rhs, start, reorth, cycles)
+            pack(tab, key, *tolerances(run, prob, tols=tols), prob.NV)
+            if log:
+                log(key)
+    return tab

@@ -62,7 +62,13 @@ the instantiations of the one-GPU test), per form over all of its cases:
     un-partitioned model on the rows of every rank: the same figures
 All below the 0.25 of the one-GPU forms; no check found a wrong entry, a stale
 halo entry or a wrong ring slot: the start residuals of 5-18 x tol of the
-partitioned path are not explained by its front or its tails' warm start.
+partitioned path are not explained by its front or its tails' warm start --
+nor by its Krylov cycle, which `tests/test_gpu_zz_dist_krylov.py` holds to the
+long double model column by column (0.04 of a tolerance at most, the same bits
+on every rank, with and without the exchange of `x`).  The path computes what
+it says; what is left is the stopping rule: a one-step cycle takes its step
+whenever the start residual is above `1e-3 tol` and reports the residual
+BEHIND the step, so a start residual of a few `tol` is by itself no error.
 
 Seconds on the MI355X: the 98 cases on one RCCL rank 7.8 in all
 (`test_gpu_imex_front.py`: 12.2 for its 114); the spawn of 2 ranks 6.8, of 3

@@ -87,6 +87,51 @@ every `k`, and the `5+5+3` runs; of those `x_13` is listed on every form for
     bicg/J2/time-step/rough      xx 3e-12 1e-11
     bicg/J2/time-step/zero       xxx 3e-13 2e-11 1e-12
 
+The runs the row-partitioned cycle adds (`tests/test_gpu_zz_dist_krylov.py`)
+are in a second file, `tests/golden/krylov_dist_tol.npz` (`--dist` writes it,
+two minutes; same recipe, same `listed()`): the form D4t (dense Schur,
+TRIANGULAR, explicit degree 4: no `J Fh^-1`), one cycle of twelve and
+`5+5+3`, and the cycle lists `1+5` (`cycle_first = 1`, `restart = 5`,
+`maxiter = 6`, `reorth = 2`: the one-step cycle of a partitioned solve is
+column 1 of GMRES, its `x_1`, `hist[0]`, `hist[1]` need no second model) on
+D4, D4f, D4t, MG.  30 runs, 192 listed `(run, k)`; of leg 1 on D4t (`k` in 1,
+2, 3, 5, 9, 12, three cases) 12, 12 and 6 of 18 for `reorth` 0, 1, 2, every
+`k` among them from zero for 0 and 1; `x_1` of every `1+5` run from zero.
+`test_golden_tolerances_of_the_second_file_are_the_models` recomputes the
+`time-step / zero` runs of D4t and of every `1+5`, `test_clean_runs_of_the_
+second_file` the noise-free part of all 30.  D4t, one cycle of twelve (as
+above), and all six `k` of the `1+5` runs:
+
+    D4t/rough/zero/r0       xxxxxxxxxxxx  4e-12 7e-11 6e-11 4e-12 4e-12 4e-12
+    D4t/rough/zero/r1       xxxxxxxxxxxx  4e-12 8e-11 7e-11 3e-12 3e-12 3e-12
+    D4t/rough/zero/r2       xx.xxxxxx...  4e-12 7e-11 1e-10 5e-11 5e-11 nan
+    D4t/time-step/rough/r0  x...........  1e-13 1e-09 2e-09 3e-09 2e-09 2e-09
+    D4t/time-step/rough/r1  x...........  1e-13 2e-09 2e-09 5e-10 2e-10 2e-10
+    D4t/time-step/rough/r2  x...........  1e-13 2e-09 6e-08 8e-08 nan nan
+    D4t/time-step/zero/r0   x.xxxxxxxxxx  4e-12 2e-10 8e-11 5e-12 5e-12 5e-12
+    D4t/time-step/zero/r1   x.xxxxxxxxxx  4e-12 2e-10 8e-11 4e-12 4e-12 4e-12
+    D4t/time-step/zero/r2   x...........  4e-12 2e-10 2e-10 2e-10 nan nan
+
+    D4/rough/zero/r2/1+5        xxxxx.  6e-11 7e-12 7e-12 7e-12 7e-12 nan
+    D4/time-step/rough/r2/1+5   .xxxx.  4e-09 9e-11 8e-12 5e-12 5e-12 nan
+    D4/time-step/zero/r2/1+5    xxxxx.  7e-11 5e-12 4e-12 4e-12 4e-12 nan
+    D4f/rough/zero/r2/1+5       xxxxx.  6e-11 7e-12 7e-12 7e-12 7e-12 nan
+    D4f/time-step/rough/r2/1+5  .xxxx.  4e-09 9e-11 8e-12 8e-12 8e-12 nan
+    D4f/time-step/zero/r2/1+5   xxxxx.  7e-11 5e-12 4e-12 4e-12 4e-12 nan
+    D4t/rough/zero/r2/1+5       xx....  4e-12 4e-12 3e-10 2e-10 2e-10 2e-10
+    D4t/time-step/rough/r2/1+5  xx....  1e-13 1e-13 2e-09 2e-08 3e-08 3e-08
+    D4t/time-step/zero/r2/1+5   xx....  4e-12 4e-12 3e-10 3e-10 4e-10 4e-10
+    MG/rough/zero/r2/1+5        xxxxxx  4e-11 2e-11 9e-12 6e-12 6e-12 6e-12
+    MG/time-step/rough/r2/1+5   ....xx  1e-10 3e-10 3e-10 1e-10 3e-11 9e-12
+    MG/time-step/zero/r2/1+5    xxxxxx  4e-11 3e-11 2e-11 8e-12 5e-12 4e-12
+
+(`5+5+3` on D4t: `x_13` listed in all nine runs.  The triangular form takes
+the time step's right-hand side slowly -- the residual is still 1.0 of
+`||b||` after one column, 4.5e-9 after twelve -- and from the rough start every
+`x_k` past the first is a small difference of large vectors.  The restart
+behind the one-step cycle gives the fused form a fresh basis: D4 lists `x_2` ..
+`x_5` of `1+5`, of one cycle of twelve `x_1` alone.)
+
 What the table says about the device algorithm (each a consequence of the
 code, none an error):
 
@@ -125,6 +170,7 @@ factor 100; the largest `error / tol` over the listed cases):
     beta_plain     BiCGStab: `beta` without `alpha / omega`        4.2e+11
     parity         BiCGStab: the scalars of the other parity slot  1.9e+12
     omega_ss       BiCGStab: `omega = (t.s) / (s.s)`               1.0e+12
+    lazy_no_norm   one-step cycle: `alpha = <w, r>`, not `/ <w, w>` 2.8e+15
 """
 import os
 import sys
@@ -152,6 +198,11 @@ def bench(toy_prob):
 @pytest.fixture(scope='module')
 def golden(golden_dir):
     return dict(np.load(os.path.join(golden_dir, kl.GOLDEN)))
+
+
+@pytest.fixture(scope='module')
+def golden_dist(golden_dir):
+    return dict(np.load(os.path.join(golden_dir, kl.GOLDEN_DIST)))
 
 
 @pytest.fixture(scope='module')
@@ -233,6 +284,107 @@ def test_golden_tolerances_are_the_models(bench, golden):
     assert 0.5 <= noisy/golden['stagnation'][0] <= 2.
     assert np.allclose([clean, rounded, bnorm], golden['stagnation'][1:],
                        rtol=1e-6)
+
+
+def test_golden_tolerances_of_the_second_file_are_the_models(bench,
+                                                             golden_dist):
+    """the same comparison for `krylov_dist_tol.npz`: the `time-step / zero`
+    runs of D4t (12, 5+5+3, all three `reorth`) and the `1+5` run of every
+    form of `LAZY_FORMS` from `time-step / zero`"""
+    tab = kl.dist_tolerance_table(bench, runs=kl.dist_runs(
+        cases=(('time-step', 'zero'),), lazy_cases=(('time-step', 'zero'),)))
+    assert len(tab) == 4*(2*3 + 4)
+    for key in runs_of(tab, 'gmres'):
+        for s in ('/nx', '/h'):
+            assert np.allclose(tab[key + s], golden_dist[key + s], rtol=1e-9,
+                               atol=0., equal_nan=True), key
+        for k in range(1, len(tab[key + '/tx']) + 1):
+            assert kl.listed(tab, key, k) == kl.listed(golden_dist, key, k), \
+                (key, k)
+            if kl.listed(tab, key, k):
+                assert np.allclose(tab[key + '/tx'][k - 1],
+                                   golden_dist[key + '/tx'][k - 1], rtol=1e-2)
+                th = golden_dist[key + '/th'][:k + 1]
+                h = golden_dist[key + '/h'][:k + 1]
+                ok = th <= 1e-6*h
+                assert np.allclose(tab[key + '/th'][:k + 1][ok], th[ok],
+                                   rtol=1e-2)
+        if key.endswith('/12'):
+            for k in kl.LEG4_K:
+                assert (kl.stop_between(tab, key, k) is None) == \
+                    (kl.stop_between(golden_dist, key, k) is None), (key, k)
+
+
+def test_clean_runs_of_the_second_file(bench, golden_dist):
+    """the noise-free arrays of EVERY run in `krylov_dist_tol.npz`"""
+    tab = kl.dist_clean_table(bench)
+    assert sorted(tab) == sorted(k for k in golden_dist
+                                 if k.endswith(('/nx', '/h')))
+    for key, val in tab.items():
+        assert np.allclose(val, golden_dist[key], rtol=1e-9, atol=0.,
+                           equal_nan=True), key
+
+
+def test_print_the_second_table(golden_dist):
+    print()
+    for line in table_lines(golden_dist):
+        print(line)
+
+
+def test_what_is_listed_in_the_second_file(golden, golden_dist):
+    """the runs, the shapes and the listed set of `krylov_dist_tol.npz` are
+    what the module docstring says; no key of the first file is repeated"""
+    want = []
+    for form, rhs, start, cycles, reorths in kl.dist_runs():
+        want += [kl.gmres_key(form, rhs, start, r, cycles) for r in reorths]
+    assert sorted(want) == runs_of(golden_dist, 'gmres')
+    assert len(want) == 18 + 12 and not set(golden_dist) & set(golden)
+    assert runs_of(golden_dist, 'bicg') == []
+
+    def ks(form, rhs, start, reorth, cycles=kl.LONG):
+        key = kl.gmres_key(form, rhs, start, reorth, cycles)
+        return [k for k in range(1, sum(cycles) + 1)
+                if kl.listed(golden_dist, key, k)]
+    count = 0
+    for key in want:
+        n = sum(int(c) for c in key.split('/')[-1].split('+'))
+        tx, th, nx = (golden_dist[key + s] for s in ('/tx', '/th', '/nx'))
+        assert tx.shape == (n, 2) and th.shape == (n + 1,)
+        for k in range(1, n + 1):
+            if kl.listed(golden_dist, key, k):
+                count += 1
+                assert (tx[k - 1] <= 1e-10*nx[k - 1]).all()
+                assert (tx[k - 1] >= 16*kl.U64*nx[k - 1]).all()
+                assert np.isfinite(th[:k + 1]).all()
+    assert count == 192
+    every = list(range(1, 13))
+    for r in (0, 1):
+        # D4t, explicit Gram-Schmidt: the rough right-hand side from zero
+        # through all twelve columns (every `k` of leg 1), the time step's
+        # all but `x_2` (2e-10); from the rough start `x_1` alone in one
+        # cycle and `x_13` of the restarted run
+        assert ks('D4t', 'rough', 'zero', r) == every
+        assert ks('D4t', 'time-step', 'zero', r) == [1] + every[2:]
+        assert ks('D4t', 'time-step', 'rough', r) == [1]
+        for rhs, start in kl.CASES:
+            assert 13 in ks('D4t', rhs, start, r, kl.RESTARTED)
+    # fused: the first column everywhere
+    for rhs, start in kl.CASES:
+        assert 1 in ks('D4t', rhs, start, 2)
+    # leg 1 (`LEG1_K` of the three cases): 12, 12 and 6 of 18
+    for r, n in ((0, 12), (1, 12), (2, 6)):
+        assert sum(k in ks('D4t', rhs, start, r) for rhs, start in kl.CASES
+                   for k in kl.LEG1_K) == n
+    # the one-step cycle and the cycle of five behind it: `x_1` from zero on
+    # every form; `x_6` on MG alone (dense block: NaN by the fifth fused
+    # column, D4t: 3e-10 from the third)
+    for form in kl.LAZY_FORMS:
+        for rhs in ('time-step', 'rough'):
+            assert 1 in ks(form, rhs, 'zero', 2, kl.LAZY)
+        assert (6 in ks(form, 'time-step', 'zero', 2, kl.LAZY)) == \
+            (form == 'MG')
+    assert ks('D4', 'time-step', 'zero', 2, kl.LAZY) == [1, 2, 3, 4, 5]
+    assert ks('D4t', 'time-step', 'zero', 2, kl.LAZY) == [1, 2]
 
 
 def test_clean_runs_of_the_golden_file(bench, golden):
@@ -430,13 +582,42 @@ def test_mutation_is_caught(bench, probs, golden, mut):
     assert ex >= 100.
 
 
+@pytest.mark.parametrize('mut', kl.LAZY_MUTATIONS)
+def test_mutation_of_the_one_step_cycle_is_caught(bench, probs, golden_dist,
+                                                  mut):
+    """`x_1` and the rows behind it of the `1+5` runs (D4 and D4t, the two
+    starts of the time step's right-hand side)"""
+    rhs_of, start_of = kl.right_hand_sides(bench), kl.starts(bench)
+    worst = 0.
+    for form in ('D4', 'D4t'):
+        prob = probs[form] if form in probs else \
+            kl.Problem(bench, kl.ALL_FORMS[form])
+        for rhs, start in kl.CASES[:2]:
+            args = (prob, rhs_of[rhs], start_of[start], kl.LAZY, 2)
+            key = kl.gmres_key(form, rhs, start, 2, kl.LAZY)
+            worst = max(worst, excess(
+                golden_dist, key, kl.gmres_cycles(*args, mut=mut),
+                kl.gmres_cycles(*args), prob.NV, range(1, 7)))
+    print('    %-14s error / tol %.1e' % (mut, worst))
+    assert worst >= 100.
+
+
 if __name__ == '__main__':
     # no argument: write the golden file and print the table (five minutes);
     # `--check`: recompute ALL of it and compare with the file instead
+    # `--dist`: the second file (`krylov_dist_tol.npz`, two minutes) alone
     import scenarios
     bench_ = kl.toy_bench(scenarios.toy_problem())
-    tab_ = kl.tolerance_table(bench_, log=lambda k: print(k, flush=True))
     here = os.path.dirname(os.path.abspath(__file__))
+    if '--dist' in sys.argv:
+        tab_ = kl.dist_tolerance_table(bench_,
+                                       log=lambda k: print(k, flush=True))
+        np.savez_compressed(os.path.join(here, 'golden', kl.GOLDEN_DIST),
+                            **tab_)
+        for line_ in table_lines(tab_):
+            print(line_)
+        sys.exit(0)
+    tab_ = kl.tolerance_table(bench_, log=lambda k: print(k, flush=True))
     path_ = os.path.join(here, 'golden', kl.GOLDEN)
     if '--check' in sys.argv:
         old_ = dict(np.load(path_))
