@@ -367,6 +367,10 @@ SIGNATURES = {
     'dns_conv_set_base_rows': (ct.c_int, [_VP, ct.c_int32, c_int32_p]),
     'dns_conv_set_base_row': (ct.c_int, [_VP, ct.c_int32]),
     'dns_conv_get_base_info': (ct.c_int, [_VP, c_int32_p, c_int32_p]),
+    'dns_conv_set_base_rows_lerp': (ct.c_int, [_VP, ct.c_int32, c_int32_p,
+                                               c_double_p]),
+    'dns_conv_set_base_row_lerp': (ct.c_int, [_VP, ct.c_int32, ct.c_double]),
+    'dns_conv_get_base_lerp': (ct.c_int, [_VP, c_int32_p]),
     'dns_imex_ensemble_to_base': (ct.c_int, [_VP, ct.c_int32, ct.c_int32, _VP,
                                              ct.c_int32, c_double_p,
                                              ct.c_int32]),

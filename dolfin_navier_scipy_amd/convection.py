@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _capi as C
 
-__all__ = ['ConvectionP2', 'BaseTrajectory']
+__all__ = ['ConvectionP2', 'BaseTrajectory', 'lerp_rows']
 
 ROM_MAX_BASIS = 33          # kRomMaxBasis of csrc/galerkin_host.hpp
 
@@ -55,10 +55,20 @@ def check_basis(nv, ndbc, basis, dbc_rows=None, ntest=None):
 TIME_ATOL = 1e-8
 
 
+def lerp_rows(v0, v1, theta):
+    """`v0 + theta*(v1 - v0)`, each operation rounded once: the base flow an
+    interpolating operator evaluates about, bit for bit (the device does the
+    same three operations, uncontracted)"""
+    v0 = np.asarray(v0, dtype=np.float64)
+    return v0 + np.float64(theta)*(np.asarray(v1, dtype=np.float64) - v0)
+
+
 class BaseTrajectory(object):
     """A time-varying base flow for `ConvectionP2.set_base_flow`: `m` stored
-    flows and their times, held piecewise constant (zero-order hold, no
-    interpolation).
+    flows and their times, held piecewise constant (zero-order hold) or, with
+    `interpolate=True`, interpolated linearly between the stored times
+    (`weights_at`; the loops of `time_int_utils` then arm weights beside the
+    rows).
 
     `times`: `m` ascending stored times.  `v_rows`: `(m, nv)` inner values or
     `(m, vdim)` full velocity vectors (`None`: the rows are on the device
@@ -66,9 +76,12 @@ class BaseTrajectory(object):
     Dirichlet values, `(ndbc,)` for every row or `(m, ndbc)` (`None` with full
     vectors: taken from them).  `time_map`: loop time -> stored time, the
     identity by default; `lambda t: T - t` makes an adjoint run walk a stored
-    forward run backwards."""
+    forward run backwards.  `interpolate`: a flow stored every k-th step is
+    a second-order representation of `V(t)` instead of a first-order one, at
+    the price of a second gather in the element kernels."""
 
-    def __init__(self, times, v_rows, dbcvals=None, time_map=None):
+    def __init__(self, times, v_rows, dbcvals=None, time_map=None,
+                 interpolate=False):
         t = np.array(times, dtype=np.float64).reshape(-1)
         if t.size < 1 or not np.all(np.isfinite(t)) \
                 or np.any(np.diff(t) <= TIME_ATOL):
@@ -85,10 +98,62 @@ class BaseTrajectory(object):
             np.asarray(dbcvals, dtype=np.float64)
         # one stored flow holds for good; else a row holds for one interval
         self.hold = np.inf if t.size == 1 else t[-1] - t[-2]
+        self.interpolate = bool(interpolate)
 
     @property
     def nrows(self):
         return self.times.size
+
+    def _stored_time(self, t):
+        """`(time_map(t), how the refusals name the time)`"""
+        tm = float(t) if self.time_map is None \
+            else float(self.time_map(float(t)))
+        what = 'time {0!r}'.format(float(t)) + (
+            '' if self.time_map is None
+            else ' (stored time {0!r})'.format(tm))
+        return tm, what
+
+    def weights_at(self, ts):
+        """`(rows, theta)` for linear interpolation: `rows` as `rows_at`,
+        `theta = (tm - t_r)/(t_{r+1} - t_r)` in `[0, 1)` with `tm =
+        time_map(t)` -- exactly 0.0 within `TIME_ATOL` of a stored time (a
+        time that close to the NEXT stored time is that row with weight 0).
+        No extrapolation: `ValueError`, by the time, before the first stored
+        time and more than `TIME_ATOL` behind the last (the one-interval hold
+        of `rows_at` does not apply)"""
+        rows = np.empty(len(ts), dtype=np.int32)
+        theta = np.zeros(len(ts))
+        times = self.times
+        for k, t in enumerate(ts):
+            tm, what = self._stored_time(t)
+            r = int(np.searchsorted(times, tm + TIME_ATOL, side='right')) - 1
+            if r < 0 or not np.isfinite(tm):
+                raise ValueError(
+                    'base trajectory: {0} lies before the first stored time '
+                    '{1!r}'.format(what, float(times[0])))
+            rows[k] = r
+            if abs(tm - times[r]) <= TIME_ATOL:
+                continue
+            if r + 1 >= times.size:
+                raise ValueError(
+                    'base trajectory: {0} lies behind the last stored time '
+                    '{1!r}: interpolation between stored rows does not '
+                    'extrapolate'.format(what, float(times[-1])))
+            th = (tm - times[r])/(times[r + 1] - times[r])
+            theta[k] = min(max(th, 0.0), np.nextafter(1.0, 0.0))
+        return rows, theta
+
+    def flow_at(self, time):
+        """the row of `v_rows` the operator evaluates about at loop time
+        `time` -- held, or with `interpolate` `lerp_rows` of the two rows: the
+        host statement of a step is `fem.TaylorHood.linearised_convection_vec`
+        about this vector"""
+        if not self.interpolate:
+            return self.v_rows[self.row_at(time)]
+        rows, th = self.weights_at([time])
+        r = int(rows[0])
+        return lerp_rows(self.v_rows[r],
+                         self.v_rows[min(r + 1, self.nrows - 1)], th[0])
 
     def row_at(self, time):
         return int(self.rows_at([time])[0])
@@ -215,7 +280,8 @@ class ConvectionP2(object):
         `base` may be a `BaseTrajectory`: a time-varying base flow, uploaded
         once.  `set_base_rows` then names the row of every step of an attached
         loop, `set_base_row` the row for `apply`; `cnab` / `sbdftwo` arm both
-        from the trajectory's times"""
+        from the trajectory's times -- with the weights towards the next row
+        when the trajectory was made with `interpolate=True`"""
         if isinstance(base, BaseTrajectory):
             return self._set_base_trajectory(base, adjoint)
         if isinstance(base, (tuple, list)) and len(base) == 2:
@@ -250,19 +316,51 @@ class ConvectionP2(object):
             int(rows.shape[1]), int(sets), C.dptr(dflat), int(bool(adjoint))))
         self.base_trajectory = traj
 
-    def set_base_rows(self, rows):
+    def set_base_rows(self, rows, weights=None):
         """the per-step index table of a base trajectory: the `s`-th step of
         the chunk an attached stepper runs next evaluates about row
         `rows[min(s, len(rows) - 1)]` (descending: a reversed adjoint run;
-        repeats: a trajectory stored every k-th step)"""
+        repeats: a trajectory stored every k-th step).  `weights`: one
+        `theta` in `[0, 1)` per entry, the step evaluates about `V_r +
+        theta*(V_{r+1} - V_r)` (`lerp_rows`, bit for bit); `None`: the
+        zero-order hold, which also takes weights off that were set.
+        `ValueError`, the operator as it was: weights outside `[0, 1)` or not
+        finite, a non-zero weight on the last row, another length than
+        `rows`"""
         r = _i32(np.asarray(rows).reshape(-1))
-        C.check(self.lib.dns_conv_set_base_rows(
-            self._h, int(r.size), r.ctypes.data_as(C.c_int32_p)))
+        if weights is None:
+            C.check(self.lib.dns_conv_set_base_rows(
+                self._h, int(r.size), r.ctypes.data_as(C.c_int32_p)))
+            return
+        w = np.ascontiguousarray(
+            np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w.size != r.size:
+            raise ValueError(
+                'base trajectory: {0} interpolation weights for {1} base '
+                'rows, one per entry'.format(w.size, r.size))
+        C.check(self.lib.dns_conv_set_base_rows_lerp(
+            self._h, int(r.size), r.ctypes.data_as(C.c_int32_p),
+            C.dptr(w if w.size else np.zeros(1))))
 
-    def set_base_row(self, row):
+    def set_base_row(self, row, weight=0.0):
         """the row of the base trajectory `apply`, `cell_values` and
-        `host_callback` evaluate about (takes the index table off)"""
-        C.check(self.lib.dns_conv_set_base_row(self._h, int(row)))
+        `host_callback` evaluate about (takes the index table off); with a
+        non-zero `weight` in `(0, 1)`, between that row and the next.  Weight
+        0.0 is the row itself: the zero-order entry point, which takes the
+        weights off"""
+        if weight == 0.0:
+            C.check(self.lib.dns_conv_set_base_row(self._h, int(row)))
+        else:
+            C.check(self.lib.dns_conv_set_base_row_lerp(
+                self._h, int(row), float(weight)))
+
+    @property
+    def interpolates(self):
+        """True while interpolation weights are armed (`set_base_rows` with
+        `weights`, `set_base_row` with a non-zero `weight`)"""
+        lerp = ct.c_int32(0)
+        C.check(self.lib.dns_conv_get_base_lerp(self._h, ct.byref(lerp)))
+        return bool(lerp.value)
 
     @property
     def base_trajectory_rows(self):

@@ -243,26 +243,53 @@ int dns_conv_set_base_trajectory(dns_conv *cv, int32_t nrows,
 } DNS_CAPI_CATCH
 
 // The per-step index table: step s of the chunk an attached stepper runs next
-// (its counter) evaluates about row rows[min(s, n - 1)]
-int dns_conv_set_base_rows(dns_conv *cv, int32_t n, const int32_t *rows) try {
-    if (!cv) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
-    DNS_TRY(dns::check_base_rows(n, rows, cv->bt_rows));
+// (its counter) evaluates about row rows[min(s, n - 1)] -- with `weights`,
+// between that row and the next.  The caller has checked the table.
+static int set_base_table(dns_conv *cv, int32_t n, const int32_t *rows,
+                          const double *weights) {
     DNS_HIP(hipSetDevice(cv->device));
     DNS_HIP(hipDeviceSynchronize());           // replays may still read it
-    if (cv->brow.n < (size_t)n) {
-        DevBuf<int> tab;
-        DNS_TRY(tab.alloc((size_t)n));
+    // (whatever can run out of memory comes before the first change)
+    DevBuf<int> tab;
+    DevBuf<double> wtab;
+    if (cv->brow.n < (size_t)n) DNS_TRY(tab.alloc((size_t)n));
+    if (weights && cv->bwgt.n < (size_t)n) DNS_TRY(wtab.alloc((size_t)n));
+    if (tab.p) {
         std::swap(cv->brow.p, tab.p);
         std::swap(cv->brow.n, tab.n);
     }
+    if (wtab.p) {
+        std::swap(cv->bwgt.p, wtab.p);
+        std::swap(cv->bwgt.n, wtab.n);
+    }
     cv->nbrow = 0;                             // (until the table is there)
     cv->bt_ctr = nullptr;
+    cv->bt_lerp = false;
+    cv->bt_weight = 0.0;
     cv->dbc_gen++;
     DNS_TRY(cv->brow.upload(rows, (size_t)n, nullptr));
+    if (weights) DNS_TRY(cv->bwgt.upload(weights, (size_t)n, nullptr));
     cv->nbrow = n;
     cv->bt_row = rows[0];
+    if (weights) {
+        cv->bt_lerp = true;
+        cv->bt_weight = weights[0];
+    }
     cv->brow_gen++;
     return DNS_OK;
+}
+
+int dns_conv_set_base_rows(dns_conv *cv, int32_t n, const int32_t *rows) try {
+    if (!cv) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(dns::check_base_rows(n, rows, cv->bt_rows));
+    return set_base_table(cv, n, rows, nullptr);
+} DNS_CAPI_CATCH
+
+int dns_conv_set_base_rows_lerp(dns_conv *cv, int32_t n, const int32_t *rows,
+                                const double *weights) try {
+    if (!cv) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(dns::check_base_rows_lerp(n, rows, weights, cv->bt_rows));
+    return set_base_table(cv, n, rows, weights);
 } DNS_CAPI_CATCH
 
 // The row for dns_conv_apply and the probes outside a stepper -- and, since it
@@ -273,7 +300,28 @@ int dns_conv_set_base_row(dns_conv *cv, int32_t row) try {
     cv->bt_row = row;
     cv->nbrow = 0;
     cv->bt_ctr = nullptr;
+    cv->bt_lerp = false;
+    cv->bt_weight = 0.0;
     cv->dbc_gen++;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+// ... between that row and the next: V_row + weight (V_{row+1} - V_row)
+int dns_conv_set_base_row_lerp(dns_conv *cv, int32_t row, double weight) try {
+    if (!cv) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    DNS_TRY(dns::check_base_row_lerp(row, weight, cv->bt_rows));
+    cv->bt_row = row;
+    cv->nbrow = 0;
+    cv->bt_ctr = nullptr;
+    cv->bt_lerp = true;
+    cv->bt_weight = weight;
+    cv->dbc_gen++;
+    return DNS_OK;
+} DNS_CAPI_CATCH
+
+int dns_conv_get_base_lerp(const dns_conv *cv, int32_t *lerp) try {
+    if (!cv || !lerp) return fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    *lerp = cv->bt_lerp ? 1 : 0;
     return DNS_OK;
 } DNS_CAPI_CATCH
 

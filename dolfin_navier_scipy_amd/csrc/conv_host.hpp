@@ -2,8 +2,8 @@
 // conv_capi.inc): the expansion of a base flow into the twelve slots of every
 // cell, the layout and the index table of a base trajectory and what the
 // adjoint mode asks of the Dirichlet values.  No HIP in here:
-// tests/conv_lin_host_sanitize.cpp and tests/conv_traj_host_sanitize.cpp
-// exercise it on the host alone.
+// tests/conv_lin_host_sanitize.cpp, tests/conv_traj_host_sanitize.cpp and
+// tests/conv_interp_host_sanitize.cpp exercise it on the host alone.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -135,6 +135,46 @@ inline int check_base_row(int row, int nrows) {
                     "linearised convection: base row %d outside 0..%d (the "
                     "rows of the base trajectory)", row, nrows - 1);
     return DNS_OK;
+}
+
+// ---- linear interpolation between row r and row r + 1 -----------------------
+// One weight beside every entry of the index table (or beside the named row):
+// the element kernels evaluate about V_r + th (V_{r+1} - V_r).  A weight is
+// finite and lies in [0, 1) -- th = 1 is row r + 1 with weight 0 --, and a
+// non-zero weight needs the row behind its own.
+inline int check_base_weight(int entry, int row, double weight, int nrows) {
+    // (entry < 0: the single host-named row)
+    char where[48];
+    if (entry >= 0) snprintf(where, sizeof where, "base rows: entry %d", entry);
+    else snprintf(where, sizeof where, "base row %d", row);
+    if (!(weight >= 0.0 && weight < 1.0))    // (a NaN fails both comparisons)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: %s has the interpolation weight "
+                    "%.17g, outside [0, 1)", where, weight);
+    if (weight != 0.0 && (long)row + 1 >= (long)nrows)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: %s: the interpolation weight "
+                    "%.17g on row %d, the last of the %d rows of the base "
+                    "trajectory (no row %ld to interpolate towards)", where,
+                    weight, row, nrows, (long)row + 1);
+    return DNS_OK;
+}
+
+inline int check_base_rows_lerp(int n, const int32_t *rows,
+                                const double *weights, int nrows) {
+    DNS_TRY(check_base_rows(n, rows, nrows));
+    if (!weights)
+        return fail(DNS_ERR_BAD_ARGUMENT,
+                    "linearised convection: base rows: %d entries without "
+                    "their interpolation weights", n);
+    for (int s = 0; s < n; ++s)
+        DNS_TRY(check_base_weight(s, rows[s], weights[s], nrows));
+    return DNS_OK;
+}
+
+inline int check_base_row_lerp(int row, double weight, int nrows) {
+    DNS_TRY(check_base_row(row, nrows));
+    return check_base_weight(-1, row, weight, nrows);
 }
 
 // slots [first, first + count) of an ensemble of `nslots` slots

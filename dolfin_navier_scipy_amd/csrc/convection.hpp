@@ -408,12 +408,22 @@ conv_lin_values(int q, const double (&gl)[3][2], const double (&wl)[6][2],
 //               counter of the stepper the operator is attached to, or the
 //               row the host names (`ctr` null).  Zero-order hold: nothing is
 //               rounded, the values are those of BaseCells about that row.
+//   BaseTrajLerp : between row r and its partner p = min(r + 1, nrows - 1) of
+//               the same trajectory, with a weight th in [0, 1) from a table
+//               of doubles as long as `brow`, read through the same clamped
+//               counter (or the weight the host names beside its row).  Every
+//               gathered dof, inner or Dirichlet, is
+//                   V_r + th * (V_p - V_r)
+//               in three separately rounded operations (`base_lerp_at`):
+//               NumPy's `V0 + th*(V1 - V0)` bit for bit.
 struct BaseCells {
     static constexpr bool kTrajectory = false;
+    static constexpr bool kLerp = false;
     const double *vbase;
 };
 struct BaseTraj {
     static constexpr bool kTrajectory = true;
+    static constexpr bool kLerp = false;
     const double *V, *Vd;
     const int *ctr, *brow;
     int nbrow, row, nrows, dstride;
@@ -435,6 +445,49 @@ __device__ __forceinline__ double base_traj_at(const BaseTraj &b, int r, int m) 
     return (m >= 0) ? b.V[(size_t)r * b.ldv + m]
                     : b.Vd[(size_t)r * b.dstride + (-m - 1)];
 }
+struct BaseTrajLerp {
+    static constexpr bool kTrajectory = true;
+    static constexpr bool kLerp = true;
+    BaseTraj t;
+    const double *bwgt;          // [nbrow] weights, beside t.brow
+    double weight;               // the host-named weight (t.ctr null)
+};
+struct LerpRow {
+    int r, p;
+    double th;
+};
+// The weight is asked for beside the table entry, both behind the counter
+// alone: the two gathers of V wait for the same one round trip more than the
+// gather of w, not for two.  (r, p and th are the same in every thread.)
+__device__ __forceinline__ LerpRow base_lerp_row(const BaseTrajLerp &b) {
+    int r = b.t.row;
+    double th = b.weight;
+    if (b.t.ctr) {
+        int i = *b.t.ctr;
+        i = i < 0 ? 0 : (i >= b.t.nbrow ? b.t.nbrow - 1 : i);
+        r = b.t.brow[i];
+        th = b.bwgt[i];
+    }
+    r = r < 0 ? 0 : (r >= b.t.nrows ? b.t.nrows - 1 : r);
+    const int p = r + 1 < b.t.nrows ? r + 1 : b.t.nrows - 1;
+    return {r, p, th};
+}
+// (both rows are loaded whatever the weight: th == 0 gives V_r + 0 * d, which
+// is V_r for every finite d and every V_r but -0.0, and the formula is the
+// contract)
+__device__ __forceinline__ double base_lerp_at(const BaseTrajLerp &b,
+                                               const LerpRow &lr, int m) {
+#pragma clang fp contract(off)
+    const double v0 = base_traj_at(b.t, lr.r, m);
+    const double v1 = base_traj_at(b.t, lr.p, m);
+    // = __dadd_rn(v0, __dmul_rn(th, __dsub_rn(v1, v0))), written with the
+    // operators: the pragma above reaches them, while HIP's __d*_rn are plain
+    // `x * y` / `x + y` compiled under the default contraction, and the
+    // backend fused the product into the sum (v_fmac_f64) across them
+    const double d = v1 - v0;
+    const double td = lr.th * d;
+    return v0 + td;
+}
 
 // Eight lanes per cell, the sibling of conv_cells_block_to: lane q fetches dof
 // slots q and q + 8 of w (map entry, then the value) and of V (BaseCells:
@@ -452,7 +505,9 @@ conv_lin_cells_block_to(int bid, int ncells,
 #pragma clang fp contract(off)
     const double *__restrict__ dbcvals = tab_row(dbctab);
     int brow = 0;
-    if constexpr (BASE::kTrajectory) brow = base_traj_row(base);
+    LerpRow lrow{0, 0, 0.0};
+    if constexpr (BASE::kLerp) lrow = base_lerp_row(base);
+    else if constexpr (BASE::kTrajectory) brow = base_traj_row(base);
     const int t = bid * kBlock + threadIdx.x;
     const int slot = t >> 3;
     const int q = t & 7;
@@ -464,7 +519,10 @@ conv_lin_cells_block_to(int bid, int ncells,
     const int m_a = cellmap[(size_t)q * ncells + cc];
     const int m_b = (q < 4) ? cellmap[(size_t)(q + 8) * ncells + cc] : -1;
     double V_a, V_b;
-    if constexpr (BASE::kTrajectory) {
+    if constexpr (BASE::kLerp) {
+        V_a = base_lerp_at(base, lrow, m_a);
+        V_b = (q < 4) ? base_lerp_at(base, lrow, m_b) : 0.0;
+    } else if constexpr (BASE::kTrajectory) {
         V_a = base_traj_at(base, brow, m_a);
         V_b = (q < 4) ? base_traj_at(base, brow, m_b) : 0.0;
     } else {
@@ -536,7 +594,9 @@ k_conv_lin_cells_lane(int ncells, const int *__restrict__ cellmap,
 #pragma clang fp contract(off)
     const double *__restrict__ dbcvals = tab_row(dbctab);
     int brow = 0;
-    if constexpr (BASE::kTrajectory) brow = base_traj_row(base);
+    LerpRow lrow{0, 0, 0.0};
+    if constexpr (BASE::kLerp) lrow = base_lerp_row(base);
+    else if constexpr (BASE::kTrajectory) brow = base_traj_row(base);
     const int slot = blockIdx.x * kBlock + threadIdx.x;
     const bool live = sel ? slot < nsel : slot < ncells;
     if (!live) return;
@@ -545,7 +605,11 @@ k_conv_lin_cells_lane(int ncells, const int *__restrict__ cellmap,
 #pragma unroll
     for (int k = 0; k < 12; ++k) m[k] = cellmap[(size_t)k * ncells + c];
     double Vl[6][2];
-    if constexpr (BASE::kTrajectory) {
+    if constexpr (BASE::kLerp) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+            Vl[k >> 1][k & 1] = base_lerp_at(base, lrow, m[k]);
+    } else if constexpr (BASE::kTrajectory) {
 #pragma unroll
         for (int k = 0; k < 12; ++k)
             Vl[k >> 1][k & 1] = base_traj_at(base, brow, m[k]);
@@ -727,11 +791,25 @@ struct dns_conv {
                 bt_row, bt_rows, dns::base_traj_dbc_stride(bt_dbc_rows, ndbc),
                 dns::base_traj_ldv(nv_inner)};
     }
+    // Linear interpolation between row r and row r + 1 (dns_conv_set_base_rows_
+    // lerp, dns_conv_set_base_row_lerp): `bwgt`, one weight in [0, 1) beside
+    // every entry of `brow`, or `bt_weight` beside `bt_row`.  `bt_lerp` picks
+    // the interpolating instances of the element kernels; the setters without
+    // weights take it off again.
+    dns::DevBuf<double> bwgt;
+    bool bt_lerp = false;
+    double bt_weight = 0.0;
+    dns::BaseTrajLerp base_traj_lerp() const {
+        return {base_traj(), bwgt.p, bt_weight};
+    }
     void release_base_trajectory() {
         btraj.release();
         btraj_dbc.release();
         brow.release();
+        bwgt.release();
         bt_rows = bt_dbc_rows = nbrow = bt_row = 0;
+        bt_lerp = false;
+        bt_weight = 0.0;
         bt_ctr = nullptr;
     }
     // The rows `T` (nrows x ldv, on the device by the time `s` has run) take
@@ -1362,7 +1440,8 @@ struct dns_conv_mat {
 inline dns_conv::~dns_conv() { delete mat; }
 
 // the element launch of a linearised operator: mode x regime, four kernels,
-// each with the constant base flow or a row of the base trajectory behind it
+// each with the constant base flow, a row of the base trajectory or two rows
+// and a weight behind it
 inline int dns_conv::enqueue_lin_cells(const double *w_dev, hipStream_t s,
                                        const int *sel, int nsel) {
     const int live = sel ? nsel : ncells;
@@ -1380,7 +1459,29 @@ inline int dns_conv::enqueue_lin_cells(const double *w_dev, hipStream_t s,
                        sel, nsel)
     const int g1 = (live + dns::kBlock - 1) / dns::kBlock;
     const int g8 = (8 * live + dns::kBlock - 1) / dns::kBlock;
-    if (traj) {
+    if (traj && bt_lerp) {
+        using dns::BaseTrajLerp;
+        if (nbrow > 0 && bwgt.n < (size_t)nbrow)
+            return dns::fail(DNS_ERR_NOT_READY,
+                             "linearised convection operator: interpolation "
+                             "weights shorter than the index table");
+        const BaseTrajLerp bl = base_traj_lerp();
+        if (live >= lane_min) {
+            if (adj)
+                DNS_LIN_LAUNCH((dns::k_conv_lin_cells_lane<true, BaseTrajLerp>),
+                               g1, bl);
+            else
+                DNS_LIN_LAUNCH((dns::k_conv_lin_cells_lane<false, BaseTrajLerp>),
+                               g1, bl);
+        } else {
+            if (adj)
+                DNS_LIN_LAUNCH((dns::k_conv_lin_cells<true, BaseTrajLerp>), g8,
+                               bl);
+            else
+                DNS_LIN_LAUNCH((dns::k_conv_lin_cells<false, BaseTrajLerp>), g8,
+                               bl);
+        }
+    } else if (traj) {
         using dns::BaseTraj;
         const BaseTraj bt = base_traj();
         if (live >= lane_min) {

@@ -24,6 +24,12 @@ uint64_t dns_imex::config_key(const dns_imex_coeffs *cf) const {
         k = mix64(k, {kw(conv->btraj.p), kw(conv->btraj_dbc.p),
                       kw(conv->bt_rows + 2 * (conv->bt_dbc_rows > 1)),
                       kw(conv->brow.p), kw(conv->nbrow), kw(conv->bt_row)});
+    // (interpolating between its rows: another instance of the element
+    // kernels, with the weight table, its length and the host-named weight
+    // among its arguments)
+    if (conv && conv->linearised() && conv->bt_rows > 0 && conv->bt_lerp)
+        k = mix64(k, {kw(1), kw(conv->bwgt.p), kw(conv->bwgt.n),
+                      kw(conv->nbrow), kw(conv->bt_weight)});
     return attachments_key(k);
 }
 

@@ -1063,7 +1063,8 @@ class ImexStepper(object):
         return out
 
     def ensemble_to_base(self, conv, times=None, first=0, count=None,
-                         dbcvals=None, adjoint=False, time_map=None):
+                         dbcvals=None, adjoint=False, time_map=None,
+                         interpolate=False):
         """slots `first .. first + count` of the ensemble (default: all from
         `first` on) become the base trajectory of the linearised operator
         `conv` (`ConvectionP2.set_base_flow` of a `BaseTrajectory`), device to
@@ -1073,7 +1074,9 @@ class ImexStepper(object):
         thing that crosses the bus.  With `times` (one per slot, ascending;
         `time_map` as in `BaseTrajectory`) the operator gets the trajectory's
         clock as well, so that `cnab` / `sbdftwo` arm its rows; without, name
-        them with `conv.set_base_rows` / `set_base_row`.  Refused by name
+        them with `conv.set_base_rows` / `set_base_row`.  `interpolate`: as in
+        `BaseTrajectory`, the loops arm weights beside the rows (slots kept
+        `every=k` then stand for a flow that moves every step).  Refused by name
         (`ValueError`): no ensemble, slots out of range, another device,
         another number of inner dofs"""
         from .convection import BaseTrajectory
@@ -1082,7 +1085,8 @@ class ImexStepper(object):
             count = (nslots if nslots is not None else 0) - int(first)
         count = int(count)
         traj = BaseTrajectory(np.arange(count) if times is None else times,
-                              None, dbcvals, time_map=time_map) \
+                              None, dbcvals, time_map=time_map,
+                              interpolate=interpolate) \
             if count >= 1 else None
         if traj is not None and traj.nrows != count:
             raise ValueError('base trajectory: {0} `times` for {1} slots'

@@ -898,6 +898,33 @@ _SBDF2 = _Scheme(
     keep_prev=True, state_v_p=True, guard_prev=True)
 
 
+# A base trajectory (`convection.BaseTrajectory`) names the row of every time
+# convection is evaluated at -- with `interpolate`, the row and the weight
+# towards the next one.  The three places that arm it: the coverage check
+# before the loop, a chunk's table, and a single time (Heun start, host step).
+def _base_rows_at(traj, ts):
+    """`(rows, weights or None)`; `ValueError` by the time not covered"""
+    if getattr(traj, 'interpolate', False):
+        return traj.weights_at(ts)
+    return traj.rows_at(ts), None
+
+
+def _arm_base_rows(conv, traj, ts):
+    rows, weights = _base_rows_at(traj, ts)
+    if weights is None:
+        conv.set_base_rows(rows)
+    else:
+        conv.set_base_rows(rows, weights)
+
+
+def _arm_base_row(conv, traj, time):
+    rows, weights = _base_rows_at(traj, [time])
+    if weights is None:
+        conv.set_base_row(int(rows[0]))
+    else:
+        conv.set_base_row(int(rows[0]), float(weights[0]))
+
+
 class _ImexLoop(object):
     """The AB2 / BDF2 steps of `cnab` and `sbdftwo` behind the Heun start: how
     `resident=` is read, the terms of the last two times (`prev`, `cur`) and
@@ -1105,7 +1132,7 @@ class _ImexLoop(object):
             elif moving:
                 self.conv.set_dbc_table(dbt[a:b])
             if self.traj is not None:
-                self.conv.set_base_rows(self.traj.rows_at(t_cur[a:b]))
+                _arm_base_rows(self.conv, self.traj, t_cur[a:b])
             tables = _Tables(dbt[a:b + 1] if moving else None)
             for att in self.attachments:
                 att.arm(ctrange[a:b], tables)
@@ -1154,7 +1181,7 @@ class _ImexLoop(object):
         if conv is not None and (self.moving or self.statvals):
             conv.set_dbcvals(self._dbc(cur))
         if conv is not None and self.traj is not None:
-            conv.set_base_row(self.traj.row_at(self.t_n))
+            _arm_base_row(conv, self.traj, self.t_n)
         nfc_new = None if conv is not None \
             else self.f_vdp(self.appndbcs(v_c, cur.bcs))
         nxt, gp = self._terms_at(ctime, v_c, p_c)
@@ -1356,10 +1383,10 @@ def _imex_loop(scheme, trange, inivel, inip, bcs_ini, M, A, J, f_vdp, f_tdp,
     traj = getattr(device_convection, 'base_trajectory', None)
     base_row = None
     if traj is not None:
-        traj.rows_at(trange[:-1])
+        _base_rows_at(traj, trange[:-1])
 
         def base_row(time):
-            device_convection.set_base_row(traj.row_at(time))
+            _arm_base_row(device_convection, traj, time)
     if device_convection is not None and f_vdp is None:
         f_vdp = device_convection.host_callback(invinds)   # Heun start only
     dynamic_rhs, f_vdp = _wrap_callbacks(NV, dynamic_rhs, f_tvdp, f_vdp)

@@ -881,8 +881,8 @@ int dns_conv_get_mode(const dns_conv *cv, int32_t *mode);
  * dbc_nrows == nrows: row-major nrows x ndbc.  One upload; V is gathered
  * through the cell map as the perturbation is.  Modes, the perturbation's own
  * Dirichlet values and every refusal are those of dns_conv_set_base_flow.
- * Which row an element launch evaluates about (zero-order hold, no
- * interpolation):
+ * Which row an element launch evaluates about (zero-order hold; the _lerp
+ * forms below interpolate between two rows):
  *   dns_conv_set_base_rows  a per-step index table of n entries, each in
  *                           0..nrows-1 (anything else is refused by name before
  *                           anything is uploaded): the s-th step of the
@@ -905,6 +905,30 @@ int dns_conv_set_base_trajectory(dns_conv *cv, int32_t nrows,
 int dns_conv_set_base_rows(dns_conv *cv, int32_t n, const int32_t *rows);
 int dns_conv_set_base_row(dns_conv *cv, int32_t row);
 int dns_conv_get_base_info(const dns_conv *cv, int32_t *nrows, int32_t *nbrow);
+/* Linear interpolation between the stored rows: with a weight th beside a row
+ * r the element launches evaluate, for every dof they gather (inner values and
+ * the base flow's Dirichlet values alike), about
+ *   V = V_r + th * (V_p - V_r),   p = min(r + 1, nrows - 1),
+ * three separately rounded fp64 operations (subtract, multiply, add; no
+ * contraction) -- NumPy's V0 + th*(V1 - V0) bit for bit.
+ *   dns_conv_set_base_rows_lerp  the index table of dns_conv_set_base_rows and
+ *                           n weights beside it, read through the same clamped
+ *                           step counter (rows[min(s, n - 1)] with
+ *                           weights[min(s, n - 1)]); outside a stepper rows[0]
+ *                           with weights[0].  The attached stepper counts from
+ *                           0 again as after dns_conv_set_base_rows
+ *   dns_conv_set_base_row_lerp   one row and one weight the host names; takes
+ *                           the index table off
+ * Refused by name before anything is uploaded, the operator left as it was: a
+ * weight that is not finite or outside [0, 1) (th = 1 is row r + 1 with weight
+ * 0), a non-zero weight on the last row, weights without a trajectory, a null
+ * table.  All-zero weights give the bits of the zero-order hold.
+ * dns_conv_set_base_rows / _set_base_row keep their meaning and take the
+ * weights off; dns_conv_get_base_lerp: 1 while weights are armed, else 0 */
+int dns_conv_set_base_rows_lerp(dns_conv *cv, int32_t n, const int32_t *rows,
+                                const double *weights);
+int dns_conv_set_base_row_lerp(dns_conv *cv, int32_t row, double weight);
+int dns_conv_get_base_lerp(const dns_conv *cv, int32_t *lerp);
 /* ... adopted from the snapshot ensemble of a stepper (dns_imex_set_ensemble):
  * slots first .. first + count - 1 become rows 0 .. count - 1, copied device to
  * device on the stepper's stream; only dbc_vals (as above, dbc_nrows 1 or

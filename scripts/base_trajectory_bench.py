@@ -19,6 +19,14 @@ rotating with the repeat:
         entry names the row of variant c -- the run of c, bit for bit, through
         the trajectory instance of the element kernel: what that instance
         costs in the loop)
+  h<k>  (`--lerp k`) the resident loop about a trajectory STORED every k-th
+        step (every k-th slot, uploaded), the row of the last stored time held
+        -- a<k> with the trajectory a user who stores every k-th step has
+  i<k>  the same trajectory interpolated linearly between its rows (weights
+        beside the index table): a base flow that moves a little every step
+  z<k>  the tables of h<k> with all-zero weights: the run of h<k> bit for bit
+        through the interpolating instance of the element kernel (two gathers
+        of V) -- what that instance costs in the loop
   b     what had to be done before: one `set_base_flow` per step (the slot's
         row from a host copy of the ensemble) and `run(1)`, `--steps-b` steps,
         wall clock; with the loops' solver options (captured graphs: every
@@ -94,7 +102,8 @@ def run_repeat(su, args, rep):
             out.append(dict(variant='adopt', mode=mode, nslots=nslots,
                             bytes=int(E.nbytes), d2d_seconds=t_d2d,
                             upload_seconds=t_h2d))
-            order = ['a%d' % k for k in args.strides] + ['b', 'b0', 'c']
+            order = ['a%d' % k for k in args.strides] + ['b', 'b0', 'c'] \
+                + ['%s%d' % (v, k) for k in args.lerp for v in 'hiz']
             order = order[rep % len(order):] + order[:rep % len(order)]
             nograph = type(lopts).from_buffer_copy(lopts)
             nograph.use_graph = 0
@@ -104,7 +113,30 @@ def run_repeat(su, args, rep):
                     cv.set_base_flow(base, adjoint=adj)
                     nfc0 = cv.apply(w0, scale=-1.0)
                     lin.set_state(w0, nfc_c=nfc0, nfc_o=nfc0)
-                if variant.startswith('a'):
+                if variant[0] in 'hiz':
+                    # every k-th slot stored (uploaded: the ensemble's slots
+                    # are contiguous), the position moving with every step
+                    k = int(variant[1:])
+                    Ek = E[::k]
+                    span = k*(Ek.shape[0] - 1)
+                    cv.set_base_flow(convection.BaseTrajectory(
+                        np.arange(Ek.shape[0]), Ek, dbv), adjoint=adj)
+                    pos = [(span - n % span) if adj else n % span
+                           for n in range(args.spin + 3*steps)]
+                    rows = [p//k for p in pos]
+                    wts = None if variant[0] == 'h' else \
+                        [((p % k)/float(k) if variant[0] == 'i' else 0.0)
+                         for p in pos]
+                    cv.set_base_row(rows[0], 0.0 if wts is None else wts[0])
+                    nfc0 = cv.apply(w0, scale=-1.0)
+                    lin.set_state(w0, nfc_c=nfc0, nfc_o=nfc0)
+                    cv.set_base_rows(rows, wts)
+                    lin.run(args.spin, lcf, lopts)
+                    secs, its, n = rb._timed_window(lin, lcf, lopts, steps)
+                    rec = rb._record(lin, steps, secs, its)
+                    rec.update(windows=n, stored_every=k,
+                               interpolates=bool(cv.interpolates))
+                elif variant.startswith('a'):
                     stride = int(variant[1:])
                     fwd.ensemble_to_base(cv, dbcvals=dbv, adjoint=adj)
                     cv.set_base_row(slot_of(0))
@@ -156,6 +188,9 @@ def main():
     ap.add_argument('--steps', type=int, default=400)
     ap.add_argument('--steps-b', type=int, default=100)
     ap.add_argument('--strides', default='0,1,4')
+    ap.add_argument('--lerp', default='',
+                    help='storage strides k of the variants h<k>, i<k>, z<k>, '
+                         'e.g. 4')
     ap.add_argument('--spin', type=int, default=64)
     ap.add_argument('--skip', default='',
                     help='variants to leave out, e.g. b,b0')
@@ -163,7 +198,8 @@ def main():
     ap.add_argument('--refine', type=int, default=0)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    args.strides = [int(k) for k in args.strides.split(',')]
+    args.strides = [int(k) for k in args.strides.split(',') if k]
+    args.lerp = [int(k) for k in args.lerp.split(',') if k]
     import record_bench as rb
     if args.refine > 0:
         su = rb.RefinedSetup(args.refine)
