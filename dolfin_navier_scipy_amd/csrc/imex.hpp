@@ -1,5 +1,6 @@
 // Device-resident IMEX stepper state (CNAB / SBDF2 inner loops).
 #pragma once
+#include "attach_host.hpp"
 #include "batch_policy.hpp"
 #include "convection.hpp"
 #include "ensemble.hpp"
@@ -164,10 +165,12 @@ struct dns_imex : dns::Ring {
     int fb_launch(hipStream_t s);  // k_lti_step / k_lti_bc_step for the step
                                    // about to run
     uint64_t fb_key() const;
-    // trajectory recorder (record.hpp): k_record_step runs in front of every
-    // step (behind k_lti_step) and once behind the last step of a call; it
-    // writes row `counter - 1`, so a restored batch overwrites its own rows
-    // and the buffers need no checkpoint.  Present = on.
+    // The other five (their place among the nodes: attachments()) run in
+    // front of every step and once behind the last step of a call and work on
+    // row `counter - 1`: a restored batch overwrites its own rows, so their
+    // buffers need no checkpoint (the statistics ADD: see there).  Present = on.
+    //
+    // trajectory recorder (record.hpp): k_record_step.
     struct Recorder {
         int rows = 0;              // steps the slot table / the y log cover
         int Ny = 0, nslots = 0;    // 0: no outputs / no snapshots
@@ -180,29 +183,58 @@ struct dns_imex : dns::Ring {
     std::unique_ptr<Recorder> rec;
     int rec_launch(hipStream_t s); // k_record_step for the state as it stands
     uint64_t rec_key() const;
-    // force functionals (functional.hpp): k_functional_step runs in front of
-    // every step (behind k_lti_step and k_record_step) and once behind the
-    // last step of a call; it writes row `counter - 1` of the log, so a
-    // restored batch overwrites its own rows and the log needs no checkpoint
-    // (with moving Dirichlet values the counter selects their table rows too).
-    // Present = on.
+    // The Dirichlet values of functionals and quadratics: constant (`ndbc` =
+    // 0), a table of their own (`gtab`, `rows` + 1 rows of `ndbc`: the `_bc`
+    // setters) or, `live`, the attached convection operator's table, which
+    // boundary feedback writes (the `_live` setters).
+    struct MovingBc {
+        int ndbc = 0;
+        dns::DevBuf<double> gtab;
+        bool live = false;
+        bool moving() const { return ndbc > 0; }
+        // the table in use (check_step has seen to a live one's shape)
+        struct Table {
+            const double *p;
+            int stride, rows;
+        };
+        Table table(const dns_imex &st, int rows) const {
+            if (live && st.conv)
+                return {st.conv->dbc_tab.p, std::max(1, st.conv->ndbc),
+                        st.conv->dbc_rows};
+            return {gtab.p, ndbc, rows + 1};
+        }
+        uint64_t key(uint64_t k, const dns_imex &st, int rows) const;
+        // a setter's refusals (`const_refusal`: constant values beside a
+        // per-step table on the operator), then its upload
+        static int check_set(const dns_imex &st, const char *noun,
+                             const char *const_refusal, bool moving, bool live,
+                             int ndbc, int rows);
+        int set(bool moving, bool live, int ndbc, int rows,
+                const double *dbc_table, hipStream_t s);
+        // a step's refusals: the operator may have changed since
+        int check_step(const dns_imex &st, int rows, const char *noun,
+                       const char *setter, const char *const_refusal) const;
+    };
+    // Their log: the share of each of `G` workgroups in each of `n` entries of
+    // every row, zeroed when set, summed in index order by the getters.
+    struct ShareLog {
+        dns::DevBuf<double> buf;
+        int G = 1, n = 0, rows = 0;
+        int ensure(int rows, int G, int n, hipStream_t s);
+        int download_sums(dns_imex *st, int first, int count, double *out,
+                          const char *what) const;
+    };
+    // force functionals (functional.hpp): k_functional_step.
     struct Functionals {
-        int nF = 0, G = 1, rows = 0;
+        int nF = 0;
         int ncl = 0;               // listed cells (all functionals)
         double dt = 1.0;
         dns::DevBuf<int> rp, ci;   // the 3 nF (moving: 5 nF) sparse rows
         dns::DevBuf<double> va;    // (k, term)
         dns::DevBuf<int> cptr, cidx;
         dns::DevBuf<double> cw, scale, c0;
-        dns::DevBuf<double> log;   // rows x G x nF
-        // moving Dirichlet values (dns_imex_set_functionals_bc): the table of
-        // their own, (rows + 1) x ndbc; ndbc = 0: constant values
-        int ndbc = 0;
-        dns::DevBuf<double> gtab;
-        bool moving() const { return ndbc > 0; }
-        // dns_imex_set_functionals_live: no table of their own, the rows are
-        // those of the attached convection operator's table (bc_table())
-        bool live = false;
+        ShareLog log;              // rows x G x nF
+        MovingBc bc;               // (moving: the terms cab, cmb are there)
         // the convection operator whose cell order `cidx` refers to (a step
         // with another one attached is refused)
         const dns_conv *conv = nullptr;
@@ -212,13 +244,11 @@ struct dns_imex : dns::Ring {
     std::unique_ptr<Functionals> fn;
     int fn_launch(hipStream_t s);  // k_functional_step for the state as it stands
     uint64_t fn_key() const;
-    // flow statistics (stats.hpp): k_stats_step runs in front of every step
-    // (behind the other three) and once behind the last step of a call; it
-    // ADDS row `counter - 1` to running sums, so -- unlike the rows of the
-    // other three -- a row must not be seen twice: the workgroups' marks
-    // (the head of `acc`) drop the second launch for a row, rewind_tables()
-    // zeroes them with the counter, and a batch checkpoints `acc` as a whole
-    // (`ck_st`: `ck` can be full without it).  Present = on.
+    // flow statistics (stats.hpp): k_stats_step ADDS its row to running sums,
+    // so -- unlike the rows of the others -- a row must not be seen twice: the
+    // workgroups' marks (the head of `acc`) drop the second launch for a row,
+    // rewind_tables() zeroes them with the counter, and a batch checkpoints
+    // `acc` as a whole (`ck_st`: `ck` can be full without it).
     struct Statistics {
         dns::StLayout lay;
         int rows = 0;              // steps the bin table covers
@@ -231,14 +261,11 @@ struct dns_imex : dns::Ring {
     dns::Checkpoint ck_st;
     int st_launch(hipStream_t s);  // k_stats_step for the state as it stands
     uint64_t st_key() const;
-    // quadratic functionals (quadratic.hpp): k_quadratic_step runs in front of
-    // every step (the last of the front nodes) and once behind the last step
-    // of a call; it writes row `counter - 1` of the log, so a restored batch
-    // overwrites its own rows and the log needs no checkpoint.  The matrices
+    // quadratic functionals (quadratic.hpp): k_quadratic_step.  The matrices
     // stay on the device across calls that hand over the same ones (`Qh`:
-    // what the device holds).  Present = on.
+    // what the device holds).
     struct Quadratics {
-        int nM = 0, nQ = 0, G = 1, rows = 0;
+        int nM = 0, nQ = 0;
         double dt = 1.0;
         int mat[dns::kQdMaxForms] = {}, lop[dns::kQdMaxForms] = {},
             rop[dns::kQdMaxForms] = {};
@@ -253,43 +280,20 @@ struct dns_imex : dns::Ring {
         dns::DevBuf<double> va;
         dns::DevBuf<int> lrp, lci; // the 2 nQ sparse rows (k, qa / qw)
         dns::DevBuf<double> lva, scale, c0;
-        dns::DevBuf<double> log;   // rows x G x nQ
-        // moving Dirichlet values (dns_imex_set_quadratics_bc / _live):
-        // matrices and sparse rows are nv + ndbc wide; the table of their own,
-        // (rows + 1) x ndbc, or (`live`) the convection operator's; ndbc = 0:
-        // constant values
-        int ndbc = 0;
-        dns::DevBuf<double> gtab;
-        bool live = false;
-        bool moving() const { return ndbc > 0; }
+        ShareLog log;              // rows x G x nQ
+        MovingBc bc;               // (moving: matrices and sparse rows are
+                                   // nv + ndbc wide)
     };
     std::unique_ptr<Quadratics> qd;
-    // Where an attachment with moving Dirichlet values reads them: its own
-    // table (`own`, `rows` + 1 rows of `ndbc`) or, `live`, the table of the
-    // attached convection operator (check_attachments has seen to its width
-    // and length) -- pointer, row stride, rows.
-    struct BcTable {
-        const double *p;
-        int stride, rows;
-    };
-    BcTable bc_table(bool live, const dns::DevBuf<double> &own, int ndbc,
-                     int rows) const {
-        if (live && conv)
-            return {conv->dbc_tab.p, std::max(1, conv->ndbc), conv->dbc_rows};
-        return {own.p, ndbc, rows + 1};
-    }
     int check_live(const char *noun, int ndbc, int rows) const;
     int qd_launch(hipStream_t s);  // k_quadratic_step for the state as it stands
     uint64_t qd_key() const;
-    // snapshot ensemble (ensemble.hpp): k_ensemble_step runs in front of every
-    // step (the last of the front nodes) and once behind the last step of a
-    // call; it copies v into slot `slot[counter - 1]` of E, which the stepper
-    // owns ACROSS the slices of a time loop (they re-arm the slot table only).
-    // A row copied twice or by a restored batch has the same bits: no marks,
-    // no checkpoint.  The Gram matrix and the linear combinations run behind
-    // the loop as plain launches (`W`: the weights as uploaded last, `Wh`
-    // what they are; `y`, `part`, `gm`, `cf`, `out`: their scratch).
-    // Present = on.
+    // snapshot ensemble (ensemble.hpp): k_ensemble_step copies v into slot
+    // `slot[counter - 1]` of E, which the stepper owns ACROSS the slices of a
+    // time loop (they re-arm the slot table only).  The Gram matrix and the
+    // linear combinations run behind the loop as plain launches (`W`: the
+    // weights as uploaded last, `Wh` what they are; `y`, `part`, `gm`, `cf`,
+    // `out`: their scratch).
     struct Ensemble {
         int rows = 0, nslots = 0;
         size_t ldv = 0;
@@ -302,10 +306,25 @@ struct dns_imex : dns::Ring {
     std::unique_ptr<Ensemble> ens;
     int ens_launch(hipStream_t s); // k_ensemble_step for the state as it stands
     uint64_t ens_key() const;
-    // What the six have in common (imex_attach_capi.inc): which of them
-    // run in front of a step and which behind the last step of a call, what
-    // they add to the key of a captured step, the refusals a step makes on
-    // their behalf, and what they mean for the step counter.
+    // What the six have in common (imex_attach_capi.inc): attachments() lists
+    // those present, in launch order -- noun, why a row-partitioned stepper
+    // refuses it, rows of its table, whether it runs behind the last step of
+    // a call too, its part of a captured step's key, its launch.  Front and
+    // closing nodes, key, refusals and the counter's limits loop over it.
+    struct Attachment {
+        const char *noun, *partitioned;
+        int rows;
+        bool closing;
+        uint64_t (dns_imex::*key)() const;
+        int (dns_imex::*launch)(hipStream_t);
+    };
+    struct Attachments {
+        Attachment a[6];
+        int n = 0;
+        const Attachment *begin() const { return a; }
+        const Attachment *end() const { return a + n; }
+    };
+    Attachments attachments() const;
     int launch_front_nodes(hipStream_t s);
     int launch_closing_nodes(hipStream_t s);
     uint64_t attachments_key(uint64_t k) const;

@@ -3,7 +3,11 @@
 // (functional.hpp), flow statistics (stats.hpp), quadratic functionals
 // (quadratic.hpp), snapshot ensemble (ensemble.hpp): one node each in front of
 // every step -- and their extern "C" entry points (included by dns_amd.hip
-// behind imex_capi.inc).
+// behind imex_capi.inc).  First each one's key and launch, then
+// dns_imex::attachments(), the one list of them that everything else loops
+// over; what functionals and quadratics share (the source of moving Dirichlet
+// values, the log of the workgroups' shares) is MovingBc and ShareLog, and
+// attach_host.hpp for what needs no device.
 
 // "feedback on", its shape, its coefficients and every buffer k_lti_step is
 // handed: a graph captured for another set must not be replayed
@@ -51,23 +55,28 @@ int dns_imex::rec_launch(hipStream_t s) {
     return DNS_OK;
 }
 
+// with moving values: that they are, how many, their source and the table in
+// use -- their own or the operator's --, its stride and rows
+uint64_t dns_imex::MovingBc::key(uint64_t k, const dns_imex &st,
+                                 int rows) const {
+    if (!moving()) return k;
+    const Table t = table(st, rows);
+    return mix64(k, {kw(0xbc), kw(ndbc), kw(live), kw(t.p), kw(t.stride),
+                     kw(t.rows)});
+}
+
 // "functionals on", their shape and instance (constant or moving Dirichlet
-// values: the table in use -- their own or the operator's --, its stride and
-// rows), every buffer k_functional_step is handed (the ring vectors come with
-// the step key) and the pressure scale
+// values), every buffer k_functional_step is handed (the ring vectors come
+// with the step key) and the pressure scale
 uint64_t dns_imex::fn_key() const {
     const Functionals &f = *fn;
-    uint64_t k = mix64(0xf6, {kw(f.nF), kw(f.G), kw(f.rows), kw(f.ncl),
+    uint64_t k = mix64(0xf6, {kw(f.nF), kw(f.log.G), kw(f.log.rows), kw(f.ncl),
                               kw(f.dt), kw(last_pscale), kw(f.rp.p),
                               kw(f.ci.p), kw(f.va.p), kw(f.cptr.p)});
-    if (f.moving()) {
-        const BcTable t = bc_table(f.live, f.gtab, f.ndbc, f.rows);
-        k = mix64(k, {kw(0xbc), kw(f.ndbc), kw(f.live), kw(t.p), kw(t.stride),
-                      kw(t.rows)});
-    }
+    k = f.bc.key(k, *this, f.log.rows);
     return mix64(k,
                  {kw(f.cidx.p), kw(f.cw.p), kw(f.scale.p), kw(f.c0.p),
-                  kw(f.log.p), kw(stepctr.p), kw(conv ? conv->ncells : 0),
+                  kw(f.log.buf.p), kw(stepctr.p), kw(conv ? conv->ncells : 0),
                   kw(conv ? conv->cellmap.p : nullptr),
                   kw(conv ? conv->glam.p : nullptr),
                   kw(conv ? conv->area.p : nullptr),
@@ -77,26 +86,27 @@ uint64_t dns_imex::fn_key() const {
 int dns_imex::fn_launch(hipStream_t s) {
     const Functionals &f = *fn;
     const bool cells = f.ncl > 0;
-    const dns::FnArgs a{stepctr.p, f.rows, xs[cur].p, xs[prev].p, sys->nv,
-                        last_pscale, f.dt, f.nF, f.G, f.rp.p, f.ci.p, f.va.p,
+    const int G = f.log.G;
+    const dns::FnArgs a{stepctr.p, f.log.rows, xs[cur].p, xs[prev].p, sys->nv,
+                        last_pscale, f.dt, f.nF, G, f.rp.p, f.ci.p, f.va.p,
                         f.ncl, f.cptr.p, f.cidx.p, f.cw.p,
                         cells ? conv->ncells : 0,
                         cells ? conv->cellmap.p : (const int *)nullptr,
                         cells ? conv->glam.p : (const double *)nullptr,
                         cells ? conv->area.p : (const double *)nullptr,
                         cells ? conv->dbcvals.p : (const double *)nullptr,
-                        f.scale.p, f.c0.p, f.log.p};
-    if (f.moving()) {
+                        f.scale.p, f.c0.p, f.log.buf.p};
+    if (f.bc.moving()) {
         dns::FnBcArgs b;
         static_cast<dns::FnArgs &>(b) = a;
         // (a live table is as wide as the functionals' own -- its stride is
         // ndbc -- and has more than `rows` rows: check_attachments)
-        b.gtab = bc_table(f.live, f.gtab, f.ndbc, f.rows).p;
-        b.ndbc = f.ndbc;
-        hipLaunchKernelGGL(dns::k_functional_step<dns::FnBcArgs>, f.G,
+        b.gtab = f.bc.table(*this, f.log.rows).p;
+        b.ndbc = f.bc.ndbc;
+        hipLaunchKernelGGL(dns::k_functional_step<dns::FnBcArgs>, G,
                            dns::kBlock, 0, s, b);
     } else {
-        hipLaunchKernelGGL(dns::k_functional_step<dns::FnArgs>, f.G,
+        hipLaunchKernelGGL(dns::k_functional_step<dns::FnArgs>, G,
                            dns::kBlock, 0, s, a);
     }
     DNS_HIP(hipGetLastError());
@@ -170,35 +180,30 @@ int dns_imex::st_launch(hipStream_t s) {
 // with moving Dirichlet values, the table in use, its stride and rows
 uint64_t dns_imex::qd_key() const {
     const Quadratics &q = *qd;
-    uint64_t k = mix64(0x9d, {kw(q.nM), kw(q.nQ), kw(q.G), kw(q.rows),
+    uint64_t k = mix64(0x9d, {kw(q.nM), kw(q.nQ), kw(q.log.G), kw(q.log.rows),
                               kw(q.dt), kw(q.rp.p), kw(q.ci.p), kw(q.va.p),
                               kw(q.lrp.p), kw(q.lci.p), kw(q.lva.p),
-                              kw(q.scale.p), kw(q.c0.p), kw(q.log.p),
+                              kw(q.scale.p), kw(q.c0.p), kw(q.log.buf.p),
                               kw(stepctr.p)});
     for (int m = 0; m < q.nM; ++m)
         k = mix64(k, {kw(q.nzbase[m]), kw(q.need[m])});
     for (int f = 0; f < q.nQ; ++f)
         k = mix64(k, {kw(q.mat[f]), kw(q.lop[f]), kw(q.rop[f])});
-    if (q.moving()) {
-        const BcTable t = bc_table(q.live, q.gtab, q.ndbc, q.rows);
-        k = mix64(k, {kw(0xbc), kw(q.ndbc), kw(q.live), kw(t.p), kw(t.stride),
-                      kw(t.rows)});
-    }
-    return k;
+    return q.bc.key(k, *this, q.log.rows);
 }
 
 int dns_imex::qd_launch(hipStream_t s) {
     const Quadratics &q = *qd;
     dns::QdArgs a{};
     a.stepctr = stepctr.p;
-    a.nrows = q.rows;
+    a.nrows = q.log.rows;
     a.x = xs[cur].p;
     a.xp = xs[prev].p;
     a.nv = sys->nv;
     a.dt = q.dt;
     a.nM = q.nM;
     a.nQ = q.nQ;
-    a.G = q.G;
+    a.G = q.log.G;
     a.rp = q.rp.p;
     a.ci = q.ci.p;
     a.va = q.va.p;
@@ -214,18 +219,18 @@ int dns_imex::qd_launch(hipStream_t s) {
     a.lva = q.lva.p;
     a.scale = q.scale.p;
     a.c0 = q.c0.p;
-    a.log = q.log.p;
-    if (q.moving()) {
-        const BcTable t = bc_table(q.live, q.gtab, q.ndbc, q.rows);
+    a.log = q.log.buf.p;
+    if (q.bc.moving()) {
+        const MovingBc::Table t = q.bc.table(*this, q.log.rows);
         dns::QdBcArgs b;
         static_cast<dns::QdArgs &>(b) = a;
         b.gtab = t.p;
-        b.ndbc = q.ndbc;                // (== t.stride: check_attachments)
+        b.ndbc = q.bc.ndbc;             // (== t.stride: check_attachments)
         b.trows = t.rows;
-        hipLaunchKernelGGL(dns::k_quadratic_step<dns::QdBcArgs>, q.G,
+        hipLaunchKernelGGL(dns::k_quadratic_step<dns::QdBcArgs>, a.G,
                            dns::kBlock, 0, s, b);
     } else {
-        hipLaunchKernelGGL(dns::k_quadratic_step<dns::QdArgs>, q.G,
+        hipLaunchKernelGGL(dns::k_quadratic_step<dns::QdArgs>, a.G,
                            dns::kBlock, 0, s, a);
     }
     DNS_HIP(hipGetLastError());
@@ -252,9 +257,26 @@ int dns_imex::ens_launch(hipStream_t s) {
 
 // ---- what the six have in common --------------------------------------------
 
-// In front of every step, in this order: k_lti_step leaves the right-hand
-// side the front kernels read, the other five write down / add the row of
-// the step before.
+// (why a row-partitioned / distributed stepper refuses each: refuse_partitioned)
+static const char *const kFbPartitioned =
+    "the outputs y = C v would need an all-reduce (multi-rank feedback is not "
+    "supported)";
+static const char *const kRecPartitioned =
+    "the outputs y = C v would need an all-reduce, the snapshots a gather "
+    "(multi-rank recording is not supported)";
+static const char *const kFnPartitioned = "the sums would need an all-reduce",
+                         *const kQdPartitioned = kFnPartitioned;
+static const char *const kStPartitioned =
+    "the sums are local to a rank, the getter would need a gather (multi-rank "
+    "statistics are not supported)";
+static const char *const kEnsPartitioned =
+    "the slots would hold a rank's rows only, the Gram matrix would need an "
+    "all-reduce (multi-rank ensembles are not supported)";
+
+// Those present, in the order of their nodes in front of every step:
+// k_lti_step leaves the right-hand side the front kernels read, the other
+// five write down / add the row of the step before -- and run once more
+// behind the last step of a call (`closing`).
 //
 // Functionals and quadratics that read the operator's LIVE Dirichlet table
 // (boundary feedback) depend on this order: k_lti_bc_step, the FIRST front
@@ -263,50 +285,55 @@ int dns_imex::ens_launch(hipStream_t s) {
 // rows s and s - 1, which the two nodes of step s read behind it on the same
 // stream, were complete a step earlier (row 0 was uploaded).  The closing
 // launch reads row `rows`, which the last step's observer node wrote.
+dns_imex::Attachments dns_imex::attachments() const {
+    Attachments l;
+    if (fb)
+        l.a[l.n++] = {"observer feedback", kFbPartitioned, fb->rows, false,
+                      &dns_imex::fb_key, &dns_imex::fb_launch};
+    if (rec)
+        l.a[l.n++] = {"recorder", kRecPartitioned, rec->rows, true,
+                      &dns_imex::rec_key, &dns_imex::rec_launch};
+    if (fn)
+        l.a[l.n++] = {"functionals", kFnPartitioned, fn->log.rows, true,
+                      &dns_imex::fn_key, &dns_imex::fn_launch};
+    if (stat)
+        l.a[l.n++] = {"statistics", kStPartitioned, stat->rows, true,
+                      &dns_imex::st_key, &dns_imex::st_launch};
+    if (qd)
+        l.a[l.n++] = {"quadratics", kQdPartitioned, qd->log.rows, true,
+                      &dns_imex::qd_key, &dns_imex::qd_launch};
+    if (ens)
+        l.a[l.n++] = {"ensemble", kEnsPartitioned, ens->rows, true,
+                      &dns_imex::ens_key, &dns_imex::ens_launch};
+    return l;
+}
+
 int dns_imex::launch_front_nodes(hipStream_t s) {
-    if (fb) DNS_TRY(fb_launch(s));
-    if (rec) DNS_TRY(rec_launch(s));
-    if (fn) DNS_TRY(fn_launch(s));
-    if (stat) DNS_TRY(st_launch(s));
-    if (qd) DNS_TRY(qd_launch(s));
-    if (ens) DNS_TRY(ens_launch(s));
+    for (const Attachment &a : attachments()) DNS_TRY((this->*a.launch)(s));
     return DNS_OK;
 }
 
 // Behind the last step of a call: the rows nobody runs a prologue for.
 int dns_imex::launch_closing_nodes(hipStream_t s) {
-    if (rec) DNS_TRY(rec_launch(s));
-    if (fn) DNS_TRY(fn_launch(s));
-    if (stat) DNS_TRY(st_launch(s));
-    if (qd) DNS_TRY(qd_launch(s));
-    if (ens) DNS_TRY(ens_launch(s));
+    for (const Attachment &a : attachments())
+        if (a.closing) DNS_TRY((this->*a.launch)(s));
     return DNS_OK;
 }
 
 uint64_t dns_imex::attachments_key(uint64_t k) const {
-    if (fb) k = mix64(k, {fb_key()});
-    if (rec) k = mix64(k, {rec_key()});
-    if (fn) k = mix64(k, {fn_key()});
-    if (stat) k = mix64(k, {st_key()});
-    if (qd) k = mix64(k, {qd_key()});
-    if (ens) k = mix64(k, {ens_key()});
+    for (const Attachment &a : attachments()) k = mix64(k, {(this->*a.key)()});
     return k;
 }
 
 bool dns_imex::tables() const {
     return tab_rows > 0 || (conv && conv->dbc_rows > 0) ||
-           (conv && conv->nbrow > 0) || fb || rec || fn || stat || qd || ens;
+           (conv && conv->nbrow > 0) || attachments().n > 0;
 }
 
 int dns_imex::rows_left() const {
     int lim = 1 << 30;
     if (tab_rows > 0) lim = std::min(lim, tab_rows);
-    if (fb) lim = std::min(lim, fb->rows);
-    if (rec) lim = std::min(lim, rec->rows);
-    if (fn) lim = std::min(lim, fn->rows);
-    if (stat) lim = std::min(lim, stat->rows);
-    if (qd) lim = std::min(lim, qd->rows);
-    if (ens) lim = std::min(lim, ens->rows);
+    for (const Attachment &a : attachments()) lim = std::min(lim, a.rows);
     if (conv && conv->dbc_rows > 0) lim = std::min(lim, conv->dbc_rows);
     return lim - tab_pos;
 }
@@ -352,26 +379,21 @@ int dns_imex::refuse_partitioned(const char *noun, const char *reason) const {
                      noun, reason);
 }
 
-static const char *const kFbPartitioned =
-    "the outputs y = C v would need an all-reduce (multi-rank feedback is not "
-    "supported)";
-static const char *const kRecPartitioned =
-    "the outputs y = C v would need an all-reduce, the snapshots a gather "
-    "(multi-rank recording is not supported)";
-static const char *const kFnPartitioned = "the sums would need an all-reduce";
-static const char *const kStPartitioned =
-    "the sums are local to a rank, the getter would need a gather (multi-rank "
-    "statistics are not supported)";
-static const char *const kQdPartitioned = "the sums would need an all-reduce";
-static const char *const kEnsPartitioned =
-    "the slots would hold a rank's rows only, the Gram matrix would need an "
-    "all-reduce (multi-rank ensembles are not supported)";
 static const char *const kLinPartitioned =
     "the tails of the partitioned step evaluate N(v)v";
+// (constant Dirichlet values beside a per-step table on the operator: what
+// the setters say, and what a step says later)
 static const char *const kQdMovingBc =
     "quadratics with a per-step Dirichlet table on the convection operator "
     "(dns_conv_set_dbc_table): moving boundary values are not part of the "
     "constants";
+static const char *const kFnMovingBcSet =
+    "functionals with a per-step Dirichlet table on the convection operator "
+    "(dns_conv_set_dbc_table): the moving-boundary terms are not part of the "
+    "functional";
+static const char *const kFnMovingBcStep =
+    "functionals with a per-step Dirichlet table on the convection operator: "
+    "the moving-boundary terms are not part of the functional";
 
 // What reading the operator's live Dirichlet table takes: the operator, its
 // width and `rows` + 1 rows (the setters and the step ask alike).
@@ -410,7 +432,8 @@ int dns_imex::check_attachments() const {
             DNS_TRY(dns::check_adjoint_dbc(conv->dbc_host.data(), conv->ndbc,
                                            conv->dbc_rows));
     }
-    if (fb) DNS_TRY(refuse_partitioned("observer feedback", kFbPartitioned));
+    for (const Attachment &a : attachments())
+        DNS_TRY(refuse_partitioned(a.noun, a.partitioned));
     if (fb && fb->bc) {
         const Feedback::Boundary &b = *fb->bc;
         // k_lti_bc_step writes row `counter + 1` of the operator's table
@@ -432,34 +455,20 @@ int dns_imex::check_attachments() const {
                              "row 0: the values of the current state)",
                              conv->dbc_rows, fb->rows, fb->rows + 1);
         // (the device makes the values: a host-made copy cannot hold them)
-        if ((fn && !fn->live) || (qd && !qd->live))
+        if ((fn && !fn->bc.live) || (qd && !qd->bc.live))
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
                              "boundary feedback with %s that do not read the "
                              "operator's live Dirichlet table: their Dirichlet "
                              "values are host-made copies (%s)",
-                             fn && !fn->live ? "functionals" : "quadratics",
-                             fn && !fn->live ? "dns_imex_set_functionals_live"
-                                             : "dns_imex_set_quadratics_live");
+                             fn && !fn->bc.live ? "functionals" : "quadratics",
+                             fn && !fn->bc.live
+                                 ? "dns_imex_set_functionals_live"
+                                 : "dns_imex_set_quadratics_live");
     }
-    if (rec) DNS_TRY(refuse_partitioned("recorder", kRecPartitioned));
-    if (stat) DNS_TRY(refuse_partitioned("statistics", kStPartitioned));
-    if (ens) DNS_TRY(refuse_partitioned("ensemble", kEnsPartitioned));
-    if (qd) {
-        DNS_TRY(refuse_partitioned("quadratics", kQdPartitioned));
-        if (!qd->moving() && conv && conv->dbc_rows > 0)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT, "%s", kQdMovingBc);
-        // (the columns behind nv are positions in the operator's values)
-        if (qd->moving() && conv && conv->ndbc != qd->ndbc)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "quadratics with moving Dirichlet values were set "
-                             "for %d values, the convection operator attached "
-                             "now has %d: set them again "
-                             "(dns_imex_set_quadratics_bc)", qd->ndbc,
-                             conv->ndbc);
-        if (qd->live) DNS_TRY(check_live("quadratics", qd->ndbc, qd->rows));
-    }
+    if (qd)
+        DNS_TRY(qd->bc.check_step(*this, qd->log.rows, "quadratics",
+                                  "dns_imex_set_quadratics_bc", kQdMovingBc));
     if (!fn) return DNS_OK;
-    DNS_TRY(refuse_partitioned("functionals", kFnPartitioned));
     if (fn->ncl > 0 && !conv)
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "functionals with cells need the device convection "
@@ -472,21 +481,34 @@ int dns_imex::check_attachments() const {
                          "functionals with cells were set with another "
                          "convection operator than the one attached now: "
                          "set them again (dns_imex_set_functionals)");
-    if (!fn->moving() && conv && conv->dbc_rows > 0)
+    return fn->bc.check_step(*this, fn->log.rows, "functionals",
+                             "dns_imex_set_functionals_bc", kFnMovingBcStep);
+}
+
+// (the table rows are `ndbc` wide, and so are the cells' Dirichlet slots of
+// the functionals and the columns behind nv of the quadratics: positions in
+// the operator's values)
+int dns_imex::MovingBc::check_step(const dns_imex &st, int rows,
+                                   const char *noun, const char *setter,
+                                   const char *const_refusal) const {
+    const dns_conv *cv = st.conv;
+    if (!moving() && cv && cv->dbc_rows > 0)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "%s", const_refusal);
+    if (moving() && cv && cv->ndbc != ndbc)
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "functionals with a per-step Dirichlet table on "
-                         "the convection operator: the moving-boundary "
-                         "terms are not part of the functional");
-    // (their table rows and the cells' Dirichlet slots are that wide)
-    if (fn->moving() && conv && conv->ndbc != fn->ndbc)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "functionals with moving Dirichlet values were set "
-                         "for %d values, the convection operator attached "
-                         "now has %d: set them again "
-                         "(dns_imex_set_functionals_bc)", fn->ndbc,
-                         conv->ndbc);
-    if (fn->live) DNS_TRY(check_live("functionals", fn->ndbc, fn->rows));
-    return DNS_OK;
+                         "%s with moving Dirichlet values were set for %d "
+                         "values, the convection operator attached now has "
+                         "%d: set them again (%s)", noun, ndbc, cv->ndbc,
+                         setter);
+    return live ? st.check_live(noun, ndbc, rows) : DNS_OK;
+}
+
+int dns_imex::MovingBc::check_set(const dns_imex &st, const char *noun,
+                                  const char *const_refusal, bool moving,
+                                  bool live, int ndbc, int rows) {
+    if (!moving && st.conv && st.conv->dbc_rows > 0)
+        return dns::fail(DNS_ERR_BAD_ARGUMENT, "%s", const_refusal);
+    return live ? st.check_live(noun, ndbc, rows) : DNS_OK;
 }
 
 // the handle, the attachment (`what`: "... is" / "... are") and the device
@@ -538,12 +560,62 @@ static void adopt(dns::DevBuf<T> &dst, dns::DevBuf<T> &old) {
     std::swap(dst.n, old.n);
 }
 
-// Before an attachment is taken off: replays may still use its buffers.  (The
-// counter goes on counting for the other tables, if any.)
+// a host vector into a buffer that is kept where it is large enough
+template <typename T>
+static int put(dns::DevBuf<T> &buf, const std::vector<T> &host, hipStream_t s) {
+    DNS_TRY(keep_or_alloc(buf, buf, host.size()));
+    if (!host.empty()) DNS_TRY(buf.upload(host.data(), host.size(), s));
+    return DNS_OK;
+}
+
+int dns_imex::MovingBc::set(bool moving, bool live_, int ndbc_, int rows,
+                            const double *dbc_table, hipStream_t s) {
+    if (moving && !live_) {
+        const size_t ng = ((size_t)rows + 1) * ndbc_;
+        DNS_TRY(keep_or_alloc(gtab, gtab, ng));
+        DNS_TRY(gtab.upload(dbc_table, ng, s));
+    }
+    ndbc = moving ? ndbc_ : 0;
+    live = live_;
+    return DNS_OK;
+}
+
+int dns_imex::ShareLog::ensure(int rows_, int G_, int n_, hipStream_t s) {
+    DNS_TRY(keep_or_alloc(buf, buf, (size_t)rows_ * G_ * n_));
+    DNS_TRY(buf.zero(s));
+    rows = rows_;
+    G = G_;
+    n = n_;
+    return DNS_OK;
+}
+
+// rows [first, first + count) of the log, the shares summed (`what`: the rows
+// in a refusal); complete on return
+int dns_imex::ShareLog::download_sums(dns_imex *st, int first, int count,
+                                      double *out, const char *what) const {
+    if (!out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
+    const size_t per = (size_t)G * n;
+    std::vector<double> part((size_t)std::min(std::max(count, 0), rows) * per);
+    DNS_TRY(download_log_rows(st, part.data(), buf.p, first, count, per, rows,
+                              what, "log"));
+    dns::sum_shares(part.data(), count, G, n, out);
+    return DNS_OK;
+}
+
+// Before an attachment is set again or taken off: replays may still use its
+// buffers.  (The counter goes on counting for the other tables, if any.)
 static int quiesce(dns_imex *st) {
     if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     DNS_HIP(hipSetDevice(st->sys->device));
     DNS_HIP(hipStreamSynchronize(st->sys->stream));
+    return DNS_OK;
+}
+
+// the exports that clear an attachment
+template <typename T>
+static int take_off(dns_imex *st, std::unique_ptr<T> dns_imex::*which) {
+    DNS_TRY(quiesce(st));
+    (st->*which).reset();
     return DNS_OK;
 }
 
@@ -564,51 +636,17 @@ static int set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
     if (!st) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
     DNS_TRY(st->refuse_partitioned("functionals", kFnPartitioned));
-    if (nF < 1 || nF > dns::kFnMax)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "functionals: nF = %d outside 1..%d", (int)nF,
-                         dns::kFnMax);
-    if (nrows < 1)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT, "functionals: nrows = %d < 1",
-                         (int)nrows);
-    if (!(dt > 0.0))
-        return dns::fail(DNS_ERR_BAD_ARGUMENT, "functionals: dt must be "
-                         "positive");
-    if (moving && ndbc < 1)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "functionals: ndbc = %d < 1 (constant Dirichlet "
-                         "values: dns_imex_set_functionals)", (int)ndbc);
-    if (moving && !live && !dbc_table)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "functionals: no table of the Dirichlet values");
-    if (live) DNS_TRY(st->check_live("functionals", ndbc, nrows));
     const int nterms = moving ? 5 : 3;
     const dns_csr *terms[5] = {ca, cm, cp, cab, cmb};
-    const char *names[5] = {"ca", "cm", "cp", "cab", "cmb"};
-    for (int t = 0; t < nterms; ++t) {
-        if (!terms[t]) continue;
-        DNS_TRY(dns::check_csr(terms[t], names[t]));
-        const int want = t == 2 ? h->np : (t > 2 ? (int)ndbc : h->nv);
-        if (terms[t]->nrows != nF || terms[t]->ncols != want)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "functionals: %s must be nF x %d, it is %d x %d",
-                             names[t], want, (int)terms[t]->nrows,
-                             (int)terms[t]->ncols);
-    }
+    DNS_TRY(dns::check_functionals_args(nF, dns::kFnMax, nrows, dt, moving,
+                                        live, ndbc, dbc_table, terms, h->nv,
+                                        h->np, cell_ptr, cell_idx, cell_w));
+    for (int t = 0; t < nterms; ++t)
+        if (terms[t]) DNS_TRY(dns::check_csr(terms[t], dns::kFnTermNames[t]));
+    DNS_TRY(dns_imex::MovingBc::check_set(*st, "functionals", kFnMovingBcSet,
+                                          moving, live, ndbc, nrows));
     const int ncl = cell_ptr ? cell_ptr[nF] : 0;
-    if (cell_ptr) {
-        if (cell_ptr[0] != 0)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "functionals: cell_ptr[0] must be 0");
-        for (int k = 0; k < nF; ++k)
-            if (cell_ptr[k + 1] < cell_ptr[k])
-                return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                                 "functionals: cell_ptr not monotone");
-    }
     if (ncl > 0) {
-        if (!cell_idx || !cell_w)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "functionals: cells without cell_idx / cell_w");
         if (!st->conv)
             return dns::fail(DNS_ERR_BAD_ARGUMENT,
                              "functionals with cells need a device convection "
@@ -625,51 +663,26 @@ static int set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
                          "functionals: ndbc = %d, the convection operator of "
                          "the listed cells has %d Dirichlet values",
                          (int)ndbc, st->conv->ndbc);
-    if (!moving && st->conv && st->conv->dbc_rows > 0)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "functionals with a per-step Dirichlet table on the "
-                         "convection operator (dns_conv_set_dbc_table): the "
-                         "moving-boundary terms are not part of the "
-                         "functional");
-    // the 3 nF (5 nF) sparse rows (k, term) in one CSR; a null term is an
-    // empty row
-    std::vector<int> rp((size_t)nterms * nF + 1, 0), ci;
-    std::vector<double> va;
-    for (int k = 0; k < nF; ++k)
-        for (int t = 0; t < nterms; ++t) {
-            if (terms[t])
-                for (int64_t z = terms[t]->rowptr[k];
-                     z < terms[t]->rowptr[k + 1]; ++z) {
-                    ci.push_back(terms[t]->colidx[z]);
-                    va.push_back(terms[t]->vals[z]);
-                }
-            rp[(size_t)nterms * k + t + 1] = (int)ci.size();
-        }
+    // the 3 nF (5 nF) sparse rows (k, term) in one CSR
+    std::vector<int> rp, ci;
+    std::vector<double> va, sc, cc;
+    dns::stack_rows(terms, nterms, nF, rp, ci, va);
     std::vector<int> cptr(nF + 1, 0);
     if (cell_ptr) cptr.assign(cell_ptr, cell_ptr + nF + 1);
-    std::vector<double> sc(nF, 1.0), cc(nF, 0.0);
-    if (scale) sc.assign(scale, scale + nF);
-    if (c0) cc.assign(c0, c0 + nF);
-    DNS_HIP(hipSetDevice(h->device));
+    dns::scale_c0(scale, c0, nF, sc, cc);
+    DNS_TRY(quiesce(st));                       // replays may still write it
     hipStream_t s = h->stream;
-    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
     // In place (keep_or_alloc; everything was checked above: a failed
     // allocation leaves the stepper without functionals).
     std::unique_ptr<dns_imex::Functionals> f = std::move(st->fn);
     if (!f) f.reset(new (std::nothrow) dns_imex::Functionals());
     if (!f) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
-    const int G = dns::functional_grid(nF, ncl, nterms);
-    auto put = [&](auto &buf, const auto &host) -> int {
-        DNS_TRY(keep_or_alloc(buf, buf, host.size()));
-        if (!host.empty()) DNS_TRY(buf.upload(host.data(), host.size(), s));
-        return DNS_OK;
-    };
-    DNS_TRY(put(f->rp, rp));
-    DNS_TRY(put(f->ci, ci));
-    DNS_TRY(put(f->va, va));
-    DNS_TRY(put(f->cptr, cptr));
-    DNS_TRY(put(f->scale, sc));
-    DNS_TRY(put(f->c0, cc));
+    DNS_TRY(put(f->rp, rp, s));
+    DNS_TRY(put(f->ci, ci, s));
+    DNS_TRY(put(f->va, va, s));
+    DNS_TRY(put(f->cptr, cptr, s));
+    DNS_TRY(put(f->scale, sc, s));
+    DNS_TRY(put(f->c0, cc, s));
     DNS_TRY(keep_or_alloc(f->cidx, f->cidx, (size_t)ncl));
     DNS_TRY(keep_or_alloc(f->cw, f->cw, (size_t)12 * ncl));
     if (ncl > 0) {
@@ -680,18 +693,9 @@ static int set_functionals(dns_imex *st, int32_t nF, const dns_csr *ca,
         DNS_TRY(f->cidx.upload(cint.data(), (size_t)ncl, s));
         DNS_TRY(f->cw.upload(cell_w, (size_t)12 * ncl, s));
     }
-    DNS_TRY(keep_or_alloc(f->log, f->log, (size_t)nrows * G * nF));
-    DNS_TRY(f->log.zero(s));
-    if (moving && !live) {
-        const size_t ng = ((size_t)nrows + 1) * ndbc;
-        DNS_TRY(keep_or_alloc(f->gtab, f->gtab, ng));
-        DNS_TRY(f->gtab.upload(dbc_table, ng, s));
-    }
-    f->ndbc = moving ? ndbc : 0;
-    f->live = live;
+    DNS_TRY(f->log.ensure(nrows, dns::functional_grid(nF, ncl, nterms), nF, s));
+    DNS_TRY(f->bc.set(moving, live, ndbc, nrows, dbc_table, s));
     f->nF = nF;
-    f->G = G;
-    f->rows = nrows;
     f->ncl = ncl;
     f->dt = dt;
     f->conv = ncl > 0 ? st->conv : nullptr;
@@ -758,9 +762,8 @@ int dns_imex_set_feedback(dns_imex *st, const dns_csr *cmat, const dns_csr *bmat
                          (long long)cmat->nnz, dns::kFbMaxNnzC);
     if (!(dt > 0.0))
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "observer feedback: dt <= 0");
-    DNS_HIP(hipSetDevice(h->device));
+    DNS_TRY(quiesce(st));                       // replays may still read it
     hipStream_t s = h->stream;
-    DNS_HIP(hipStreamSynchronize(s));           // replays may still read it
     // A fresh one (the plain mode: dns_imex_set_feedback_boundary follows),
     // moved in once nothing can fail any more; a `geff` that is large enough
     // is taken over from the one that was there.
@@ -851,9 +854,7 @@ int dns_imex_get_feedback_log(dns_imex *st, int32_t first, int32_t count,
 } DNS_CAPI_CATCH
 
 int dns_imex_clear_feedback(dns_imex *st) try {
-    DNS_TRY(quiesce(st));
-    st->fb.reset();
-    return DNS_OK;
+    return take_off(st, &dns_imex::fb);
 } DNS_CAPI_CATCH
 
 // ---- boundary feedback (k_lti_bc_step) -------------------------------------
@@ -912,9 +913,8 @@ int dns_imex_set_feedback_boundary(dns_imex *st, const dns_csr *smat,
                                  (int)mats[t]->nrows, (int)mats[t]->ncols);
         }
     }
-    DNS_HIP(hipSetDevice(h->device));
+    DNS_TRY(quiesce(st));                       // replays may still read it
     hipStream_t s = h->stream;
-    DNS_HIP(hipStreamSynchronize(s));           // replays may still read it
     std::unique_ptr<dns_imex::Feedback::Boundary> b(
         new (std::nothrow) dns_imex::Feedback::Boundary());
     if (!b) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
@@ -1033,9 +1033,8 @@ int dns_imex_set_recorder(dns_imex *st, const dns_csr *cmat, int32_t nrows,
                                  "recorder: snap_slot[%d] = %d outside -1..%d",
                                  r, (int)snap_slot[r], (int)nslots - 1);
     }
-    DNS_HIP(hipSetDevice(h->device));
+    DNS_TRY(quiesce(st));                       // replays may still write it
     hipStream_t s = h->stream;
-    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
     // Built aside: a refusal below leaves the recorder that was there.  What
     // that one holds is taken over where it is large enough (keep_or_alloc;
     // C where it is the same matrix).
@@ -1116,9 +1115,7 @@ int dns_imex_get_record_snapshots(dns_imex *st, int32_t first_slot,
 } DNS_CAPI_CATCH
 
 int dns_imex_clear_recorder(dns_imex *st) try {
-    DNS_TRY(quiesce(st));
-    st->rec.reset();
-    return DNS_OK;
+    return take_off(st, &dns_imex::rec);
 } DNS_CAPI_CATCH
 
 // ---- force functionals (functional.hpp) ------------------------------------
@@ -1163,27 +1160,11 @@ int dns_imex_get_functionals(dns_imex *st, int32_t first, int32_t count,
                              double *out) try {
     DNS_TRY(need(st, st && st->fn, "functionals are",
                  "dns_imex_set_functionals"));
-    const dns_imex::Functionals &f = *st->fn;
-    if (!out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
-    const size_t per = (size_t)f.G * f.nF;
-    std::vector<double> part((size_t)std::min(std::max(count, 0), f.rows) * per);
-    DNS_TRY(download_log_rows(st, part.data(), f.log.p, first, count, per,
-                              f.rows, "functional rows", "log"));
-    // the workgroups' shares, in index order
-    for (int r = 0; r < count; ++r)
-        for (int k = 0; k < f.nF; ++k) {
-            double y = 0.0;
-            for (int g = 0; g < f.G; ++g)
-                y += part[(size_t)r * per + (size_t)g * f.nF + k];
-            out[(size_t)r * f.nF + k] = y;
-        }
-    return DNS_OK;
+    return st->fn->log.download_sums(st, first, count, out, "functional rows");
 } DNS_CAPI_CATCH
 
 int dns_imex_clear_functionals(dns_imex *st) try {
-    DNS_TRY(quiesce(st));
-    st->fn.reset();
-    return DNS_OK;
+    return take_off(st, &dns_imex::fn);
 } DNS_CAPI_CATCH
 
 // ---- flow statistics (stats.hpp) -------------------------------------------
@@ -1228,9 +1209,8 @@ int dns_imex_set_stats(dns_imex *st, int32_t nrows, const int32_t *bin,
                              "statistics: pair %d = (%d, %d) outside 0..%d "
                              "(NV + NP - 1)", q, (int)pair_i[q],
                              (int)pair_j[q], h->n - 1);
-    DNS_HIP(hipSetDevice(h->device));
+    DNS_TRY(quiesce(st));                       // replays may still add to it
     hipStream_t s = h->stream;
-    DNS_HIP(hipStreamSynchronize(s));           // replays may still add to it
     // In place (keep_or_alloc; everything was checked above: a failed
     // allocation leaves the stepper without statistics).
     std::unique_ptr<dns_imex::Statistics> t = std::move(st->stat);
@@ -1278,9 +1258,7 @@ int dns_imex_get_stats(dns_imex *st, int32_t first_bin, int32_t count,
 } DNS_CAPI_CATCH
 
 int dns_imex_clear_stats(dns_imex *st) try {
-    DNS_TRY(quiesce(st));
-    st->stat.reset();
-    return DNS_OK;
+    return take_off(st, &dns_imex::stat);
 } DNS_CAPI_CATCH
 
 // ---- quadratic functionals (quadratic.hpp) ---------------------------------
@@ -1302,81 +1280,28 @@ static int set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
     dns_saddle *h = st->sys;
     DNS_TRY(st->refuse_partitioned("quadratics", kQdPartitioned));
-    if (!moving && st->conv && st->conv->dbc_rows > 0)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT, "%s", kQdMovingBc);
-    if (moving && ndbc < 1)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "quadratics: ndbc = %d < 1 (constant Dirichlet "
-                         "values: dns_imex_set_quadratics)", (int)ndbc);
-    if (moving && !live && !dbc_table)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "quadratics: no table of the Dirichlet values");
-    if (nM < 1 || nM > dns::kQdMaxMats)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "quadratics: nM = %d outside 1..%d", (int)nM,
-                         dns::kQdMaxMats);
-    if (nQ < 1 || nQ > dns::kQdMaxForms)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "quadratics: nQ = %d outside 1..%d", (int)nQ,
-                         dns::kQdMaxForms);
-    if (nrows < 1)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT, "quadratics: nrows = %d < 1",
-                         (int)nrows);
-    if (max_grid < 0)
-        return dns::fail(DNS_ERR_BAD_ARGUMENT, "quadratics: max_grid = %d < 0",
-                         (int)max_grid);
-    if (!(dt > 0.0))
-        return dns::fail(DNS_ERR_BAD_ARGUMENT, "quadratics: dt must be "
-                         "positive");
-    if (live) DNS_TRY(st->check_live("quadratics", ndbc, nrows));
+    // (`nv`: the width of every matrix and row, NV + ndbc with moving values)
+    const int nv = h->nv + (moving ? ndbc : 0);
+    const dns_csr *lin[2] = {qa, qw};
+    DNS_TRY(dns::check_quadratics_args(nM, dns::kQdMaxMats, nQ,
+                                       dns::kQdMaxForms, nrows, max_grid, dt,
+                                       moving, live, ndbc, dbc_table, mats,
+                                       mat, lop, rop, lin, nv));
+    // (check_csr: every column index inside [0, ncols))
+    for (int m = 0; m < nM; ++m)
+        DNS_TRY(dns::check_csr(&mats[m], "quadratics: a matrix"));
+    for (int t = 0; t < 2; ++t)
+        if (lin[t]) DNS_TRY(dns::check_csr(lin[t], dns::kQdLinNames[t]));
+    DNS_TRY(dns_imex::MovingBc::check_set(*st, "quadratics", kQdMovingBc,
+                                          moving, live, ndbc, nrows));
     // (the columns behind NV are positions in the operator's values)
     if (moving && st->conv && st->conv->ndbc != ndbc)
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "quadratics: ndbc = %d, the convection operator "
                          "attached has %d Dirichlet values", (int)ndbc,
                          st->conv->ndbc);
-    // (`nv`: the width of every matrix and row, NV + ndbc with moving values)
-    const int nv = h->nv + (moving ? ndbc : 0);
-    for (int m = 0; m < nM; ++m) {
-        // (check_csr: every column index inside [0, ncols))
-        DNS_TRY(dns::check_csr(&mats[m], "quadratics: a matrix"));
-        if (mats[m].nrows != nv || mats[m].ncols != nv)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "quadratics: matrix %d must be %s (%d), it "
-                             "is %d x %d", m,
-                             moving ? "(NV + ndbc) x (NV + ndbc)" : "NV x NV",
-                             nv, (int)mats[m].nrows, (int)mats[m].ncols);
-    }
-    const dns_csr *lin[2] = {qa, qw};
-    const char *lname[2] = {"qa", "qw"};
-    for (int t = 0; t < 2; ++t) {
-        if (!lin[t]) continue;
-        DNS_TRY(dns::check_csr(lin[t], lname[t]));
-        if (lin[t]->nrows != nQ || lin[t]->ncols != nv)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "quadratics: %s must be nQ x %s (%d x %d), it is "
-                             "%d x %d", lname[t],
-                             moving ? "(NV + ndbc)" : "NV", (int)nQ, nv,
-                             (int)lin[t]->nrows, (int)lin[t]->ncols);
-    }
-    for (int k = 0; k < nQ; ++k) {
-        if (mat[k] < 0 || mat[k] >= nM)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "quadratics: mat[%d] = %d outside 0..%d", k,
-                             (int)mat[k], (int)nM - 1);
-        if (lop[k] < 0 || lop[k] > 1 || rop[k] < 0 || rop[k] > 1)
-            return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                             "quadratics: operands (%d, %d) of form %d are "
-                             "not 0 (v) or 1 (v - v_prev)", (int)lop[k],
-                             (int)rop[k], k);
-    }
     const int G = dns::quadratic_grid(nM, nv, max_grid);
-    if ((size_t)nrows * G * nQ >= ((size_t)1 << 31))
-        return dns::fail(DNS_ERR_BAD_ARGUMENT,
-                         "quadratics: a log of %zu entries (%d rows x %d "
-                         "workgroups x %d forms), the limit is 2^31 - 1: cap "
-                         "the grid (max_grid) or take shorter slices",
-                         (size_t)nrows * G * nQ, (int)nrows, G, (int)nQ);
+    DNS_TRY(dns::check_quadratics_log(nrows, G, nQ));
     // the same matrices as the device holds: as many, and each equal entry by
     // entry (row pointers, columns and the bytes of the values)
     dns_imex::Quadratics none;
@@ -1391,35 +1316,18 @@ static int set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
                (c.nnz == 0 ||
                 memcmp(o.va.data(), c.vals, (size_t)c.nnz * sizeof(double)) == 0);
     }
-    // the 2 nQ sparse rows (k, qa / qw) in one CSR; a null term is an empty row
-    std::vector<int> lrp((size_t)2 * nQ + 1, 0), lci;
-    std::vector<double> lva;
-    for (int k = 0; k < nQ; ++k)
-        for (int t = 0; t < 2; ++t) {
-            if (lin[t])
-                for (int64_t z = lin[t]->rowptr[k]; z < lin[t]->rowptr[k + 1];
-                     ++z) {
-                    lci.push_back(lin[t]->colidx[z]);
-                    lva.push_back(lin[t]->vals[z]);
-                }
-            lrp[(size_t)2 * k + t + 1] = (int)lci.size();
-        }
-    std::vector<double> sc(nQ, 1.0), cc(nQ, 0.0);
-    if (scale) sc.assign(scale, scale + nQ);
-    if (c0) cc.assign(c0, c0 + nQ);
-    DNS_HIP(hipSetDevice(h->device));
+    // the 2 nQ sparse rows (k, qa / qw) in one CSR
+    std::vector<int> lrp, lci;
+    std::vector<double> lva, sc, cc;
+    dns::stack_rows(lin, 2, nQ, lrp, lci, lva);
+    dns::scale_c0(scale, c0, nQ, sc, cc);
+    DNS_TRY(quiesce(st));                       // replays may still write it
     hipStream_t s = h->stream;
-    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
     // In place (keep_or_alloc; everything was checked above: a failed
     // allocation leaves the stepper without quadratics).
     std::unique_ptr<dns_imex::Quadratics> q = std::move(st->qd);
     if (!q) q.reset(new (std::nothrow) dns_imex::Quadratics());
     if (!q) return dns::fail(DNS_ERR_BAD_ARGUMENT, "out of host memory");
-    auto put = [&](auto &buf, const auto &host) -> int {
-        DNS_TRY(keep_or_alloc(buf, buf, host.size()));
-        if (!host.empty()) DNS_TRY(buf.upload(host.data(), host.size(), s));
-        return DNS_OK;
-    };
     if (!same) {
         size_t total = 0;
         for (int m = 0; m < nM; ++m) total += (size_t)mats[m].nnz;
@@ -1448,20 +1356,13 @@ static int set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
         for (int m = nM; m < dns::kQdMaxMats; ++m) q->nzbase[m] = 0;
         q->Qh = std::move(held);
     }
-    DNS_TRY(put(q->lrp, lrp));
-    DNS_TRY(put(q->lci, lci));
-    DNS_TRY(put(q->lva, lva));
-    DNS_TRY(put(q->scale, sc));
-    DNS_TRY(put(q->c0, cc));
-    DNS_TRY(keep_or_alloc(q->log, q->log, (size_t)nrows * G * nQ));
-    DNS_TRY(q->log.zero(s));
-    if (moving && !live) {
-        const size_t ng = ((size_t)nrows + 1) * ndbc;
-        DNS_TRY(keep_or_alloc(q->gtab, q->gtab, ng));
-        DNS_TRY(q->gtab.upload(dbc_table, ng, s));
-    }
-    q->ndbc = moving ? ndbc : 0;
-    q->live = live;
+    DNS_TRY(put(q->lrp, lrp, s));
+    DNS_TRY(put(q->lci, lci, s));
+    DNS_TRY(put(q->lva, lva, s));
+    DNS_TRY(put(q->scale, sc, s));
+    DNS_TRY(put(q->c0, cc, s));
+    DNS_TRY(q->log.ensure(nrows, G, nQ, s));
+    DNS_TRY(q->bc.set(moving, live, ndbc, nrows, dbc_table, s));
     for (int m = 0; m < dns::kQdMaxMats; ++m) q->need[m] = 0;
     for (int k = 0; k < dns::kQdMaxForms; ++k) {
         q->mat[k] = k < nQ ? mat[k] : 0;
@@ -1471,8 +1372,6 @@ static int set_quadratics(dns_imex *st, int32_t nM, const dns_csr *mats,
     }
     q->nM = nM;
     q->nQ = nQ;
-    q->G = G;
-    q->rows = nrows;
     q->dt = dt;
     st->qd = std::move(q);
     return st->rewind_tables();
@@ -1514,35 +1413,19 @@ int dns_imex_get_quadratics(dns_imex *st, int32_t first, int32_t count,
                             double *out) try {
     DNS_TRY(need(st, st && st->qd, "quadratics are",
                  "dns_imex_set_quadratics"));
-    const dns_imex::Quadratics &q = *st->qd;
-    if (!out) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
-    const size_t per = (size_t)q.G * q.nQ;
-    std::vector<double> part((size_t)std::min(std::max(count, 0), q.rows) * per);
-    DNS_TRY(download_log_rows(st, part.data(), q.log.p, first, count, per,
-                              q.rows, "quadratic rows", "log"));
-    // the workgroups' shares, in index order
-    for (int r = 0; r < count; ++r)
-        for (int k = 0; k < q.nQ; ++k) {
-            double y = 0.0;
-            for (int g = 0; g < q.G; ++g)
-                y += part[(size_t)r * per + (size_t)g * q.nQ + k];
-            out[(size_t)r * q.nQ + k] = y;
-        }
-    return DNS_OK;
+    return st->qd->log.download_sums(st, first, count, out, "quadratic rows");
 } DNS_CAPI_CATCH
 
 int dns_imex_quadratics_grid(dns_imex *st, int32_t *grid) try {
     DNS_TRY(need(st, st && st->qd, "quadratics are",
                  "dns_imex_set_quadratics"));
     if (!grid) return dns::fail(DNS_ERR_BAD_ARGUMENT, "null argument");
-    *grid = st->qd->G;
+    *grid = st->qd->log.G;
     return DNS_OK;
 } DNS_CAPI_CATCH
 
 int dns_imex_clear_quadratics(dns_imex *st) try {
-    DNS_TRY(quiesce(st));
-    st->qd.reset();
-    return DNS_OK;
+    return take_off(st, &dns_imex::qd);
 } DNS_CAPI_CATCH
 
 // ---- snapshot ensemble (ensemble.hpp) --------------------------------------
@@ -1555,9 +1438,8 @@ int dns_imex_set_ensemble(dns_imex *st, int32_t nrows, const int32_t *slot,
     DNS_TRY(dns::check_slot_table(nrows, slot, nslots));
     const size_t ldv = dns::ens_ldv(h->nv);
     DNS_TRY(dns::check_ensemble_shape(nslots, h->nv, ldv));
-    DNS_HIP(hipSetDevice(h->device));
+    DNS_TRY(quiesce(st));                       // replays may still write it
     hipStream_t s = h->stream;
-    DNS_HIP(hipStreamSynchronize(s));           // replays may still write it
     // Built aside where it is not kept: a refusal (a failed allocation) leaves
     // the ensemble that was there.
     dns_imex::Ensemble none;
@@ -1665,9 +1547,7 @@ int dns_imex_ensemble_combine(dns_imex *st, int32_t m, int32_t r,
 } DNS_CAPI_CATCH
 
 int dns_imex_clear_ensemble(dns_imex *st) try {
-    DNS_TRY(quiesce(st));
-    st->ens.reset();
-    return DNS_OK;
+    return take_off(st, &dns_imex::ens);
 } DNS_CAPI_CATCH
 
 // Slots [first, first + count) of the ensemble become the base trajectory of

@@ -1387,7 +1387,7 @@ int dns_imex_front_probe(dns_imex *st, const dns_imex_coeffs *cf,
     if (!st || !cf || !out || cycle_len < 0 || out->parts_cap < 0)
         return dns::fail(DNS_ERR_BAD_ARGUMENT, "bad argument");
     dns_saddle *h = st->sys;
-    if (st->fb || st->rec || st->fn || st->stat || st->qd || st->ens)
+    if (st->attachments().n > 0)
         return dns::fail(DNS_ERR_BAD_ARGUMENT,
                          "the front probe takes a stepper without attachments "
                          "(feedback, recorder, functionals, statistics, "

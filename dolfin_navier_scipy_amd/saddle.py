@@ -738,6 +738,54 @@ class ImexStepper(object):
             C.dptr(p.reshape(-1))))
         return v, p
 
+    # ---- what functionals and quadratics share ------------------------------
+    @staticmethod
+    def _dbc_source(dbc_table, nrows, ndbc=None):
+        """`(live, table)` of a `dbc_table` argument: None (constant values),
+        `'operator'` (live: the convection operator's table) or the rows,
+        `nrows + 1` of them (`ndbc` wide where it is given)"""
+        if dbc_table is None:
+            return False, None
+        if isinstance(dbc_table, str):
+            if dbc_table != 'operator':
+                raise ValueError('`dbc_table`: a table or the string '
+                                 '\'operator\', not {0!r}'.format(dbc_table))
+            return True, None
+        tab = np.ascontiguousarray(dbc_table, dtype=np.float64)
+        if ndbc is None and (tab.ndim != 2 or tab.shape[0] != nrows + 1):
+            raise ValueError('`dbc_table` must have nrows + 1 = {0} rows, '
+                             'it is {1}'.format(nrows + 1, tab.shape))
+        if ndbc is not None and tab.shape != (nrows + 1, ndbc):
+            raise ValueError(
+                '`dbc_table` must be (nrows + 1) x ndbc = {0} x {1}, it '
+                'is {2}'.format(nrows + 1, ndbc, tab.shape))
+        return False, tab
+
+    def _set_log(self, setter, head, live, tab, ndbc):
+        """the export `setter` for constant values, or its `_bc` / `_live`
+        form (`_dbc_source`), on the arguments `head` all three share"""
+        if live:
+            C.check(getattr(self.lib, setter + '_live')(*head, ndbc))
+        elif tab is not None:
+            C.check(getattr(self.lib, setter + '_bc')(
+                *head, ndbc, C.dptr(tab.reshape(-1))))
+        else:
+            C.check(getattr(self.lib, setter)(*head))
+
+    def _log_rows(self, shape_attr, unset, getter, first, count):
+        """rows `first .. first + count` of a log `(nrows, n)` through the
+        export `getter` (default: of all steps taken since it was set)"""
+        shape = getattr(self, shape_attr, None)
+        if shape is None:
+            raise ValueError(unset)
+        if count is None:
+            count = self.table_position()[0] - first
+        out = np.empty((int(count), shape[1]))
+        C.check(getattr(self.lib, getter)(
+            self._h, int(first), int(count),
+            C.dptr(out.reshape(-1) if out.size else np.zeros(1))))
+        return out
+
     # ---- force functionals (`dns_imex_set_functionals`) ---------------------
     def set_functionals(self, fn, nrows, dt, dbc_table=None):
         """the next `nrows` steps (`step` and `run` alike) evaluate the
@@ -770,23 +818,13 @@ class ImexStepper(object):
         nrows = int(nrows)
         if nrows < 1:
             raise ValueError('`nrows` must be positive')
-        live = isinstance(dbc_table, str)
-        if live and dbc_table != 'operator':
-            raise ValueError('`dbc_table`: a table or the string '
-                             '\'operator\', not {0!r}'.format(dbc_table))
         moving = dbc_table is not None
+        live, tab = self._dbc_source(dbc_table, nrows)
         args = fn.device_args(moving=True) if moving else fn.device_args()
         nF = int(args['scale'].size)
         terms = [('ca', self.sys.NV), ('cm', self.sys.NV), ('cp', self.sys.NP)]
-        if live:
-            ndbc = int(args['cab'].shape[1])
-            terms += [('cab', ndbc), ('cmb', ndbc)]
-        elif moving:
-            tab = np.ascontiguousarray(dbc_table, dtype=np.float64)
-            if tab.ndim != 2 or tab.shape[0] != nrows + 1:
-                raise ValueError('`dbc_table` must have nrows + 1 = {0} rows, '
-                                 'it is {1}'.format(nrows + 1, tab.shape))
-            ndbc = int(tab.shape[1])
+        if moving:
+            ndbc = int(args['cab'].shape[1] if live else tab.shape[1])
             terms += [('cab', ndbc), ('cmb', ndbc)]
         views = []
         for name, ncol in terms:
@@ -807,15 +845,8 @@ class ImexStepper(object):
         refs = [None if v is None else v.byref() for v in views]
         tail = (C.dptr(c0), C.dptr(scale), cptr.ctypes.data_as(C.c_int32_p),
                 cidx.ctypes.data_as(C.c_int32_p), C.dptr(cw), float(dt), nrows)
-        if live:
-            C.check(self.lib.dns_imex_set_functionals_live(
-                self._h, nF, *refs, *tail, ndbc))
-        elif moving:
-            C.check(self.lib.dns_imex_set_functionals_bc(
-                self._h, nF, *refs, *tail, ndbc, C.dptr(tab.reshape(-1))))
-        else:
-            C.check(self.lib.dns_imex_set_functionals(self._h, nF, *refs,
-                                                      *tail))
+        self._set_log('dns_imex_set_functionals', (self._h, nF, *refs, *tail),
+                      live, tab, ndbc if moving else 0)
         self._fn_shape = (nrows, nF)
 
     def clear_functionals(self):
@@ -825,16 +856,9 @@ class ImexStepper(object):
     def get_functionals(self, first=0, count=None):
         """rows `first .. first + count` of the functionals' log (default: of
         all steps taken since `set_functionals`), `(count, nF)`"""
-        shape = getattr(self, '_fn_shape', None)
-        if shape is None:
-            raise ValueError('no functionals are set (`set_functionals`)')
-        if count is None:
-            count = self.table_position()[0] - first
-        out = np.empty((int(count), shape[1]))
-        C.check(self.lib.dns_imex_get_functionals(
-            self._h, int(first), int(count),
-            C.dptr(out.reshape(-1) if out.size else np.zeros(1))))
-        return out
+        return self._log_rows('_fn_shape', 'no functionals are set '
+                              '(`set_functionals`)',
+                              'dns_imex_get_functionals', first, count)
 
     # ---- flow statistics (`dns_imex_set_stats`) ------------------------------
     def set_statistics(self, bins, nbins=None, pairs=None, reset=False):
@@ -937,10 +961,6 @@ class ImexStepper(object):
         nrows = int(nrows)
         if nrows < 1:
             raise ValueError('`nrows` must be positive')
-        live = isinstance(dbc_table, str)
-        if live and dbc_table != 'operator':
-            raise ValueError('`dbc_table`: a table or the string '
-                             '\'operator\', not {0!r}'.format(dbc_table))
         args = qf.device_args()
         ndbc = int(args.get('ndbc', 0))
         if ndbc > 0 and dbc_table is None:
@@ -951,12 +971,7 @@ class ImexStepper(object):
             raise ValueError(
                 '`dbc_table` with quadratics that carry constant Dirichlet '
                 'values (ndbc = 0): build them with `moving=True`')
-        if ndbc > 0 and not live:
-            tab = np.ascontiguousarray(dbc_table, dtype=np.float64)
-            if tab.ndim != 2 or tab.shape != (nrows + 1, ndbc):
-                raise ValueError(
-                    '`dbc_table` must be (nrows + 1) x ndbc = {0} x {1}, it '
-                    'is {2}'.format(nrows + 1, ndbc, tab.shape))
+        live, tab = self._dbc_source(dbc_table, nrows, ndbc)
         NV = self.sys.NV + ndbc
         nQ = int(args['scale'].size)
         mats = args['mats']
@@ -984,13 +999,7 @@ class ImexStepper(object):
                 *[None if v is None else v.byref() for v in lin],
                 C.dptr(c0), C.dptr(scale), float(dt), nrows,
                 0 if max_grid is None else int(max_grid))
-        if live:
-            C.check(self.lib.dns_imex_set_quadratics_live(*head, ndbc))
-        elif ndbc > 0:
-            C.check(self.lib.dns_imex_set_quadratics_bc(
-                *head, ndbc, C.dptr(tab.reshape(-1))))
-        else:
-            C.check(self.lib.dns_imex_set_quadratics(*head))
+        self._set_log('dns_imex_set_quadratics', head, live, tab, ndbc)
         self._qd_shape = (nrows, nQ)
 
     def clear_quadratics(self):
@@ -1007,16 +1016,9 @@ class ImexStepper(object):
     def get_quadratics(self, first=0, count=None):
         """rows `first .. first + count` of the quadratics' log (default: of
         all steps taken since `set_quadratics`), `(count, nQ)`"""
-        shape = getattr(self, '_qd_shape', None)
-        if shape is None:
-            raise ValueError('no quadratics are set (`set_quadratics`)')
-        if count is None:
-            count = self.table_position()[0] - first
-        out = np.empty((int(count), shape[1]))
-        C.check(self.lib.dns_imex_get_quadratics(
-            self._h, int(first), int(count),
-            C.dptr(out.reshape(-1) if out.size else np.zeros(1))))
-        return out
+        return self._log_rows('_qd_shape', 'no quadratics are set '
+                              '(`set_quadratics`)',
+                              'dns_imex_get_quadratics', first, count)
 
     # ---- snapshot ensemble (`dns_imex_set_ensemble`) -------------------------
     def set_ensemble(self, slots, nslots=None, reset=False):

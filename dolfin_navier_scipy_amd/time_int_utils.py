@@ -589,17 +589,67 @@ class _DeviceRecord(object):
         return dict(record='device', record_y=rec_y, record_t=rec_t)
 
 
-class _FunctionalLog(_Attachment):
+class _RowLog(_Attachment):
+    """What `_FunctionalLog` and `_QuadraticLog` share: one row per step, from
+    the device's log per slice (or chunk) or, where the loop takes one step
+    at a time, from the host.  With controlled (moving) Dirichlet values `arm`
+    takes their rows from `tables` -- one more than steps -- or, `live`
+    (beside a resident `BoundaryFeedback`, which makes them on the device),
+    points at the operator's table; `host_row` gets those of the two states.
+    A subclass has `_set(nrows, dbc_table)`, `_get(count)`, `_evaluate(step)`,
+    `key` (the prefix of its `LAST_RUN` keys), `width` (entries of a row),
+    `moving` (False: constant values, no rows are handed on) and `need_rows`
+    (moving values cannot do without them)."""
+    key, width, moving, need_rows = None, 0, True, False
+
+    def __init__(self, stepper, dt, live, names):
+        self.stepper, self.dt, self.live = stepper, dt, live
+        self.ys, self.ts = [], []
+        self.where = None
+        self.names = names
+
+    def arm(self, times, tables):
+        if not self.moving:
+            return self._set(len(times), None)
+        dbc_rows = 'operator' if self.live else tables.dbc
+        short = self.need_rows if dbc_rows is None else \
+            (not self.live and len(dbc_rows) != len(times) + 1)
+        if short:
+            raise ValueError('{0} steps need {1} rows of Dirichlet values, '
+                             'got {2}'.format(
+                                 len(times), len(times) + 1,
+                                 None if dbc_rows is None else len(dbc_rows)))
+        self._set(len(times), dbc_rows)
+
+    def collect(self, times):
+        self.add(self._get(len(times)), times)
+        self.where = 'device'
+
+    def add(self, rows, times):
+        self.ys.append(np.asarray(rows, dtype=np.float64))
+        self.ts.extend(times)
+
+    def host_row(self, step):
+        self.add(self._evaluate(step).reshape((1, -1)), [step.time])
+        self.where = 'host'
+
+    def result(self):
+        y = np.vstack(self.ys) if self.ys else np.zeros((0, self.width))
+        return y, np.array(self.ts, dtype=np.float64)
+
+    def report(self):
+        y, t = self.result()
+        return {self.key: y, self.key + '_t': t, self.key + '_on': self.where,
+                self.key + '_names': self.names}
+
+
+class _FunctionalLog(_RowLog):
     """`resident=dict(functionals=fn)` of `cnab` / `sbdftwo`: arms the
-    stepper's functionals per slice (or chunk) next to the tables, collects
-    the rows of the device's log and their times; where the loop takes one
-    step at a time the same rows come from `fn.evaluate` on the host.  With
-    controlled (moving) Dirichlet values `arm` takes their rows from `tables`
-    -- one more than steps --, `host_row` the values of the two states; the
-    loop has `ndbc` of them, static ones included, and the functionals'
-    boundary rows `cab`, `cmb` must be as wide, in that order.  `live`
-    (beside a resident `BoundaryFeedback`): the device makes the values, so
-    `arm` points the functionals at the operator's table instead"""
+    stepper's functionals next to the tables and collects their rows
+    (`_RowLog`).  With controlled (moving) Dirichlet values the loop has
+    `ndbc` of them, static ones included, and the functionals' boundary rows
+    `cab`, `cmb` must be as wide, in that order"""
+    key = 'functionals'
 
     def __init__(self, stepper, fn, dt, ndbc=None, live=False):
         if ndbc is not None and fn.inv is not None and fn.cab.shape[1] != ndbc:
@@ -608,64 +658,33 @@ class _FunctionalLog(_Attachment):
                 'they were built for {0} Dirichlet dofs, the loop has {1} '
                 '(`static_dbcvals` then the controlled ones: build them with '
                 '`dbcinds` in that order)'.format(fn.cab.shape[1], ndbc))
-        self.stepper, self.fn, self.dt = stepper, fn, dt
-        self.live = live
-        self.ys, self.ts = [], []
-        self.where = None
-        self.names = None if fn is None else list(fn.names)
+        _RowLog.__init__(self, stepper, dt, live,
+                         None if fn is None else list(fn.names))
+        self.fn = fn
+        self.width = 0 if fn is None else fn.nF
 
-    def arm(self, times, tables):
-        if self.live:
-            self.stepper.set_functionals(self.fn, len(times), self.dt,
-                                         dbc_table='operator')
-            return
-        dbc_rows = tables.dbc
-        if dbc_rows is not None and len(dbc_rows) != len(times) + 1:
-            raise ValueError('{0} steps need {1} rows of Dirichlet values, '
-                             'got {2}'.format(len(times), len(times) + 1,
-                                              len(dbc_rows)))
-        self.stepper.set_functionals(self.fn, len(times), self.dt,
-                                     dbc_table=dbc_rows)
+    def _set(self, nrows, dbc_table):
+        self.stepper.set_functionals(self.fn, nrows, self.dt,
+                                     dbc_table=dbc_table)
 
-    def collect(self, times):
-        self.add(self.stepper.get_functionals(0, len(times)), times)
-        self.where = 'device'
+    def _get(self, count):
+        return self.stepper.get_functionals(0, count)
 
-    def add(self, rows, times):
-        self.ys.append(np.asarray(rows, dtype=np.float64))
-        self.ts.extend(times)
-
-    def host_row(self, step):
-        self.add(self.fn.evaluate(step.v, step.v_prev, step.p, self.dt,
-                                  dbc=step.dbc, dbc_prev=step.dbc_prev
-                                  ).reshape((1, -1)), [step.time])
-        self.where = 'host'
-
-    def result(self):
-        nf = 0 if self.fn is None else self.fn.nF
-        y = np.vstack(self.ys) if self.ys else np.zeros((0, nf))
-        return y, np.array(self.ts, dtype=np.float64)
-
-    def report(self):
-        fy, ft = self.result()
-        return dict(functionals=fy, functionals_t=ft,
-                    functionals_on=self.where, functionals_names=self.names)
+    def _evaluate(self, step):
+        return self.fn.evaluate(step.v, step.v_prev, step.p, self.dt,
+                                dbc=step.dbc, dbc_prev=step.dbc_prev)
 
 
-class _QuadraticLog(_Attachment):
+class _QuadraticLog(_RowLog):
     """`resident=dict(quadratics=qf)` of `cnab` / `sbdftwo`, `qf` a
     `fem.QuadraticFunctionals` (the energy budget): arms the stepper's
-    quadratics per slice (or chunk) next to the tables -- the matrices stay on
-    the device from slice to slice --, collects the rows of the device's log
-    and their times; where the loop takes one step at a time the same rows
-    come from `qf.evaluate` on the host.  Forms that carry CONSTANT Dirichlet
-    values (`qf.ndbc == 0`) are for loops without moving ones (`ndbc` None).
-    With controlled (moving) Dirichlet values `arm` takes their rows from
-    `tables` -- one more than steps --, `host_row` the values of the two
-    states; the loop has `ndbc` of them, static ones included, and the forms
-    must stand on `NV + ndbc` dofs, the Dirichlet dofs in that order.  `live`
-    (beside a resident `BoundaryFeedback`): `arm` points the forms at the
-    operator's table, which the device writes"""
+    quadratics next to the tables -- the matrices stay on the device from
+    slice to slice -- and collects their rows (`_RowLog`).  Forms that carry
+    CONSTANT Dirichlet values (`qf.ndbc == 0`) are for loops without moving
+    ones (`ndbc` None).  With controlled (moving) Dirichlet values the loop
+    has `ndbc` of them, static ones included, and the forms must stand on
+    `NV + ndbc` dofs, the Dirichlet dofs in that order"""
+    key, need_rows = 'quadratics', True
 
     def __init__(self, stepper, qf, dt, max_grid=None, ndbc=None,
                  live=False):
@@ -680,51 +699,21 @@ class _QuadraticLog(_Attachment):
                 'they were built for {0} Dirichlet dofs, the loop has {1} '
                 '(`static_dbcvals` then the controlled ones: build them with '
                 '`dbcinds` in that order)'.format(qf.ndbc, ndbc or 0))
-        self.stepper, self.qf, self.dt = stepper, qf, dt
-        self.live = live
-        self.max_grid = max_grid
-        self.ys, self.ts = [], []
-        self.where = None
-        self.names = list(qf.names)
+        _RowLog.__init__(self, stepper, dt, live, list(qf.names))
+        self.qf, self.max_grid = qf, max_grid
+        self.width, self.moving = qf.nQ, qf.ndbc > 0
 
-    def arm(self, times, tables):
-        if self.qf.ndbc == 0:
-            self.stepper.set_quadratics(self.qf, len(times), self.dt,
-                                        max_grid=self.max_grid)
-            return
-        dbc_rows = 'operator' if self.live else tables.dbc
-        if not self.live and (dbc_rows is None
-                              or len(dbc_rows) != len(times) + 1):
-            raise ValueError('{0} steps need {1} rows of Dirichlet values, '
-                             'got {2}'.format(
-                                 len(times), len(times) + 1,
-                                 None if dbc_rows is None else len(dbc_rows)))
-        self.stepper.set_quadratics(self.qf, len(times), self.dt,
-                                    max_grid=self.max_grid,
-                                    dbc_table=dbc_rows)
+    def _set(self, nrows, dbc_table):
+        kw = {} if dbc_table is None else dict(dbc_table=dbc_table)
+        self.stepper.set_quadratics(self.qf, nrows, self.dt,
+                                    max_grid=self.max_grid, **kw)
 
-    def collect(self, times):
-        self.add(self.stepper.get_quadratics(0, len(times)), times)
-        self.where = 'device'
+    def _get(self, count):
+        return self.stepper.get_quadratics(0, count)
 
-    def add(self, rows, times):
-        self.ys.append(np.asarray(rows, dtype=np.float64))
-        self.ts.extend(times)
-
-    def host_row(self, step):
-        self.add(self.qf.evaluate(step.v, step.v_prev, self.dt,
-                                  dbc=step.dbc, dbc_prev=step.dbc_prev
-                                  ).reshape((1, -1)), [step.time])
-        self.where = 'host'
-
-    def result(self):
-        y = np.vstack(self.ys) if self.ys else np.zeros((0, self.qf.nQ))
-        return y, np.array(self.ts, dtype=np.float64)
-
-    def report(self):
-        qy, qt = self.result()
-        return dict(quadratics=qy, quadratics_t=qt,
-                    quadratics_on=self.where, quadratics_names=self.names)
+    def _evaluate(self, step):
+        return self.qf.evaluate(step.v, step.v_prev, self.dt, dbc=step.dbc,
+                                dbc_prev=step.dbc_prev)
 
 
 class _PodEnsemble(_Attachment):
